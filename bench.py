@@ -8,6 +8,12 @@ One process per GPU, one independent 640x480 camera stream per GPU (the path sha
 collective, "weak" scaling). A step = one frame pushed through the pipeline: EdgeDetector::detect of frame k on the
 detect stream overlapped with the full tracking step of pair (k-2, k-1) on the track stream, u8 frames resident
 in HBM. Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the window's frame times).
+Everything else it can measure - the all-kernel event pass (stage / per-kernel times, roofline of the dominant kernel), the
+launch-time sample of the dominant kernel, the long window behind a short one, the PCIe-inclusive window, the 4- / 8-lane
+batches, the rebvio::Rebvio host class rate and the CPU baseline - runs only with --full.
+--dump-outputs DIR writes what the timed path handed back for its last step as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -163,13 +169,13 @@ def percentiles_ms(stamps_s) -> dict:
     return {"p50": float(np.percentile(d, 50)), "p99": float(np.percentile(d, 99)), "mean": float(d.mean())}
 
 
-def self_launch(n: int, argv) -> int:
+def self_launch(n: int, argv, cpu_baseline_leg: bool) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (rank r -> GPU r) BEFORE this process
     makes any GPU call, pass rank 0's JSON line through, fail if any rank fails. (The driver's
     `python -m torch.distributed.run ... bench.py --gpus N` sets WORLD_SIZE itself and never comes here.)"""
     import socket
     import subprocess
-    if "--no-cpu-baseline" not in argv:
+    if cpu_baseline_leg:
         build_cpu_oracle()  # once, before the ranks exist: they find it up to date (and would serialise on its lock otherwise)
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -222,6 +228,12 @@ def main():
                          "always measures the sustained rate, never the faster first frames of a stream")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--base-frames", type=int, default=24, help="distinct rendered frames (ping-pong replay)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure as well: all-kernel event pass (stage_us, kernel_us_per_frame, "
+                         "roofline), long and PCIe-inclusive windows, batched lanes, host class rate, CPU baseline. The --no-* / "
+                         "--lanes / --cpu-seconds options below apply to this mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the pair record and keyline count the last timed step produced as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--lanes", default="4,8",
@@ -236,7 +248,7 @@ def main():
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
+        raise SystemExit(self_launch(args.gpus, sys.argv[1:], args.full and not args.no_cpu_baseline))
     if args.batched_child:
         import torch  # noqa: F401  (same load order as the parent)
         from rebvio_amd import synth
@@ -268,7 +280,7 @@ def main():
         tmax = shard.max_over_ranks(float(rank + 1), world, "cpu")
         # the CPU-baseline leg's build + load path, as every rank of a real run takes it (no GPU needed)
         oracle_ok = 0.0
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from oracle import oracle_py as O
             path = build_cpu_oracle_ranked(rank, world, dist.barrier)
             try:
@@ -338,8 +350,8 @@ def main():
     settle = max(0, 1000 - warmup)
     # A window of few frames also carries the pipeline's fill and drain (GPU idle at both brackets, ~130 us = 1.6 frames,
     # 8 % of a 20-frame window): runs shorter than 1000 steps are followed by an extra, separately bracketed window of 2000
-    # frames whose rate is reported next to the contract's figure (config.long_window), never instead of it.
-    long_steps = 2000 if steps < 1000 else 0
+    # frames whose rate is reported next to the contract's figure (config.long_window, --full), never instead of it.
+    long_steps = 2000 if steps < 1000 and args.full else 0
     order = synth.pingpong_indices(args.base_frames, settle + warmup + steps + long_steps + 800 + 96)  # GPU leg only; the CPU leg builds its own list
 
     def push(i):
@@ -350,40 +362,46 @@ def main():
         if world > 1:
             dist.barrier()
 
+    tap = RecordTap()
+
     # ---- warm-up (threshold servo settles at keylines_ref; pools, streams, code objects warm) --------------
     k = 0
     last_warm = min(warmup, 32)  # the warm-up frames that run directly in front of the timed region (below)
     for _ in range(settle + warmup - last_warm):
-        push(k)
+        tap(push(k))
         k += 1
     torch.cuda.synchronize()
 
-    # ---- find the dominant kernel (all-kernel event pass, untimed; BEFORE the warm-up so that the W warm-up frames run
-    # right in front of the timed region - reading ~300 event pairs back keeps the host busy and the GPU idle for
-    # milliseconds, after which the first frames run a few per cent slower) ------------------------------------
-    ctx.profile_reset()
-    ctx.profile(True)
+    # ---- find the dominant kernel (--full: all-kernel event pass, untimed; BEFORE the warm-up so that the W warm-up frames
+    # run right in front of the timed region - reading ~300 event pairs back keeps the host busy and the GPU idle for
+    # milliseconds, after which the first frames run a few per cent slower). A plain run pushes the same frames without the
+    # events: its timed window sees the same frames and the same stream state ---------------------------------------
+    if args.full:
+        ctx.profile_reset()
+        ctx.profile(True)
     nprof = 24
     kl_counts = []
     for _ in range(nprof):
-        out, n = push(k)
+        out, n = tap(push(k))
         kl_counts.append(n)
         k += 1
     torch.cuda.synchronize()
-    prof = ctx.profile_read()
-    ctx.profile(False)
-    per_frame = {name: avg * calls / nprof for name, (avg, calls) in prof.items()}
-    # The event pair around a launch adds its own few microseconds to every sample, which favours kernels launched several
-    # times per frame when two candidates are close (k_colscan x 3 against the LM kernel x 1). The choice is made on the
-    # per-frame sums with an empty event pair's time taken off every launch; the reported figures stay as measured.
-    ev_over = event_pair_overhead_us()
-    debiased = {kname: max(0.0, us - ev_over) * cnt / nprof for kname, (us, cnt) in prof.items() if cnt > 0}
-    dominant = max(debiased, key=debiased.get)
     n_keylines = int(np.median([c for c in kl_counts if c >= 0])) if kl_counts else 0
+    prof, per_frame, dominant = {}, {}, None
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile(False)
+        per_frame = {name: avg * calls / nprof for name, (avg, calls) in prof.items()}
+        # The event pair around a launch adds its own few microseconds to every sample, which favours kernels launched several
+        # times per frame when two candidates are close (k_colscan x 3 against the LM kernel x 1). The choice is made on the
+        # per-frame sums with an empty event pair's time taken off every launch; the reported figures stay as measured.
+        ev_over = event_pair_overhead_us()
+        debiased = {kname: max(0.0, us - ev_over) * cnt / nprof for kname, (us, cnt) in prof.items() if cnt > 0}
+        dominant = max(debiased, key=debiased.get)
 
     # ---- the last warm-up frames, directly in front of the timed region --------------------------------------------
     for _ in range(last_warm):
-        push(k)
+        tap(push(k))
         k += 1
     torch.cuda.synchronize()
 
@@ -410,46 +428,60 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = t1 - t0
+    # the timed pushes' records, counted after the fact; the record of the last timed frame's pair (frames k-2, k-1) comes back
+    # with a later push or from the flush (the detect stage leads the tracker by at least 3 frames)
+    tap.n += sum(1 for s in statuses if s != -1)
+    tap.want = k - 2 if args.dump_outputs else None
+    tapping = tap.want is not None
     long_elapsed = 0.0
     if long_steps:
         barrier()
         tl0 = time.perf_counter()
         for _ in range(long_steps):
-            push(k)
+            r = push(k)
+            if tapping:
+                tap(r)
             k += 1
         torch.cuda.synchronize()
         long_elapsed = time.perf_counter() - tl0
         if world > 1:
             dist.barrier()
-    # ---- launch time of the dominant kernel: HIP events around every 8th launch (on the stream it runs on) over 800 further
-    # frames of the same stream, ~100 samples whatever --steps is; never inside a timed window
-    sample_steps = 800
-    ctx.profile_reset()
-    ctx.profile(True, only=dominant, stride=int(os.environ.get("REBVIO_BENCH_STRIDE", 8)))
-    for _ in range(sample_steps):
-        push(k)
-        k += 1
-    torch.cuda.synchronize()
-    dom = ctx.profile_read().get(dominant, (0.0, 0))
-    ctx.profile(False)
-    if world > 1:
-        dist.barrier()
+    # ---- launch time of the dominant kernel (--full): HIP events around every 8th launch (on the stream it runs on) over 800
+    # further frames of the same stream, ~100 samples whatever --steps is; never inside a timed window
+    dom = (0.0, 0)
+    if args.full:
+        sample_steps = 800
+        ctx.profile_reset()
+        ctx.profile(True, only=dominant, stride=int(os.environ.get("REBVIO_BENCH_STRIDE", 8)))
+        for _ in range(sample_steps):
+            r = push(k)
+            if tapping:
+                tap(r)
+            k += 1
+        torch.cuda.synchronize()
+        dom = ctx.profile_read().get(dominant, (0.0, 0))
+        ctx.profile(False)
+        if world > 1:
+            dist.barrier()
     # ---- the same loop with every frame handed over from HOST memory (the reference's contract starts at a host image,
-    # rebvio.cpp:38-48): pinned ring + asynchronous copy ahead of the frame's scans. Reported as config.pcie_inclusive_fps,
-    # never as `value`.
-    pcie_steps = 0 if args.no_pcie else 1500
+    # rebvio.cpp:38-48): pinned ring + asynchronous copy ahead of the frame's scans. Reported as config.pcie_inclusive_fps
+    # (--full), never as `value`.
+    pcie_steps = 1500 if args.full and not args.no_pcie else 0
     pcie_elapsed = 0.0
     if pcie_steps:
         barrier()
         tp0 = time.perf_counter()
         for _ in range(pcie_steps):
-            ctx.push_frame_u8(frames[int(order[k % len(order)])], k * 50000)
+            r = ctx.push_frame_u8(frames[int(order[k % len(order)])], k * 50000)
+            if tapping:
+                tap(r)
             k += 1
         torch.cuda.synchronize()
         pcie_elapsed = time.perf_counter() - tp0
         if world > 1:
             dist.barrier()
-    ctx.flush()
+    for r in ctx.flush():
+        tap(r)
 
     tmax = shard.max_over_ranks(elapsed, world, "cuda" if backend_name == "nccl" else "cpu")
     long_tmax = shard.max_over_ranks(long_elapsed, world, "cuda" if backend_name == "nccl" else "cpu") if long_steps else 0.0
@@ -457,7 +489,7 @@ def main():
     # CPU baseline of an N-stream run: N instances of the restatement x 2 threads, one per rank, at the same
     # time; rank 0 reports the sum. (N = 1: rank 0's own leg below, with the serial figure and the stage split.)
     cpu_multi = None
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and args.full and not args.no_cpu_baseline:
         build_cpu_oracle_ranked(rank, world, dist.barrier)  # rank 0 builds, the others find it up to date
         mine = cpu_baseline(frames, cam, cfg, args.base_frames, min(args.cpu_seconds, 10.0), serial_leg=False)
         tot = shard.sum_over_ranks(mine["value"], world, "cuda" if backend_name == "nccl" else "cpu")
@@ -470,13 +502,11 @@ def main():
         print(f"[rank {rank}] WARNING: {bad} of {steps} frame pairs ended with a non-zero tracking status", file=sys.stderr)
 
     if rank == 0:
+        if args.dump_outputs:
+            if tap.got is None:
+                raise SystemExit(f"--dump-outputs: the record of pair {tap.want} never came back ({tap.n} records)")
+            dump_outputs(args.dump_outputs, *tap.got)
         fps = shard.whole_job_fps(world, steps, tmax)
-        dom_us = dom[0]
-        ab = algorithmic_bytes(dominant, npx, n_keylines)
-        if dominant in ("k_colscan", "k_colscan4"):
-            ab = (8 * npx + 16 * npx + 16 * npx) / 3.0  # mean over its three launches per frame (1, 2, 2 filters)
-        achieved = ab / (dom_us * 1e-6) / 1e9 if dom_us > 0 else 0.0
-        rp = rocprof_avg_us(dominant)
         result = {
             "metric": "frames/sec at 640x480 (~15k keylines); 1-GPU and 8-stream/8-GPU batch",
             "value": fps,
@@ -512,30 +542,39 @@ def main():
                                          "agree - the sequential-fp32 restatement itself is 0.25-4.8 % from that "
                                          "(tests/test_parity_gpu.py::test_stream_divergence_report)"},
             "frame_ms": percentiles_ms(push_done),
-            "stage_us": stage_us(per_frame),
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic_bytes(dominant),
-                         "traffic_source": (f"{os.path.relpath(pmc_profile_path(), ROOT)}: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of "
-                                            "this command (separate runs, committed), 2 x FETCH_SIZE + WRITE_SIZE per launch - NOT measured in "
-                                            "this run" if pmc_profile_path() else None),
-                         "avg_launch_us": dom_us, "launches": dom[1], "algorithmic_bytes_per_launch": ab,
-                         "avg_launch_us_basis": "HIP events around every 8th launch on the kernel's stream, in a window of 800 frames behind "
-                                                "the timed region (an event pair brackets the dispatch as well: a few us above rocprofv3's figure)",
-                         "rocprof_avg_launch_us": (rp[0] if rp else None), "rocprof_launches": (rp[1] if rp else None),
-                         "frac_rocprof": ((ab / (rp[0] * 1e-6) / 1e9 / HBM_PEAK_GBS) if rp else None),
-                         "rocprof_source": (f"{os.path.relpath(rocprof_stats_path(), ROOT)}: rocprofv3 --kernel-trace --stats of this command, "
-                                            "committed - NOT measured in this run" if rocprof_stats_path() else None),
-                         "frame_algorithmic_bytes": 112 * npx + 1740 * n_keylines,
-                         "frame_achieved_GBs": (112 * npx + 1740 * n_keylines) * (fps / world) / 1e9},
-            "kernel_us_per_frame": {kname: round(v, 3) for kname, v in sorted(per_frame.items(), key=lambda kv: -kv[1])},
-            # per kernel: algorithmic bytes of one launch; its mean duration in the all-kernel event pass ("hip_event_us": 24 frames,
-            # every launch bracketed by a HIP event pair on its stream, ~2-4 us above rocprofv3's figure for the short kernels) and in
-            # the committed rocprofv3 summary of this command ("rocprof_us"); fraction of the HBM peak on either basis
-            "kernel_roofline": kernel_roofline_table(prof, npx, n_keylines),
         }
+        if args.full:
+            dom_us = dom[0]
+            ab = algorithmic_bytes(dominant, npx, n_keylines)
+            if dominant in ("k_colscan", "k_colscan4"):
+                ab = (8 * npx + 16 * npx + 16 * npx) / 3.0  # mean over its three launches per frame (1, 2, 2 filters)
+            achieved = ab / (dom_us * 1e-6) / 1e9 if dom_us > 0 else 0.0
+            rp = rocprof_avg_us(dominant)
+            result.update({
+                "stage_us": stage_us(per_frame),
+                "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic_bytes(dominant),
+                             "traffic_source": (f"{os.path.relpath(pmc_profile_path(), ROOT)}: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of "
+                                                "this command (separate runs, committed), 2 x FETCH_SIZE + WRITE_SIZE per launch - NOT measured in "
+                                                "this run" if pmc_profile_path() else None),
+                             "avg_launch_us": dom_us, "launches": dom[1], "algorithmic_bytes_per_launch": ab,
+                             "avg_launch_us_basis": "HIP events around every 8th launch on the kernel's stream, in a window of 800 frames behind "
+                                                    "the timed region (an event pair brackets the dispatch as well: a few us above rocprofv3's figure)",
+                             "rocprof_avg_launch_us": (rp[0] if rp else None), "rocprof_launches": (rp[1] if rp else None),
+                             "frac_rocprof": ((ab / (rp[0] * 1e-6) / 1e9 / HBM_PEAK_GBS) if rp else None),
+                             "rocprof_source": (f"{os.path.relpath(rocprof_stats_path(), ROOT)}: rocprofv3 --kernel-trace --stats of this command, "
+                                                "committed - NOT measured in this run" if rocprof_stats_path() else None),
+                             "frame_algorithmic_bytes": 112 * npx + 1740 * n_keylines,
+                             "frame_achieved_GBs": (112 * npx + 1740 * n_keylines) * (fps / world) / 1e9},
+                "kernel_us_per_frame": {kname: round(v, 3) for kname, v in sorted(per_frame.items(), key=lambda kv: -kv[1])},
+                # per kernel: algorithmic bytes of one launch; its mean duration in the all-kernel event pass ("hip_event_us": 24 frames,
+                # every launch bracketed by a HIP event pair on its stream, ~2-4 us above rocprofv3's figure for the short kernels) and in
+                # the committed rocprofv3 summary of this command ("rocprof_us"); fraction of the HBM peak on either basis
+                "kernel_roofline": kernel_roofline_table(prof, npx, n_keylines),
+            })
         if cpu_multi is not None:
             result["cpu_baseline"] = cpu_multi
-        if world == 1 and args.lanes not in ("", "0"):
+        if args.full and world == 1 and args.lanes not in ("", "0"):
             # Each batched run gets a process of its own: the HIP runtime maps streams onto a pool of hardware queues that
             # outlives the streams, and the batch's three streams must not end up sharing queues with this process's earlier
             # ones (measured: the same batch ran at half its rate after the single-stream context had lived here).
@@ -553,7 +592,7 @@ def main():
                 else:
                     print(f"batched run with {b} lanes failed: {r.stderr[-800:]}", file=sys.stderr)
             result["streams_per_gpu"] = runs
-        if world == 1 and args.config == "c2" and not args.no_host_class:
+        if args.full and world == 1 and args.config == "c2" and not args.no_host_class:
             try:
                 hc = host_class_rate(frames, cam, cfg)
                 result["config"]["host_class_fps"] = hc["fps"]
@@ -563,7 +602,7 @@ def main():
                                                        "through rebvio_replay; wall clock, first to last odometry record")
             except Exception as e:  # the extra figure must never cost the line
                 print(f"host class rate not measured: {e}", file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(frames, cam, cfg, args.base_frames, args.cpu_seconds)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
@@ -571,6 +610,43 @@ def main():
         os.dup2(2, 1)  # process-group teardown may log again
     if world > 1:
         dist.destroy_process_group()
+
+
+class RecordTap:
+    """Counts the pair records the streaming driver's pushes hand back - in pair order, several pushes late: record j
+    describes frames (j, j + 1) - and keeps the (record, keyline count) numbered `want` when it comes by."""
+
+    def __init__(self):
+        self.n, self.want, self.got = 0, None, None
+
+    def __call__(self, r):
+        if r[0].status != -1:  # -1: no finished pair to report in that call
+            if self.n == self.want:
+                self.got = r
+            self.n += 1
+        return r
+
+
+def dump_outputs(out_dir, rec, keylines):
+    """--dump-outputs: what the timed path hands its caller for its last step - the pair record of the last timed frame
+    (rebvio_hip_pair_out: one file per field, float32, the integer fields as float64; 3x3 / 6x6 matrices in their shape) and
+    the keyline count that came with it. The frames, their order and time stamps depend on the arguments only, so two runs
+    with the same arguments get the same inputs."""
+    from rebvio_amd import backend as B
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {"P_Vg": (3, 3), "W_Xv": (6, 6), "R": (3, 3), "P_V": (3, 3)}
+    arrays = {"keylines": np.array([keylines], np.float64)}
+    for name, _ in B.PairOut._fields_:
+        v = getattr(rec, name)
+        if isinstance(v, int):
+            arrays[f"pair_{name}"] = np.array([v], np.float64)
+        elif isinstance(v, float):
+            arrays[f"pair_{name}"] = np.array([v], np.float32)
+        else:
+            arrays[f"pair_{name}"] = np.array(v[:], np.float32).reshape(shapes.get(name, (-1,)))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    print(f"bench.py: {len(arrays)} output arrays written to {out_dir}", file=sys.stderr)
 
 
 def kernel_roofline_table(prof, npx, n_keylines):

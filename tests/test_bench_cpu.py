@@ -21,7 +21,7 @@ def _env_without_ranks():
 
 def test_gpus_n_without_launcher_starts_n_ranks():
     """`python bench.py --gpus 2` with WORLD_SIZE unset must start 2 ranks itself (here: control plane only, gloo)."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--control-plane-only"], env=_env_without_ranks(),
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--control-plane-only"], env=_env_without_ranks(),
                        capture_output=True, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
@@ -50,7 +50,7 @@ def test_ranks_under_a_launcher_build_the_cpu_oracle_once():
         procs = []
         for r in range(2):
             env = dict(_env_without_ranks(), RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-            procs.append(subprocess.Popen([sys.executable, BENCH, "--gpus", "2", "--control-plane-only"], env=env, stdout=subprocess.PIPE,
+            procs.append(subprocess.Popen([sys.executable, BENCH, "--gpus", "2", "--full", "--control-plane-only"], env=env, stdout=subprocess.PIPE,
                                           stderr=subprocess.PIPE))
         outs = [q.communicate(timeout=600) for q in procs]
         assert all(q.returncode == 0 for q in procs), [o[1].decode()[-800:] for o in outs]
@@ -58,6 +58,18 @@ def test_ranks_under_a_launcher_build_the_cpu_oracle_once():
         assert d["cpu_oracle_loaded_ranks"] == 2
     built = glob.glob(os.path.join(ROOT, "oracle", "_build", "native-*", "librebvio_oracle.so"))
     assert len(built) == 1 and not glob.glob(os.path.join(ROOT, "oracle", "_build", "native-*", "*.tmp.*"))
+
+
+def test_plain_run_leaves_the_cpu_baseline_to_full():
+    """A plain `bench.py --gpus 2` measures only its headline figure: no rank builds or loads the CPU oracle (that leg is --full's)."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--control-plane-only"], env=_env_without_ranks(),
+                       capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["max_over_ranks"] == 2.0
+    assert d["cpu_oracle_loaded_ranks"] == 0
 
 
 def test_world_size_mismatch_is_an_error():
@@ -116,3 +128,30 @@ def test_percentiles():
     p = bench.percentiles_ms(np.arange(101) * 1e-3)
     assert p["p50"] == pytest.approx(1.0) and p["p99"] == pytest.approx(1.0)
     assert bench.percentiles_ms([0.0])["p50"] is None
+
+
+def test_dump_outputs_takes_the_record_of_the_last_timed_pair(tmp_path):
+    """--dump-outputs: records come back in pair order, several pushes late; the tap keeps record number `want` (pushes with
+    status -1 hand back nothing) and the dump writes every field of it, float32 / float64, in the record's shapes."""
+    import bench
+    from rebvio_amd import backend as B
+    recs = []
+    for j in range(4):
+        o = B.PairOut()
+        o.Vg[0], o.W_Xv[7], o.F, o.klm_num, o.status = j + 0.5, 2.0 * j, 0.25, 1000 + j, 0
+        recs.append((o, 100 + j))
+    none = B.PairOut()
+    none.status = -1
+    tap = bench.RecordTap()
+    tap.want = 2
+    for r in [recs[0], (none, -1), recs[1], (none, -1), recs[2], recs[3]]:
+        tap(r)
+    assert tap.n == 4 and tap.got is recs[2]
+    bench.dump_outputs(str(tmp_path), *tap.got)
+    got = {p.name[:-4]: np.load(p) for p in tmp_path.iterdir()}
+    assert set(got) == {"keylines"} | {f"pair_{name}" for name, _ in B.PairOut._fields_}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["keylines"].tolist() == [102.0] and got["pair_klm_num"].tolist() == [1002.0]
+    assert got["pair_Vg"].dtype == np.float32 and got["pair_Vg"].tolist() == [2.5, 0.0, 0.0]
+    assert got["pair_W_Xv"].shape == (6, 6) and got["pair_W_Xv"][1, 1] == 4.0
+    assert got["pair_R"].shape == (3, 3) and got["pair_F"].tolist() == [0.25]

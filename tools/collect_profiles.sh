@@ -7,7 +7,7 @@ R=${1:-r03}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-BENCH="bench.py --no-cpu-baseline --lanes 0 --no-host-class --no-pcie"
+BENCH="bench.py --full --no-cpu-baseline --lanes 0 --no-host-class --no-pcie"
 echo "kernel trace c2"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2 -- python3 $BENCH --steps 600 --warmup 1000 > $OUT/c2.log 2>&1
 echo "kernel trace c3"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3 -- python3 $BENCH --config c3 --steps 300 > $OUT/c3.log 2>&1
 echo "kernel trace batch4"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/b4 -- python3 tools/batch_rate.py 4 400 800 > $OUT/b4.log 2>&1

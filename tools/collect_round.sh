@@ -12,10 +12,10 @@ case $WHAT in
     bash tools/collect_profiles.sh $R > $OUT/collect.log 2>&1 || { tail -5 $OUT/collect.log; exit 1; }
     tail -16 $OUT/collect.log ;;
   bench)
-    python3 bench.py > $OUT/bench.json 2> $OUT/bench.err && echo "bench default done" &&
-    python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err && echo "bench driver flags done" &&
-    python3 bench.py --config c3 --no-cpu-baseline --lanes 0 --no-host-class --no-pcie > $OUT/bench_c3.json 2> $OUT/bench_c3.err && echo "bench c3 done" &&
-    REBVIO_HIP_LM_STAMPS=1 REBVIO_HIP_DM_STATS=1 python3 bench.py --no-cpu-baseline --lanes 0 --no-host-class --no-pcie --steps 600 > /dev/null 2> $OUT/lm_stamps.txt
+    python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err && echo "bench default done" &&
+    python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err && echo "bench driver flags done" &&
+    python3 bench.py --full --config c3 --no-cpu-baseline --lanes 0 --no-host-class --no-pcie > $OUT/bench_c3.json 2> $OUT/bench_c3.err && echo "bench c3 done" &&
+    REBVIO_HIP_LM_STAMPS=1 REBVIO_HIP_DM_STATS=1 python3 bench.py --full --no-cpu-baseline --lanes 0 --no-host-class --no-pcie --steps 600 > /dev/null 2> $OUT/lm_stamps.txt
     grep "rebvio_hip" $OUT/lm_stamps.txt | cut -c1-400
     tail -c 400 $OUT/bench.json ;;
   pmc)

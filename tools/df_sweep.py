@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B runs of the distance-field build: bench.py under different REBVIO_HIP_DF / REBVIO_HIP_DF_STRIP settings; prints
+"""A/B runs of the distance-field build: bench.py --full under different REBVIO_HIP_DF / REBVIO_HIP_DF_STRIP settings; prints
 frames/s and the per-launch time of the distance-field kernel (HIP events, all-kernel pass)."""
 import json
 import os
@@ -15,7 +15,7 @@ for s in settings:
     else:
         env["REBVIO_HIP_DF_STRIP"] = s
     extra = os.environ.get("DF_SWEEP_ARGS", "--steps 2000 --no-cpu-baseline").split()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + extra, env=env, capture_output=True, text=True)
     if r.returncode != 0:
         print(s, "FAILED", r.stderr[-500:])
         continue
