@@ -1,5 +1,5 @@
 // Minimal stand-in for the cv::Mat subset rebvio's public API exposes (a ref-counted dense 2-D image container,
-// 8UC1 / 32FC1 / 32SC1, ptr<T>(row), at<T>, convertTo with a scale). Used ONLY when <opencv2/core.hpp> is not
+// 8UC1 / 8UC3 / 8UC4 / 32FC1 / 32SC1, ptr<T>(row), at<T>, convertTo with a scale). Used ONLY when <opencv2/core.hpp> is not
 // installed; with OpenCV on the include path the real header is used and this file is not compiled.
 #pragma once
 
@@ -8,6 +8,8 @@
 #include <memory>
 
 #define CV_8UC1 0
+#define CV_8UC3 16
+#define CV_8UC4 24
 #define CV_32SC1 4
 #define CV_32FC1 5
 
@@ -41,7 +43,7 @@ class Mat {
   T& at(int r, int c) { return ptr<T>(r)[c]; }
   template <typename T>
   const T& at(int r, int c) const { return ptr<T>(r)[c]; }
-  // convertTo(dst, CV_32FC1, alpha): dst = saturate(src * alpha); only u8/f32 -> f32 is needed by rebvio.cpp:43
+  // convertTo(dst, CV_32FC1, alpha): dst = saturate(src * alpha); only 1-channel u8/f32 -> f32 is needed by rebvio.cpp:43
   void convertTo(Mat& dst, int rtype, double alpha = 1.0) const {
     Mat out(rows, cols, rtype);
     for (int r = 0; r < rows; ++r) {
@@ -63,7 +65,7 @@ class Mat {
   }
 
  private:
-  static size_t elem_size(int type) { return type == CV_8UC1 ? 1 : 4; }
+  static size_t elem_size(int type) { return type == CV_8UC1 ? 1 : type == CV_8UC3 ? 3 : 4; }
   int type_ = CV_8UC1;
   std::shared_ptr<unsigned char> store_;
 };

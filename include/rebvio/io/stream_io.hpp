@@ -16,12 +16,22 @@
 #include "rebvio/types/image.hpp"
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/odometry.hpp"
+#include "rebvio_hip.h"
 
 namespace rebvio {
 namespace io {
 
 // 8-bit grey image from a PNG file (grey 8/16 bit, RGB/RGBA 8 bit -> luma; non-interlaced). Throws std::runtime_error.
 cv::Mat readPngGray(const std::string& path);
+
+// The stored pixels of a PNG file, not converted: 8-bit RGB -> CV_8UC3, RGBA -> CV_8UC4, grey -> CV_8UC1 (grey + alpha: the
+// grey channel; 16-bit grey: the most significant byte). `format` is the REBVIO_HIP_PX_* code of the bytes. opencv_order swaps
+// R and B as cv::imread does (CV_8UC3 / CV_8UC4 in OpenCV's BGR / BGRA order, what rebvio::Rebvio::imageCallback expects).
+struct PngPixels {
+  cv::Mat data;
+  int format = REBVIO_HIP_PX_GRAY8;
+};
+PngPixels readPngPixels(const std::string& path, bool opencv_order = false);
 
 struct FrameRef {
   uint64_t ts_us;
@@ -34,7 +44,7 @@ class StreamSource {
   virtual ~StreamSource() {}
   virtual size_t numFrames() const = 0;
   virtual uint64_t frameTs(size_t i) const = 0;
-  virtual cv::Mat frame(size_t i) = 0;  // CV_8UC1
+  virtual cv::Mat frame(size_t i) = 0;  // CV_8UC1 (EurocReader with colour: CV_8UC3 / CV_8UC4 for colour PNGs)
   const std::vector<rebvio::types::Imu>& imu() const { return imu_; }
 
  protected:
@@ -43,14 +53,17 @@ class StreamSource {
 
 class EurocReader : public StreamSource {
  public:
-  // `mav0_dir` = the folder holding cam0/ and imu0/; timestamps in the csv files are nanoseconds
-  explicit EurocReader(const std::string& mav0_dir, const std::string& cam = "cam0", const std::string& imu = "imu0");
+  // `mav0_dir` = the folder holding cam0/ and imu0/; timestamps in the csv files are nanoseconds. colour: RGB(A) PNGs are
+  // delivered as they are stored (in OpenCV's BGR(A) order: readPngPixels) for the device to convert, not as luma.
+  explicit EurocReader(const std::string& mav0_dir, const std::string& cam = "cam0", const std::string& imu = "imu0",
+                       bool colour = false);
   size_t numFrames() const override { return frames_.size(); }
   uint64_t frameTs(size_t i) const override { return frames_[i].ts_us; }
-  cv::Mat frame(size_t i) override { return readPngGray(frames_[i].path); }
+  cv::Mat frame(size_t i) override { return colour_ ? readPngPixels(frames_[i].path, true).data : readPngGray(frames_[i].path); }
 
  private:
   std::vector<FrameRef> frames_;
+  bool colour_;
 };
 
 class RawReader : public StreamSource {

@@ -128,6 +128,32 @@ int rebvio_hip_detect_u8(rebvio_hip_ctx* ctx, const uint8_t* img_host, size_t pi
 int rebvio_hip_set_undistort(rebvio_hip_ctx* ctx, const float K4[4], const float D5[5]);
 /* The front end alone: u8 host frame -> undistorted fp32 host frame (rows*cols floats). Needs a lens model. */
 int rebvio_hip_front_end_u8(rebvio_hip_ctx* ctx, const uint8_t* img_host, float* out_host);
+/* Pixel formats of the *_px entries: the frame's grey byte is formed on the device, fused into the first scan pass (or into
+ * the lens front end), then x3 as for a MONO8 frame, so everything downstream sees the values of the grey frame.
+ *   GRAY8          1 byte/px   the byte (the *_u8 entries)
+ *   RGB8 / BGR8    3 bytes/px  (R*4899 + G*9617 + B*1868 + 8192) >> 14 (cv::cvtColor RGB2GRAY / BGR2GRAY, what cv_bridge's
+ *                              MONO8 conversion computes)
+ *   RGBA8 / BGRA8  4 bytes/px  the same, alpha ignored
+ *   YUYV           2 bytes/px  Y; bytes Y0 U Y1 V (cv::COLOR_YUV2GRAY_YUY2, UVC webcams)
+ *   UYVY           2 bytes/px  Y; bytes U Y0 V Y1 (ROS "yuv422", cv::COLOR_YUV2GRAY_UYVY)
+ * YUYV / UYVY frames need an even width. Device frames are dense (rows of cols * bytes/px); host frames take pitch_bytes >=
+ * cols * bytes/px (0 = dense). With cols a multiple of 4 the first pass reads a lane's four pixels as one 8-, 12- or 16-byte
+ * load: a device frame should start 16-byte aligned (as hipMalloc'd memory does). The format is an argument
+ * of each call: one stream may change it from frame to frame. Every
+ * _px entry checks its arguments before it touches the device and refuses (-3, rebvio_hip_last_error says why) an unknown
+ * format, an odd width for YUYV / UYVY, a pitch below a row's bytes and a null frame. GRAY8 through a _px entry is the
+ * matching _u8 entry. */
+#define REBVIO_HIP_PX_GRAY8 0
+#define REBVIO_HIP_PX_RGB8 1
+#define REBVIO_HIP_PX_BGR8 2
+#define REBVIO_HIP_PX_RGBA8 3
+#define REBVIO_HIP_PX_BGRA8 4
+#define REBVIO_HIP_PX_YUYV 5
+#define REBVIO_HIP_PX_UYVY 6
+int rebvio_hip_detect_px(rebvio_hip_ctx* ctx, const void* img_host, size_t pitch_bytes, int fmt, uint64_t ts_us, rebvio_hip_map** out);
+int rebvio_hip_detect_px_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, uint64_t ts_us, rebvio_hip_map** out);
+/* rebvio_hip_front_end_u8 for a frame of any format (host memory, pitch_bytes 0 = dense). Needs a lens model. */
+int rebvio_hip_front_end_px(rebvio_hip_ctx* ctx, const void* img_host, size_t pitch_bytes, int fmt, float* out_host);
 /* config_->threshold after the servo and auto_threshold_ (edge_detector.hpp:84,91). Synchronises. */
 int rebvio_hip_detector_state(rebvio_hip_ctx* ctx, float* threshold, float* auto_threshold, int* keylines_count);
 
@@ -276,6 +302,11 @@ int rebvio_hip_push_frame_u8_device(rebvio_hip_ctx* ctx, const uint8_t* frame_de
  * (the caller's buffer is free when the call returns) and from there to the device ahead of the frame's scans, in stream order. */
 int rebvio_hip_push_frame_u8(rebvio_hip_ctx* ctx, const uint8_t* frame_host, size_t pitch_bytes, uint64_t ts_us,
                              rebvio_hip_pair_out* out, int* keylines);
+/* The two push entries for a frame of any REBVIO_HIP_PX_* format (see rebvio_hip_detect_px). */
+int rebvio_hip_push_frame_px(rebvio_hip_ctx* ctx, const void* frame_host, size_t pitch_bytes, int fmt, uint64_t ts_us,
+                             rebvio_hip_pair_out* out, int* keylines);
+int rebvio_hip_push_frame_px_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, uint64_t ts_us,
+                                    rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_next_record(rebvio_hip_ctx* ctx, rebvio_hip_pair_out* out, int* keylines);
 /* Frame pairs the streaming driver has queued on the device so far (a measurement aid: pairs are queued in groups, so a short
  * window of pushes may start a few pairs more or fewer than it pushes frames). */
@@ -306,6 +337,9 @@ int rebvio_hip_batch_lanes(rebvio_hip_batch* b);
 rebvio_hip_ctx* rebvio_hip_batch_lane(rebvio_hip_batch* b, int lane);
 int rebvio_hip_batch_push_u8_device(rebvio_hip_batch* b, const uint8_t* const* frames_dev, uint64_t ts_us, rebvio_hip_pair_out* out,
                                     int* keylines);
+/* The same with every lane's frame in the REBVIO_HIP_PX_* format `fmt` (dense in device memory; see rebvio_hip_detect_px). */
+int rebvio_hip_batch_push_px_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, uint64_t ts_us,
+                                    rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_batch_next_records(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_batch_flush(rebvio_hip_batch* b);
 

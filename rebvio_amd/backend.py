@@ -69,6 +69,9 @@ SIGNATURES = {
     "rebvio_hip_detect_u8": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.POINTER(_vp)]),
     "rebvio_hip_set_undistort": (C.c_int, [_vp, _fp, _fp]),
     "rebvio_hip_front_end_u8": (C.c_int, [_vp, _vp, _fp]),
+    "rebvio_hip_detect_px": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(_vp)]),
+    "rebvio_hip_detect_px_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.POINTER(_vp)]),
+    "rebvio_hip_front_end_px": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp]),
     "rebvio_hip_detector_state": (C.c_int, [_vp, _fp, _fp, _ip]),
     "rebvio_hip_map_size": (C.c_int, [_vp]),
     "rebvio_hip_map_threshold": (C.c_float, [_vp]),
@@ -103,6 +106,8 @@ SIGNATURES = {
     "rebvio_hip_track_pair_hint_next": (C.c_int, [_vp, _vp]),
     "rebvio_hip_push_frame_u8_device": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_push_frame_u8": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_push_frame_px": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_push_frame_px_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_next_record": (C.c_int, [_vp, C.POINTER(PairOut), _ip]),
     "rebvio_hip_pairs_started": (C.c_uint64, [_vp]),
     "rebvio_hip_flush": (C.c_int, [_vp]),
@@ -111,6 +116,7 @@ SIGNATURES = {
     "rebvio_hip_batch_lanes": (C.c_int, [_vp]),
     "rebvio_hip_batch_lane": (_vp, [_vp, C.c_int]),
     "rebvio_hip_batch_push_u8_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_batch_push_px_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_batch_next_records": (C.c_int, [_vp, C.POINTER(PairOut), _ip]),
     "rebvio_hip_batch_flush": (C.c_int, [_vp]),
     "rebvio_hip_test_glue": (C.c_int, [_vp, _fp, _fp, C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.c_float, _fp, _fp, _fp,
@@ -149,6 +155,23 @@ def lib():
             f.argtypes = args
         _lib = L
     return _lib
+
+
+# pixel formats of the *_px entries (REBVIO_HIP_PX_*) and their bytes per pixel
+PX_GRAY8, PX_RGB8, PX_BGR8, PX_RGBA8, PX_BGRA8, PX_YUYV, PX_UYVY = range(7)
+PX_BPP = (1, 3, 3, 4, 4, 2, 2)
+
+
+def _px_frame(frame: np.ndarray, fmt: int, rows: int, cols: int):
+    """(pointer, pitch_bytes) of a host frame of pixel format fmt: uint8 [H, W] (1 byte per pixel) or [H, W, bytes per pixel] with
+    dense pixels; the row pitch is taken from the array (a padded view is passed as it is)."""
+    assert frame.dtype == np.uint8 and 0 <= fmt < len(PX_BPP), (frame.dtype, fmt)
+    bpp = PX_BPP[fmt]
+    if frame.ndim == 2:
+        assert bpp == 1 and frame.shape == (rows, cols) and frame.strides[1] == 1, (frame.shape, frame.strides)
+    else:
+        assert frame.shape == (rows, cols, bpp) and frame.strides[1:] == (bpp, 1), (frame.shape, frame.strides)
+    return _vp(frame.ctypes.data), frame.strides[0]
 
 
 class HipError(RuntimeError):
@@ -319,6 +342,24 @@ class Context:
         _chk(lib().rebvio_hip_front_end_u8(self.h, frame_u8.ctypes.data_as(_vp), out.ctypes.data_as(_fp)))
         return out
 
+    def detect_px(self, frame: np.ndarray, fmt: int, ts_us=0) -> Map:
+        """Host frame of pixel format fmt (PX_*, see _px_frame) through the device front end."""
+        ptr, pitch = _px_frame(frame, fmt, self.rows, self.cols)
+        h = _vp()
+        _chk(lib().rebvio_hip_detect_px(self.h, ptr, pitch, fmt, ts_us, C.byref(h)))
+        return Map(self, h)
+
+    def detect_px_device(self, dev_addr: int, fmt: int, ts_us=0) -> Map:
+        h = _vp()
+        _chk(lib().rebvio_hip_detect_px_device(self.h, _vp(dev_addr), fmt, ts_us, C.byref(h)))
+        return Map(self, h)
+
+    def front_end_px(self, frame: np.ndarray, fmt: int) -> np.ndarray:
+        ptr, pitch = _px_frame(frame, fmt, self.rows, self.cols)
+        out = np.empty((self.rows, self.cols), np.float32)
+        _chk(lib().rebvio_hip_front_end_px(self.h, ptr, pitch, fmt, out.ctypes.data_as(_fp)))
+        return out
+
     def upload_frames(self, frames_u8: np.ndarray) -> int:
         """Stage u8 frames in HBM; returns the device address of frame 0."""
         frames_u8 = np.ascontiguousarray(frames_u8, np.uint8)
@@ -468,6 +509,20 @@ class Context:
         _chk(lib().rebvio_hip_push_frame_u8(self.h, _vp(frame_u8.ctypes.data), frame_u8.strides[0], ts_us, C.byref(out), C.byref(n)))
         return out, n.value
 
+    def push_frame_px(self, frame: np.ndarray, fmt: int, ts_us: int):
+        """Streaming push of a host frame of pixel format fmt (PX_*, see _px_frame)."""
+        ptr, pitch = _px_frame(frame, fmt, self.rows, self.cols)
+        out = PairOut()
+        n = C.c_int()
+        _chk(lib().rebvio_hip_push_frame_px(self.h, ptr, pitch, fmt, ts_us, C.byref(out), C.byref(n)))
+        return out, n.value
+
+    def push_frame_px_device(self, dev_addr: int, fmt: int, ts_us: int):
+        out = PairOut()
+        n = C.c_int()
+        _chk(lib().rebvio_hip_push_frame_px_device(self.h, _vp(dev_addr), fmt, ts_us, C.byref(out), C.byref(n)))
+        return out, n.value
+
     def test_glue(self, vel, JtJ6, F, sigma_rho_min, accept_mask, xrv, n_new, frame_dt, Bg, W_Bg, R_prior):
         """The pair glue on the device and on the host from the same inputs: ((out, state[22], second[44 words]) per side)."""
         vel, pv = _f(vel)
@@ -545,6 +600,12 @@ class Batch:
         for l, a in enumerate(dev_addrs):
             self._frames[l] = int(a)
         _chk(lib().rebvio_hip_batch_push_u8_device(self.h, self._frames, ts_us, self._out, self._n))
+        return self._out, self._n
+
+    def push_px_device(self, dev_addrs, fmt: int, ts_us: int):
+        for l, a in enumerate(dev_addrs):
+            self._frames[l] = int(a)
+        _chk(lib().rebvio_hip_batch_push_px_device(self.h, self._frames, fmt, ts_us, self._out, self._n))
         return self._out, self._n
 
     def flush(self):

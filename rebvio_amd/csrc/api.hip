@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "glue.hpp"
 #include "hostmath.hpp"
+#include "pixel_format.hpp"
 
 using namespace rh;
 
@@ -375,6 +376,7 @@ struct rebvio_hip_ctx {
     const MapState* prev_st;
     int pin_slot = -1;      // host-frame entries: pinned ring slot to copy to `img` (device staging frame) ahead of the scans
     size_t pin_bytes = 0;
+    int fmt = 0;            // pixel format of a u8 frame (pixel_format.hpp)
   };
   std::thread det_thread;
   std::mutex det_mu;
@@ -620,16 +622,21 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
   if (c->prev_ready[b]) HIPCHK(hipStreamWaitEvent(c->s_det, c->prev_ready[b], 0));
   const void* img = j.img;
   int is_u8 = j.is_u8;
+  int fmt = is_u8 ? j.fmt : 0;
   if (is_u8 && c->undist_map) {  // x3 + undistort (rebvio.cpp:43-47); its output was last read by the scans two frames ago
-    launch_front_end_u8(c->s_det, c->K, (const uint8_t*)img, c->undist_map, c->undist_img[b]);
+    if (fmt == px::GRAY8)
+      launch_front_end_u8(c->s_det, c->K, (const uint8_t*)img, c->undist_map, c->undist_img[b]);
+    else  // grey byte of every tap first (cv_bridge MONO8), then x3 + undistort
+      launch_front_end_px(c->s_det, c->K, (const uint8_t*)img, fmt, c->undist_map, c->undist_img[b]);
     img = c->undist_img[b];
     is_u8 = 0;
+    fmt = 0;
   }
   // The scan stream is the busiest of the three: it hands the frame over after the last ROW pass, the last column pass and
   // the DoG / gradient kernel run at the head of the keyline stream.
   // Their inputs sb.a[] are then read while the scan stream already works on the next frame, hence the pair per parity;
   // the frame after next waits for this frame's `ready` event (prev_ready[b]) above.
-  launch_scale_space(c->s_det, c->K, img, is_u8, sb, c->widths, db.rowcount, 1);
+  launch_scale_space(c->s_det, c->K, img, is_u8, sb, c->widths, db.rowcount, 1, false, fmt);
   HIPCHK(hipEventRecord(c->ev_scan[b], c->s_det));
   // keyline extraction + chaining (s_key), overlapping the next frame's scans
   HIPCHK(hipStreamWaitEvent(c->s_key, c->ev_scan[b], 0));
@@ -648,7 +655,7 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
 }
 
 // caller-thread half: takes a pooled map and fixes the servo-state ring slots of this frame
-int detect_prepare(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_ctx::DetJob* job) {
+int detect_prepare(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_ctx::DetJob* job, int fmt = 0) {
   rebvio_hip_map* m = acquire_map(c);
   if (!m) return fail_msg("edge-map pool exhausted (release maps or raise map_pool)", -2);
   m->ts = ts;
@@ -657,6 +664,7 @@ int detect_prepare(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t t
   job->m = m;
   job->img = img_dev;
   job->is_u8 = is_u8;
+  job->fmt = fmt;
   job->det_in = c->det + (c->frame_index % kDetRing);
   job->det_out = c->det + ((c->frame_index + 1) % kDetRing);
   job->prev_st = c->last_detected ? c->last_detected->d.st : nullptr;
@@ -678,13 +686,13 @@ void detect_failed(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& job) {
   release_map(job.m, nullptr);
 }
 
-int detect_common(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_map** out) {
+int detect_common(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_map** out, int fmt = 0) {
   {
     std::lock_guard<std::mutex> lk(c->det_mu);
     if (!c->det_error.empty()) return fail_msg(c->det_error.c_str(), -8);
   }
   rebvio_hip_ctx::DetJob job;
-  int rc = detect_prepare(c, img_dev, is_u8, ts, &job);
+  int rc = detect_prepare(c, img_dev, is_u8, ts, &job, fmt);
   if (rc) return rc;
   // a queued asynchronous detect must be launched first (stream order = frame order)
   while (c->det_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
@@ -724,17 +732,19 @@ void det_worker_main(rebvio_hip_ctx* c) {
 }
 
 int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, size_t row_bytes, int* slot_out, size_t* bytes_out);
-// host_u8 != null: a MONO8 frame in host memory, staged through the pinned ring; the worker queues its copy to the device
-// staging frame ahead of the scans (same stream: stream order is reuse order)
+void* u8_staging(rebvio_hip_ctx* c, int fmt);
+// host_u8 != null: a u8 frame (pixel format fmt) in host memory, staged through the pinned ring; the worker queues its copy to the
+// device staging frame ahead of the scans (same stream: stream order is reuse order)
 int detect_async(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_map** out, const uint8_t* host_u8 = nullptr,
-                 size_t host_pitch = 0) {
+                 size_t host_pitch = 0, int fmt = 0) {
   rebvio_hip_ctx::DetJob job;
   if (host_u8) {
-    const int rcs = stage_host_frame(c, host_u8, host_pitch ? host_pitch : (size_t)c->P.cols, (size_t)c->P.cols, &job.pin_slot, &job.pin_bytes);
+    const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
+    const int rcs = stage_host_frame(c, host_u8, host_pitch ? host_pitch : rowb, rowb, &job.pin_slot, &job.pin_bytes);
     if (rcs) return rcs;
-    img_dev = c->img8_dev;
+    img_dev = u8_staging(c, fmt);
   }
-  int rc = detect_prepare(c, img_dev, is_u8, ts, &job);
+  int rc = detect_prepare(c, img_dev, is_u8, ts, &job, fmt);
   if (rc && job.pin_slot >= 0) c->pin_staged[job.pin_slot].store(0, std::memory_order_release);
   if (rc) return rc;
   if (!c->det_worker) {  // REBVIO_HIP_DETECT_WORKER=0: the caller launches the detect kernels itself (one thread issues every runtime call)
@@ -1013,11 +1023,40 @@ int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, siz
   return 0;
 }
 
+// Device staging frame of a host u8 frame of pixel format fmt. MONO8: img8_dev (rows * cols bytes). Wider formats: img_dev, the
+// fp32 host frame's staging (rows * cols * 4 bytes + 16, as large as the widest format), allocated with the context - a colour
+// stream allocates nothing, and nothing grows or stalls the frames in flight when the format changes. Both are written and read
+// by the scan stream's own operations only, so stream order is reuse order, whichever format each frame has.
+void* u8_staging(rebvio_hip_ctx* c, int fmt) { return fmt == px::GRAY8 ? (void*)c->img8_dev : (void*)c->img_dev; }
+
+// Argument checks of the *_px entries, before anything touches the device. host: pitch_bytes is checked (0 = dense).
+int check_px(const rebvio_hip_ctx* c, const char* who, const void* frame, int fmt, bool host, size_t pitch_bytes) {
+  char buf[192];
+  if (!px::valid(fmt)) {
+    std::snprintf(buf, sizeof(buf), "%s: unknown pixel format %d (REBVIO_HIP_PX_GRAY8 .. REBVIO_HIP_PX_UYVY)", who, fmt);
+    return fail_msg(buf, -3);
+  }
+  if (!frame) {
+    std::snprintf(buf, sizeof(buf), "%s: null frame", who);
+    return fail_msg(buf, -3);
+  }
+  if (px::needs_even_cols(fmt) && (c->P.cols & 1)) {
+    std::snprintf(buf, sizeof(buf), "%s: YUYV / UYVY frames need an even width (cols = %d)", who, c->P.cols);
+    return fail_msg(buf, -3);
+  }
+  const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
+  if (host && pitch_bytes != 0 && pitch_bytes < rowb) {
+    std::snprintf(buf, sizeof(buf), "%s: pitch_bytes %zu below a row's %zu bytes (cols * bytes per pixel)", who, pitch_bytes, rowb);
+    return fail_msg(buf, -3);
+  }
+  return 0;
+}
+
 // Detection of a host frame: staged through the pinned ring and launched by the caller. (Handing the launch to the context's
 // detect worker was measured with rebvio::Rebvio in round 2: the acquisition thread's time per frame dropped, the fusion
 // thread's own launches slowed down by as much - runtime calls of different threads largely serialise - no gain, removed.)
 int detect_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, size_t row_bytes, void* dst_dev, int is_u8, uint64_t ts,
-                      rebvio_hip_map** out) {
+                      rebvio_hip_map** out, int fmt = 0) {
   {
     std::lock_guard<std::mutex> lk(c->det_mu);
     if (!c->det_error.empty()) return fail_msg(c->det_error.c_str(), -8);
@@ -1025,7 +1064,7 @@ int detect_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, si
   rebvio_hip_ctx::DetJob job;
   int rc = stage_host_frame(c, img, pitch_bytes, row_bytes, &job.pin_slot, &job.pin_bytes);
   if (rc) return rc;
-  rc = detect_prepare(c, dst_dev, is_u8, ts, &job);
+  rc = detect_prepare(c, dst_dev, is_u8, ts, &job, fmt);
   if (rc) {
     c->pin_staged[job.pin_slot].store(0, std::memory_order_release);
     return rc;
@@ -1426,6 +1465,24 @@ int rebvio_hip_detect_u8(rebvio_hip_ctx* c, const uint8_t* img, size_t pitch_byt
   return detect_host_frame(c, img, pitch_bytes, rowb, c->img8_dev, 1, ts_us, out);
 }
 
+int rebvio_hip_detect_px(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, int fmt, uint64_t ts_us, rebvio_hip_map** out) {
+  int rc = check_px(c, "detect_px", img, fmt, true, pitch_bytes);
+  if (rc) return rc;
+  if (fmt == px::GRAY8) return rebvio_hip_detect_u8(c, static_cast<const uint8_t*>(img), pitch_bytes, ts_us, out);
+  HIPCHK(hipSetDevice(c->device));
+  const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
+  if (pitch_bytes == 0) pitch_bytes = rowb;
+  return detect_host_frame(c, img, pitch_bytes, rowb, u8_staging(c, fmt), 1, ts_us, out, fmt);
+}
+
+int rebvio_hip_detect_px_device(rebvio_hip_ctx* c, const void* frame_dev, int fmt, uint64_t ts_us, rebvio_hip_map** out) {
+  int rc = check_px(c, "detect_px_device", frame_dev, fmt, false, 0);
+  if (rc) return rc;
+  if (fmt == px::GRAY8) return rebvio_hip_detect_u8_device(c, static_cast<const uint8_t*>(frame_dev), ts_us, out);
+  HIPCHK(hipSetDevice(c->device));
+  return detect_common(c, frame_dev, 1, ts_us, out, fmt);
+}
+
 int rebvio_hip_set_undistort(rebvio_hip_ctx* c, const float K4[4], const float D5[5]) {
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipDeviceSynchronize());  // no frame in flight may still read the old map
@@ -1453,6 +1510,23 @@ int rebvio_hip_front_end_u8(rebvio_hip_ctx* c, const uint8_t* img, float* out) {
   const size_t Pn = (size_t)c->P.rows * c->P.cols;
   HIPCHK(hipMemcpyAsync(c->img8_dev, img, Pn, hipMemcpyHostToDevice, c->s_det));
   launch_front_end_u8(c->s_det, c->K, c->img8_dev, c->undist_map, c->undist_img[0]);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, c->undist_img[0], Pn * sizeof(float), hipMemcpyDeviceToHost, c->s_det));
+  HIPCHK(hipStreamSynchronize(c->s_det));
+  return 0;
+}
+
+int rebvio_hip_front_end_px(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, int fmt, float* out) {
+  int rc = check_px(c, "front_end_px", img, fmt, true, pitch_bytes);
+  if (rc) return rc;
+  if (!out) return fail_msg("front_end_px: null output", -3);
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->undist_map) return fail_msg("front_end_px: no distortion model set (rebvio_hip_set_undistort)", -3);
+  const size_t Pn = (size_t)c->P.rows * c->P.cols;
+  const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
+  uint8_t* stage = static_cast<uint8_t*>(u8_staging(c, fmt));
+  HIPCHK(hipMemcpy2DAsync(stage, rowb, img, pitch_bytes ? pitch_bytes : rowb, rowb, (size_t)c->P.rows, hipMemcpyHostToDevice, c->s_det));
+  launch_front_end_px(c->s_det, c->K, stage, fmt, c->undist_map, c->undist_img[0]);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, c->undist_img[0], Pn * sizeof(float), hipMemcpyDeviceToHost, c->s_det));
   HIPCHK(hipStreamSynchronize(c->s_det));
@@ -2306,7 +2380,7 @@ int stream_drain(rebvio_hip_ctx* c) {
 
 namespace {
 int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame_host, size_t host_pitch, uint64_t ts_us, rebvio_hip_pair_out* out,
-               int* keylines) {
+               int* keylines, int fmt = 0) {
   // Software pipeline over the three HIP streams of the context:
   //   scan / keyline streams : frame f (this call, through the detect worker)
   //   track stream           : see the comment above stream_wait_maps
@@ -2326,7 +2400,7 @@ int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame
   }
   if (keylines) *keylines = -1;
   c->min_pool = c->lead + 3 * c->group + 3;
-  int rc = detect_async(c, frame_dev, 1, ts_us, &m, frame_host, host_pitch);
+  int rc = detect_async(c, frame_dev, 1, ts_us, &m, frame_host, host_pitch, fmt);
   if (rc) return rc;
   {
     std::lock_guard<std::mutex> lk(c->det_mu);  // written by the detect worker
@@ -2370,6 +2444,20 @@ int rebvio_hip_push_frame_u8(rebvio_hip_ctx* c, const uint8_t* frame_host, size_
                              int* keylines) {
   if (!frame_host) return fail_msg("push_frame_u8: null frame", -3);
   return push_frame(c, nullptr, frame_host, pitch_bytes, ts_us, out, keylines);
+}
+
+int rebvio_hip_push_frame_px_device(rebvio_hip_ctx* c, const void* frame_dev, int fmt, uint64_t ts_us, rebvio_hip_pair_out* out,
+                                    int* keylines) {
+  const int rc = check_px(c, "push_frame_px_device", frame_dev, fmt, false, 0);
+  if (rc) return rc;
+  return push_frame(c, static_cast<const uint8_t*>(frame_dev), nullptr, 0, ts_us, out, keylines, fmt);
+}
+
+int rebvio_hip_push_frame_px(rebvio_hip_ctx* c, const void* frame_host, size_t pitch_bytes, int fmt, uint64_t ts_us, rebvio_hip_pair_out* out,
+                             int* keylines) {
+  const int rc = check_px(c, "push_frame_px", frame_host, fmt, true, pitch_bytes);
+  if (rc) return rc;
+  return push_frame(c, nullptr, static_cast<const uint8_t*>(frame_host), pitch_bytes, ts_us, out, keylines, fmt);
 }
 
 uint64_t rebvio_hip_pairs_started(rebvio_hip_ctx* c) { return c->pair_seq; }
@@ -2712,6 +2800,7 @@ struct rebvio_hip_batch {
     hipEvent_t reuse_done;  // last consumer of the maps this step reuses (null: fresh maps)
     std::vector<rebvio_hip_map*> maps;
     bool lens;
+    int fmt = 0;  // pixel format of every lane's frame
   };
   std::thread det_thread;
   std::mutex det_mu;
@@ -2763,7 +2852,7 @@ int batch_detect_launch(rebvio_hip_batch* b, const rebvio_hip_batch::DetStep& j)
   // (8 lanes 42.4 k -> 39.7 k frames/s, 4 lanes 32.9 k -> 32.2 k), like the single stream's other moves of scan work to the
   // keyline stream - opt-in here (REBVIO_HIP_BATCH_FUSE_DOG=1), the default for one stream
   const bool fuse = b->fuse_dog;
-  launch_scale_space_b(b->st.s_det, b->K, 0, B, b->ls_dev, j.dyn, b->lane[0]->widths, j.lens, fuse);
+  launch_scale_space_b(b->st.s_det, b->K, 0, B, b->ls_dev, j.dyn, b->lane[0]->widths, j.lens, fuse, j.fmt);
   HIPCHK(hipEventRecord(b->ev_scan[par], b->st.s_det));
   HIPCHK(hipStreamWaitEvent(b->st.s_key, b->ev_scan[par], 0));
   if (j.reuse_done) HIPCHK(hipStreamWaitEvent(b->st.s_key, j.reuse_done, 0));
@@ -3153,8 +3242,7 @@ int rebvio_hip_batch_test_forge_record_stamp(rebvio_hip_batch* b) {
 }
 rebvio_hip_ctx* rebvio_hip_batch_lane(rebvio_hip_batch* b, int lane) { return (lane >= 0 && lane < b->B) ? b->lane[lane] : nullptr; }
 
-int rebvio_hip_batch_push_u8_device(rebvio_hip_batch* b, const uint8_t* const* frames_dev, uint64_t ts_us, rebvio_hip_pair_out* out,
-                                    int* keylines) {
+static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines) {
   HIPCHK(hipSetDevice(b->device));
   if (b->poisoned) return fail_msg("batch: an earlier step failed half way; the lanes are out of lock-step (destroy the batch)", -11);
   const int B = b->B;
@@ -3204,7 +3292,7 @@ int rebvio_hip_batch_push_u8_device(rebvio_hip_batch* b, const uint8_t* const* f
     rebvio_hip_ctx* c = b->lane[l];
     rebvio_hip_ctx::DetJob job;
     c->min_pool = std::min(kLaneMaps - 2, b->lead + 3 * b->group + 3);
-    int rc = detect_prepare(c, frames_dev[l], 1, ts_us, &job);
+    int rc = detect_prepare(c, frames_dev[l], 1, ts_us, &job, fmt);
     if (rc == 0) {
       rebvio_hip_map* m = job.m;
       if (m->tab_idx < 0 || std::memcmp(&m->canon.pos, &m->d.pos, sizeof(void*)) != 0)  // a map the pool has just grown by
@@ -3241,6 +3329,7 @@ int rebvio_hip_batch_push_u8_device(rebvio_hip_batch* b, const uint8_t* const* f
   job.reuse_done = (last_reused && last_reused->has_done) ? (last_reused->done_ref ? last_reused->done_ref : last_reused->done) : nullptr;
   job.maps = fr.m;
   job.lens = b->lens;
+  job.fmt = fmt;
   for (auto* m : fr.m) m->enqueued.store(0, std::memory_order_relaxed);
   if (!b->det_worker) {  // the caller launches the step's detect kernels itself (see detect_async)
     const auto t0 = std::chrono::steady_clock::now();
@@ -3283,6 +3372,21 @@ int rebvio_hip_batch_push_u8_device(rebvio_hip_batch* b, const uint8_t* const* f
   if (rc) return rc;
   (void)batch_pop(b, out, keylines);
   return 0;
+}
+
+int rebvio_hip_batch_push_u8_device(rebvio_hip_batch* b, const uint8_t* const* frames_dev, uint64_t ts_us, rebvio_hip_pair_out* out,
+                                    int* keylines) {
+  return batch_push(b, reinterpret_cast<const void* const*>(frames_dev), px::GRAY8, ts_us, out, keylines);
+}
+
+int rebvio_hip_batch_push_px_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, uint64_t ts_us, rebvio_hip_pair_out* out,
+                                    int* keylines) {
+  if (!frames_dev) return fail_msg("batch_push_px_device: null frame array", -3);
+  for (int l = 0; l < b->B; ++l) {
+    const int rc = check_px(b->lane[l], "batch_push_px_device", frames_dev[l], fmt, false, 0);
+    if (rc) return rc;
+  }
+  return batch_push(b, frames_dev, fmt, ts_us, out, keylines);
 }
 
 int rebvio_hip_batch_next_records(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines) { return batch_pop(b, out, keylines); }

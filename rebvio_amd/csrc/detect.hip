@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "pixel_format.hpp"
 
 namespace rh {
 
@@ -112,13 +113,51 @@ __device__ __forceinline__ float4 box_avg4_interior(const float* __restrict__ II
   return o;
 }
 
-// Input images (MODE 0 / 1) are dense (row stride C). Widths that are not a multiple of 4 take element loads guarded at
+// MODE 0 with a colour / packed-YUV frame (FMT != px::GRAY8, pixel_format.hpp): the four pixels of a lane are one run of
+// 4 * bytes-per-pixel bytes (12 for RGB8 / BGR8, 16 for RGBA8 / BGRA8, 8 for YUYV / UYVY) at a byte offset that is a multiple of
+// the run's length, loaded with one dwordx3 / dwordx4 / dwordx2; each pixel becomes its grey byte in registers, then x3 as
+// for a grey frame - the same fp32 values.
+struct __attribute__((aligned(4))) RunX3 {
+  uint32_t w[3];
+};
+template <int FMT>
+__device__ __forceinline__ float4 grey4_x3_aligned(const uint8_t* __restrict__ p /* first byte of pixel c, run-aligned */) {
+  constexpr int bpp = px::bytes_per_pixel(FMT);
+  union {
+    uint32_t w[4];
+    uint8_t b[16];
+  } u;
+  if (bpp == 4) {
+    const uint4 q = *reinterpret_cast<const uint4*>(p);
+    u.w[0] = q.x, u.w[1] = q.y, u.w[2] = q.z, u.w[3] = q.w;
+  } else if (bpp == 3) {
+    const RunX3 q = *reinterpret_cast<const RunX3*>(p);
+    u.w[0] = q.w[0], u.w[1] = q.w[1], u.w[2] = q.w[2], u.w[3] = 0u;
+  } else {
+    const uint2 q = *reinterpret_cast<const uint2*>(p);
+    u.w[0] = q.x, u.w[1] = q.y, u.w[2] = 0u, u.w[3] = 0u;
+  }
+  return make_float4((float)px::grey_at<FMT>(u.b, 0) * 3.0f, (float)px::grey_at<FMT>(u.b, 1) * 3.0f,
+                     (float)px::grey_at<FMT>(u.b, 2) * 3.0f, (float)px::grey_at<FMT>(u.b, 3) * 3.0f);
+}
+
+// Input images (MODE 0 / 1) are dense (row stride C pixels). Widths that are not a multiple of 4 take element loads guarded at
 // the row end (the vector forms would straddle rows and run past the last one); the columns >= C of the pitch padding
-// read 0. Integral images (MODE 2) have the padded pitch `ld`.
-template <int MODE>
+// read 0. Integral images (MODE 2) have the padded pitch `ld`. FMT: pixel format of a MODE 0 frame.
+template <int MODE, int FMT = px::GRAY8>
 __device__ __forceinline__ float4 rowscan_fetch(const void* __restrict__ src, int r, int c4, int d, int d2, int R, int C, int ld) {
   const int c = c4 * 4;
-  if (MODE == 0) {
+  if (MODE == 0 && FMT != px::GRAY8) {
+    constexpr int bpp = px::bytes_per_pixel(FMT);
+    const uint8_t* row = reinterpret_cast<const uint8_t*>(src) + (size_t)r * C * bpp;
+    if ((C & 3) == 0) return grey4_x3_aligned<FMT>(row + (size_t)c * bpp);
+    float4 v;
+    v.x = (c < C) ? (float)px::grey_at<FMT>(row, c) * 3.0f : 0.0f;
+    v.y = (c + 1 < C) ? (float)px::grey_at<FMT>(row, c + 1) * 3.0f : 0.0f;
+    v.z = (c + 2 < C) ? (float)px::grey_at<FMT>(row, c + 2) * 3.0f : 0.0f;
+    v.w = (c + 3 < C) ? (float)px::grey_at<FMT>(row, c + 3) * 3.0f : 0.0f;
+    return v;
+  } else if (MODE == 0) {
     if ((C & 3) == 0) {
       const uchar4 u = reinterpret_cast<const uchar4*>(src)[((size_t)r * C + c) >> 2];
       return make_float4((float)u.x * 3.0f, (float)u.y * 3.0f, (float)u.z * 3.0f, (float)u.w * 3.0f);
@@ -258,7 +297,7 @@ __device__ __forceinline__ bool wave_chain_any(float* __restrict__ arr, int n4) 
   }
 }
 
-template <int MODE>  // 0: u8 image * 3.0f, 1: fp32 image, 2: box average (width d) of an integral image
+template <int MODE, int FMT = px::GRAY8>  // 0: u8 image (pixel format FMT) * 3.0f, 1: fp32 image, 2: box average (width d) of an integral image
 __device__ __forceinline__ void rowscan_body(const void* __restrict__ src0, const void* __restrict__ src1,
                                                  float* __restrict__ dst0, float* __restrict__ dst1, int R, int Cimg, int d0,
                                                  int d1, int ldw) {
@@ -285,9 +324,9 @@ __device__ __forceinline__ void rowscan_body(const void* __restrict__ src0, cons
   constexpr int kCPP = 64;   // chunks per pass
   for (int base = 0; base < C4; base += kCPP * kBatch) {
     // named registers, not an array (arrays of float4 end up in scratch with this compiler)
-    const float4 v0 = rowscan_fetch<MODE>(src, r, min(base + 0 * kCPP + cb, C4 - 1), d, d2, R, Cimg, C);
-    const float4 v1 = rowscan_fetch<MODE>(src, r, min(base + 1 * kCPP + cb, C4 - 1), d, d2, R, Cimg, C);
-    const float4 v2 = rowscan_fetch<MODE>(src, r, min(base + 2 * kCPP + cb, C4 - 1), d, d2, R, Cimg, C);
+    const float4 v0 = rowscan_fetch<MODE, FMT>(src, r, min(base + 0 * kCPP + cb, C4 - 1), d, d2, R, Cimg, C);
+    const float4 v1 = rowscan_fetch<MODE, FMT>(src, r, min(base + 1 * kCPP + cb, C4 - 1), d, d2, R, Cimg, C);
+    const float4 v2 = rowscan_fetch<MODE, FMT>(src, r, min(base + 2 * kCPP + cb, C4 - 1), d, d2, R, Cimg, C);
     __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first LDS write
 #define RH_RS_ST(k, v)                                                                  \
     {                                                                                   \
@@ -395,6 +434,18 @@ __global__ __launch_bounds__(256) void k_rowscan_b(const LaneStatic* __restrict_
     o1 = gptr(L.mag2[par]);
   }
   rowscan_body<MODE>(s0, s1, o0, o1, R, Cimg, d0, d1, ldw);
+}
+// the first pass (MODE 0) on a frame of a colour / packed-YUV format FMT; single stream, and batched (stage 0 only: every
+// lane's frame -> its a[0])
+template <int FMT>
+__global__ __launch_bounds__(256) void k_rowscan_px(const void* __restrict__ src, float* __restrict__ dst, int R, int Cimg, int ldw) {
+  rowscan_body<0, FMT>(src, src, dst, dst, R, Cimg, 0, 0, ldw);
+}
+template <int FMT>
+__global__ __launch_bounds__(256) void k_rowscan_px_b(const LaneStatic* __restrict__ ls, LaneDynB dyn, int lane0, int R, int Cimg, int ldw) {
+  const int lane = lane0 + blockIdx.z;
+  float* o = gptr(ls[lane].sa[0]);
+  rowscan_body<0, FMT>(dyn.v[lane].img, dyn.v[lane].img, o, o, R, Cimg, 0, 0, ldw);
 }
 
 // ---- column accumulation (scale_space.cpp:59-65) --------------------------------------------------------------
@@ -1539,6 +1590,9 @@ static int lds_pitch(int cols) {
 // map = fixed-point source coordinates (1/32 px, hostmath.hpp undistort_fixed_map). Weights (1-a)(1-b) .. with a, b
 // multiples of 1/32 and 8-bit*3 sources make every product and the 4-term sum exact in fp32, so the result does not
 // depend on evaluation order; taps outside the image read the constant border 0 (BORDER_CONSTANT).
+// FMT (pixel_format.hpp): every tap is first its pixel's grey byte, then x3, then weighted - the reference's order (cv_bridge
+// MONO8, convertTo(CV_32F, 3.0), undistort).
+template <int FMT = px::GRAY8>
 __device__ __forceinline__ void front_end_body(const uint8_t* __restrict__ src, const int2* __restrict__ map, float* __restrict__ dst,
                                                int rows, int cols) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1548,12 +1602,13 @@ __device__ __forceinline__ void front_end_body(const uint8_t* __restrict__ src, 
   const float ax = (float)(m.x & 31) * 0.03125f, ay = (float)(m.y & 31) * 0.03125f;
   const bool x0 = (unsigned)sx < (unsigned)cols, x1 = (unsigned)(sx + 1) < (unsigned)cols;
   const bool y0 = (unsigned)sy < (unsigned)rows, y1 = (unsigned)(sy + 1) < (unsigned)rows;
-  const uint8_t* r0 = src + (size_t)(y0 ? sy : 0) * cols;
-  const uint8_t* r1 = src + (size_t)(y1 ? sy + 1 : 0) * cols;
-  const float s00 = (x0 && y0) ? (float)r0[sx] * 3.0f : 0.0f;
-  const float s01 = (x1 && y0) ? (float)r0[sx + 1] * 3.0f : 0.0f;
-  const float s10 = (x0 && y1) ? (float)r1[sx] * 3.0f : 0.0f;
-  const float s11 = (x1 && y1) ? (float)r1[sx + 1] * 3.0f : 0.0f;
+  constexpr int bpp = px::bytes_per_pixel(FMT);
+  const uint8_t* r0 = src + (size_t)(y0 ? sy : 0) * cols * bpp;
+  const uint8_t* r1 = src + (size_t)(y1 ? sy + 1 : 0) * cols * bpp;
+  const float s00 = (x0 && y0) ? (float)px::grey_at<FMT>(r0, sx) * 3.0f : 0.0f;
+  const float s01 = (x1 && y0) ? (float)px::grey_at<FMT>(r0, sx + 1) * 3.0f : 0.0f;
+  const float s10 = (x0 && y1) ? (float)px::grey_at<FMT>(r1, sx) * 3.0f : 0.0f;
+  const float s11 = (x1 && y1) ? (float)px::grey_at<FMT>(r1, sx + 1) * 3.0f : 0.0f;
   const float w00 = (1.0f - ay) * (1.0f - ax), w01 = (1.0f - ay) * ax, w10 = ay * (1.0f - ax), w11 = ay * ax;
   dst[i] = s00 * w00 + s01 * w01 + s10 * w10 + s11 * w11;
 }
@@ -1566,6 +1621,18 @@ __global__ __launch_bounds__(256) void k_front_end_u8_b(const LaneStatic* __rest
   const int lane = lane0 + blockIdx.z;
   const LaneStatic& L = ls[lane];
   front_end_body(static_cast<const uint8_t*>(dyn.v[lane].img), gptr(L.undist_map), gptr(L.undist_img[dyn.v[lane].parity]), rows, cols);
+}
+// the same two for a frame of a colour / packed-YUV format
+template <int FMT>
+__global__ __launch_bounds__(256) void k_front_end_px(const uint8_t* __restrict__ src, const int2* __restrict__ map, float* __restrict__ dst,
+                                                      int rows, int cols) {
+  front_end_body<FMT>(src, map, dst, rows, cols);
+}
+template <int FMT>
+__global__ __launch_bounds__(256) void k_front_end_px_b(const LaneStatic* __restrict__ ls, LaneDynB dyn, int lane0, int rows, int cols) {
+  const int lane = lane0 + blockIdx.z;
+  const LaneStatic& L = ls[lane];
+  front_end_body<FMT>(static_cast<const uint8_t*>(dyn.v[lane].img), gptr(L.undist_map), gptr(L.undist_img[dyn.v[lane].parity]), rows, cols);
 }
 
 // Host frame -> device staging frame as a kernel of the scan stream (16 bytes per lane straight from the pinned ring slot over
@@ -1583,11 +1650,33 @@ void launch_copy_from_pinned(hipStream_t s, const void* src_pinned, void* dst_de
 void launch_front_end_u8(hipStream_t s, const KParams& p, const uint8_t* src, const int2* map, float* dst) {
   RH_LAUNCH(k_front_end_u8, dim3(div_up(p.rows * p.cols, 256)), dim3(256), 0, s, src, map, dst, p.rows, p.cols);
 }
+void launch_front_end_px(hipStream_t s, const KParams& p, const uint8_t* src, int fmt, const int2* map, float* dst) {
+  const dim3 g(div_up(p.rows * p.cols, 256));
+  switch (fmt) {
+#define RH_FE_PX(F) \
+  case F: RH_LAUNCH(k_front_end_px<F>, g, dim3(256), 0, s, src, map, dst, p.rows, p.cols); break;
+    RH_FE_PX(px::RGB8) RH_FE_PX(px::BGR8) RH_FE_PX(px::RGBA8) RH_FE_PX(px::BGRA8) RH_FE_PX(px::YUYV) RH_FE_PX(px::UYVY)
+#undef RH_FE_PX
+    default: launch_front_end_u8(s, p, src, map, dst);
+  }
+}
+
+// dynamic LDS above 64 KiB for the colour first-pass kernels, once (the first frame of such a format)
+static void rowscan_px_attrs() {
+  static bool done = false;
+  if (done) return;
+#define RH_PX_ATTR(F)                                                                                                        \
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rowscan_px<F>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rowscan_px_b<F>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  RH_PX_ATTR(px::RGB8) RH_PX_ATTR(px::BGR8) RH_PX_ATTR(px::RGBA8) RH_PX_ATTR(px::BGRA8) RH_PX_ATTR(px::YUYV) RH_PX_ATTR(px::UYVY)
+#undef RH_PX_ATTR
+  done = true;
+}
 
 // part: 1 = everything up to the row pass of the third box filter (five kernels), 2 = its column pass + k_dog_mag, 3 = both.
 // The streaming driver runs part 2 on the keyline stream: the scan stream is the busiest of a frame's three.
 void launch_scale_space(hipStream_t s, const KParams& p, const void* img, int img_is_u8, const ScaleBufs& sb,
-                        const int widths[2][3], int* rowcount_to_zero, int part, bool fuse_dog) {
+                        const int widths[2][3], int* rowcount_to_zero, int part, bool fuse_dog, int fmt) {
   const int R = p.rows, C = p.cols;
   const int Cp = (C + 3) & ~3;  // pitch of the scan buffers sb.a / sb.b
   const int ldw_abs = lds_pitch(Cp);
@@ -1608,7 +1697,17 @@ void launch_scale_space(hipStream_t s, const KParams& p, const void* img, int im
 #define RH_COLSCAN(one, b0, b1) RH_LAUNCH(k_colscan, (one) ? c1 : c2, dim3(256), cshm, s, b0, b1, R, Cp, ldh, (int*)nullptr, 0)
   if (part & 1) {
     // pass 1: both filters share the integral image of the input (scale_space.cpp:175)
-    if (img_is_u8)
+    if (img_is_u8 && fmt != px::GRAY8) {
+      rowscan_px_attrs();
+      switch (fmt) {
+#define RH_RS_PX(F)                                                                                         \
+  case F:                                                                                                   \
+    RH_LAUNCH(k_rowscan_px<F>, g1, dim3(256), shm, s, img, sb.a[0], R, C, ldw);                               \
+    break;
+        RH_RS_PX(px::RGB8) RH_RS_PX(px::BGR8) RH_RS_PX(px::RGBA8) RH_RS_PX(px::BGRA8) RH_RS_PX(px::YUYV) RH_RS_PX(px::UYVY)
+#undef RH_RS_PX
+      }
+    } else if (img_is_u8)
       RH_LAUNCH(k_rowscan<0>, g1, dim3(256), shm, s, img, img, sb.a[0], sb.a[0], R, C, 0, 0, ldw);
     else
       RH_LAUNCH(k_rowscan<1>, g1, dim3(256), shm, s, img, img, sb.a[0], sb.a[0], R, C, 0, 0, ldw);
@@ -1664,7 +1763,7 @@ void launch_smooth_n(hipStream_t s, const KParams& p, const float* img, const Sc
 
 // ---- batched launchers (lane = blockIdx.z): the same grids with a third dimension ------------------------------------------
 void launch_scale_space_b(hipStream_t s, const KParams& p, int lane0, int lanes, const LaneStatic* ls, const LaneDynB& dyn,
-                          const int widths[2][3], bool lens, bool fuse_dog) {
+                          const int widths[2][3], bool lens, bool fuse_dog, int fmt) {
   const int R = p.rows, C = p.cols;
   const int Cp = (C + 3) & ~3;
   const int ldw_abs = lds_pitch(Cp);
@@ -1685,8 +1784,25 @@ void launch_scale_space_b(hipStream_t s, const KParams& p, int lane0, int lanes,
   const dim3 c1(div_up(Cp, kColStrip), 1, z), c2(div_up(Cp, kColStrip), 2, z);
 #define RH_COLSCAN_B(which) RH_LAUNCH(k_colscan_b, (which) == 0 ? c1 : c2, dim3(256), cshm, s, ls, lane0, which, R, Cp, ldh, -1)
   if (lens) {  // x3 + undistort of every lane's frame (rebvio.cpp:43-47), then the first pass on the fp32 result
-    RH_LAUNCH(k_front_end_u8_b, dim3(div_up(R * C, 256), 1, z), dim3(256), 0, s, ls, dyn, lane0, R, C);
+    const dim3 gf(div_up(R * C, 256), 1, z);
+    switch (fmt) {
+#define RH_FE_PX_B(F) \
+  case F: RH_LAUNCH(k_front_end_px_b<F>, gf, dim3(256), 0, s, ls, dyn, lane0, R, C); break;
+      RH_FE_PX_B(px::RGB8) RH_FE_PX_B(px::BGR8) RH_FE_PX_B(px::RGBA8) RH_FE_PX_B(px::BGRA8) RH_FE_PX_B(px::YUYV) RH_FE_PX_B(px::UYVY)
+#undef RH_FE_PX_B
+      default: RH_LAUNCH(k_front_end_u8_b, gf, dim3(256), 0, s, ls, dyn, lane0, R, C);
+    }
     RH_LAUNCH(k_rowscan_b<1>, g1, dim3(256), shm, s, ls, dyn, lane0, 3, R, C, 0, 0, ldw);
+  } else if (fmt != px::GRAY8) {  // the first pass converts every lane's colour / packed-YUV frame itself
+    rowscan_px_attrs();
+    switch (fmt) {
+#define RH_RS_PX_B(F)                                                                                        \
+  case F:                                                                                                    \
+    RH_LAUNCH(k_rowscan_px_b<F>, g1, dim3(256), shm, s, ls, dyn, lane0, R, C, ldw);                            \
+    break;
+      RH_RS_PX_B(px::RGB8) RH_RS_PX_B(px::BGR8) RH_RS_PX_B(px::RGBA8) RH_RS_PX_B(px::BGRA8) RH_RS_PX_B(px::YUYV) RH_RS_PX_B(px::UYVY)
+#undef RH_RS_PX_B
+    }
   } else {
     RH_LAUNCH(k_rowscan_b<0>, g1, dim3(256), shm, s, ls, dyn, lane0, 0, R, C, 0, 0, ldw);
   }

@@ -22,6 +22,7 @@
 #include <limits>
 
 #include "../csrc/hostmath.hpp"
+#include "../csrc/pixel_format.hpp"
 #include "rebvio/util/log.hpp"
 #include "session.hpp"
 
@@ -69,12 +70,13 @@ Rebvio::~Rebvio() {
 
 void Rebvio::imageCallback(rebvio::types::Image&& image) {
   std::lock_guard<std::mutex> guard(image_buffer_mutex_);
-  if (image.data.type() != CV_8UC1) {
-    // not a MONO8 frame: convert and undistort here like the reference does (rebvio.cpp:43-47)
+  const int t = image.data.type();
+  if (t != CV_8UC1 && t != CV_8UC3 && t != CV_8UC4) {
+    // not an 8-bit frame: convert and undistort here like the reference does (rebvio.cpp:43-47)
     cv::Mat img;
     image.data.convertTo(img, CV_FLOAT_PRECISION, 3.0);  // 0..765, matches max_image_value_ (edge_detector.cpp:21)
     image.data = camera_.undistort(img);
-  }  // else: the u8 frame goes to the device as it is; x3 + undistort run there (1 byte/pixel over PCIe instead of 4)
+  }  // else: the u8 frame (MONO8, BGR8 or BGRA8) goes to the device as it is; grey conversion, x3 and undistort run there
   image_buffer_.push(image);
   ++num_images_;
 }
@@ -137,13 +139,25 @@ void Rebvio::dataAcquisitionProcess() {
     }
     if (!edge_image_callbacks_.empty()) {
       // callbacks see the undistorted frame, as in the reference; for a raw u8 frame of a distorting lens it is fetched
-      // from the device front end (only when somebody listens)
-      if (img.data.type() == CV_8UC1 && core_.session()->hasDistortion()) {
+      // from the device front end (only when somebody listens). A colour frame gives what its grey frame would: the device
+      // front end's output with a lens model, else the CV_8UC1 grey frame of the host form of the conversion.
+      const int t = img.data.type();
+      const int fmt = t == CV_8UC3 ? REBVIO_HIP_PX_BGR8 : t == CV_8UC4 ? REBVIO_HIP_PX_BGRA8 : REBVIO_HIP_PX_GRAY8;
+      if (t == CV_8UC1 && core_.session()->hasDistortion()) {
         cv::Mat und(img.data.rows, img.data.cols, CV_32FC1);
         cv::Mat dense = (img.data.step == (size_t)img.data.cols) ? img.data : img.data.clone();
         backend::check("rebvio_hip_front_end_u8",
                        rebvio_hip_front_end_u8(core_.session()->ctx(), dense.ptr<unsigned char>(0), und.ptr<float>(0)));
         img.data = und;
+      } else if (fmt != REBVIO_HIP_PX_GRAY8 && core_.session()->hasDistortion()) {
+        cv::Mat und(img.data.rows, img.data.cols, CV_32FC1);
+        backend::check("rebvio_hip_front_end_px", rebvio_hip_front_end_px(core_.session()->ctx(), img.data.ptr<unsigned char>(0),
+                                                                          img.data.step, fmt, und.ptr<float>(0)));
+        img.data = und;
+      } else if (fmt != REBVIO_HIP_PX_GRAY8) {
+        cv::Mat grey(img.data.rows, img.data.cols, CV_8UC1);
+        rh::px::to_grey(fmt, img.data.ptr<unsigned char>(0), img.data.step, img.data.rows, img.data.cols, grey.ptr<unsigned char>(0));
+        img.data = grey;
       }
       for (auto& cb : edge_image_callbacks_) cb(img.data, edge_map);
     }

@@ -1,8 +1,10 @@
 // rebvio_replay: run rebvio::Rebvio over a dataset on disk and write the odometry in the reference's regression format.
-//   rebvio_replay --asl <mav0 dir> --euroc --out odometry.txt [--first N --count M]
+//   rebvio_replay --asl <mav0 dir> --euroc --out odometry.txt [--first N --count M] [--colour]
 //   rebvio_replay --raw frames.u8 --size W H [--imu imu.bin] [--dt 50000] [--camera fm cx cy [k1 k2 p1 p2 k3]] --out odometry.txt
 // --euroc selects the reference's built-in EuRoC MH cam0 model (camera.hpp:25-45). With the real MH_03 data
 // (first = the frame at 15 s) this replays what ros_rebvio/test/test_ros_rebvio.cpp checks against its golden file.
+// --colour: RGB(A) PNG frames go to rebvio::Rebvio as CV_8UC3 / CV_8UC4 (OpenCV's channel order) and are converted to grey on the
+// device, instead of to luma while they are read; the odometry is the same.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -19,7 +21,7 @@ int main(int argc, char** argv) {
   int W = 0, H = 0;
   size_t first = 0, count = (size_t)-1;
   uint64_t dt = 50000;
-  bool euroc = false;
+  bool euroc = false, colour = false;
   float cam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   for (int i = 1; i < argc; ++i) {
@@ -40,6 +42,7 @@ int main(int argc, char** argv) {
     else if (a == "--count") count = (size_t)std::atoll(next());
     else if (a == "--dt") dt = (uint64_t)std::atoll(next());
     else if (a == "--euroc") euroc = true;
+    else if (a == "--colour") colour = true;
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
     else if (a == "--camera") {
@@ -52,12 +55,12 @@ int main(int argc, char** argv) {
     }
   }
   if ((asl.empty() == raw.empty()) || out.empty()) {
-    std::fprintf(stderr, "usage: %s (--asl mav0 | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] --out file\n", argv[0]);
+    std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] --out file\n", argv[0]);
     return 2;
   }
   try {
     std::unique_ptr<rebvio::io::StreamSource> src;
-    if (!asl.empty()) src.reset(new rebvio::io::EurocReader(asl));
+    if (!asl.empty()) src.reset(new rebvio::io::EurocReader(asl, "cam0", "imu0", colour));
     else src.reset(new rebvio::io::RawReader(raw, H, W, 0, dt, imu));
     if (src->numFrames() == 0) {
       std::fprintf(stderr, "no frames\n");

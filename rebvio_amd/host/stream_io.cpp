@@ -4,6 +4,8 @@
 
 #include <zlib.h>
 
+#include "../csrc/pixel_format.hpp"
+
 #include <algorithm>
 #include <cstring>
 #include <fstream>
@@ -45,12 +47,17 @@ std::vector<std::string> csv_fields(const std::string& line) {
 }
 }  // namespace
 
-cv::Mat readPngGray(const std::string& path) {
+namespace {
+// Decodes a PNG file: W, H and the colour type are set once the header is read, then begin(W, H) is called, then
+// row(y, bytes, bytes_per_pixel) for every image row with its unfiltered bytes.
+template <class BeginFn, class RowFn>
+void decodePng(const std::string& path, uint32_t& W, uint32_t& H, int& ctype, BeginFn begin, RowFn row) {
   const std::vector<unsigned char> file = slurp(path);
   static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
   if (file.size() < 8 + 25 || std::memcmp(file.data(), sig, 8) != 0) bad(path + ": not a PNG file");
-  uint32_t W = 0, H = 0;
-  int depth = 0, ctype = 0, interlace = 0;
+  W = 0, H = 0;
+  ctype = 0;
+  int depth = 0, interlace = 0;
   std::vector<unsigned char> idat;
   size_t pos = 8;
   bool end = false;
@@ -89,7 +96,7 @@ cv::Mat readPngGray(const std::string& path) {
   uLongf out_len = (uLongf)raw.size();
   if (uncompress(raw.data(), &out_len, idat.data(), (uLong)idat.size()) != Z_OK || out_len != raw.size()) bad(path + ": inflate failed");
   std::vector<unsigned char> prev(stride, 0), cur(stride);
-  cv::Mat img((int)H, (int)W, CV_8UC1);
+  begin(W, H);
   for (uint32_t y = 0; y < H; ++y) {
     const unsigned char ft = raw[(stride + 1) * y];
     const unsigned char* in = &raw[(stride + 1) * y + 1];
@@ -106,21 +113,56 @@ cv::Mat readPngGray(const std::string& path) {
       }
       cur[i] = (unsigned char)v;
     }
-    unsigned char* o = img.ptr<unsigned char>((int)y);
-    for (uint32_t x = 0; x < W; ++x) {
-      const unsigned char* px = &cur[(size_t)x * bpp];
-      if (ctype == 0 || ctype == 4) {
-        o[x] = px[0];  // 16-bit grey: most significant byte
-      } else {          // RGB -> luma with the fixed-point weights of cv::cvtColor(RGB2GRAY): (R*4899 + G*9617 + B*1868 + 8192) >> 14
-        o[x] = (unsigned char)((px[0] * 4899 + px[1] * 9617 + px[2] * 1868 + 8192) >> 14);
-      }
-    }
+    row(y, cur.data(), bpp);
     prev.swap(cur);
   }
+}
+}  // namespace
+
+cv::Mat readPngGray(const std::string& path) {
+  uint32_t W, H;
+  int ctype;
+  cv::Mat img;
+  decodePng(path, W, H, ctype, [&](uint32_t w, uint32_t h) { img.create((int)h, (int)w, CV_8UC1); },
+            [&](uint32_t y, const unsigned char* row, size_t bpp) {
+              unsigned char* o = img.ptr<unsigned char>((int)y);
+              for (uint32_t x = 0; x < W; ++x) {
+                const unsigned char* px = &row[(size_t)x * bpp];
+                if (ctype == 0 || ctype == 4)
+                  o[x] = px[0];  // 16-bit grey: most significant byte
+                else             // RGB(A) -> luma with the fixed-point weights of cv::cvtColor(RGB2GRAY)
+                  o[x] = rh::px::grey_at<rh::px::RGB8>(px, 0);
+              }
+            });
   return img;
 }
 
-EurocReader::EurocReader(const std::string& mav0, const std::string& cam, const std::string& imu) {
+PngPixels readPngPixels(const std::string& path, bool opencv_order) {
+  uint32_t W, H;
+  int ctype;
+  PngPixels out;
+  decodePng(path, W, H, ctype,
+            [&](uint32_t w, uint32_t h) {
+              const int ch = (ctype == 2) ? 3 : (ctype == 6) ? 4 : 1;
+              out.data.create((int)h, (int)w, ch == 3 ? CV_8UC3 : ch == 4 ? CV_8UC4 : CV_8UC1);
+              out.format = ch == 3 ? (opencv_order ? REBVIO_HIP_PX_BGR8 : REBVIO_HIP_PX_RGB8)
+                                   : ch == 4 ? (opencv_order ? REBVIO_HIP_PX_BGRA8 : REBVIO_HIP_PX_RGBA8) : REBVIO_HIP_PX_GRAY8;
+            },
+            [&](uint32_t y, const unsigned char* row, size_t bpp) {
+              unsigned char* o = out.data.ptr<unsigned char>((int)y);
+              if (ctype == 2 || ctype == 6) {
+                const size_t ch = ctype == 2 ? 3 : 4;
+                std::memcpy(o, row, (size_t)W * ch);
+                if (opencv_order)
+                  for (uint32_t x = 0; x < W; ++x) std::swap(o[(size_t)x * ch], o[(size_t)x * ch + 2]);
+              } else {
+                for (uint32_t x = 0; x < W; ++x) o[x] = row[(size_t)x * bpp];  // grey + alpha: grey; 16-bit grey: most significant byte
+              }
+            });
+  return out;
+}
+
+EurocReader::EurocReader(const std::string& mav0, const std::string& cam, const std::string& imu, bool colour) : colour_(colour) {
   {
     const std::string dir = mav0 + "/" + cam;
     std::ifstream f(dir + "/data.csv");
