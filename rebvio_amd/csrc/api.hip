@@ -148,7 +148,7 @@ struct Profiler {
   }
 };
 Profiler g_prof;
-// The open bracket belongs to the launching THREAD (the caller thread and the detect worker launch concurrently).
+// The open bracket belongs to the launching THREAD (a batch's caller thread and its detect worker launch concurrently).
 struct ProfOpen {
   int group_depth = 0;  // inside prof_group_begin/end the individual launches are not bracketed again
   int count = 1;
@@ -228,7 +228,7 @@ struct rebvio_hip_map {
   uint64_t release_seq = 0;  // order of release (pool reuse is oldest-first)
   bool df_built = false;
   bool raster_order = false;  // keylines + row_start as detection left them (false after map_upload)
-  std::atomic<int> enqueued{1};  // 0 while the detect worker still has to record `ready` (streaming driver)
+  std::atomic<int> enqueued{1};  // 0 while the batch's detect worker still has to record `ready`
   bool pre_rotated = false;  // the next pair's first rotateKeylines (+ histogram) was already applied by the fused B-chain
   int n_host = -1;
   float thr_host = -1.0f;
@@ -239,6 +239,35 @@ struct rebvio_hip_map {
   hm::M3 pre_R{};           // ... with this rotation (per-pair API: checked against the prior the next _begin is given)
   int tab_idx = -1;         // entry of this map in its lane's device map table (batch driver)
   MapDev canon{};           // ... as uploaded there (the live `d` differs from it by the ping-pong swaps only)
+};
+
+// A finished pair's record as the caller gets it.
+struct PairRec {
+  rebvio_hip_pair_out out;
+  int keylines;
+};
+
+// What the streaming driver (one lane) and a batch (its lanes, in lock-step) share from queueing a step's pairs on the track stream
+// to handing their records to the caller. A step holds one pair per lane; the queue never holds more than kPairSlots - 1 steps
+// (the result slot of step k is reused by step k + kPairSlots), so it is a fixed ring: no heap allocation per step.
+struct PairQueue {
+  struct Step {                     // a step whose kernels are queued and whose records have not been read yet
+    rebvio_hip_map* nm[kMaxLanes];  // each lane's new map
+    uint32_t seq = 0;               // the step's sequence stamp (all lanes)
+    int slot = -1;
+    int ev_slot = -1;               // the slot whose event stands for this step's completion (its group's last step)
+  };
+  Step ring[kPairSlots];
+  int head = 0, count = 0;
+  Step& operator[](int i) { return ring[(head + i) % kPairSlots]; }
+  void push_back(const Step& st) { ring[(head + count++) % kPairSlots] = st; }
+  void pop_front() {
+    head = (head + 1) % kPairSlots;
+    --count;
+  }
+  std::deque<PairRec> done;          // records waiting for the caller: one per lane and step, in lane order
+  hipEvent_t slot_ev[kPairSlots]{};  // recorded behind a group's last kernel
+  double t_wait = 0;                 // REBVIO_HIP_DEBUG: host time spent waiting for result slots (us)
 };
 
 struct rebvio_hip_ctx {
@@ -277,7 +306,6 @@ struct rebvio_hip_ctx {
   void* pin[kPin]{};
   hipEvent_t pin_ev[kPin]{};
   bool pin_used[kPin]{};
-  std::atomic<int> pin_staged[kPin]{};  // 1: the slot holds a frame whose host-to-device copy the detect worker has not queued yet
   uint64_t pin_next = 0;
   int2* undist_map = nullptr;      // fixed-point source coordinates (null: no lens distortion, front end = x3 only)
   float* undist_img[kDetPar]{};    // undistorted fp32 frame, buffered like dog2 / mag2
@@ -328,7 +356,6 @@ struct rebvio_hip_ctx {
   // host reads a pair's records kSlots - 1 pairs late at most.
   static constexpr int kSlots = kPairSlots;
   PairSlot* slot[kSlots]{};    // pinned: LM state + map state records, written by the pair's first kernel
-  hipEvent_t slot_ev[kSlots]{};  // recorded behind the pair's last kernel
   GlueRec* rec[kSlots]{};      // pinned: what the device glue of the pair reports
   GlueDev* glue_dev = nullptr;    // [kSlots] second-half inputs left by the device glue for the kernels behind it
   GlueStage* glue_stage = nullptr;  // [kSlots] host records on their way out: written by the glue, forwarded by the directedMatch launch
@@ -345,28 +372,15 @@ struct rebvio_hip_ctx {
   uint32_t stamp_seq = 0;         // last value handed out
   uint32_t last_stamp = 0;        // stamp of the pair enqueue_pair_lm queued last
   bool forge_stamp = false;       // rebvio_hip_test_forge_record_stamp: the next pair's kernels are handed a wrong stamp
-  struct InFlight {               // a pair whose kernels are queued and whose record has not been read yet
-    rebvio_hip_map* nm = nullptr;
-    uint32_t seq = 0;             // its sequence stamp
-    int slot = -1;
-    int ev_slot = -1;             // the slot whose event stands for this pair's completion (its group's last pair)
-    float frame_dt = 0.f;
-  };
-  struct Done {                   // a complete record waiting to be handed to the caller
-    rebvio_hip_pair_out out;
-    int keylines;
-  };
   // Pool bookkeeping (in_use, has_done / done / done_ref, release_seq, release_counter, df_map, the pool vector) is written by
   // whoever releases a map - the tracking thread, or any thread that lets go of an EdgeMap (an edge-image consumer,
   // ros_rebvio.cpp:32-51) - and read by the acquisition thread: one mutex around both sides, so that a map seen as free is seen
   // with the event its next user has to wait for.
   std::mutex pool_mu;
   std::vector<rebvio_hip_map*> frames;  // detected maps not yet consumed as "old"
-  std::deque<InFlight> inflight;
-  std::deque<Done> done;
+  PairQueue q;                          // pairs in flight and records waiting for the caller (streaming driver)
   uint64_t pair_seq = 0;
-  // detect-enqueue worker (the reference's data-acquisition thread, rebvio.cpp:28): launches the detect kernels so
-  // that the caller thread's launches (track chains) and the detect launches proceed in parallel on the host
+  // one frame's detection: its map and servo-state ring slots (detect_prepare), launched by detect_launch
   struct DetJob {
     rebvio_hip_map* m;
     const void* img;
@@ -378,27 +392,17 @@ struct rebvio_hip_ctx {
     size_t pin_bytes = 0;
     int fmt = 0;            // pixel format of a u8 frame (pixel_format.hpp)
   };
-  std::thread det_thread;
   std::mutex det_mu;
-  std::condition_variable det_cv;
-  std::deque<DetJob> det_jobs;
-  std::atomic<int> det_pending{0};
-  bool det_stop = false;
-  std::string det_error;
+  std::string det_error;  // a detection failed half way (detect_failed): every later detect / push reports -8 with it
   // host-side phase timing of the streaming driver (printed by flush when REBVIO_HIP_DEBUG is set)
-  double t_detect_enq = 0, t_wait = 0, t_enq = 0, t_queued = 0;
-  std::atomic<uint64_t> t_worker_ns{0}, t_worker_n{0};  // the detect worker's launches (one job = one frame)
+  double t_detect_enq = 0, t_enq = 0, t_queued = 0;
+  double t_det_launch = 0;  // the detect launches alone (us, one per frame) ...
+  uint64_t t_det_n = 0;     // ... over this many frames
   bool dbg = false;
   // host shadow of the information matrix W_Bg the DEVICE glue works on (streaming driver, glue_params_pre)
   hm::M3 wbg_shadow{};
   bool wbg_shadow_valid = false;
-  bool fuse_dog = true;  // REBVIO_HIP_FUSE_DOG=0: k_dog_mag + k_keyline_flag instead of k_keyline_flag_ii
   bool gyro_pre_on = true;  // REBVIO_HIP_GYRO_PRE=0: the device forms the gyroBiasCorrection matrices itself
-  // REBVIO_HIP_DETECT_WORKER=1: a worker thread launches the streaming driver's detect kernels. Off by default since round 3: the
-  // runtime calls of two threads largely serialise AND slow each other down (detect launches 36 us per frame alone, 65 us beside
-  // the caller's pair launches), so a burst of pushes - the driver's 20-frame window - ran at 10.4 k frames/s with the worker and
-  // runs at 13.0 k with the caller launching everything itself (47 + 21 us of host time per 74 us frame).
-  bool det_worker = false;
   uint64_t t_frames = 0;
   bool owns_streams = true;  // false for the lanes of a batch (rebvio_hip_batch_*)
   rebvio_hip_map* bf_map[2] = {nullptr, nullptr};  // new map of the pair whose counters result slot r will report
@@ -414,24 +418,29 @@ struct rebvio_hip_ctx {
 };
 
 namespace {
-void release_map(rebvio_hip_map* m, hipEvent_t done_ref);
+void release_map(rebvio_hip_map* m, hipEvent_t done_ref = nullptr, bool record_done = true);
 
 // A map handle whose context has been destroyed: every entry point that takes a map alone answers with this.
 inline bool map_dead(const rebvio_hip_map* m) { return !m || !m->life || m->life->dead.load(std::memory_order_acquire); }
-// Holds the life block (shared) for the rest of the calling function: a rebvio_hip_destroy on another thread waits until the
-// entry has returned instead of freeing the context under it (the check alone would leave a window between test and use).
-#define MAP_ALIVE_OR(m, ret)                                                   \
-  const std::shared_ptr<LifeBlock> life_hold_ = (m) ? (m)->life : nullptr;     \
-  std::shared_lock<std::shared_mutex> life_lock_;                              \
-  if (life_hold_) life_lock_ = std::shared_lock<std::shared_mutex>(life_hold_->mu); \
-  do {                                                                         \
-    if (map_dead(m)) {                                                         \
-      g_err = "the map's context has been destroyed (rebvio_hip_destroy)";     \
-      return ret;                                                              \
-    }                                                                          \
-  } while (0)
+// Holds the life block (shared) for as long as it lives - declared at the top of an entry, for the rest of it: a rebvio_hip_destroy
+// on another thread waits until the entry has returned instead of freeing the context under it (the check alone would leave a
+// window between test and use). dead(): the context is gone already (g_err says so); the entry returns at once.
+class MapAlive {
+ public:
+  explicit MapAlive(const rebvio_hip_map* m) : hold_(m ? m->life : nullptr) {
+    if (hold_) lock_ = std::shared_lock<std::shared_mutex>(hold_->mu);
+    dead_ = map_dead(m);
+    if (dead_) g_err = "the map's context has been destroyed (rebvio_hip_destroy)";
+  }
+  bool dead() const { return dead_; }
 
-// events of a map may only be waited on once the detect worker has recorded them
+ private:
+  std::shared_ptr<LifeBlock> hold_;
+  std::shared_lock<std::shared_mutex> lock_;
+  bool dead_;
+};
+
+// events of a map may only be waited on once the batch's detect worker has recorded them
 inline void wait_enqueued(rebvio_hip_map* m) {
   while (!m->enqueued.load(std::memory_order_acquire)) std::this_thread::yield();
 }
@@ -616,7 +625,6 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
   if (j.pin_slot >= 0) {  // host frame: pinned slot -> device staging frame, read by this stream's own kernels only
     launch_copy_from_pinned(c->s_det, c->pin[j.pin_slot], const_cast<void*>(j.img), j.pin_bytes);
     HIPCHK(hipEventRecord(c->pin_ev[j.pin_slot], c->s_det));
-    c->pin_staged[j.pin_slot].store(0, std::memory_order_release);
   }
   // scans of this frame (s_det); its DoG / gradient buffers were last read by the candidate kernel two frames ago
   if (c->prev_ready[b]) HIPCHK(hipStreamWaitEvent(c->s_det, c->prev_ready[b], 0));
@@ -636,21 +644,19 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
   // the DoG / gradient kernel run at the head of the keyline stream.
   // Their inputs sb.a[] are then read while the scan stream already works on the next frame, hence the pair per parity;
   // the frame after next waits for this frame's `ready` event (prev_ready[b]) above.
-  launch_scale_space(c->s_det, c->K, img, is_u8, sb, c->widths, db.rowcount, 1, false, fmt);
+  launch_scale_space(c->s_det, c->K, img, is_u8, sb, c->widths, db.rowcount, 1, fmt);
   HIPCHK(hipEventRecord(c->ev_scan[b], c->s_det));
   // keyline extraction + chaining (s_key), overlapping the next frame's scans
   HIPCHK(hipStreamWaitEvent(c->s_key, c->ev_scan[b], 0));
-  launch_scale_space(c->s_key, c->K, img, is_u8, sb, c->widths, db.rowcount, 2, c->fuse_dog);
+  launch_scale_space(c->s_key, c->K, img, is_u8, sb, c->widths, db.rowcount, 2);
   if (m->has_done) HIPCHK(hipStreamWaitEvent(c->s_key, m->done_ref ? m->done_ref : m->done, 0));
-  const int fw[2] = {c->widths[0][2], c->widths[1][2]};
-  launch_keylines(c->s_key, c->K, sb, db, m->d, j.det_in, j.det_out, j.prev_st, c->fuse_dog ? fw : nullptr);
+  launch_keylines(c->s_key, c->K, sb, db, m->d, j.det_in, j.det_out, j.prev_st, c->widths);
   HIPCHK(hipGetLastError());
   // distance field of this map, behind its keylines on the same stream (stream order is the dependency)
   launch_df_build(c->s_key, c->K, m->d, j.det_out, true);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(m->ready, c->s_key));
   c->prev_ready[b] = m->ready;  // (pooled maps and their events live as long as the context)
-  m->enqueued.store(1, std::memory_order_release);
   return 0;
 }
 
@@ -674,103 +680,46 @@ int detect_prepare(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t t
 }
 
 // A detect_launch that failed half way: the frame's map has been taken, the servo ring and last_detected have advanced and some of
-// its kernels may be queued. The map goes back to the pool, a staged host frame is dropped, and the context is marked failed
-// (every later push / detect reports -8 with this error) - the detector's state is one frame out of step and cannot be trusted.
+// its kernels may be queued. The map goes back to the pool and the context is marked failed (every later push / detect reports
+// -8 with this error) - the detector's state is one frame out of step and cannot be trusted.
 void detect_failed(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& job) {
   {
     std::lock_guard<std::mutex> lk(c->det_mu);
     if (c->det_error.empty()) c->det_error = g_err.empty() ? std::string("detect launch failed") : g_err;
   }
-  if (job.pin_slot >= 0) c->pin_staged[job.pin_slot].store(0, std::memory_order_release);
-  job.m->enqueued.store(1, std::memory_order_release);
   release_map(job.m, nullptr);
 }
 
-int detect_common(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_map** out, int fmt = 0) {
+int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, size_t row_bytes, int* slot_out, size_t* bytes_out);
+
+// Detection of one frame, launched by the caller's thread. (Handing the launches to a detect worker thread was measured twice
+// and removed: with rebvio::Rebvio in round 2 the acquisition thread's time per frame dropped and the fusion thread's own launches
+// slowed down by as much - runtime calls of different threads largely serialise; for the streaming driver in round 3 a burst of
+// pushes ran at 10.2-10.7 k frames/s with the worker and at 12.9-13.0 k without it)
+// img_dev: the frame in device memory, or (host != null) the device staging frame that a host frame is copied to. A host frame
+// (rows of row_bytes, pitch_bytes apart) goes through the pinned ring; detect_launch queues its copy ahead of the scans, on the
+// scan stream (stream order is reuse order). fmt: pixel format of a u8 frame (pixel_format.hpp).
+int detect(rebvio_hip_ctx* c, const void* img_dev, int is_u8, int fmt, uint64_t ts, rebvio_hip_map** out, const void* host = nullptr,
+           size_t pitch_bytes = 0, size_t row_bytes = 0) {
   {
     std::lock_guard<std::mutex> lk(c->det_mu);
     if (!c->det_error.empty()) return fail_msg(c->det_error.c_str(), -8);
   }
   rebvio_hip_ctx::DetJob job;
-  int rc = detect_prepare(c, img_dev, is_u8, ts, &job, fmt);
+  int rc = host ? stage_host_frame(c, host, pitch_bytes, row_bytes, &job.pin_slot, &job.pin_bytes) : 0;
   if (rc) return rc;
-  // a queued asynchronous detect must be launched first (stream order = frame order)
-  while (c->det_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
+  rc = detect_prepare(c, img_dev, is_u8, ts, &job, fmt);
+  if (rc) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
   rc = detect_launch(c, job);
+  if (c->dbg) {
+    c->t_det_launch += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    c->t_det_n++;
+  }
   if (rc) {
     detect_failed(c, job);
     return rc;
   }
-  *out = job.m;
-  return 0;
-}
-
-void det_worker_main(rebvio_hip_ctx* c) {
-  (void)hipSetDevice(c->device);
-  for (;;) {
-    rebvio_hip_ctx::DetJob j;
-    {
-      std::unique_lock<std::mutex> lk(c->det_mu);
-      c->det_cv.wait(lk, [&] { return c->det_stop || !c->det_jobs.empty(); });
-      if (c->det_jobs.empty()) return;
-      j = c->det_jobs.front();
-      c->det_jobs.pop_front();
-    }
-    const auto tw0 = std::chrono::steady_clock::now();
-    if (detect_launch(c, j) != 0) {
-      std::lock_guard<std::mutex> lk(c->det_mu);
-      c->det_error = g_err;
-      j.m->enqueued.store(1, std::memory_order_release);
-    }
-    if (c->dbg) {
-      c->t_worker_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tw0).count(),
-                               std::memory_order_relaxed);
-      c->t_worker_n.fetch_add(1, std::memory_order_relaxed);
-    }
-    c->det_pending.fetch_sub(1, std::memory_order_release);
-  }
-}
-
-int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, size_t row_bytes, int* slot_out, size_t* bytes_out);
-void* u8_staging(rebvio_hip_ctx* c, int fmt);
-// host_u8 != null: a u8 frame (pixel format fmt) in host memory, staged through the pinned ring; the worker queues its copy to the
-// device staging frame ahead of the scans (same stream: stream order is reuse order)
-int detect_async(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_map** out, const uint8_t* host_u8 = nullptr,
-                 size_t host_pitch = 0, int fmt = 0) {
-  rebvio_hip_ctx::DetJob job;
-  if (host_u8) {
-    const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
-    const int rcs = stage_host_frame(c, host_u8, host_pitch ? host_pitch : rowb, rowb, &job.pin_slot, &job.pin_bytes);
-    if (rcs) return rcs;
-    img_dev = u8_staging(c, fmt);
-  }
-  int rc = detect_prepare(c, img_dev, is_u8, ts, &job, fmt);
-  if (rc && job.pin_slot >= 0) c->pin_staged[job.pin_slot].store(0, std::memory_order_release);
-  if (rc) return rc;
-  if (!c->det_worker) {  // REBVIO_HIP_DETECT_WORKER=0: the caller launches the detect kernels itself (one thread issues every runtime call)
-    const auto tw0 = std::chrono::steady_clock::now();
-    rc = detect_launch(c, job);
-    if (c->dbg) {
-      c->t_worker_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tw0).count(),
-                               std::memory_order_relaxed);
-      c->t_worker_n.fetch_add(1, std::memory_order_relaxed);
-    }
-    if (rc) {
-      detect_failed(c, job);
-      return rc;
-    }
-    job.m->enqueued.store(1, std::memory_order_release);
-    *out = job.m;
-    return 0;
-  }
-  if (!c->det_thread.joinable()) c->det_thread = std::thread(det_worker_main, c);
-  job.m->enqueued.store(0, std::memory_order_relaxed);
-  c->det_pending.fetch_add(1, std::memory_order_release);
-  {
-    std::lock_guard<std::mutex> lk(c->det_mu);
-    c->det_jobs.push_back(job);
-  }
-  c->det_cv.notify_one();
   *out = job.m;
   return 0;
 }
@@ -841,17 +790,20 @@ void lm_to_out(const LmState& s, float vel[3], float Rvel[9], float* F, int* mas
   if (srm) *srm = s.sigma_rho_min;
 }
 
+// Start state of minimizeVel from vel0: the constant zero state, or vel0 uploaded into c->lm[0] on the track stream.
+LmState* start_lm_state(rebvio_hip_ctx* c, const float vel0[3]) {
+  if (vel0[0] == 0.f && vel0[1] == 0.f && vel0[2] == 0.f) return c->lm_zero;
+  LmState init;
+  std::memset(&init, 0, sizeof(init));
+  for (int i = 0; i < 3; ++i) init.vel[i] = vel0[i];
+  c->h_lm[1] = init;
+  (void)hipMemcpyAsync(c->lm, &c->h_lm[1], sizeof(LmState), hipMemcpyHostToDevice, c->s_trk);
+  return c->lm;
+}
+
 // minimizeVel on the track stream: histogram must already be in c->hist and residuals zeroed.
 void enqueue_lm_chain(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map* nm, const float vel0[3]) {
-  LmState* first = c->lm_zero;
-  if (vel0[0] != 0.f || vel0[1] != 0.f || vel0[2] != 0.f) {
-    LmState init;
-    std::memset(&init, 0, sizeof(init));
-    for (int i = 0; i < 3; ++i) init.vel[i] = vel0[i];
-    c->h_lm[1] = init;
-    (void)hipMemcpyAsync(c->lm, &c->h_lm[1], sizeof(LmState), hipMemcpyHostToDevice, c->s_trk);
-    first = c->lm;
-  }
+  LmState* first = start_lm_state(c, vel0);
   const int calls = (int)c->P.iterations + 1;
   const size_t cs = part_call_stride(c);
   prof_group_begin(c->s_trk, "k_try_vel", calls);
@@ -929,6 +881,29 @@ int poll_pair_records(rebvio_hip_ctx* c, const PairSlot* slot, uint32_t seq) {
   return 0;
 }
 
+// 0, or -9 once a persistent LM kernel of lane c has set its sticky time-out flag: the error names what the kernel reports and
+// the other users of the device's persistent kernels (residency_describe; owner: the context or batch that launched it).
+int lm_timed_out(const rebvio_hip_ctx* c, int device, const void* owner, const char* who) {
+  if (!*c->lm_bar_err) return 0;
+  const int* e = c->lm_bar_err;
+  char msg[320];
+  std::snprintf(msg, sizeof(msg),
+                "%spersistent LM kernel: record exchange timed out (workgroup %d/%d thread %d waited for tag %u, last saw tag %u; "
+                "tags issued so far %u); ",
+                who, e[1], e[6], e[2], (unsigned)e[3], (unsigned)e[4], c->lm_tag_base);
+  return fail_msg((std::string(msg) + residency_describe(device, owner)).c_str(), -9);
+}
+
+// The exchange tags one persistent LM launch of lane c takes (the speculative kernel numbers repeated evaluations in a second
+// range). Tags must stay unique and non-zero: before the sequence could wrap it restarts on clean exchange words.
+void advance_lm_tags(rebvio_hip_ctx* c, int calls) {
+  c->lm_tag_base += 2u * ((unsigned)calls + 1u);
+  if (c->lm_tag_base > 0xFFFFFF00u) {
+    (void)hipMemsetAsync(c->lm_xch, 0, lm_xch_words(c->maxblocks) * sizeof(unsigned long long), c->s_trk);
+    c->lm_tag_base = 0;
+  }
+}
+
 int enqueue_pair_lm(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map* nm, const float vel0[3], PairSlot* slot, float* xrv_dst,
                     const GlueArgs& ga_in) {
   const int calls = (int)c->P.iterations + 1;
@@ -946,28 +921,15 @@ int enqueue_pair_lm(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map* nm, c
     if (ga.lm) launch_pair_glue(c->s_trk, nm->d, ga);
     return 0;
   }
-  if (*c->lm_bar_err) {
-    const int* e = c->lm_bar_err;
-    char msg[256];
-    std::snprintf(msg, sizeof(msg),
-                  "persistent LM kernel: record exchange timed out (workgroup %d/%d thread %d waited for tag %u, last saw tag %u; "
-                  "tags issued so far %u); ",
-                  e[1], e[6], e[2], (unsigned)e[3], (unsigned)e[4], c->lm_tag_base);
-    return fail_msg((std::string(msg) + residency_describe(c->device, c)).c_str(), -9);
+  {
+    const int rc = lm_timed_out(c, c->device, c, "");
+    if (rc) return rc;
   }
   if (!c->residency_registered) {  // (the lane contexts of a batch never come here: the batch registers for them)
     residency_add(c->device, c, (c->K.kmax + c->lm_threads - 1) / c->lm_threads);
     c->residency_registered = true;
   }
-  LmState* first = c->lm_zero;
-  if (vel0[0] != 0.f || vel0[1] != 0.f || vel0[2] != 0.f) {
-    LmState init;
-    std::memset(&init, 0, sizeof(init));
-    for (int i = 0; i < 3; ++i) init.vel[i] = vel0[i];
-    c->h_lm[1] = init;
-    (void)hipMemcpyAsync(c->lm, &c->h_lm[1], sizeof(LmState), hipMemcpyHostToDevice, c->s_trk);
-    first = c->lm;
-  }
+  LmState* first = start_lm_state(c, vel0);
   if (c->lm_stamps && c->lm_stamps[0]) {  // stamps of the previous launch (the caller has synchronised on its slot since)
     // the buffer may be half rewritten by a launch that is already running (streaming driver): take a snapshot and use it
     // only if it is monotonic and spans less than a millisecond
@@ -986,11 +948,7 @@ int enqueue_pair_lm(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map* nm, c
   }
   launch_lm_chain(c->s_trk, c->K, om->d, nm->d, calls, lm_kernel_choice(c), first, c->lm + calls + 1, c->lm_xch, c->lm_tag_base, c->lm_bar_err, c->hist,
                   xrv_dst, slot, c->hist, c->lm_stamps, c->lm_threads, ga);
-  c->lm_tag_base += 2u * ((unsigned)calls + 1u);  // (the speculative kernel numbers repeated evaluations in a second range)
-  if (c->lm_tag_base > 0xFFFFFF00u) {  // tags must stay unique and non-zero: restart the sequence on clean exchange words
-    (void)hipMemsetAsync(c->lm_xch, 0, lm_xch_words(c->maxblocks) * sizeof(unsigned long long), c->s_trk);
-    c->lm_tag_base = 0;
-  }
+  advance_lm_tags(c, calls);
   return 0;
 }
 
@@ -998,8 +956,8 @@ int enqueue_pair_lm(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map* nm, c
 // memory is staged inside the runtime, which stays busy for the whole transfer and stalls the launches of the tracking
 // thread of rebvio::Rebvio (measured: second half of the pair step 215 us -> 47 us); it also must not outlive the caller's
 // buffer. The device staging frames are read by the scan stream's own kernels only, so stream order is reuse order.
-// Host half (caller's thread): frame -> pinned ring slot. The copy to the device and the reuse event are queued by whoever
-// launches the frame's detection (detect_launch), in stream order with its kernels.
+// Host half: frame -> pinned ring slot. The copy to the device and the slot's reuse event are queued by the frame's
+// detect_launch, in the same call, in stream order with its kernels.
 int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, size_t row_bytes, int* slot_out, size_t* bytes_out) {
   if (!c->pin[0]) {
     for (int i = 0; i < rebvio_hip_ctx::kPin; ++i) {
@@ -1008,7 +966,6 @@ int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, siz
     }
   }
   const int ps = (int)(c->pin_next++ % rebvio_hip_ctx::kPin);
-  while (c->pin_staged[ps].load(std::memory_order_acquire)) std::this_thread::yield();  // the worker is kPin frames behind
   if (c->pin_used[ps]) HIPCHK(hipEventSynchronize(c->pin_ev[ps]));  // its previous copy has left the slot
   uint8_t* dst = static_cast<uint8_t*>(c->pin[ps]);
   const uint8_t* src = static_cast<const uint8_t*>(img);
@@ -1017,7 +974,6 @@ int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, siz
   else
     for (int r = 0; r < c->P.rows; ++r) std::memcpy(dst + (size_t)r * row_bytes, src + (size_t)r * pitch_bytes, row_bytes);
   c->pin_used[ps] = true;
-  c->pin_staged[ps].store(1, std::memory_order_release);
   *slot_out = ps;
   *bytes_out = (size_t)c->P.rows * row_bytes;
   return 0;
@@ -1052,30 +1008,6 @@ int check_px(const rebvio_hip_ctx* c, const char* who, const void* frame, int fm
   return 0;
 }
 
-// Detection of a host frame: staged through the pinned ring and launched by the caller. (Handing the launch to the context's
-// detect worker was measured with rebvio::Rebvio in round 2: the acquisition thread's time per frame dropped, the fusion
-// thread's own launches slowed down by as much - runtime calls of different threads largely serialise - no gain, removed.)
-int detect_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, size_t row_bytes, void* dst_dev, int is_u8, uint64_t ts,
-                      rebvio_hip_map** out, int fmt = 0) {
-  {
-    std::lock_guard<std::mutex> lk(c->det_mu);
-    if (!c->det_error.empty()) return fail_msg(c->det_error.c_str(), -8);
-  }
-  rebvio_hip_ctx::DetJob job;
-  int rc = stage_host_frame(c, img, pitch_bytes, row_bytes, &job.pin_slot, &job.pin_bytes);
-  if (rc) return rc;
-  rc = detect_prepare(c, dst_dev, is_u8, ts, &job, fmt);
-  if (rc) {
-    c->pin_staged[job.pin_slot].store(0, std::memory_order_release);
-    return rc;
-  }
-  while (c->det_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();  // (a streaming push's detection goes first)
-  rc = detect_launch(c, job);
-  if (rc) return rc;
-  *out = job.m;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1104,7 +1036,7 @@ void rebvio_hip_default_params(rebvio_hip_params* p, int rows, int cols) {
 void rebvio_hip_reset_state(rebvio_hip_ctx* c) {
   // While the streaming driver has pairs in flight the filter state lives on the device: they are completed first (their records
   // stay available through rebvio_hip_next_record), so that no harvested record writes the old state back over the reset one.
-  if (!c->inflight.empty() || !c->frames.empty()) (void)rebvio_hip_flush(c);
+  if (c->q.count || !c->frames.empty()) (void)rebvio_hip_flush(c);
   c->wbg_shadow_valid = false;  // (the next stream's first pair uploads this state and starts the shadow from it)
   c->Bg[0] = c->Bg[1] = c->Bg[2] = 0.f;
   c->RGBias = hm::identity3();
@@ -1121,7 +1053,7 @@ int rebvio_hip_get_gyro_state(rebvio_hip_ctx* c, float Bg[3], float W_Bg[9]) {
 int rebvio_hip_set_gyro_state(rebvio_hip_ctx* c, const float Bg[3], const float W_Bg[9]) {
   // While the streaming driver has pairs or frames in flight the filter state lives on the device (and the next pair's first
   // rotation has already been applied with it): it can only be replaced between streams.
-  if (!c->inflight.empty() || !c->frames.empty())
+  if (c->q.count || !c->frames.empty())
     return fail_msg("set_gyro_state: the streaming driver has frames in flight (rebvio_hip_flush first)", -7);
   for (int i = 0; i < 3; ++i) c->Bg[i] = Bg[i];
   c->W_Bg = hm::load3(W_Bg);
@@ -1298,7 +1230,7 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
     std::memset(c->slot[i], 0, sz);
     HIPCHK(hipHostMalloc(&c->rec[i], sizeof(GlueRec), hipHostMallocDefault));
     std::memset(c->rec[i], 0, sizeof(GlueRec));
-    HIPCHK(hipEventCreateWithFlags(&c->slot_ev[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->q.slot_ev[i], hipEventDisableTiming));
   }
   HIPCHK(hipMalloc(&c->fscratch, 64 * sizeof(float)));
   HIPCHK(hipMalloc(&c->glue_dev, rebvio_hip_ctx::kSlots * sizeof(GlueDev)));
@@ -1334,9 +1266,7 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
   }
   rebvio_hip_reset_state(c);
   c->dbg = std::getenv("REBVIO_HIP_DEBUG") != nullptr;
-  if (const char* e = std::getenv("REBVIO_HIP_DETECT_WORKER")) c->det_worker = e[0] != '0';
   if (const char* e = std::getenv("REBVIO_HIP_GYRO_PRE")) c->gyro_pre_on = e[0] != '0';
-  if (const char* e = std::getenv("REBVIO_HIP_FUSE_DOG")) c->fuse_dog = e[0] != '0';
   HIPCHK(hipDeviceSynchronize());
   guard.c = nullptr;
   *out = c;
@@ -1354,14 +1284,6 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
   if (std::getenv("REBVIO_HIP_DEBUG") && c->t_begin_n)
     std::fprintf(stderr, "[rebvio_hip] track_pair_begin over %llu pairs (us): enqueue %.1f  wait for the first half %.1f\n",
                  (unsigned long long)c->t_begin_n, c->t_begin_enq / c->t_begin_n, c->t_begin_wait / c->t_begin_n);
-  if (c->det_thread.joinable()) {
-    {
-      std::lock_guard<std::mutex> lk(c->det_mu);
-      c->det_stop = true;
-    }
-    c->det_cv.notify_all();
-    c->det_thread.join();
-  }
   (void)hipDeviceSynchronize();
   {
     std::lock_guard<std::mutex> g(g_prof.mu);
@@ -1401,7 +1323,7 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
   for (int i = 0; i < rebvio_hip_ctx::kSlots; ++i) {
     if (c->slot[i]) (void)hipHostFree(c->slot[i]);
     if (c->rec[i]) (void)hipHostFree(c->rec[i]);
-    if (c->slot_ev[i]) (void)hipEventDestroy(c->slot_ev[i]);
+    if (c->q.slot_ev[i]) (void)hipEventDestroy(c->q.slot_ev[i]);
   }
   if (c->gstate) (void)hipFree(c->gstate);
   if (c->h_gstate) (void)hipHostFree(c->h_gstate);
@@ -1449,20 +1371,18 @@ int rebvio_hip_scale_space(rebvio_hip_ctx* c, const float* img, float* scale0, f
 int rebvio_hip_detect(rebvio_hip_ctx* c, const float* img, size_t pitch_bytes, uint64_t ts_us, rebvio_hip_map** out) {
   HIPCHK(hipSetDevice(c->device));
   const size_t rowb = (size_t)c->P.cols * sizeof(float);
-  if (pitch_bytes == 0) pitch_bytes = rowb;
-  return detect_host_frame(c, img, pitch_bytes, rowb, c->img_dev, 0, ts_us, out);
+  return detect(c, c->img_dev, 0, 0, ts_us, out, img, pitch_bytes ? pitch_bytes : rowb, rowb);
 }
 
 int rebvio_hip_detect_u8_device(rebvio_hip_ctx* c, const uint8_t* frame_dev, uint64_t ts_us, rebvio_hip_map** out) {
   HIPCHK(hipSetDevice(c->device));
-  return detect_common(c, frame_dev, 1, ts_us, out);
+  return detect(c, frame_dev, 1, px::GRAY8, ts_us, out);
 }
 
 int rebvio_hip_detect_u8(rebvio_hip_ctx* c, const uint8_t* img, size_t pitch_bytes, uint64_t ts_us, rebvio_hip_map** out) {
   HIPCHK(hipSetDevice(c->device));
   const size_t rowb = (size_t)c->P.cols;
-  if (pitch_bytes == 0) pitch_bytes = rowb;
-  return detect_host_frame(c, img, pitch_bytes, rowb, c->img8_dev, 1, ts_us, out);
+  return detect(c, c->img8_dev, 1, px::GRAY8, ts_us, out, img, pitch_bytes ? pitch_bytes : rowb, rowb);
 }
 
 int rebvio_hip_detect_px(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, int fmt, uint64_t ts_us, rebvio_hip_map** out) {
@@ -1471,8 +1391,7 @@ int rebvio_hip_detect_px(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes,
   if (fmt == px::GRAY8) return rebvio_hip_detect_u8(c, static_cast<const uint8_t*>(img), pitch_bytes, ts_us, out);
   HIPCHK(hipSetDevice(c->device));
   const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
-  if (pitch_bytes == 0) pitch_bytes = rowb;
-  return detect_host_frame(c, img, pitch_bytes, rowb, u8_staging(c, fmt), 1, ts_us, out, fmt);
+  return detect(c, u8_staging(c, fmt), 1, fmt, ts_us, out, img, pitch_bytes ? pitch_bytes : rowb, rowb);
 }
 
 int rebvio_hip_detect_px_device(rebvio_hip_ctx* c, const void* frame_dev, int fmt, uint64_t ts_us, rebvio_hip_map** out) {
@@ -1480,7 +1399,7 @@ int rebvio_hip_detect_px_device(rebvio_hip_ctx* c, const void* frame_dev, int fm
   if (rc) return rc;
   if (fmt == px::GRAY8) return rebvio_hip_detect_u8_device(c, static_cast<const uint8_t*>(frame_dev), ts_us, out);
   HIPCHK(hipSetDevice(c->device));
-  return detect_common(c, frame_dev, 1, ts_us, out, fmt);
+  return detect(c, frame_dev, 1, fmt, ts_us, out);
 }
 
 int rebvio_hip_set_undistort(rebvio_hip_ctx* c, const float K4[4], const float D5[5]) {
@@ -1535,7 +1454,6 @@ int rebvio_hip_front_end_px(rebvio_hip_ctx* c, const void* img, size_t pitch_byt
 
 int rebvio_hip_detector_state(rebvio_hip_ctx* c, float* threshold, float* auto_threshold, int* count) {
   HIPCHK(hipSetDevice(c->device));
-  while (c->det_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
   HIPCHK(hipStreamSynchronize(c->s_det));
   HIPCHK(hipStreamSynchronize(c->s_key));
   DetState d;
@@ -1558,19 +1476,22 @@ int rebvio_hip_detector_state(rebvio_hip_ctx* c, float* threshold, float* auto_t
 }
 
 int rebvio_hip_map_size(rebvio_hip_map* m) {
-  MAP_ALIVE_OR(m, -10);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
   if (ensure_size(m)) return -1;
   return m->n_host;
 }
 float rebvio_hip_map_threshold(rebvio_hip_map* m) {
-  MAP_ALIVE_OR(m, std::numeric_limits<float>::quiet_NaN());
+  const MapAlive alive(m);
+  if (alive.dead()) return std::numeric_limits<float>::quiet_NaN();
   if (ensure_size(m)) return std::numeric_limits<float>::quiet_NaN();
   return m->thr_host;
 }
 uint64_t rebvio_hip_map_ts(rebvio_hip_map* m) { return m->ts; }
 
 int rebvio_hip_map_download(rebvio_hip_map* m, rebvio_hip_keyline* keylines, int* mask) {
-  MAP_ALIVE_OR(m, -10);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));
   int rc = ensure_size(m);
@@ -1579,7 +1500,7 @@ int rebvio_hip_map_download(rebvio_hip_map* m, rebvio_hip_keyline* keylines, int
   // "has the tracker touched this map" decision below against the tracker's first use of it (trk_wait_ready)
   std::lock_guard<std::mutex> dl(c->dl_mu);
   // The mirror reflects everything enqueued so far that concerns THIS map: its detection and distance field (`ready`,
-  // recorded behind them; ensure_size has waited for the detect worker to enqueue them) and, once the tracker has used the
+  // recorded behind them; ensure_size has waited for them to be enqueued) and, once the tracker has used the
   // map, the track stream. A map fresh from detect() (edge-image callbacks, ros_rebvio.cpp:32-50) does not wait for the
   // tracker - which may be a pair ahead, or hold a second half parked until the fusion thread releases it.
   if (m->trk_touched.load(std::memory_order_acquire) || !c->owns_streams) {
@@ -1602,7 +1523,8 @@ int rebvio_hip_map_download(rebvio_hip_map* m, rebvio_hip_keyline* keylines, int
 }
 
 int rebvio_hip_render_edge_image(rebvio_hip_map* m, const uint8_t* gray, uint8_t* rgb_out) {
-  MAP_ALIVE_OR(m, -10);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));
   std::lock_guard<std::mutex> dl(c->dl_mu);
@@ -1621,7 +1543,8 @@ int rebvio_hip_render_edge_image(rebvio_hip_map* m, const uint8_t* gray, uint8_t
 }
 
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n) {
-  MAP_ALIVE_OR(m, -10);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));
   int rc = ensure_size(m);
@@ -1650,19 +1573,21 @@ void rebvio_hip_map_release(rebvio_hip_map* m) {
     if (m->in_use) delete m;
     return;
   }
-  release_map(m, nullptr);
+  (void)hipSetDevice(m->ctx->device);
+  release_map(m);
 }
 
 }  // extern "C"
 
 namespace {
 // Stream-ordered return of a map to its pool (the library's own releases call this directly; the C-ABI entry adds the
-// lifetime check).
-// done_ref: an event already recorded behind the map's last consumer (null: one is recorded here).
-void release_map(rebvio_hip_map* m, hipEvent_t done_ref = nullptr) {
+// lifetime check and selects the device).
+// done_ref: an event already recorded behind the map's last consumer. Null: one is recorded here on the track stream, unless
+// record_done is false (a batch releases a step's maps at one point of the track stream, and only its last lane's is marked:
+// the detect stage waits for that one event).
+void release_map(rebvio_hip_map* m, hipEvent_t done_ref, bool record_done) {
   if (!m || !m->in_use) return;
   rebvio_hip_ctx* c = m->ctx;
-  (void)hipSetDevice(c->device);
   wait_enqueued(m);
   // a pair's counters still waiting in this map's state record (track_pair_finish_async without its _result yet): copy them
   // out in stream order before the map can be handed to another frame
@@ -1674,8 +1599,12 @@ void release_map(rebvio_hip_map* m, hipEvent_t done_ref = nullptr) {
   }
   std::lock_guard<std::mutex> pool_lk(c->pool_mu);
   m->done_ref = done_ref;
-  if (!done_ref) (void)hipEventRecord(m->done, c->s_trk);
-  m->has_done = true;
+  if (done_ref) {
+    m->has_done = true;
+  } else if (record_done) {
+    (void)hipEventRecord(m->done, c->s_trk);
+    m->has_done = true;
+  }
   if (c->df_map == m) c->df_map = nullptr;
   m->release_seq = ++c->release_counter;
   m->in_use = false;  // (c->last_detected may keep pointing at it: only its MapState is read, stream-ordered)
@@ -1712,7 +1641,8 @@ int rebvio_hip_distance_field(rebvio_hip_ctx* c, int* id_out, int* dist_out) {
 }
 
 int rebvio_hip_map_distance_field(rebvio_hip_map* m, int* id_out, int* dist_out) {
-  MAP_ALIVE_OR(m, -10);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));
   if (!m->df_built) return fail_msg("map_distance_field: no distance field has been built from this map", -7);
@@ -1753,7 +1683,6 @@ int rebvio_hip_smooth_n(rebvio_hip_ctx* c, const float* img, const int* widths, 
     HIPCHK(hipMalloc(&c->diag0, nb));
     HIPCHK(hipMalloc(&c->diag1, nb));
   }
-  while (c->det_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
   HIPCHK(hipStreamSynchronize(c->s_key));  // the scratch DoG / gradient buffers below belong to frames in flight
   HIPCHK(hipMemcpyAsync(c->img_dev, img, nb, hipMemcpyHostToDevice, c->s_det));
   ScaleBufs sb = c->sb;
@@ -2011,6 +1940,14 @@ hm::M3 prior_rotation(rebvio_hip_ctx* c, const float* R_prior) {
   // R = imu.R(); R.T() = SO3(Bg) * R.T()  (rebvio.cpp:163-164)
   return hm::prior_rotation(c->Bg, R_prior ? hm::load3(R_prior) : hm::identity3());
 }
+
+// The match counters of a finished pair from its new map's state record; too few matches: status 2 (rebvio.cpp:247-252).
+void match_counters(rebvio_hip_pair_out* o, const MapState& st, const rebvio_hip_params& P) {
+  o->klm_num = st.dm_matches;
+  o->kf_matches = st.dm_kf;
+  o->reg_num = st.reg_count;
+  if ((unsigned)o->klm_num < P.global_min_matches_threshold) o->status = 2;
+}
 }  // namespace
 
 int rebvio_hip_track_pair(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map* nm, const float* R_prior, float frame_dt,
@@ -2045,10 +1982,7 @@ int rebvio_hip_track_pair(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map*
   }
   HIPCHK(hipMemcpyAsync(&c->h_st[1], nm->d.st, sizeof(MapState), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  out->klm_num = c->h_st[1].dm_matches;
-  out->kf_matches = c->h_st[1].dm_kf;
-  out->reg_num = c->h_st[1].reg_count;
-  if ((unsigned)out->klm_num < c->P.global_min_matches_threshold) out->status = 2;  // rebvio.cpp:247-252
+  match_counters(out, c->h_st[1], c->P);
   return 0;
 }
 
@@ -2186,15 +2120,15 @@ int rebvio_hip_track_pair_result(rebvio_hip_ctx* c, int* klm_num, int* kf_matche
     HIPCHK(hipEventSynchronize(c->bf_done[r]));  // (a copy queued by _begin sits ahead of that pair's parked second half)
     c->bf_have[r] = true;
   }
-  if (c->bf_nan[r]) {
-    if (status) *status = 1;
-    return 0;
-  }
-  const MapState& st = c->h_bf[r];
-  if (klm_num) *klm_num = st.dm_matches;
-  if (kf_matches) *kf_matches = st.dm_kf;
-  if (reg_num) *reg_num = st.reg_count;
-  if (status) *status = ((unsigned)st.dm_matches < c->P.global_min_matches_threshold) ? 2 : 0;
+  rebvio_hip_pair_out o{};
+  if (c->bf_nan[r])
+    o.status = 1;
+  else
+    match_counters(&o, c->h_bf[r], c->P);
+  if (klm_num) *klm_num = o.klm_num;
+  if (kf_matches) *kf_matches = o.kf_matches;
+  if (reg_num) *reg_num = o.reg_num;
+  if (status) *status = o.status;
   return 0;
 }
 
@@ -2216,55 +2150,139 @@ namespace {
 //   directedMatch head (reads glue_dev[slot]) -> directedMatch tail -> regularize / depth EKF / next pair's first rotation
 // The host never stands between a pair's halves (round 2: kernel end -> event -> host glue -> flag -> wait kernel, 8-10 us
 // of an ~80 us frame, and the reason the rate moved with the box's host): it queues pair k as soon as frame k + lead - 2 has
-// been handed to the detect worker and reads the pairs' records up to kSlots - 1 pairs later. A pair's match counters are
+// been queued for detection and reads the pairs' records up to kSlots - 1 pairs later. A pair's match counters are
 // read from the NEXT pair's slot (its first kernel copies its old map's state record), so pair k is reported once pair
 // k + 1's event has fired; rebvio_hip_flush() fetches the last pair's counters itself.
 
-int stream_finish_record(rebvio_hip_ctx* c, const rebvio_hip_ctx::InFlight& a, const MapState& st) {
-  const GlueRec* r = c->rec[a.slot];
-  if (r->seq_out != a.seq || r->seq_gs != a.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);
-  rebvio_hip_ctx::Done d;
-  d.out = r->out;
-  if (d.out.status != 1) {
-    d.out.klm_num = st.dm_matches;
-    d.out.kf_matches = st.dm_kf;
-    d.out.reg_num = st.reg_count;
-    if ((unsigned)d.out.klm_num < c->P.global_min_matches_threshold) d.out.status = 2;  // rebvio.cpp:247-252
+// The lanes whose pairs a PairQueue holds: the streaming driver's context alone, or a batch's lanes. owner / who: the time-out
+// error's residency report (the context or the batch) and its prefix.
+struct LaneSet {
+  rebvio_hip_ctx* const* c;
+  int n;
+  int device;
+  const void* owner;
+  const char* who;
+};
+
+// A step's records as the caller gets them, lane by lane: the device glue's output, the match counters from each lane's new map
+// state record st[l], and the lane's host mirror of the filter state (rebvio_hip_get_gyro_state; authoritative again after a flush).
+int finish_step(PairQueue& q, const LaneSet& L, const PairQueue::Step& a, const MapState* st) {
+  for (int l = 0; l < L.n; ++l) {
+    const GlueRec* r = L.c[l]->rec[a.slot];
+    if (r->seq_out != a.seq || r->seq_gs != a.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);
   }
-  d.keylines = st.n;
-  // host mirror of the filter state (rebvio_hip_get_gyro_state; authoritative again after a flush)
-  for (int i = 0; i < 3; ++i) c->Bg[i] = r->gs.Bg[i];
-  c->W_Bg = hm::load3(r->gs.W_Bg);
-  c->gs_R = hm::load3(r->gs.R);
-  note_accept_mask(c, d.out.lm_accept_mask);
-  c->t_queued += (double)st.dm_queued;
-  c->done.push_back(d);
+  for (int l = 0; l < L.n; ++l) {
+    rebvio_hip_ctx* c = L.c[l];
+    const GlueRec* r = c->rec[a.slot];
+    PairRec d;
+    d.out = r->out;
+    if (d.out.status != 1) match_counters(&d.out, st[l], c->P);
+    d.keylines = st[l].n;
+    for (int i = 0; i < 3; ++i) c->Bg[i] = r->gs.Bg[i];
+    c->W_Bg = hm::load3(r->gs.W_Bg);
+    c->gs_R = hm::load3(r->gs.R);
+    note_accept_mask(c, d.out.lm_accept_mask);
+    c->t_queued += (double)st[l].dm_queued;
+    q.done.push_back(d);
+  }
   return 0;
 }
 
-// Reports the pairs whose successor has completed; `need` > 0: blocks until at least that many have been reported.
-int stream_harvest(rebvio_hip_ctx* c, int need) {
-  while (c->inflight.size() >= 2) {
-    const rebvio_hip_ctx::InFlight& a = c->inflight[0];
-    const rebvio_hip_ctx::InFlight& b = c->inflight[1];
+// Reports the steps whose successor has completed (a step's match counters ride in its successor's slots: the successor's first
+// kernel copies its old maps' state records); `need` > 0: blocks until at least that many have been reported.
+int harvest(PairQueue& q, const LaneSet& L, int need) {
+  MapState st[kMaxLanes];
+  while (q.count >= 2) {
+    const PairQueue::Step& a = q[0];
+    const PairQueue::Step& n = q[1];
     if (need > 0) {
       const auto t0 = std::chrono::steady_clock::now();
-      HIPCHK(hipEventSynchronize(c->slot_ev[b.ev_slot]));
-      c->t_wait += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+      HIPCHK(hipEventSynchronize(q.slot_ev[n.ev_slot]));
+      q.t_wait += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     } else {
-      const hipError_t q = hipEventQuery(c->slot_ev[b.ev_slot]);
-      if (q == hipErrorNotReady) break;
-      HIPCHK(q);
+      const hipError_t e = hipEventQuery(q.slot_ev[n.ev_slot]);
+      if (e == hipErrorNotReady) break;
+      HIPCHK(e);
     }
-    if (*c->lm_bar_err) return fail_msg(("persistent LM kernel: record exchange timed out; " + residency_describe(c->device, c)).c_str(), -9);
-    if (c->slot[b.slot]->seq != b.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);  // (pair a's counters ride in pair b's slot)
-    const int frc = stream_finish_record(c, a, c->slot[b.slot]->old_st);
+    for (int l = 0; l < L.n; ++l) {
+      const rebvio_hip_ctx* c = L.c[l];
+      const int rc = lm_timed_out(c, L.device, L.owner, L.who);
+      if (rc) return rc;
+      if (c->slot[n.slot]->seq != n.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);
+      st[l] = c->slot[n.slot]->old_st;
+    }
+    const int frc = finish_step(q, L, a, st);
     if (frc) return frc;
-    c->inflight.pop_front();
+    q.pop_front();
     --need;
   }
   return 0;
 }
+
+// Everything queued completes; every step's records end in q.done. The last step has no successor to carry its counters: they
+// are copied from its new maps.
+int drain(PairQueue& q, const LaneSet& L) {
+  int rc = harvest(q, L, q.count);
+  if (rc) return rc;
+  if (q.count == 1) {
+    const PairQueue::Step& a = q[0];
+    HIPCHK(hipEventSynchronize(q.slot_ev[a.ev_slot]));
+    for (int l = 0; l < L.n; ++l) {
+      rebvio_hip_ctx* c = L.c[l];
+      rc = lm_timed_out(c, L.device, L.owner, L.who);
+      if (rc) return rc;
+      if (c->slot[a.slot]->seq != a.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);
+      HIPCHK(hipMemcpyAsync(&c->h_st[1], a.nm[l]->d.st, sizeof(MapState), hipMemcpyDeviceToHost, c->s_trk));
+    }
+    HIPCHK(hipStreamSynchronize(L.c[0]->s_trk));  // (the lanes of a batch share its track stream)
+    MapState st[kMaxLanes];
+    for (int l = 0; l < L.n; ++l) st[l] = L.c[l]->h_st[1];
+    rc = finish_step(q, L, a, st);
+    if (rc) return rc;
+    q.pop_front();
+  }
+  return 0;
+}
+
+// The oldest step's records, one per lane, to the caller; 0: none is waiting.
+int pop_records(PairQueue& q, int lanes, rebvio_hip_pair_out* out, int* keylines) {
+  if (q.done.empty()) return 0;
+  for (int l = 0; l < lanes; ++l) {
+    if (out) out[l] = q.done.front().out;
+    if (keylines) keylines[l] = q.done.front().keylines;
+    q.done.pop_front();
+  }
+  return 1;
+}
+
+// Pairs (batch: steps) to queue as one group now, with `queued` detected frames (steps) waiting and `inflight` steps queued. Full
+// groups while the device has pairs queued (fewest stream operations per pair); as soon as it is about to run dry - a stream's
+// start, or right after the caller synchronised - whatever can start is started at once, down to single pairs. Either way the
+// newest map of a group was detected at least lead - 2 calls ago.
+int group_size(int queued, int inflight, int lead, int group) {
+  const bool shallow = inflight < group;
+  return shallow ? std::min(group, queued - lead + 1) : (queued >= lead + group - 1 ? group : 0);
+}
+
+// First pair of a lane's stream (or after a flush): no second half has applied the prior rotation yet, and the filter state the
+// device glue works on is the host's. It goes up into the state of pair parity gpar; then the old map's first rotateKeylines.
+int start_lane_stream(rebvio_hip_ctx* c, rebvio_hip_map* om, int gpar) {
+  const hm::M3 R = prior_rotation(c, nullptr);
+  GlueState& gs = c->h_gstate[gpar];
+  for (int i = 0; i < 3; ++i) gs.Bg[i] = c->Bg[i];
+  hm::store3(c->W_Bg, gs.W_Bg);
+  hm::store3(R, gs.R);
+  gs.pad = 0.f;
+  HIPCHK(hipMemcpyAsync(c->gstate + gpar, &gs, sizeof(GlueState), hipMemcpyHostToDevice, c->s_trk));
+  float RT[9];
+  hm::store3(hm::transpose(R), RT);
+  launch_rotate(c->s_trk, c->K, om->d, RT, c->hist, 0);
+  return 0;
+}
+
+// The streaming driver as one lane (the set points at the caller's own `c`: use it within that call)
+LaneSet stream_lanes(rebvio_hip_ctx* const& c) { return LaneSet{&c, 1, c->device, c, ""}; }
+
 
 // `npairs` consecutive pairs (frames[0..npairs]) as ONE group on the track stream. Every stream operation between two
 // kernels is a packet of its own for the command processor, and with the kernels queued back to back those packets are what
@@ -2274,8 +2292,8 @@ int stream_harvest(rebvio_hip_ctx* c, int need) {
 // release of every old map.
 int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
   // the slot of pair k is reused by pair k + kSlots: its record (and its successor's) must have been read
-  while ((int)c->inflight.size() + npairs > rebvio_hip_ctx::kSlots - 1) {
-    const int rc = stream_harvest(c, 1);
+  while (c->q.count + npairs > rebvio_hip_ctx::kSlots - 1) {
+    const int rc = harvest(c->q, stream_lanes(c), 1);
     if (rc) return rc;
   }
   hipStream_t s = c->s_trk;
@@ -2286,7 +2304,7 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
   }
   {
     rebvio_hip_map* newest = c->frames[(size_t)npairs];
-    wait_enqueued(newest);  // (the detect worker launches in order: the maps before it are enqueued too)
+    wait_enqueued(newest);
     HIPCHK(trk_wait_ready(s, newest));
     for (int g = 1; g <= npairs; ++g) {
       c->frames[(size_t)g]->trk_waited = true;
@@ -2303,20 +2321,10 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
     const int slot = (int)(c->pair_seq % rebvio_hip_ctx::kSlots);
     const int gpar = (int)(c->pair_seq & 1);
     if (!om->pre_rotated) {
-      // first pair of a stream (or after a flush): no second half has applied the prior rotation yet, and the filter state
-      // the device works on is the host's
-      const hm::M3 R = prior_rotation(c, nullptr);
-      GlueState& gs = c->h_gstate[gpar];
-      for (int i = 0; i < 3; ++i) gs.Bg[i] = c->Bg[i];
-      hm::store3(c->W_Bg, gs.W_Bg);
-      hm::store3(R, gs.R);
-      gs.pad = 0.f;
-      HIPCHK(hipMemcpyAsync(c->gstate + gpar, &gs, sizeof(GlueState), hipMemcpyHostToDevice, s));
+      const int rc = start_lane_stream(c, om, gpar);
+      if (rc) return rc;
       c->wbg_shadow = c->W_Bg;  // what the device's filter state starts from
       c->wbg_shadow_valid = true;
-      float RT[9];
-      hm::store3(hm::transpose(R), RT);
-      launch_rotate(s, c->K, om->d, RT, c->hist, 0);
     }
     const float v0[3] = {0, 0, 0};
     const float frame_dt = (float)((double)(float)(nm->ts - om->ts) / 1000000.0);  // rebvio.cpp:183
@@ -2340,49 +2348,30 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
     std::swap(nm->d.grad, nm->d.grad_tmp);
     nm->pre_rotated = true;
     HIPCHK(hipGetLastError());
-    rebvio_hip_ctx::InFlight f;
-    f.nm = nm;
+    PairQueue::Step f;
+    f.nm[0] = nm;
     f.seq = c->last_stamp;
     f.slot = slot;
-    f.ev_slot = -1;
-    f.frame_dt = frame_dt;
-    c->inflight.push_back(f);
+    c->q.push_back(f);
     last_slot = slot;
     c->pair_seq++;
   }
-  HIPCHK(hipEventRecord(c->slot_ev[last_slot], s));
+  HIPCHK(hipEventRecord(c->q.slot_ev[last_slot], s));
   for (int g = 0; g < npairs; ++g) {
-    c->inflight[c->inflight.size() - 1 - (size_t)g].ev_slot = last_slot;
-    release_map(c->frames[(size_t)g], c->slot_ev[last_slot]);  // stream-ordered: reusable once the group has drained
+    c->q[c->q.count - 1 - g].ev_slot = last_slot;
+    release_map(c->frames[(size_t)g], c->q.slot_ev[last_slot]);  // stream-ordered: reusable once the group has drained
   }
   c->frames.erase(c->frames.begin(), c->frames.begin() + npairs);
   return 0;
 }
 
-// everything queued completes; every pair's record ends in c->done
-int stream_drain(rebvio_hip_ctx* c) {
-  int rc = stream_harvest(c, (int)c->inflight.size());
-  if (rc) return rc;
-  if (c->inflight.size() == 1) {  // the last pair has no successor to carry its counters
-    const rebvio_hip_ctx::InFlight a = c->inflight[0];
-    HIPCHK(hipEventSynchronize(c->slot_ev[a.ev_slot]));
-    if (*c->lm_bar_err) return fail_msg(("persistent LM kernel: record exchange timed out; " + residency_describe(c->device, c)).c_str(), -9);
-    HIPCHK(hipMemcpyAsync(&c->h_st[1], a.nm->d.st, sizeof(MapState), hipMemcpyDeviceToHost, c->s_trk));
-    HIPCHK(hipStreamSynchronize(c->s_trk));
-    if (c->slot[a.slot]->seq != a.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);
-    const int frc = stream_finish_record(c, a, c->h_st[1]);
-    if (frc) return frc;
-    c->inflight.pop_front();
-  }
-  return 0;
-}
 }  // namespace
 
 namespace {
 int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame_host, size_t host_pitch, uint64_t ts_us, rebvio_hip_pair_out* out,
                int* keylines, int fmt = 0) {
   // Software pipeline over the three HIP streams of the context:
-  //   scan / keyline streams : frame f (this call, through the detect worker)
+  //   scan / keyline streams : frame f (this call)
   //   track stream           : see the comment above stream_wait_maps
   // The returned record is the oldest COMPLETE pair not yet handed out, several frames behind f in steady state; status -1
   // while there is none.
@@ -2400,36 +2389,27 @@ int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame
   }
   if (keylines) *keylines = -1;
   c->min_pool = c->lead + 3 * c->group + 3;
-  int rc = detect_async(c, frame_dev, 1, ts_us, &m, frame_host, host_pitch, fmt);
-  if (rc) return rc;
-  {
-    std::lock_guard<std::mutex> lk(c->det_mu);  // written by the detect worker
-    if (!c->det_error.empty()) return fail_msg(c->det_error.c_str(), -8);
+  int rc;
+  if (frame_host) {
+    const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
+    rc = detect(c, u8_staging(c, fmt), 1, fmt, ts_us, &m, frame_host, host_pitch ? host_pitch : rowb, rowb);
+  } else {
+    rc = detect(c, frame_dev, 1, fmt, ts_us, &m);
   }
+  if (rc) return rc;
   const auto td1 = std::chrono::steady_clock::now();
   c->t_detect_enq += std::chrono::duration<double, std::micro>(td1 - td0).count();
   c->t_frames++;
   c->frames.push_back(m);
-  {
-    // Full groups while the device has pairs queued (fewest stream operations per pair); as soon as it is about to run dry - a
-    // stream's start, or right after the caller synchronised - whatever can start is started at once, down to single pairs.
-    // Either way the newest map of a group was handed to the detect worker at least lead - 2 calls ago.
-    const int Q = (int)c->frames.size();
-    const bool shallow = (int)c->inflight.size() < c->group;
-    const int npairs = shallow ? std::min(c->group, Q - c->lead + 1) : (Q >= c->lead + c->group - 1 ? c->group : 0);
-    if (npairs >= 1) {
-      rc = stream_enqueue_group(c, npairs);
-      if (rc) return rc;
-    }
+  const int npairs = group_size((int)c->frames.size(), c->q.count, c->lead, c->group);
+  if (npairs >= 1) {
+    rc = stream_enqueue_group(c, npairs);
+    if (rc) return rc;
   }
   c->t_enq += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - td1).count();
-  rc = stream_harvest(c, 0);
+  rc = harvest(c->q, stream_lanes(c), 0);
   if (rc) return rc;
-  if (!c->done.empty()) {
-    if (out) *out = c->done.front().out;
-    if (keylines) *keylines = c->done.front().keylines;
-    c->done.pop_front();
-  }
+  (void)pop_records(c->q, 1, out, keylines);
   return 0;
 }
 
@@ -2471,13 +2451,7 @@ int rebvio_hip_test_forge_record_stamp(rebvio_hip_ctx* c) {
 }
 
 
-int rebvio_hip_next_record(rebvio_hip_ctx* c, rebvio_hip_pair_out* out, int* keylines) {
-  if (c->done.empty()) return 0;
-  if (out) *out = c->done.front().out;
-  if (keylines) *keylines = c->done.front().keylines;
-  c->done.pop_front();
-  return 1;
-}
+int rebvio_hip_next_record(rebvio_hip_ctx* c, rebvio_hip_pair_out* out, int* keylines) { return pop_records(c->q, 1, out, keylines); }
 
 int rebvio_hip_flush(rebvio_hip_ctx* c) {
   HIPCHK(hipSetDevice(c->device));
@@ -2552,22 +2526,20 @@ int rebvio_hip_flush(rebvio_hip_ctx* c) {
     std::fprintf(stderr,
                  "[rebvio_hip] host time per frame (us): detect hand-over %.1f  pair enqueue %.1f  waiting for result slots %.1f | long "
                  "directedMatch searches per pair %.0f\n",
-                 c->t_detect_enq / n, c->t_enq / n, c->t_wait / n, c->t_queued / n);
-    const uint64_t wn = c->t_worker_n.load();
-    if (wn)
-      std::fprintf(stderr, "[rebvio_hip] detect worker: %.1f us of launches per frame over %llu frames\n", (double)c->t_worker_ns.load() * 1e-3 / (double)wn,
-                   (unsigned long long)wn);
+                 c->t_detect_enq / n, c->t_enq / n, c->q.t_wait / n, c->t_queued / n);
+    if (c->t_det_n)
+      std::fprintf(stderr, "[rebvio_hip] detect: %.1f us of launches per frame over %llu frames\n", c->t_det_launch / (double)c->t_det_n,
+                   (unsigned long long)c->t_det_n);
     // (the counters start again: a caller that flushes between phases reads each phase on its own)
-    c->t_detect_enq = c->t_enq = c->t_wait = c->t_queued = 0;
+    c->t_detect_enq = c->t_enq = c->q.t_wait = c->t_queued = 0;
     c->t_frames = 0;
-    c->t_worker_ns.store(0);
-    c->t_worker_n.store(0);
+    c->t_det_launch = 0;
+    c->t_det_n = 0;
   }
-  while (c->det_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
   int rc = 0;
   while (rc == 0 && c->frames.size() >= 2)  // the pairs no group was started for yet
     rc = stream_enqueue_group(c, std::min(c->group, (int)c->frames.size() - 1));
-  if (rc == 0) rc = stream_drain(c);
+  if (rc == 0) rc = drain(c->q, stream_lanes(c));
   for (auto* m : c->frames)
     if (m->in_use) release_map(m, nullptr);
   c->frames.clear();
@@ -2756,25 +2728,13 @@ struct rebvio_hip_batch {
   bool ev_flag_used[kDetPar]{};
   static constexpr int kReadyRing = 16;
   hipEvent_t ev_ready[kReadyRing]{};  // keylines + distance fields of a step finished (keyline stream)
-  hipEvent_t slot_ev[rebvio_hip_ctx::kSlots]{};
   uint64_t step = 0;
   struct Frame {
     std::vector<rebvio_hip_map*> m;  // one detected map per lane
     uint64_t step;
   };
   std::deque<Frame> frames;
-  struct InFlight {  // a step's pairs (one per lane) whose kernels are queued and whose records have not been read yet
-    Frame nf;
-    uint32_t seq = 0;  // the step's sequence stamp (all lanes)
-    int slot = -1;
-    int ev_slot = -1;  // the slot whose event stands for this step's completion (its group's last step)
-  };
-  struct Done {
-    std::vector<rebvio_hip_pair_out> out;
-    std::vector<int> keylines;
-  };
-  std::deque<InFlight> inflight;
-  std::deque<Done> done;
+  PairQueue q;  // steps in flight and records waiting for the caller
   uint64_t pair_seq = 0;
   uint32_t stamp_seq = 0;   // sequence stamps of the lanes' records, one value per step (rebvio_hip_ctx::stamp_seq)
   bool forge_stamp = false;
@@ -2786,13 +2746,12 @@ struct rebvio_hip_batch {
   // result slots (printed by rebvio_hip_batch_flush)
   bool dbg = false;
   std::atomic<uint64_t> t_det_ns{0};
-  bool det_worker = true;  // REBVIO_HIP_DETECT_WORKER
-  bool fuse_dog = false;   // REBVIO_HIP_BATCH_FUSE_DOG=1
-  double t_trk_enq = 0, t_slot_wait = 0;
+  double t_trk_enq = 0;
   int dm_head_form = 0;   // REBVIO_HIP_BATCH_DM_HEAD: 0 by lane count and map size, 1 compact8, 2 compact4, 3 compact1
   bool poisoned = false;  // a step failed half way (some lanes prepared, others not): every later call is refused
   // detect-enqueue worker: launches the detect stage of a step while the caller thread launches the track stage (the
-  // reference's data-acquisition thread, rebvio.cpp:28; same split as the single-stream driver)
+  // reference's data-acquisition thread, rebvio.cpp:28). A batch step's detect launches take long enough on the host for the
+  // split to pay (the single stream measured it the other way round: DESIGN.md 6d).
   struct DetStep {
     LaneDynB dyn;
     int par;
@@ -2826,38 +2785,17 @@ int batch_upload_map_entry(rebvio_hip_batch* b, int lane, rebvio_hip_map* m) {
 }
 inline unsigned map_swap_bits(const rebvio_hip_map* m) { return (m->d.rs != m->canon.rs ? 1u : 0u) | (m->d.grad != m->canon.grad ? 2u : 0u); }
 
-// a map of a batch goes back to its lane's pool; only the last lane's release is marked in the stream (the releases of a
-// step sit at one point of the track stream, and the detect stage waits for that one event)
-void batch_release_map(rebvio_hip_map* m, bool record_done, hipEvent_t done_ref = nullptr) {
-  if (!m || !m->in_use) return;
-  rebvio_hip_ctx* c = m->ctx;
-  wait_enqueued(m);
-  std::lock_guard<std::mutex> pool_lk(c->pool_mu);
-  m->done_ref = done_ref;
-  if (done_ref) {
-    m->has_done = true;  // (the step's slot event, already recorded behind the maps' last consumer)
-  } else if (record_done) {
-    (void)hipEventRecord(m->done, c->s_trk);
-    m->has_done = true;
-  }
-  if (c->df_map == m) c->df_map = nullptr;
-  m->release_seq = ++c->release_counter;
-  m->in_use = false;
-}
-
 int batch_detect_launch(rebvio_hip_batch* b, const rebvio_hip_batch::DetStep& j) {
   const int B = b->B, par = j.par;
   if (b->ev_flag_used[par]) HIPCHK(hipStreamWaitEvent(b->st.s_det, b->ev_flag[par], 0));
-  // the fused candidate kernel moves the last box pass from the scan stream to the keyline stream: measured SLOWER for batches
-  // (8 lanes 42.4 k -> 39.7 k frames/s, 4 lanes 32.9 k -> 32.2 k), like the single stream's other moves of scan work to the
-  // keyline stream - opt-in here (REBVIO_HIP_BATCH_FUSE_DOG=1), the default for one stream
-  const bool fuse = b->fuse_dog;
-  launch_scale_space_b(b->st.s_det, b->K, 0, B, b->ls_dev, j.dyn, b->lane[0]->widths, j.lens, fuse, j.fmt);
+  // k_dog_mag_b + k_keyline_flag_b: the single stream's fused candidate kernel moves the last box pass from the scan stream to
+  // the keyline stream, measured SLOWER for batches (8 lanes 42.4 k -> 39.7 k frames/s, 4 lanes 32.9 k -> 32.2 k), like the
+  // single stream's other moves of scan work to the keyline stream
+  launch_scale_space_b(b->st.s_det, b->K, 0, B, b->ls_dev, j.dyn, b->lane[0]->widths, j.lens, j.fmt);
   HIPCHK(hipEventRecord(b->ev_scan[par], b->st.s_det));
   HIPCHK(hipStreamWaitEvent(b->st.s_key, b->ev_scan[par], 0));
   if (j.reuse_done) HIPCHK(hipStreamWaitEvent(b->st.s_key, j.reuse_done, 0));
-  const int fw[2] = {b->lane[0]->widths[0][2], b->lane[0]->widths[1][2]};
-  launch_keylines_b(b->st.s_key, b->K, B, b->ls_dev, b->maptab_dev, j.dyn, fuse ? fw : nullptr);
+  launch_keylines_b(b->st.s_key, b->K, B, b->ls_dev, b->maptab_dev, j.dyn);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(b->ev_flag[par], b->st.s_key));
   b->ev_flag_used[par] = true;
@@ -2897,70 +2835,14 @@ void batch_det_worker(rebvio_hip_batch* b) {
   }
 }
 
-int batch_finish_records(rebvio_hip_batch* b, const rebvio_hip_batch::InFlight& a, const MapState* st_of_lane /*[B]*/) {
-  for (int l = 0; l < b->B; ++l) {
-    const GlueRec* r = b->lane[l]->rec[a.slot];
-    if (r->seq_out != a.seq || r->seq_gs != a.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);
-  }
-  rebvio_hip_batch::Done d;
-  d.out.resize((size_t)b->B);
-  d.keylines.resize((size_t)b->B);
-  for (int l = 0; l < b->B; ++l) {
-    rebvio_hip_ctx* c = b->lane[l];
-    const GlueRec* r = c->rec[a.slot];
-    const MapState& st = st_of_lane[l];
-    rebvio_hip_pair_out o = r->out;
-    if (o.status != 1) {
-      o.klm_num = st.dm_matches;
-      o.kf_matches = st.dm_kf;
-      o.reg_num = st.reg_count;
-      if ((unsigned)o.klm_num < c->P.global_min_matches_threshold) o.status = 2;
-    }
-    d.out[(size_t)l] = o;
-    d.keylines[(size_t)l] = st.n;
-    for (int i = 0; i < 3; ++i) c->Bg[i] = r->gs.Bg[i];
-    c->W_Bg = hm::load3(r->gs.W_Bg);
-    c->gs_R = hm::load3(r->gs.R);
-    note_accept_mask(c, o.lm_accept_mask);
-  }
-  b->done.push_back(std::move(d));
-  return 0;
-}
-
-// as stream_harvest, for all lanes of a step at once (one event per step)
-int batch_harvest(rebvio_hip_batch* b, int need) {
-  std::vector<MapState> st((size_t)b->B);
-  while (b->inflight.size() >= 2) {
-    const rebvio_hip_batch::InFlight& a = b->inflight[0];
-    const rebvio_hip_batch::InFlight& n = b->inflight[1];
-    if (need > 0) {
-      const auto t0 = std::chrono::steady_clock::now();
-      HIPCHK(hipEventSynchronize(b->slot_ev[n.ev_slot]));
-      b->t_slot_wait += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    } else {
-      const hipError_t q = hipEventQuery(b->slot_ev[n.ev_slot]);
-      if (q == hipErrorNotReady) break;
-      HIPCHK(q);
-    }
-    for (int l = 0; l < b->B; ++l) {
-      if (*b->lane[l]->lm_bar_err) return fail_msg(("batch: persistent LM kernel: record exchange timed out; " + residency_describe(b->device, b)).c_str(), -9);
-      if (b->lane[l]->slot[n.slot]->seq != n.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);  // (step a's counters ride in step n's slots)
-      st[(size_t)l] = b->lane[l]->slot[n.slot]->old_st;
-    }
-    const int frc = batch_finish_records(b, a, st.data());
-    if (frc) return frc;
-    b->inflight.pop_front();
-    --need;
-  }
-  return 0;
-}
+LaneSet batch_lanes(const rebvio_hip_batch* b) { return LaneSet{b->lane.data(), b->B, b->device, b, "batch: "}; }
 
 // `nsteps` consecutive steps' pairs, all lanes, as one group on the track stream (see stream_enqueue_group): per step [rotate +]
 // LM kernel with every lane's glue at its end, directedMatch head, tail, regularize / EKF / next rotation; per group one wait
 // for the newest step's detection and one event
 int batch_enqueue_group(rebvio_hip_batch* b, int nsteps) {
-  while ((int)b->inflight.size() + nsteps > rebvio_hip_ctx::kSlots - 1) {
-    const int rc = batch_harvest(b, 1);
+  while (b->q.count + nsteps > rebvio_hip_ctx::kSlots - 1) {
+    const int rc = harvest(b->q, batch_lanes(b), 1);
     if (rc) return rc;
   }
   hipStream_t s = b->st.s_trk;
@@ -2983,17 +2865,9 @@ int batch_enqueue_group(rebvio_hip_batch* b, int nsteps) {
       rebvio_hip_map *om = of.m[l], *nm = nf.m[l];
       c->df_map = nm;
       dyn.v[l].seq = (b->forge_stamp && l == b->B - 1) ? (step_seq ^ 0x40000000u) : step_seq;
-      if (!om->pre_rotated) {  // first pair of the lane: no second half has applied the prior rotation yet; the host's state goes up
-        const hm::M3 R = prior_rotation(c, nullptr);
-        GlueState& gs = c->h_gstate[gpar];
-        for (int i = 0; i < 3; ++i) gs.Bg[i] = c->Bg[i];
-        hm::store3(c->W_Bg, gs.W_Bg);
-        hm::store3(R, gs.R);
-        gs.pad = 0.f;
-        HIPCHK(hipMemcpyAsync(c->gstate + gpar, &gs, sizeof(GlueState), hipMemcpyHostToDevice, s));
-        float RT[9];
-        hm::store3(hm::transpose(R), RT);
-        launch_rotate(s, c->K, om->d, RT, c->hist, 0);
+      if (!om->pre_rotated) {
+        const int rc = start_lane_stream(c, om, gpar);
+        if (rc) return rc;
       }
       LaneDyn& d = dyn.v[l];
       d.nm = (short)nm->tab_idx;
@@ -3003,11 +2877,7 @@ int batch_enqueue_group(rebvio_hip_batch* b, int nsteps) {
       d.slot = (unsigned char)slot;
       d.gpar = (unsigned char)gpar;
       d.tag_base = c->lm_tag_base;
-      c->lm_tag_base += 2u * ((unsigned)calls + 1u);
-      if (c->lm_tag_base > 0xFFFFFF00u) {
-        (void)hipMemsetAsync(c->lm_xch, 0, lm_xch_words(c->maxblocks) * sizeof(unsigned long long), s);
-        c->lm_tag_base = 0;
-      }
+      advance_lm_tags(c, calls);
     }
     // one launch for all lanes: the most cautious of the lanes' choices (1 sequential; otherwise the LATEST first speculative
     // evaluation any lane asks for)
@@ -3035,53 +2905,23 @@ int batch_enqueue_group(rebvio_hip_batch* b, int nsteps) {
       nm->pre_rotated = true;
     }
     b->forge_stamp = false;
-    rebvio_hip_batch::InFlight f;
-    f.nf = nf;
+    PairQueue::Step f;
+    for (int l = 0; l < b->B; ++l) f.nm[l] = nf.m[l];
     f.seq = step_seq;
     f.slot = slot;
-    f.ev_slot = -1;
-    b->inflight.push_back(f);
+    b->q.push_back(f);
     olds.push_back(of);
     b->frames.pop_front();
     b->pair_seq++;
     last_slot = slot;
   }
-  HIPCHK(hipEventRecord(b->slot_ev[last_slot], s));
-  for (int g = 0; g < nsteps; ++g) b->inflight[b->inflight.size() - 1 - (size_t)g].ev_slot = last_slot;
+  HIPCHK(hipEventRecord(b->q.slot_ev[last_slot], s));
+  for (int g = 0; g < nsteps; ++g) b->q[b->q.count - 1 - g].ev_slot = last_slot;
   for (auto& of : olds)
-    for (auto* m : of.m) batch_release_map(m, false, b->slot_ev[last_slot]);  // the group's one event covers every old map
+    for (auto* m : of.m) release_map(m, b->q.slot_ev[last_slot], false);  // the group's one event covers every old map
   return 0;
 }
 
-int batch_drain(rebvio_hip_batch* b) {
-  int rc = batch_harvest(b, (int)b->inflight.size());
-  if (rc) return rc;
-  if (b->inflight.size() == 1) {  // the last step has no successor to carry its counters
-    const rebvio_hip_batch::InFlight a = b->inflight[0];
-    HIPCHK(hipEventSynchronize(b->slot_ev[a.ev_slot]));
-    std::vector<MapState> st((size_t)b->B);
-    for (int l = 0; l < b->B; ++l) {
-      if (*b->lane[l]->lm_bar_err) return fail_msg(("batch: persistent LM kernel: record exchange timed out; " + residency_describe(b->device, b)).c_str(), -9);
-      if (b->lane[l]->slot[a.slot]->seq != a.seq) return fail_msg(kStaleRecordMsg, kStaleRecord);
-      HIPCHK(hipMemcpy(&st[(size_t)l], a.nf.m[l]->d.st, sizeof(MapState), hipMemcpyDeviceToHost));
-    }
-    const int frc = batch_finish_records(b, a, st.data());
-    if (frc) return frc;
-    b->inflight.pop_front();
-  }
-  return 0;
-}
-
-int batch_pop(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines) {
-  if (b->done.empty()) return 0;
-  const rebvio_hip_batch::Done& d = b->done.front();
-  for (int l = 0; l < b->B; ++l) {
-    if (out) out[l] = d.out[(size_t)l];
-    if (keylines) keylines[l] = d.keylines[(size_t)l];
-  }
-  b->done.pop_front();
-  return 1;
-}
 }  // namespace
 
 extern "C" {
@@ -3102,8 +2942,8 @@ void rebvio_hip_batch_destroy(rebvio_hip_batch* b) {
   // the maps of queued steps and of the pairs in flight are the batch's own, not handles a caller holds
   for (auto& f : b->frames)
     for (auto* m : f.m) m->in_use = false;
-  for (auto& f : b->inflight)
-    for (auto* m : f.nf.m) m->in_use = false;
+  for (int i = 0; i < b->q.count; ++i)
+    for (int l = 0; l < b->B; ++l) b->q[i].nm[l]->in_use = false;
   for (auto* c : b->lane) rebvio_hip_destroy(c);
   if (b->ls_dev) (void)hipFree(b->ls_dev);
   if (b->maptab_dev) (void)hipFree(b->maptab_dev);
@@ -3113,7 +2953,7 @@ void rebvio_hip_batch_destroy(rebvio_hip_batch* b) {
   }
   for (auto& e : b->ev_ready)
     if (e) (void)hipEventDestroy(e);
-  for (auto& e : b->slot_ev)
+  for (auto& e : b->q.slot_ev)
     if (e) (void)hipEventDestroy(e);
   if (b->st.s_det) (void)hipStreamDestroy(b->st.s_det);
   if (b->st.s_key) (void)hipStreamDestroy(b->st.s_key);
@@ -3147,8 +2987,6 @@ int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_ba
   b->lm_lanes_per_launch = lm_lanes_per_launch;
   b->lm_capacity_wgs = lm_chain_b_capacity_wgs(p->device_id, p->keylines_max, (int)p->iterations + 1);
   b->dbg = std::getenv("REBVIO_HIP_DEBUG") != nullptr;
-  if (const char* e = std::getenv("REBVIO_HIP_DETECT_WORKER")) b->det_worker = e[0] != '0';
-  if (const char* e = std::getenv("REBVIO_HIP_BATCH_FUSE_DOG")) b->fuse_dog = e[0] == '1';
   struct Guard {
     rebvio_hip_batch* b;
     ~Guard() {
@@ -3221,7 +3059,7 @@ int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_ba
     HIPCHK(hipEventCreateWithFlags(&b->ev_flag[i], hipEventDisableTiming));
   }
   for (auto& e : b->ev_ready) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : b->slot_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : b->q.slot_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   if (const char* e = std::getenv("REBVIO_HIP_BATCH_LEAD")) b->lead = std::min(8, std::max(3, std::atoi(e)));
   if (const char* e = std::getenv("REBVIO_HIP_BATCH_GROUP")) b->group = std::min(4, std::max(1, std::atoi(e)));
   if (const char* e = std::getenv("REBVIO_HIP_BATCH_DM_HEAD"))
@@ -3331,46 +3169,30 @@ static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fm
   job.lens = b->lens;
   job.fmt = fmt;
   for (auto* m : fr.m) m->enqueued.store(0, std::memory_order_relaxed);
-  if (!b->det_worker) {  // the caller launches the step's detect kernels itself (see detect_async)
-    const auto t0 = std::chrono::steady_clock::now();
-    const int drc = batch_detect_launch(b, job);
-    if (b->dbg) b->t_det_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
-    for (auto* m : fr.m) m->enqueued.store(1, std::memory_order_release);
-    b->det_done_steps.store(job.step + 1, std::memory_order_release);
-    if (drc) {
-      b->poisoned = true;
-      return drc;
-    }
-  } else {
-    if (!b->det_thread.joinable()) b->det_thread = std::thread(batch_det_worker, b);
-    {
-      std::lock_guard<std::mutex> lk(b->det_mu);
-      b->det_jobs.push_back(job);
-    }
-    b->det_cv.notify_one();
+  if (!b->det_thread.joinable()) b->det_thread = std::thread(batch_det_worker, b);
+  {
+    std::lock_guard<std::mutex> lk(b->det_mu);
+    b->det_jobs.push_back(job);
   }
+  b->det_cv.notify_one();
   b->frames.push_back(fr);
   b->step++;
 
   // ---- track stage: the step's pairs, whole, for every lane; then whatever records have become complete ----
-  {
-    const int Q = (int)b->frames.size();  // (group size by queue depth: see push_frame)
-    const bool shallow = (int)b->inflight.size() < b->group;
-    const int nsteps = shallow ? std::min(b->group, Q - b->lead + 1) : (Q >= b->lead + b->group - 1 ? b->group : 0);
-    if (nsteps >= 1) {
-      const auto t0 = std::chrono::steady_clock::now();
-      const double w0 = b->t_slot_wait;
-      const int rc = batch_enqueue_group(b, nsteps);
-      b->t_trk_enq += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() - (b->t_slot_wait - w0);
-      if (rc) {
-        b->poisoned = true;
-        return rc;
-      }
+  const int nsteps = group_size((int)b->frames.size(), b->q.count, b->lead, b->group);
+  if (nsteps >= 1) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const double w0 = b->q.t_wait;
+    const int rc = batch_enqueue_group(b, nsteps);
+    b->t_trk_enq += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() - (b->q.t_wait - w0);
+    if (rc) {
+      b->poisoned = true;
+      return rc;
     }
   }
-  int rc = batch_harvest(b, 0);
+  int rc = harvest(b->q, batch_lanes(b), 0);
   if (rc) return rc;
-  (void)batch_pop(b, out, keylines);
+  (void)pop_records(b->q, b->B, out, keylines);
   return 0;
 }
 
@@ -3389,7 +3211,7 @@ int rebvio_hip_batch_push_px_device(rebvio_hip_batch* b, const void* const* fram
   return batch_push(b, frames_dev, fmt, ts_us, out, keylines);
 }
 
-int rebvio_hip_batch_next_records(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines) { return batch_pop(b, out, keylines); }
+int rebvio_hip_batch_next_records(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines) { return pop_records(b->q, b->B, out, keylines); }
 
 int rebvio_hip_batch_flush(rebvio_hip_batch* b) {
   HIPCHK(hipSetDevice(b->device));
@@ -3397,16 +3219,16 @@ int rebvio_hip_batch_flush(rebvio_hip_batch* b) {
   if (b->dbg && b->step)
     std::fprintf(stderr, "[rebvio_hip] batch of %d lanes, host time per step (us): detect worker's launches %.1f  track enqueue %.1f  waiting "
                  "for result slots %.1f\n", b->B, (double)b->t_det_ns.load() / 1e3 / (double)b->step, b->t_trk_enq / (double)b->step,
-                 b->t_slot_wait / (double)b->step);
+                 b->q.t_wait / (double)b->step);
   if (b->dbg)
     std::fprintf(stderr, "[rebvio_hip] batch: pool of lane 0 holds %d maps (min_pool %d), %d steps in flight, %d detected steps queued\n",
-                 (int)b->lane[0]->pool.size(), b->lane[0]->min_pool, (int)b->inflight.size(), (int)b->frames.size());
+                 (int)b->lane[0]->pool.size(), b->lane[0]->min_pool, b->q.count, (int)b->frames.size());
   int rc = 0;
   while (rc == 0 && b->frames.size() >= 2)  // the steps no group was started for yet
     rc = batch_enqueue_group(b, std::min(b->group, (int)b->frames.size() - 1));
-  if (rc == 0) rc = batch_drain(b);
+  if (rc == 0) rc = drain(b->q, batch_lanes(b));
   for (auto& f : b->frames)
-    for (size_t l = 0; l < f.m.size(); ++l) batch_release_map(f.m[l], l + 1 == f.m.size());
+    for (size_t l = 0; l < f.m.size(); ++l) release_map(f.m[l], nullptr, l + 1 == f.m.size());
   b->frames.clear();
   for (auto* c : b->lane)  // as rebvio_hip_flush: no histogram counts of a pair that will not come
     HIPCHK(hipMemsetAsync(c->hist, 0, 128 * sizeof(int), b->st.s_trk));

@@ -149,11 +149,11 @@ void launch_front_end_u8(hipStream_t s, const KParams& p, const uint8_t* src, co
 void launch_front_end_px(hipStream_t s, const KParams& p, const uint8_t* src, int fmt, const int2* map, float* dst);
 void launch_copy_from_pinned(hipStream_t s, const void* src_pinned, void* dst_dev, size_t bytes);
 void launch_scale_space(hipStream_t s, const KParams& p, const void* img, int img_is_u8, const ScaleBufs& sb,
-                        const int widths[2][3], int* rowcount_to_zero, int part = 3, bool fuse_dog = false,
+                        const int widths[2][3], int* rowcount_to_zero, int part = 3,
                         int fmt = 0 /* pixel format of a u8 frame (pixel_format.hpp) */);
 void launch_smooth_n(hipStream_t s, const KParams& p, const float* img, const ScaleBufs& sb, const int* widths, int n, int* rowcount_to_zero);
 void launch_keylines(hipStream_t s, const KParams& p, const ScaleBufs& sb, const DetectBufs& db, const MapDev& m,
-                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int* fuse_widths = nullptr);
+                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int widths[2][3]);
 // Tile grid of the keyline-driven distance-field build (shared by the binning pass in k_join_edges and the tile kernel).
 struct DfGrid {
   int T, ntx, nty;
@@ -440,9 +440,8 @@ __device__ __forceinline__ uint2 xcd_band_block() {
 
 #endif
 void launch_scale_space_b(hipStream_t s, const KParams& p, int lane0, int lanes, const LaneStatic* ls, const LaneDynB& dyn,
-                          const int widths[2][3], bool lens, bool fuse_dog = false, int fmt = 0 /* of every lane's frame */);
-void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn,
-                       const int* fuse_widths = nullptr);
+                          const int widths[2][3], bool lens, int fmt = 0 /* of every lane's frame */);
+void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn);
 void launch_df_build_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn);
 void launch_lm_chain_b(hipStream_t s, const KParams& p, int lanes, int lanes_per_launch, const LaneStatic* ls, const MapDev* maptab,
                        const LaneDynB& dyn, int calls, int spec, const GlueParams& gp);

@@ -798,12 +798,6 @@ __device__ __forceinline__ void keyline_flag_body(const float* __restrict__ dog,
   }
 }
 
-template <int TR>
-__global__ __launch_bounds__(256) void k_keyline_flag(const float* __restrict__ dog, const float* __restrict__ mag, KParams p,
-                                                      const DetState* __restrict__ det_in, float4* __restrict__ stash,
-                                                      unsigned long long* __restrict__ bits, int* __restrict__ rowcount) {
-  keyline_flag_body<TR>(dog, mag, p, det_in, stash, bits, rowcount);
-}
 __global__ __launch_bounds__(256) void k_keyline_flag_b(KParams p, const LaneStatic* __restrict__ ls, LaneDynB dyn) {
   const LaneStatic& L = ls[blockIdx.z];
   const LaneDyn d = dyn.v[blockIdx.z];
@@ -952,12 +946,6 @@ __global__ __launch_bounds__(256) void k_keyline_flag_ii(const float* __restrict
                                                          const DetState* __restrict__ det_in, float4* __restrict__ stash,
                                                          unsigned long long* __restrict__ bits, int* __restrict__ rowcount) {
   keyline_flag_ii_body<TR>(II0, II1, d0, d1, p, det_in, stash, bits, rowcount);
-}
-__global__ __launch_bounds__(256) void k_keyline_flag_ii_b(KParams p, const LaneStatic* __restrict__ ls, LaneDynB dyn, int d0, int d1) {
-  const LaneStatic& L = ls[blockIdx.z];
-  const LaneDyn d = dyn.v[blockIdx.z];
-  keyline_flag_ii_body<16>(gptr(L.dog2[d.parity]), gptr(L.mag2[d.parity]), d0, d1, p, gptr(L.det) + d.det_in, gptr(L.stash), gptr(L.bits),
-                           gptr(L.rowcount2[d.parity]));
 }
 
 __device__ __forceinline__ int wave_sum(int v) {
@@ -1673,10 +1661,11 @@ static void rowscan_px_attrs() {
   done = true;
 }
 
-// part: 1 = everything up to the row pass of the third box filter (five kernels), 2 = its column pass + k_dog_mag, 3 = both.
+// part: 1 = everything up to the row pass of the third box filter (five kernels); 2 = its column pass alone, for the fused
+// candidate kernel (launch_keylines, k_keyline_flag_ii); 3 = both, then k_dog_mag (DoG, gradient and both scales in memory).
 // The streaming driver runs part 2 on the keyline stream: the scan stream is the busiest of a frame's three.
 void launch_scale_space(hipStream_t s, const KParams& p, const void* img, int img_is_u8, const ScaleBufs& sb,
-                        const int widths[2][3], int* rowcount_to_zero, int part, bool fuse_dog, int fmt) {
+                        const int widths[2][3], int* rowcount_to_zero, int part, int fmt) {
   const int R = p.rows, C = p.cols;
   const int Cp = (C + 3) & ~3;  // pitch of the scan buffers sb.a / sb.b
   const int ldw_abs = lds_pitch(Cp);
@@ -1720,7 +1709,7 @@ void launch_scale_space(hipStream_t s, const KParams& p, const void* img, int im
     RH_LAUNCH(k_rowscan<2>, g2, dim3(256), shm, s, (const void*)sb.b[0], (const void*)sb.b[1], sb.a[0], sb.a[1], R, C, widths[0][1],
               widths[1][1], ldw);
   }
-  if ((part & 2) && fuse_dog) {
+  if (part == 2) {
     // the candidate kernel forms the last box pass, DoG and gradient itself (launch_keylines, k_keyline_flag_ii): only the
     // column pass remains here, and it clears the frame's row counters
     RH_LAUNCH(k_colscan, c2, dim3(256), cshm, s, sb.a[0], sb.a[1], R, Cp, ldh, rowcount_to_zero, R);
@@ -1763,7 +1752,7 @@ void launch_smooth_n(hipStream_t s, const KParams& p, const float* img, const Sc
 
 // ---- batched launchers (lane = blockIdx.z): the same grids with a third dimension ------------------------------------------
 void launch_scale_space_b(hipStream_t s, const KParams& p, int lane0, int lanes, const LaneStatic* ls, const LaneDynB& dyn,
-                          const int widths[2][3], bool lens, bool fuse_dog, int fmt) {
+                          const int widths[2][3], bool lens, int fmt) {
   const int R = p.rows, C = p.cols;
   const int Cp = (C + 3) & ~3;
   const int ldw_abs = lds_pitch(Cp);
@@ -1809,25 +1798,16 @@ void launch_scale_space_b(hipStream_t s, const KParams& p, int lane0, int lanes,
   RH_COLSCAN_B(0);
   RH_LAUNCH(k_rowscan_b<2>, g2, dim3(256), shm, s, ls, dyn, lane0, 1, R, C, widths[0][0], widths[1][0], ldw);
   RH_COLSCAN_B(1);
-  if (fuse_dog) {  // k_keyline_flag_ii_b forms the last box pass, DoG and gradient itself (launch_keylines_b)
-    RH_LAUNCH(k_rowscan_b<2>, g2, dim3(256), shm, s, ls, dyn, lane0, 4, R, C, widths[0][1], widths[1][1], ldw);
-    RH_LAUNCH(k_colscan_b, c2, dim3(256), cshm, s, ls, lane0, 3, R, Cp, ldh, (int)dyn.v[lane0].parity);
-    return;
-  }
   RH_LAUNCH(k_rowscan_b<2>, g2, dim3(256), shm, s, ls, dyn, lane0, 2, R, C, widths[0][1], widths[1][1], ldw);
   RH_COLSCAN_B(2);
   RH_LAUNCH(k_dog_mag_b, dim3(div_up(C, 64), div_up(R, 16), z), dim3(64, 4), 0, s, ls, dyn, lane0, widths[0][2], widths[1][2], R, C);
 #undef RH_COLSCAN_B
 }
 
-void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn,
-                       const int* fuse_widths) {
+void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn) {
   const unsigned z = (unsigned)lanes;
   const DfGrid dg = df_grid(p.rows, p.cols);
-  if (fuse_widths)
-    RH_LAUNCH(k_keyline_flag_ii_b, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, dyn, fuse_widths[0], fuse_widths[1]);
-  else
-    RH_LAUNCH(k_keyline_flag_b, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, dyn);
+  RH_LAUNCH(k_keyline_flag_b, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, dyn);
   RH_LAUNCH(k_keyline_emit_b, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, maptab, dyn, 0, dg.ntx * dg.nty);
   RH_LAUNCH(k_join_edges_b, dim3(div_up(p.kmax, 256), 1, z), dim3(256), (size_t)dg.ntx * dg.nty * sizeof(int), s, p, maptab, dyn, dg.T, dg.ntx,
             dg.nty);
@@ -1857,15 +1837,12 @@ void launch_df_build_b(hipStream_t s, const KParams& p, int lanes, const LaneSta
 }
 
 void launch_keylines(hipStream_t s, const KParams& p, const ScaleBufs& sb, const DetectBufs& db, const MapDev& m,
-                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int* fuse_widths) {
+                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int widths[2][3]) {
   const DfGrid dg = df_grid(p.rows, p.cols);
   const dim3 gt(div_up(p.cols, 64), div_up(p.rows, kTileRowsSingle));
-  if (fuse_widths)  // sb.a[] hold the third filter pass's integral images (launch_scale_space with fuse_dog)
-    RH_LAUNCH(k_keyline_flag_ii<kTileRowsSingle>, gt, dim3(64, 4), 0, s, (const float*)sb.a[0], (const float*)sb.a[1], fuse_widths[0], fuse_widths[1], p,
-              det_in, db.stash, db.bits, db.rowcount);
-  else
-    RH_LAUNCH(k_keyline_flag<kTileRowsSingle>, gt, dim3(64, 4), 0, s, (const float*)sb.dog, (const float*)sb.mag, p, det_in, db.stash, db.bits,
-              db.rowcount);
+  // sb.a[] hold the third filter pass's integral images (launch_scale_space part 2)
+  RH_LAUNCH(k_keyline_flag_ii<kTileRowsSingle>, gt, dim3(64, 4), 0, s, (const float*)sb.a[0], (const float*)sb.a[1], widths[0][2], widths[1][2], p,
+            det_in, db.stash, db.bits, db.rowcount);
   RH_LAUNCH(k_keyline_emit<kTileRowsSingle>, gt, dim3(64, 4), 0, s, p, m, (const float4*)db.stash, (const unsigned long long*)db.bits,
             (const int*)db.rowcount, det_in, det_out, prev_st, 0, dg.ntx * dg.nty);
   RH_LAUNCH(k_join_edges, dim3(div_up(p.kmax, 256)), dim3(256), (size_t)dg.ntx * dg.nty * sizeof(int), s, p, m, dg.T, dg.ntx, dg.nty);

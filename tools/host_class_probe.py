@@ -7,7 +7,7 @@ import numpy as np
 from rebvio_amd import synth
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4000
-variants = [v for v in sys.argv[2:]] or ["", "REBVIO_HIP_PAIR_PRELAUNCH=1"]
+variants = [v for v in sys.argv[2:]] or [""]
 frames, cam = synth.render_stream(640, 480, 24)
 order = synth.pingpong_indices(24, n)
 d = tempfile.mkdtemp()
