@@ -38,6 +38,9 @@ class EdgeDetector {
 
   // Asynchronous on the GPU: returns as soon as the kernels are enqueued; size()/keylines() of the map synchronise.
   rebvio::EdgeMap::SharedPtr detect(rebvio::types::Image& image);
+  // addition: detection mask (CV_8UC1 of the camera's size, in the coordinates of the undistorted image; non-zero = keylines may
+  // come from here; an empty Mat clears it). Applies to the frames detected after the call (rebvio_hip_set_detection_mask).
+  void setDetectionMask(const cv::Mat& mask);
 
  private:
   EdgeDetectorConfig::SharedPtr config_;

@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <deque>
 #include <queue>
@@ -39,6 +40,9 @@ class Rebvio {
   void imuCallback(rebvio::types::Imu&& imu);
   void registerEdgeImageCallback(std::function<void(cv::Mat&, rebvio::EdgeMap::SharedPtr&)> cb);
   void registerOdometryCallback(std::function<void(rebvio::types::Odometry&)> cb);
+  // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
+  // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
+  void setDetectionMask(const cv::Mat& mask);
 
   // additions for embedding without ROS: block until every queued frame has been processed / current status
   void waitIdle();
@@ -59,6 +63,8 @@ class Rebvio {
   rebvio::SABEstimator::State sab_state_;  // after core_ and config_ in construction order
 
   std::queue<rebvio::types::Image> image_buffer_;
+  std::queue<std::shared_ptr<const cv::Mat>> image_mask_buffer_;  // the detection mask of each queued image (null: none)
+  std::shared_ptr<const cv::Mat> mask_;                          // ... for the images queued next (under image_buffer_mutex_)
   std::mutex image_buffer_mutex_;
   std::queue<rebvio::types::Imu> imu_buffer_;
   std::mutex imu_buffer_mutex_;

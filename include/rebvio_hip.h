@@ -154,6 +154,27 @@ int rebvio_hip_detect_px(rebvio_hip_ctx* ctx, const void* img_host, size_t pitch
 int rebvio_hip_detect_px_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, uint64_t ts_us, rebvio_hip_map** out);
 /* rebvio_hip_front_end_u8 for a frame of any format (host memory, pitch_bytes 0 = dense). Needs a lens model. */
 int rebvio_hip_front_end_px(rebvio_hip_ctx* ctx, const void* img_host, size_t pitch_bytes, int fmt, float* out_host);
+/* Detection masks: where keylines may come from. One byte per pixel in the coordinates of the image the scale space sees (with a
+ * lens model: UNDISTORTED coordinates); non-zero = "keylines may come from here", as OpenCV's mask arguments (a torch bool or
+ * uint8 tensor has this layout). A masked pixel is skipped in buildEdgeMap (edge_detector.cpp:73-121) exactly like one that
+ * fails the magnitude test; nothing else changes: the scale space, DoG and gradient cover the whole frame, keylines_max counts
+ * the surviving candidates in raster order, joinEdges links surviving keylines only, tuneThreshold and the threshold servo see
+ * the masked keyline count, tracking is untouched. Two kinds, which may be combined (a pixel must then pass both):
+ *  - the static mask of a context, rebvio_hip_set_detection_mask: copied to the device (the caller's buffer is free when the call
+ *    returns; pitch_bytes >= cols, 0 = dense; NULL clears it). It applies to every detect and push entry of the context from the
+ *    next frame on; frames already queued keep the mask they were queued with (the call waits until their candidate kernels
+ *    have run before it rewrites the device copy). A batch lane's static mask is set on rebvio_hip_batch_lane(b, l) and is
+ *    picked up by the batch's next push.
+ *  - a per-frame mask in device memory (dense, rows*cols bytes), with device-resident frames only: the *_masked_device entries.
+ *    The device reads it (and the frame) on the library's streams after the call returns: keep both unchanged until the frame's
+ *    detection has finished. A point the caller can rely on: once rebvio_hip_map_size (or any other call that waits for the map)
+ *    has returned for a detect entry's map; for a push entry, once the record of the pair that ends at this frame has been
+ *    handed out (push, next_record or flush).
+ * The masked entries refuse (-3, rebvio_hip_last_error says why) before anything is queued: a null frame or mask, an unknown
+ * pixel format, a host pitch below cols; a bad frame as their unmasked *_px_device twins do. */
+int rebvio_hip_set_detection_mask(rebvio_hip_ctx* ctx, const uint8_t* mask_host, size_t pitch_bytes);
+int rebvio_hip_detect_px_masked_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, const uint8_t* mask_dev, uint64_t ts_us,
+                                       rebvio_hip_map** out);
 /* config_->threshold after the servo and auto_threshold_ (edge_detector.hpp:84,91). Synchronises. */
 int rebvio_hip_detector_state(rebvio_hip_ctx* ctx, float* threshold, float* auto_threshold, int* keylines_count);
 
@@ -307,6 +328,9 @@ int rebvio_hip_push_frame_px(rebvio_hip_ctx* ctx, const void* frame_host, size_t
                              rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_push_frame_px_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, uint64_t ts_us,
                                     rebvio_hip_pair_out* out, int* keylines);
+/* push_frame_px_device with a per-frame detection mask (rows*cols bytes in device memory; see rebvio_hip_set_detection_mask). */
+int rebvio_hip_push_frame_px_masked_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, const uint8_t* mask_dev, uint64_t ts_us,
+                                           rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_next_record(rebvio_hip_ctx* ctx, rebvio_hip_pair_out* out, int* keylines);
 /* Frame pairs the streaming driver has queued on the device so far (a measurement aid: pairs are queued in groups, so a short
  * window of pushes may start a few pairs more or fewer than it pushes frames). */
@@ -340,6 +364,10 @@ int rebvio_hip_batch_push_u8_device(rebvio_hip_batch* b, const uint8_t* const* f
 /* The same with every lane's frame in the REBVIO_HIP_PX_* format `fmt` (dense in device memory; see rebvio_hip_detect_px). */
 int rebvio_hip_batch_push_px_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, uint64_t ts_us,
                                     rebvio_hip_pair_out* out, int* keylines);
+/* The same with a per-frame detection mask for every lane: masks_dev[l] = lane l's mask (rows*cols bytes in device memory), or
+ * NULL for none (see rebvio_hip_set_detection_mask; a lane's static mask applies as well). */
+int rebvio_hip_batch_push_px_masked_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, const uint8_t* const* masks_dev,
+                                           uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_batch_next_records(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_batch_flush(rebvio_hip_batch* b);
 

@@ -72,6 +72,8 @@ SIGNATURES = {
     "rebvio_hip_detect_px": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(_vp)]),
     "rebvio_hip_detect_px_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.POINTER(_vp)]),
     "rebvio_hip_front_end_px": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp]),
+    "rebvio_hip_set_detection_mask": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "rebvio_hip_detect_px_masked_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_uint64, C.POINTER(_vp)]),
     "rebvio_hip_detector_state": (C.c_int, [_vp, _fp, _fp, _ip]),
     "rebvio_hip_map_size": (C.c_int, [_vp]),
     "rebvio_hip_map_threshold": (C.c_float, [_vp]),
@@ -108,6 +110,7 @@ SIGNATURES = {
     "rebvio_hip_push_frame_u8": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_push_frame_px": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_push_frame_px_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_push_frame_px_masked_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_next_record": (C.c_int, [_vp, C.POINTER(PairOut), _ip]),
     "rebvio_hip_pairs_started": (C.c_uint64, [_vp]),
     "rebvio_hip_flush": (C.c_int, [_vp]),
@@ -117,6 +120,8 @@ SIGNATURES = {
     "rebvio_hip_batch_lane": (_vp, [_vp, C.c_int]),
     "rebvio_hip_batch_push_u8_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_batch_push_px_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_batch_push_px_masked_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_uint64, C.POINTER(PairOut),
+                                                         _ip]),
     "rebvio_hip_batch_next_records": (C.c_int, [_vp, C.POINTER(PairOut), _ip]),
     "rebvio_hip_batch_flush": (C.c_int, [_vp]),
     "rebvio_hip_test_glue": (C.c_int, [_vp, _fp, _fp, C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.c_float, _fp, _fp, _fp,
@@ -172,6 +177,31 @@ def _px_frame(frame: np.ndarray, fmt: int, rows: int, cols: int):
     else:
         assert frame.shape == (rows, cols, bpp) and frame.strides[1:] == (bpp, 1), (frame.shape, frame.strides)
     return _vp(frame.ctypes.data), frame.strides[0]
+
+
+def _dev_addr(a, nbytes: int, device: int, what: str, dtypes=("uint8",)) -> int:
+    """Device address of a frame or detection mask: an int is taken as it is; a torch CUDA tensor is checked (dtype, size,
+    contiguity, device) and torch's current stream on it is synchronised, because the library's streams are private and would
+    not wait for the kernels that wrote it. The tensor must stay alive and unchanged as rebvio_hip.h says."""
+    if isinstance(a, int) or isinstance(a, np.integer):
+        return int(a)
+    import torch
+    if not isinstance(a, torch.Tensor):
+        raise TypeError(f"{what}: a device address or a torch tensor, not {type(a).__name__}")
+    if str(a.dtype).replace("torch.", "") not in dtypes:
+        raise TypeError(f"{what}: dtype {a.dtype}, expected one of {dtypes}")
+    if not a.is_cuda or a.device.index != device:
+        raise ValueError(f"{what}: tensor on {a.device}, the context runs on cuda:{device}")
+    if not a.is_contiguous() or a.numel() * a.element_size() != nbytes:
+        raise ValueError(f"{what}: a dense tensor of {nbytes} bytes expected, got shape {tuple(a.shape)} (contiguous: {a.is_contiguous()})")
+    torch.cuda.current_stream(a.device).synchronize()
+    return a.data_ptr()
+
+
+def _mask_addr(m, rows: int, cols: int, device: int, what: str) -> int:
+    if not (isinstance(m, int) or isinstance(m, np.integer)) and tuple(getattr(m, "shape", ())) != (rows, cols):
+        raise ValueError(f"{what}: mask of shape {tuple(getattr(m, 'shape', ()))}, expected ({rows}, {cols})")
+    return _dev_addr(m, rows * cols, device, what, ("uint8", "bool"))
 
 
 class HipError(RuntimeError):
@@ -354,6 +384,32 @@ class Context:
         _chk(lib().rebvio_hip_detect_px_device(self.h, _vp(dev_addr), fmt, ts_us, C.byref(h)))
         return Map(self, h)
 
+    def set_detection_mask(self, mask):
+        """Static detection mask (rebvio_hip_set_detection_mask): a 2-D array of shape (rows, cols), any dtype, non-zero = "keylines
+        may come from here"; None clears it. Applies from the next frame on."""
+        if mask is None:
+            _chk(lib().rebvio_hip_set_detection_mask(self.h, None, 0))
+            return
+        if hasattr(mask, "detach"):  # a torch tensor, wherever it lives
+            mask = mask.detach().cpu().numpy()
+        mask = np.asarray(mask)
+        if mask.shape != (self.rows, self.cols):
+            raise ValueError(f"set_detection_mask: shape {mask.shape}, expected ({self.rows}, {self.cols})")
+        m = np.ascontiguousarray(mask != 0, np.uint8)
+        _chk(lib().rebvio_hip_set_detection_mask(self.h, _vp(m.ctypes.data), self.cols))
+
+    def _frame_addr(self, frame, fmt: int) -> int:
+        return _dev_addr(frame, self.rows * self.cols * PX_BPP[fmt] if 0 <= fmt < len(PX_BPP) else 0, self.p.device_id, "frame")
+
+    def detect_px_masked_device(self, frame, fmt: int, mask, ts_us=0) -> Map:
+        """detect_px_device with a per-frame detection mask; frame and mask: device addresses or torch CUDA tensors (uint8 frame,
+        uint8 / bool (rows, cols) mask)."""
+        fa = self._frame_addr(frame, fmt)
+        ma = _mask_addr(mask, self.rows, self.cols, self.p.device_id, "detect_px_masked_device")
+        h = _vp()
+        _chk(lib().rebvio_hip_detect_px_masked_device(self.h, _vp(fa), fmt, _vp(ma), ts_us, C.byref(h)))
+        return Map(self, h)
+
     def front_end_px(self, frame: np.ndarray, fmt: int) -> np.ndarray:
         ptr, pitch = _px_frame(frame, fmt, self.rows, self.cols)
         out = np.empty((self.rows, self.cols), np.float32)
@@ -523,6 +579,15 @@ class Context:
         _chk(lib().rebvio_hip_push_frame_px_device(self.h, _vp(dev_addr), fmt, ts_us, C.byref(out), C.byref(n)))
         return out, n.value
 
+    def push_frame_px_masked_device(self, frame, fmt: int, mask, ts_us: int):
+        """push_frame_px_device with a per-frame detection mask (device addresses or torch CUDA tensors, see detect_px_masked_device)."""
+        fa = self._frame_addr(frame, fmt)
+        ma = _mask_addr(mask, self.rows, self.cols, self.p.device_id, "push_frame_px_masked_device")
+        out = PairOut()
+        n = C.c_int()
+        _chk(lib().rebvio_hip_push_frame_px_masked_device(self.h, _vp(fa), fmt, _vp(ma), ts_us, C.byref(out), C.byref(n)))
+        return out, n.value
+
     def test_glue(self, vel, JtJ6, F, sigma_rho_min, accept_mask, xrv, n_new, frame_dt, Bg, W_Bg, R_prior):
         """The pair glue on the device and on the host from the same inputs: ((out, state[22], second[44 words]) per side)."""
         vel, pv = _f(vel)
@@ -593,6 +658,7 @@ class Batch:
         self.h = h
         self.lanes = [Context(params, _handle=lib().rebvio_hip_batch_lane(h, l)) for l in range(lanes)]
         self._frames = (_vp * lanes)()
+        self._masks = (_vp * lanes)()
         self._out = (PairOut * lanes)()
         self._n = (C.c_int * lanes)()
 
@@ -606,6 +672,16 @@ class Batch:
         for l, a in enumerate(dev_addrs):
             self._frames[l] = int(a)
         _chk(lib().rebvio_hip_batch_push_px_device(self.h, self._frames, fmt, ts_us, self._out, self._n))
+        return self._out, self._n
+
+    def push_px_masked_device(self, frames, fmt: int, masks, ts_us: int):
+        """push_px_device with a per-frame detection mask per lane: masks[l] is a device address, a torch CUDA tensor or None (no
+        per-frame mask for lane l); frames[l] a device address or a torch CUDA tensor."""
+        rows, cols, dev = self.p.rows, self.p.cols, self.p.device_id
+        for l in range(self.B):
+            self._frames[l] = self.lanes[l]._frame_addr(frames[l], fmt)
+            self._masks[l] = None if masks[l] is None else _mask_addr(masks[l], rows, cols, dev, "batch push_px_masked_device")
+        _chk(lib().rebvio_hip_batch_push_px_masked_device(self.h, self._frames, fmt, self._masks, ts_us, self._out, self._n))
         return self._out, self._n
 
     def flush(self):

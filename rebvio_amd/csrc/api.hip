@@ -309,6 +309,9 @@ struct rebvio_hip_ctx {
   uint64_t pin_next = 0;
   int2* undist_map = nullptr;      // fixed-point source coordinates (null: no lens distortion, front end = x3 only)
   float* undist_img[kDetPar]{};    // undistorted fp32 frame, buffered like dog2 / mag2
+  uint8_t* dmask_buf = nullptr;    // static detection mask, rows*cols bytes (rebvio_hip_set_detection_mask; allocated on first use)
+  const uint8_t* dmask = nullptr;  // dmask_buf while a static mask is set, else null
+  rebvio_hip_batch* batch = nullptr;  // the batch this context is a lane of (null: a stand-alone context)
   rebvio_hip_keyline* aos_dev = nullptr;
   int* scratch_i = nullptr;  // 2 * rows*cols ints (df decode)
   float* diag0 = nullptr;
@@ -391,6 +394,8 @@ struct rebvio_hip_ctx {
     int pin_slot = -1;      // host-frame entries: pinned ring slot to copy to `img` (device staging frame) ahead of the scans
     size_t pin_bytes = 0;
     int fmt = 0;            // pixel format of a u8 frame (pixel_format.hpp)
+    const uint8_t* mask_static = nullptr;  // detection masks of this frame (null: none): the context's static mask ...
+    const uint8_t* mask_frame = nullptr;   // ... and the caller's per-frame device mask
   };
   std::mutex det_mu;
   std::string det_error;  // a detection failed half way (detect_failed): every later detect / push reports -8 with it
@@ -650,7 +655,7 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
   HIPCHK(hipStreamWaitEvent(c->s_key, c->ev_scan[b], 0));
   launch_scale_space(c->s_key, c->K, img, is_u8, sb, c->widths, db.rowcount, 2);
   if (m->has_done) HIPCHK(hipStreamWaitEvent(c->s_key, m->done_ref ? m->done_ref : m->done, 0));
-  launch_keylines(c->s_key, c->K, sb, db, m->d, j.det_in, j.det_out, j.prev_st, c->widths);
+  launch_keylines(c->s_key, c->K, sb, db, m->d, j.det_in, j.det_out, j.prev_st, c->widths, j.mask_static, j.mask_frame);
   HIPCHK(hipGetLastError());
   // distance field of this map, behind its keylines on the same stream (stream order is the dependency)
   launch_df_build(c->s_key, c->K, m->d, j.det_out, true);
@@ -660,8 +665,10 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
   return 0;
 }
 
-// caller-thread half: takes a pooled map and fixes the servo-state ring slots of this frame
-int detect_prepare(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_ctx::DetJob* job, int fmt = 0) {
+// caller-thread half: takes a pooled map and fixes the servo-state ring slots of this frame (and its detection masks: the
+// context's static mask as it is now, mask_frame the caller's per-frame device mask or null)
+int detect_prepare(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t ts, rebvio_hip_ctx::DetJob* job, int fmt = 0,
+                   const uint8_t* mask_frame = nullptr) {
   rebvio_hip_map* m = acquire_map(c);
   if (!m) return fail_msg("edge-map pool exhausted (release maps or raise map_pool)", -2);
   m->ts = ts;
@@ -671,6 +678,8 @@ int detect_prepare(rebvio_hip_ctx* c, const void* img_dev, int is_u8, uint64_t t
   job->img = img_dev;
   job->is_u8 = is_u8;
   job->fmt = fmt;
+  job->mask_static = c->dmask;
+  job->mask_frame = mask_frame;
   job->det_in = c->det + (c->frame_index % kDetRing);
   job->det_out = c->det + ((c->frame_index + 1) % kDetRing);
   job->prev_st = c->last_detected ? c->last_detected->d.st : nullptr;
@@ -698,9 +707,10 @@ int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, siz
 // pushes ran at 10.2-10.7 k frames/s with the worker and at 12.9-13.0 k without it)
 // img_dev: the frame in device memory, or (host != null) the device staging frame that a host frame is copied to. A host frame
 // (rows of row_bytes, pitch_bytes apart) goes through the pinned ring; detect_launch queues its copy ahead of the scans, on the
-// scan stream (stream order is reuse order). fmt: pixel format of a u8 frame (pixel_format.hpp).
+// scan stream (stream order is reuse order). fmt: pixel format of a u8 frame (pixel_format.hpp). mask_frame: per-frame detection
+// mask in device memory (null: none).
 int detect(rebvio_hip_ctx* c, const void* img_dev, int is_u8, int fmt, uint64_t ts, rebvio_hip_map** out, const void* host = nullptr,
-           size_t pitch_bytes = 0, size_t row_bytes = 0) {
+           size_t pitch_bytes = 0, size_t row_bytes = 0, const uint8_t* mask_frame = nullptr) {
   {
     std::lock_guard<std::mutex> lk(c->det_mu);
     if (!c->det_error.empty()) return fail_msg(c->det_error.c_str(), -8);
@@ -708,7 +718,7 @@ int detect(rebvio_hip_ctx* c, const void* img_dev, int is_u8, int fmt, uint64_t 
   rebvio_hip_ctx::DetJob job;
   int rc = host ? stage_host_frame(c, host, pitch_bytes, row_bytes, &job.pin_slot, &job.pin_bytes) : 0;
   if (rc) return rc;
-  rc = detect_prepare(c, img_dev, is_u8, ts, &job, fmt);
+  rc = detect_prepare(c, img_dev, is_u8, ts, &job, fmt, mask_frame);
   if (rc) return rc;
   const auto t0 = std::chrono::steady_clock::now();
   rc = detect_launch(c, job);
@@ -1299,7 +1309,7 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
   c->pool.clear();
   void* dptr[] = {c->sb.a[0], c->sb.a[1], c->sb.b[0], c->sb.b[1], c->sb.dog, c->sb.mag, c->db.stash, c->db.bits,
                   c->db.rowcount, c->det, c->img_dev, c->img8_dev, c->aos_dev, c->scratch_i, c->diag0, c->diag1, c->lm,
-                  c->part, c->xrv_part, c->hist, c->fscratch};
+                  c->part, c->xrv_part, c->hist, c->fscratch, c->dmask_buf};
   for (void* p : dptr)
     if (p) (void)hipFree(p);
   for (int f = 0; f < 2; ++f)
@@ -1400,6 +1410,15 @@ int rebvio_hip_detect_px_device(rebvio_hip_ctx* c, const void* frame_dev, int fm
   if (fmt == px::GRAY8) return rebvio_hip_detect_u8_device(c, static_cast<const uint8_t*>(frame_dev), ts_us, out);
   HIPCHK(hipSetDevice(c->device));
   return detect(c, frame_dev, 1, fmt, ts_us, out);
+}
+
+int rebvio_hip_detect_px_masked_device(rebvio_hip_ctx* c, const void* frame_dev, int fmt, const uint8_t* mask_dev, uint64_t ts_us,
+                                       rebvio_hip_map** out) {
+  int rc = check_px(c, "detect_px_masked_device", frame_dev, fmt, false, 0);
+  if (rc == 0 && !mask_dev) rc = fail_msg("detect_px_masked_device: null mask", -3);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  return detect(c, frame_dev, 1, fmt, ts_us, out, nullptr, 0, 0, mask_dev);
 }
 
 int rebvio_hip_set_undistort(rebvio_hip_ctx* c, const float K4[4], const float D5[5]) {
@@ -2369,7 +2388,7 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
 
 namespace {
 int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame_host, size_t host_pitch, uint64_t ts_us, rebvio_hip_pair_out* out,
-               int* keylines, int fmt = 0) {
+               int* keylines, int fmt = 0, const uint8_t* mask_frame = nullptr) {
   // Software pipeline over the three HIP streams of the context:
   //   scan / keyline streams : frame f (this call)
   //   track stream           : see the comment above stream_wait_maps
@@ -2394,7 +2413,7 @@ int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame
     const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
     rc = detect(c, u8_staging(c, fmt), 1, fmt, ts_us, &m, frame_host, host_pitch ? host_pitch : rowb, rowb);
   } else {
-    rc = detect(c, frame_dev, 1, fmt, ts_us, &m);
+    rc = detect(c, frame_dev, 1, fmt, ts_us, &m, nullptr, 0, 0, mask_frame);
   }
   if (rc) return rc;
   const auto td1 = std::chrono::steady_clock::now();
@@ -2438,6 +2457,14 @@ int rebvio_hip_push_frame_px(rebvio_hip_ctx* c, const void* frame_host, size_t p
   const int rc = check_px(c, "push_frame_px", frame_host, fmt, true, pitch_bytes);
   if (rc) return rc;
   return push_frame(c, nullptr, static_cast<const uint8_t*>(frame_host), pitch_bytes, ts_us, out, keylines, fmt);
+}
+
+int rebvio_hip_push_frame_px_masked_device(rebvio_hip_ctx* c, const void* frame_dev, int fmt, const uint8_t* mask_dev, uint64_t ts_us,
+                                           rebvio_hip_pair_out* out, int* keylines) {
+  int rc = check_px(c, "push_frame_px_masked_device", frame_dev, fmt, false, 0);
+  if (rc == 0 && !mask_dev) rc = fail_msg("push_frame_px_masked_device: null mask", -3);
+  if (rc) return rc;
+  return push_frame(c, static_cast<const uint8_t*>(frame_dev), nullptr, 0, ts_us, out, keylines, fmt, mask_dev);
 }
 
 uint64_t rebvio_hip_pairs_started(rebvio_hip_ctx* c) { return c->pair_seq; }
@@ -2760,6 +2787,8 @@ struct rebvio_hip_batch {
     std::vector<rebvio_hip_map*> maps;
     bool lens;
     int fmt = 0;  // pixel format of every lane's frame
+    bool masked = false;  // some lane has a detection mask: the masked candidate kernel, with `masks`
+    LaneMasks masks{};
   };
   std::thread det_thread;
   std::mutex det_mu;
@@ -2795,7 +2824,7 @@ int batch_detect_launch(rebvio_hip_batch* b, const rebvio_hip_batch::DetStep& j)
   HIPCHK(hipEventRecord(b->ev_scan[par], b->st.s_det));
   HIPCHK(hipStreamWaitEvent(b->st.s_key, b->ev_scan[par], 0));
   if (j.reuse_done) HIPCHK(hipStreamWaitEvent(b->st.s_key, j.reuse_done, 0));
-  launch_keylines_b(b->st.s_key, b->K, B, b->ls_dev, b->maptab_dev, j.dyn);
+  launch_keylines_b(b->st.s_key, b->K, B, b->ls_dev, b->maptab_dev, j.dyn, j.masked ? &j.masks : nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(b->ev_flag[par], b->st.s_key));
   b->ev_flag_used[par] = true;
@@ -3010,6 +3039,7 @@ int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_ba
     const int rc = rebvio_hip_create(&pl, &c);
     t_adopt_streams = nullptr;
     if (rc) return rc;
+    c->batch = b;
     b->lane.push_back(c);
   }
   b->K = b->lane[0]->K;
@@ -3080,7 +3110,9 @@ int rebvio_hip_batch_test_forge_record_stamp(rebvio_hip_batch* b) {
 }
 rebvio_hip_ctx* rebvio_hip_batch_lane(rebvio_hip_batch* b, int lane) { return (lane >= 0 && lane < b->B) ? b->lane[lane] : nullptr; }
 
-static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines) {
+// masks_dev: this step's per-frame detection mask of every lane (null array, or a null entry: none)
+static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines,
+                      const uint8_t* const* masks_dev = nullptr) {
   HIPCHK(hipSetDevice(b->device));
   if (b->poisoned) return fail_msg("batch: an earlier step failed half way; the lanes are out of lock-step (destroy the batch)", -11);
   const int B = b->B;
@@ -3126,11 +3158,13 @@ static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fm
   LaneDynB dyn{};
   const int par = (int)(b->step % kDetPar);
   rebvio_hip_map* last_reused = nullptr;
+  LaneMasks masks{};
+  bool masked = false;
   for (int l = 0; l < B; ++l) {
     rebvio_hip_ctx* c = b->lane[l];
     rebvio_hip_ctx::DetJob job;
     c->min_pool = std::min(kLaneMaps - 2, b->lead + 3 * b->group + 3);
-    int rc = detect_prepare(c, frames_dev[l], 1, ts_us, &job, fmt);
+    int rc = detect_prepare(c, frames_dev[l], 1, ts_us, &job, fmt, masks_dev ? masks_dev[l] : nullptr);
     if (rc == 0) {
       rebvio_hip_map* m = job.m;
       if (m->tab_idx < 0 || std::memcmp(&m->canon.pos, &m->d.pos, sizeof(void*)) != 0)  // a map the pool has just grown by
@@ -3158,6 +3192,11 @@ static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fm
     d.parity = (unsigned char)par;
     d.det_in = (unsigned char)(job.det_in - c->det);
     d.det_out = (unsigned char)(job.det_out - c->det);
+    // detection masks: the lane's static mask as it is at this push (rebvio_hip_set_detection_mask waits for the steps queued
+    // before it), and this step's per-frame mask
+    masks.stat[l] = job.mask_static;
+    masks.frame[l] = job.mask_frame;
+    masked = masked || job.mask_static || job.mask_frame;
   }
   rebvio_hip_batch::DetStep job;
   job.dyn = dyn;
@@ -3168,6 +3207,8 @@ static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fm
   job.maps = fr.m;
   job.lens = b->lens;
   job.fmt = fmt;
+  job.masked = masked;
+  job.masks = masks;
   for (auto* m : fr.m) m->enqueued.store(0, std::memory_order_relaxed);
   if (!b->det_thread.joinable()) b->det_thread = std::thread(batch_det_worker, b);
   {
@@ -3209,6 +3250,42 @@ int rebvio_hip_batch_push_px_device(rebvio_hip_batch* b, const void* const* fram
     if (rc) return rc;
   }
   return batch_push(b, frames_dev, fmt, ts_us, out, keylines);
+}
+
+int rebvio_hip_batch_push_px_masked_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, const uint8_t* const* masks_dev,
+                                           uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines) {
+  if (!frames_dev) return fail_msg("batch_push_px_masked_device: null frame array", -3);
+  if (!masks_dev) return fail_msg("batch_push_px_masked_device: null mask array", -3);
+  for (int l = 0; l < b->B; ++l) {
+    const int rc = check_px(b->lane[l], "batch_push_px_masked_device", frames_dev[l], fmt, false, 0);
+    if (rc) return rc;
+  }
+  return batch_push(b, frames_dev, fmt, ts_us, out, keylines, masks_dev);
+}
+
+// Static detection mask of a context (a batch lane's included). The candidate kernels of the frames queued so far read the old
+// mask from the same buffer: a batch lane first waits until its batch's detect worker has launched every queued step, then the
+// keyline stream (where the candidate kernels run) is drained before the buffer is rewritten. Clearing needs neither: frames
+// queued from here on do not read the buffer, frames queued before it still find their mask there.
+int rebvio_hip_set_detection_mask(rebvio_hip_ctx* c, const uint8_t* mask, size_t pitch_bytes) {
+  const size_t rows = (size_t)c->P.rows, cols = (size_t)c->P.cols;
+  if (!mask) {
+    c->dmask = nullptr;
+    return 0;
+  }
+  if (pitch_bytes != 0 && pitch_bytes < cols) {
+    char buf[128];
+    std::snprintf(buf, sizeof(buf), "set_detection_mask: pitch_bytes %zu below cols %zu", pitch_bytes, cols);
+    return fail_msg(buf, -3);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (rebvio_hip_batch* b = c->batch)
+    while (b->det_done_steps.load(std::memory_order_acquire) < b->step) std::this_thread::yield();
+  HIPCHK(hipStreamSynchronize(c->s_key));
+  if (!c->dmask_buf) HIPCHK(hipMalloc(&c->dmask_buf, rows * cols));
+  HIPCHK(hipMemcpy2D(c->dmask_buf, cols, mask, pitch_bytes ? pitch_bytes : cols, cols, rows, hipMemcpyHostToDevice));
+  c->dmask = c->dmask_buf;
+  return 0;
 }
 
 int rebvio_hip_batch_next_records(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines) { return pop_records(b->q, b->B, out, keylines); }

@@ -153,7 +153,8 @@ void launch_scale_space(hipStream_t s, const KParams& p, const void* img, int im
                         int fmt = 0 /* pixel format of a u8 frame (pixel_format.hpp) */);
 void launch_smooth_n(hipStream_t s, const KParams& p, const float* img, const ScaleBufs& sb, const int* widths, int n, int* rowcount_to_zero);
 void launch_keylines(hipStream_t s, const KParams& p, const ScaleBufs& sb, const DetectBufs& db, const MapDev& m,
-                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int widths[2][3]);
+                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int widths[2][3],
+                     const uint8_t* mask_static = nullptr, const uint8_t* mask_frame = nullptr /* detection masks (null: none) */);
 // Tile grid of the keyline-driven distance-field build (shared by the binning pass in k_join_edges and the tile kernel).
 struct DfGrid {
   int T, ntx, nty;
@@ -340,6 +341,11 @@ struct LaneDyn {
 struct LaneDynB {
   LaneDyn v[kMaxLanes];
 };
+// detection masks of a step's lanes (rows * cols bytes each, null: none), an argument of the masked candidate kernel alone
+struct LaneMasks {
+  const uint8_t* stat[kMaxLanes];   // the lane context's static mask (rebvio_hip_set_detection_mask)
+  const uint8_t* frame[kMaxLanes];  // this step's per-frame mask (rebvio_hip_batch_push_px_masked_device)
+};
 __host__ __device__ inline MapDev lane_map(const MapDev* __restrict__ tab, int lane, int idx, unsigned swap) {
   MapDev m = tab[lane * kLaneMaps + idx];
   if (swap & 1u) {
@@ -441,7 +447,9 @@ __device__ __forceinline__ uint2 xcd_band_block() {
 #endif
 void launch_scale_space_b(hipStream_t s, const KParams& p, int lane0, int lanes, const LaneStatic* ls, const LaneDynB& dyn,
                           const int widths[2][3], bool lens, int fmt = 0 /* of every lane's frame */);
-void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn);
+// masks: every lane's detection masks (null: no lane has one; the unmasked candidate kernel)
+void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn,
+                       const LaneMasks* masks = nullptr);
 void launch_df_build_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn);
 void launch_lm_chain_b(hipStream_t s, const KParams& p, int lanes, int lanes_per_launch, const LaneStatic* ls, const MapDev* maptab,
                        const LaneDynB& dyn, int calls, int spec, const GlueParams& gp);

@@ -723,16 +723,35 @@ __device__ __forceinline__ float servo_threshold(const KParams& p, const DetStat
   return t;
 }
 
+// Detection masks: keep[k] = the pixel (row r_first + 4 k, column c) passes the static mask m0 and the per-frame mask m1 (null:
+// no such mask; a non-zero byte means "keylines may come from here"). Only pixels of the plane-fit interior are read.
+template <int kFlagRows>
+__device__ __forceinline__ void mask_bytes(const uint8_t* __restrict__ m0, const uint8_t* __restrict__ m1, int r_first, int c, int R,
+                                           int C, bool* keep) {
+#pragma unroll
+  for (int k = 0; k < kFlagRows / 4; ++k) {
+    const int r = r_first + 4 * k;
+    const bool in = r >= 2 && r < R - 2 && c >= 2 && c < C - 2;
+    const size_t i = in ? (size_t)r * C + c : 0;
+    const unsigned b0 = (in && m0) ? m0[i] : 1u;
+    const unsigned b1 = (in && m1) ? m1[i] : 1u;
+    keep[k] = in && b0 != 0u && b1 != 0u;
+  }
+}
+
 // ---- candidate test + plane fit (edge_detector.cpp:73-107) ---------------------------------------------
 // Tile = kFlagRows rows x 64 columns per workgroup of four waves; a wavefront works on one 64-pixel row segment at a time
 // (rows wave, wave + 4, ...), so a __ballot is exactly the raster-ordered candidate set of that segment. The DoG tile with
 // its two-pixel ring is staged once: (kFlagRows + 4) x 68 values for kFlagRows x 64 pixels (1.33 x; the 4-row tile of the
 // first rounds staged 2.1 x and had a quarter of the loads in flight per thread).
-template <int kFlagRows>
+// kMasked (the masked instance, picked by the host only when a detection mask is set): m0 / m1 are the static and the per-frame
+// mask (rows * cols bytes, either may be null); a pixel that fails either is skipped like one that fails the magnitude test.
+template <int kFlagRows, bool kMasked = false>
 __device__ __forceinline__ void keyline_flag_body(const float* __restrict__ dog, const float* __restrict__ mag,
                                                       KParams p, const DetState* __restrict__ det_in,
                                                       float4* __restrict__ stash, unsigned long long* __restrict__ bits,
-                                                      int* __restrict__ rowcount) {
+                                                      int* __restrict__ rowcount, const uint8_t* __restrict__ m0 = nullptr,
+                                                      const uint8_t* __restrict__ m1 = nullptr) {
   const uint2 vb = xcd_band_block();  // tile coordinates: contiguous bands of tiles per XCD (see xcd_band_block)
   __shared__ float sd[kFlagRows + 4][68];
   const int R = p.rows, C = p.cols;
@@ -750,6 +769,8 @@ __device__ __forceinline__ void keyline_flag_body(const float* __restrict__ dog,
     const int r = r0 + threadIdx.y + 4 * k;
     mgv[k] = (r >= 2 && r < R - 2 && c >= 2 && c < C - 2) ? mag[(size_t)r * C + c] : 0.0f;
   }
+  bool keep[kFlagRows / 4];  // (kMasked) the pixel passes both masks
+  if constexpr (kMasked) mask_bytes<kFlagRows>(m0, m1, r0 + threadIdx.y, c, R, C, keep);
   __syncthreads();
   const float thr = servo_threshold(p, *det_in);
   const float pn_threshold = float((2.0 * 2 + 1.0) * (2.0 * 2 + 1.0)) * p.pos_neg_threshold;
@@ -761,7 +782,7 @@ __device__ __forceinline__ void keyline_flag_body(const float* __restrict__ dog,
     if (r >= R) break;  // (whole wave)
     bool cand = false;
     float4 fit = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r >= 2 && r < R - 2 && c >= 2 && c < C - 2) {
+    if (r >= 2 && r < R - 2 && c >= 2 && c < C - 2 && (!kMasked || keep[k])) {
       const float mg = mgv[k];
       if (!(mg < mag_threshold)) {
         int pn = 0;
@@ -803,6 +824,14 @@ __global__ __launch_bounds__(256) void k_keyline_flag_b(KParams p, const LaneSta
   const LaneDyn d = dyn.v[blockIdx.z];
   keyline_flag_body<16>(gptr(L.dog2[d.parity]), gptr(L.mag2[d.parity]), p, gptr(L.det) + d.det_in, gptr(L.stash), gptr(L.bits), gptr(L.rowcount2[d.parity]));
 }
+// the masked instance: each lane's static and per-frame mask from the argument (LaneMasks), so that the kernel-argument layout
+// of every other batch kernel stays as it is
+__global__ __launch_bounds__(256) void k_keyline_flag_b_m(KParams p, const LaneStatic* __restrict__ ls, LaneDynB dyn, LaneMasks mk) {
+  const LaneStatic& L = ls[blockIdx.z];
+  const LaneDyn d = dyn.v[blockIdx.z];
+  keyline_flag_body<16, true>(gptr(L.dog2[d.parity]), gptr(L.mag2[d.parity]), p, gptr(L.det) + d.det_in, gptr(L.stash), gptr(L.bits),
+                              gptr(L.rowcount2[d.parity]), mk.stat[blockIdx.z], mk.frame[blockIdx.z]);
+}
 
 // ---- candidate test + plane fit straight from the integral images: the last box pass, DoG and squared gradient of the tile
 // (k_dog_mag) are formed in LDS instead of travelling through two per-pixel arrays and a launch of their own ----------------
@@ -810,10 +839,11 @@ __global__ __launch_bounds__(256) void k_keyline_flag_b(KParams p, const LaneSta
 // (its 3 x 3 gradient stencil sits inside it): both box averages are evaluated on (kFlagRows + 4) x 68 pixels from the two
 // integral-image tiles staged as in dog_mag_body - the same corners, operand order and reciprocals, hence the same DoG and
 // gradient bits as the unfused kernels, and from there on keyline_flag_body's statements.
-template <int kFlagRows>
+template <int kFlagRows, bool kMasked = false>  // kMasked, m0, m1: see keyline_flag_body
 __device__ __forceinline__ void keyline_flag_ii_body(const float* __restrict__ II0, const float* __restrict__ II1, int d0, int d1, KParams p,
                                                      const DetState* __restrict__ det_in, float4* __restrict__ stash,
-                                                     unsigned long long* __restrict__ bits, int* __restrict__ rowcount) {
+                                                     unsigned long long* __restrict__ bits, int* __restrict__ rowcount,
+                                                     const uint8_t* __restrict__ m0 = nullptr, const uint8_t* __restrict__ m1 = nullptr) {
   const uint2 vb = xcd_band_block();
   constexpr int kReg = kFlagRows + 4;              // rows of the DoG region
   constexpr int kTRows = kReg + kDogMaxD;          // integral-image tile: kReg + 2 h + 1 rows, h <= 5
@@ -844,6 +874,8 @@ __device__ __forceinline__ void keyline_flag_ii_body(const float* __restrict__ I
     wa[k] = row1[ca1];
     wb[k] = row1[cb1];
   }
+  bool keep[kFlagRows / 4];  // (kMasked) the mask bytes travel with the tile's loads
+  if constexpr (kMasked) mask_bytes<kFlagRows>(m0, m1, r0 + ty, c0 + tx, R, C, keep);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int k = 0; k < kIt; ++k) {
@@ -901,7 +933,7 @@ __device__ __forceinline__ void keyline_flag_ii_body(const float* __restrict__ I
     if (r >= R) break;  // (whole wave)
     bool cand = false;
     float4 fit = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r >= 2 && r < R - 2 && c >= 2 && c < C - 2) {
+    if (r >= 2 && r < R - 2 && c >= 2 && c < C - 2 && (!kMasked || keep[k])) {
       // calculateGradientMagnitude (scale_space.cpp:221-232) of this pixel
       const float dx = sa[lr + 2][tx + 3] - sa[lr + 2][tx + 1];
       const float dy = sa[lr + 3][tx + 2] - sa[lr + 1][tx + 2];
@@ -946,6 +978,13 @@ __global__ __launch_bounds__(256) void k_keyline_flag_ii(const float* __restrict
                                                          const DetState* __restrict__ det_in, float4* __restrict__ stash,
                                                          unsigned long long* __restrict__ bits, int* __restrict__ rowcount) {
   keyline_flag_ii_body<TR>(II0, II1, d0, d1, p, det_in, stash, bits, rowcount);
+}
+template <int TR>
+__global__ __launch_bounds__(256) void k_keyline_flag_ii_m(const float* __restrict__ II0, const float* __restrict__ II1, int d0, int d1, KParams p,
+                                                           const DetState* __restrict__ det_in, float4* __restrict__ stash,
+                                                           unsigned long long* __restrict__ bits, int* __restrict__ rowcount,
+                                                           const uint8_t* __restrict__ m0, const uint8_t* __restrict__ m1) {
+  keyline_flag_ii_body<TR, true>(II0, II1, d0, d1, p, det_in, stash, bits, rowcount, m0, m1);
 }
 
 __device__ __forceinline__ int wave_sum(int v) {
@@ -1804,10 +1843,14 @@ void launch_scale_space_b(hipStream_t s, const KParams& p, int lane0, int lanes,
 #undef RH_COLSCAN_B
 }
 
-void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn) {
+void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn,
+                       const LaneMasks* masks) {
   const unsigned z = (unsigned)lanes;
   const DfGrid dg = df_grid(p.rows, p.cols);
-  RH_LAUNCH(k_keyline_flag_b, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, dyn);
+  if (masks)
+    RH_LAUNCH(k_keyline_flag_b_m, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, dyn, *masks);
+  else
+    RH_LAUNCH(k_keyline_flag_b, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, dyn);
   RH_LAUNCH(k_keyline_emit_b, dim3(div_up(p.cols, 64), div_up(p.rows, 16), z), dim3(64, 4), 0, s, p, ls, maptab, dyn, 0, dg.ntx * dg.nty);
   RH_LAUNCH(k_join_edges_b, dim3(div_up(p.kmax, 256), 1, z), dim3(256), (size_t)dg.ntx * dg.nty * sizeof(int), s, p, maptab, dyn, dg.T, dg.ntx,
             dg.nty);
@@ -1837,12 +1880,17 @@ void launch_df_build_b(hipStream_t s, const KParams& p, int lanes, const LaneSta
 }
 
 void launch_keylines(hipStream_t s, const KParams& p, const ScaleBufs& sb, const DetectBufs& db, const MapDev& m,
-                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int widths[2][3]) {
+                     const DetState* det_in, DetState* det_out, const MapState* prev_st, const int widths[2][3], const uint8_t* mask_static,
+                     const uint8_t* mask_frame) {
   const DfGrid dg = df_grid(p.rows, p.cols);
   const dim3 gt(div_up(p.cols, 64), div_up(p.rows, kTileRowsSingle));
   // sb.a[] hold the third filter pass's integral images (launch_scale_space part 2)
-  RH_LAUNCH(k_keyline_flag_ii<kTileRowsSingle>, gt, dim3(64, 4), 0, s, (const float*)sb.a[0], (const float*)sb.a[1], widths[0][2], widths[1][2], p,
-            det_in, db.stash, db.bits, db.rowcount);
+  if (mask_static || mask_frame)
+    RH_LAUNCH(k_keyline_flag_ii_m<kTileRowsSingle>, gt, dim3(64, 4), 0, s, (const float*)sb.a[0], (const float*)sb.a[1], widths[0][2], widths[1][2],
+              p, det_in, db.stash, db.bits, db.rowcount, mask_static, mask_frame);
+  else
+    RH_LAUNCH(k_keyline_flag_ii<kTileRowsSingle>, gt, dim3(64, 4), 0, s, (const float*)sb.a[0], (const float*)sb.a[1], widths[0][2], widths[1][2], p,
+              det_in, db.stash, db.bits, db.rowcount);
   RH_LAUNCH(k_keyline_emit<kTileRowsSingle>, gt, dim3(64, 4), 0, s, p, m, (const float4*)db.stash, (const unsigned long long*)db.bits,
             (const int*)db.rowcount, det_in, det_out, prev_st, 0, dg.ntx * dg.nty);
   RH_LAUNCH(k_join_edges, dim3(div_up(p.kmax, 256)), dim3(256), (size_t)dg.ntx * dg.nty * sizeof(int), s, p, m, dg.T, dg.ntx, dg.nty);

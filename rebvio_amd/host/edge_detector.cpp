@@ -34,4 +34,15 @@ rebvio::EdgeMap::SharedPtr EdgeDetector::detect(rebvio::types::Image& image) {
   return map;
 }
 
+void EdgeDetector::setDetectionMask(const cv::Mat& mask) {
+  rebvio_hip_ctx* ctx = session_->ctx();
+  if (mask.empty()) {
+    backend::check("rebvio_hip_set_detection_mask", rebvio_hip_set_detection_mask(ctx, nullptr, 0));
+    return;
+  }
+  if (mask.type() != CV_8UC1 || mask.rows != (int)camera_->rows_ || mask.cols != (int)camera_->cols_)
+    backend::fail("EdgeDetector::setDetectionMask: the mask must be CV_8UC1 of the camera's size", -1);
+  backend::check("rebvio_hip_set_detection_mask", rebvio_hip_set_detection_mask(ctx, mask.ptr<unsigned char>(0), mask.step));
+}
+
 }  // namespace rebvio

@@ -78,7 +78,20 @@ void Rebvio::imageCallback(rebvio::types::Image&& image) {
     image.data = camera_.undistort(img);
   }  // else: the u8 frame (MONO8, BGR8 or BGRA8) goes to the device as it is; grey conversion, x3 and undistort run there
   image_buffer_.push(image);
+  image_mask_buffer_.push(mask_);
   ++num_images_;
+}
+
+void Rebvio::setDetectionMask(const cv::Mat& mask) {
+  std::shared_ptr<const cv::Mat> m;
+  if (!mask.empty()) {
+    if (mask.type() != CV_8UC1 || mask.rows != (int)camera_.rows_ || mask.cols != (int)camera_.cols_)
+      backend::fail("Rebvio::setDetectionMask: the mask must be CV_8UC1 of the camera's size", -1);
+    m = std::make_shared<const cv::Mat>(mask.clone());
+  }
+  // the acquisition thread hands it to the detector in front of the first frame queued from here on
+  std::lock_guard<std::mutex> guard(image_buffer_mutex_);
+  mask_ = m;
 }
 
 void Rebvio::imuCallback(rebvio::types::Imu&& imu) {
@@ -102,14 +115,18 @@ void Rebvio::waitIdle() {
 
 void Rebvio::dataAcquisitionProcess() {
   REBVIO_INFO("Starting Data Acquisition Process..");
+  std::shared_ptr<const cv::Mat> mask_set;  // the detection mask the detector has now
   while (run_) {
     rebvio::types::Image img;
+    std::shared_ptr<const cv::Mat> mask;
     bool have = false;
     {
       std::lock_guard<std::mutex> guard(image_buffer_mutex_);
       if (!image_buffer_.empty()) {
         img = image_buffer_.front();
         image_buffer_.pop();
+        mask = image_mask_buffer_.front();
+        image_mask_buffer_.pop();
         have = true;
       }
     }
@@ -127,6 +144,10 @@ void Rebvio::dataAcquisitionProcess() {
       }
       if (queued < 8 || !run_) break;
       std::this_thread::sleep_for(std::chrono::microseconds(50));
+    }
+    if (mask != mask_set) {  // (this thread launches every detection: the frames detected so far keep their mask)
+      edge_detector_.setDetectionMask(mask ? *mask : cv::Mat());
+      mask_set = mask;
     }
     static const bool acq_timers = std::getenv("REBVIO_HOST_TIMERS") != nullptr;
     const auto td0 = std::chrono::steady_clock::now();

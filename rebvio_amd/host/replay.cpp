@@ -5,6 +5,8 @@
 // (first = the frame at 15 s) this replays what ros_rebvio/test/test_ros_rebvio.cpp checks against its golden file.
 // --colour: RGB(A) PNG frames go to rebvio::Rebvio as CV_8UC3 / CV_8UC4 (OpenCV's channel order) and are converted to grey on the
 // device, instead of to luma while they are read; the odometry is the same.
+// --mask mask.png: a grey PNG of the frames' size as the detection mask (Rebvio::setDetectionMask): keylines come only from pixels
+// whose byte is non-zero (in undistorted coordinates when a lens model is given).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -17,13 +19,18 @@
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
-  std::string asl, raw, imu, out;
+  std::string asl, raw, imu, out, mask_png;
   int W = 0, H = 0;
   size_t first = 0, count = (size_t)-1;
   uint64_t dt = 50000;
   bool euroc = false, colour = false;
   float cam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
+  auto usage = [&]() {
+    std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
+                 "[--mask mask.png] --out file\n", argv[0]);
+    return 2;
+  };
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -43,6 +50,10 @@ int main(int argc, char** argv) {
     else if (a == "--dt") dt = (uint64_t)std::atoll(next());
     else if (a == "--euroc") euroc = true;
     else if (a == "--colour") colour = true;
+    else if (a == "--mask") {
+      if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0) return usage();
+      mask_png = argv[++i];
+    }
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
     else if (a == "--camera") {
@@ -54,10 +65,7 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if ((asl.empty() == raw.empty()) || out.empty()) {
-    std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] --out file\n", argv[0]);
-    return 2;
-  }
+  if ((asl.empty() == raw.empty()) || out.empty()) return usage();
   try {
     std::unique_ptr<rebvio::io::StreamSource> src;
     if (!asl.empty()) src.reset(new rebvio::io::EurocReader(asl, "cam0", "imu0", colour));
@@ -88,6 +96,18 @@ int main(int argc, char** argv) {
     if (min_matches >= 0) config.core.global_min_matches_threshold = (unsigned)min_matches;
     rebvio::io::OdometryWriter writer(out);
     rebvio::Rebvio rebvio(config);
+    if (!mask_png.empty()) {
+      const rebvio::io::PngPixels m = rebvio::io::readPngPixels(mask_png);
+      if (m.format != REBVIO_HIP_PX_GRAY8) {
+        std::fprintf(stderr, "error: mask %s is not a grey PNG\n", mask_png.c_str());
+        return 1;
+      }
+      if (m.data.rows != H || m.data.cols != W) {
+        std::fprintf(stderr, "error: mask %s is %dx%d, the frames are %dx%d\n", mask_png.c_str(), m.data.cols, m.data.rows, W, H);
+        return 1;
+      }
+      rebvio.setDetectionMask(m.data);
+    }
     std::mutex mu;
     size_t n_odo = 0;
     std::chrono::steady_clock::time_point t_first, t_last;
