@@ -65,13 +65,33 @@ def test_invalid_params_rejected(backend):
     # validated before any device is touched
     # keylines_max 65537: one more than the 256 record groups the LM reduction stages in LDS (search_range 20 keeps the
     # distance-field key bound, the only other limit on it, satisfied)
+    # the first sizes outside the accepted envelope (32x32 .. 4096 columns x 2548 rows) and the first search_range past 255
+    # (with a keylines_max and a match uncertainty that keep the other two limits on it satisfied)
     for kw in (dict(rows=16), dict(quantile_num_bins=500), dict(keylines_max=200000),
-               dict(keylines_max=65537, search_range=20.0), dict(keylines_max=0)):
+               dict(keylines_max=65537, search_range=20.0), dict(keylines_max=0),
+               dict(cols=4097), dict(rows=2549), dict(rows=31), dict(cols=31),
+               dict(search_range=256.0, keylines_max=1000, pixel_uncertainty_match=0.0)):
         p = backend.default_params(480, 640)
         for k, v in kw.items():
             setattr(p, k, v)
-        with pytest.raises(backend.HipError):
+        with pytest.raises(backend.HipError) as e:
             backend.Context(p)
+        assert "error -3:" in str(e.value), (kw, str(e.value))  # the parameter check's own code, with or without a device
+
+
+def test_envelope_corners_pass_the_parameter_check(backend):
+    """The corners of the accepted envelope get past validation: without a device create fails at the device query that follows it,
+    not with the parameter check's -3; with one, the context exists."""
+    import torch
+    for rows, cols, kw in ((32, 32, {}), (2548, 4096, dict(keylines_max=65536, keylines_ref=60000)),
+                           (144, 192, dict(search_range=255.0, keylines_max=2000, keylines_ref=1500, pixel_uncertainty_match=1.0))):
+        p = backend.default_params(rows, cols, **kw)
+        if torch.cuda.is_available():
+            backend.Context(p).close()
+        else:
+            with pytest.raises(backend.HipError) as e:
+                backend.Context(p)
+            assert "error -3:" not in str(e.value), str(e.value)
 
 
 def test_library_installs_no_signal_handlers(backend):

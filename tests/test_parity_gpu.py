@@ -541,6 +541,53 @@ def _record_words(po):
     return np.concatenate(out)
 
 
+def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, what, every_pair_tracks=False):
+    """frames[order] through the oracle (keyline sums in the kernels' order) and through the library, the state carried
+    independently on both sides: every word of every pair record equal through the per-pair API and through the streaming
+    driver, every keyline field of the newest map equal after the last pair. every_pair_tracks: a precondition on the oracle
+    alone - each pair ends with status 0 and at least global_min_matches_threshold LM matches (a real pair, not a failure
+    path); without it only the last pair is asked for motion and more than min_klm matches."""
+    W, H, npairs = cam.width, cam.height, len(order) - 1
+    p_o = params_for(orc_mod, cam, **kw)
+    orc = orc_mod.Oracle(p_o)
+    orc.set_sum_order("device")
+    gpu = B.Context(params_for(B, cam, **kw))
+    mo, mg, rec_o = [], [], []
+    for k, i in enumerate(order):
+        mo.append(orc.detect_u8(frames[i], k * 50000))
+        mg.append(gpu.detect_u8(frames[i], k * 50000))
+        if len(mo) > 2:
+            mo.pop(0)
+            mg.pop(0).release()
+        if k == 0:
+            continue
+        po = orc.track_pair(mo[0], mo[1])
+        if every_pair_tracks:
+            assert po.status == 0 and po.klm_num >= p_o.global_min_matches_threshold, (what, k, po.status, po.klm_num)
+        pg = gpu.track_pair(mg[0], mg[1])
+        wo, wg = _record_words(po), _record_words(pg)
+        assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
+        rec_o.append(wo)
+    assert rec_o[-1][0] != 0 and po.klm_num > min_klm
+    # the map that carries the state into the next pair (the older one is dropped after its pair, rebvio.cpp:136-139)
+    assert_keylines_equal(mo[1].keylines(), mg[1].keylines(), what=f"{what}: newest map after {npairs} pairs")
+    gpu.close()
+    # the streaming driver on the same frames: device glue, persistent speculative LM kernel, pairs queued in groups
+    ctx = B.Context(params_for(B, cam, **kw))
+    dev = ctx.upload_frames(frames)
+    got = []
+    for k, i in enumerate(order):
+        out, _ = ctx.push_frame_u8_device(dev + int(i) * W * H, k * 50000)
+        if out.status >= 0:
+            got.append(_record_words(out))
+    for out, _ in ctx.flush():
+        got.append(_record_words(out))
+    ctx.close()
+    assert len(got) == len(rec_o) == npairs
+    for k, (wo, wg) in enumerate(zip(rec_o, got)):
+        assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8])
+
+
 @pytest.mark.parametrize("stream_id,config", [(0, "c2"), (1, "c2"), (2, "c2"), (0, "c3")],
                          ids=["c2-stream0", "c2-stream1", "c2-stream2", "c3-1280x960-64k"])
 def test_whole_pipeline_is_bit_identical_with_the_sums_in_one_order(orc_mod, B, stream_id, config):
@@ -562,41 +609,7 @@ def test_whole_pipeline_is_bit_identical_with_the_sums_in_one_order(orc_mod, B, 
         W, H, npairs, kw, min_klm = 1280, 960, 9, KW_C3, 20000
         frames, cam = synth.render_stream(W, H, 8, stream_id=stream_id, density=2.0)
     order = synth.pingpong_indices(8, npairs + 1)
-    orc = orc_mod.Oracle(params_for(orc_mod, cam, **kw))
-    orc.set_sum_order("device")
-    gpu = B.Context(params_for(B, cam, **kw))
-    mo, mg, rec_o = [], [], []
-    for k, i in enumerate(order):
-        mo.append(orc.detect_u8(frames[i], k * 50000))
-        mg.append(gpu.detect_u8(frames[i], k * 50000))
-        if len(mo) > 2:
-            mo.pop(0)
-            mg.pop(0).release()
-        if k == 0:
-            continue
-        po = orc.track_pair(mo[0], mo[1])
-        pg = gpu.track_pair(mg[0], mg[1])
-        wo, wg = _record_words(po), _record_words(pg)
-        assert np.array_equal(wo, wg), (k, np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
-        rec_o.append(wo)
-    assert rec_o[-1][0] != 0 and po.klm_num > min_klm
-    # the map that carries the state into the next pair (the older one is dropped after its pair, rebvio.cpp:136-139)
-    assert_keylines_equal(mo[1].keylines(), mg[1].keylines(), what=f"{config} stream {stream_id}: newest map after {npairs} pairs")
-    gpu.close()
-    # the streaming driver on the same frames: device glue, persistent speculative LM kernel, pairs queued in groups
-    ctx = B.Context(params_for(B, cam, **kw))
-    dev = ctx.upload_frames(frames)
-    got = []
-    for k, i in enumerate(order):
-        out, _ = ctx.push_frame_u8_device(dev + int(i) * W * H, k * 50000)
-        if out.status >= 0:
-            got.append(_record_words(out))
-    for out, _ in ctx.flush():
-        got.append(_record_words(out))
-    ctx.close()
-    assert len(got) == len(rec_o) == npairs
-    for k, (wo, wg) in enumerate(zip(rec_o, got)):
-        assert np.array_equal(wo, wg), (k, np.flatnonzero(wo != wg)[:8])
+    assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, what=f"{config} stream {stream_id}")
 
 
 def test_pose_deviation_is_the_references_own_rounding_noise(orc_mod, B, c2_stream):

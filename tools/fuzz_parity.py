@@ -27,7 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-SIZES = [(640, 480), (320, 240), (752, 480), (420, 293), (192, 144), (256, 64), (132, 257), (1280, 960), (96, 80), (1000, 75)]
+SIZES = [(640, 480), (320, 240), (752, 480), (420, 293), (192, 144), (256, 64), (132, 257), (1280, 960), (96, 80), (1000, 75),
+         (2052, 40), (2112, 2048)]  # past 2048 columns: the one-lane row walk; past 4096 tiles of 32 x 32: 64-pixel distance-field tiles
 
 
 def bits_equal(a, b):
@@ -192,14 +193,14 @@ def trial_stream(O, B, synth, t):
 
 def make_trial(rng, k, stateful=False):
     W, H = SIZES[int(rng.integers(0, len(SIZES)))] if k % 7 else (640, 480)
-    if stateful and (W, H) == (1000, 75):
-        # A 1000 x 75 strip leaves extRotVel's 6x6 system nearly singular (translation along the strip against rotation about the
+    if stateful and (W, H) in ((1000, 75), (2052, 40)):
+        # A 1000 x 75 strip (a 2052 x 40 one all the more) leaves extRotVel's 6x6 system nearly singular (translation along the strip against rotation about the
         # axis across it: |X| ~ 3 where a frame gives 1e-2). There the two stand-ins for the reference's SVD back-substitution -
         # the restatement's Jacobi pseudo-inverse, the library's LDL^T in double with that pseudo-inverse as its fall-back -
         # no longer round to the same floats (observed: 5e-6 of |X|, seed 11 trial 9), and a stream's states part from that
         # pair on. The stage-wise fuzz keeps the size; whole streams are compared where the pose is observable.
         W, H = 420, 293
-    if (W, H) == (1280, 960) and rng.random() < 0.5:
+    if (W, H) in ((1280, 960), (2112, 2048)) and rng.random() < 0.5:
         W, H = 640, 480
     px = W * H
     base = max(64, int(px * 0.05))
@@ -208,7 +209,7 @@ def make_trial(rng, k, stateful=False):
     kref = min(kref, kmax)
     return dict(size=(W, H), frames=int(rng.integers(4, 7)), stream=int(rng.integers(0, 1 << 20)), density=float(rng.uniform(0.4, 2.6)),
                 kref=kref, kmax=kmax, rot=(float(rng.normal(0, 0.004)), float(rng.normal(0, 0.003))),
-                vel=[float(x) for x in rng.normal(0, 0.012, 3)], stream_frames=int(rng.integers(8, 25)) if (W, H) != (1280, 960) else 8)
+                vel=[float(x) for x in rng.normal(0, 0.012, 3)], stream_frames=int(rng.integers(8, 25)) if W * H < 1280 * 960 else 8)
 
 
 def main():
