@@ -10,6 +10,7 @@
 
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/keyline.hpp"
+#include "rebvio/types/point_cloud.hpp"
 
 struct rebvio_hip_map;
 struct rebvio_hip_ctx;
@@ -53,6 +54,10 @@ class EdgeMap {
   int directedMatch(rebvio::EdgeMap::SharedPtr map, const rebvio::types::Vector3f& vel, const rebvio::types::Matrix3f& Rvel,
                     const rebvio::types::Matrix3f& Rback, int& kf_matches, types::Float max_radius);
   int regularize1Iter();
+  // addition: the map's depth-bearing keylines as a point cloud, extracted on the device (rebvio_hip_map_point_cloud says
+  // exactly which keylines and where; the synchronous form: it waits for everything queued that concerns this map)
+  std::vector<rebvio::types::CloudPoint> pointCloud(const rebvio::types::CloudFilter& filter = rebvio::types::CloudFilter(),
+                                                    const rebvio::types::CloudPose& pose = rebvio::types::CloudPose());
 
   // --- backend plumbing (not part of the reference surface) ---
   // `keepalive` owns the backend context the handle belongs to (backend::Session): a map kept by an edge-image consumer

@@ -4,6 +4,7 @@
 //   RawReader        - dense MONO8 frames (rows*cols bytes each) + optional IMU records {int64 ts_us, float gyro[3], acc[3]}
 //   OdometryWriter   - "ts_us wx wy wz px py pz" lines, %.6f, the format of the reference's regression file
 //                      ros_rebvio/test/data/MH_03_medium_test_15s-30s_odometry.txt
+//   writePointCloudPly / readPointCloudPly - a point cloud as a binary little-endian PLY file (x, y, z, intensity)
 //   replay()         - time-ordered playback into imageCallback / imuCallback
 #pragma once
 
@@ -16,6 +17,7 @@
 #include "rebvio/types/image.hpp"
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/odometry.hpp"
+#include "rebvio/types/point_cloud.hpp"
 #include "rebvio_hip.h"
 
 namespace rebvio {
@@ -91,6 +93,17 @@ class OdometryWriter {
  private:
   std::FILE* f_;
 };
+
+// A point cloud as a PLY file, "format binary_little_endian 1.0": one vertex per point with the float properties x, y, z
+// (CloudPoint::xyz) and intensity (CloudPoint::gradient_norm), in the cloud's order; ts_us goes into a comment line. What
+// MeshLab, CloudCompare, Open3D and PCL read. Throws std::runtime_error when the file cannot be written.
+void writePointCloudPly(const std::string& path, const rebvio::types::CloudPoint* points, size_t n, uint64_t ts_us = 0);
+// Reads such a file back: x, y, z, intensity per vertex. Accepts what writePointCloudPly writes (four float properties of these
+// names in this order), nothing else. Throws std::runtime_error.
+struct PlyVertex {
+  float x, y, z, intensity;
+};
+std::vector<PlyVertex> readPointCloudPly(const std::string& path, uint64_t* ts_us = nullptr);
 
 // Plays frames [first, first+count) in time order: every IMU sample with ts <= the frame's stamp is delivered before the
 // frame (a time-ordered bag delivers them that way, ros_rebvio.cpp:108-121). Returns the number of frames delivered.

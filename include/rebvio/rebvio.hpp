@@ -20,6 +20,7 @@
 #include "rebvio/types/image.hpp"
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/odometry.hpp"
+#include "rebvio/types/point_cloud.hpp"
 
 namespace rebvio {
 
@@ -40,6 +41,14 @@ class Rebvio {
   void imuCallback(rebvio::types::Imu&& imu);
   void registerEdgeImageCallback(std::function<void(cv::Mat&, rebvio::EdgeMap::SharedPtr&)> cb);
   void registerOdometryCallback(std::function<void(rebvio::types::Odometry&)> cb);
+  // addition: the depth-bearing keylines of every published pair's new map as a point cloud (rebvio/types/point_cloud.hpp), in the
+  // odometry's frame and metric: pose = R_global, Pos, K of the record. Called once per published odometry record, right after
+  // the odometry callbacks, with the same ts_us, on the state-estimation thread; the points are valid during the call. The
+  // cloud is extracted on the device behind the pair's second half and nobody waits for it before the pair's counters are
+  // waited for anyway. While a callback is registered the next pair's first rotation is not fused into this pair's last kernel
+  // (one launch more per pair); the odometry does not change by a digit. Register before the first frame is handed in.
+  void registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb,
+                                  rebvio::types::CloudFilter filter = rebvio::types::CloudFilter());
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -72,6 +81,11 @@ class Rebvio {
   std::mutex edge_map_buffer_mutex_;
   std::vector<std::function<void(cv::Mat&, rebvio::EdgeMap::SharedPtr&)>> edge_image_callbacks_;
   std::vector<std::function<void(rebvio::types::Odometry&)>> odometry_callbacks_;
+  struct PointCloudCallback {
+    std::function<void(const rebvio::types::PointCloud&)> cb;
+    rebvio::types::CloudFilter filter;
+  };
+  std::vector<PointCloudCallback> point_cloud_callbacks_;
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };
 

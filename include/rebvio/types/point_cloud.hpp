@@ -1,0 +1,46 @@
+// Point cloud of an edge map's depth-bearing keylines (no reference counterpart: the reference hands out poses, edge images
+// and whole maps only). Records, filter and pose are layout-compatible with the C-ABI's rebvio_hip_cloud_point / _filter / _pose;
+// rebvio_hip.h defines the filter and the position of a point exactly.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace rebvio {
+namespace types {
+
+struct CloudPoint {
+  float xyz[3];          // pose.R * (pos_img / fm, 1) * pose.scale / rho + pose.t
+  float rho;             // KeyLine::rho
+  float sigma_rho;       // KeyLine::sigma_rho
+  float gradient_norm;   // KeyLine::gradient_norm ("intensity" of a sensor_msgs/PointCloud2)
+  int keyline;           // index of the source keyline in its map; strictly increasing within a cloud
+  unsigned int matches;  // KeyLine::matches
+};
+static_assert(sizeof(CloudPoint) == 32, "CloudPoint must stay layout-compatible with rebvio_hip_cloud_point");
+
+// A keyline passes when matches >= min_matches, rho_min <= rho <= rho_max and sigma_rho <= max_rel_sigma * rho.
+// The defaults are rebvio_hip_default_cloud_filter's.
+struct CloudFilter {
+  unsigned int min_matches{2};
+  float max_rel_sigma{0.5f};
+  float rho_min{1e-3f};
+  float rho_max{20.0f};
+};
+
+struct CloudPose {
+  float R[9]{1, 0, 0, 0, 1, 0, 0, 0, 1};  // row-major
+  float t[3]{0, 0, 0};
+  float scale{1.0f};
+};
+
+// What a point-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
+struct PointCloud {
+  uint64_t ts_us;            // the odometry record's stamp (= the map's)
+  CloudPose pose;            // R_global, Pos, K of that record: the points are metric, in the odometry's frame
+  const CloudPoint* points;
+  size_t size;
+};
+
+}  // namespace types
+}  // namespace rebvio

@@ -21,7 +21,9 @@ extern "C" {
 #endif
 
 /* 3: status -12 (a pair's record read before the device wrote it: sequence stamps), rebvio_hip_test_forge_record_stamp,
- *    REBVIO_HIP_DM_HEAD values compact8 / compact4 / compact1 (2: map handles outlive their context, -10) */
+ *    REBVIO_HIP_DM_HEAD values compact8 / compact4 / compact1 (2: map handles outlive their context, -10)
+ *    Added since, without a new version (additions only): the point-cloud entries rebvio_hip_default_cloud_filter,
+ *    rebvio_hip_map_point_cloud(_async), rebvio_hip_cloud_wait / _release and their three structs. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -193,6 +195,67 @@ int rebvio_hip_map_download(rebvio_hip_map* m, rebvio_hip_keyline* keylines, int
  * (round(pos[1]), round(pos[0])) set to (255,0,0). rgb_out = rows*cols*3 bytes. Synchronises. */
 int rebvio_hip_render_edge_image(rebvio_hip_map* map, const uint8_t* gray_host, uint8_t* rgb_out_host);
 
+/* The depth-bearing keylines of a map as a packed point cloud, extracted on the device by kernels of their own (an
+ * order-preserving compaction over the map's keyline arrays; nothing of the tracking kernels changes). No reference counterpart:
+ * it is what regularize1Iter / updateInverseDepth (edge_map.cpp:220-259, core.cpp:417-456) are run for.
+ * A keyline passes the filter when ALL of
+ *   matches >= min_matches,  rho >= rho_min,  rho <= rho_max,  sigma_rho <= max_rel_sigma * rho   (one rounded fp32 multiply)
+ * hold (a NaN in rho or sigma_rho fails them). A filter with rho_min <= 0, rho_min > rho_max, max_rel_sigma < 0 or a NaN field is
+ * refused (-3), so rho > 0 for every point. With fm of the context's parameters and pos_img the principal-point coordinates
+ * rotateKeylines works on (edge_map.cpp:60), every operation one IEEE fp32 operation in this order, no contraction:
+ *   u = pos_img[0] / fm;  v = pos_img[1] / fm;  z = scale / rho;  xc = u * z;  yc = v * z;  zc = z;
+ *   xyz[i] = ((R[3i] * xc + R[3i+1] * yc) + R[3i+2] * zc) + t[i]
+ * pose NULL = identity, zero, 1. Points come in ascending keyline index; `keyline` is strictly increasing and the cloud is
+ * reproducible bit for bit. *count = keylines that pass; min(count, cap) records are written (a cap below count is no error).
+ * State: the cloud shows the map's keylines as they are when the extraction runs in stream order (the rule of
+ * rebvio_hip_map_download). So a map that has since served as a pair's OLD map has been rotated into the newer frame by that pair;
+ * and a map handed to rebvio_hip_track_pair_finish_async with R_prior_next is already rotated for the next pair when its second
+ * half ends: until the next _begin has consumed that promise both entries refuse it (-7) rather than return a cloud in a frame the
+ * caller did not ask for. */
+typedef struct rebvio_hip_cloud_point {
+  float xyz[3];        /* position, see above */
+  float rho;           /* KeyLine::rho as stored */
+  float sigma_rho;     /* KeyLine::sigma_rho as stored */
+  float gradient_norm; /* KeyLine::gradient_norm ("intensity" for PointCloud2 consumers) */
+  int keyline;         /* index of the source keyline in its map */
+  unsigned int matches; /* KeyLine::matches */
+} rebvio_hip_cloud_point;
+typedef struct rebvio_hip_cloud_filter {
+  unsigned int min_matches;
+  float max_rel_sigma, rho_min, rho_max;
+} rebvio_hip_cloud_filter;
+typedef struct rebvio_hip_cloud_pose {
+  float R[9]; /* row-major */
+  float t[3];
+  float scale;
+} rebvio_hip_cloud_pose;
+typedef struct rebvio_hip_cloud rebvio_hip_cloud;
+/* min_matches 2, max_rel_sigma 0.5, rho in [1e-3, 20] (the bounds KeyLine::rho is clamped to; DESIGN.md 5e says why). */
+void rebvio_hip_default_cloud_filter(rebvio_hip_cloud_filter* f);
+/* Synchronous: waits for everything queued that concerns the map (like rebvio_hip_render_edge_image), extracts, and returns the
+ * cloud in caller memory (points_host: cap records; may be NULL with cap 0: only the count). filter NULL = the default filter.
+ * -3: null map / count, negative cap, null points with cap > 0, invalid filter, NaN in the pose - all checked before the device
+ * is touched; -10: the map's context has been destroyed; -7: see "State" above.
+ * Although it takes a map alone, this entry is a TRACK-side entry like the queued one below: the extraction runs on the track
+ * stream, so it is called from the context's tracking thread (not concurrently with a tracking call), unlike
+ * rebvio_hip_map_download / _render_edge_image. Once a cloud of a map has been extracted the map counts as used by the tracker:
+ * later rebvio_hip_map_download calls on it wait for the track stream as well. */
+int rebvio_hip_map_point_cloud(rebvio_hip_map* map, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose,
+                               rebvio_hip_cloud_point* points_host, int cap, int* count);
+/* Queued: the extraction goes on the TRACK stream in call order and the call returns at once. Called between _finish_async(k) and
+ * _begin(k+1) it sees map k exactly as pair k left it, without the host waiting for anything. The records are extracted into device
+ * memory (capacity keylines_max); a kernel on a stream of its own then writes exactly those that exist into host-visible memory,
+ * the count and a sequence stamp behind them - no copy of `capacity` records for a count the host does not have yet.
+ * rebvio_hip_cloud_wait blocks until that extraction has run: *points = host-readable records, valid until the release;
+ * *device_points = the records in device memory, for consumers that stay on the GPU (either may be NULL). A cloud
+ * whose stamp is not the extraction's own - read before it was written - is -12, never stale points. -10 after
+ * rebvio_hip_destroy. rebvio_hip_cloud_release returns the buffer to a small pool of the context (exactly once per handle; safe
+ * after rebvio_hip_destroy). */
+int rebvio_hip_map_point_cloud_async(rebvio_hip_ctx* ctx, rebvio_hip_map* map, const rebvio_hip_cloud_filter* filter,
+                                     const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud** out);
+int rebvio_hip_cloud_wait(rebvio_hip_cloud* cloud, const rebvio_hip_cloud_point** points, int* count, const void** device_points);
+void rebvio_hip_cloud_release(rebvio_hip_cloud* cloud);
+
 /* Test hook: overwrite the device keylines (count must equal the map size). */
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n);
 /* Map handles may outlive their context: after rebvio_hip_destroy the entries that take a map alone (size, threshold, download,
@@ -288,7 +351,8 @@ int rebvio_hip_track_pair_finish(rebvio_hip_ctx* ctx, rebvio_hip_map* old_map, r
  * anything: _finish_async hands over the fusion's results and returns at once; _result waits for the second half and returns
  * its counters / status (what rebvio.cpp:245-259 needs for the "insufficient matches" stop and what the odometry record carries).
  * Allowed order: begin(k), finish_async(k), begin(k+1), result(k), finish_async(k+1), ... - one result may be outstanding.
- * Between _begin and _finish(_async) of a pair only _result of the previous pair may be called.
+ * Between _begin and _finish(_async) of a pair only _result of the previous pair may be called. Between _finish_async(k) and
+ * _begin(k+1) rebvio_hip_map_point_cloud_async is allowed as well (it queues behind pair k and waits for nothing).
  * A pair's match counters ride to the host in the NEXT pair's first-half record when that pair continues from this pair's new
  * map (no copy, no extra wait); otherwise _begin / _result copy them. (Releasing that map before _result is allowed: the
  * release copies them out first.) */

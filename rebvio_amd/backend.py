@@ -22,6 +22,11 @@ KEYLINE_DTYPE = np.dtype([
     ("match_id_forward", "<i4"), ("match_id_keyframe", "<i4"), ("matches", "<u4")])
 assert KEYLINE_DTYPE.itemsize == 84
 
+# rebvio_hip_cloud_point: one record of a map's point cloud
+CLOUD_POINT_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("rho", "<f4"), ("sigma_rho", "<f4"), ("gradient_norm", "<f4"),
+                              ("keyline", "<i4"), ("matches", "<u4")])
+assert CLOUD_POINT_DTYPE.itemsize == 32
+
 
 class Params(C.Structure):
     _fields_ = [
@@ -53,6 +58,14 @@ class PairMid(C.Structure):
                 ("Xgv", C.c_float * 6), ("W_Xgv", C.c_float * 36), ("R", C.c_float * 9)]
 
 
+class CloudFilter(C.Structure):
+    _fields_ = [("min_matches", C.c_uint), ("max_rel_sigma", C.c_float), ("rho_min", C.c_float), ("rho_max", C.c_float)]
+
+
+class CloudPose(C.Structure):
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("scale", C.c_float)]
+
+
 # every symbol include/rebvio_hip.h declares: (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
@@ -80,6 +93,11 @@ SIGNATURES = {
     "rebvio_hip_map_ts": (C.c_uint64, [_vp]),
     "rebvio_hip_map_download": (C.c_int, [_vp, _vp, _ip]),
     "rebvio_hip_render_edge_image": (C.c_int, [_vp, _vp, _vp]),
+    "rebvio_hip_default_cloud_filter": (None, [C.POINTER(CloudFilter)]),
+    "rebvio_hip_map_point_cloud": (C.c_int, [_vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), _vp, C.c_int, _ip]),
+    "rebvio_hip_map_point_cloud_async": (C.c_int, [_vp, _vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), C.POINTER(_vp)]),
+    "rebvio_hip_cloud_wait": (C.c_int, [_vp, C.POINTER(_vp), _ip, C.POINTER(_vp)]),
+    "rebvio_hip_cloud_release": (None, [_vp]),
     "rebvio_hip_map_upload": (C.c_int, [_vp, _vp, C.c_int]),
     "rebvio_hip_map_release": (None, [_vp]),
     "rebvio_hip_build_distance_field": (C.c_int, [_vp, _vp]),
@@ -226,6 +244,67 @@ def default_params(rows, cols, **over) -> Params:
     return p
 
 
+def default_cloud_filter(**over) -> CloudFilter:
+    f = CloudFilter()
+    lib().rebvio_hip_default_cloud_filter(C.byref(f))
+    for k, v in over.items():
+        setattr(f, k, v)
+    return f
+
+
+def _cloud_filter(f):
+    """None (the library's default), a CloudFilter, or a dict of the fields to change from the default."""
+    if f is None or isinstance(f, CloudFilter):
+        return f
+    return default_cloud_filter(**f)
+
+
+def cloud_pose(R=None, t=None, scale=1.0) -> CloudPose:
+    p = CloudPose()
+    p.R[:] = [float(v) for v in np.asarray(np.eye(3) if R is None else R, np.float32).reshape(9)]
+    p.t[:] = [float(v) for v in np.asarray(np.zeros(3) if t is None else t, np.float32).reshape(3)]
+    p.scale = float(np.float32(scale))
+    return p
+
+
+def _cloud_pose(pose):
+    """None (identity), a CloudPose, or (R, t, scale)."""
+    if pose is None or isinstance(pose, CloudPose):
+        return pose
+    return cloud_pose(*pose)
+
+
+class Cloud:
+    """A queued point cloud (rebvio_hip_map_point_cloud_async): wait() for the records, release() when done with them."""
+
+    def __init__(self, h):
+        self.h = h
+        self.device_points = None
+
+    def wait(self, copy=True) -> np.ndarray:
+        """The records as a CLOUD_POINT_DTYPE array: a copy, or with copy=False a view of the library's buffer that is valid until
+        release(). device_points then holds the device address of the same records."""
+        pts, dev, n = _vp(), _vp(), C.c_int()
+        _chk(lib().rebvio_hip_cloud_wait(self.h, C.byref(pts), C.byref(n), C.byref(dev)))
+        self.device_points = dev.value
+        if n.value == 0:
+            return np.zeros(0, CLOUD_POINT_DTYPE)
+        buf = (C.c_char * (n.value * CLOUD_POINT_DTYPE.itemsize)).from_address(pts.value)
+        a = np.frombuffer(buf, CLOUD_POINT_DTYPE)
+        return a.copy() if copy else a
+
+    def release(self):
+        if self.h:
+            lib().rebvio_hip_cloud_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 class Map:
     def __init__(self, ctx, h):
         self.ctx, self.h = ctx, h
@@ -288,6 +367,19 @@ class Map:
         out = C.c_int(-2)
         _chk(lib().rebvio_hip_search_match(self.ctx.h, self.h, q.ctypes.data, pv, prv, prb, max_radius, C.byref(out)))
         return out.value
+
+    def point_cloud(self, filter=None, pose=None, cap=None, return_count=False):
+        """The map's depth-bearing keylines as a CLOUD_POINT_DTYPE array (rebvio_hip_map_point_cloud; filter / pose: see
+        _cloud_filter / _cloud_pose). cap: at most this many records (default: the map's size); return_count: also the number of
+        keylines that passed, which may exceed cap."""
+        if cap is None:
+            cap = self.size()
+        out = np.zeros(cap, CLOUD_POINT_DTYPE)
+        n = C.c_int()
+        _chk(lib().rebvio_hip_map_point_cloud(self.h, _cloud_filter(filter), _cloud_pose(pose), out.ctypes.data if cap else None,
+                                              cap, C.byref(n)))
+        out = out[:min(n.value, cap)]
+        return (out, n.value) if return_count else out
 
     def upload(self, kl: np.ndarray):
         kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)
@@ -547,6 +639,13 @@ class Context:
         v = [C.c_int() for _ in range(4)]
         _chk(lib().rebvio_hip_track_pair_result(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    def point_cloud_async(self, m: Map, filter=None, pose=None) -> Cloud:
+        """Queues the extraction of m's point cloud on the track stream and returns at once (allowed between
+        track_pair_finish_async(k) and track_pair_begin(k+1))."""
+        h = _vp()
+        _chk(lib().rebvio_hip_map_point_cloud_async(self.h, m.h, _cloud_filter(filter), _cloud_pose(pose), C.byref(h)))
+        return Cloud(h)
 
     def track_pair_hint_next(self, next_new: Map):
         _chk(lib().rebvio_hip_track_pair_hint_next(self.h, next_new.h))

@@ -237,8 +237,27 @@ struct rebvio_hip_map {
   // the map's own detection (`ready`), not for the track stream (which may hold another pair's parked second half)
   std::atomic<bool> trk_touched{false};
   hm::M3 pre_R{};           // ... with this rotation (per-pair API: checked against the prior the next _begin is given)
+  // per-pair API: _finish_async was given R_prior_next for this map and the next _begin has not consumed it yet - the keylines are
+  // (or will be, in stream order) in the next pair's frame: the point-cloud entries refuse the map (-7)
+  std::atomic<bool> promised{false};
   int tab_idx = -1;         // entry of this map in its lane's device map table (batch driver)
   MapDev canon{};           // ... as uploaded there (the live `d` differs from it by the ping-pong swaps only)
+};
+
+// One point cloud (rebvio_hip_map_point_cloud*): the device buffer the extraction kernels write (track stream), the host-visible
+// buffer the copy kernel fills from it (cloud stream) - head, then the records, in both - and the events behind the two. Pooled
+// per context; like a map handle it may outlive the context as a husk.
+struct rebvio_hip_cloud {
+  rebvio_hip_ctx* ctx = nullptr;
+  std::shared_ptr<LifeBlock> life;
+  CloudHdr* hdr = nullptr;     // hipHostMalloc: 64-byte head + keylines_max records
+  char* dev_buf = nullptr;     // hipMalloc, the same shape: the count at byte 0, the records at byte 64
+  void* dev = nullptr;         // device address of the records (dev_buf + 64)
+  hipEvent_t extracted{};      // recorded on the track stream behind the extraction
+  hipEvent_t done{};           // recorded on the cloud stream behind the copy to the host
+  unsigned seq = 0;            // the extraction's sequence stamp
+  int cap = 0;                 // records the extraction may write
+  bool in_use = false;
 };
 
 // A finished pair's record as the caller gets it.
@@ -420,10 +439,19 @@ struct rebvio_hip_ctx {
   int bf_cur = 0;            // slot of the pair between _begin and _finish_async
   int bf_res = -1;           // slot whose result is to be fetched (-1: none)
   bool bf_nan[2] = {false, false};
+  // point clouds: buffers (allocated on first use, kept), the block counts + ticket word of the extraction kernels, and the
+  // stamp counter. cloud_mu: the pool (rebvio_hip_cloud_release may come from any thread). The entries that queue an extraction
+  // follow the track-entry thread rule: they launch on the track stream.
+  std::mutex cloud_mu;
+  std::vector<rebvio_hip_cloud*> clouds;
+  int* cloud_scratch = nullptr;  // [kMaxRecBlocks] counts, then the ticket word
+  hipStream_t s_cloud{};         // the copies to the host: PCIe writes next to the track stream's kernels, not between them
+  unsigned cloud_seq = 0;
 };
 
 namespace {
 void release_map(rebvio_hip_map* m, hipEvent_t done_ref = nullptr, bool record_done = true);
+void free_cloud_device(rebvio_hip_cloud* cl);
 
 // A map handle whose context has been destroyed: every entry point that takes a map alone answers with this.
 inline bool map_dead(const rebvio_hip_map* m) { return !m || !m->life || m->life->dead.load(std::memory_order_acquire); }
@@ -549,6 +577,7 @@ rebvio_hip_map* acquire_map(rebvio_hip_ctx* c) {
     m->df_built = false;
     m->raster_order = false;
     m->pre_rotated = false;
+    m->promised.store(false, std::memory_order_relaxed);
     m->n_host = -1;
     m->thr_host = -1.0f;
     m->trk_waited = false;
@@ -1354,6 +1383,12 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   if (c->h_bf) (void)hipHostFree(c->h_bf);
   if (c->lm_zero) (void)hipFree(c->lm_zero);
+  for (auto* cl : c->clouds) {
+    free_cloud_device(cl);
+    if (!cl->in_use) delete cl;  // (else: the handle is still out; its release deletes the husk)
+  }
+  if (c->cloud_scratch) (void)hipFree(c->cloud_scratch);
+  if (c->s_cloud) (void)hipStreamDestroy(c->s_cloud);
   delete c;
 }
 
@@ -1559,6 +1594,207 @@ int rebvio_hip_render_edge_image(rebvio_hip_map* m, const uint8_t* gray, uint8_t
   HIPCHK(hipMemcpyAsync(rgb_out, rgb, 3 * Pn, hipMemcpyDeviceToHost, c->s_key));
   HIPCHK(hipStreamSynchronize(c->s_key));
   return 0;
+}
+
+}  // extern "C"
+
+namespace {
+int check_cloud_args(const char* who, const rebvio_hip_cloud_filter* f, const rebvio_hip_cloud_pose* pose) {
+  if (f) {
+    if (std::isnan(f->max_rel_sigma) || std::isnan(f->rho_min) || std::isnan(f->rho_max))
+      return fail_msg((std::string(who) + ": NaN in the filter").c_str(), -3);
+    if (!(f->rho_min > 0.0f)) return fail_msg((std::string(who) + ": filter rho_min must be > 0").c_str(), -3);
+    if (f->rho_min > f->rho_max) return fail_msg((std::string(who) + ": filter rho_min > rho_max").c_str(), -3);
+    if (f->max_rel_sigma < 0.0f) return fail_msg((std::string(who) + ": filter max_rel_sigma must be >= 0").c_str(), -3);
+  }
+  if (pose) {
+    bool nan = std::isnan(pose->scale);
+    for (float v : pose->R) nan = nan || std::isnan(v);
+    for (float v : pose->t) nan = nan || std::isnan(v);
+    if (nan) return fail_msg((std::string(who) + ": NaN in the pose").c_str(), -3);
+  }
+  return 0;
+}
+
+static_assert(sizeof(rebvio_hip_cloud_point) == 32 && sizeof(CloudHdr) == 64, "a cloud record is two 16-byte stores behind a 64-byte head");
+
+int alloc_cloud(rebvio_hip_ctx* c, rebvio_hip_cloud* cl) {
+  const size_t bytes = sizeof(CloudHdr) + (size_t)c->P.keylines_max * sizeof(rebvio_hip_cloud_point);
+  HIPCHK(hipHostMalloc((void**)&cl->hdr, bytes, hipHostMallocDefault));
+  std::memset(cl->hdr, 0, sizeof(CloudHdr));
+  HIPCHK(hipMalloc((void**)&cl->dev_buf, bytes));
+  cl->dev = cl->dev_buf + sizeof(CloudHdr);
+  HIPCHK(hipEventCreateWithFlags(&cl->extracted, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&cl->done, hipEventDisableTiming));
+  return 0;
+}
+
+// buffers and events of a cloud; the host struct stays (a handle the caller still holds is deleted by its release)
+void free_cloud_device(rebvio_hip_cloud* cl) {
+  if (cl->hdr) (void)hipHostFree(cl->hdr);
+  if (cl->dev_buf) (void)hipFree(cl->dev_buf);
+  if (cl->done) (void)hipEventDestroy(cl->done);
+  if (cl->extracted) (void)hipEventDestroy(cl->extracted);
+  cl->hdr = nullptr;
+  cl->dev_buf = nullptr;
+  cl->dev = nullptr;
+  cl->done = cl->extracted = hipEvent_t{};
+  cl->ctx = nullptr;
+}
+
+void release_cloud(rebvio_hip_cloud* cl) {
+  std::lock_guard<std::mutex> lk(cl->ctx->cloud_mu);
+  cl->in_use = false;
+}
+
+// Queues one extraction on the track stream; the caller holds the map's life block. cap < 0: the buffer's capacity.
+int enqueue_cloud(const char* who, rebvio_hip_map* m, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose, int cap,
+                  rebvio_hip_cloud** out) {
+  rebvio_hip_ctx* c = m->ctx;
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg((std::string(who) + ": the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
+                     "its cloud is available again once the next track_pair_begin has run").c_str(), -7);
+  HIPCHK(hipSetDevice(c->device));
+  rebvio_hip_cloud_filter f;
+  if (filter) f = *filter; else rebvio_hip_default_cloud_filter(&f);
+  CloudArgs a{};
+  a.min_matches = f.min_matches;
+  a.max_rel_sigma = f.max_rel_sigma;
+  a.rho_min = f.rho_min;
+  a.rho_max = f.rho_max;
+  for (int i = 0; i < 9; ++i) a.R[i] = pose ? pose->R[i] : (i % 4 == 0 ? 1.0f : 0.0f);
+  for (int i = 0; i < 3; ++i) a.t[i] = pose ? pose->t[i] : 0.0f;
+  a.scale = pose ? pose->scale : 1.0f;
+  a.cap = (cap < 0 || cap > c->P.keylines_max) ? c->P.keylines_max : cap;
+  std::lock_guard<std::mutex> lk(c->cloud_mu);
+  if (!c->cloud_scratch) {
+    HIPCHK(hipMalloc(&c->cloud_scratch, (kMaxRecBlocks + 1) * sizeof(int)));
+    HIPCHK(hipMemset(c->cloud_scratch, 0, (kMaxRecBlocks + 1) * sizeof(int)));
+    HIPCHK(hipStreamSynchronize(nullptr));  // (hipMemset returns before the fill has run: alloc_map)
+    HIPCHK(hipStreamCreateWithFlags(&c->s_cloud, hipStreamNonBlocking));
+  }
+  rebvio_hip_cloud* cl = nullptr;
+  for (auto* x : c->clouds)
+    if (!x->in_use) cl = x;
+  if (!cl) {
+    if (c->clouds.size() >= 64) return fail_msg((std::string(who) + ": 64 clouds are out; release some (rebvio_hip_cloud_release)").c_str(), -2);
+    cl = new rebvio_hip_cloud;
+    cl->ctx = c;
+    cl->life = c->life;
+    const int rc = alloc_cloud(c, cl);
+    if (rc) {  // nothing half-made stays in the pool
+      free_cloud_device(cl);
+      delete cl;
+      return rc;
+    }
+    c->clouds.push_back(cl);
+  }
+  // a buffer released without having been waited for: its copy to the host may still be reading the device buffer
+  if (cl->seq != 0 && hipEventQuery(cl->done) != hipSuccess) HIPCHK(hipStreamWaitEvent(c->s_trk, cl->done, 0));
+  if (++c->cloud_seq == 0) ++c->cloud_seq;  // non-zero: a fresh buffer's head reads 0
+  a.seq = cl->seq = c->cloud_seq;
+  cl->cap = a.cap;
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  void* hdr_host_dev = nullptr;  // the host-visible buffer as the device addresses it
+  HIPCHK(hipHostGetDevicePointer(&hdr_host_dev, cl->hdr, 0));
+  launch_point_cloud(c->s_trk, c->K, m->d, a, c->cloud_scratch, reinterpret_cast<int*>(cl->dev_buf), cl->dev);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(cl->extracted, c->s_trk));
+  HIPCHK(hipStreamWaitEvent(c->s_cloud, cl->extracted, 0));
+  launch_point_cloud_copy(c->s_cloud, c->K, cl->dev, reinterpret_cast<const int*>(cl->dev_buf), a,
+                          reinterpret_cast<unsigned*>(c->cloud_scratch + kMaxRecBlocks), reinterpret_cast<CloudHdr*>(hdr_host_dev),
+                          reinterpret_cast<char*>(hdr_host_dev) + sizeof(CloudHdr));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(cl->done, c->s_cloud));
+  cl->in_use = true;
+  *out = cl;
+  return 0;
+}
+
+// Waits for a queued extraction (polling, like trk_sync) and checks its stamp.
+int wait_cloud(rebvio_hip_cloud* cl, int* count) {
+  for (;;) {
+    const hipError_t e = hipEventQuery(cl->done);
+    if (e == hipSuccess) break;
+    if (e != hipErrorNotReady) HIPCHK(e);
+    std::this_thread::yield();
+  }
+  const unsigned seq = __atomic_load_n(&cl->hdr->seq, __ATOMIC_ACQUIRE);
+  if (seq != cl->seq) return fail_msg("a point cloud was read before the device had written it (sequence stamp mismatch)", kStaleRecord);
+  *count = cl->hdr->count;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+void rebvio_hip_default_cloud_filter(rebvio_hip_cloud_filter* f) {
+  f->min_matches = 2;
+  f->max_rel_sigma = 0.5f;
+  f->rho_min = 1e-3f;  // types/keyline.hpp:17-18: the bounds rho is clamped to
+  f->rho_max = 20.0f;
+}
+
+int rebvio_hip_map_point_cloud(rebvio_hip_map* m, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose,
+                               rebvio_hip_cloud_point* points, int cap, int* count) {
+  if (!m) return fail_msg("map_point_cloud: null map", -3);
+  if (!count) return fail_msg("map_point_cloud: null count", -3);
+  if (cap < 0 || (cap > 0 && !points)) return fail_msg("map_point_cloud: cap records need a points buffer (cap >= 0)", -3);
+  int rc = check_cloud_args("map_point_cloud", filter, pose);
+  if (rc) return rc;
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  *count = 0;
+  rebvio_hip_cloud* cl = nullptr;
+  rc = enqueue_cloud("map_point_cloud", m, filter, pose, cap, &cl);
+  if (rc) return rc;
+  rc = wait_cloud(cl, count);
+  if (rc == 0) {
+    const int k = *count < cl->cap ? *count : cl->cap;
+    if (k > 0) std::memcpy(points, reinterpret_cast<const char*>(cl->hdr) + sizeof(CloudHdr), (size_t)k * sizeof(rebvio_hip_cloud_point));
+  }
+  release_cloud(cl);
+  return rc;
+}
+
+int rebvio_hip_map_point_cloud_async(rebvio_hip_ctx* c, rebvio_hip_map* m, const rebvio_hip_cloud_filter* filter,
+                                     const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud** out) {
+  if (out) *out = nullptr;
+  if (!c || !m || !out) return fail_msg("map_point_cloud_async: null context, map or output", -3);
+  const int rc = check_cloud_args("map_point_cloud_async", filter, pose);
+  if (rc) return rc;
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (m->ctx != c) return fail_msg("map_point_cloud_async: map of another context", -3);
+  return enqueue_cloud("map_point_cloud_async", m, filter, pose, -1, out);
+}
+
+int rebvio_hip_cloud_wait(rebvio_hip_cloud* cl, const rebvio_hip_cloud_point** points, int* count, const void** device_points) {
+  if (points) *points = nullptr;
+  if (device_points) *device_points = nullptr;
+  if (!cl || !count) return fail_msg("cloud_wait: null cloud or count", -3);
+  *count = 0;
+  const std::shared_ptr<LifeBlock> life = cl->life;
+  std::shared_lock<std::shared_mutex> lk(life->mu);
+  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the cloud's context has been destroyed (rebvio_hip_destroy)", -10);
+  HIPCHK(hipSetDevice(cl->ctx->device));
+  const int rc = wait_cloud(cl, count);
+  if (rc) return rc;
+  if (points) *points = reinterpret_cast<const rebvio_hip_cloud_point*>(reinterpret_cast<const char*>(cl->hdr) + sizeof(CloudHdr));
+  if (device_points) *device_points = cl->dev;
+  return 0;
+}
+
+void rebvio_hip_cloud_release(rebvio_hip_cloud* cl) {
+  if (!cl) return;
+  const std::shared_ptr<LifeBlock> life = cl->life;
+  std::shared_lock<std::shared_mutex> lk(life->mu);
+  if (life->dead.load(std::memory_order_acquire)) {  // the context is gone (its buffers with it): drop the husk
+    if (cl->in_use) delete cl;
+    return;
+  }
+  release_cloud(cl);
 }
 
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n) {
@@ -2038,6 +2274,7 @@ int rebvio_hip_track_pair_begin(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hi
     // last kernel; it was told the same prior
     if (std::memcmp(&om->pre_R, &R, sizeof(R)) != 0)
       return fail_msg("track_pair_begin: R_prior (or the gyro state) differs from the R_prior_next the previous finish_async applied", -7);
+    om->promised.store(false, std::memory_order_release);  // consumed: the map is in the frame this pair asked for
   } else {
     float RT[9];
     hm::store3(hm::transpose(R), RT);
@@ -2109,6 +2346,7 @@ int rebvio_hip_track_pair_finish_async(rebvio_hip_ctx* c, rebvio_hip_map* om, re
   if (R_prior_next) {  // the next pair's first rotateKeylines rides in this pair's last kernel (rebvio.cpp:163-165 of that pair)
     nm->pre_R = prior_rotation(c, R_prior_next);
     hm::store3(hm::transpose(nm->pre_R), RT_next);
+    nm->promised.store(true, std::memory_order_release);
   }
   enqueue_b_chain(c, om, nm, g, R_prior_next ? RT_next : nullptr);
   HIPCHK(hipGetLastError());

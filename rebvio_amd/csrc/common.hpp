@@ -291,6 +291,28 @@ void launch_depth_ekf(hipStream_t s, const KParams& p, const MapDev& m, const fl
 void launch_render_edge_image(hipStream_t s, const KParams& p, const MapDev& m, const uint8_t* gray_or_null, uint8_t* rgb);
 void launch_map_pack(hipStream_t s, const KParams& p, const MapDev& m, rebvio_hip_keyline* aos_dev);
 void launch_map_unpack(hipStream_t s, const KParams& p, const MapDev& m, const rebvio_hip_keyline* aos_dev, int n);
+// Point cloud of a map (rebvio_hip_map_point_cloud*): filter, pose and capacity of one extraction, by value.
+struct CloudArgs {
+  unsigned min_matches;
+  float max_rel_sigma, rho_min, rho_max;
+  float R[9], t[3], scale;
+  int cap;       // records the buffer takes
+  unsigned seq;  // sequence stamp of this extraction (CloudHdr::seq)
+};
+// Head of a cloud's host-visible buffer; the records follow at byte 64. (The device buffer has the same shape: count, records.)
+struct CloudHdr {
+  int count;     // keylines that passed (may exceed the records written: CloudArgs::cap)
+  unsigned seq;  // stored last, behind the records and the count (PairSlot::seq convention)
+  unsigned pad[14];
+};
+// k_cloud_count + k_cloud_emit on stream s: blk_cnt = kMaxRecBlocks ints of device memory that only extractions on this stream use;
+// count_dev / records_dev = the cloud's device buffer (passing keylines; 32-byte rebvio_hip_cloud_point records).
+void launch_point_cloud(hipStream_t s, const KParams& p, const MapDev& m, const CloudArgs& a, int* blk_cnt, int* count_dev,
+                        void* records_dev);
+// k_cloud_copy on stream s (behind the extraction): the records that exist -> host-visible memory, then count and stamp into
+// *hdr. ticket = one zeroed word of device memory that only copies on this stream use.
+void launch_point_cloud_copy(hipStream_t s, const KParams& p, const void* records_dev, const int* count_dev, const CloudArgs& a,
+                             unsigned* ticket, CloudHdr* hdr, void* records_host);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 

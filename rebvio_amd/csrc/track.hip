@@ -3137,4 +3137,111 @@ void launch_depth_ekf(hipStream_t s, const KParams& p, const MapDev& m, const fl
   RH_LAUNCH(k_depth_ekf, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, p, m, vec3(vel), use_tmp, gate);
 }
 
+// ---- point cloud of a map's depth-bearing keylines (rebvio_hip_map_point_cloud*; no reference counterpart) ------------------
+// An order-preserving stream compaction over the keyline arrays in two launches of one workgroup per 256 keylines:
+//   k_cloud_count  each workgroup's number of passing keylines -> blk_cnt[workgroup]
+//   k_cloud_emit   block offset = sum of the counts in front of it (fixed order: integer sums), place within the block from a
+//                  wave64 ballot + lane-prefix popcount and the wave totals in LDS; one 32-byte record = two 16-byte stores.
+// A point's place depends on the keyline index alone - no atomic decides an order - so the cloud is reproducible bit for bit.
+// Both write device memory. k_cloud_copy, on a stream of its own behind them, moves exactly the records that exist into
+// host-visible memory: 16 bytes per lane, consecutive lanes consecutive addresses, so that the writes cross the bus as whole
+// lines (records stored there by k_cloud_emit directly - 16 bytes per lane at a 32-byte stride, one bus write each - took 1.0 ms
+// for 13 500 points). The count and the sequence stamp behind it are stored by the workgroup that finishes last (a
+// ticket counter tells which: it orders nothing but that one store), after every workgroup's stores have left.
+__device__ __forceinline__ bool cloud_pass(const CloudArgs& a, float2 rs, unsigned matches) {
+  // positive tests: a NaN in rho or sigma_rho fails them
+  return matches >= a.min_matches && rs.x >= a.rho_min && rs.x <= a.rho_max && rs.y <= a.max_rel_sigma * rs.x;
+}
+// (count of passing lanes in front of this lane, count of the wave)
+__device__ __forceinline__ int2 wave_place(bool pass) {
+  const unsigned long long b = __ballot(pass);
+  const int before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+  return make_int2(before, __popcll(b));
+}
+
+__global__ __launch_bounds__(256) void k_cloud_count(MapDev m, CloudArgs a, int* __restrict__ blk_cnt) {
+  __shared__ int sh[4];
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const float2 rs = m.rs[idx];  // bound-free early loads (the arrays are padded to the launch grid)
+  const unsigned mt = m.matches[idx];
+  const int n = m.st->n;
+  const int2 w = wave_place(idx < n && cloud_pass(a, rs, mt));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w.y;
+  __syncthreads();
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void k_cloud_emit(KParams p, MapDev m, CloudArgs a, const int* __restrict__ blk_cnt,
+                                                    int* __restrict__ count_out, float4* __restrict__ out) {
+  __shared__ int sh_w[4], sh_lo[4], sh_all[4];
+  const int tid = threadIdx.x, idx = blockIdx.x * 256 + tid, wv = tid >> 6;
+  const float2 pi = m.pos_img[idx];
+  const float2 rs = m.rs[idx];
+  const float gn = m.gnorm[idx];
+  const unsigned mt = m.matches[idx];
+  const int n = m.st->n;
+  // every workgroup's count, one per thread (gridDim.x <= kMaxRecBlocks = 256)
+  const int c = tid < (int)gridDim.x ? blk_cnt[tid] : 0;
+  const int lo = wave_sum_i(tid < (int)blockIdx.x ? c : 0), all = wave_sum_i(c);
+  const bool pass = idx < n && cloud_pass(a, rs, mt);
+  const int2 w = wave_place(pass);
+  if ((tid & 63) == 0) {
+    sh_w[wv] = w.y;
+    sh_lo[wv] = lo;
+    sh_all[wv] = all;
+  }
+  __syncthreads();
+  int rank = (sh_lo[0] + sh_lo[1]) + (sh_lo[2] + sh_lo[3]) + w.x;
+  for (int k = 0; k < wv; ++k) rank += sh_w[k];
+  if (blockIdx.x == 0 && tid == 0) *count_out = (sh_all[0] + sh_all[1]) + (sh_all[2] + sh_all[3]);
+  if (pass && rank < a.cap) {
+    const float u = pi.x / p.fm, v = pi.y / p.fm;  // (the divisions of rotateKeylines, edge_map.cpp:60)
+    const float z = a.scale / rs.x;
+    const float xc = u * z, yc = v * z;
+    float q[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) q[i] = ((a.R[3 * i] * xc + a.R[3 * i + 1] * yc) + a.R[3 * i + 2] * z) + a.t[i];
+    // two 16-byte stores per record (volatile: left alone, the compiler re-cuts the 32 bytes into 12 + 12 + 8)
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) volatile v4f* GRec;  // (global_store, not flat_store: common.hpp gptr)
+    GRec rec = (GRec)(out + 2 * (size_t)rank);
+    rec[0] = v4f{q[0], q[1], q[2], rs.x};
+    rec[1] = v4f{rs.y, gn, __int_as_float(idx), __uint_as_float(mt)};
+  }
+}
+
+// records[0 .. min(*count, cap)) -> host-visible memory, then the head: count, and the stamp behind everything
+__global__ __launch_bounds__(256) void k_cloud_copy(const float4* __restrict__ src, const int* __restrict__ count, int cap, unsigned seq,
+                                                    unsigned* __restrict__ ticket, CloudHdr* __restrict__ hdr, float4* __restrict__ dst) {
+  __shared__ int sh_last;
+  const int total = *count;
+  const int chunks = 2 * (total < cap ? total : cap);  // 16-byte pieces
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < chunks; i += gridDim.x * 256) dst[i] = src[i];
+  // this wave's stores have left (host-visible memory is written through), then the workgroup takes its ticket
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) sh_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u;
+  __syncthreads();
+  if (sh_last && threadIdx.x == 0) {
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next copy (stream-ordered)
+    hdr->count = total;
+    stamp_drain(&hdr->seq, seq);
+  }
+}
+
+void launch_point_cloud(hipStream_t s, const KParams& p, const MapDev& m, const CloudArgs& a, int* blk_cnt, int* count_dev,
+                        void* records_dev) {
+  const dim3 grid(div_up(p.kmax, 256));
+  RH_LAUNCH(k_cloud_count, grid, dim3(256), 0, s, m, a, blk_cnt);
+  RH_LAUNCH(k_cloud_emit, grid, dim3(256), 0, s, p, m, a, (const int*)blk_cnt, count_dev, reinterpret_cast<float4*>(records_dev));
+}
+
+void launch_point_cloud_copy(hipStream_t s, const KParams& p, const void* records_dev, const int* count_dev, const CloudArgs& a,
+                             unsigned* ticket, CloudHdr* hdr, void* records_host) {
+  const int blocks = std::max(1, std::min(64, div_up(2 * a.cap, 256)));
+  RH_LAUNCH(k_cloud_copy, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(records_dev), count_dev, a.cap, a.seq, ticket, hdr,
+            reinterpret_cast<float4*>(records_host));
+}
+
 }  // namespace rh

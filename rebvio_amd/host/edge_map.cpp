@@ -131,4 +131,17 @@ int EdgeMap::regularize1Iter() {
   return n;
 }
 
+std::vector<rebvio::types::CloudPoint> EdgeMap::pointCloud(const rebvio::types::CloudFilter& filter, const rebvio::types::CloudPose& pose) {
+  static_assert(sizeof(types::CloudPoint) == sizeof(rebvio_hip_cloud_point) && sizeof(types::CloudFilter) == sizeof(rebvio_hip_cloud_filter) &&
+                    sizeof(types::CloudPose) == sizeof(rebvio_hip_cloud_pose), "point-cloud types mirror the C-ABI's");
+  std::vector<rebvio::types::CloudPoint> points((size_t)size());
+  int count = 0;
+  check("rebvio_hip_map_point_cloud",
+        rebvio_hip_map_point_cloud(handle_, reinterpret_cast<const rebvio_hip_cloud_filter*>(&filter),
+                                   reinterpret_cast<const rebvio_hip_cloud_pose*>(&pose),
+                                   reinterpret_cast<rebvio_hip_cloud_point*>(points.data()), (int)points.size(), &count));
+  points.resize((size_t)count);
+  return points;
+}
+
 }  // namespace rebvio

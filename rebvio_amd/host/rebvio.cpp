@@ -105,6 +105,10 @@ void Rebvio::registerEdgeImageCallback(std::function<void(cv::Mat&, rebvio::Edge
 
 void Rebvio::registerOdometryCallback(std::function<void(rebvio::types::Odometry&)> cb) { odometry_callbacks_.push_back(cb); }
 
+void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
+  point_cloud_callbacks_.push_back({cb, filter});
+}
+
 void Rebvio::waitIdle() {
   while (run_) {
     const unsigned imgs = num_images_;
@@ -318,6 +322,10 @@ void Rebvio::stateEstimationProcess() {
     bool fetched = false;  // counters in, record not yet handed to the callbacks
     types::Odometry odometry;
     rebvio::EdgeMap::SharedPtr old_map, new_map;
+    // point-cloud callbacks: the pose the pair's clouds were queued with and one queued cloud per callback (waited for where
+    // the pair's counters are)
+    types::CloudPose cloud_pose;
+    std::vector<rebvio_hip_cloud*> clouds;
   } pending;
   // Two steps: the counters (and with them the stop conditions of rebvio.cpp:236-252) are fetched as soon as the next pair's
   // first half is back; the callbacks run after that pair's second half has been launched, off the path between its halves.
@@ -325,6 +333,21 @@ void Rebvio::stateEstimationProcess() {
     if (!pending.fetched) return;
     pending.fetched = false;
     for (auto& cb : odometry_callbacks_) cb(pending.odometry);
+    // every cloud goes back to its pool, also when a callback (or the wait) throws
+    struct CloudsBack {
+      std::vector<rebvio_hip_cloud*>& v;
+      ~CloudsBack() {
+        for (rebvio_hip_cloud* cl : v) rebvio_hip_cloud_release(cl);
+        v.clear();
+      }
+    } clouds_back{pending.clouds};
+    for (size_t i = 0; i < pending.clouds.size(); ++i) {
+      const rebvio_hip_cloud_point* pts = nullptr;
+      int n = 0;
+      backend::check("rebvio_hip_cloud_wait", rebvio_hip_cloud_wait(pending.clouds[i], &pts, &n, nullptr));  // (has run: fetch_pending)
+      const types::PointCloud pc{pending.odometry.ts_us, pending.cloud_pose, reinterpret_cast<const types::CloudPoint*>(pts), (size_t)n};
+      point_cloud_callbacks_[i].cb(pc);
+    }
     pending.old_map.reset();
     pending.new_map.reset();
     ++num_published_;
@@ -335,6 +358,10 @@ void Rebvio::stateEstimationProcess() {
     pending.fetched = true;
     int klm_num = 0, kf_matches = 0, reg_num = 0, status = 0;
     backend::check("rebvio_hip_track_pair_result", rebvio_hip_track_pair_result(ctx, &klm_num, &kf_matches, &reg_num, &status));
+    for (rebvio_hip_cloud* cl : pending.clouds) {  // queued right behind that second half
+      int n = 0;
+      backend::check("rebvio_hip_cloud_wait", rebvio_hip_cloud_wait(cl, nullptr, &n, nullptr));
+    }
     pending.old_map->invalidateMirror();
     pending.new_map->invalidateMirror();
     bool ok = true;
@@ -493,9 +520,28 @@ void Rebvio::stateEstimationProcess() {
     store3(Rgva, rg);
     store3(R_second, r2);
     timers.lap(1);
+    // gravity-aligned pose integration (rebvio.cpp:263-271): needs nothing from the device. With a point-cloud callback it runs
+    // ahead of the hand-over, because the pair's cloud is queued with this pose right behind the second half.
+    auto integrate_pose = [&]() {
+      if (num_frames_ > 4u + (unsigned)config_.imu_state.init_bias_frame_num) {
+        imu_state_.u_est = Rgva.T() * imu_state_.u_est;
+        imu_state_.u_est =
+            imu_state_.u_est - (imu_state_.u_est * sab_state_.g_est) / (sab_state_.g_est * sab_state_.g_est) * sab_state_.g_est;
+        imu_state_.u_est = imu_state_.u_est / std::sqrt(imu_state_.u_est * imu_state_.u_est);
+        const types::Matrix3f R1 = TooN::SO3<types::Float>(sab_state_.g_est, TooN::makeVector(0.0f, 1.0f, 0.0f)).get_matrix();
+        const types::Matrix3f R2 = TooN::SO3<types::Float>(R1 * imu_state_.u_est, TooN::makeVector(1.0f, 0.0f, 0.0f)).get_matrix();
+        R_global = R2 * R1;
+        Pos += -(R_global * imu_state_.Vgva) * K;
+      }
+    };
+    const bool want_cloud = !point_cloud_callbacks_.empty();
+    std::vector<rebvio_hip_cloud*> clouds;
+    types::CloudPose cloud_pose;
+    if (want_cloud) integrate_pose();
     // If the following frame is already queued, its gyro pre-integration (complete before the map was queued) is the next
     // pair's prior: that pair's first rotateKeylines then rides in this pair's last kernel. Only once the gyro bias is
-    // initialised (until then the bias still changes between pairs, rebvio.cpp:146-160).
+    // initialised (until then the bias still changes between pairs, rebvio.cpp:146-160). Not with a point-cloud callback: the
+    // cloud shows the new map in THIS pair's frame, so the next pair's _begin launches its rotation itself.
     float Rnext[9];
     bool have_next = false;
     rebvio::EdgeMap::SharedPtr next_map;
@@ -503,7 +549,7 @@ void Rebvio::stateEstimationProcess() {
       std::lock_guard<std::mutex> guard(edge_map_buffer_mutex_);
       if (edge_map_buffer_.size() >= 2) {
         next_map = edge_map_buffer_[1];
-        if (imu_state_.initialized) {
+        if (imu_state_.initialized && !want_cloud) {
           store3(next_map->imu().R(), Rnext);
           have_next = true;
         }
@@ -514,20 +560,22 @@ void Rebvio::stateEstimationProcess() {
     backend::check("rebvio_hip_track_pair_finish_async",
                    rebvio_hip_track_pair_finish_async(ctx, old_edge_map->handle(), new_edge_map->handle(), V, pv, rg, r2,
                                                       have_next ? Rnext : nullptr));
+    if (want_cloud) {
+      store3(R_global, cloud_pose.R);
+      for (int i = 0; i < 3; ++i) cloud_pose.t[i] = Pos[i];
+      cloud_pose.scale = K;
+      for (const PointCloudCallback& pcc : point_cloud_callbacks_) {
+        rebvio_hip_cloud* cl = nullptr;
+        backend::check("rebvio_hip_map_point_cloud_async",
+                       rebvio_hip_map_point_cloud_async(ctx, new_edge_map->handle(), reinterpret_cast<const rebvio_hip_cloud_filter*>(&pcc.filter),
+                                                        reinterpret_cast<const rebvio_hip_cloud_pose*>(&cloud_pose), &cl));
+        clouds.push_back(cl);
+      }
+    }
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
     timers.lap(2);
 
-    // gravity-aligned pose integration (rebvio.cpp:263-271)
-    if (num_frames_ > 4u + (unsigned)config_.imu_state.init_bias_frame_num) {
-      imu_state_.u_est = Rgva.T() * imu_state_.u_est;
-      imu_state_.u_est =
-          imu_state_.u_est - (imu_state_.u_est * sab_state_.g_est) / (sab_state_.g_est * sab_state_.g_est) * sab_state_.g_est;
-      imu_state_.u_est = imu_state_.u_est / std::sqrt(imu_state_.u_est * imu_state_.u_est);
-      const types::Matrix3f R1 = TooN::SO3<types::Float>(sab_state_.g_est, TooN::makeVector(0.0f, 1.0f, 0.0f)).get_matrix();
-      const types::Matrix3f R2 = TooN::SO3<types::Float>(R1 * imu_state_.u_est, TooN::makeVector(1.0f, 0.0f, 0.0f)).get_matrix();
-      R_global = R2 * R1;
-      Pos += -(R_global * imu_state_.Vgva) * K;
-    }
+    if (!want_cloud) integrate_pose();
     types::Odometry odometry;
     odometry.ts_us = new_edge_map->ts_us();
     odometry.orientation = TooN::SO3<types::Float>(R_global).ln();
@@ -539,6 +587,8 @@ void Rebvio::stateEstimationProcess() {
     pending.odometry = odometry;
     pending.old_map = old_edge_map;
     pending.new_map = new_edge_map;
+    pending.cloud_pose = cloud_pose;
+    pending.clouds = clouds;
     timers.lap(3);
     timers.end_pair();
     timers.n++;

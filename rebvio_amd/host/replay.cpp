@@ -7,6 +7,10 @@
 // device, instead of to luma while they are read; the odometry is the same.
 // --mask mask.png: a grey PNG of the frames' size as the detection mask (Rebvio::setDetectionMask): keylines come only from pixels
 // whose byte is non-zero (in undistorted coordinates when a lens model is given).
+// --cloud PREFIX: every published record's point cloud (Rebvio::registerPointCloudCallback, default filter) as a binary
+// little-endian PLY file PREFIX<ts_us>.ply with the vertex properties x, y, z, intensity (io::writePointCloudPly).
+// --cloud-dry: the callback is registered and counts points, no file is written (what the callback costs the pipeline:
+// tools/cloud_rate.py).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -19,16 +23,16 @@
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
-  std::string asl, raw, imu, out, mask_png;
+  std::string asl, raw, imu, out, mask_png, cloud_prefix;
   int W = 0, H = 0;
   size_t first = 0, count = (size_t)-1;
   uint64_t dt = 50000;
-  bool euroc = false, colour = false;
+  bool euroc = false, colour = false, cloud_dry = false;
   float cam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] --out file\n", argv[0]);
+                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -54,6 +58,8 @@ int main(int argc, char** argv) {
       if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0) return usage();
       mask_png = argv[++i];
     }
+    else if (a == "--cloud") cloud_prefix = next();
+    else if (a == "--cloud-dry") cloud_dry = true;
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
     else if (a == "--camera") {
@@ -118,11 +124,19 @@ int main(int argc, char** argv) {
       if (n_odo == 0) t_first = t_last;
       ++n_odo;
     });
+    size_t n_clouds = 0, n_points = 0;
+    if (!cloud_prefix.empty() || cloud_dry)
+      rebvio.registerPointCloudCallback([&](const rebvio::types::PointCloud& pc) {
+        if (!cloud_prefix.empty()) rebvio::io::writePointCloudPly(cloud_prefix + std::to_string(pc.ts_us) + ".ply", pc.points, pc.size, pc.ts_us);
+        ++n_clouds;
+        n_points += pc.size;
+      });
     const size_t n = rebvio::io::replay(
         *src, [&](rebvio::types::Image&& im) { rebvio.imageCallback(std::move(im)); },
         [&](rebvio::types::Imu&& s) { rebvio.imuCallback(std::move(s)); }, first, count);
     rebvio.waitIdle();
     std::fprintf(stderr, "frames=%zu odometry=%zu running=%d\n", n, n_odo, (int)rebvio.running());
+    if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
     if (n_odo > 1) {  // wall clock between the first and the last published odometry: the whole class, input thread included
       const double sec = std::chrono::duration<double>(t_last - t_first).count();
       std::fprintf(stderr, "[replay] %zu odometry records in %.3f s = %.0f frames/s (wall clock, first to last record)\n", n_odo, sec,

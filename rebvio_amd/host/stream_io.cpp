@@ -243,6 +243,68 @@ void OdometryWriter::write(const rebvio::types::Odometry& o) {
   std::fflush(f_);
 }
 
+void writePointCloudPly(const std::string& path, const rebvio::types::CloudPoint* points, size_t n, uint64_t ts_us) {
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) bad("cannot create " + path);
+  std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment rebvio point cloud ts_us %llu\nelement vertex %zu\n"
+               "property float x\nproperty float y\nproperty float z\nproperty float intensity\nend_header\n",
+               (unsigned long long)ts_us, n);
+  std::vector<unsigned char> body(n * 16);
+  for (size_t i = 0; i < n; ++i) {
+    const float v[4] = {points[i].xyz[0], points[i].xyz[1], points[i].xyz[2], points[i].gradient_norm};
+    for (int k = 0; k < 4; ++k) {
+      uint32_t w;
+      std::memcpy(&w, &v[k], 4);
+      for (int b = 0; b < 4; ++b) body[i * 16 + k * 4 + b] = (unsigned char)(w >> (8 * b));  // little-endian on any host
+    }
+  }
+  const bool ok = body.empty() || std::fwrite(body.data(), 1, body.size(), f) == body.size();
+  if (std::fclose(f) != 0 || !ok) bad("cannot write " + path);
+}
+
+std::vector<PlyVertex> readPointCloudPly(const std::string& path, uint64_t* ts_us) {
+  std::FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) bad("cannot open " + path);
+  std::vector<std::string> lines;
+  std::string line;
+  for (int c; (c = std::fgetc(f)) != EOF;) {
+    if (c != '\n') {
+      line.push_back((char)c);
+      if (line.size() > 200) break;
+      continue;
+    }
+    lines.push_back(line);
+    if (line == "end_header") break;
+    line.clear();
+  }
+  unsigned long long ts = 0, n = 0;
+  const bool header_ok = lines.size() == 9 && lines[0] == "ply" && lines[1] == "format binary_little_endian 1.0" &&
+                         std::sscanf(lines[2].c_str(), "comment rebvio point cloud ts_us %llu", &ts) == 1 &&
+                         std::sscanf(lines[3].c_str(), "element vertex %llu", &n) == 1 && lines[4] == "property float x" &&
+                         lines[5] == "property float y" && lines[6] == "property float z" && lines[7] == "property float intensity" &&
+                         lines[8] == "end_header";
+  if (!header_ok) {
+    std::fclose(f);
+    bad(path + ": not a point-cloud PLY file of writePointCloudPly");
+  }
+  std::vector<unsigned char> body((size_t)n * 16);
+  const bool ok = (body.empty() || std::fread(body.data(), 1, body.size(), f) == body.size()) && std::fgetc(f) == EOF;
+  std::fclose(f);
+  if (!ok) bad(path + ": the vertex data do not match the header's count");
+  std::vector<PlyVertex> out((size_t)n);
+  for (size_t i = 0; i < out.size(); ++i) {
+    float v[4];
+    for (int k = 0; k < 4; ++k) {
+      uint32_t w = 0;
+      for (int b = 0; b < 4; ++b) w |= (uint32_t)body[i * 16 + k * 4 + b] << (8 * b);
+      std::memcpy(&v[k], &w, 4);
+    }
+    out[i] = PlyVertex{v[0], v[1], v[2], v[3]};
+  }
+  if (ts_us) *ts_us = ts;
+  return out;
+}
+
 size_t replay(StreamSource& src, const std::function<void(rebvio::types::Image&&)>& image_cb,
               const std::function<void(rebvio::types::Imu&&)>& imu_cb, size_t first, size_t count) {
   const auto& imu = src.imu();
