@@ -23,7 +23,8 @@ extern "C" {
 /* 3: status -12 (a pair's record read before the device wrote it: sequence stamps), rebvio_hip_test_forge_record_stamp,
  *    REBVIO_HIP_DM_HEAD values compact8 / compact4 / compact1 (2: map handles outlive their context, -10)
  *    Added since, without a new version (additions only): the point-cloud entries rebvio_hip_default_cloud_filter,
- *    rebvio_hip_map_point_cloud(_async), rebvio_hip_cloud_wait / _release and their three structs. */
+ *    rebvio_hip_map_point_cloud(_async), rebvio_hip_cloud_wait / _release and their three structs; the test hook
+ *    rebvio_hip_test_live_resources. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -455,6 +456,13 @@ int rebvio_hip_test_glue(rebvio_hip_ctx* ctx, const float vel[3], const float Jt
  * like to the reader. */
 int rebvio_hip_test_forge_record_stamp(rebvio_hip_ctx* ctx);
 int rebvio_hip_batch_test_forge_record_stamp(rebvio_hip_batch* b);
+
+/* Test hook for leaks: the device buffers, pinned host buffers, events and streams that the contexts, edge maps, point clouds and
+ * batches of this process hold right now, as one exact count (not bytes). Creating any of them raises it, destroying a context
+ * or a batch lowers it by all that the object took, what it allocated on first use included; a map or cloud handle kept across
+ * rebvio_hip_destroy holds none. A process that has destroyed everything it created reads the value it started with. Memory
+ * from rebvio_hip_device_alloc belongs to the caller and is not counted, nor are the profiler's pooled events. */
+long rebvio_hip_test_live_resources(void);
 
 /* Per-kernel device timing of the last N launches of each kernel, measured with HIP events on the
  * stream the kernel runs on. names: '\n'-separated. Used by bench.py's roofline leg. */

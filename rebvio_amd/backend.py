@@ -146,6 +146,7 @@ SIGNATURES = {
                                       C.POINTER(PairOut), _fp, _fp, C.POINTER(PairOut), _fp, _fp]),
     "rebvio_hip_test_forge_record_stamp": (C.c_int, [_vp]),
     "rebvio_hip_batch_test_forge_record_stamp": (C.c_int, [_vp]),
+    "rebvio_hip_test_live_resources": (C.c_long, []),
     "rebvio_hip_profile_enable": (C.c_int, [_vp, C.c_int]),
     "rebvio_hip_profile_select": (C.c_int, [_vp, C.c_char_p]),
     "rebvio_hip_profile_reset": (C.c_int, [_vp]),
@@ -234,6 +235,11 @@ def _chk(rc):
 def _f(a):
     a = np.ascontiguousarray(a, np.float32)
     return a, a.ctypes.data_as(_fp)
+
+
+def test_live_resources() -> int:
+    """Device buffers, pinned buffers, events and streams the library holds in this process (rebvio_hip_test_live_resources)."""
+    return int(lib().rebvio_hip_test_live_resources())
 
 
 def default_params(rows, cols, **over) -> Params:

@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "glue.hpp"
 #include "hostmath.hpp"
+#include "owned.hpp"
 #include "pixel_format.hpp"
 
 using namespace rh;
@@ -217,6 +218,7 @@ struct LifeBlock {
 struct rebvio_hip_map {
   rebvio_hip_ctx* ctx = nullptr;
   std::shared_ptr<LifeBlock> life;
+  Owned own;  // the arrays of `d` and the three events below
   MapDev d{};
   bool in_use = false;
   uint64_t ts = 0;
@@ -250,8 +252,9 @@ struct rebvio_hip_map {
 struct rebvio_hip_cloud {
   rebvio_hip_ctx* ctx = nullptr;
   std::shared_ptr<LifeBlock> life;
-  CloudHdr* hdr = nullptr;     // hipHostMalloc: 64-byte head + keylines_max records
-  char* dev_buf = nullptr;     // hipMalloc, the same shape: the count at byte 0, the records at byte 64
+  Owned own;                   // the two buffers and the two events
+  CloudHdr* hdr = nullptr;     // pinned: 64-byte head + keylines_max records
+  char* dev_buf = nullptr;     // device, the same shape: the count at byte 0, the records at byte 64
   void* dev = nullptr;         // device address of the records (dev_buf + 64)
   hipEvent_t extracted{};      // recorded on the track stream behind the extraction
   hipEvent_t done{};           // recorded on the cloud stream behind the copy to the host
@@ -291,6 +294,10 @@ struct PairQueue {
 
 struct rebvio_hip_ctx {
   std::shared_ptr<LifeBlock> life = std::make_shared<LifeBlock>();
+  // Every device buffer, pinned buffer, event and stream of the context, those allocated on first use included. The pointers
+  // and handles below are views of them (copied by value into MapDev, LaneStatic and kernel arguments); pooled maps and clouds
+  // own theirs, a batch owns the streams its lanes adopt.
+  Owned own;
   rebvio_hip_params P{};
   KParams K{};
   int device = 0;
@@ -322,7 +329,7 @@ struct rebvio_hip_ctx {
   float* img_dev = nullptr;
   uint8_t* img8_dev = nullptr;
   static constexpr int kPin = 16;  // pinned staging ring of the host-frame detect entries (allocated on first use)
-  void* pin[kPin]{};
+  uint8_t* pin[kPin]{};
   hipEvent_t pin_ev[kPin]{};
   bool pin_used[kPin]{};
   uint64_t pin_next = 0;
@@ -435,6 +442,9 @@ struct rebvio_hip_ctx {
   // two result slots: the next pair's first half (and its parked second half) may be queued before the caller fetches the
   // previous pair's counters (rebvio_hip_track_pair_finish_async / _result)
   hipEvent_t bf_done[2]{};
+  // fetch_map_state: orders its copy behind another stream (created on first use). Only the tracking thread's entries
+  // (directed_match, regularize) pass that stream, and they already share h_st, so neither the first use nor the event is raced.
+  hipEvent_t fetch_ev{};
   MapState* h_bf = nullptr;  // [2] pinned
   int bf_cur = 0;            // slot of the pair between _begin and _finish_async
   int bf_res = -1;           // slot whose result is to be fetched (-1: none)
@@ -495,40 +505,36 @@ int alloc_map(rebvio_hip_ctx* c, rebvio_hip_map* m) {
   // keyline arrays are padded to the launch grids (256- and 1024-thread workgroups) so kernels may load before checking n
   const size_t M = (size_t)div_up(c->P.keylines_max, 1024) * 1024, Pn = (size_t)c->P.rows * c->P.cols;
   MapDev& d = m->d;
-  HIPCHK(hipMalloc(&d.pos, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.pos_img, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.mpos_img, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.grad, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.mgrad, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.gnorm, M * sizeof(float)));
-  HIPCHK(hipMalloc(&d.mgnorm, M * sizeof(float)));
-  HIPCHK(hipMalloc(&d.rs, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.rs_tmp, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.grad_tmp, M * sizeof(float2)));
-  HIPCHK(hipMalloc(&d.id_prev, M * sizeof(int)));
-  HIPCHK(hipMalloc(&d.id_next, M * sizeof(int)));
-  HIPCHK(hipMalloc(&d.match_id, M * sizeof(int)));
-  HIPCHK(hipMalloc(&d.match_fwd, M * sizeof(int)));
-  HIPCHK(hipMalloc(&d.match_kf, M * sizeof(int)));
-  HIPCHK(hipMalloc(&d.matches, M * sizeof(unsigned)));
-  HIPCHK(hipMalloc(&d.fwd_key, M * sizeof(unsigned long long)));
-  HIPCHK(hipMalloc(&d.residual, M * sizeof(float)));
-  HIPCHK(hipMalloc(&d.mask, Pn * sizeof(int)));
-  HIPCHK(hipMalloc(&d.df, Pn * sizeof(unsigned)));
-  HIPCHK(hipMalloc(&d.unit, M * sizeof(float2)));
+  Owned& own = m->own;
+  HIPCHK(own.device(&d.pos, M));
+  HIPCHK(own.device(&d.pos_img, M));
+  HIPCHK(own.device(&d.mpos_img, M));
+  HIPCHK(own.device(&d.grad, M));
+  HIPCHK(own.device(&d.mgrad, M));
+  HIPCHK(own.device(&d.gnorm, M));
+  HIPCHK(own.device(&d.mgnorm, M));
+  HIPCHK(own.device(&d.rs, M));
+  HIPCHK(own.device(&d.rs_tmp, M));
+  HIPCHK(own.device(&d.grad_tmp, M));
+  HIPCHK(own.device(&d.id_prev, M));
+  HIPCHK(own.device(&d.id_next, M));
+  HIPCHK(own.device(&d.match_id, M));
+  HIPCHK(own.device(&d.match_fwd, M));
+  HIPCHK(own.device(&d.match_kf, M));
+  HIPCHK(own.device(&d.matches, M));
+  HIPCHK(own.device(&d.fwd_key, M));
+  HIPCHK(own.device(&d.residual, M));
+  HIPCHK(own.device(&d.mask, Pn, 0xFF));
+  HIPCHK(own.device(&d.df, Pn, 0xFF));
+  HIPCHK(own.device(&d.unit, M));
   {
     const DfGrid g = df_grid(c->P.rows, c->P.cols);
     const size_t nt = (size_t)g.ntx * g.nty;
-    HIPCHK(hipMalloc(&d.tile_cnt, nt * sizeof(int)));
-    HIPCHK(hipMemset(d.tile_cnt, 0, nt * sizeof(int)));
-    HIPCHK(hipMalloc(&d.tile_list, nt * kDfTileCap * 2 * sizeof(float4)));
+    HIPCHK(own.device(&d.tile_cnt, nt, 0));
+    HIPCHK(own.device(&d.tile_list, nt * kDfTileCap * 2));
   }
-  HIPCHK(hipMalloc(&d.row_start, ((size_t)c->P.rows + 1) * sizeof(int)));
-  HIPCHK(hipMemset(d.row_start, 0, ((size_t)c->P.rows + 1) * sizeof(int)));
-  HIPCHK(hipMalloc(&d.st, sizeof(MapState)));
-  HIPCHK(hipMemset(d.st, 0, sizeof(MapState)));
-  HIPCHK(hipMemset(d.mask, 0xFF, Pn * sizeof(int)));
-  HIPCHK(hipMemset(d.df, 0xFF, Pn * sizeof(unsigned)));
+  HIPCHK(own.device(&d.row_start, (size_t)c->P.rows + 1, 0));
+  HIPCHK(own.device(&d.st, 1, 0));
   // hipMemset on device memory returns BEFORE the fill has run (tools/memset_probe.hip on this runtime: the call takes 2.5 us, the
   // device finishes 10 us later for 1.2 MB), on the null stream, which the context's non-blocking streams do not wait for. A map
   // the pool grows by while the pipeline is running is handed to the detect kernels microseconds later: without this wait a late
@@ -536,24 +542,17 @@ int alloc_map(rebvio_hip_ctx* c, rebvio_hip_map* m) {
   // penalty: zero velocity, NaN covariance) - on a few per cent of fresh streams' first frames. (Round 3 saw records of this kind
   // on its 192x144 stream with kernel-bound stop events; the race explains them, that configuration was not re-run.)
   HIPCHK(hipStreamSynchronize(nullptr));
-  HIPCHK(hipEventCreateWithFlags(&m->ready, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->detected, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
+  HIPCHK(own.event(&m->ready));
+  HIPCHK(own.event(&m->detected));
+  HIPCHK(own.event(&m->done));
   return 0;
 }
 
 // device arrays and events of a map; the host struct stays (a handle the caller still holds is deleted by its release)
 void free_map_device(rebvio_hip_map* m) {
-  MapDev& d = m->d;
-  void* ptrs[] = {d.pos, d.pos_img, d.mpos_img, d.grad, d.grad_tmp, d.mgrad, d.gnorm, d.mgnorm, d.rs, d.rs_tmp, d.id_prev, d.id_next,
-                  d.match_id, d.match_fwd, d.match_kf, d.matches, d.fwd_key, d.residual, d.mask, d.df, d.unit, d.tile_cnt, d.tile_list, d.row_start, d.st};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  d = MapDev{};
+  m->own.release();
+  m->d = MapDev{};
   m->canon = MapDev{};
-  if (m->ready) (void)hipEventDestroy(m->ready);
-  if (m->detected) (void)hipEventDestroy(m->detected);
-  if (m->done) (void)hipEventDestroy(m->done);
   m->ready = m->detected = m->done = hipEvent_t{};
   m->ctx = nullptr;
 }
@@ -606,11 +605,9 @@ int fetch_map_state(rebvio_hip_map* m, MapState* out, hipStream_t after) {
   wait_enqueued(m);
   HIPCHK(hipStreamWaitEvent(c->s_key, m->ready, 0));
   if (after) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(e, after));
-    HIPCHK(hipStreamWaitEvent(c->s_key, e, 0));
-    (void)hipEventDestroy(e);
+    if (!c->fetch_ev) HIPCHK(c->own.event(&c->fetch_ev));
+    HIPCHK(hipEventRecord(c->fetch_ev, after));
+    HIPCHK(hipStreamWaitEvent(c->s_key, c->fetch_ev, 0));
   }
   HIPCHK(hipMemcpyAsync(c->h_st, m->d.st, sizeof(MapState), hipMemcpyDeviceToHost, c->s_key));
   HIPCHK(hipStreamSynchronize(c->s_key));
@@ -1000,13 +997,13 @@ int enqueue_pair_lm(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map* nm, c
 int stage_host_frame(rebvio_hip_ctx* c, const void* img, size_t pitch_bytes, size_t row_bytes, int* slot_out, size_t* bytes_out) {
   if (!c->pin[0]) {
     for (int i = 0; i < rebvio_hip_ctx::kPin; ++i) {
-      HIPCHK(hipHostMalloc(&c->pin[i], (size_t)c->P.rows * c->P.cols * sizeof(float) + 16, hipHostMallocDefault));  // (+16: copied in whole 16-byte units)
-      HIPCHK(hipEventCreateWithFlags(&c->pin_ev[i], hipEventDisableTiming));
+      HIPCHK(c->own.pinned(&c->pin[i], (size_t)c->P.rows * c->P.cols * sizeof(float) + 16, false));  // (+16: copied in whole 16-byte units)
+      HIPCHK(c->own.event(&c->pin_ev[i]));
     }
   }
   const int ps = (int)(c->pin_next++ % rebvio_hip_ctx::kPin);
   if (c->pin_used[ps]) HIPCHK(hipEventSynchronize(c->pin_ev[ps]));  // its previous copy has left the slot
-  uint8_t* dst = static_cast<uint8_t*>(c->pin[ps]);
+  uint8_t* dst = c->pin[ps];
   const uint8_t* src = static_cast<const uint8_t*>(img);
   if (pitch_bytes == row_bytes)
     std::memcpy(dst, src, (size_t)c->P.rows * row_bytes);
@@ -1171,12 +1168,12 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
     c->s_trk = t_adopt_streams->s_trk;
     c->owns_streams = false;
   } else {
-    HIPCHK(hipStreamCreateWithPriority(&c->s_det, hipStreamNonBlocking, prio_mid));
+    HIPCHK(c->own.stream(&c->s_det, hipStreamNonBlocking, prio_mid));
     // one stream per priority class: the runtime pools hardware queues per class (GPU_MAX_HW_QUEUES each) and lets streams of
     // a class share a queue once the pool is full, so two of our streams in one class can end up serialised behind each
     // other depending on what else the process created (measured with extra torch streams: 9.3k -> 7.0k frames/s)
-    HIPCHK(hipStreamCreateWithPriority(&c->s_key, hipStreamNonBlocking, prio_least));
-    HIPCHK(hipStreamCreateWithPriority(&c->s_trk, hipStreamNonBlocking, prio_greatest));
+    HIPCHK(c->own.stream(&c->s_key, hipStreamNonBlocking, prio_least));
+    HIPCHK(c->own.stream(&c->s_trk, hipStreamNonBlocking, prio_greatest));
     // Three streams per context (scans | keylines + distance field | tracking), deliberately not more: on this runtime every
     // additional stream of the process slowed the whole pipeline (measured, same code: 3 streams 9.3k frames/s, 4 streams
     // 9.2k, 5 streams 9.1k; creating a sixth, even unused, 2.6k). The rare copies of the synchronous API ride on the keyline stream.
@@ -1186,34 +1183,30 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
   // other per-pixel array is dense
   const size_t Pp = (size_t)p->rows * ((p->cols + 3) & ~3);
   for (int f = 0; f < 2; ++f) {
-    HIPCHK(hipMalloc(&c->sb.a[f], Pp * sizeof(float)));
-    HIPCHK(hipMalloc(&c->sb.b[f], Pp * sizeof(float)));
+    HIPCHK(c->own.device(&c->sb.a[f], Pp));
+    HIPCHK(c->own.device(&c->sb.b[f], Pp));
   }
   // (DoG / gradient buffers have the size of an integral image, padded pitch: a batch's fused path keeps the third pass's
   // integral images of a step parity in them)
-  HIPCHK(hipMalloc(&c->sb.dog, Pp * sizeof(float)));
-  HIPCHK(hipMalloc(&c->sb.mag, Pp * sizeof(float)));
-  HIPCHK(hipMalloc(&c->db.stash, Pn * sizeof(float4)));
-  HIPCHK(hipMalloc(&c->db.bits, (size_t)p->rows * K.nseg * sizeof(unsigned long long)));
-  HIPCHK(hipMalloc(&c->db.rowcount, (size_t)p->rows * sizeof(int)));
-  HIPCHK(hipMemset(c->db.rowcount, 0, (size_t)p->rows * sizeof(int)));
+  HIPCHK(c->own.device(&c->sb.dog, Pp));
+  HIPCHK(c->own.device(&c->sb.mag, Pp));
+  HIPCHK(c->own.device(&c->db.stash, Pn));
+  HIPCHK(c->own.device(&c->db.bits, (size_t)p->rows * K.nseg));
+  HIPCHK(c->own.device(&c->db.rowcount, (size_t)p->rows, 0));
   c->dog2[0] = c->sb.dog;
   c->mag2[0] = c->sb.mag;
   c->rowcount2[0] = c->db.rowcount;
-  for (int i = 0; i < 2; ++i) {
-    HIPCHK(hipEventCreateWithFlags(&c->ev_scan[i], hipEventDisableTiming));
-  }
+  for (auto& e : c->ev_scan) HIPCHK(c->own.event(&e));
   for (int f = 0; f < 2; ++f) {
     c->sa2[0][f] = c->sb.a[f];
-    HIPCHK(hipMalloc(&c->sa2[1][f], Pp * sizeof(float)));
+    HIPCHK(c->own.device(&c->sa2[1][f], Pp));
   }
   for (int i = 1; i < kDetPar; ++i) {
-    HIPCHK(hipMalloc(&c->dog2[i], Pp * sizeof(float)));
-    HIPCHK(hipMalloc(&c->mag2[i], Pp * sizeof(float)));
-    HIPCHK(hipMalloc(&c->rowcount2[i], (size_t)p->rows * sizeof(int)));
-    HIPCHK(hipMemset(c->rowcount2[i], 0, (size_t)p->rows * sizeof(int)));
+    HIPCHK(c->own.device(&c->dog2[i], Pp));
+    HIPCHK(c->own.device(&c->mag2[i], Pp));
+    HIPCHK(c->own.device(&c->rowcount2[i], (size_t)p->rows, 0));
   }
-  HIPCHK(hipMalloc(&c->det, (kDetRing + 1) * sizeof(DetState)));
+  HIPCHK(c->own.device(&c->det, kDetRing + 1));
   DetState d0[kDetRing + 1];
   for (int i = 0; i < kDetRing + 1; ++i) {
     d0[i].threshold = p->threshold;       // config_->threshold
@@ -1222,25 +1215,21 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
     d0[i].pad = 0;
   }
   HIPCHK(hipMemcpy(c->det, d0, sizeof(d0), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&c->img_dev, Pn * sizeof(float) + 16));  // (+16: host frames arrive in whole 16-byte units)
-  HIPCHK(hipMalloc(&c->img8_dev, Pn + 16));
-  HIPCHK(hipMalloc(&c->aos_dev, (size_t)p->keylines_max * sizeof(rebvio_hip_keyline)));
-  HIPCHK(hipMalloc(&c->scratch_i, 2 * Pn * sizeof(int)));
+  HIPCHK(c->own.device_bytes(&c->img_dev, Pn * sizeof(float) + 16));  // (+16: host frames arrive in whole 16-byte units)
+  HIPCHK(c->own.device(&c->img8_dev, Pn + 16));
+  HIPCHK(c->own.device(&c->aos_dev, (size_t)p->keylines_max));
+  HIPCHK(c->own.device(&c->scratch_i, 2 * Pn));
 
   c->maxblocks = div_up(p->keylines_max, 1024) * 4;  // record groups of 256 keylines, padded to whole 1024-thread workgroups
   // [2 parity slots][record groups][kPartStride] + the final-velocity broadcast words
-  HIPCHK(hipMalloc(&c->lm_xch, lm_xch_words(c->maxblocks) * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(c->lm_xch, 0, lm_xch_words(c->maxblocks) * sizeof(unsigned long long)));  // tag 0 = never published
-  HIPCHK(hipHostMalloc(&c->lm_bar_err, 8 * sizeof(int), hipHostMallocDefault));
-  std::memset(c->lm_bar_err, 0, 8 * sizeof(int));
+  HIPCHK(c->own.device(&c->lm_xch, lm_xch_words(c->maxblocks), 0));  // tag 0 = never published
+  HIPCHK(c->own.pinned(&c->lm_bar_err, 8, true));
   if (std::getenv("REBVIO_HIP_LM_STAMPS")) {
-    HIPCHK(hipHostMalloc(&c->lm_stamps, 64 * sizeof(unsigned long long), hipHostMallocDefault));
-    std::memset(c->lm_stamps, 0, 64 * sizeof(unsigned long long));
+    HIPCHK(c->own.pinned(&c->lm_stamps, 64, true));
     K.dbg = c->lm_stamps;
     if (std::getenv("REBVIO_HIP_DM_STATS")) {
       c->dm_stats_words = 16 * (size_t)(p->keylines_max / 8 + 130);
-      HIPCHK(hipMalloc(&c->dm_stats, c->dm_stats_words * sizeof(unsigned long long)));
-      HIPCHK(hipMemset(c->dm_stats, 0, c->dm_stats_words * sizeof(unsigned long long)));
+      HIPCHK(c->own.device(&c->dm_stats, c->dm_stats_words, 0));
       K.dm_stats = c->dm_stats;
     }
   }
@@ -1253,32 +1242,21 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
     c->lm_spec_forced_kf = std::strcmp(e, "spec3") == 0 ? 3 : 2;
     if (std::strncmp(e, "mix", 3) == 0) c->lm_mix = std::max(1, std::atoi(e + 3));
   }
-  HIPCHK(hipMalloc(&c->lm, 16 * sizeof(LmState)));
-  HIPCHK(hipMemset(c->lm, 0, 16 * sizeof(LmState)));
-  HIPCHK(hipMalloc(&c->part, (size_t)(kMaxLmCalls + 1) * part_call_stride(c) * sizeof(float)));
-  HIPCHK(hipMemset(c->part, 0, (size_t)(kMaxLmCalls + 1) * part_call_stride(c) * sizeof(float)));
-  HIPCHK(hipMalloc(&c->xrv_part, (size_t)c->maxblocks * kXrvStride * sizeof(float)));
-  HIPCHK(hipMalloc(&c->hist, 128 * sizeof(int)));
-  HIPCHK(hipMemset(c->hist, 0, 128 * sizeof(int)));
-  // long-search queue: keyline indices, then three float4 of probe geometry per entry (dm_queue_put in track.hip)
-  HIPCHK(hipMalloc(&c->lm_zero, sizeof(LmState)));
-  HIPCHK(hipMemset(c->lm_zero, 0, sizeof(LmState)));
+  HIPCHK(c->own.device(&c->lm, 16, 0));
+  HIPCHK(c->own.device(&c->part, (size_t)(kMaxLmCalls + 1) * part_call_stride(c), 0));
+  HIPCHK(c->own.device(&c->xrv_part, (size_t)c->maxblocks * kXrvStride));
+  HIPCHK(c->own.device(&c->hist, 128, 0));
+  HIPCHK(c->own.device(&c->lm_zero, 1, 0));
   for (int i = 0; i < rebvio_hip_ctx::kSlots; ++i) {
-    const size_t sz = sizeof(PairSlot) + (size_t)c->maxblocks * kXrvStride * sizeof(float);
-    HIPCHK(hipHostMalloc(&c->slot[i], sz, hipHostMallocDefault));
-    std::memset(c->slot[i], 0, sz);
-    HIPCHK(hipHostMalloc(&c->rec[i], sizeof(GlueRec), hipHostMallocDefault));
-    std::memset(c->rec[i], 0, sizeof(GlueRec));
-    HIPCHK(hipEventCreateWithFlags(&c->q.slot_ev[i], hipEventDisableTiming));
+    HIPCHK(c->own.pinned_bytes(&c->slot[i], sizeof(PairSlot) + (size_t)c->maxblocks * kXrvStride * sizeof(float), true));
+    HIPCHK(c->own.pinned(&c->rec[i], 1, true));
+    HIPCHK(c->own.event(&c->q.slot_ev[i]));
   }
-  HIPCHK(hipMalloc(&c->fscratch, 64 * sizeof(float)));
-  HIPCHK(hipMalloc(&c->glue_dev, rebvio_hip_ctx::kSlots * sizeof(GlueDev)));
-  HIPCHK(hipMemset(c->glue_dev, 0, rebvio_hip_ctx::kSlots * sizeof(GlueDev)));
-  HIPCHK(hipMalloc(&c->glue_stage, rebvio_hip_ctx::kSlots * sizeof(GlueStage)));
-  HIPCHK(hipMemset(c->glue_stage, 0, rebvio_hip_ctx::kSlots * sizeof(GlueStage)));
-  HIPCHK(hipMalloc(&c->gstate, 2 * sizeof(GlueState)));
-  HIPCHK(hipMemset(c->gstate, 0, 2 * sizeof(GlueState)));
-  HIPCHK(hipHostMalloc(&c->h_gstate, 2 * sizeof(GlueState), hipHostMallocDefault));
+  HIPCHK(c->own.device(&c->fscratch, 64));
+  HIPCHK(c->own.device(&c->glue_dev, rebvio_hip_ctx::kSlots, 0));
+  HIPCHK(c->own.device(&c->glue_stage, rebvio_hip_ctx::kSlots, 0));
+  HIPCHK(c->own.device(&c->gstate, 2, 0));
+  HIPCHK(c->own.pinned(&c->h_gstate, 2, false));
   if (const char* l = std::getenv("REBVIO_HIP_LEAD")) c->lead = std::min(12, std::max(3, std::atoi(l)));
   if (const char* g = std::getenv("REBVIO_HIP_GROUP")) c->group = std::min(6, std::max(1, std::atoi(g)));
   if (const char* e = std::getenv("REBVIO_HIP_LM_THREADS")) {
@@ -1287,11 +1265,11 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
   }
   if (const char* e = std::getenv("REBVIO_HIP_DM_HEAD"))  // directedMatch head form (track.hip, dm_head_wide): thread | wide; default by map size
     c->dm_head_form = dm_form_by_name(e);
-  HIPCHK(hipHostMalloc(&c->h_lm, 2 * sizeof(LmState), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc(&c->h_part, part_call_stride(c) * sizeof(float), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc(&c->h_xrv, (size_t)c->maxblocks * kXrvStride * sizeof(float), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc(&c->h_st, 2 * sizeof(MapState), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc(&c->h_f, 64 * sizeof(float), hipHostMallocDefault));
+  HIPCHK(c->own.pinned(&c->h_lm, 2, false));
+  HIPCHK(c->own.pinned(&c->h_part, part_call_stride(c), false));
+  HIPCHK(c->own.pinned(&c->h_xrv, (size_t)c->maxblocks * kXrvStride, false));
+  HIPCHK(c->own.pinned(&c->h_st, 2, false));
+  HIPCHK(c->own.pinned(&c->h_f, 64, false));
 
   int pool = p->map_pool > 0 ? p->map_pool : 6;
   if (pool < 4) pool = 4;
@@ -1336,59 +1314,11 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
     if (!m->in_use) delete m;  // (else: a handle is still out; its release deletes the husk)
   }
   c->pool.clear();
-  void* dptr[] = {c->sb.a[0], c->sb.a[1], c->sb.b[0], c->sb.b[1], c->sb.dog, c->sb.mag, c->db.stash, c->db.bits,
-                  c->db.rowcount, c->det, c->img_dev, c->img8_dev, c->aos_dev, c->scratch_i, c->diag0, c->diag1, c->lm,
-                  c->part, c->xrv_part, c->hist, c->fscratch, c->dmask_buf};
-  for (void* p : dptr)
-    if (p) (void)hipFree(p);
-  for (int f = 0; f < 2; ++f)
-    if (c->sa2[1][f]) (void)hipFree(c->sa2[1][f]);
-  void* hptr[] = {c->h_lm, c->h_part, c->h_xrv, c->h_st, c->h_f};
-  for (void* p : hptr)
-    if (p) (void)hipHostFree(p);
-  if (c->owns_streams) {
-    if (c->s_det) (void)hipStreamDestroy(c->s_det);
-    if (c->s_trk) (void)hipStreamDestroy(c->s_trk);
-    if (c->s_key) (void)hipStreamDestroy(c->s_key);
-  }
-  for (int i = 0; i < 2; ++i) {
-    if (c->ev_scan[i]) (void)hipEventDestroy(c->ev_scan[i]);
-  }
-  for (int i = 1; i < kDetPar; ++i) {
-    if (c->dog2[i]) (void)hipFree(c->dog2[i]);
-    if (c->mag2[i]) (void)hipFree(c->mag2[i]);
-    if (c->rowcount2[i]) (void)hipFree(c->rowcount2[i]);
-  }
-  for (int i = 0; i < rebvio_hip_ctx::kSlots; ++i) {
-    if (c->slot[i]) (void)hipHostFree(c->slot[i]);
-    if (c->rec[i]) (void)hipHostFree(c->rec[i]);
-    if (c->q.slot_ev[i]) (void)hipEventDestroy(c->q.slot_ev[i]);
-  }
-  if (c->gstate) (void)hipFree(c->gstate);
-  if (c->h_gstate) (void)hipHostFree(c->h_gstate);
-  if (c->undist_map) (void)hipFree(c->undist_map);
-  for (int i = 0; i < kDetPar; ++i)
-    if (c->undist_img[i]) (void)hipFree(c->undist_img[i]);
-  if (c->lm_xch) (void)hipFree(c->lm_xch);
-  for (int i = 0; i < rebvio_hip_ctx::kPin; ++i) {
-    if (c->pin[i]) (void)hipHostFree(c->pin[i]);
-    if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]);
-  }
-  if (c->glue_dev) (void)hipFree(c->glue_dev);
-  if (c->glue_stage) (void)hipFree(c->glue_stage);
-  if (c->lm_bar_err) (void)hipHostFree(c->lm_bar_err);
-  if (c->lm_stamps) (void)hipHostFree(c->lm_stamps);
-  if (c->dm_stats) (void)hipFree(c->dm_stats);
-  for (auto& e : c->bf_done)
-    if (e) (void)hipEventDestroy(e);
-  if (c->h_bf) (void)hipHostFree(c->h_bf);
-  if (c->lm_zero) (void)hipFree(c->lm_zero);
   for (auto* cl : c->clouds) {
     free_cloud_device(cl);
     if (!cl->in_use) delete cl;  // (else: the handle is still out; its release deletes the husk)
   }
-  if (c->cloud_scratch) (void)hipFree(c->cloud_scratch);
-  if (c->s_cloud) (void)hipStreamDestroy(c->s_cloud);
+  c->own.release();
   delete c;
 }
 
@@ -1396,8 +1326,8 @@ int rebvio_hip_scale_space(rebvio_hip_ctx* c, const float* img, float* scale0, f
   HIPCHK(hipSetDevice(c->device));
   const size_t nb = (size_t)c->P.rows * c->P.cols * sizeof(float);
   if (!c->diag0) {
-    HIPCHK(hipMalloc(&c->diag0, nb));
-    HIPCHK(hipMalloc(&c->diag1, nb));
+    HIPCHK(c->own.device_bytes(&c->diag0, nb));
+    HIPCHK(c->own.device_bytes(&c->diag1, nb));
   }
   HIPCHK(hipMemcpyAsync(c->img_dev, img, nb, hipMemcpyHostToDevice, c->s_det));
   ScaleBufs sb = c->sb;
@@ -1462,17 +1392,16 @@ int rebvio_hip_set_undistort(rebvio_hip_ctx* c, const float K4[4], const float D
   bool any = false;
   for (int i = 0; i < 5; ++i) any = any || (D5[i] != 0.0f);
   if (!any) {  // identity: the fixed-point map reproduces x3 exactly, skip the gather
-    if (c->undist_map) (void)hipFree(c->undist_map);
-    c->undist_map = nullptr;
+    c->own.drop(&c->undist_map);
     return 0;
   }
   if (!(K4[0] > 0.0f) || !(K4[1] > 0.0f)) return fail_msg("set_undistort: focal lengths must be positive", -3);
   const size_t Pn = (size_t)c->P.rows * c->P.cols;
   std::vector<int> map(2 * Pn);
   hm::undistort_fixed_map(c->P.rows, c->P.cols, K4[0], K4[1], K4[2], K4[3], D5[0], D5[1], D5[2], D5[3], D5[4], map.data());
-  if (!c->undist_map) HIPCHK(hipMalloc(&c->undist_map, Pn * sizeof(int2)));
+  if (!c->undist_map) HIPCHK(c->own.device(&c->undist_map, Pn));
   for (int i = 0; i < kDetPar; ++i)
-    if (!c->undist_img[i]) HIPCHK(hipMalloc(&c->undist_img[i], Pn * sizeof(float)));
+    if (!c->undist_img[i]) HIPCHK(c->own.device(&c->undist_img[i], Pn));
   HIPCHK(hipMemcpy(c->undist_map, map.data(), Pn * sizeof(int2), hipMemcpyHostToDevice));
   return 0;
 }
@@ -1620,21 +1549,18 @@ static_assert(sizeof(rebvio_hip_cloud_point) == 32 && sizeof(CloudHdr) == 64, "a
 
 int alloc_cloud(rebvio_hip_ctx* c, rebvio_hip_cloud* cl) {
   const size_t bytes = sizeof(CloudHdr) + (size_t)c->P.keylines_max * sizeof(rebvio_hip_cloud_point);
-  HIPCHK(hipHostMalloc((void**)&cl->hdr, bytes, hipHostMallocDefault));
+  HIPCHK(cl->own.pinned_bytes(&cl->hdr, bytes, false));
   std::memset(cl->hdr, 0, sizeof(CloudHdr));
-  HIPCHK(hipMalloc((void**)&cl->dev_buf, bytes));
+  HIPCHK(cl->own.device(&cl->dev_buf, bytes));
   cl->dev = cl->dev_buf + sizeof(CloudHdr);
-  HIPCHK(hipEventCreateWithFlags(&cl->extracted, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&cl->done, hipEventDisableTiming));
+  HIPCHK(cl->own.event(&cl->extracted));
+  HIPCHK(cl->own.event(&cl->done));
   return 0;
 }
 
 // buffers and events of a cloud; the host struct stays (a handle the caller still holds is deleted by its release)
 void free_cloud_device(rebvio_hip_cloud* cl) {
-  if (cl->hdr) (void)hipHostFree(cl->hdr);
-  if (cl->dev_buf) (void)hipFree(cl->dev_buf);
-  if (cl->done) (void)hipEventDestroy(cl->done);
-  if (cl->extracted) (void)hipEventDestroy(cl->extracted);
+  cl->own.release();
   cl->hdr = nullptr;
   cl->dev_buf = nullptr;
   cl->dev = nullptr;
@@ -1668,10 +1594,9 @@ int enqueue_cloud(const char* who, rebvio_hip_map* m, const rebvio_hip_cloud_fil
   a.cap = (cap < 0 || cap > c->P.keylines_max) ? c->P.keylines_max : cap;
   std::lock_guard<std::mutex> lk(c->cloud_mu);
   if (!c->cloud_scratch) {
-    HIPCHK(hipMalloc(&c->cloud_scratch, (kMaxRecBlocks + 1) * sizeof(int)));
-    HIPCHK(hipMemset(c->cloud_scratch, 0, (kMaxRecBlocks + 1) * sizeof(int)));
+    HIPCHK(c->own.device(&c->cloud_scratch, kMaxRecBlocks + 1, 0));
     HIPCHK(hipStreamSynchronize(nullptr));  // (hipMemset returns before the fill has run: alloc_map)
-    HIPCHK(hipStreamCreateWithFlags(&c->s_cloud, hipStreamNonBlocking));
+    HIPCHK(c->own.stream(&c->s_cloud, hipStreamNonBlocking));
   }
   rebvio_hip_cloud* cl = nullptr;
   for (auto* x : c->clouds)
@@ -1935,8 +1860,8 @@ int rebvio_hip_smooth_n(rebvio_hip_ctx* c, const float* img, const int* widths, 
     if (widths[k] < 3 || widths[k] > 11 || (widths[k] & 1) == 0) return fail_msg("smooth: box widths must be odd and in 3..11", -3);
   const size_t nb = (size_t)c->P.rows * c->P.cols * sizeof(float);
   if (!c->diag0) {
-    HIPCHK(hipMalloc(&c->diag0, nb));
-    HIPCHK(hipMalloc(&c->diag1, nb));
+    HIPCHK(c->own.device_bytes(&c->diag0, nb));
+    HIPCHK(c->own.device_bytes(&c->diag1, nb));
   }
   HIPCHK(hipStreamSynchronize(c->s_key));  // the scratch DoG / gradient buffers below belong to frames in flight
   HIPCHK(hipMemcpyAsync(c->img_dev, img, nb, hipMemcpyHostToDevice, c->s_det));
@@ -2248,8 +2173,8 @@ int rebvio_hip_track_pair_begin(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hi
   std::memset(mid, 0, sizeof(*mid));
   hipStream_t s = c->s_trk;
   if (!c->h_bf) {
-    HIPCHK(hipHostMalloc(&c->h_bf, 2 * sizeof(MapState), hipHostMallocDefault));
-    for (auto& e : c->bf_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(c->own.pinned(&c->h_bf, 2, false));
+    for (auto& e : c->bf_done) HIPCHK(c->own.event(&e));
   }
   c->bf_cur = (c->bf_res == 0) ? 1 : 0;  // the slot that does not hold an unfetched result
   // The previous pair's match counters (unfetched: result slot bf_res). If this pair continues from its new map they arrive
@@ -2852,11 +2777,8 @@ int rebvio_hip_test_glue(rebvio_hip_ctx* c, const float vel[3], const float JtJ6
   { const int rc_ts = trk_sync(c); if (rc_ts) return rc_ts; }
   char* buf = nullptr;
   const size_t xb = (size_t)std::max(nb, 1) * kXrvStride * sizeof(float);
-  HIPCHK(hipMalloc(&buf, sizeof(LmState) + sizeof(MapState) + 2 * sizeof(GlueState) + sizeof(GlueDev) + sizeof(GlueRec) + xb));
-  struct Free {
-    char* p;
-    ~Free() { (void)hipFree(p); }
-  } guard{buf};
+  Owned scratch;
+  HIPCHK(scratch.device(&buf, sizeof(LmState) + sizeof(MapState) + 2 * sizeof(GlueState) + sizeof(GlueDev) + sizeof(GlueRec) + xb));
   LmState* d_lm = reinterpret_cast<LmState*>(buf);
   MapState* d_ms = reinterpret_cast<MapState*>(d_lm + 1);
   GlueState* d_st = reinterpret_cast<GlueState*>(d_ms + 1);
@@ -2983,6 +2905,7 @@ struct rebvio_hip_batch {
   int device = 0;
   rebvio_hip_params P{};
   KParams K{};
+  Owned own;  // the batch's buffers and events, and the three streams its lanes adopt
   SharedStreams st{};
   std::vector<rebvio_hip_ctx*> lane;
   LaneStatic* ls_dev = nullptr;
@@ -3212,19 +3135,7 @@ void rebvio_hip_batch_destroy(rebvio_hip_batch* b) {
   for (int i = 0; i < b->q.count; ++i)
     for (int l = 0; l < b->B; ++l) b->q[i].nm[l]->in_use = false;
   for (auto* c : b->lane) rebvio_hip_destroy(c);
-  if (b->ls_dev) (void)hipFree(b->ls_dev);
-  if (b->maptab_dev) (void)hipFree(b->maptab_dev);
-  for (int i = 0; i < kDetPar; ++i) {
-    if (b->ev_scan[i]) (void)hipEventDestroy(b->ev_scan[i]);
-    if (b->ev_flag[i]) (void)hipEventDestroy(b->ev_flag[i]);
-  }
-  for (auto& e : b->ev_ready)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : b->q.slot_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (b->st.s_det) (void)hipStreamDestroy(b->st.s_det);
-  if (b->st.s_key) (void)hipStreamDestroy(b->st.s_key);
-  if (b->st.s_trk) (void)hipStreamDestroy(b->st.s_trk);
+  b->own.release();
   delete b;
 }
 
@@ -3266,9 +3177,9 @@ int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_ba
   b->P = *p;
   // the three stages of a step overlap across steps like the stages of one stream do; one priority class for all
   // (see the comment on rebvio_hip_batch: priorities are what made pipelines starve each other)
-  HIPCHK(hipStreamCreateWithFlags(&b->st.s_det, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&b->st.s_key, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&b->st.s_trk, hipStreamNonBlocking));
+  HIPCHK(b->own.stream(&b->st.s_det, hipStreamNonBlocking));
+  HIPCHK(b->own.stream(&b->st.s_key, hipStreamNonBlocking));
+  HIPCHK(b->own.stream(&b->st.s_trk, hipStreamNonBlocking));
   for (int l = 0; l < lanes; ++l) {
     rebvio_hip_ctx* c = nullptr;
     rebvio_hip_params pl = *p;
@@ -3282,8 +3193,7 @@ int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_ba
   }
   b->K = b->lane[0]->K;
   std::vector<LaneStatic> ls((size_t)lanes);
-  HIPCHK(hipMalloc(&b->maptab_dev, (size_t)lanes * kLaneMaps * sizeof(MapDev)));
-  HIPCHK(hipMemset(b->maptab_dev, 0, (size_t)lanes * kLaneMaps * sizeof(MapDev)));
+  HIPCHK(b->own.device(&b->maptab_dev, (size_t)lanes * kLaneMaps, 0));
   for (int l = 0; l < lanes; ++l) {
     rebvio_hip_ctx* c = b->lane[l];
     LaneStatic& L = ls[l];
@@ -3319,15 +3229,15 @@ int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_ba
       if (rc) return rc;
     }
   }
-  HIPCHK(hipMalloc(&b->ls_dev, ls.size() * sizeof(LaneStatic)));
+  HIPCHK(b->own.device(&b->ls_dev, ls.size()));
   HIPCHK(hipMemcpy(b->ls_dev, ls.data(), ls.size() * sizeof(LaneStatic), hipMemcpyHostToDevice));
   b->ls_host = ls;
   for (int i = 0; i < kDetPar; ++i) {
-    HIPCHK(hipEventCreateWithFlags(&b->ev_scan[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&b->ev_flag[i], hipEventDisableTiming));
+    HIPCHK(b->own.event(&b->ev_scan[i]));
+    HIPCHK(b->own.event(&b->ev_flag[i]));
   }
-  for (auto& e : b->ev_ready) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : b->q.slot_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : b->ev_ready) HIPCHK(b->own.event(&e));
+  for (auto& e : b->q.slot_ev) HIPCHK(b->own.event(&e));
   if (const char* e = std::getenv("REBVIO_HIP_BATCH_LEAD")) b->lead = std::min(8, std::max(3, std::atoi(e)));
   if (const char* e = std::getenv("REBVIO_HIP_BATCH_GROUP")) b->group = std::min(4, std::max(1, std::atoi(e)));
   if (const char* e = std::getenv("REBVIO_HIP_BATCH_DM_HEAD"))
@@ -3346,6 +3256,7 @@ int rebvio_hip_batch_test_forge_record_stamp(rebvio_hip_batch* b) {
   b->forge_stamp = true;
   return 0;
 }
+long rebvio_hip_test_live_resources(void) { return g_live_resources.load(std::memory_order_relaxed); }
 rebvio_hip_ctx* rebvio_hip_batch_lane(rebvio_hip_batch* b, int lane) { return (lane >= 0 && lane < b->B) ? b->lane[lane] : nullptr; }
 
 // masks_dev: this step's per-frame detection mask of every lane (null array, or a null entry: none)
@@ -3520,7 +3431,7 @@ int rebvio_hip_set_detection_mask(rebvio_hip_ctx* c, const uint8_t* mask, size_t
   if (rebvio_hip_batch* b = c->batch)
     while (b->det_done_steps.load(std::memory_order_acquire) < b->step) std::this_thread::yield();
   HIPCHK(hipStreamSynchronize(c->s_key));
-  if (!c->dmask_buf) HIPCHK(hipMalloc(&c->dmask_buf, rows * cols));
+  if (!c->dmask_buf) HIPCHK(c->own.device(&c->dmask_buf, rows * cols));
   HIPCHK(hipMemcpy2D(c->dmask_buf, cols, mask, pitch_bytes ? pitch_bytes : cols, cols, rows, hipMemcpyHostToDevice));
   c->dmask = c->dmask_buf;
   return 0;
