@@ -757,8 +757,10 @@ __global__ __launch_bounds__(256) void k_lm_final(MapDev om, int calls, const Lm
   __shared__ float red[16];
   __shared__ float carry_in;
   __shared__ float rec[kMaxRecBlocks * kPartStride];
-  stage_prev_records(part_prev, kMaxRecBlocks, rec);
+  // only the live groups: the launch has one workgroup, and the records of one evaluation are as many as the context's keyline
+  // budget has groups - staging kMaxRecBlocks of them read past the end of the buffer for budgets under 16 k keylines
   const int nb = (om.st->n + 255) / 256;
+  stage_prev_records(part_prev, nb, rec);
   __syncthreads();
   reduce_staged_records(rec, nb, red, &carry_in, 0, 1);
   __syncthreads();

@@ -541,18 +541,19 @@ def _record_words(po):
     return np.concatenate(out)
 
 
-def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, what, every_pair_tracks=False):
+def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, what, every_pair_tracks=False, expect_status=None):
     """frames[order] through the oracle (keyline sums in the kernels' order) and through the library, the state carried
     independently on both sides: every word of every pair record equal through the per-pair API and through the streaming
     driver, every keyline field of the newest map equal after the last pair. every_pair_tracks: a precondition on the oracle
     alone - each pair ends with status 0 and at least global_min_matches_threshold LM matches (a real pair, not a failure
-    path); without it only the last pair is asked for motion and more than min_klm matches."""
+    path); without it only the last pair is asked for motion and more than min_klm matches. expect_status: the oracle's pair
+    statuses, one per pair - asked for in place of that closing condition, for streams whose pairs are meant to fail."""
     W, H, npairs = cam.width, cam.height, len(order) - 1
     p_o = params_for(orc_mod, cam, **kw)
     orc = orc_mod.Oracle(p_o)
     orc.set_sum_order("device")
     gpu = B.Context(params_for(B, cam, **kw))
-    mo, mg, rec_o = [], [], []
+    mo, mg, rec_o, status_o = [], [], [], []
     for k, i in enumerate(order):
         mo.append(orc.detect_u8(frames[i], k * 50000))
         mg.append(gpu.detect_u8(frames[i], k * 50000))
@@ -568,7 +569,11 @@ def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, w
         wo, wg = _record_words(po), _record_words(pg)
         assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
         rec_o.append(wo)
-    assert rec_o[-1][0] != 0 and po.klm_num > min_klm
+        status_o.append(po.status)
+    if expect_status is None:
+        assert rec_o[-1][0] != 0 and po.klm_num > min_klm
+    else:
+        assert status_o == list(expect_status), (what, status_o)
     # the map that carries the state into the next pair (the older one is dropped after its pair, rebvio.cpp:136-139)
     assert_keylines_equal(mo[1].keylines(), mg[1].keylines(), what=f"{what}: newest map after {npairs} pairs")
     gpu.close()
