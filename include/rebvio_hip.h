@@ -303,7 +303,8 @@ int rebvio_hip_minimize_vel(rebvio_hip_ctx* ctx, rebvio_hip_map* m, float vel[3]
 int rebvio_hip_forward_match(rebvio_hip_ctx* ctx, rebvio_hip_map* old_map, rebvio_hip_map* new_map);
 /* Core::extRotVel (core.cpp:191-261) on the distance field's map. JtJ 6x6 row-major, JtF[6], X[6]. */
 int rebvio_hip_ext_rot_vel(rebvio_hip_ctx* ctx, const float vel[3], float Wx[36], float JtF[6], float X[6], int* ok);
-/* EdgeMap::directedMatch (edge_map.cpp:186-218): new_map->directedMatch(old_map, ...). */
+/* EdgeMap::directedMatch (edge_map.cpp:186-218): new_map->directedMatch(old_map, ...). -3 when max_radius is outside 0..255 or
+ * max_radius + 2 * pixel_uncertainty_match + 2 exceeds 260 (the bound rebvio_hip_create puts on search_range). */
 int rebvio_hip_directed_match(rebvio_hip_ctx* ctx, rebvio_hip_map* new_map, rebvio_hip_map* old_map, const float vel[3],
                               const float Rvel[9], const float Rback[9], float max_radius, int* matches,
                               int* kf_matches);

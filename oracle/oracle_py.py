@@ -129,6 +129,7 @@ def lib(path: str | None = None):
         "orc_ext_rot_vel": (C.c_int, [vp, fp, fp, fp, fp]),
         "orc_directed_match": (C.c_int, [vp, vp, vp, fp, fp, fp, ip, C.c_float]),
         "orc_regularize": (C.c_int, [vp]),
+        "orc_regularize_cfg": (C.c_int, [vp, vp]),
         "orc_update_inverse_depth": (None, [vp, fp]),
         "orc_reset_state": (None, [vp]),
         "orc_track_pair": (C.c_int, [vp, vp, vp, fp, C.c_float, C.POINTER(PairOut)]),
@@ -141,6 +142,8 @@ def lib(path: str | None = None):
         "orc_so3_exp": (None, [fp, fp]),
         "orc_sym6_solve": (None, [fp, fp, fp]),
         "orc_search_match": (C.c_int, [vp, vp, vp, fp, fp, fp, C.c_float]),
+        "orc_search_match_step": (C.c_int, [vp, vp, vp, fp, fp, fp, C.c_float, ip]),
+        "orc_search_setup": (None, [vp, vp, fp, fp, fp, C.c_float, fp]),
         "orc_test_fk": (C.c_int, [vp, vp, C.c_float]),
         "orc_calculate_fj": (C.c_float, [vp, C.c_int, fp, fp, vp, C.c_float, C.c_float, ip, fp]),
         "orc_update_inverse_depth_arlu": (None, [vp, vp, fp]),
@@ -325,7 +328,7 @@ class Oracle:
         return n, kf.value
 
     def regularize(self, m: Map):
-        return self.L.orc_regularize(m.h)
+        return self.L.orc_regularize_cfg(self.h, m.h)
 
     def search_match(self, searched: Map, query_keyline, vel, Rvel, Rback, max_radius=40.0) -> int:
         q = np.ascontiguousarray(np.asarray(query_keyline, KEYLINE_DTYPE).reshape(1))
@@ -333,6 +336,35 @@ class Oracle:
         Rvel, prv = _f(np.asarray(Rvel).reshape(9))
         Rback, prb = _f(np.asarray(Rback).reshape(9))
         return self.L.orc_search_match(self.h, searched.h, q.ctypes.data, pv, prv, prb, max_radius)
+
+    def search_match_steps(self, searched: Map, queries: np.ndarray, vel, Rvel, Rback, max_radius=40.0):
+        """search_match for every record of `queries`: (matched index, step of the probe loop at which it was accepted), -1 each
+        where there is no match."""
+        q = np.ascontiguousarray(queries, KEYLINE_DTYPE)
+        vel, pv = _f(vel)
+        Rvel, prv = _f(np.asarray(Rvel).reshape(9))
+        Rback, prb = _f(np.asarray(Rback).reshape(9))
+        ids = np.full(len(q), -1, np.int32)
+        steps = np.full(len(q), -1, np.int32)
+        st = C.c_int(-1)
+        for i in range(len(q)):
+            ids[i] = self.L.orc_search_match_step(self.h, searched.h, q.ctypes.data + i * KEYLINE_DTYPE.itemsize, pv, prv, prb,
+                                                  max_radius, C.byref(st))
+            steps[i] = st.value
+        return ids, steps
+
+    def search_setup(self, queries: np.ndarray, vel, Rvel, Rback, max_radius=40.0) -> np.ndarray:
+        """The probe geometry of searchMatch per record of `queries`: columns dq_min, dq_rho, dq_max, t_x, t_y, norm_t, t_steps,
+        sigma2_t."""
+        q = np.ascontiguousarray(queries, KEYLINE_DTYPE)
+        vel, pv = _f(vel)
+        Rvel, prv = _f(np.asarray(Rvel).reshape(9))
+        Rback, prb = _f(np.asarray(Rback).reshape(9))
+        out = np.zeros((len(q), 8), np.float32)
+        for i in range(len(q)):
+            self.L.orc_search_setup(self.h, q.ctypes.data + i * KEYLINE_DTYPE.itemsize, pv, prv, prb, max_radius,
+                                    out[i].ctypes.data_as(C.POINTER(C.c_float)))
+        return out
 
     def smooth(self, img, sigma, n=3):
         img, pi = _f(img)

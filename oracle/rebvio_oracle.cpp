@@ -1064,8 +1064,11 @@ inline int get_index(const orc_params& P, float frow, float fcol) {
 
 // EdgeMap::searchMatch (edge_map.cpp:101-184) on `old_map`, for keyline `kq` of the other map.
 int search_match(const orc_ctx* c, const orc_map* old_map, const orc_keyline& kq, const float vel[3],
-                 const M3& Rvel, const M3& Rback, float max_radius) {
+                 const M3& Rvel, const M3& Rback, float max_radius, int* step_out = nullptr,
+                 float* setup_out = nullptr) {
+  // step_out (a diagnostic for the tests): the step t_i at which the match was accepted, -1 without a match
   const orc_params& P = c->p;
+  if (step_out) *step_out = -1;
   const float cang_min_edge = std::cos(P.match_threshold_angle * M_PI / 180.0);
 
   float v3[3] = {kq.pos_img[0], kq.pos_img[1], P.fm};
@@ -1119,6 +1122,11 @@ int search_match(const orc_ctx* c, const orc_map* old_map, const orc_keyline& kq
     t_steps = cvtt(dq_max);
   }
 
+  if (setup_out) {  // (a diagnostic for the tests: the probe geometry alone, nothing is searched)
+    const float v[8] = {dq_min, dq_rho, dq_max, t_x, t_y, norm_t, (float)t_steps, sigma2_t};
+    std::memcpy(setup_out, v, sizeof(v));
+    return -1;
+  }
   float tn = dq_rho;
   float tp = dq_rho + 1;
   for (int t_i = 0; t_i < t_steps; ++t_i, ++tp, --tn) {
@@ -1141,6 +1149,7 @@ int search_match(const orc_ctx* c, const orc_map* old_map, const orc_keyline& kq
       float v_rho_dr = (P.pixel_uncertainty_match * P.pixel_uncertainty_match + k.sigma_rho * k.sigma_rho * norm_t * norm_t +
                         sigma2_t * k.rho * k.rho);
       if ((t - norm_t * k.rho) * (t - norm_t * k.rho) > v_rho_dr) continue;
+      if (step_out) *step_out = t_i;
       return cand;
     }
   }
@@ -1758,6 +1767,12 @@ int orc_regularize(orc_map* m) {
   return regularize_1iter(nullptr, m, 0.5f);
 }
 
+int orc_regularize_cfg(orc_ctx* c, orc_map* m) {
+  // a map handed the context's EdgeMapConfig (edge_map.hpp:19-26, :34): regularization_threshold is one of its four members,
+  // like the three that searchMatch reads from the same parameters
+  return regularize_1iter(c, m, c->p.regularization_threshold);
+}
+
 void orc_update_inverse_depth(orc_ctx* c, const float vel[3]) {
   // Core::updateInverseDepth (core.cpp:417-422)
   orc_map* m = c->df_map;
@@ -1863,7 +1878,7 @@ int orc_track_pair(orc_ctx* c, orc_map* old_map, orc_map* new_map, const float* 
     out->status = 2;
     return 2;
   }
-  out->reg_num = orc_regularize(new_map);  // rebvio.cpp:256
+  out->reg_num = orc_regularize_cfg(c, new_map);  // rebvio.cpp:256
   orc_update_inverse_depth(c, V);          // rebvio.cpp:259
   return 0;
 }
@@ -1914,6 +1929,16 @@ void orc_sym6_solve(const float A[36], const float b[6], float x[6]) { sym_pinv_
 int orc_search_match(orc_ctx* c, orc_map* searched, const orc_keyline* query, const float vel[3], const float Rvel[9],
                      const float Rback[9], float max_radius) {
   return search_match(c, searched, *query, vel, m3_from(Rvel), m3_from(Rback), max_radius);
+}
+
+int orc_search_match_step(orc_ctx* c, orc_map* searched, const orc_keyline* query, const float vel[3], const float Rvel[9],
+                          const float Rback[9], float max_radius, int* step_out) {
+  return search_match(c, searched, *query, vel, m3_from(Rvel), m3_from(Rback), max_radius, step_out);
+}
+
+void orc_search_setup(orc_ctx* c, const orc_keyline* query, const float vel[3], const float Rvel[9], const float Rback[9],
+                      float max_radius, float out[8]) {
+  search_match(c, nullptr, *query, vel, m3_from(Rvel), m3_from(Rback), max_radius, nullptr, out);
 }
 
 int orc_test_fk(const orc_keyline* k1, const orc_keyline* k2, float similarity_threshold) {
@@ -2376,7 +2401,7 @@ extern "C" int orc_vio_step(orc_ctx* c, orc_map* old_map, orc_map* new_map, orc_
       c->P_Kp = FMAX;
       po->status = 2;
     } else {
-      po->reg_num = orc_regularize(new_map);
+      po->reg_num = orc_regularize_cfg(c, new_map);
       orc_update_inverse_depth(c, V);
     }
   }

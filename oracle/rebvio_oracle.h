@@ -124,7 +124,8 @@ int orc_forward_match(orc_map* old_map, orc_map* new_map);
 int orc_ext_rot_vel(orc_ctx* c, const float vel[3], float Wx[36], float X[6], float JtF_out[6]);
 int orc_directed_match(orc_ctx* c, orc_map* new_map, orc_map* old_map, const float vel[3],
                        const float Rvel[9], const float Rback[9], int* kf_matches, float max_radius);
-int orc_regularize(orc_map* m);
+int orc_regularize(orc_map* m);                 /* regularize1Iter at the default threshold 0.5 */
+int orc_regularize_cfg(orc_ctx* c, orc_map* m); /* ... at the context's regularization_threshold  */
 void orc_update_inverse_depth(orc_ctx* c, const float vel[3]);
 
 /* Single-keyline forms of the reference's public methods: EdgeMap::searchMatch (edge_map.cpp:101-184) on `searched`,
@@ -132,6 +133,13 @@ void orc_update_inverse_depth(orc_ctx* c, const float vel[3]);
  * Core::updateInverseDepthARLU (core.cpp:424-456), FastGaussian(camera, sigma, n).smooth (scale_space.cpp:14-41,173-182). */
 int orc_search_match(orc_ctx* c, orc_map* searched, const orc_keyline* query, const float vel[3], const float Rvel[9],
                      const float Rback[9], float max_radius);
+/* orc_search_match, and the step t_i of the reference's probe loop at which the match was accepted (-1: none) */
+int orc_search_match_step(orc_ctx* c, orc_map* searched, const orc_keyline* query, const float vel[3], const float Rvel[9],
+                          const float Rback[9], float max_radius, int* step_out);
+/* the probe geometry searchMatch derives for `query` (edge_map.cpp:107-147): dq_min, dq_rho, dq_max, t_x, t_y, norm_t, t_steps,
+ * sigma2_t */
+void orc_search_setup(orc_ctx* c, const orc_keyline* query, const float vel[3], const float Rvel[9], const float Rback[9],
+                      float max_radius, float out[8]);
 int orc_test_fk(const orc_keyline* k1, const orc_keyline* k2, float similarity_threshold);
 float orc_calculate_fj(orc_ctx* c, int f_inx, float* df_dx, float* df_dy, orc_keyline* keyline, float px, float py, int* mnum,
                        float* fi);

@@ -1111,7 +1111,7 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
   if (p->keylines_max < 1 || div_up(p->keylines_max, 256) > kMaxRecBlocks)
     return fail_msg("keylines_max must be in 1..65536 (the LM reduction stages at most 256 record groups of 256 keylines)", -3);
   if (!(p->pixel_uncertainty_match >= 0.0f) || p->search_range + 2.0f * p->pixel_uncertainty_match + 2.0f > 260.0f)
-    return fail_msg("search_range + 2 * pixel_uncertainty_match must stay below 258 (probe sequence buffer)", -3);
+    return fail_msg("search_range + 2 * pixel_uncertainty_match must be at most 258 (probe sequence buffer)", -3);
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail_msg("no HIP device present: the gfx950 backend has no CPU fallback", -4);
@@ -2005,6 +2005,9 @@ int rebvio_hip_directed_match(rebvio_hip_ctx* c, rebvio_hip_map* nm, rebvio_hip_
   // (a probe's slot index 2 * step + side takes 10 bits of a candidate-list entry of k_directed_match_c; rebvio_hip_create bounds
   // search_range the same way)
   if (!(max_radius >= 0.f) || max_radius > 255.f) return fail_msg("directed_match: max_radius outside 0..255", -3);
+  // (a long search walks up to max_radius + 2 * pixel_uncertainty_match steps: the bound of rebvio_hip_create on search_range)
+  if (max_radius + 2.0f * c->P.pixel_uncertainty_match + 2.0f > 260.0f)
+    return fail_msg("directed_match: max_radius + 2 * pixel_uncertainty_match must be at most 258 (probe sequence buffer)", -3);
   HIPCHK(trk_wait_ready(c->s_trk, om));
   HIPCHK(trk_wait_ready(c->s_trk, nm));
   float vel_r[3], Rvel_r[9];

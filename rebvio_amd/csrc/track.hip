@@ -2533,9 +2533,15 @@ __device__ __forceinline__ void directed_match_c_body(KParams p, MapDev nm, MapD
       W.q_gn[jj] = gnq;
       W.best[jj] = kDmcNone;
     }
-    // no search is longer than the radius allows (t_steps <= search_range + pixel_uncertainty_match + 1, bounded at create):
-    // one window with the default radius of 40
-    const int tmax = cvtt_f32(max_radius + p.pixel_uncertainty_match) + 2;
+    // no search is longer than the radius allows: in search_setup dq_rho <= dq_max <= fl(max_radius + pu) and dq_min >= -pu (pu =
+    // pixel_uncertainty_match), so t_steps = cvtt(fl(dq_rho - dq_min)) <= cvtt(fl(fl(max_radius + pu) + pu)) - rounding is
+    // monotonic, so the same two additions give the bound itself and no slack is needed (the other branches are shorter: dq_max -
+    // dq_rho <= dq_max, and the midpoint start probes only inside [dq_min, dq_max]). That is max_radius + 2 pu, not + pu: the
+    // descending chain runs from dq_max down to -pu. Bounded at create and in rebvio_hip_directed_match, so a slot 2 * step + side
+    // stays inside its 10 bits. With the defaults (40, 2) this is 44: the one window [kHeadSteps, kHeadSteps + kDmcWin)
+    // (This holds for keylines of the domain: rho > 0 in front of the camera, p_m3[2] > 0, so dq_rho >= 0. An uploaded map with a
+    // negative rho has dq_max - dq_rho > dq_max: its search is cut at this bound, while k_search_match_one walks all of it.)
+    const int tmax = cvtt_f32((max_radius + p.pixel_uncertainty_match) + p.pixel_uncertainty_match);
     for (int step0 = kHeadSteps; step0 < tmax; step0 += kDmcWin) {
       // the chains continue through this window (tn, tp stand at step0): with two or more lanes per keyline lane 0 walks tn and
       // lane 1 tp (x - 1.0f and x + (-1.0f) are the same IEEE operation), a lone lane walks both
