@@ -103,7 +103,17 @@ void rebvio_hip_default_params(rebvio_hip_params* p, int rows, int cols);
  * cols <= 4096, rows <= 2548 (LDS-staged scan strips); -3 otherwise.
  * Also -3: search_range > 255 or search_range + 2 * pixel_uncertainty_match >= 258 (per-wave probe sequence buffer),
  * quantile_num_bins outside 1..128, keylines_max * 2 * search_range >= 2^23 (distance-field key encoding),
- * keylines_max outside 1..65536 (the LM reduction stages at most 256 record groups of 256 keylines in LDS). */
+ * keylines_max outside 1..65536 (the LM reduction stages at most 256 record groups of 256 keylines in LDS).
+ * Also -3 (rebvio_hip_last_error names the fields), checked with the rest before a device is queried, here and in
+ * rebvio_hip_batch_create: detection parameters whose gradient gate cannot reject a zero gradient. The gate keeps a candidate
+ * unless g2 < (thr * 765 * dog_threshold)^2 (edge_detector.cpp:70,107), and the lowest thr the servo hands it is
+ *   lo = min(min_threshold, max_threshold) with gain > 0 (both clamps apply on every frame),  lo = threshold otherwise.
+ * Required: pos_neg_threshold, dog_threshold, threshold, gain, min_threshold and max_threshold finite; pos_neg_threshold >= 0;
+ * (lo * 765 * dog_threshold)^2 > 0, evaluated in fp32 as the kernels spell it. Why: with a bound of zero a pixel of a flat region
+ * passes every gate with a zero gradient (theta2 / 0 is NaN and fabs(NaN) > 0.5 is false), its keyline gets a NaN position, and
+ * the reference's joinEdges indexes its mask with that position (edge_detector.cpp:125-165: it writes outside the mask; the
+ * same parameters crash the CPU oracle of the tests). min_threshold > max_threshold is legal: the servo's threshold then takes
+ * only these two values (max_threshold whenever it is above it, min_threshold otherwise). */
 int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out);
 void rebvio_hip_destroy(rebvio_hip_ctx* ctx);
 

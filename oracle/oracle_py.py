@@ -101,6 +101,7 @@ def lib(path: str | None = None):
     sig = {
         "orc_default_params": (None, [C.POINTER(Params), C.c_int, C.c_int]),
         "orc_create": (vp, [C.POINTER(Params)]),
+        "orc_last_error": (C.c_char_p, []),
         "orc_destroy": (None, [vp]),
         "orc_set_wide_sums": (None, [vp, C.c_int]),
         "orc_scale_space": (None, [vp, fp, fp, fp, fp, fp]),
@@ -222,6 +223,8 @@ class Oracle:
         self.p = params
         self.rows, self.cols = params.rows, params.cols
         self.h = self.L.orc_create(C.byref(params))
+        if not self.h:
+            raise ValueError(f"oracle: parameters refused: {self.L.orc_last_error().decode()}")
 
     def __del__(self):
         if getattr(self, "h", None):

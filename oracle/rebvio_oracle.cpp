@@ -34,6 +34,7 @@
 #include <deque>
 #include <limits>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -1611,7 +1612,29 @@ void orc_reset_state(orc_ctx* c) {
   orc_ls4_reset(c);
 }
 
+static std::string g_orc_err;
+const char* orc_last_error(void) { return g_orc_err.c_str(); }
+
 orc_ctx* orc_create(const orc_params* p) {
+  // The parameters rebvio_hip_create refuses for the same reason (include/rebvio_hip.h): with a gradient bound of zero,
+  //   gradient_threshold_squared = (thr * 765 * dog_threshold)^2 (build_edge_map), thr >= lo,
+  // a zero gradient passes every gate (theta2 / 0 is NaN, fabs(NaN) > 0.5 is false), the keyline's position is NaN and
+  // join_edges - like the reference's joinEdges, edge_detector.cpp:125-165 - indexes the mask with cvtt(NaN).
+  g_orc_err.clear();
+  const float six[6] = {p->pos_neg_threshold, p->dog_threshold, p->threshold, p->gain, p->min_threshold, p->max_threshold};
+  for (float v : six)
+    if (!std::isfinite(v))
+      g_orc_err = "pos_neg_threshold, dog_threshold, threshold, gain, min_threshold and max_threshold must be finite";
+  if (g_orc_err.empty() && !(p->pos_neg_threshold >= 0.0f)) g_orc_err = "pos_neg_threshold must be >= 0";
+  if (g_orc_err.empty()) {
+    const volatile float lo = p->gain > 0 ? std::min(p->min_threshold, p->max_threshold) : p->threshold;
+    const volatile float g = lo * MAX_IMAGE_VALUE * p->dog_threshold;
+    const volatile float gradient_threshold_squared = g * g;
+    if (!(gradient_threshold_squared > 0.0f))
+      g_orc_err = "(lo * 765 * dog_threshold)^2 must be > 0 in fp32, lo = min(min_threshold, max_threshold) with gain > 0 and "
+                  "threshold otherwise: the gradient gate could not reject a zero gradient";
+  }
+  if (!g_orc_err.empty()) return nullptr;
   orc_ctx* c = new orc_ctx;
   c->p = *p;
   const size_t n = (size_t)p->rows * p->cols;

@@ -83,7 +83,13 @@ typedef struct orc_pair_out {
 } orc_pair_out;
 
 void orc_default_params(orc_params* p, int rows, int cols);
+/* NULL (orc_last_error says why) for detection parameters whose gradient gate cannot reject a zero gradient - the set
+   rebvio_hip_create refuses with -3: a non-finite pos_neg_threshold, dog_threshold, threshold, gain, min_threshold or
+   max_threshold, pos_neg_threshold < 0, or (lo * 765 * dog_threshold)^2 not above zero in fp32, lo = min(min_threshold,
+   max_threshold) with gain > 0 and threshold otherwise. Such a keyline has a NaN position and joinEdges (edge_detector.cpp:125-165)
+   indexes the mask with it. */
 orc_ctx* orc_create(const orc_params* p);
+const char* orc_last_error(void);
 /* DIAGNOSTICS (not the reference) for the keyline sums of tryVel / extRotVel: 1 = accumulated in double, 2 = the fp32 terms added
    in the HIP kernels' order (rebvio_oracle.cpp, struct Acc); default 0 = fp32 in index order, as the reference adds. */
 void orc_set_wide_sums(orc_ctx* c, int on);

@@ -1097,6 +1097,31 @@ int rebvio_hip_set_gyro_state(rebvio_hip_ctx* c, const float Bg[3], const float 
   return 0;
 }
 
+// The detection parameters a context may be created with. The gradient gate of the candidate test is
+//   !(g2 < gradient_threshold_squared),   gradient_threshold_squared = (thr * 765 * dog_threshold)^2 in fp32,
+// and thr never falls below lo = min(min_threshold, max_threshold) with the servo on (gain > 0: both clamps apply on every frame),
+// threshold itself otherwise. A bound of zero lets a zero gradient through (theta2 / 0 is NaN and fabs(NaN) > 0.5 is false), the
+// keyline gets a NaN position, and the reference's joinEdges indexes its mask with it (edge_detector.cpp:125-165) - so such
+// parameters are refused here, before any device is touched. Evaluated as the kernels spell it (detect.hip).
+static int check_detection_params(const rebvio_hip_params* p) {
+  const float six[6] = {p->pos_neg_threshold, p->dog_threshold, p->threshold, p->gain, p->min_threshold, p->max_threshold};
+  for (float v : six)
+    if (!std::isfinite(v))
+      return fail_msg("pos_neg_threshold, dog_threshold, threshold, gain, min_threshold and max_threshold must be finite", -3);
+  if (!(p->pos_neg_threshold >= 0.0f)) return fail_msg("pos_neg_threshold must be >= 0", -3);
+  const volatile float lo = p->gain > 0 ? std::min(p->min_threshold, p->max_threshold) : p->threshold;
+  const volatile float g = lo * kMaxImageValue * p->dog_threshold;
+  const volatile float gradient_threshold_squared = g * g;
+  if (!(gradient_threshold_squared > 0.0f))
+    return fail_msg(p->gain > 0
+                        ? "(min(min_threshold, max_threshold) * 765 * dog_threshold)^2 must be > 0 in fp32 (gain > 0): the gradient "
+                          "gate could not reject a zero gradient"
+                        : "(threshold * 765 * dog_threshold)^2 must be > 0 in fp32 (gain <= 0): the gradient gate could not reject "
+                          "a zero gradient",
+                    -3);
+  return 0;
+}
+
 int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
   *out = nullptr;
   if (p->rows < 32 || p->cols < 32) return fail_msg("rows/cols must be >= 32", -3);
@@ -1112,6 +1137,7 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
     return fail_msg("keylines_max must be in 1..65536 (the LM reduction stages at most 256 record groups of 256 keylines)", -3);
   if (!(p->pixel_uncertainty_match >= 0.0f) || p->search_range + 2.0f * p->pixel_uncertainty_match + 2.0f > 260.0f)
     return fail_msg("search_range + 2 * pixel_uncertainty_match must be at most 258 (probe sequence buffer)", -3);
+  if (int rc = check_detection_params(p)) return rc;
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail_msg("no HIP device present: the gfx950 backend has no CPU fallback", -4);
@@ -3145,6 +3171,7 @@ void rebvio_hip_batch_destroy(rebvio_hip_batch* b) {
 int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_batch** out) {
   *out = nullptr;
   if (lanes < 1 || lanes > kMaxLanes) return fail_msg("batch: lanes must be in 1..16", -3);
+  if (int rc = check_detection_params(p)) return rc;
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail_msg("no HIP device present: the gfx950 backend has no CPU fallback", -4);

@@ -94,6 +94,69 @@ def test_envelope_corners_pass_the_parameter_check(backend):
             assert "error -3:" not in str(e.value), str(e.value)
 
 
+# detection parameters whose gradient gate, !(g2 < (thr * 765 * dog_threshold)^2), cannot reject a zero gradient at the lowest
+# threshold the servo can reach; and non-finite or negative ones. (fields to set, words the error has to name)
+_NAN = float("nan")
+REFUSED_DETECTION_PARAMS = (
+    (dict(threshold=0.0, dog_threshold=0.0, pos_neg_threshold=1.0, gain=0.0), ["threshold", "dog_threshold"]),
+    (dict(dog_threshold=0.0), ["dog_threshold"]),
+    (dict(threshold=0.0, gain=0.0), ["threshold", "dog_threshold"]),
+    (dict(min_threshold=0.0, gain=5e-7), ["min_threshold", "dog_threshold"]),
+    (dict(pos_neg_threshold=_NAN), ["pos_neg_threshold", "finite"]),
+    (dict(dog_threshold=_NAN), ["dog_threshold", "finite"]),
+    (dict(threshold=_NAN), ["threshold", "finite"]),
+    (dict(gain=_NAN), ["gain", "finite"]),
+    (dict(min_threshold=_NAN), ["min_threshold", "finite"]),
+    (dict(max_threshold=_NAN), ["max_threshold", "finite"]),
+    (dict(pos_neg_threshold=-0.1), ["pos_neg_threshold"]),
+)
+
+
+def test_detection_params_whose_gradient_gate_cannot_reject_a_zero_gradient_are_refused(backend):
+    """rebvio_hip_create and rebvio_hip_batch_create return -3, before any device is queried, and the message names the fields.
+    (On a constant frame the first of these makes every interior pixel a keyline with a NaN position - theta2 / 0 - and the
+    reference's joinEdges indexes its mask with it.)"""
+    import ctypes as C
+    L = backend.lib()
+    for kw, words in REFUSED_DETECTION_PARAMS:
+        p = backend.default_params(144, 192, **kw)
+        h = C.c_void_p()
+        for rc in (L.rebvio_hip_create(C.byref(p), C.byref(h)), L.rebvio_hip_batch_create(C.byref(p), 2, C.byref(h))):
+            msg = L.rebvio_hip_last_error().decode()
+            assert rc == -3 and not h.value, (kw, rc, msg)
+            assert all(w in msg for w in words), (kw, msg)
+        with pytest.raises(backend.HipError) as e:
+            backend.Context(p)
+        assert "error -3:" in str(e.value), (kw, str(e.value))
+
+
+def test_legal_detection_corners_pass_the_parameter_check(backend):
+    """Small but non-zero bounds, and min_threshold > max_threshold (the servo's threshold then takes only these two values, both above
+    zero), get past validation: without a device create fails at the device query that follows it, not with -3."""
+    import torch
+    for kw in (dict(dog_threshold=1e-3, threshold=1e-3), dict(min_threshold=0.03, max_threshold=0.02, gain=2e-6)):
+        p = backend.default_params(144, 192, keylines_ref=1500, keylines_max=2000, **kw)
+        if torch.cuda.is_available():
+            backend.Context(p).close()
+            backend.Batch(p, 2).close()
+        else:
+            with pytest.raises(backend.HipError) as e:
+                backend.Context(p)
+            assert "error -3:" not in str(e.value), str(e.value)
+            with pytest.raises(backend.HipError) as e:
+                backend.Batch(p, 2)
+            assert "error -3:" not in str(e.value), str(e.value)
+
+
+def test_oracle_refuses_the_same_detection_params(orc_mod):
+    """The oracle's context creation raises for the same set instead of crashing in join_edges later."""
+    for kw, _ in REFUSED_DETECTION_PARAMS:
+        with pytest.raises(ValueError, match="refused"):
+            orc_mod.Oracle(orc_mod.default_params(144, 192, **kw))
+    for kw in (dict(dog_threshold=1e-3, threshold=1e-3), dict(min_threshold=0.03, max_threshold=0.02, gain=2e-6)):
+        orc_mod.Oracle(orc_mod.default_params(144, 192, **kw))
+
+
 def test_library_installs_no_signal_handlers(backend):
     """Round 1 probed a BAR mapping under a process-wide SIGSEGV/SIGBUS handler; a library inside a ROS node must not touch
     signal dispositions. The shared object does not even import the calls."""
