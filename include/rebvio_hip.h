@@ -24,7 +24,8 @@ extern "C" {
  *    REBVIO_HIP_DM_HEAD values compact8 / compact4 / compact1 (2: map handles outlive their context, -10)
  *    Added since, without a new version (additions only): the point-cloud entries rebvio_hip_default_cloud_filter,
  *    rebvio_hip_map_point_cloud(_async), rebvio_hip_cloud_wait / _release and their three structs; the test hook
- *    rebvio_hip_test_live_resources. */
+ *    rebvio_hip_test_live_resources; the gyro-rotation entries of the streaming and batch drivers rebvio_hip_push_frame_px_gyro(_device),
+ *    rebvio_hip_batch_push_px_gyro_device, the host helper rebvio_hip_gyro_integrate and the test hook rebvio_hip_test_glue_set_next. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -407,6 +408,31 @@ int rebvio_hip_push_frame_px_device(rebvio_hip_ctx* ctx, const void* frame_dev, 
 /* push_frame_px_device with a per-frame detection mask (rows*cols bytes in device memory; see rebvio_hip_set_detection_mask). */
 int rebvio_hip_push_frame_px_masked_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, const uint8_t* mask_dev, uint64_t ts_us,
                                            rebvio_hip_pair_out* out, int* keylines);
+/* The push entries for a camera with an IMU: the reference starts every pair from the gyro - imu.R(), corrected by the bias
+ * estimate, rotates the old keylines ahead of minimizeVel (rebvio.cpp:163-165), and gyroBiasCorrection weighs the visual rotation
+ * against that measurement (rebvio.cpp:186-190). R_gyro: 9 floats, row-major, the gyro rotation pre-integrated over the interval
+ * from the frame pushed before this one to this frame - exactly R_prior of rebvio_hip_track_pair for the pair that ENDS at this
+ * frame (rebvio_hip_gyro_integrate forms it from rate samples). The records equal those of rebvio_hip_track_pair(map_k, map_k+1,
+ * R_gyro(k+1), ...) on the same frames bit for bit, and rebvio_hip_get_gyro_state after a flush likewise. NULL = identity = what
+ * the entries above push; a stream's first frame has no earlier frame and its rotation is ignored. mask_dev: per-frame detection
+ * mask as rebvio_hip_push_frame_px_masked_device takes it, or NULL for none. Frame, format, pitch and mask are checked as by the
+ * *_px entries; a non-finite entry of R_gyro is refused (-3, rebvio_hip_last_error names the argument) before anything is
+ * queued. There is no orthonormality check, as R_prior has none.
+ * Flushes: a pair's last kernel applies the NEXT pair's first rotation, which needs the rotation of the frame behind it. The last
+ * pair in front of a rebvio_hip_flush cannot know it. From the first non-NULL R_gyro on a context is a gyro stream and stays one:
+ * its flush leaves the newest map un-rotated and KEEPS it, and the next frame pushed continues the stream from it (its R_gyro spans
+ * the interval from that map's frame; n frames around any number of flushes yield n - 1 records; rebvio_hip_reset_state ends the
+ * stream). A context that has never been given a rotation flushes as before: the stream ends, its newest map rotated for an
+ * identity measurement. A rotation that is not bit for bit the identity, pushed right after such a flush, has no frame to be
+ * measured from and is refused (-7); NULL or the identity start the new stream. */
+int rebvio_hip_push_frame_px_gyro_device(rebvio_hip_ctx* ctx, const void* frame_dev, int fmt, const uint8_t* mask_dev /*NULL = none*/,
+                                         const float* R_gyro /*NULL = identity*/, uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines);
+int rebvio_hip_push_frame_px_gyro(rebvio_hip_ctx* ctx, const void* frame_host, size_t pitch_bytes, int fmt, const float* R_gyro,
+                                  uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines);
+/* R <- R * exp(gyro_cam * dt_s): one step of IntegratedImu::add (types/imu.hpp:72) with the library's own SO3 exponential, so that a
+ * caller holding raw rate samples (rad/s, already rotated into the camera frame: the reference applies R_c2i there) can form
+ * R_gyro: start from the identity at a frame and call it once per sample up to the next frame. Host only, touches no device. */
+void rebvio_hip_gyro_integrate(float R[9], const float gyro_cam[3], float dt_s);
 int rebvio_hip_next_record(rebvio_hip_ctx* ctx, rebvio_hip_pair_out* out, int* keylines);
 /* Frame pairs the streaming driver has queued on the device so far (a measurement aid: pairs are queued in groups, so a short
  * window of pushes may start a few pairs more or fewer than it pushes frames). */
@@ -444,6 +470,15 @@ int rebvio_hip_batch_push_px_device(rebvio_hip_batch* b, const void* const* fram
  * NULL for none (see rebvio_hip_set_detection_mask; a lane's static mask applies as well). */
 int rebvio_hip_batch_push_px_masked_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, const uint8_t* const* masks_dev,
                                            uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines);
+/* The same with a gyro rotation per lane (rebvio_hip_push_frame_px_gyro_device; rebvio.cpp:163-165 per lane): R_gyro = NULL, or
+ * one pointer per lane with NULL entries for the identity; masks_dev = NULL, or as above. Between two flushes every lane equals a
+ * stand-alone context pushed the same frames and rotations; a lane that is never given one equals a lane of the entries above.
+ * Across a flush the two differ: unlike a context's flush, rebvio_hip_batch_flush ends every lane's stream, rotations or not (the
+ * lanes stay in lock-step). The step pushed next is every lane's first frame, its rotations are ignored, and the pair across
+ * the flush, which a stand-alone context with rotations tracks, does not exist for a lane. */
+int rebvio_hip_batch_push_px_gyro_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, const uint8_t* const* masks_dev /*NULL or NULL entries*/,
+                                         const float* const* R_gyro /*NULL, or one pointer per lane, NULL entries = identity*/,
+                                         uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_batch_next_records(rebvio_hip_batch* b, rebvio_hip_pair_out* out, int* keylines);
 int rebvio_hip_batch_flush(rebvio_hip_batch* b);
 
@@ -457,6 +492,10 @@ int rebvio_hip_test_glue(rebvio_hip_ctx* ctx, const float vel[3], const float Jt
                          const float* xrv, int n_new, float frame_dt, const float Bg[3], const float W_Bg[9], const float R_prior[9],
                          rebvio_hip_pair_out* out_dev, float* state_dev, float* second_dev, rebvio_hip_pair_out* out_host,
                          float* state_host, float* second_host);
+/* Test hook: the gyro rotation of the NEXT pair that later rebvio_hip_test_glue calls of this context hand to both forms (what a
+ * frame pushed with R_gyro gives the glue of the pair in front of it), and whether it is known (has_next = 0: the last pair in
+ * front of a flush on a stream with rotations). R_next = NULL: back to the identity, known. Touches nothing but that hook. */
+int rebvio_hip_test_glue_set_next(rebvio_hip_ctx* ctx, const float* R_next, int has_next);
 
 /* Test hook for the sequence stamps of the host-visible pair records. Every pair the library queues carries a non-zero sequence
  * number; the pair's kernels store it as the LAST word of each record they write into host-visible memory (result slot, glue

@@ -129,6 +129,9 @@ SIGNATURES = {
     "rebvio_hip_push_frame_px": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_push_frame_px_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_push_frame_px_masked_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_push_frame_px_gyro_device": (C.c_int, [_vp, _vp, C.c_int, _vp, _fp, C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_push_frame_px_gyro": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.c_uint64, C.POINTER(PairOut), _ip]),
+    "rebvio_hip_gyro_integrate": (None, [_fp, _fp, C.c_float]),
     "rebvio_hip_next_record": (C.c_int, [_vp, C.POINTER(PairOut), _ip]),
     "rebvio_hip_pairs_started": (C.c_uint64, [_vp]),
     "rebvio_hip_flush": (C.c_int, [_vp]),
@@ -140,10 +143,13 @@ SIGNATURES = {
     "rebvio_hip_batch_push_px_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_batch_push_px_masked_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_uint64, C.POINTER(PairOut),
                                                          _ip]),
+    "rebvio_hip_batch_push_px_gyro_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(_fp), C.c_uint64,
+                                                       C.POINTER(PairOut), _ip]),
     "rebvio_hip_batch_next_records": (C.c_int, [_vp, C.POINTER(PairOut), _ip]),
     "rebvio_hip_batch_flush": (C.c_int, [_vp]),
     "rebvio_hip_test_glue": (C.c_int, [_vp, _fp, _fp, C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.c_float, _fp, _fp, _fp,
                                       C.POINTER(PairOut), _fp, _fp, C.POINTER(PairOut), _fp, _fp]),
+    "rebvio_hip_test_glue_set_next": (C.c_int, [_vp, _fp, C.c_int]),
     "rebvio_hip_test_forge_record_stamp": (C.c_int, [_vp]),
     "rebvio_hip_batch_test_forge_record_stamp": (C.c_int, [_vp]),
     "rebvio_hip_test_live_resources": (C.c_long, []),
@@ -235,6 +241,23 @@ def _chk(rc):
 def _f(a):
     a = np.ascontiguousarray(a, np.float32)
     return a, a.ctypes.data_as(_fp)
+
+
+def _gyro(R):
+    """(keep-alive array, pointer) of a gyro rotation: 9 floats row-major (3x3 or flat), or (None, NULL) for None."""
+    if R is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(R, np.float32).reshape(9))
+    return a, a.ctypes.data_as(_fp)
+
+
+def gyro_integrate(R, gyro, dt) -> np.ndarray:
+    """R * exp(gyro * dt) as float32 [3, 3]: one gyro sample (rad/s, in the camera frame) added to a pre-integrated rotation
+    (rebvio_hip_gyro_integrate; start from np.eye(3) at a frame, the result at the next frame is that frame's R_gyro)."""
+    out = np.array(np.asarray(R, np.float32).reshape(9), np.float32)
+    g, pg = _f(np.asarray(gyro, np.float32).reshape(3))
+    lib().rebvio_hip_gyro_integrate(out.ctypes.data_as(_fp), pg, float(dt))
+    return out.reshape(3, 3)
 
 
 def test_live_resources() -> int:
@@ -693,6 +716,27 @@ class Context:
         _chk(lib().rebvio_hip_push_frame_px_masked_device(self.h, _vp(fa), fmt, _vp(ma), ts_us, C.byref(out), C.byref(n)))
         return out, n.value
 
+    def push_frame_px_gyro_device(self, frame, fmt: int, R_gyro=None, mask=None, ts_us: int = 0):
+        """push_frame_px_device with the gyro rotation over the interval from the previously pushed frame to this one (3x3 or 9
+        floats, row-major; None: identity) and an optional per-frame detection mask; frame / mask: device addresses or torch CUDA
+        tensors. The pair that ends at this frame equals track_pair(..., R_prior=R_gyro)."""
+        fa = self._frame_addr(frame, fmt)
+        ma = None if mask is None else _vp(_mask_addr(mask, self.rows, self.cols, self.p.device_id, "push_frame_px_gyro_device"))
+        _keep, pr = _gyro(R_gyro)
+        out = PairOut()
+        n = C.c_int()
+        _chk(lib().rebvio_hip_push_frame_px_gyro_device(self.h, _vp(fa), fmt, ma, pr, ts_us, C.byref(out), C.byref(n)))
+        return out, n.value
+
+    def push_frame_px_gyro(self, frame: np.ndarray, fmt: int, R_gyro, ts_us: int):
+        """push_frame_px (host frame of pixel format fmt) with a gyro rotation (see push_frame_px_gyro_device)."""
+        ptr, pitch = _px_frame(frame, fmt, self.rows, self.cols)
+        _keep, pr = _gyro(R_gyro)
+        out = PairOut()
+        n = C.c_int()
+        _chk(lib().rebvio_hip_push_frame_px_gyro(self.h, ptr, pitch, fmt, pr, ts_us, C.byref(out), C.byref(n)))
+        return out, n.value
+
     def test_glue(self, vel, JtJ6, F, sigma_rho_min, accept_mask, xrv, n_new, frame_dt, Bg, W_Bg, R_prior):
         """The pair glue on the device and on the host from the same inputs: ((out, state[22], second[44 words]) per side)."""
         vel, pv = _f(vel)
@@ -711,6 +755,11 @@ class Context:
         for i in range(2):
             res.append((outs[i], sts[i], sec[i]))
         return res
+
+    def test_glue_set_next(self, R_next=None, has_next=True):
+        """The next pair's gyro rotation (None: identity) and whether it is known, for the test_glue calls that follow."""
+        _keep, pr = _gyro(R_next)
+        _chk(lib().rebvio_hip_test_glue_set_next(self.h, pr, 1 if has_next else 0))
 
     def pairs_started(self) -> int:
         """Frame pairs the streaming driver has queued on the device so far."""
@@ -787,6 +836,27 @@ class Batch:
             self._frames[l] = self.lanes[l]._frame_addr(frames[l], fmt)
             self._masks[l] = None if masks[l] is None else _mask_addr(masks[l], rows, cols, dev, "batch push_px_masked_device")
         _chk(lib().rebvio_hip_batch_push_px_masked_device(self.h, self._frames, fmt, self._masks, ts_us, self._out, self._n))
+        return self._out, self._n
+
+    def push_px_gyro_device(self, frames, fmt: int, R_gyros, masks=None, ts_us: int = 0):
+        """push_px_device with a gyro rotation per lane (R_gyros: None, or one entry per lane, each 3x3 / 9 floats or None for
+        the identity) and optional per-frame masks (as push_px_masked_device)."""
+        rows, cols, dev = self.p.rows, self.p.cols, self.p.device_id
+        keep = []
+        rot = None
+        if R_gyros is not None:
+            rot = (_fp * self.B)()
+            for l in range(self.B):
+                a, ptr = _gyro(R_gyros[l])
+                keep.append(a)
+                if ptr is not None:
+                    rot[l] = ptr
+        for l in range(self.B):
+            self._frames[l] = self.lanes[l]._frame_addr(frames[l], fmt)
+            if masks is not None:
+                self._masks[l] = None if masks[l] is None else _mask_addr(masks[l], rows, cols, dev, "batch push_px_gyro_device")
+        _chk(lib().rebvio_hip_batch_push_px_gyro_device(self.h, self._frames, fmt, self._masks if masks is not None else None, rot, ts_us,
+                                                        self._out, self._n))
         return self._out, self._n
 
     def flush(self):

@@ -242,6 +242,10 @@ struct rebvio_hip_map {
   // per-pair API: _finish_async was given R_prior_next for this map and the next _begin has not consumed it yet - the keylines are
   // (or will be, in stream order) in the next pair's frame: the point-cloud entries refuse the map (-7)
   std::atomic<bool> promised{false};
+  // streaming / batch drivers: the gyro rotation the frame was pushed with (interval from the frame pushed before it to this one;
+  // rebvio_hip_push_frame_px_gyro*). Not set: the identity.
+  bool gyro_set = false;
+  float gyro_R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   int tab_idx = -1;         // entry of this map in its lane's device map table (batch driver)
   MapDev canon{};           // ... as uploaded there (the live `d` differs from it by the ping-pong swaps only)
 };
@@ -409,6 +413,16 @@ struct rebvio_hip_ctx {
   std::vector<rebvio_hip_map*> frames;  // detected maps not yet consumed as "old"
   PairQueue q;                          // pairs in flight and records waiting for the caller (streaming driver)
   uint64_t pair_seq = 0;
+  // Gyro rotations in the streaming driver (rebvio_hip_push_frame_px_gyro*). gyro_stream: a frame has been pushed with a rotation;
+  // from then on a flush leaves the newest map un-rotated (its successor's rotation is not known) and keeps it in `carry`, and the
+  // next push continues the stream from it. plain_flushed: a stream WITHOUT rotations was flushed, i.e. its newest map was rotated
+  // for an identity measurement and dropped: a rotation pushed next has no frame to refer to (refused, -7).
+  bool gyro_stream = false;
+  bool plain_flushed = false;
+  rebvio_hip_map* carry = nullptr;
+  // rebvio_hip_test_glue_set_next: GlueParams::R_next / has_next of the rebvio_hip_test_glue calls
+  float test_R_next[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  int test_has_next = 1;
   // one frame's detection: its map and servo-state ring slots (detect_prepare), launched by detect_launch
   struct DetJob {
     rebvio_hip_map* m;
@@ -462,6 +476,13 @@ struct rebvio_hip_ctx {
 namespace {
 void release_map(rebvio_hip_map* m, hipEvent_t done_ref = nullptr, bool record_done = true);
 void free_cloud_device(rebvio_hip_cloud* cl);
+// the map a flushed stream with gyro rotations would continue from (rebvio_hip_ctx::carry) goes back to the pool
+inline void drop_carry(rebvio_hip_ctx* c) {
+  if (!c->carry) return;
+  (void)hipSetDevice(c->device);
+  release_map(c->carry, nullptr);
+  c->carry = nullptr;
+}
 
 // A map handle whose context has been destroyed: every entry point that takes a map alone answers with this.
 inline bool map_dead(const rebvio_hip_map* m) { return !m || !m->life || m->life->dead.load(std::memory_order_acquire); }
@@ -576,6 +597,7 @@ rebvio_hip_map* acquire_map(rebvio_hip_ctx* c) {
     m->df_built = false;
     m->raster_order = false;
     m->pre_rotated = false;
+    m->gyro_set = false;
     m->promised.store(false, std::memory_order_relaxed);
     m->n_host = -1;
     m->thr_host = -1.0f;
@@ -1073,6 +1095,8 @@ void rebvio_hip_reset_state(rebvio_hip_ctx* c) {
   // While the streaming driver has pairs in flight the filter state lives on the device: they are completed first (their records
   // stay available through rebvio_hip_next_record), so that no harvested record writes the old state back over the reset one.
   if (c->q.count || !c->frames.empty()) (void)rebvio_hip_flush(c);
+  drop_carry(c);  // a reset ends a stream with gyro rotations too: the next frame pushed is a first frame
+  c->plain_flushed = false;  // ... and whatever it is pushed with is a first frame's rotation: ignored, as on a fresh context
   c->wbg_shadow_valid = false;  // (the next stream's first pair uploads this state and starts the shadow from it)
   c->Bg[0] = c->Bg[1] = c->Bg[2] = 0.f;
   c->RGBias = hm::identity3();
@@ -1334,6 +1358,7 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
   }
   // maps the streaming driver still holds are the library's own, not the caller's
   for (auto* m : c->frames) m->in_use = false;
+  if (c->carry) c->carry->in_use = false;
   life->dead.store(true, std::memory_order_release);
   for (auto* m : c->pool) {
     free_map_device(m);
@@ -2086,7 +2111,17 @@ GlueParams glue_params(const rebvio_hip_ctx* c, float frame_dt) {
   gp.gyro_bias_std_dev = c->P.gyro_bias_std_dev;
   gp.has_pre = 0;
   std::memset(gp.pre, 0, sizeof(gp.pre));
+  gp.has_next = 1;  // no gyro rotation known for the next pair: the identity (glue_params_next)
+  hm::store3(hm::identity3(), gp.R_next);
   return gp;
+}
+// Streaming and batch drivers: what the glue of a pair needs of the pair AFTER it - the gyro rotation `next` was pushed with (the
+// frame behind the pair's new map). next == null: not pushed yet. A stream without rotations goes on with the identity; on one
+// that carries rotations the pair runs without the next rotation (GlueParams::has_next). Returns has_next.
+bool glue_params_next(const rebvio_hip_ctx* c, const rebvio_hip_map* next, GlueParams* gp) {
+  gp->has_next = (next || !c->gyro_stream) ? 1 : 0;
+  if (next && next->gyro_set) std::memcpy(gp->R_next, next->gyro_R, sizeof(gp->R_next));
+  return gp->has_next != 0;
 }
 // Streaming driver: the pair's gyroBiasCorrection matrices from the host's shadow of the device's W_Bg (GlueParams::pre); the
 // shadow advances with every pair queued. Not valid (after rebvio_hip_set_gyro_state, before the first pair of a stream has
@@ -2476,9 +2511,10 @@ int group_size(int queued, int inflight, int lead, int group) {
 }
 
 // First pair of a lane's stream (or after a flush): no second half has applied the prior rotation yet, and the filter state the
-// device glue works on is the host's. It goes up into the state of pair parity gpar; then the old map's first rotateKeylines.
-int start_lane_stream(rebvio_hip_ctx* c, rebvio_hip_map* om, int gpar) {
-  const hm::M3 R = prior_rotation(c, nullptr);
+// device glue works on is the host's. It goes up into the state of pair parity gpar; then the old map's first rotateKeylines,
+// for the gyro rotation the pair's newer frame nm was pushed with (rebvio.cpp:163-165).
+int start_lane_stream(rebvio_hip_ctx* c, rebvio_hip_map* om, const rebvio_hip_map* nm, int gpar) {
+  const hm::M3 R = prior_rotation(c, nm->gyro_set ? nm->gyro_R : nullptr);
   GlueState& gs = c->h_gstate[gpar];
   for (int i = 0; i < 3; ++i) gs.Bg[i] = c->Bg[i];
   hm::store3(c->W_Bg, gs.W_Bg);
@@ -2532,7 +2568,7 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
     const int slot = (int)(c->pair_seq % rebvio_hip_ctx::kSlots);
     const int gpar = (int)(c->pair_seq & 1);
     if (!om->pre_rotated) {
-      const int rc = start_lane_stream(c, om, gpar);
+      const int rc = start_lane_stream(c, om, nm, gpar);
       if (rc) return rc;
       c->wbg_shadow = c->W_Bg;  // what the device's filter state starts from
       c->wbg_shadow_valid = true;
@@ -2550,14 +2586,18 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
     ga.stage = c->glue_stage + slot;
     ga.gp = glue_params(c, frame_dt);
     glue_params_pre(c, &ga.gp);
+    // the glue forms the NEXT pair's prior rotation: the rotation of the frame behind nm (queued already, but for a flush's last pair)
+    const bool has_next = glue_params_next(c, (size_t)g + 2 < c->frames.size() ? c->frames[(size_t)g + 2] : nullptr, &ga.gp);
     int rc = enqueue_pair_lm(c, om, nm, v0, c->slot[slot], c->xrv_part, ga);  // rebvio.cpp:167-177 + the glue of rebvio.cpp:177-233
     if (rc) return rc;
     launch_directed_match_dev(s, c->K, nm->d, om->d, c->glue_dev + slot, c->glue_stage + slot, c->P.search_range, c->dm_head_form);
     const int gate = (int)c->P.global_min_matches_threshold;
     launch_regularize_ekf_dev(s, c->K, nm->d, c->glue_dev + slot, gate > 0 ? gate : 0, c->hist);  // rebvio.cpp:256-259
     std::swap(nm->d.rs, nm->d.rs_tmp);
-    std::swap(nm->d.grad, nm->d.grad_tmp);
-    nm->pre_rotated = true;
+    if (has_next) {  // (else the last kernel has left the new map in its own frame: the next pair starts through start_lane_stream)
+      std::swap(nm->d.grad, nm->d.grad_tmp);
+      nm->pre_rotated = true;
+    }
     HIPCHK(hipGetLastError());
     PairQueue::Step f;
     f.nm[0] = nm;
@@ -2580,7 +2620,7 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
 
 namespace {
 int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame_host, size_t host_pitch, uint64_t ts_us, rebvio_hip_pair_out* out,
-               int* keylines, int fmt = 0, const uint8_t* mask_frame = nullptr) {
+               int* keylines, int fmt = 0, const uint8_t* mask_frame = nullptr, const float* R_gyro = nullptr) {
   // Software pipeline over the three HIP streams of the context:
   //   scan / keyline streams : frame f (this call)
   //   track stream           : see the comment above stream_wait_maps
@@ -2611,6 +2651,16 @@ int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame
   const auto td1 = std::chrono::steady_clock::now();
   c->t_detect_enq += std::chrono::duration<double, std::micro>(td1 - td0).count();
   c->t_frames++;
+  if (R_gyro) {  // (checked by the entry: finite)
+    m->gyro_set = true;
+    std::memcpy(m->gyro_R, R_gyro, sizeof(m->gyro_R));
+    c->gyro_stream = true;
+  }
+  c->plain_flushed = false;
+  if (c->carry) {  // a flushed stream with gyro rotations goes on from its newest map
+    c->frames.push_back(c->carry);
+    c->carry = nullptr;
+  }
   c->frames.push_back(m);
   const int npairs = group_size((int)c->frames.size(), c->q.count, c->lead, c->group);
   if (npairs >= 1) {
@@ -2657,6 +2707,50 @@ int rebvio_hip_push_frame_px_masked_device(rebvio_hip_ctx* c, const void* frame_
   if (rc == 0 && !mask_dev) rc = fail_msg("push_frame_px_masked_device: null mask", -3);
   if (rc) return rc;
   return push_frame(c, static_cast<const uint8_t*>(frame_dev), nullptr, 0, ts_us, out, keylines, fmt, mask_dev);
+}
+
+namespace {
+// Argument check of the *_gyro entries, before anything is queued: every entry of R_gyro finite (-3; no orthonormality check, as
+// R_prior of rebvio_hip_track_pair has none), and a frame to measure the rotation from (-7, see rebvio_hip_ctx::plain_flushed).
+int check_gyro(const rebvio_hip_ctx* c, const char* who, const float* R_gyro) {
+  if (!R_gyro) return 0;
+  char buf[256];
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(R_gyro[i])) {
+      std::snprintf(buf, sizeof(buf), "%s: R_gyro[%d] is not finite", who, i);
+      return fail_msg(buf, -3);
+    }
+  static const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (c->plain_flushed && !c->gyro_stream && std::memcmp(R_gyro, I, sizeof(I)) != 0) {
+    std::snprintf(buf, sizeof(buf), "%s: R_gyro is not the identity, but the stream before the flush carried no rotations: its newest map was "
+                  "rotated for an identity measurement there and the stream ended. Push this frame with R_gyro = NULL (or the identity) "
+                  "as the first frame of a new stream", who);
+    return fail_msg(buf, -7);
+  }
+  return 0;
+}
+}  // namespace
+
+int rebvio_hip_push_frame_px_gyro_device(rebvio_hip_ctx* c, const void* frame_dev, int fmt, const uint8_t* mask_dev, const float* R_gyro,
+                                         uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines) {
+  int rc = check_px(c, "push_frame_px_gyro_device", frame_dev, fmt, false, 0);
+  if (rc == 0) rc = check_gyro(c, "push_frame_px_gyro_device", R_gyro);
+  if (rc) return rc;
+  return push_frame(c, static_cast<const uint8_t*>(frame_dev), nullptr, 0, ts_us, out, keylines, fmt, mask_dev, R_gyro);
+}
+
+int rebvio_hip_push_frame_px_gyro(rebvio_hip_ctx* c, const void* frame_host, size_t pitch_bytes, int fmt, const float* R_gyro, uint64_t ts_us,
+                                  rebvio_hip_pair_out* out, int* keylines) {
+  int rc = check_px(c, "push_frame_px_gyro", frame_host, fmt, true, pitch_bytes);
+  if (rc == 0) rc = check_gyro(c, "push_frame_px_gyro", R_gyro);
+  if (rc) return rc;
+  return push_frame(c, nullptr, static_cast<const uint8_t*>(frame_host), pitch_bytes, ts_us, out, keylines, fmt, nullptr, R_gyro);
+}
+
+void rebvio_hip_gyro_integrate(float R[9], const float gyro_cam[3], float dt_s) {
+  // R = R * SO3::exp(gyro * dt)  (types/imu.hpp:72), with the so3_exp every prior rotation of the library goes through
+  const float w[3] = {gyro_cam[0] * dt_s, gyro_cam[1] * dt_s, gyro_cam[2] * dt_s};
+  hm::store3(hm::mul(hm::load3(R), hm::so3_exp(w)), R);
 }
 
 uint64_t rebvio_hip_pairs_started(rebvio_hip_ctx* c) { return c->pair_seq; }
@@ -2759,6 +2853,14 @@ int rebvio_hip_flush(rebvio_hip_ctx* c) {
   while (rc == 0 && c->frames.size() >= 2)  // the pairs no group was started for yet
     rc = stream_enqueue_group(c, std::min(c->group, (int)c->frames.size() - 1));
   if (rc == 0) rc = drain(c->q, stream_lanes(c));
+  if (c->gyro_stream && rc == 0 && c->frames.size() == 1 && c->frames[0]->in_use && !c->frames[0]->pre_rotated) {
+    // A stream that carries gyro rotations continues across the flush: the rotation of the next frame pushed spans the interval
+    // from this map's frame, and the last pair has left the map un-rotated for it (GlueParams::has_next == 0).
+    c->carry = c->frames[0];
+    c->frames.clear();
+  } else if (!c->frames.empty() && !c->gyro_stream) {
+    c->plain_flushed = true;  // the stream ends here, its newest map rotated for an identity measurement that will not come
+  }
   for (auto* m : c->frames)
     if (m->in_use) release_map(m, nullptr);
   c->frames.clear();
@@ -2798,7 +2900,10 @@ int rebvio_hip_test_glue(rebvio_hip_ctx* c, const float vel[3], const float JtJ6
     GlueDev gl;
     std::memset(&gl, 0, sizeof(gl));
     std::memset(out_host, 0, sizeof(*out_host));
-    hm::pair_glue_core(lm, xrv, n_new, glue_params(c, frame_dt), sh, gl, *out_host);
+    GlueParams gph = glue_params(c, frame_dt);
+    gph.has_next = c->test_has_next;
+    std::memcpy(gph.R_next, c->test_R_next, sizeof(gph.R_next));
+    hm::pair_glue_core(lm, xrv, n_new, gph, sh, gl, *out_host);
     std::memcpy(state_host, &sh, sizeof(sh));
     std::memcpy(second_host, &gl, sizeof(gl));
   }
@@ -2833,6 +2938,8 @@ int rebvio_hip_test_glue(rebvio_hip_ctx* c, const float vel[3], const float JtJ6
   ga.stage = nullptr;
   ga.seq = 1u;
   ga.gp = glue_params(c, frame_dt);
+  ga.gp.has_next = c->test_has_next;
+  std::memcpy(ga.gp.R_next, c->test_R_next, sizeof(ga.gp.R_next));
   launch_pair_glue(c->s_trk, fake, ga);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->s_trk));
@@ -2846,6 +2953,14 @@ int rebvio_hip_test_glue(rebvio_hip_ctx* c, const float vel[3], const float JtJ6
   std::memcpy(state_dev, &sd, sizeof(sd));
   std::memcpy(second_dev, &gd, sizeof(gd));
   if (std::memcmp(&rec.gs, &sd, sizeof(sd)) != 0) return fail_msg("test_glue: the record's state copy differs from the state written", -5);
+  return 0;
+}
+
+int rebvio_hip_test_glue_set_next(rebvio_hip_ctx* c, const float* R_next, int has_next) {
+  if (!c) return -3;
+  static const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  std::memcpy(c->test_R_next, R_next ? R_next : I, sizeof(c->test_R_next));
+  c->test_has_next = R_next ? (has_next != 0) : 1;
   return 0;
 }
 
@@ -3079,13 +3194,18 @@ int batch_enqueue_group(rebvio_hip_batch* b, int nsteps) {
     const int gpar = (int)(b->pair_seq & 1);
     const uint32_t step_seq = next_stamp(&b->stamp_seq);
     LaneDynB dyn{};
+    // every lane's gyro rotation for its NEXT pair: what the step behind nf was pushed with (the identity for a lane pushed without
+    // one, and for the last step in front of a flush: a batch's flush ends every lane's stream, whatever it carried)
+    LaneGyroB gyro;
+    for (int l = 0; l < kMaxLanes; ++l) hm::store3(hm::identity3(), gyro.R_next[l]);
     for (int l = 0; l < b->B; ++l) {
       rebvio_hip_ctx* c = b->lane[l];
       rebvio_hip_map *om = of.m[l], *nm = nf.m[l];
+      if (b->frames.size() > 2 && b->frames[2].m[l]->gyro_set) std::memcpy(gyro.R_next[l], b->frames[2].m[l]->gyro_R, sizeof(gyro.R_next[l]));
       c->df_map = nm;
       dyn.v[l].seq = (b->forge_stamp && l == b->B - 1) ? (step_seq ^ 0x40000000u) : step_seq;
       if (!om->pre_rotated) {
-        const int rc = start_lane_stream(c, om, gpar);
+        const int rc = start_lane_stream(c, om, nm, gpar);
         if (rc) return rc;
       }
       LaneDyn& d = dyn.v[l];
@@ -3113,7 +3233,7 @@ int batch_enqueue_group(rebvio_hip_batch* b, int nsteps) {
     const int users = std::max(1, residency_users(b->device));
     const int per_lane_wgs = (b->K.kmax + 511) / 512;
     const int lanes_now = users <= 1 ? b->lm_lanes_per_launch : std::max(1, std::min(b->lm_lanes_per_launch, b->lm_capacity_wgs / users / per_lane_wgs));
-    launch_lm_chain_b(s, b->K, b->B, lanes_now, b->ls_dev, b->maptab_dev, dyn, calls, spec_now, glue_params(b->lane[0], frame_dt));
+    launch_lm_chain_b(s, b->K, b->B, lanes_now, b->ls_dev, b->maptab_dev, dyn, calls, spec_now, glue_params(b->lane[0], frame_dt), gyro);
     const int gate = (int)b->P.global_min_matches_threshold;
     launch_b_chain_b(s, b->K, b->B, b->ls_dev, b->maptab_dev, dyn, b->P.search_range, gate > 0 ? gate : 0, b->dm_head_form);
     HIPCHK(hipGetLastError());
@@ -3289,9 +3409,10 @@ int rebvio_hip_batch_test_forge_record_stamp(rebvio_hip_batch* b) {
 long rebvio_hip_test_live_resources(void) { return g_live_resources.load(std::memory_order_relaxed); }
 rebvio_hip_ctx* rebvio_hip_batch_lane(rebvio_hip_batch* b, int lane) { return (lane >= 0 && lane < b->B) ? b->lane[lane] : nullptr; }
 
-// masks_dev: this step's per-frame detection mask of every lane (null array, or a null entry: none)
+// masks_dev: this step's per-frame detection mask of every lane (null array, or a null entry: none); R_gyro: the gyro rotation
+// of every lane's frame (null array, or a null entry: the identity)
 static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines,
-                      const uint8_t* const* masks_dev = nullptr) {
+                      const uint8_t* const* masks_dev = nullptr, const float* const* R_gyro = nullptr) {
   HIPCHK(hipSetDevice(b->device));
   if (b->poisoned) return fail_msg("batch: an earlier step failed half way; the lanes are out of lock-step (destroy the batch)", -11);
   const int B = b->B;
@@ -3359,6 +3480,11 @@ static int batch_push(rebvio_hip_batch* b, const void* const* frames_dev, int fm
     // a pooled map comes back with whatever ping-pong state its last pair left: the detector writes the canonical arrays
     m->d = m->canon;
     fr.m[l] = m;
+    if (R_gyro && R_gyro[l]) {  // (checked by the entry: finite)
+      m->gyro_set = true;
+      std::memcpy(m->gyro_R, R_gyro[l], sizeof(m->gyro_R));
+      c->gyro_stream = true;
+    }
     if (l == B - 1) last_reused = m;
     LaneDyn& d = dyn.v[l];
     d.img = frames_dev[l];
@@ -3440,6 +3566,17 @@ int rebvio_hip_batch_push_px_masked_device(rebvio_hip_batch* b, const void* cons
     if (rc) return rc;
   }
   return batch_push(b, frames_dev, fmt, ts_us, out, keylines, masks_dev);
+}
+
+int rebvio_hip_batch_push_px_gyro_device(rebvio_hip_batch* b, const void* const* frames_dev, int fmt, const uint8_t* const* masks_dev,
+                                         const float* const* R_gyro, uint64_t ts_us, rebvio_hip_pair_out* out, int* keylines) {
+  if (!frames_dev) return fail_msg("batch_push_px_gyro_device: null frame array", -3);
+  for (int l = 0; l < b->B; ++l) {
+    int rc = check_px(b->lane[l], "batch_push_px_gyro_device", frames_dev[l], fmt, false, 0);
+    if (rc == 0 && R_gyro) rc = check_gyro(b->lane[l], "batch_push_px_gyro_device", R_gyro[l]);
+    if (rc) return rc;
+  }
+  return batch_push(b, frames_dev, fmt, ts_us, out, keylines, masks_dev, R_gyro);
 }
 
 // Static detection mask of a context (a batch lane's included). The candidate kernels of the frames queued so far read the old

@@ -241,6 +241,13 @@ struct GlueParams {
   // [0] Wg  [1] Wb' = invert(invert(W_Bg) + Rb)  [2] Wg + Wb'  [3] iWgWb  [4] upd  [5] (Wg iWgWb) Wb'
   int has_pre;
   float pre[6][9];
+  // The gyro's rotation over the interval of the NEXT pair (imu.R() of rebvio.cpp:163 as that pair sees it; the identity where no
+  // IMU is heard): the glue forms that pair's prior rotation from it and from the bias it has just corrected (RT_next, and the R
+  // of the filter state it leaves). has_next == 0: the next frame's rotation is not known when this pair is queued (the last pair
+  // in front of a flush, on a stream that carries rotations): the new map stays as it is and the next pair starts like a stream's
+  // first pair. Becomes GlueDev::has_next.
+  int has_next;
+  float R_next[9];
 };
 
 // Device glue of a pair, run by workgroup 0 of the persistent LM kernel behind its last phase (glue_dev.hpp). lm == null: no
@@ -368,6 +375,10 @@ struct LaneMasks {
   const uint8_t* stat[kMaxLanes];   // the lane context's static mask (rebvio_hip_set_detection_mask)
   const uint8_t* frame[kMaxLanes];  // this step's per-frame mask (rebvio_hip_batch_push_px_masked_device)
 };
+// GlueParams::R_next of every lane of a batched LM launch: the one by-value glue parameter that differs between a step's lanes
+struct LaneGyroB {
+  float R_next[kMaxLanes][9];
+};
 __host__ __device__ inline MapDev lane_map(const MapDev* __restrict__ tab, int lane, int idx, unsigned swap) {
   MapDev m = tab[lane * kLaneMaps + idx];
   if (swap & 1u) {
@@ -474,7 +485,7 @@ void launch_keylines_b(hipStream_t s, const KParams& p, int lanes, const LaneSta
                        const LaneMasks* masks = nullptr);
 void launch_df_build_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn);
 void launch_lm_chain_b(hipStream_t s, const KParams& p, int lanes, int lanes_per_launch, const LaneStatic* ls, const MapDev* maptab,
-                       const LaneDynB& dyn, int calls, int spec, const GlueParams& gp);
+                       const LaneDynB& dyn, int calls, int spec, const GlueParams& gp, const LaneGyroB& gyro);
 void launch_b_chain_b(hipStream_t s, const KParams& p, int lanes, const LaneStatic* ls, const MapDev* maptab, const LaneDynB& dyn,
                       float max_radius, int gate, int head_form);
 

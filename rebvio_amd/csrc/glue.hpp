@@ -50,7 +50,7 @@ RH_HD inline void lm_rvel(const LmState& s, float Rvel[9]) {
 }
 
 // The whole glue. `st` is the filter state: read, then replaced by the state after this pair (st.R = the prior rotation of
-// the NEXT pair under "no IMU prior", which is what the streaming drivers use). `gl` is what the second half of the pair
+// the NEXT pair for the gyro rotation gp.R_next, which is what the streaming drivers use). `gl` is what the second half of the pair
 // reads; `out` the record for the caller.
 RH_HD inline void pair_glue_core(const LmState& lm, const float* xrv, int n_new, const GlueParams& gp, GlueState& st, GlueDev& gl,
                                  rebvio_hip_pair_out& out) {
@@ -100,11 +100,12 @@ RH_HD inline void pair_glue_core(const LmState& lm, const float* xrv, int n_new,
   store3(R0, gl.R0a);
   for (int i = 0; i < 3; ++i) gl.V[i] = V[i];
   gl.nan_v = (V[0] != V[0] || V[1] != V[1] || V[2] != V[2]) ? 1 : 0;
-  // the new map becomes the next pair's old map: its first rotation (prior after this pair's bias update) rides along
-  const M3 Rn = prior_rotation(st.Bg, identity3());
+  // the new map becomes the next pair's old map: its first rotation (that pair's gyro measurement, corrected by the bias as this
+  // pair leaves it: rebvio.cpp:163-165 of the next pair) rides along
+  const M3 Rn = prior_rotation(st.Bg, load3(gp.R_next));
   store3(Rn, st.R);
   store3(transpose(Rn), gl.RT_next);
-  gl.has_next = 1;
+  gl.has_next = gp.has_next;
   for (int i = 0; i < 3; ++i) {
     out.Vg[i] = Vg[i];
     out.V[i] = V[i];

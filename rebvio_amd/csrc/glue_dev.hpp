@@ -358,11 +358,11 @@ __device__ __forceinline__ void glue_workgroup(GlueLds& w, const LmState& lm /*L
     for (int i = 0; i < 3; ++i) st.Bg[i] += dg[i];
 #pragma unroll
     for (int i = 0; i < 9; ++i) st.W_Bg[i] = M[3][i];
-    const hm::M3 Rn = hm::prior_rotation(st.Bg, hm::identity3());
+    const hm::M3 Rn = hm::prior_rotation(st.Bg, hm::load3(ga.gp.R_next));
     hm::store3(Rn, st.R);
     st.pad = 0.f;
     hm::store3(hm::transpose(Rn), ga.gd_copy->RT_next);
-    ga.gd_copy->has_next = 1;
+    ga.gd_copy->has_next = ga.gp.has_next;
     *ga.st_out = st;
     if (ga.stage) {
       ga.stage->rec.gs = st;

@@ -1102,7 +1102,8 @@ __device__ __forceinline__ void chain_collect_records(const unsigned long long* 
   __syncthreads();
 }
 
-__device__ __forceinline__ GlueArgs lane_glue_args(const LaneStatic& L, const LaneDyn& d, int calls, const GlueParams& gp) {
+__device__ __forceinline__ GlueArgs lane_glue_args(const LaneStatic& L, const LaneDyn& d, int calls, const GlueParams& gp,
+                                                   const float (&R_next)[9]) {
   GlueArgs ga;
   ga.lm = gptr(L.lm) + calls + 1;
   ga.xrv = gptr(L.xrv_part);
@@ -1118,6 +1119,10 @@ __device__ __forceinline__ GlueArgs lane_glue_args(const LaneStatic& L, const La
   ga.gp.gyro_std_dev = gp.gyro_std_dev;
   ga.gp.gyro_bias_std_dev = gp.gyro_bias_std_dev;
   ga.gp.has_pre = 0;
+  // the lane's own gyro rotation for its next pair (a batch always knows it: its flush ends every lane's stream)
+  ga.gp.has_next = 1;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) ga.gp.R_next[i] = R_next[i];
   return ga;
 }
 
@@ -2058,14 +2063,14 @@ __global__ __launch_bounds__(kChainThreads) void k_lm_chain_spec(KParams p, MapD
 template <int kChainThreads>
 __global__ __launch_bounds__(kChainThreads) void k_lm_chain_spec_b(KParams p, const LaneStatic* __restrict__ ls,
                                                                    const MapDev* __restrict__ maptab, LaneDynB dyn, int calls, int slow_poll,
-                                                                   GlueParams gp, int lane0, int kf) {
+                                                                   GlueParams gp, LaneGyroB gyro, int lane0, int kf) {
   const int lane = lane0 + (int)blockIdx.z;  // a launch carries the lanes that fit the device together (launch_lm_chain_b)
   const LaneStatic& L = ls[lane];
   const LaneDyn d = dyn.v[lane];
   PairSlot* slot = gptr(L.slot[d.slot]);
   lm_chain_spec_body<kChainThreads>(p, global_map(lane_map(maptab, lane, d.om, d.om_swap)), global_map(lane_map(maptab, lane, d.nm, d.nm_swap)), calls,
                                     gptr(L.lm_zero), gptr(L.lm) + calls + 1, gptr(L.lm_xch), d.tag_base, gptr(L.lm_bar_err), gptr(L.hist), 0u, gptr(L.xrv_part), slot, gptr(L.hist),
-                                    nullptr, slow_poll, lane_glue_args(L, d, calls, gp), kf);
+                                    nullptr, slow_poll, lane_glue_args(L, d, calls, gp, gyro.R_next[lane]), kf);
 }
 
 template <int kChainThreads>
@@ -2083,14 +2088,14 @@ __global__ __launch_bounds__(kChainThreads) void k_lm_chain(KParams p, MapDev om
 template <int kChainThreads>
 __global__ __launch_bounds__(kChainThreads) void k_lm_chain_b(KParams p, const LaneStatic* __restrict__ ls,
                                                               const MapDev* __restrict__ maptab, LaneDynB dyn, int calls, int slow_poll,
-                                                              GlueParams gp, int lane0) {
+                                                              GlueParams gp, LaneGyroB gyro, int lane0) {
   const int lane = lane0 + (int)blockIdx.z;  // a launch carries the lanes that fit the device together (launch_lm_chain_b)
   const LaneStatic& L = ls[lane];
   const LaneDyn d = dyn.v[lane];
   PairSlot* slot = gptr(L.slot[d.slot]);
   lm_chain_body<kChainThreads>(p, global_map(lane_map(maptab, lane, d.om, d.om_swap)), global_map(lane_map(maptab, lane, d.nm, d.nm_swap)), calls, 1,
                                gptr(L.lm_zero), gptr(L.lm) + calls + 1, gptr(L.lm_xch), d.tag_base, gptr(L.lm_bar_err), gptr(L.hist), 0u, gptr(L.xrv_part), slot, gptr(L.hist), nullptr,
-                               slow_poll, lane_glue_args(L, d, calls, gp));
+                               slow_poll, lane_glue_args(L, d, calls, gp, gyro.R_next[lane]));
 }
 
 // The device glue behind the per-call kernels (REBVIO_HIP_LM=percall): one workgroup; the extRotVel records are in memory
@@ -3091,7 +3096,7 @@ void launch_regularize_ekf_dev(hipStream_t s, const KParams& p, const MapDev& m,
 }
 
 void launch_lm_chain_b(hipStream_t s, const KParams& p, int lanes, int lanes_per_launch, const LaneStatic* ls, const MapDev* maptab,
-                       const LaneDynB& dyn, int calls, int spec, const GlueParams& gp) {
+                       const LaneDynB& dyn, int calls, int spec, const GlueParams& gp, const LaneGyroB& gyro) {
   // 512-thread workgroups (the single-stream default). The workgroups of a lane wait for each other's records, and HIP promises
   // nothing about the order in which a grid's workgroups become resident (MI355X_MICROARCH.md, contract [G]): a launch carries
   // only as many lanes as fit the device TOGETHER (lm_chain_b_max_lanes: 8 lanes of 16 k keylines at one workgroup per CU), a
@@ -3102,9 +3107,9 @@ void launch_lm_chain_b(hipStream_t s, const KParams& p, int lanes, int lanes_per
   for (int l0 = 0; l0 < lanes; l0 += per) {
     const dim3 grid((p.kmax + 511) / 512, 1, (unsigned)std::min(per, lanes - l0));
     if (use_spec)
-      RH_LAUNCH(k_lm_chain_spec_b<512>, grid, dim3(512), lm_spec_shm(p.kmax, calls), s, p, ls, maptab, dyn, calls, slow_poll, gp, l0, spec);
+      RH_LAUNCH(k_lm_chain_spec_b<512>, grid, dim3(512), lm_spec_shm(p.kmax, calls), s, p, ls, maptab, dyn, calls, slow_poll, gp, gyro, l0, spec);
     else
-      RH_LAUNCH(k_lm_chain_b<512>, grid, dim3(512), 0, s, p, ls, maptab, dyn, calls, slow_poll, gp, l0);
+      RH_LAUNCH(k_lm_chain_b<512>, grid, dim3(512), 0, s, p, ls, maptab, dyn, calls, slow_poll, gp, gyro, l0);
   }
 }
 
