@@ -310,7 +310,11 @@ int rebvio_hip_try_vel(rebvio_hip_ctx* ctx, rebvio_hip_map* m, const float vel[3
  * vel is in/out; Rvel = invert(JtJ); returns score in *F. */
 int rebvio_hip_minimize_vel(rebvio_hip_ctx* ctx, rebvio_hip_map* m, float vel[3], float Rvel[9], float* F,
                             int* accept_mask, float* sigma_rho_min);
-/* EdgeMap::forwardMatch (edge_map.cpp:73-99): old_map->forwardMatch(new_map). */
+/* EdgeMap::forwardMatch (edge_map.cpp:73-99): old_map->forwardMatch(new_map). Depends on nothing but old_map's match_id_forward
+ * and the two maps' keylines as they stand at the call, like the reference's: it may be repeated, follow any number of
+ * rebvio_hip_minimize_vel / rebvio_hip_try_vel calls or an upload of either map, and go into a new_map that already holds matches -
+ * a target that is matched and holds a larger rho than its best writer keeps its fields (edge_map.cpp:83). (Per target the
+ * writer of largest rho wins, the largest index among equals: what the reference's walk in index order comes to.) */
 int rebvio_hip_forward_match(rebvio_hip_ctx* ctx, rebvio_hip_map* old_map, rebvio_hip_map* new_map);
 /* Core::extRotVel (core.cpp:191-261) on the distance field's map. JtJ 6x6 row-major, JtF[6], X[6]. */
 int rebvio_hip_ext_rot_vel(rebvio_hip_ctx* ctx, const float vel[3], float Wx[36], float JtF[6], float X[6], int* ok);
@@ -332,7 +336,14 @@ int rebvio_hip_get_gyro_state(rebvio_hip_ctx* ctx, float Bg[3], float W_Bg[9]);
 int rebvio_hip_set_gyro_state(rebvio_hip_ctx* ctx, const float Bg[3], const float W_Bg[9]);
 /* One frame pair, rebvio.cpp:142-259 (accelerometer/SAB branch excluded): distance field of new_map
  * (if not yet built), rotate, minimizeVel, forwardMatch, extRotVel, gyroBiasCorrection, rotate,
- * directedMatch, regularize1Iter, updateInverseDepth. R_prior = IMU inter-frame rotation or NULL. */
+ * directedMatch, regularize1Iter, updateInverseDepth. R_prior = IMU inter-frame rotation or NULL.
+ * forwardMatch inside a pair (here, in rebvio_hip_track_pair_begin and in the streaming / batch pushes): the winners are
+ * published by the pair's last tryVel evaluation into new_map, and edge_map.cpp:83 holds as in rebvio_hip_forward_match - a
+ * new_map keyline that comes in matched keeps its fields against a writer of smaller rho. What a pair does NOT do is forget the
+ * winners of an earlier pair: new_map must not have been the new map of an earlier pair (or of a rebvio_hip_minimize_vel whose
+ * distance field it was) since it was detected. The drivers always hand over a map fresh from detection; tracking one new map
+ * a second time through the pair entries is not supported - use the stepwise calls, whose rebvio_hip_forward_match starts from
+ * match_id_forward alone. */
 int rebvio_hip_track_pair(rebvio_hip_ctx* ctx, rebvio_hip_map* old_map, rebvio_hip_map* new_map, const float* R_prior,
                           float frame_dt, rebvio_hip_pair_out* out);
 
@@ -340,6 +351,7 @@ int rebvio_hip_track_pair(rebvio_hip_ctx* ctx, rebvio_hip_map* old_map, rebvio_h
  * scale-attitude-bias filter decides the final V, Rgva and the second rotation):
  *   begin  = rebvio.cpp:142-191: distance field, rotate by the gyro prior, minimizeVel, forwardMatch, extRotVel,
  *            gyroBiasCorrection. Returns Vg, P_Vg, Xv, W_Xv, Xgv, W_Xgv (after correction) and R (prior corrected by Bg).
+ *            (new_map: not the new map of an earlier pair, see rebvio_hip_track_pair.)
  *   finish = rebvio.cpp:223/232 + 236-259: rotate the old map by R_second, directedMatch with (V, P_V, Rgva),
  *            regularize1Iter, updateInverseDepth; status 0 / 1 (NaN in V) / 2 (< global_min_matches_threshold). */
 typedef struct rebvio_hip_pair_mid {
@@ -386,7 +398,8 @@ int rebvio_hip_track_pair_hint_next(rebvio_hip_ctx* ctx, rebvio_hip_map* next_ne
  * the tracking of EARLIER pairs on the track stream. A pair runs on the device from end to end: the glue between its halves
  * (6x6 solve, gyroBiasCorrection, SO3, covariance: rebvio.cpp:177-233 without the accelerometer branch) is evaluated in front
  * of the directedMatch kernel from the first half's records, with the gyro-bias state kept in device memory, so the host only
- * queues launches and reads records. `out` receives the oldest COMPLETE pair not handed out yet, in pair order, several calls
+ * queues launches and reads records. (Every pair's new map is fresh from detection here and in the batch pushes, which is what
+ * forwardMatch inside a pair expects: see rebvio_hip_track_pair.) `out` receives the oldest COMPLETE pair not handed out yet, in pair order, several calls
  * behind `frame` (the detect stage leads the tracker by REBVIO_HIP_LEAD frames, default 5; pairs are queued on the track stream
  * in groups of REBVIO_HIP_GROUP, default 4, with one stream wait and one event per group; a pair's match counters arrive with
  * the next pair; up to fifteen pairs are in flight between the device and the host); status -1 while there is none.

@@ -2021,6 +2021,9 @@ int rebvio_hip_forward_match(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_m
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(trk_wait_ready(c->s_trk, om));
   HIPCHK(trk_wait_ready(c->s_trk, nm));
+  // the winners follow from match_id_forward as it stands now (edge_map.cpp:78-81): keys that an earlier minimize_vel or
+  // forward_match into this map has left are not part of it (covers [0, n): n <= keylines_max)
+  HIPCHK(hipMemsetAsync(nm->d.fwd_key, 0, (size_t)c->P.keylines_max * sizeof(unsigned long long), c->s_trk));
   launch_forward_keys(c->s_trk, c->K, om->d, nm->d);
   const float v0[3] = {0, 0, 0};
   launch_ext_rot_vel(c->s_trk, c->K, om->d, nm->d, 1, 0, 0, c->lm, c->lm, c->part, c->xrv_part, v0, nullptr, nullptr);

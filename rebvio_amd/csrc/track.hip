@@ -819,7 +819,9 @@ __device__ __forceinline__ void xrv_apply(const KParams& p, MapDev& nm, int idx,
   float2 rs = k.rs, mpi = k.mpi;
   int mid = k.mid;
   if (do_forward) {
-    if (f.o >= 0) {
+    // edge_map.cpp:83: a target that is already matched and holds a larger rho than the winning writer keeps what it has (a
+    // map fresh from detection has match_id = -1 everywhere)
+    if (f.o >= 0 && !(k.mid >= 0 && k.rs.x > f.rs.x)) {
       const int o = f.o;
       rs = f.rs;
       mpi = f.mpi;
@@ -882,7 +884,8 @@ __device__ __forceinline__ void xrv_record_stamp(float* rec, int k, unsigned seq
 
 // ---- EdgeMap::forwardMatch gather (edge_map.cpp:78-96) + Core::extRotVel sums (core.cpp:198-245) -------------
 // Sequential rule "overwrite unless the target already holds a larger rho" == the writer with the largest
-// rho wins, ties -> largest index: exactly the atomicMax key. One thread per keyline of the NEW map.
+// rho wins, ties -> largest index: exactly the atomicMax key; a target that came in matched is one more contender, which
+// keeps its fields unless that writer's rho reaches its own (xrv_apply). One thread per keyline of the NEW map.
 // Per-thread outer product of the 6-vector row (Phi is never materialised): 21 + 6 sums + match count.
 __global__ __launch_bounds__(256) void k_ext_rot_vel(KParams p, MapDev om, MapDev nm, int do_forward, int do_lm_final,
                                                      int calls, const LmState* __restrict__ st_in,

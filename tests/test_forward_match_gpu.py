@@ -1,0 +1,243 @@
+"""GPU parity of forwardMatch where natural frames never take it: many writers per target, ties, targets that are already matched,
+the step repeated on the same maps, minimizeVel from non-zero start velocities.
+
+The reference walks the old map in index order (edge_map.cpp:73-99); the library publishes one 64-bit key per writer,
+order_key(rho) << 32 | old index, with atomicMax into the new map's fwd_key[] - from k_forward_keys for the stepwise entry, from the
+last tryVel evaluation of every LM kernel form for a pair - and xrv_apply hands the largest key's keyline over. On the 192x144
+stream a target has at most 3 writers and no tie (tests/test_forward_match.py), so the arbitration across waves and workgroups, the
+tie rule, edge_map.cpp:83 and a second run into the same map are launched here on purpose, on the crafted maps of
+tests/test_forward_match.py, which also holds the oracle's forward_match to a closed form first.
+
+Every comparison is bit for bit against the oracle with its keyline sums in the kernels' order; no tolerance anywhere. A case that
+claims to reach something asserts that on the oracle's result alone, before the library is looked at.
+
+Two rules were missing in the library and sections b and c fail without them (counts in the docstrings): rebvio_hip_forward_match
+kept the keys of earlier runs into the same new map, and xrv_apply overwrote a matched target whatever its rho.
+"""
+import numpy as np
+import pytest
+
+from test_forward_match import (DONOR, LAYOUTS, PATTERNS, RERUN_VELS, START_VELS, assert_bits_equal, assert_donor_pair, behind_the_camera,
+                                craft_donor_copies, craft_writers, drop_every_second_writer, forward_match_closed_form,
+                                kept_and_overwritten, preset_targets, targets_of, writers_by_target)
+from test_keyline_counts_gpu import FORMS, set_forms
+from test_parity_gpu import Pair, _bits_equal, _record_words, assert_keylines_equal, warm
+from test_track_params_gpu import KW, matching_stage, set_new_map
+
+pytestmark = pytest.mark.gpu
+
+FORM_IDS = ["-".join(str(v) for v in f if v is not None) or "default" for f in FORMS]
+
+
+@pytest.fixture(scope="module")
+def B():
+    import torch  # noqa: F401  (as in test_parity_gpu: torch's HIP runtime first)
+    from rebvio_amd import backend
+    backend.lib()
+    return backend
+
+
+def fresh_stage(O, B, stream):
+    """warm(…, 3), the oracle's sums in the kernels' order from here on, the distance field of the newest map on both sides: the
+    old map carries depth state, the newest one is fresh from detection on both sides and has never been a pair's new map."""
+    frames, cam = stream
+    P = warm(O, B, frames, cam, 3, **KW)
+    P.orc.set_sum_order("device")
+    P.orc.build_distance_field(P.om[1])
+    P.ctx.build_distance_field(P.gm[1])
+    return P
+
+
+def set_old_map(P, kl):
+    """the same crafted array into the older map of both sides; every forward match inside the newest map"""
+    assert len(kl) == P.om[0].size()
+    assert (kl["match_id_forward"] >= -1).all() and (kl["match_id_forward"] < P.om[1].size()).all()
+    P.om[0].set_keylines(kl)
+    P.gm[0].upload(kl)
+
+
+def assert_forward_match_equal(P, what):
+    """forward_match on both sides: every field of the newest map"""
+    P.orc.forward_match(P.om[0], P.om[1])
+    P.ctx.forward_match(P.gm[0], P.gm[1])
+    ko = P.om[1].keylines()
+    assert_keylines_equal(ko, P.gm[1].keylines(), what=what)
+    return ko
+
+
+def assert_ext_rot_vel_equal(P, vel, what):
+    eo, eg = P.orc.ext_rot_vel(vel), P.ctx.ext_rot_vel(vel)
+    assert np.abs(eo["Wx"]).max() > 0
+    assert _bits_equal(np.float32(eo["Wx"]), np.float32(eg["Wx"])), (what, np.abs(eo["Wx"] - eg["Wx"]).max())
+    assert _bits_equal(np.float32(eo["JtF"]), np.float32(eg["JtF"])), (what, eo["JtF"], eg["JtF"])
+
+
+# ---- a. many writers, stepwise ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_many_writers_per_target(orc_mod, B, small_stream, layout, pattern):
+    """k_forward_keys and the gather on groups of 1, 2, 3, 63, 64, 65, 256, 257 and 600 writers per target (and 120 groups of 1 - 3,
+    old index 0 and n - 1 as sole writers, targets 0 and n_new - 1), contiguous and six apart - the last three sizes from several
+    256-thread workgroups; 600 writers six apart do not fit a 2 027-keyline map, the large groups go on in a second residue class -
+    with distinct rhos, all rhos equal, the maximum shared by two writers in different workgroups, writers at kRhoMin and kRhoMax.
+    Every field of the newest map, then extRotVel's sums at the pair's velocity."""
+    P = fresh_stage(orc_mod, B, small_stream)
+    ro = P.orc.minimize_vel(P.om[0])
+    new = P.om[1].keylines()
+    assert (new["match_id"] == -1).all()
+    old, groups = craft_writers(P.om[0].keylines(), len(new), layout, pattern)   # (asserts the layout on the crafted array)
+    set_old_map(P, old)
+    want, _ = forward_match_closed_form(old, new)
+    ko = assert_forward_match_equal(P, f"forwardMatch, {layout}, {pattern}")
+    assert_bits_equal(ko, want, "the oracle against the closed form")
+    assert int((ko["match_id"] >= 0).sum()) == len(groups) == 131
+    assert_ext_rot_vel_equal(P, ro["vel"], f"{layout}, {pattern}")
+
+
+# ---- b. already-matched targets -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_already_matched_targets_keep_a_larger_rho(orc_mod, B, small_stream, layout, pattern):
+    """edge_map.cpp:83 on section a's groups: the newest map holds the pair's natural forward matches, and every crafted target is
+    pre-set matched with its rho above, equal to, one ulp above, one ulp below and well below the winning writer's. On the oracle
+    53 targets keep every bit and 78 are overwritten (33 / 98 with the writers at the clamps); at least 20 each are asked for.
+    Before xrv_apply applied the rule the library overwrote every target that has a writer, so each of the eight cases differed
+    from the oracle at its 53 (33) kept targets."""
+    P, ro = matching_stage(orc_mod, B, small_stream)
+    P.orc.set_sum_order("device")
+    old, groups = craft_writers(P.om[0].keylines(), P.om[1].size(), layout, pattern)
+    new, kinds = preset_targets(P.om[1].keylines(), old, groups)
+    assert int((new["match_id"] >= 0).sum()) > 1000
+    set_old_map(P, old)
+    set_new_map(P, new)
+    want, _ = forward_match_closed_form(old, new)
+    P.orc.forward_match(P.om[0], P.om[1])
+    ko = P.om[1].keylines()
+    assert_bits_equal(ko, want, "the oracle against the closed form")
+    kept, over = kept_and_overwritten(new, ko, groups)
+    print(f"{layout}, {pattern}: {kept} targets kept, {over} overwritten")
+    assert kept >= 20 and over >= 20, (kept, over)
+    P.ctx.forward_match(P.gm[0], P.gm[1])
+    assert_keylines_equal(ko, P.gm[1].keylines(), what=f"forwardMatch into matched targets, {layout}, {pattern}")
+    assert_ext_rot_vel_equal(P, ro["vel"], f"{layout}, {pattern}")
+
+
+# ---- c. repeats on the same map handles -----------------------------------------------------------------------------------
+def test_forward_match_twice(orc_mod, B, small_stream):
+    """The step twice in a row: the second run finds every target matched with exactly its winner's rho and writes the same again.
+    (This one also held before the two fixes: the same keys, the same winners.)"""
+    P = fresh_stage(orc_mod, B, small_stream)
+    P.orc.minimize_vel(P.om[0])
+    P.sync_gpu_from_oracle()
+    first = assert_forward_match_equal(P, "first forwardMatch")
+    assert int((first["match_id"] >= 0).sum()) > 1000
+    second = assert_forward_match_equal(P, "second forwardMatch")
+    assert_bits_equal(first, second, "the oracle's second run")
+
+
+@pytest.mark.parametrize("which", ["natural", "crafted_equal_rho"])
+def test_forward_match_again_after_writers_dropped(orc_mod, B, small_stream, which):
+    """forward_match, then the old map uploaded with every second writer's match_id_forward dropped, then forward_match again, on
+    the same handles. natural: the pair's own matches - a target whose winner was dropped keeps its fields by edge_map.cpp:83,
+    which is also what a stale key rewrites, so this case held before the fixes. crafted_equal_rho: section a's contiguous groups
+    with all rhos equal - where the largest index is dropped the remaining largest index has to take the target over (63 of the
+    131 targets); the first run's keys, equal in rho and larger in index, used to keep the dropped writer in every one of them."""
+    P = fresh_stage(orc_mod, B, small_stream)
+    P.orc.minimize_vel(P.om[0])
+    old = P.om[0].keylines()
+    if which == "crafted_equal_rho":
+        old, _ = craft_writers(old, P.om[1].size(), "contiguous", "equal")
+    set_old_map(P, old)
+    first = assert_forward_match_equal(P, "first forwardMatch")
+    dropped = drop_every_second_writer(old)
+    set_old_map(P, dropped)
+    before, after = writers_by_target(old), writers_by_target(dropped)
+    lost_winner = sum(first["match_id"][t] not in after.get(t, ()) for t in before)
+    want, _ = forward_match_closed_form(dropped, first)
+    second = assert_forward_match_equal(P, f"forwardMatch after the drop, {which}")
+    assert_bits_equal(second, want, "the oracle against the closed form")
+    taken_over = int((second["match_id"] != first["match_id"]).sum())
+    print(f"{which}: {len(before)} targets, {lost_winner} lost their winner, {taken_over} taken over by another writer")
+    assert lost_winner >= 50
+    if which == "crafted_equal_rho":
+        assert taken_over >= 20
+
+
+@pytest.mark.parametrize("vel0", RERUN_VELS, ids=lambda v: ",".join(f"{x:g}" for x in v))
+def test_forward_match_after_a_second_minimize_vel(orc_mod, B, small_stream, vel0):
+    """minimize_vel from 0, then from another start velocity, then forward_match: the reference's forwardMatch reads
+    match_id_forward as the last run left it. On the oracle 93 (from (0, 0, -0.06)) and 1161 (from (0.2, 0.1, 0)) of the first
+    run's 1430 targets are untargeted after the second; at least 50 are asked for. The LM kernel of the first run has left its
+    keys in the new map, and before rebvio_hip_forward_match cleared them every one of those targets was handed a match, and a
+    target of both runs the first run's writer wherever its key was the larger."""
+    P = fresh_stage(orc_mod, B, small_stream)
+    for k, v in enumerate(((0.0, 0.0, 0.0), vel0)):
+        ro, rg = P.orc.minimize_vel(P.om[0], v), P.ctx.minimize_vel(P.gm[0], v)
+        assert ro["accept_mask"] == rg["accept_mask"]
+        for f in ("vel", "F", "Rvel", "sigma_rho_min"):
+            assert _bits_equal(np.float32(ro[f]), np.float32(rg[f])), (v, f, ro[f], rg[f])
+        kl = P.om[0].keylines()
+        assert np.array_equal(kl["match_id_forward"], P.gm[0].keylines()["match_id_forward"])
+        if k == 0:
+            first = targets_of(kl)
+    gone = len(first - targets_of(kl))
+    print(f"second minimizeVel from {vel0}: {gone} of {len(first)} targets untargeted")
+    assert gone >= 50, gone
+    ko = assert_forward_match_equal(P, f"forwardMatch after minimizeVel from 0 and from {vel0}")
+    assert int((ko["match_id"] >= 0).sum()) == len(targets_of(kl))
+    assert_ext_rot_vel_equal(P, ro["vel"], str(vel0))
+
+
+# ---- d. minimize_vel from non-zero starts ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+@pytest.mark.parametrize("start", START_VELS, ids=lambda s: ",".join(f"{x:g}" for x in s[0]))
+def test_minimize_vel_from_a_start_velocity(orc_mod, B, small_stream, monkeypatch, start, form):
+    """The LM run from (0.05, 0, 0), (0, 0, -0.06), (0.2, 0.1, 0) and (0, 0, -0.9) in every LM kernel form: velocity, score,
+    covariance, sigma quantile, accept mask and every forward match. The oracle's masks are 00001, 00001, 01111 and 01111; the
+    last start sends 733 evaluated keylines through z_p <= 0 (core.cpp:98) in the first evaluation, the others none."""
+    vel0, mask = start
+    set_forms(monkeypatch, *form)
+    P = fresh_stage(orc_mod, B, small_stream)
+    ro = P.orc.minimize_vel(P.om[0], vel0)
+    kl = P.om[0].keylines()
+    assert f"{ro['accept_mask']:05b}" == mask, ro["accept_mask"]
+    behind = behind_the_camera(kl, P.om[0].threshold, ro["sigma_rho_min"], vel0[2])
+    assert behind >= 20 if vel0[2] == -0.9 else behind == 0, behind
+    rg = P.ctx.minimize_vel(P.gm[0], vel0)
+    assert ro["accept_mask"] == rg["accept_mask"], (ro["accept_mask"], rg["accept_mask"])
+    for f in ("vel", "F", "Rvel", "sigma_rho_min"):
+        assert _bits_equal(np.float32(ro[f]), np.float32(rg[f])), (f, ro[f], rg[f])
+    assert np.array_equal(kl["match_id_forward"], P.gm[0].keylines()["match_id_forward"])
+
+
+# ---- e. many writers through a whole pair ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+@pytest.mark.parametrize("varied", [False, True], ids=["equal_rho", "varied_rho"])
+def test_many_writers_through_a_whole_pair(orc_mod, B, small_stream, monkeypatch, varied, form):
+    """The keys published from the last tryVel evaluation of the LM kernels: 300 old keylines (3, 9, 15, …) made copies of keyline
+    936, so that through track_pair all 301 forward to target 950, from 8 record groups. On the oracle the pair ends with status 0
+    and 1847 matches; with equal rho the winner is index 1797, with rho * (1 + (k % 37 - 18) * 2^-14) the maximum is shared and
+    1773 wins. Every word of the pair record, the old map's match_id_forward and every field of the newest map, in every LM and
+    directedMatch form."""
+    set_forms(monkeypatch, *form)
+    frames, cam = small_stream
+    P = Pair(orc_mod, B, frames, cam, **KW)
+    P.orc.set_sum_order("device")
+    P.detect(0)
+    for i in (1, 2, 3, 4):   # (both sides track: the gyro-bias filter carries state from pair to pair)
+        P.detect(i)
+        if i < 4:
+            P.orc.track_pair(P.om[0], P.om[1])
+            P.ctx.track_pair(P.gm[0], P.gm[1])
+    old, idx = craft_donor_copies(P.om[0].keylines(), DONOR, varied)
+    P.om[0].set_keylines(old)
+    P.sync_gpu_from_oracle()
+    po = P.orc.track_pair(P.om[0], P.om[1])
+    old_after = P.om[0].keylines()
+    t, m = assert_donor_pair(po, old_after, idx, varied)
+    assert set(idx.tolist()) <= set(m.tolist())
+    pg = P.ctx.track_pair(P.gm[0], P.gm[1])
+    wo, wg = _record_words(po), _record_words(pg)
+    assert np.array_equal(wo, wg), (np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
+    assert np.array_equal(old_after["match_id_forward"], P.gm[0].keylines()["match_id_forward"])
+    assert_keylines_equal(P.om[1].keylines(), P.gm[1].keylines(), what="newest map after the pair")
