@@ -58,6 +58,12 @@ class EdgeMap {
   // exactly which keylines and where; the synchronous form: it waits for everything queued that concerns this map)
   std::vector<rebvio::types::CloudPoint> pointCloud(const rebvio::types::CloudFilter& filter = rebvio::types::CloudFilter(),
                                                     const rebvio::types::CloudPose& pose = rebvio::types::CloudPose());
+  // addition: keyframes (rebvio_hip.h "Keyframes"). markKeyframe makes this map the keyframe: match_id_keyframe[i] = i for every
+  // keyline, queued on the track stream - call it after the map has been a pair's new map and before it serves as an old map.
+  // keyframeMatches(kf_size): which keylines of a keyframe of kf_size keylines live on in this map, in ascending kf_keyline
+  // (synchronous, from the tracking thread, like pointCloud).
+  void markKeyframe();
+  std::vector<rebvio::types::KfMatch> keyframeMatches(int kf_size);
 
   // --- backend plumbing (not part of the reference surface) ---
   // `keepalive` owns the backend context the handle belongs to (backend::Session): a map kept by an edge-image consumer

@@ -49,6 +49,15 @@ class Rebvio {
   // (one launch more per pair); the odometry does not change by a digit. Register before the first frame is handed in.
   void registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb,
                                   rebvio::types::CloudFilter filter = rebvio::types::CloudFilter());
+  // addition: keyframes (rebvio_hip.h "Keyframes"). requestKeyframe: the newest tracked map becomes the keyframe - it is marked
+  // (EdgeMap::markKeyframe) behind the second half of the pair being tracked when the request is seen, in front of the next pair's
+  // first half; callable from any thread. The keyframe callback is called once per published odometry record, right after the
+  // odometry callbacks, on the state-estimation thread: the record's stamp, kf_matches of its pair (keylines of the new map that
+  // continue a keyline of the keyframe; 0 until a keyframe was requested) and the new map's keyline count - kf_matches / keylines
+  // is the usual signal for requesting the next keyframe. With neither used the launches and the odometry are what they are
+  // without them.
+  void requestKeyframe() { keyframe_requested_ = true; }
+  void registerKeyframeCallback(std::function<void(uint64_t ts_us, int kf_matches, int keylines)> cb);
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -86,6 +95,8 @@ class Rebvio {
     rebvio::types::CloudFilter filter;
   };
   std::vector<PointCloudCallback> point_cloud_callbacks_;
+  std::vector<std::function<void(uint64_t, int, int)>> keyframe_callbacks_;
+  std::atomic<bool> keyframe_requested_{false};
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };
 

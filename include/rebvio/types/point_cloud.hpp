@@ -34,6 +34,18 @@ struct CloudPose {
   float scale{1.0f};
 };
 
+// One keyframe-to-current correspondence (EdgeMap::keyframeMatches; layout-compatible with the C-ABI's rebvio_hip_kf_match, which
+// defines claimants and winner exactly): keyline `kf_keyline` of the keyframe map lives on in this map as keyline `keyline`.
+struct KfMatch {
+  int kf_keyline;        // index in the keyframe map; strictly increasing within a result
+  int keyline;           // index in this map of the winning claimant (smallest sigma_rho, smallest index among equals)
+  int claimants;         // keylines of this map whose match_id_keyframe is kf_keyline
+  unsigned int matches;  // winner's KeyLine::matches
+  float rho, sigma_rho;  // winner's
+  float pos_img[2];      // winner's
+};
+static_assert(sizeof(KfMatch) == 32, "KfMatch must stay layout-compatible with rebvio_hip_kf_match");
+
 // What a point-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
   uint64_t ts_us;            // the odometry record's stamp (= the map's)

@@ -25,7 +25,9 @@ extern "C" {
  *    Added since, without a new version (additions only): the point-cloud entries rebvio_hip_default_cloud_filter,
  *    rebvio_hip_map_point_cloud(_async), rebvio_hip_cloud_wait / _release and their three structs; the test hook
  *    rebvio_hip_test_live_resources; the gyro-rotation entries of the streaming and batch drivers rebvio_hip_push_frame_px_gyro(_device),
- *    rebvio_hip_batch_push_px_gyro_device, the host helper rebvio_hip_gyro_integrate and the test hook rebvio_hip_test_glue_set_next. */
+ *    rebvio_hip_batch_push_px_gyro_device, the host helper rebvio_hip_gyro_integrate and the test hook rebvio_hip_test_glue_set_next;
+ *    the keyframe entries rebvio_hip_map_mark_keyframe, rebvio_hip_keyframe_next, rebvio_hip_map_keyframe_matches and their struct
+ *    rebvio_hip_kf_match. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -268,6 +270,42 @@ int rebvio_hip_map_point_cloud_async(rebvio_hip_ctx* ctx, rebvio_hip_map* map, c
 int rebvio_hip_cloud_wait(rebvio_hip_cloud* cloud, const rebvio_hip_cloud_point** points, int* count, const void** device_points);
 void rebvio_hip_cloud_release(rebvio_hip_cloud* cloud);
 
+/* Keyframes. Every keyline carries match_id_keyframe, "ID of the matching keyline in the last keyframe" (types/keyline.hpp:39):
+ * forwardMatch and directedMatch copy it from the matched keyline of the old map (edge_map.cpp:93,210) and directedMatch counts the
+ * keylines that still hold one into kf_matches (edge_map.cpp:212). Detection writes -1 and the reference never sets anything else,
+ * so kf_matches is 0 until a map is MARKED: match_id_keyframe[i] = i for every keyline i of the map - the map becomes the keyframe,
+ * and from then on the field tells, in every later map of the stream, which keyline of the keyframe a keyline continues, and
+ * kf_matches / keylines how much of the keyframe is still alive (the usual signal for choosing the next one).
+ * Mark a map AFTER it has been a pair's new map and BEFORE it serves as an old map: being tracked as a new map overwrites the ids of
+ * its matched keylines with those of the previous keyframe (that is the field's meaning in the reference).
+ * rebvio_hip_map_mark_keyframe queues one kernel on the TRACK stream in call order and returns at once; it waits for nothing on the
+ * host. Nothing else of the map changes. A track-side entry like rebvio_hip_map_point_cloud_async: allowed between stepwise calls,
+ * between rebvio_hip_track_pair calls and between _finish_async(k) and _begin(k+1). The ids do not depend on the keylines' frame, so
+ * a map promised to R_prior_next is marked like any other (no -7). The map counts as used by the tracker afterwards (see
+ * rebvio_hip_map_download). -3: null context or map, a map of another context; -10: the context has been destroyed - all checked
+ * before the device is touched. */
+int rebvio_hip_map_mark_keyframe(rebvio_hip_ctx* ctx, rebvio_hip_map* map);
+/* Keyframe-to-current correspondences of a map. A keyline i of the map is a claimant of keyframe slot j when
+ * 0 <= match_id_keyframe[i] == j < kf_size (ids of -1 or >= kf_size are ignored; kf_size = the keyframe map's size). Per slot with at
+ * least one claimant one record, in ascending kf_keyline: the number of claimants and the winner - the claimant of smallest key
+ * (sk << 32) | i with sk = the bits of sigma_rho + 0.0f when sigma_rho >= 0, 0xFFFFFFFF otherwise (NaN, negative): the smallest
+ * sigma_rho wins, the smallest index among equals. *count = such slots; min(count, cap) records are written (a cap below count is no
+ * error). Bit-reproducible: the only atomics are a 64-bit minimum and an integer add per slot, both independent of order.
+ * Synchronous and track-side, exactly as rebvio_hip_map_point_cloud: the map's keylines as they are when the kernels run in stream
+ * order, called from the tracking thread, and the map counts as used by the tracker afterwards. kf_size 0: count 0, nothing is
+ * launched. -3, before the device is touched: null map or count, negative cap, null out_host with cap > 0, kf_size outside
+ * 0..keylines_max; -10: the context has been destroyed; -7: the map is promised to R_prior_next (the record carries pos_img; see
+ * "State" of the point-cloud entries). */
+typedef struct rebvio_hip_kf_match { /* 32 bytes */
+  int kf_keyline;       /* index in the keyframe map */
+  int keyline;          /* index in THIS map of the winning claimant */
+  int claimants;        /* keylines of this map with match_id_keyframe == kf_keyline */
+  unsigned int matches; /* winner's KeyLine::matches */
+  float rho, sigma_rho; /* winner's, as stored */
+  float pos_img[2];     /* winner's, as stored */
+} rebvio_hip_kf_match;
+int rebvio_hip_map_keyframe_matches(rebvio_hip_map* map, int kf_size, rebvio_hip_kf_match* out_host, int cap, int* count);
+
 /* Test hook: overwrite the device keylines (count must equal the map size). */
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n);
 /* Map handles may outlive their context: after rebvio_hip_destroy the entries that take a map alone (size, threshold, download,
@@ -446,6 +484,14 @@ int rebvio_hip_push_frame_px_gyro(rebvio_hip_ctx* ctx, const void* frame_host, s
  * caller holding raw rate samples (rad/s, already rotated into the camera frame: the reference applies R_c2i there) can form
  * R_gyro: start from the identity at a frame and call it once per sample up to the next frame. Host only, touches no device. */
 void rebvio_hip_gyro_integrate(float R[9], const float gyro_cam[3], float dt_s);
+/* Keyframes in the streaming driver: the next frame pushed, through any push entry, becomes a keyframe (see
+ * rebvio_hip_map_mark_keyframe): its map is marked behind the pair that ends at it and in front of the pair that starts from it (a
+ * stream's first frame: in front of its first pair; the map a gyro stream carries across a flush keeps the request). On the same
+ * frames the records equal those of the per-pair run track_pair(j-1, j); map_mark_keyframe(j); track_pair(j, j+1) in every word. A
+ * frame that is dropped untracked (the newest frame of a stream without rotations at its flush) takes its request with it;
+ * rebvio_hip_reset_state drops a pending one. A stream that never calls this launches exactly what it launched before. -3: a null
+ * context, or a lane of a batch (keyframes inside lock-step steps are not supported). */
+int rebvio_hip_keyframe_next(rebvio_hip_ctx* ctx);
 int rebvio_hip_next_record(rebvio_hip_ctx* ctx, rebvio_hip_pair_out* out, int* keylines);
 /* Frame pairs the streaming driver has queued on the device so far (a measurement aid: pairs are queued in groups, so a short
  * window of pushes may start a few pairs more or fewer than it pushes frames). */

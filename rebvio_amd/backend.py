@@ -27,6 +27,11 @@ CLOUD_POINT_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("rho", "<f4"), ("sigma_rho"
                               ("keyline", "<i4"), ("matches", "<u4")])
 assert CLOUD_POINT_DTYPE.itemsize == 32
 
+# rebvio_hip_kf_match: one keyframe-to-current correspondence (Map.keyframe_matches)
+KF_MATCH_DTYPE = np.dtype([("kf_keyline", "<i4"), ("keyline", "<i4"), ("claimants", "<i4"), ("matches", "<u4"), ("rho", "<f4"),
+                           ("sigma_rho", "<f4"), ("pos_img", "<f4", (2,))])
+assert KF_MATCH_DTYPE.itemsize == 32
+
 
 class Params(C.Structure):
     _fields_ = [
@@ -66,6 +71,11 @@ class CloudPose(C.Structure):
     _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("scale", C.c_float)]
 
 
+class KfMatch(C.Structure):
+    _fields_ = [("kf_keyline", C.c_int), ("keyline", C.c_int), ("claimants", C.c_int), ("matches", C.c_uint), ("rho", C.c_float),
+                ("sigma_rho", C.c_float), ("pos_img", C.c_float * 2)]
+
+
 # every symbol include/rebvio_hip.h declares: (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
@@ -98,6 +108,8 @@ SIGNATURES = {
     "rebvio_hip_map_point_cloud_async": (C.c_int, [_vp, _vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), C.POINTER(_vp)]),
     "rebvio_hip_cloud_wait": (C.c_int, [_vp, C.POINTER(_vp), _ip, C.POINTER(_vp)]),
     "rebvio_hip_cloud_release": (None, [_vp]),
+    "rebvio_hip_map_mark_keyframe": (C.c_int, [_vp, _vp]),
+    "rebvio_hip_map_keyframe_matches": (C.c_int, [_vp, C.c_int, C.POINTER(KfMatch), C.c_int, _ip]),
     "rebvio_hip_map_upload": (C.c_int, [_vp, _vp, C.c_int]),
     "rebvio_hip_map_release": (None, [_vp]),
     "rebvio_hip_build_distance_field": (C.c_int, [_vp, _vp]),
@@ -132,6 +144,7 @@ SIGNATURES = {
     "rebvio_hip_push_frame_px_gyro_device": (C.c_int, [_vp, _vp, C.c_int, _vp, _fp, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_push_frame_px_gyro": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.c_uint64, C.POINTER(PairOut), _ip]),
     "rebvio_hip_gyro_integrate": (None, [_fp, _fp, C.c_float]),
+    "rebvio_hip_keyframe_next": (C.c_int, [_vp]),
     "rebvio_hip_next_record": (C.c_int, [_vp, C.POINTER(PairOut), _ip]),
     "rebvio_hip_pairs_started": (C.c_uint64, [_vp]),
     "rebvio_hip_flush": (C.c_int, [_vp]),
@@ -407,6 +420,25 @@ class Map:
         n = C.c_int()
         _chk(lib().rebvio_hip_map_point_cloud(self.h, _cloud_filter(filter), _cloud_pose(pose), out.ctypes.data if cap else None,
                                               cap, C.byref(n)))
+        out = out[:min(n.value, cap)]
+        return (out, n.value) if return_count else out
+
+    def mark_keyframe(self):
+        """Makes this map the keyframe: match_id_keyframe[i] = i for every keyline (rebvio_hip_map_mark_keyframe; queued on the track
+        stream, returns at once). Mark a map after it has been a pair's new map and before it serves as an old map."""
+        _chk(lib().rebvio_hip_map_mark_keyframe(self.ctx.h, self.h))
+
+    def keyframe_matches(self, kf_size: int, cap=None, return_count=False):
+        """The keyframe-to-current correspondences of this map as a KF_MATCH_DTYPE array, one record per keyline of the keyframe
+        (indices 0..kf_size-1) that a keyline of this map still continues, in ascending kf_keyline (rebvio_hip_map_keyframe_matches).
+        cap: at most this many records (default: kf_size); return_count: also the number of such keyframe keylines, which may
+        exceed cap."""
+        if cap is None:
+            cap = max(0, int(kf_size))
+        out = np.zeros(cap, KF_MATCH_DTYPE)
+        n = C.c_int()
+        _chk(lib().rebvio_hip_map_keyframe_matches(self.h, kf_size, out.ctypes.data_as(C.POINTER(KfMatch)) if cap else None, cap,
+                                                   C.byref(n)))
         out = out[:min(n.value, cap)]
         return (out, n.value) if return_count else out
 
@@ -764,6 +796,11 @@ class Context:
     def pairs_started(self) -> int:
         """Frame pairs the streaming driver has queued on the device so far."""
         return int(lib().rebvio_hip_pairs_started(self.h))
+
+    def keyframe_next(self):
+        """The next frame pushed becomes a keyframe (rebvio_hip_keyframe_next): its map is marked between the pair that ends at it
+        and the pair that starts from it."""
+        _chk(lib().rebvio_hip_keyframe_next(self.h))
 
     def next_record(self):
         """The oldest complete pair record not handed out yet, or None."""

@@ -246,6 +246,9 @@ struct rebvio_hip_map {
   // rebvio_hip_push_frame_px_gyro*). Not set: the identity.
   bool gyro_set = false;
   float gyro_R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  // streaming driver: rebvio_hip_keyframe_next was called in front of this frame - the map is marked (k_mark_keyframe) in front of
+  // the pair it is the OLD map of. Cleared there, and wherever the map goes back to the pool (release_map).
+  bool kf_flag = false;
   int tab_idx = -1;         // entry of this map in its lane's device map table (batch driver)
   MapDev canon{};           // ... as uploaded there (the live `d` differs from it by the ping-pong swaps only)
 };
@@ -471,6 +474,14 @@ struct rebvio_hip_ctx {
   int* cloud_scratch = nullptr;  // [kMaxRecBlocks] counts, then the ticket word
   hipStream_t s_cloud{};         // the copies to the host: PCIe writes next to the track stream's kernels, not between them
   unsigned cloud_seq = 0;
+  // keyframes: rebvio_hip_keyframe_next is pending for the next frame pushed; scratch of rebvio_hip_map_keyframe_matches (allocated
+  // on first use, kept; only that entry, a track-side one, uses it): the slot table - ceil(keylines_max / 256) * 256 winner keys,
+  // as many claimant counts, then kMaxRecBlocks block counts and the record count - and keylines_max records.
+  bool kf_pending = false;
+  unsigned long long* kf_key = nullptr;
+  int* kf_claimants = nullptr;  // (views into kf_key's allocation)
+  int* kf_blk = nullptr;
+  rebvio_hip_kf_match* kf_rec = nullptr;
 };
 
 namespace {
@@ -598,6 +609,7 @@ rebvio_hip_map* acquire_map(rebvio_hip_ctx* c) {
     m->raster_order = false;
     m->pre_rotated = false;
     m->gyro_set = false;
+    m->kf_flag = false;
     m->promised.store(false, std::memory_order_relaxed);
     m->n_host = -1;
     m->thr_host = -1.0f;
@@ -1096,6 +1108,7 @@ void rebvio_hip_reset_state(rebvio_hip_ctx* c) {
   // stay available through rebvio_hip_next_record), so that no harvested record writes the old state back over the reset one.
   if (c->q.count || !c->frames.empty()) (void)rebvio_hip_flush(c);
   drop_carry(c);  // a reset ends a stream with gyro rotations too: the next frame pushed is a first frame
+  c->kf_pending = false;  // a keyframe request belongs to the stream it was made in
   c->plain_flushed = false;  // ... and whatever it is pushed with is a first frame's rotation: ignored, as on a fresh context
   c->wbg_shadow_valid = false;  // (the next stream's first pair uploads this state and starts the shadow from it)
   c->Bg[0] = c->Bg[1] = c->Bg[2] = 0.f;
@@ -1773,6 +1786,63 @@ void rebvio_hip_cloud_release(rebvio_hip_cloud* cl) {
   release_cloud(cl);
 }
 
+int rebvio_hip_map_mark_keyframe(rebvio_hip_ctx* c, rebvio_hip_map* m) {
+  if (!c || !m) return fail_msg("map_mark_keyframe: null context or map", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (m->ctx != c) return fail_msg("map_mark_keyframe: map of another context", -3);
+  HIPCHK(hipSetDevice(c->device));
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  launch_mark_keyframe(c->s_trk, c->K, m->d);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static_assert(sizeof(rebvio_hip_kf_match) == 32, "a correspondence record is two 16-byte stores");
+
+int rebvio_hip_map_keyframe_matches(rebvio_hip_map* m, int kf_size, rebvio_hip_kf_match* out_host, int cap, int* count) {
+  if (!m) return fail_msg("map_keyframe_matches: null map", -3);
+  if (!count) return fail_msg("map_keyframe_matches: null count", -3);
+  if (cap < 0 || (cap > 0 && !out_host)) return fail_msg("map_keyframe_matches: cap records need an output buffer (cap >= 0)", -3);
+  if (kf_size < 0) return fail_msg("map_keyframe_matches: negative kf_size", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = m->ctx;
+  if (kf_size > c->P.keylines_max) return fail_msg("map_keyframe_matches: kf_size above keylines_max", -3);
+  *count = 0;
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg("map_keyframe_matches: the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
+                    "its correspondences are available again once the next track_pair_begin has run", -7);
+  if (kf_size == 0) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t slots = (size_t)div_up(c->P.keylines_max, 256) * 256;
+  if (!c->kf_rec) {
+    if (!c->kf_key) HIPCHK(c->own.device_bytes(&c->kf_key, slots * (sizeof(unsigned long long) + sizeof(int)) + (kMaxRecBlocks + 1) * sizeof(int)));
+    c->kf_claimants = reinterpret_cast<int*>(c->kf_key + slots);
+    c->kf_blk = c->kf_claimants + slots;
+    HIPCHK(c->own.device(&c->kf_rec, (size_t)c->P.keylines_max));
+  }
+  if (cap > c->P.keylines_max) cap = c->P.keylines_max;  // (no more slots than that can hold a claimant)
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  int* count_dev = c->kf_blk + kMaxRecBlocks;
+  HIPCHK((hipError_t)launch_kf_matches(c->s_trk, c->K, m->d, kf_size, cap, c->kf_key, c->kf_claimants, c->kf_blk, count_dev, c->kf_rec));
+  HIPCHK(hipGetLastError());
+  // the count first; then one copy of exactly the records that exist
+  int n = 0;
+  HIPCHK(hipMemcpyAsync(&n, count_dev, sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  { const int rc_ts = trk_sync(c); if (rc_ts) return rc_ts; }
+  const int k = n < cap ? n : cap;
+  if (k > 0) {
+    HIPCHK(hipMemcpyAsync(out_host, c->kf_rec, (size_t)k * sizeof(rebvio_hip_kf_match), hipMemcpyDeviceToHost, c->s_trk));
+    const int rc_ts = trk_sync(c);
+    if (rc_ts) return rc_ts;
+  }
+  *count = n;
+  return 0;
+}
+
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n) {
   const MapAlive alive(m);
   if (alive.dead()) return -10;
@@ -1838,6 +1908,7 @@ void release_map(rebvio_hip_map* m, hipEvent_t done_ref, bool record_done) {
   }
   if (c->df_map == m) c->df_map = nullptr;
   m->release_seq = ++c->release_counter;
+  m->kf_flag = false;  // (a flagged frame dropped untracked must not hand its request to the frame that reuses the map)
   m->in_use = false;  // (c->last_detected may keep pointing at it: only its MapState is read, stream-ordered)
 }
 }  // namespace
@@ -2570,6 +2641,10 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
     c->df_map = nm;
     const int slot = (int)(c->pair_seq % rebvio_hip_ctx::kSlots);
     const int gpar = (int)(c->pair_seq & 1);
+    if (om->kf_flag) {  // rebvio_hip_keyframe_next: behind the pair that ended at om (stream order), in front of this one
+      launch_mark_keyframe(s, c->K, om->d);
+      om->kf_flag = false;
+    }
     if (!om->pre_rotated) {
       const int rc = start_lane_stream(c, om, nm, gpar);
       if (rc) return rc;
@@ -2658,6 +2733,10 @@ int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame
     m->gyro_set = true;
     std::memcpy(m->gyro_R, R_gyro, sizeof(m->gyro_R));
     c->gyro_stream = true;
+  }
+  if (c->kf_pending) {  // rebvio_hip_keyframe_next
+    m->kf_flag = true;
+    c->kf_pending = false;
   }
   c->plain_flushed = false;
   if (c->carry) {  // a flushed stream with gyro rotations goes on from its newest map
@@ -2757,6 +2836,13 @@ void rebvio_hip_gyro_integrate(float R[9], const float gyro_cam[3], float dt_s) 
 }
 
 uint64_t rebvio_hip_pairs_started(rebvio_hip_ctx* c) { return c->pair_seq; }
+
+int rebvio_hip_keyframe_next(rebvio_hip_ctx* c) {
+  if (!c) return fail_msg("keyframe_next: null context", -3);
+  if (c->batch) return fail_msg("keyframe_next: the context is a lane of a batch; keyframes inside lock-step steps are not supported", -3);
+  c->kf_pending = true;
+  return 0;
+}
 
 // Test hook: the kernels of the NEXT pair this context queues (per-pair API or streaming driver) are handed a wrong sequence
 // stamp, so its records look exactly like records read before the pair wrote them; the call that reads them must fail with -12.

@@ -320,6 +320,14 @@ void launch_point_cloud(hipStream_t s, const KParams& p, const MapDev& m, const 
 // *hdr. ticket = one zeroed word of device memory that only copies on this stream use.
 void launch_point_cloud_copy(hipStream_t s, const KParams& p, const void* records_dev, const int* count_dev, const CloudArgs& a,
                              unsigned* ticket, CloudHdr* hdr, void* records_host);
+// k_mark_keyframe on stream s: match_id_keyframe[i] = i for every keyline of m (rebvio_hip_map_mark_keyframe, rebvio_hip_keyframe_next)
+void launch_mark_keyframe(hipStream_t s, const KParams& p, const MapDev& m);
+// Keyframe correspondences of m on stream s (rebvio_hip_map_keyframe_matches; kf_size in 1..kmax, cap <= kmax): the slot table -
+// key / claimants, ceil(kmax / 256) * 256 entries each, cleared here on s - then k_kf_claim, k_kf_count, k_kf_emit. blk_cnt =
+// kMaxRecBlocks ints; *count_dev = slots with a claimant; records_dev = min(count, cap) 32-byte rebvio_hip_kf_match records in
+// ascending slot order. Returns a hipError_t of the clears (0 = none).
+int launch_kf_matches(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, int cap, unsigned long long* key, int* claimants,
+                      int* blk_cnt, int* count_dev, void* records_dev);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 

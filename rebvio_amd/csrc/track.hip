@@ -3260,4 +3260,96 @@ void launch_point_cloud_copy(hipStream_t s, const KParams& p, const void* record
             reinterpret_cast<float4*>(records_host));
 }
 
+// ---- keyframes (rebvio_hip_map_mark_keyframe, rebvio_hip_keyframe_next, rebvio_hip_map_keyframe_matches) ------------------------
+// match_id_keyframe (types/keyline.hpp:39) rides through forwardMatch and directedMatch (edge_map.cpp:93,210); the reference never
+// sets it. k_mark_keyframe starts it: every keyline of the map becomes its own keyframe id. One coalesced dword store per lane;
+// nothing else of the map is written.
+__global__ __launch_bounds__(256) void k_mark_keyframe(MapDev m) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < m.st->n) m.match_kf[idx] = idx;
+}
+
+void launch_mark_keyframe(hipStream_t s, const KParams& p, const MapDev& m) {
+  RH_LAUNCH(k_mark_keyframe, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, m);
+}
+
+// Keyframe-to-current correspondences: per keyframe slot j < kf_size the keylines i of this map with match_id_keyframe[i] == j
+// ("claimants"), their number, and the one of smallest sigma_rho (smallest index among equals) as the winner.
+//   k_kf_claim  one thread per keyline: 64-bit atomicMin of (sigma key << 32 | i) and an integer atomicAdd into its slot - both
+//               independent of the order the claims arrive in, so the table is the same bit for bit on every run
+//   k_kf_count / k_kf_emit  the order-preserving compaction of k_cloud_count / k_cloud_emit over the slots that have a claimant
+// The table (keys all-ones, counts zero) is initialised on the same stream in front of k_kf_claim (launch_kf_matches).
+__device__ __forceinline__ unsigned kf_sigma_key(float sigma_rho) {
+  // positive test: NaN and negative values sort behind everything (+inf included); + 0.0f folds -0.0 into +0.0
+  return sigma_rho >= 0.0f ? __float_as_uint(sigma_rho + 0.0f) : 0xFFFFFFFFu;
+}
+
+__global__ __launch_bounds__(256) void k_kf_claim(MapDev m, int kf_size, unsigned long long* __restrict__ key, int* __restrict__ claimants) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int id = m.match_kf[idx];  // bound-free early loads (the arrays are padded to the launch grid)
+  const float2 rs = m.rs[idx];
+  if (idx >= m.st->n || id < 0 || id >= kf_size) return;
+  atomicMin(key + id, ((unsigned long long)kf_sigma_key(rs.y) << 32) | (unsigned)idx);
+  atomicAdd(claimants + id, 1);
+}
+
+__global__ __launch_bounds__(256) void k_kf_count(int kf_size, const int* __restrict__ claimants, int* __restrict__ blk_cnt) {
+  __shared__ int sh[4];
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const int2 w = wave_place(j < kf_size && claimants[j] > 0);  // (the table covers the launch grid)
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w.y;
+  __syncthreads();
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void k_kf_emit(MapDev m, int kf_size, int cap, const unsigned long long* __restrict__ key,
+                                                 const int* __restrict__ claimants, const int* __restrict__ blk_cnt,
+                                                 int* __restrict__ count_out, float4* __restrict__ out) {
+  __shared__ int sh_w[4], sh_lo[4], sh_all[4];
+  const int tid = threadIdx.x, j = blockIdx.x * 256 + tid, wv = tid >> 6;
+  const int cl = claimants[j];
+  const unsigned long long k = key[j];
+  // every workgroup's count, one per thread (gridDim.x <= kMaxRecBlocks = 256)
+  const int c = tid < (int)gridDim.x ? blk_cnt[tid] : 0;
+  const int lo = wave_sum_i(tid < (int)blockIdx.x ? c : 0), all = wave_sum_i(c);
+  const bool pass = j < kf_size && cl > 0;
+  const int2 w = wave_place(pass);
+  if ((tid & 63) == 0) {
+    sh_w[wv] = w.y;
+    sh_lo[wv] = lo;
+    sh_all[wv] = all;
+  }
+  __syncthreads();
+  int rank = (sh_lo[0] + sh_lo[1]) + (sh_lo[2] + sh_lo[3]) + w.x;
+  for (int i = 0; i < wv; ++i) rank += sh_w[i];
+  if (blockIdx.x == 0 && tid == 0) *count_out = (sh_all[0] + sh_all[1]) + (sh_all[2] + sh_all[3]);
+  if (pass && rank < cap) {
+    const int win = (int)(unsigned)k;  // a claimant's index is below the map's size: k_kf_claim
+    const float2 rs = m.rs[win];
+    const float2 pi = m.pos_img[win];
+    const unsigned mt = m.matches[win];
+    // two 16-byte stores per record, as k_cloud_emit
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) volatile v4f* GRec;
+    GRec rec = (GRec)(out + 2 * (size_t)rank);
+    rec[0] = v4f{__int_as_float(j), __int_as_float(win), __int_as_float(cl), __uint_as_float(mt)};
+    rec[1] = v4f{rs.x, rs.y, pi.x, pi.y};
+  }
+}
+
+int launch_kf_matches(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, int cap, unsigned long long* key, int* claimants,
+                      int* blk_cnt, int* count_dev, void* records_dev) {
+  // on THIS stream: a null-stream memset is not ordered against the context's non-blocking streams (alloc_map)
+  const size_t slots = (size_t)div_up(p.kmax, 256) * 256;
+  hipError_t e = hipMemsetAsync(key, 0xFF, slots * sizeof(unsigned long long), s);
+  if (e == hipSuccess) e = hipMemsetAsync(claimants, 0, slots * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  RH_LAUNCH(k_kf_claim, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, m, kf_size, key, claimants);
+  const dim3 grid(div_up(kf_size, 256));
+  RH_LAUNCH(k_kf_count, grid, dim3(256), 0, s, kf_size, (const int*)claimants, blk_cnt);
+  RH_LAUNCH(k_kf_emit, grid, dim3(256), 0, s, m, kf_size, cap, (const unsigned long long*)key, (const int*)claimants, (const int*)blk_cnt,
+            count_dev, reinterpret_cast<float4*>(records_dev));
+  return 0;
+}
+
 }  // namespace rh

@@ -144,4 +144,19 @@ std::vector<rebvio::types::CloudPoint> EdgeMap::pointCloud(const rebvio::types::
   return points;
 }
 
+void EdgeMap::markKeyframe() {
+  check("rebvio_hip_map_mark_keyframe", rebvio_hip_map_mark_keyframe(ctx_, handle_));
+  invalidateMirror();
+}
+
+std::vector<rebvio::types::KfMatch> EdgeMap::keyframeMatches(int kf_size) {
+  static_assert(sizeof(types::KfMatch) == sizeof(rebvio_hip_kf_match), "keyframe correspondences mirror the C-ABI's");
+  std::vector<rebvio::types::KfMatch> out((size_t)(kf_size > 0 ? kf_size : 0));
+  int count = 0;
+  check("rebvio_hip_map_keyframe_matches",
+        rebvio_hip_map_keyframe_matches(handle_, kf_size, reinterpret_cast<rebvio_hip_kf_match*>(out.data()), (int)out.size(), &count));
+  out.resize((size_t)count);  // (count <= kf_size: one record per keyframe keyline at most)
+  return out;
+}
+
 }  // namespace rebvio

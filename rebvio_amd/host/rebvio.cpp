@@ -105,6 +105,8 @@ void Rebvio::registerEdgeImageCallback(std::function<void(cv::Mat&, rebvio::Edge
 
 void Rebvio::registerOdometryCallback(std::function<void(rebvio::types::Odometry&)> cb) { odometry_callbacks_.push_back(cb); }
 
+void Rebvio::registerKeyframeCallback(std::function<void(uint64_t ts_us, int kf_matches, int keylines)> cb) { keyframe_callbacks_.push_back(cb); }
+
 void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
   point_cloud_callbacks_.push_back({cb, filter});
 }
@@ -326,6 +328,7 @@ void Rebvio::stateEstimationProcess() {
     // the pair's counters are)
     types::CloudPose cloud_pose;
     std::vector<rebvio_hip_cloud*> clouds;
+    int kf_matches = 0;    // of the pair, for the keyframe callbacks
   } pending;
   // Two steps: the counters (and with them the stop conditions of rebvio.cpp:236-252) are fetched as soon as the next pair's
   // first half is back; the callbacks run after that pair's second half has been launched, off the path between its halves.
@@ -333,6 +336,10 @@ void Rebvio::stateEstimationProcess() {
     if (!pending.fetched) return;
     pending.fetched = false;
     for (auto& cb : odometry_callbacks_) cb(pending.odometry);
+    if (!keyframe_callbacks_.empty()) {
+      const int keylines = pending.new_map->size();
+      for (auto& cb : keyframe_callbacks_) cb(pending.odometry.ts_us, pending.kf_matches, keylines);
+    }
     // every cloud goes back to its pool, also when a callback (or the wait) throws
     struct CloudsBack {
       std::vector<rebvio_hip_cloud*>& v;
@@ -377,6 +384,7 @@ void Rebvio::stateEstimationProcess() {
       ok = false;
     }
     pending.odometry.klm_num = klm_num;
+    pending.kf_matches = kf_matches;
     return ok;
   };
   auto complete_pending = [&]() -> bool {
@@ -572,6 +580,9 @@ void Rebvio::stateEstimationProcess() {
         clouds.push_back(cl);
       }
     }
+    // Rebvio::requestKeyframe: the new map is marked behind this pair's second half (which writes the previous keyframe's ids into
+    // it), in front of the next pair's first half (which hands the ids on)
+    if (keyframe_requested_.exchange(false)) new_edge_map->markKeyframe();
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
     timers.lap(2);
 
