@@ -6,15 +6,8 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def backend():
-    from rebvio_amd import backend as B
-    if not os.path.exists(B.LIB_PATH):
-        B.build()
-    return B
+from support import backend  # noqa: F401
+from support import ROOT
 
 
 def _declared_symbols():

@@ -13,22 +13,14 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_detection_mask_gpu import assert_map, masked_map
-from test_parity_gpu import _record_words, assert_keylines_equal, assert_pipeline_bit_identical, run_stream
+from support import B  # noqa: F401
+from support import (F32, assert_keylines_equal, assert_map, assert_pipeline_bit_identical, masked_map, record_words, run_stream,
+                     set_forms)
 
 pytestmark = pytest.mark.gpu
 
 # the base case: the servo off, so that the gates see exactly the configured threshold
 BASE = dict(keylines_ref=1500, keylines_max=6000, gain=0.0)
-F32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as in test_parity_gpu: torch's HIP runtime first)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
 
 
 def _bits(x):
@@ -52,7 +44,7 @@ def assert_detect_equal(orc, ctx, om, gm, what):
 def detect_both(orc_mod, B, cam_or_size, frames, kw, what, mask=None):
     """frames through a fresh oracle and a fresh context, a detect comparison on every frame; returns the oracle's counts.
     mask: a static detection mask for the library; the expectation is then the oracle's unmasked map with the masked pixels
-    dropped (test_detection_mask_gpu.masked_map; gain must be 0 and nothing may be truncated)."""
+    dropped (support.masked_map; gain must be 0 and nothing may be truncated)."""
     if isinstance(cam_or_size, tuple):
         H, W = cam_or_size
         orc = orc_mod.Oracle(orc_mod.default_params(H, W, **kw))
@@ -500,10 +492,10 @@ def batch_run(B, params, lanes, streams, steps):
         outs, nks = bat.push_u8_device([d + k * H * W for d in devs], k * 50000)
         for l in range(lanes):
             if outs[l].status >= 0:
-                got[l].append((_record_words(outs[l]), int(nks[l])))
+                got[l].append((record_words(outs[l]), int(nks[l])))
     for outs, nks in bat.flush():
         for l in range(lanes):
-            got[l].append((_record_words(outs[l]), int(nks[l])))
+            got[l].append((record_words(outs[l]), int(nks[l])))
     states = [bat.lanes[l].detector_state() for l in range(lanes)]
     bat.close()
     return got, states
@@ -512,7 +504,7 @@ def batch_run(B, params, lanes, streams, steps):
 def alone_run(B, params, frames, steps):
     ctx = B.Context(params)
     dev = ctx.upload_frames(frames)
-    recs = [(_record_words(o), int(n)) for o, n in run_stream(ctx, dev, range(steps), params.rows * params.cols)]
+    recs = [(record_words(o), int(n)) for o, n in run_stream(ctx, dev, range(steps), params.rows * params.cols)]
     state = ctx.detector_state()
     ctx.close()
     return recs, state
@@ -536,12 +528,9 @@ def test_batch_lanes_off_the_defaults(orc_mod, B, small_stream, monkeypatch, con
     kw = dict(BATCH_CONFIGS[config], global_min_matches_threshold=1)
     orders = lane_orders(lanes)
     streams = [np.ascontiguousarray(frames[o]) for o in orders]
-    if head:
-        monkeypatch.setenv("REBVIO_HIP_BATCH_DM_HEAD", head)
-    else:
-        monkeypatch.delenv("REBVIO_HIP_BATCH_DM_HEAD", raising=False)
+    set_forms(monkeypatch, batch_head=head)
     got, states = batch_run(B, params_for(B, cam, **kw), lanes, streams, BATCH_STEPS)
-    monkeypatch.delenv("REBVIO_HIP_BATCH_DM_HEAD", raising=False)
+    set_forms(monkeypatch)
     for l in range(lanes):
         alone, alone_state = alone_run(B, params_for(B, cam, **kw), streams[l], BATCH_STEPS)
         assert len(alone) == BATCH_STEPS - 1
@@ -555,7 +544,7 @@ def test_batch_lanes_off_the_defaults(orc_mod, B, small_stream, monkeypatch, con
             for k in range(BATCH_STEPS):
                 m = orc.detect_u8(streams[l][k], k * 50000)
                 if prev is not None:
-                    wo = _record_words(orc.track_pair(prev, m))
+                    wo = record_words(orc.track_pair(prev, m))
                     assert got[l][k - 1][1] == m.size(), (l, k, got[l][k - 1][1], m.size())
                     assert np.array_equal(got[l][k - 1][0], wo), ("oracle", l, k, np.flatnonzero(got[l][k - 1][0] != wo)[:8])
                 prev = m

@@ -8,9 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
-INC = ["-I", os.path.join(ROOT, "include")]
+from support import BUILD, INC, ROOT
+
 
 DECLS = {
     "rebvio_hip_set_detection_mask": "int rebvio_hip_set_detection_mask(rebvio_hip_ctx* ctx, const uint8_t* mask_host, size_t pitch_bytes);",

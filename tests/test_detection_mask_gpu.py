@@ -1,7 +1,7 @@
 """Detection masks (rebvio_hip_set_detection_mask and the *_masked_device entries): a masked pixel is skipped in buildEdgeMap
-(edge_detector.cpp:73-121) exactly like one that fails the magnitude test. The expected masked map is built here from the oracle's
-UNMASKED map at the same threshold: drop the keylines whose pixel is masked, truncate at keylines_max, chain with a numpy statement
-of joinEdges, threshold with one of tuneThreshold. Every comparison is bit for bit."""
+(edge_detector.cpp:73-121) exactly like one that fails the magnitude test. The expected masked map is built (support.masked_map)
+from the oracle's UNMASKED map at the same threshold: drop the keylines whose pixel is masked, truncate at keylines_max, chain with
+a numpy statement of joinEdges, threshold with one of tuneThreshold. Every comparison is bit for bit."""
 import os
 import subprocess
 
@@ -9,22 +9,13 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_parity_gpu import EUROC_D, KW_C2, _bits_equal, _record_words, assert_keylines_equal
+from support import B, host_lib  # noqa: F401
+from support import (EUROC_D, INC, KW_C2, ROOT, assert_keylines_equal, assert_map, bits_equal, c2_order, masked_map, rec, record_words,
+                     same_records)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
-INC = ["-I", os.path.join(ROOT, "include")]
 KMAX_ALL = 65536   # the oracle's budget: every candidate of a 640x480 frame
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as test_parity_gpu.py: torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
 
 
 def blocky_mask(H, W, seed, block=16, p=0.6):
@@ -41,62 +32,6 @@ def bottom_third_masked(H, W):
     m = np.ones((H, W), np.uint8)
     m[H - H // 3:] = 0
     return m
-
-
-# ---- numpy statement of the masked detector ------------------------------------------------------------------------------
-def join_edges(kl, dense):
-    """EdgeDetector::joinEdges / nextKeylineIdx (edge_detector.cpp:124-165) over the keylines kl and their dense index mask"""
-    kl["id_prev"] = -1
-    kl["id_next"] = -1
-    if len(kl) == 0:
-        return
-    pos = kl["pos"].astype(np.float64)
-    x = (pos[:, 0] + 0.5).astype(np.int64)
-    y = (pos[:, 1] + 0.5).astype(np.int64)
-    tx, ty = -kl["gradient"][:, 1], kl["gradient"][:, 0]
-    sx = np.where(ty > 0, np.where(tx > 0, 1, -1), np.where(tx < 0, -1, 1))
-    sy = np.where(ty > 0, 1, -1)
-    c1, c2, c3 = dense[y, x + sx], dense[y + sy, x], dense[y + sy, x + sx]
-    nxt = np.where(c1 >= 0, c1, np.where(c2 >= 0, c2, np.where(c3 >= 0, c3, -1)))
-    kl["id_next"] = nxt
-    prev = kl["id_prev"]
-    for idx, j in enumerate(nxt.tolist()):   # in index order: a later keyline overwrites id_prev
-        if j >= 0:
-            prev[j] = idx
-
-
-def tune_threshold(kl, previous):
-    """tuneThreshold (edge_detector.cpp:167-186) with size <= keylines_max: the cumulative loop ends at i = num_bins"""
-    if len(kl) == 0:
-        return np.float32(previous)
-    g = kl["gradient_norm"]
-    mx, mn = g.max(), g.min()
-    return np.float32(mx - np.float32(np.float32(100) * (mx - mn)) / np.float32(100))
-
-
-def masked_map(om, H, W, keep, kmax, previous_auto):
-    """(keylines, dense mask, map threshold) the masked detector must produce, from the oracle's unmasked map om"""
-    kl = om.keylines()
-    dense = om.mask(H, W).ravel()
-    pix = np.full(len(kl), -1, np.int64)
-    at = np.flatnonzero(dense >= 0)
-    pix[dense[at]] = at                         # each keyline's pixel
-    assert (pix >= 0).all() and (np.diff(pix) > 0).all()
-    sel = keep.ravel()[pix] != 0
-    kl, pix = kl[sel][:kmax].copy(), pix[sel][:kmax]
-    d2 = np.full(H * W, -1, np.int32)
-    d2[pix] = np.arange(len(kl), dtype=np.int32)
-    d2 = d2.reshape(H, W)
-    join_edges(kl, d2)
-    return kl, d2, tune_threshold(kl, previous_auto)
-
-
-def assert_map(want, gm, what):
-    kl, dense, thr = want
-    assert gm.size() == len(kl), (what, gm.size(), len(kl))
-    assert_keylines_equal(kl, gm.keylines(), what=what)
-    assert np.array_equal(gm.mask(), dense), what
-    assert _bits_equal(np.float32(gm.threshold), thr), (what, gm.threshold, thr)
 
 
 # ---- 1. against the oracle, threshold fixed --------------------------------------------------------------------------------
@@ -131,7 +66,7 @@ def test_masked_map_equals_the_oracle_map_with_masked_pixels_dropped(orc_mod, B,
         assert_map(want, gm, f"frame {i}")
         assert len(want[0]) > 300 and len(want[0]) < om.size()
         thr, auto_dev, cnt = ctx.detector_state()
-        assert cnt == len(want[0]) and _bits_equal(np.float32(auto_dev), want[2])
+        assert cnt == len(want[0]) and bits_equal(np.float32(auto_dev), want[2])
         auto = want[2]
         gm.release()
     if kmax == 3000:
@@ -160,8 +95,8 @@ def test_threshold_servo_follows_the_masked_keyline_count(orc_mod, B, c2_stream)
         gm = ctx.detect_u8(frames[i], i * 50000)
         assert_map(want, gm, f"frame {i}")
         t_dev, a_dev, c_dev = ctx.detector_state()
-        assert _bits_equal(np.float32(t_dev), thr), (i, t_dev, thr)
-        assert c_dev == len(want[0]) and _bits_equal(np.float32(a_dev), want[2])
+        assert bits_equal(np.float32(t_dev), thr), (i, t_dev, thr)
+        assert c_dev == len(want[0]) and bits_equal(np.float32(a_dev), want[2])
         count, auto = len(want[0]), want[2]
         gm.release()
     assert len(set(thrs)) >= 4, thrs     # the servo moved
@@ -169,9 +104,6 @@ def test_threshold_servo_follows_the_masked_keyline_count(orc_mod, B, c2_stream)
 
 
 # ---- 3 / 4. all-ones masks, and the streaming driver against the per-pair API --------------------------------------------------
-def _order():
-    from rebvio_amd import synth
-    return synth.pingpong_indices(8, 16)
 
 
 def _pairs(B, cam, frames, order, static=None, per_frame=None):
@@ -191,7 +123,7 @@ def _pairs(B, cam, frames, order, static=None, per_frame=None):
         if len(maps) > 2:
             maps.pop(0).release()
         if k:
-            recs.append(np.append(_record_words(ctx.track_pair(maps[0], maps[1])), np.uint32(maps[1].size())))
+            recs.append(rec(ctx.track_pair(maps[0], maps[1]), maps[1].size()))
     kl = maps[-1].keylines()
     ctx.close()
     return recs, kl
@@ -211,35 +143,29 @@ def _stream(B, cam, frames, order, static=None, per_frame=None):
         else:
             out, n = ctx.push_frame_px_masked_device(dev + int(i) * npx, B.PX_GRAY8, mdev, k * 50000)
         if out.status >= 0:
-            recs.append(np.append(_record_words(out), np.uint32(n)))
-    recs.extend(np.append(_record_words(o), np.uint32(n)) for o, n in ctx.flush())
+            recs.append(rec(out, n))
+    recs.extend(rec(o, n) for o, n in ctx.flush())
     state = ctx.detector_state()
     ctx.close()
     return recs, state
 
 
-def _same(a, b, what):
-    assert len(a) == len(b), (what, len(a), len(b))
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(x, y), (what, k, np.flatnonzero(x != y)[:8])
-
-
 def test_all_ones_mask_equals_no_mask(B, c2_stream):
     frames, cam = c2_stream
     H, W = cam.height, cam.width
-    order = _order()
+    order = c2_order()
     ones = np.full((H, W), 255, np.uint8)
     want, kl = _pairs(B, cam, frames, order)
     for kw in (dict(static=ones), dict(per_frame=ones), dict(static=ones, per_frame=ones)):
         got, kg = _pairs(B, cam, frames, order, **kw)
-        _same(want, got, f"per-pair {list(kw)}")
+        same_records(want, got, f"per-pair {list(kw)}")
         assert_keylines_equal(kl, kg, what=f"per-pair {list(kw)}")
     want_s, st = _stream(B, cam, frames, order)
-    _same(want, want_s, "per-pair vs stream, no mask")
+    same_records(want, want_s, "per-pair vs stream, no mask")
     for kw in (dict(static=ones), dict(per_frame=ones)):
         got, sg = _stream(B, cam, frames, order, **kw)
-        _same(want_s, got, f"stream {list(kw)}")
-        assert all(_bits_equal(np.float32(a), np.float32(b)) for a, b in zip(st, sg))
+        same_records(want_s, got, f"stream {list(kw)}")
+        assert all(bits_equal(np.float32(a), np.float32(b)) for a, b in zip(st, sg))
     assert want[-1][-1] > 1000 and any(w[0] != 0 for w in want)
     # a 4-lane batch: static all-ones masks on lanes 0 / 1, per-frame ones on lanes 2 / 3, against a batch without masks
     from rebvio_amd import synth
@@ -248,18 +174,18 @@ def test_all_ones_mask_equals_no_mask(B, c2_stream):
     a = _batch(B, cam, streams, order)
     b = _batch(B, cam, streams, order, static=[ones, ones, None, None], per_frame=[None, None, ones, ones])
     for l in range(L):
-        _same(a[l], b[l], f"batch lane {l}")
+        same_records(a[l], b[l], f"batch lane {l}")
 
 
 def test_streaming_driver_with_masks_equals_the_per_pair_api(B, c2_stream):
     frames, cam = c2_stream
     H, W = cam.height, cam.width
-    order = _order()
+    order = c2_order()
     for kw in (dict(static=blocky_mask(H, W, 4)), dict(per_frame=noise_mask(H, W, 5)),
                dict(static=bottom_third_masked(H, W), per_frame=blocky_mask(H, W, 6))):
         want, _ = _pairs(B, cam, frames, order, **kw)
         got, _ = _stream(B, cam, frames, order, **kw)
-        _same(want, got, list(kw))
+        same_records(want, got, list(kw))
         assert want[-1][-1] > 500
 
 
@@ -267,17 +193,17 @@ def test_streaming_driver_with_masks_equals_the_per_pair_api(B, c2_stream):
 def test_per_frame_mask_equals_static_mask_and_they_combine_as_and(B, c2_stream):
     frames, cam = c2_stream
     H, W = cam.height, cam.width
-    order = _order()
+    order = c2_order()
     m1, m2 = blocky_mask(H, W, 8), noise_mask(H, W, 9, p=0.8)
     s, _ = _stream(B, cam, frames, order, static=m1)
     f, _ = _stream(B, cam, frames, order, per_frame=m1)
-    _same(s, f, "static vs per-frame")
+    same_records(s, f, "static vs per-frame")
     both = (m1 != 0) & (m2 != 0)
     a, _ = _stream(B, cam, frames, order, static=m1, per_frame=m2)
     b, _ = _stream(B, cam, frames, order, static=both.astype(np.uint8))
     c, _ = _stream(B, cam, frames, order, static=m2, per_frame=m1)
-    _same(a, b, "static m1 + per-frame m2 vs static (m1 & m2)")
-    _same(a, c, "the two kinds swapped")
+    same_records(a, b, "static m1 + per-frame m2 vs static (m1 & m2)")
+    same_records(a, c, "the two kinds swapped")
     none, _ = _stream(B, cam, frames, order)
     assert not all(np.array_equal(x, y) for x, y in zip(none, s))      # the mask matters
     assert a[-1][-1] < s[-1][-1]
@@ -302,7 +228,7 @@ def _batch(B, cam, streams, order, static=None, per_frame=None, lens=False):
     def take(outs, ns):
         for l in range(L):
             if outs[l].status >= 0:
-                recs[l].append(np.append(_record_words(outs[l]), np.uint32(ns[l])))
+                recs[l].append(rec(outs[l], ns[l]))
 
     for k, i in enumerate(order):
         fr = [devs[l] + int(i) * H * W for l in range(L)]
@@ -322,7 +248,7 @@ def test_batch_lanes_with_different_masks_equal_stand_alone_contexts(B, lens):
     W, H, L = 640, 480, 4
     streams = [synth.render_stream(W, H, 8, stream_id=l)[0] for l in range(L)]
     cam = synth.render_stream(W, H, 1)[1]
-    order = _order()
+    order = c2_order()
     static = [blocky_mask(H, W, 10), None, bottom_third_masked(H, W), None]
     per_frame = [None, noise_mask(H, W, 11), blocky_mask(H, W, 12), None]
     got = _batch(B, cam, streams, order, static, per_frame, lens)
@@ -340,10 +266,10 @@ def test_batch_lanes_with_different_masks_equal_stand_alone_contexts(B, lens):
             out, n = (ctx.push_frame_px_masked_device(fa, B.PX_GRAY8, mdev, k * 50000) if mdev is not None
                       else ctx.push_frame_u8_device(fa, k * 50000))
             if out.status >= 0:
-                want.append(np.append(_record_words(out), np.uint32(n)))
-        want.extend(np.append(_record_words(o), np.uint32(n)) for o, n in ctx.flush())
+                want.append(rec(out, n))
+        want.extend(rec(o, n) for o, n in ctx.flush())
         ctx.close()
-        _same(want, got[l], f"lane {l}")
+        same_records(want, got[l], f"lane {l}")
         assert len(want) == len(order) - 1 and want[-1][-1] > 500
 
 
@@ -353,7 +279,7 @@ def test_static_mask_change_applies_from_the_next_frame_on(B, c2_stream):
     kernels have run), frames pushed after it get the new one: the same records as per-frame masks switched at that frame."""
     frames, cam = c2_stream
     H, W = cam.height, cam.width
-    order = _order()
+    order = c2_order()
     npx = H * W
     m_old, m_new, switch = blocky_mask(H, W, 13), noise_mask(H, W, 14), 7
 
@@ -372,12 +298,12 @@ def test_static_mask_change_applies_from_the_next_frame_on(B, c2_stream):
             else:
                 out, n = ctx.push_frame_px_masked_device(dev + int(i) * npx, B.PX_GRAY8, mdev + (k >= switch) * npx, k * 50000)
             if out.status >= 0:
-                recs.append(np.append(_record_words(out), np.uint32(n)))
-        recs.extend(np.append(_record_words(o), np.uint32(n)) for o, n in ctx.flush())
+                recs.append(rec(out, n))
+        recs.extend(rec(o, n) for o, n in ctx.flush())
         ctx.close()
         return recs
 
-    _same(run(False), run(True), "static mask switched at frame 7")
+    same_records(run(False), run(True), "static mask switched at frame 7")
     # and in a batch lane: picked up by the next push
     from rebvio_amd import synth
     streams = [synth.render_stream(W, H, 8, stream_id=l)[0] for l in range(2)]
@@ -399,16 +325,16 @@ def test_static_mask_change_applies_from_the_next_frame_on(B, c2_stream):
                 outs, ns = b.push_px_masked_device(fr, B.PX_GRAY8, [None, mdev[1] + (k >= switch) * npx], k * 50000)
             for l in range(2):
                 if outs[l].status >= 0:
-                    recs[l].append(np.append(_record_words(outs[l]), np.uint32(ns[l])))
+                    recs[l].append(rec(outs[l], ns[l]))
         for outs, ns in b.flush():
             for l in range(2):
-                recs[l].append(np.append(_record_words(outs[l]), np.uint32(ns[l])))
+                recs[l].append(rec(outs[l], ns[l]))
         b.close()
         return recs
 
     a, c = run_batch(False), run_batch(True)
     for l in range(2):
-        _same(a[l], c[l], f"batch lane {l}")
+        same_records(a[l], c[l], f"batch lane {l}")
 
 
 # ---- 8. argument refusals ----------------------------------------------------------------------------------------------------
@@ -454,9 +380,9 @@ def test_masked_entries_refuse_bad_arguments_before_queueing(B, c2_stream):
     for k in range(4):
         a, _ = ref.push_frame_u8_device(rdev + k * H * W, k * 50000)
         c, _ = ctx.push_frame_px_masked_device(cdev + k * H * W, B.PX_GRAY8, mdev.value, k * 50000)
-        assert np.array_equal(_record_words(a), _record_words(c)), k
+        assert np.array_equal(record_words(a), record_words(c)), k
     ra, rc_ = ref.flush(), ctx.flush()
-    assert len(ra) == len(rc_) and all(np.array_equal(_record_words(x[0]), _record_words(y[0])) for x, y in zip(ra, rc_))
+    assert len(ra) == len(rc_) and all(np.array_equal(record_words(x[0]), record_words(y[0])) for x, y in zip(ra, rc_))
     ref.close()
     ctx.close()
 
@@ -466,7 +392,7 @@ def test_torch_tensors_as_per_frame_masks(B, c2_stream):
     import torch
     frames, cam = c2_stream
     H, W = cam.height, cam.width
-    order = _order()
+    order = c2_order()
     m = blocky_mask(H, W, 15)
     want, _ = _stream(B, cam, frames, order, static=m)
     ctx = B.Context(params_for(B, cam, **KW_C2))
@@ -476,22 +402,17 @@ def test_torch_tensors_as_per_frame_masks(B, c2_stream):
     for k, i in enumerate(order):
         out, n = ctx.push_frame_px_masked_device(ft[int(i)], B.PX_GRAY8, mt, k * 50000)
         if out.status >= 0:
-            got.append(np.append(_record_words(out), np.uint32(n)))
-    got.extend(np.append(_record_words(o), np.uint32(n)) for o, n in ctx.flush())
+            got.append(rec(out, n))
+    got.extend(rec(o, n) for o, n in ctx.flush())
     with pytest.raises(TypeError):
         ctx.detect_px_masked_device(ft[0], B.PX_GRAY8, mt.float())
     with pytest.raises(ValueError):
         ctx.detect_px_masked_device(ft[0], B.PX_GRAY8, mt[:, :-1])
     ctx.close()
-    _same(want, got, "torch tensors")
+    same_records(want, got, "torch tensors")
 
 
 # ---- 9 / 10. the C++ class and rebvio_replay ---------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def host_lib():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "csrc")], check=True)
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "host")], check=True)
-    return BUILD
 
 
 def test_cpp_rebvio_set_detection_mask(host_lib, tmp_path):

@@ -17,35 +17,17 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_parity_gpu import (EUROC_D, KW_C2, _bits_equal, _record_words, assert_keylines_equal, assert_pipeline_bit_identical,
-                             pair_tuple, run_stream)
+from support import B  # noqa: F401
+from support import (BGRA8, DF_TILE_CAP, EUROC_D, KW_C2, NAMES, RGB8, UYVY, assert_crowded_and_sparse, assert_keylines_equal,
+                     assert_pipeline_bit_identical, bits_equal, colourise, df_tile_edge, enlarged_stream, noise_frames, pair_tuple,
+                     record_words, run_stream, tile_lower_bounds)
 
 pytestmark = pytest.mark.gpu
 
 KW_FULL = dict(keylines_ref=60000, keylines_max=65536)
-DF_TILE, DF_MAX_TILES, DF_TILE_CAP = 32, 4096, 512   # kDfTile, kDfMaxTiles, kDfTileCap (rebvio_amd/csrc/common.hpp)
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as test_parity_gpu.py: torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------
-def enlarged_stream(width, height, n, factor=4, **kw):
-    """n frames of a synth stream rendered at 1/factor of the size and enlarged (every pixel a factor x factor block), cut to
-    width x height; the camera of the enlarged frames (pixel (x, y) covers x*f .. x*f + f-1: centre x*f + (f-1)/2)."""
-    from rebvio_amd import synth
-    qw, qh = -(-width // factor), -(-height // factor)
-    small, qcam = synth.render_stream(qw, qh, n, **kw)
-    big = np.kron(small, np.ones((1, factor, factor), np.uint8))[:, :height, :width]
-    off = 0.5 * (factor - 1)
-    return np.ascontiguousarray(big), synth.Camera(width, height, qcam.fm * factor, qcam.cx * factor + off, qcam.cy * factor + off)
-
-
 def mixed_frames(width, height, n=2, seed=0):
     """Frames with sparse and crowded regions: the enlarged synthetic stream, with squares of uniform noise (fresh in every
     frame) on a coarse grid and in the bottom right corner. Noise saturates the keyline budget within a few rows, so the squares
@@ -59,59 +41,6 @@ def mixed_frames(width, height, n=2, seed=0):
                 y0, x0 = max(y, 0), max(x, 0)
                 f[y0:y0 + side, x0:x0 + side] = rng.integers(0, 256, f[y0:y0 + side, x0:x0 + side].shape)
     return frames, cam
-
-
-# ---- the oracle's field rule, per tile ----------------------------------------------------------------------------------
-def df_tile_edge(rows, cols):
-    """df_grid (common.hpp): the tile edge doubles while the frame has more than kDfMaxTiles tiles"""
-    T = DF_TILE
-    while -(-cols // T) * -(-rows // T) > DF_MAX_TILES:
-        T *= 2
-    return T
-
-
-def _round_half_away(x):
-    """std::round of fp32 values (get_index, oracle/rebvio_oracle.cpp), as integers"""
-    x = x.astype(np.float64)  # |x| + 0.5 is exact in double for every fp32 in the range of an image
-    return (np.sign(x) * np.floor(np.abs(x) + 0.5)).astype(np.int64)
-
-
-def tile_lower_bounds(kl, threshold, rows, cols, search_range, T):
-    """[nty, ntx]: the number of distinct keylines that write at least one cell of each T x T tile by the rule of
-    orc_build_distance_field - for r in [-search_range, search_range): cell get_index(pos + r * gradient / gradient_norm), fp32
-    operation by operation, keylines under the map's threshold skipped. Every such keyline has to be in the device's list
-    of that tile (or its field would be wrong), so this is a lower bound of the device's tile_cnt."""
-    ntx, nty = -(-cols // T), -(-rows // T)
-    thr = np.float32(threshold)
-    gn = kl["gradient_norm"].astype(np.float32)
-    keep = ~((thr > 0) & (gn < thr))
-    idx = np.flatnonzero(keep)
-    counts = np.zeros(nty * ntx, np.int64)
-    r = np.arange(-int(search_range), int(search_range), dtype=np.int64).astype(np.float32)[None, :]
-    for lo in range(0, len(idx), 8192):
-        sel = idx[lo:lo + 8192]
-        k = kl[sel]
-        ux = (k["gradient"][:, 0] / gn[sel]).astype(np.float32)[:, None]
-        uy = (k["gradient"][:, 1] / gn[sel]).astype(np.float32)[:, None]
-        fr = (uy * r).astype(np.float32) + k["pos"][:, 1].astype(np.float32)[:, None]
-        fc = (ux * r).astype(np.float32) + k["pos"][:, 0].astype(np.float32)[:, None]
-        row, col = _round_half_away(fr), _round_half_away(fc)
-        ok = (row >= 0) & (row < rows) & (col >= 0) & (col < cols)
-        tile = (row // T) * ntx + col // T
-        key = (np.arange(len(sel), dtype=np.int64)[:, None] * (ntx * nty) + tile)[ok]
-        counts += np.bincount(np.unique(key) % (ntx * nty), minlength=ntx * nty)
-    return counts.reshape(nty, ntx)
-
-
-def assert_crowded_and_sparse(om, rows, cols, search_range=40, what=""):
-    """The precondition of the crowded-tile tests, on the oracle's map alone: some tile is certainly over the list capacity
-    (lower bound > 512: rebuilt from the row range) and some non-empty tile is certainly under it (the device's count can
-    exceed the lower bound - its clip adds a cell each side - so the margin is a factor of two: <= 256)."""
-    T = df_tile_edge(rows, cols)
-    lb = tile_lower_bounds(om.keylines(), om.threshold, rows, cols, search_range, T)
-    assert lb.max() > DF_TILE_CAP, f"{what}: no tile over the cap (T = {T}, peak {lb.max()})"
-    assert ((lb > 0) & (lb <= DF_TILE_CAP // 2)).any(), f"{what}: no non-empty tile certainly on the list path"
-    return lb
 
 
 # ---- comparisons ------------------------------------------------------------------------------------------------------
@@ -129,7 +58,7 @@ def assert_field_equal(orc, ctx, om, gm, what):
 def assert_detect_equal(om, gm, rows, cols, what):
     assert_keylines_equal(om.keylines(), gm.keylines(), what=what)
     assert np.array_equal(om.mask(rows, cols), gm.mask()), f"{what}: dense mask"
-    assert _bits_equal(np.float32(om.threshold), np.float32(gm.threshold)), (what, om.threshold, gm.threshold)
+    assert bits_equal(np.float32(om.threshold), np.float32(gm.threshold)), (what, om.threshold, gm.threshold)
 
 
 # ---- A: the size grid ---------------------------------------------------------------------------------------------------
@@ -167,7 +96,7 @@ def test_size_grid_scale_space_detect_and_field(orc_mod, B, size):
     img = rng.integers(0, 256, (H, W)).astype(np.float32) * np.float32(3.0)
     so, sg = orc.scale_space(img), ctx.scale_space(img)
     for k in ("scale0", "scale1", "dog", "mag"):
-        assert _bits_equal(so[k], sg[k]), f"{W}x{H} {k}: {(so[k].view(np.uint32) != sg[k].view(np.uint32)).sum()} pixels differ"
+        assert bits_equal(so[k], sg[k]), f"{W}x{H} {k}: {(so[k].view(np.uint32) != sg[k].view(np.uint32)).sum()} pixels differ"
     del so, sg
     sizes, last_row = [], 0.0
     for i, f in enumerate(_grid_frames(W, H, 3 if big else 2)):
@@ -183,9 +112,6 @@ def test_size_grid_scale_space_detect_and_field(orc_mod, B, size):
 
 
 # ---- B: crowded tiles and search ranges ---------------------------------------------------------------------------------
-def _noise_frames(W, H, n, seed):
-    rng = np.random.default_rng(seed)
-    return rng.integers(0, 256, (n, H, W)).astype(np.uint8)
 
 
 @pytest.mark.parametrize("case", ["noise-640x480", "noise-192x144", "enlarged-2304x1900"])
@@ -200,7 +126,7 @@ def test_crowded_tiles_fall_back_to_the_row_range(orc_mod, B, case):
     else:
         W, H = (640, 480) if case == "noise-640x480" else (192, 144)
         kw = {}  # the default budget: 12 000 / 16 000
-        frames = _noise_frames(W, H, 2, 5)
+        frames = noise_frames(W, H, 2, 5)
     orc = orc_mod.Oracle(orc_mod.default_params(H, W, **kw))
     ctx = B.Context(B.default_params(H, W, **kw))
     for i, f in enumerate(frames):
@@ -219,7 +145,7 @@ def test_crowded_tiles_in_a_batch(orc_mod, B, c2_stream):
     through everything the tracker reads from it (matches, sums, counters - every word of every record)."""
     frames, cam = c2_stream
     n = 6
-    noise = _noise_frames(cam.width, cam.height, 1, 11)[0]
+    noise = noise_frames(cam.width, cam.height, 1, 11)[0]
     # a noise image that moves one pixel per frame, so that the tracker has something to follow
     streams = [np.stack([np.roll(noise, k, axis=1) for k in range(n)]), np.ascontiguousarray(frames[:n])]
     order = np.arange(n)
@@ -247,10 +173,10 @@ def test_crowded_tiles_in_a_batch(orc_mod, B, c2_stream):
         outs, nks = bat.push_u8_device([d + int(k) * npx for d in devs], int(k) * 50000)
         for s in range(2):
             if outs[s].status >= 0:
-                got[s].append((_record_words(outs[s]), pair_tuple(outs[s], nks[s])))
+                got[s].append((record_words(outs[s]), pair_tuple(outs[s], nks[s])))
     for outs, nks in bat.flush():
         for s in range(2):
-            got[s].append((_record_words(outs[s]), pair_tuple(outs[s], nks[s])))
+            got[s].append((record_words(outs[s]), pair_tuple(outs[s], nks[s])))
     bat.close()
     for s in range(2):
         ctx = B.Context(params_for(B, cam, **KW_C2))
@@ -260,7 +186,7 @@ def test_crowded_tiles_in_a_batch(orc_mod, B, c2_stream):
         assert len(got[s]) == len(alone) == len(want[s]) == n - 1
         for k in range(n - 1):
             assert got[s][k][1] == alone[k], (s, k)
-            wo = _record_words(want[s][k])
+            wo = record_words(want[s][k])
             assert np.array_equal(wo, got[s][k][0]), (s, k, np.flatnonzero(wo != got[s][k][0])[:8])
 
 
@@ -298,7 +224,6 @@ def test_pair_steps_at_the_large_sizes(orc_mod, B, size):
 def test_colour_and_lens_entry_points_on_a_wide_frame(orc_mod, B):
     """k_rowscan_px (one 3-byte, one 4-byte and one packed-YUV format) and the lens-model front end followed by the fp32 first
     pass, at 2300 x 64: the row pass walks each row with one lane there."""
-    from test_pixel_formats_gpu import BGRA8, NAMES, RGB8, UYVY, colourise
     W, H = 2300, 64
     frames, cam = mixed_frames(W, H, 2, seed=3)
     kw = dict(fm=cam.fm, cx=cam.cx, cy=cam.cy, keylines_ref=6000, keylines_max=8000)
@@ -318,7 +243,7 @@ def test_colour_and_lens_entry_points_on_a_wide_frame(orc_mod, B):
     ctx.set_undistort(*K, EUROC_D)
     for i in range(2):
         und = orc.front_end_u8(frames[i], *K, EUROC_D)
-        assert _bits_equal(und, ctx.front_end_u8(frames[i])), f"front end, frame {i}"
+        assert bits_equal(und, ctx.front_end_u8(frames[i])), f"front end, frame {i}"
         om, gm = orc.detect(und, i * 50000), ctx.detect_u8_host(frames[i], i * 50000)
         assert_detect_equal(om, gm, H, W, f"lens model frame {i}")
     assert om.size() > 1000

@@ -3,7 +3,7 @@ crowded-tile cases assert, on the oracle alone."""
 import numpy as np
 import pytest
 
-from test_envelope_gpu import (DF_TILE_CAP, _noise_frames, assert_crowded_and_sparse, df_tile_edge, tile_lower_bounds)
+from support import DF_TILE_CAP, assert_crowded_and_sparse, df_tile_edge, noise_frames, tile_lower_bounds
 
 
 def test_tile_edge_follows_the_tile_budget():
@@ -51,6 +51,6 @@ def test_tile_counts_bound_the_oracles_own_field(orc_mod, small_stream):
 def test_noise_frames_crowd_some_tiles_and_not_others(orc_mod, size):
     W, H = size
     orc = orc_mod.Oracle(orc_mod.default_params(H, W))
-    for i, f in enumerate(_noise_frames(W, H, 2, 5)):
+    for i, f in enumerate(noise_frames(W, H, 2, 5)):
         lb = assert_crowded_and_sparse(orc.detect_u8(f, i * 50000), H, W, what=f"{W}x{H} frame {i}")
         assert lb.max() > DF_TILE_CAP + 100   # not a marginal case

@@ -17,31 +17,22 @@ kept the keys of earlier runs into the same new map, and xrv_apply overwrote a m
 import numpy as np
 import pytest
 
-from test_forward_match import (DONOR, LAYOUTS, PATTERNS, RERUN_VELS, START_VELS, assert_bits_equal, assert_donor_pair, behind_the_camera,
-                                craft_donor_copies, craft_writers, drop_every_second_writer, forward_match_closed_form,
-                                kept_and_overwritten, preset_targets, targets_of, writers_by_target)
-from test_keyline_counts_gpu import FORMS, set_forms
-from test_parity_gpu import Pair, _bits_equal, _record_words, assert_keylines_equal, warm
-from test_track_params_gpu import KW, matching_stage, set_new_map
+from support import B  # noqa: F401
+from support import (DONOR, FORMS, KW_TRACK, LAYOUTS, PATTERNS, RERUN_VELS, START_VELS, Pair, assert_donor_pair, assert_keylines_equal,
+                     behind_the_camera, bits_equal, craft_donor_copies, craft_writers, drop_every_second_writer,
+                     forward_match_closed_form, kept_and_overwritten, matching_stage, preset_targets, record_words, set_forms,
+                     set_new_map, targets_of, warm, writers_by_target)
 
 pytestmark = pytest.mark.gpu
 
 FORM_IDS = ["-".join(str(v) for v in f if v is not None) or "default" for f in FORMS]
 
 
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as in test_parity_gpu: torch's HIP runtime first)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
-
-
 def fresh_stage(O, B, stream):
     """warm(…, 3), the oracle's sums in the kernels' order from here on, the distance field of the newest map on both sides: the
     old map carries depth state, the newest one is fresh from detection on both sides and has never been a pair's new map."""
     frames, cam = stream
-    P = warm(O, B, frames, cam, 3, **KW)
+    P = warm(O, B, frames, cam, 3, **KW_TRACK)
     P.orc.set_sum_order("device")
     P.orc.build_distance_field(P.om[1])
     P.ctx.build_distance_field(P.gm[1])
@@ -68,8 +59,8 @@ def assert_forward_match_equal(P, what):
 def assert_ext_rot_vel_equal(P, vel, what):
     eo, eg = P.orc.ext_rot_vel(vel), P.ctx.ext_rot_vel(vel)
     assert np.abs(eo["Wx"]).max() > 0
-    assert _bits_equal(np.float32(eo["Wx"]), np.float32(eg["Wx"])), (what, np.abs(eo["Wx"] - eg["Wx"]).max())
-    assert _bits_equal(np.float32(eo["JtF"]), np.float32(eg["JtF"])), (what, eo["JtF"], eg["JtF"])
+    assert bits_equal(np.float32(eo["Wx"]), np.float32(eg["Wx"])), (what, np.abs(eo["Wx"] - eg["Wx"]).max())
+    assert bits_equal(np.float32(eo["JtF"]), np.float32(eg["JtF"])), (what, eo["JtF"], eg["JtF"])
 
 
 # ---- a. many writers, stepwise ------------------------------------------------------------------------------------------
@@ -89,7 +80,7 @@ def test_many_writers_per_target(orc_mod, B, small_stream, layout, pattern):
     set_old_map(P, old)
     want, _ = forward_match_closed_form(old, new)
     ko = assert_forward_match_equal(P, f"forwardMatch, {layout}, {pattern}")
-    assert_bits_equal(ko, want, "the oracle against the closed form")
+    assert_keylines_equal(ko, want, "the oracle against the closed form")
     assert int((ko["match_id"] >= 0).sum()) == len(groups) == 131
     assert_ext_rot_vel_equal(P, ro["vel"], f"{layout}, {pattern}")
 
@@ -113,7 +104,7 @@ def test_already_matched_targets_keep_a_larger_rho(orc_mod, B, small_stream, lay
     want, _ = forward_match_closed_form(old, new)
     P.orc.forward_match(P.om[0], P.om[1])
     ko = P.om[1].keylines()
-    assert_bits_equal(ko, want, "the oracle against the closed form")
+    assert_keylines_equal(ko, want, "the oracle against the closed form")
     kept, over = kept_and_overwritten(new, ko, groups)
     print(f"{layout}, {pattern}: {kept} targets kept, {over} overwritten")
     assert kept >= 20 and over >= 20, (kept, over)
@@ -132,7 +123,7 @@ def test_forward_match_twice(orc_mod, B, small_stream):
     first = assert_forward_match_equal(P, "first forwardMatch")
     assert int((first["match_id"] >= 0).sum()) > 1000
     second = assert_forward_match_equal(P, "second forwardMatch")
-    assert_bits_equal(first, second, "the oracle's second run")
+    assert_keylines_equal(first, second, "the oracle's second run")
 
 
 @pytest.mark.parametrize("which", ["natural", "crafted_equal_rho"])
@@ -155,7 +146,7 @@ def test_forward_match_again_after_writers_dropped(orc_mod, B, small_stream, whi
     lost_winner = sum(first["match_id"][t] not in after.get(t, ()) for t in before)
     want, _ = forward_match_closed_form(dropped, first)
     second = assert_forward_match_equal(P, f"forwardMatch after the drop, {which}")
-    assert_bits_equal(second, want, "the oracle against the closed form")
+    assert_keylines_equal(second, want, "the oracle against the closed form")
     taken_over = int((second["match_id"] != first["match_id"]).sum())
     print(f"{which}: {len(before)} targets, {lost_winner} lost their winner, {taken_over} taken over by another writer")
     assert lost_winner >= 50
@@ -175,7 +166,7 @@ def test_forward_match_after_a_second_minimize_vel(orc_mod, B, small_stream, vel
         ro, rg = P.orc.minimize_vel(P.om[0], v), P.ctx.minimize_vel(P.gm[0], v)
         assert ro["accept_mask"] == rg["accept_mask"]
         for f in ("vel", "F", "Rvel", "sigma_rho_min"):
-            assert _bits_equal(np.float32(ro[f]), np.float32(rg[f])), (v, f, ro[f], rg[f])
+            assert bits_equal(np.float32(ro[f]), np.float32(rg[f])), (v, f, ro[f], rg[f])
         kl = P.om[0].keylines()
         assert np.array_equal(kl["match_id_forward"], P.gm[0].keylines()["match_id_forward"])
         if k == 0:
@@ -206,7 +197,7 @@ def test_minimize_vel_from_a_start_velocity(orc_mod, B, small_stream, monkeypatc
     rg = P.ctx.minimize_vel(P.gm[0], vel0)
     assert ro["accept_mask"] == rg["accept_mask"], (ro["accept_mask"], rg["accept_mask"])
     for f in ("vel", "F", "Rvel", "sigma_rho_min"):
-        assert _bits_equal(np.float32(ro[f]), np.float32(rg[f])), (f, ro[f], rg[f])
+        assert bits_equal(np.float32(ro[f]), np.float32(rg[f])), (f, ro[f], rg[f])
     assert np.array_equal(kl["match_id_forward"], P.gm[0].keylines()["match_id_forward"])
 
 
@@ -221,7 +212,7 @@ def test_many_writers_through_a_whole_pair(orc_mod, B, small_stream, monkeypatch
     directedMatch form."""
     set_forms(monkeypatch, *form)
     frames, cam = small_stream
-    P = Pair(orc_mod, B, frames, cam, **KW)
+    P = Pair(orc_mod, B, frames, cam, **KW_TRACK)
     P.orc.set_sum_order("device")
     P.detect(0)
     for i in (1, 2, 3, 4):   # (both sides track: the gyro-bias filter carries state from pair to pair)
@@ -237,7 +228,7 @@ def test_many_writers_through_a_whole_pair(orc_mod, B, small_stream, monkeypatch
     t, m = assert_donor_pair(po, old_after, idx, varied)
     assert set(idx.tolist()) <= set(m.tolist())
     pg = P.ctx.track_pair(P.gm[0], P.gm[1])
-    wo, wg = _record_words(po), _record_words(pg)
+    wo, wg = record_words(po), record_words(pg)
     assert np.array_equal(wo, wg), (np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
     assert np.array_equal(old_after["match_id_forward"], P.gm[0].keylines()["match_id_forward"])
     assert_keylines_equal(P.om[1].keylines(), P.gm[1].keylines(), what="newest map after the pair")

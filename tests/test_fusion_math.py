@@ -17,8 +17,7 @@ import numpy as np
 import pytest
 from scipy.linalg import expm, logm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
+from support import BUILD, ROOT
 
 
 @pytest.fixture(scope="module")

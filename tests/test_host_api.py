@@ -6,17 +6,8 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
-INC = ["-I", os.path.join(ROOT, "include")]
-
-
-@pytest.fixture(scope="module")
-def host_lib():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "csrc")], check=True)
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "host")], check=True)
-    assert os.path.exists(os.path.join(BUILD, "librebvio.so"))
-    return BUILD
+from support import host_lib  # noqa: F401
+from support import EUROC_D, INC, ROOT
 
 
 def test_ros_rebvio_call_sites_compile():
@@ -160,9 +151,6 @@ def _write_imu(path, ts, gyro, acc):
     rec["ts"], rec["gyro"], rec["acc"] = ts, gyro, acc
     assert rec.dtype.itemsize == 32
     rec.tofile(path)
-
-
-EUROC_D = [-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.0]  # camera.hpp:31-35
 
 
 # (size, frame period, keyline budget, min matches): the small 20 Hz stream of round 1, and BASELINE config 5 as stated -

@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 from conftest import params_for
+from support import KW_TRACK
 
-KW = dict(keylines_ref=1500, keylines_max=2500, global_min_matches_threshold=1)
 RHO_MIN, RHO_MAX, RHO_INIT = 1e-3, 20.0, 1.0
 RADIUS = 40.0
 
@@ -29,7 +29,7 @@ def stages(orc_mod, small_stream):
     """The pair after three warm-up pairs, stage by stage on the oracle: the newest map before directedMatch, after it, after
     regularize1Iter, after the depth filter; and what the stages were handed."""
     frames, cam = small_stream
-    orc = orc_mod.Oracle(params_for(orc_mod, cam, **KW))
+    orc = orc_mod.Oracle(params_for(orc_mod, cam, **KW_TRACK))
     maps = [orc.detect_u8(frames[0], 0)]
     for i in range(1, 5):
         maps.append(orc.detect_u8(frames[i], i * 50000))

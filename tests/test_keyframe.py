@@ -1,4 +1,4 @@
-"""Keyframes without a GPU: the numpy restatement the GPU tests compare against (tests/test_keyframe_gpu.py: np_kf_matches) on
+"""Keyframes without a GPU: the numpy restatement the GPU tests compare against (tests/support.py: np_kf_matches) on
 hand-computed cases, and the surface - the header declares the keyframe entries, the binding lists them with matching signatures,
 the library exports them."""
 import ctypes as C
@@ -8,10 +8,8 @@ import re
 import numpy as np
 import pytest
 
-from test_keyframe_gpu import KF_MATCH_DTYPE, np_kf_matches
+from support import F32, KF_MATCH_DTYPE, ROOT, np_kf_matches
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = np.float32
 ENTRIES = ("rebvio_hip_map_mark_keyframe", "rebvio_hip_keyframe_next", "rebvio_hip_map_keyframe_matches")
 
 

@@ -17,56 +17,27 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_stream_gyro_gpu import _rec, _same, _state_words, gyro_rotations
+from support import B  # noqa: F401
+from support import (F32, KF_MATCH_DTYPE, TS, assert_keylines_equal, gyro_rotations, np_kf_matches, rec, same_records, set_forms,
+                     state_words, vision_only_fusion)
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-TS = 50000
 W, H, NF = 160, 120, 10
 KW = dict(keylines_ref=600, keylines_max=800, global_min_matches_threshold=50)
-KF_MATCH_DTYPE = np.dtype([("kf_keyline", "<i4"), ("keyline", "<i4"), ("claimants", "<i4"), ("matches", "<u4"), ("rho", "<f4"),
-                           ("sigma_rho", "<f4"), ("pos_img", "<f4", (2,))])
 
 
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as test_parity_gpu.py: torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    assert backend.KF_MATCH_DTYPE == KF_MATCH_DTYPE
-    return backend
+@pytest.fixture(scope="module", autouse=True)
+def binding_record_is_the_restatements(B):
+    assert B.KF_MATCH_DTYPE == KF_MATCH_DTYPE
 
 
 @functools.lru_cache(maxsize=None)
 def stream():
-    """ten frames of the 160x120 synthetic stream, their camera, and one gyro rotation per frame (test_stream_gyro_gpu.py)"""
+    """ten frames of the 160x120 synthetic stream, their camera, and one gyro rotation per frame (as test_stream_gyro_gpu.py)"""
     from rebvio_amd import synth
     frames, cam = synth.render_stream(W, H, NF)
     return frames, cam, gyro_rotations(np.arange(NF), 5)
-
-
-# ---- the numpy restatement ------------------------------------------------------------------------------------------------------------
-def np_kf_matches(kl, kf_size):
-    """rebvio_hip_map_keyframe_matches on a KEYLINE_DTYPE array: (records in ascending kf_keyline, their number). Keyline i claims
-    slot j = match_id_keyframe[i] when 0 <= j < kf_size; per slot the claimant of smallest (sk << 32) | i wins, sk = bits of
-    sigma_rho + 0.0f when sigma_rho >= 0, 0xFFFFFFFF otherwise."""
-    ids = kl["match_id_keyframe"].astype(np.int64)
-    sr = np.ascontiguousarray(kl["sigma_rho"], F32)
-    ok = (ids >= 0) & (ids < kf_size)
-    with np.errstate(invalid="ignore"):
-        ordered = sr >= 0
-        sk = np.where(ordered, (sr + F32(0.0)).view(np.uint32), np.uint32(0xFFFFFFFF)).astype(np.uint64)
-    key = (sk << np.uint64(32)) | np.arange(len(kl), dtype=np.uint64)
-    slots = np.unique(ids[ok])
-    out = np.zeros(len(slots), KF_MATCH_DTYPE)
-    for r, j in enumerate(slots):
-        cl = np.flatnonzero(ok & (ids == j))
-        w = cl[np.argmin(key[cl])]
-        out[r]["kf_keyline"], out[r]["keyline"], out[r]["claimants"] = j, w, len(cl)
-        for f in ("matches", "rho", "sigma_rho", "pos_img"):
-            out[r][f] = kl[w][f]
-    return out, len(slots)
 
 
 def assert_matches_equal(got, want, what):
@@ -74,15 +45,6 @@ def assert_matches_equal(got, want, what):
     for f in KF_MATCH_DTYPE.names:
         a, b = np.ascontiguousarray(got[f]), np.ascontiguousarray(want[f])
         assert a.tobytes() == b.tobytes(), (what, f, np.flatnonzero((a.view(np.uint32) != b.view(np.uint32)).reshape(len(a), -1).any(1))[:8])
-
-
-def assert_keylines_equal(a, b, what, skip=()):
-    assert len(a) == len(b), (what, len(a), len(b))
-    for f in a.dtype.names:
-        if f in skip:
-            continue
-        x, y = np.ascontiguousarray(a[f]), np.ascontiguousarray(b[f])
-        assert x.tobytes() == y.tobytes(), (what, f, np.flatnonzero((x.view(np.uint32) != y.view(np.uint32)).reshape(len(x), -1).any(1))[:8])
 
 
 def sized_map(B, n, frame=1):
@@ -159,7 +121,7 @@ def _propagation(orc_mod, B, marks, pairs=6):
             po, pg = orc.track_pair(mo[0], mo[1]), gpu.track_pair(mg[0], mg[1])
             print("pair", k - 1, "keylines", mo[1].size(), "klm_num", po.klm_num, "kf_matches", po.kf_matches, "/", pg.kf_matches)
             assert po.status == 0
-            assert np.array_equal(_rec(po, mo[1].size()), _rec(pg, mg[1].size())), (k, po.kf_matches, pg.kf_matches)
+            assert np.array_equal(rec(po, mo[1].size()), rec(pg, mg[1].size())), (k, po.kf_matches, pg.kf_matches)
             assert_keylines_equal(mo[1].keylines(), mg[1].keylines(), f"new map of pair {k - 1}")
             kf.append(po.kf_matches)
         if k in marks:
@@ -200,17 +162,17 @@ def pairs_ref(B, mark_at, gyro):
             if len(maps) > 2:
                 maps.pop(0).release()
             if k:
-                recs.append(_rec(ctx.track_pair(maps[0], maps[1], R_prior=R[k] if gyro else None), maps[1].size()))
+                recs.append(rec(ctx.track_pair(maps[0], maps[1], R_prior=R[k] if gyro else None), maps[1].size()))
             if k == mark_at:
                 maps[-1].mark_keyframe()
-        st = _state_words(ctx.gyro_state())
+        st = state_words(ctx.gyro_state())
         ctx.close()
         _ref[(mark_at, gyro)] = (recs, st)
     return _ref[(mark_at, gyro)]
 
 
 def kf_words(recs):
-    """kf_matches of every record (_rec: the record's words, then the keyline count; kf_matches is the fifth word from the end of
+    """kf_matches of every record (support.rec: the record's words, then the keyline count; kf_matches is the fifth word from the end of
     the record: kf_matches, reg_num, lm_accept_mask, status)"""
     return [int(r[-5].view(np.int32)) for r in recs]
 
@@ -235,11 +197,11 @@ def run_stream(B, requests=(), gyro=False, flush_after=(), reset_after_request=F
         else:
             out, n = ctx.push_frame_u8_device(dev + int(i) * W * H, k * TS)
         if out.status >= 0:
-            recs.append(_rec(out, n))
+            recs.append(rec(out, n))
         if k + 1 in flush_after:
-            recs.extend(_rec(o, n) for o, n in ctx.flush())
-    recs.extend(_rec(o, n) for o, n in ctx.flush())
-    st = _state_words(ctx.gyro_state())
+            recs.extend(rec(o, n) for o, n in ctx.flush())
+    recs.extend(rec(o, n) for o, n in ctx.flush())
+    st = state_words(ctx.gyro_state())
     launches = None
     if profile:
         launches = {name: calls for name, (_, calls) in ctx.profile_read().items()}
@@ -265,10 +227,9 @@ def test_the_reference_runs_carry_keyframe_matches(B):
                          ids=["lead3-group1", "lead5-group4", "lead8-group2", "lead12-group6", "lm-seq", "lm-spec"])
 def test_keyframe_next_equals_the_per_pair_mark(B, monkeypatch, env, mark_at, gyro):
     want, st = pairs_ref(B, mark_at, gyro)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_forms(monkeypatch, **env)
     got, sg, _ = run_stream(B, requests=(mark_at,), gyro=gyro)
-    _same(want, got, f"{env} mark at {mark_at}")
+    same_records(want, got, f"{env} mark at {mark_at}")
     assert np.array_equal(st, sg)
 
 
@@ -276,11 +237,10 @@ def test_keyframe_next_equals_the_per_pair_mark(B, monkeypatch, env, mark_at, gy
 def test_gyro_stream_carries_the_request_across_a_flush(B, monkeypatch, flush_after):
     """keyframe_next in front of frame 5 of a gyro stream that is flushed around it. Flushed right behind frame 5 (six frames in)
     the flagged map is the one the stream carries across the flush: it keeps the flag and is marked in front of pair (5, 6)."""
-    monkeypatch.setenv("REBVIO_HIP_LEAD", "3")
-    monkeypatch.setenv("REBVIO_HIP_GROUP", "1")
+    set_forms(monkeypatch, REBVIO_HIP_LEAD="3", REBVIO_HIP_GROUP="1")
     want, st = pairs_ref(B, 5, True)
     got, sg, _ = run_stream(B, requests=(5,), gyro=True, flush_after=flush_after)
-    _same(want, got, f"flush after {flush_after}")
+    same_records(want, got, f"flush after {flush_after}")
     assert np.array_equal(st, sg)
     kf = kf_words(got)
     assert kf[:5] == [0] * 5 and all(v > 300 for v in kf[5:]), kf
@@ -291,13 +251,12 @@ def test_a_flagged_frame_dropped_at_a_flush_leaves_no_flag_in_the_pool(B, monkey
     request it carried. With lead 3 / group 1 the pool holds nine maps: the fourteen frames of the second stream reuse every one of
     them, the once-flagged map as an old map too; none of its pairs may see a keyframe id."""
     from rebvio_amd import synth
-    monkeypatch.setenv("REBVIO_HIP_LEAD", "3")
-    monkeypatch.setenv("REBVIO_HIP_GROUP", "1")
+    set_forms(monkeypatch, REBVIO_HIP_LEAD="3", REBVIO_HIP_GROUP="1")
     order = synth.pingpong_indices(NF, 20)
     want, st, _ = run_stream(B, flush_after=(6,), order=order)
     got, sg, _ = run_stream(B, requests=(5,), flush_after=(6,), order=order)
     assert len(want) == 5 + 13
-    _same(want, got, "request on the last frame in front of a flush")
+    same_records(want, got, "request on the last frame in front of a flush")
     assert np.array_equal(st, sg)
     assert kf_words(got) == [0] * 18
 
@@ -307,14 +266,14 @@ def test_streams_without_a_request_launch_what_they_launched_before(B):
     k_mark_keyframe; a request dropped by reset_state: the same launches again."""
     want, st = pairs_ref(B, None, False)
     plain, sp, launches = run_stream(B, profile=True)
-    _same(want, plain, "no request vs track_pair")
+    same_records(want, plain, "no request vs track_pair")
     assert np.array_equal(st, sp)
     assert "k_mark_keyframe" not in launches and sum(launches.values()) > 4 * NF, launches
     marked, _, lm = run_stream(B, requests=(3,), profile=True)
     assert lm == dict(launches, k_mark_keyframe=1), (lm, launches)
     assert not all(np.array_equal(x, y) for x, y in zip(plain, marked))
     dropped, sd, ld = run_stream(B, requests=(0,), reset_after_request=True, profile=True)
-    _same(plain, dropped, "request dropped by reset_state")
+    same_records(plain, dropped, "request dropped by reset_state")
     assert np.array_equal(sp, sd) and ld == launches, (ld, launches)
 
 
@@ -449,7 +408,6 @@ def test_an_empty_map_has_no_matches(B):
 
 # ---- 5. refusals and leaks ---------------------------------------------------------------------------------------------------------
 def test_refusals(B):
-    from test_point_cloud_gpu import vision_only_fusion
     frames, cam, _ = stream()
     ctx, other = B.Context(params_for(B, cam, **KW)), B.Context(params_for(B, cam, **KW))
     maps = [ctx.detect_u8(frames[k], k * TS) for k in range(3)]

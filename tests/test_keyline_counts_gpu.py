@@ -37,22 +37,14 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_parity_gpu import (_bits_equal, _record_words, _vision_only_fusion, assert_keylines_equal, assert_pipeline_bit_identical,
-                             run_stream)
+from support import B  # noqa: F401
+from support import (FORMS, KW_TRACK, Pair, assert_keylines_equal, assert_pipeline_bit_identical, bits_equal, record_words, run_stream,
+                     set_forms, vision_only_fusion, words)
 
 pytestmark = pytest.mark.gpu
 
 GREY = 118   # the synthetic scenes' base level (rebvio_amd/synth.py, _texture)
-KW_SMALL = dict(keylines_ref=1500, keylines_max=2500, global_min_matches_threshold=1)
 VEL = np.array([-0.011, -0.005, -0.003], np.float32)
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as test_parity_gpu.py: torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
 
 
 @pytest.fixture(scope="module")
@@ -60,22 +52,6 @@ def wide_stream():
     """3 frames of a 256x192 stream: more than 4 352 keyline candidates per frame (asserted where it is used)."""
     from rebvio_amd import synth
     return synth.render_stream(256, 192, 3)
-
-
-def set_forms(monkeypatch, lm=None, threads=None, head=None):
-    """The kernel forms a context reads when it is created; None = the library's default."""
-    for name, v in (("REBVIO_HIP_LM", lm), ("REBVIO_HIP_LM_THREADS", threads), ("REBVIO_HIP_DM_HEAD", head)):
-        if v is None:
-            monkeypatch.delenv(name, raising=False)
-        else:
-            monkeypatch.setenv(name, str(v))
-
-
-def _words(a):
-    """fp32 values as raw words, a NaN counted as a NaN (as _record_words)"""
-    a = np.array(a, np.float32).reshape(-1)
-    a[np.isnan(a)] = np.float32(np.nan)
-    return a.view(np.uint32)
 
 
 def cut_frames(frames, cuts):
@@ -114,10 +90,10 @@ def assert_detection_equal(orc_mod, B, frames, cam, kw, what):
         om, gm = orc.detect_u8(f, k * 50000), ctx.detect_u8(f, k * 50000)
         assert_keylines_equal(om.keylines(), gm.keylines(), what=f"{what} frame {k}")
         assert np.array_equal(om.mask(cam.height, cam.width), gm.mask()), f"{what} frame {k}: dense mask"
-        assert _bits_equal(np.float32(om.threshold), np.float32(gm.threshold)), (what, k, om.threshold, gm.threshold)
+        assert bits_equal(np.float32(om.threshold), np.float32(gm.threshold)), (what, k, om.threshold, gm.threshold)
         thr, auto, cnt = ctx.detector_state()
-        assert _bits_equal(np.float32(thr), np.float32(orc.threshold)), (what, k, thr, orc.threshold)
-        assert _bits_equal(np.float32(auto), np.float32(orc.auto_threshold)), (what, k, auto, orc.auto_threshold)
+        assert bits_equal(np.float32(thr), np.float32(orc.threshold)), (what, k, thr, orc.threshold)
+        assert bits_equal(np.float32(auto), np.float32(orc.auto_threshold)), (what, k, auto, orc.auto_threshold)
         assert cnt == om.size(), (what, k, cnt, om.size())
         gm.release()
     ctx.close()
@@ -163,7 +139,6 @@ def test_exactly_full_maps(orc_mod, B, small_stream, wide_stream, monkeypatch, k
 
 # ---- 2: kernel forms at the boundary counts ----------------------------------------------------------------------------
 BOUNDARY_COUNTS = [1, 65, 257, 513, 1025, 4352]
-FORMS = [(lm, th, None) for lm in (None, "seq", "percall", "spec3") for th in (256, 512, 1024)] + [(None, None, "compact4"), (None, None, "compact1")]
 
 
 @pytest.mark.parametrize("form", FORMS, ids=["-".join(str(v) for v in f if v is not None) or "default" for f in FORMS])
@@ -194,7 +169,7 @@ def cut_case(orc_mod, small_stream, name):
     frames, cam = small_stream
     cuts, counts, status = CUT_SEQUENCES[name]
     seq = cut_frames(frames, cuts)
-    sizes, recs, last = oracle_pairs(orc_mod, ("cut", name), seq, cam, KW_SMALL)
+    sizes, recs, last = oracle_pairs(orc_mod, ("cut", name), seq, cam, KW_TRACK)
     assert sizes == counts, (name, sizes)
     assert [r.status for r in recs] == status, (name, [r.status for r in recs])
     small = [n for n, c in zip(sizes, cuts) if c is not None]
@@ -217,8 +192,8 @@ def test_sparse_maps_next_to_full_ones(orc_mod, B, small_stream, monkeypatch, na
     with maps of a few, a hundred and a few hundred keylines of a 2 500 budget."""
     set_forms(monkeypatch)
     seq, cam, status, _, _ = cut_case(orc_mod, small_stream, name)
-    assert_detection_equal(orc_mod, B, seq, cam, KW_SMALL, name)
-    assert_pipeline_bit_identical(orc_mod, B, seq, cam, np.arange(len(seq)), KW_SMALL, 0, name, expect_status=status)
+    assert_detection_equal(orc_mod, B, seq, cam, KW_TRACK, name)
+    assert_pipeline_bit_identical(orc_mod, B, seq, cam, np.arange(len(seq)), KW_TRACK, 0, name, expect_status=status)
 
 
 def _oracle_fusion(orc_mod, po):
@@ -233,10 +208,10 @@ def _oracle_fusion(orc_mod, po):
 
 
 def _guarded_vision_only_fusion(mid):
-    """_vision_only_fusion where it is defined; a pair without a velocity or with a singular information matrix hands NaN on
+    """vision_only_fusion where it is defined; a pair without a velocity or with a singular information matrix hands NaN on
     (status 1: the second half is skipped), the same in every call order."""
     try:
-        V, P, R, R0 = _vision_only_fusion(mid)
+        V, P, R, R0 = vision_only_fusion(mid)
         if all(np.isfinite(a).all() for a in (V, P, R, R0)):
             return V, P, R, R0
     except (np.linalg.LinAlgError, ValueError):
@@ -252,7 +227,7 @@ def _split_run(B, cam, seq, fuse, overlapped):
     """seq through rebvio_hip_track_pair_begin / _finish_async / _result, serially or with the next pair's first half queued
     before the result is fetched (the order rebvio::Rebvio uses): per pair the first half's record and the counters; the
     newest map's keylines. fuse(k, mid) -> (V, P_V, Rgva, R_second)."""
-    ctx = B.Context(params_for(B, cam, **KW_SMALL))
+    ctx = B.Context(params_for(B, cam, **KW_TRACK))
     maps = [ctx.detect_u8(f, k * 50000) for k, f in enumerate(seq)]
     mids, res = [], []
     for k in range(len(seq) - 1):
@@ -284,7 +259,7 @@ def test_sparse_maps_through_the_split_api(orc_mod, B, small_stream, monkeypatch
         mids, res, kl = _split_run(B, cam, seq, lambda k, mid: _oracle_fusion(orc_mod, recs[k]), overlapped)
         for k, (mid, po) in enumerate(zip(mids, recs)):
             for f in MID_FIELDS:
-                assert np.array_equal(_words(getattr(mid, f)), _words(getattr(po, f))), (name, overlapped, k, f)
+                assert np.array_equal(words(getattr(mid, f)), words(getattr(po, f))), (name, overlapped, k, f)
             assert (mid.lm_accept_mask, mid.ext_ok) == (po.lm_accept_mask, po.ext_ok), (name, overlapped, k)
             assert res[k] == (po.klm_num, po.kf_matches, po.reg_num, po.status), (name, overlapped, k, res[k])
         assert_keylines_equal(last, kl, what=f"{name}: newest map, overlapped {overlapped}")
@@ -292,7 +267,7 @@ def test_sparse_maps_through_the_split_api(orc_mod, B, small_stream, monkeypatch
     b = _split_run(B, cam, seq, lambda k, mid: _guarded_vision_only_fusion(mid), True)
     assert len(a[1]) == len(b[1]) == len(seq) - 1 and a[1] == b[1], (name, a[1], b[1])
     for k, (ma, mb) in enumerate(zip(a[0], b[0])):
-        assert np.array_equal(_record_words(ma), _record_words(mb)), (name, k)
+        assert np.array_equal(record_words(ma), record_words(mb)), (name, k)
     assert_keylines_equal(a[2], b[2], what=f"{name}: vision-only fusion, serial vs overlapped")
     assert a[1][0][3] == 0 and a[1][-1][3] == 0, a[1]   # the full pairs at both ends track
 
@@ -314,20 +289,20 @@ def test_blank_frames_in_a_stream(orc_mod, B, small_stream, monkeypatch):
     and the gyro-bias state after the flush is that of the per-pair run."""
     set_forms(monkeypatch)
     seq, cam = blank_sequence(small_stream)
-    sizes, recs, last = oracle_pairs(orc_mod, "blank", seq, cam, KW_SMALL)
+    sizes, recs, last = oracle_pairs(orc_mod, "blank", seq, cam, KW_TRACK)
     assert sizes[2] == sizes[3] == 0 and min(sizes[:2] + sizes[4:]) > 1500, sizes
     assert [r.status for r in recs] == BLANK_STATUS
     assert all(r.klm_num > 1000 for r in recs[4:]), [r.klm_num for r in recs]   # the pairs after the blank frames track again
-    assert_detection_equal(orc_mod, B, seq, cam, KW_SMALL, "blank sequence")
-    want = [_record_words(r) for r in recs]
+    assert_detection_equal(orc_mod, B, seq, cam, KW_TRACK, "blank sequence")
+    want = [record_words(r) for r in recs]
     npx = cam.width * cam.height
     # per-pair API
-    ctx = B.Context(params_for(B, cam, **KW_SMALL))
+    ctx = B.Context(params_for(B, cam, **KW_TRACK))
     prev = None
     for k, f in enumerate(seq):
         m = ctx.detect_u8(f, k * 50000)
         if prev is not None:
-            wg = _record_words(ctx.track_pair(prev, m))
+            wg = record_words(ctx.track_pair(prev, m))
             assert np.array_equal(want[k - 1], wg), ("track_pair", k, np.flatnonzero(want[k - 1] != wg)[:8])
             prev.release()
         prev = m
@@ -337,7 +312,7 @@ def test_blank_frames_in_a_stream(orc_mod, B, small_stream, monkeypatch):
     ctx.close()
     # streaming driver, frames in device memory and frames in host memory
     for source in ("device", "host"):
-        ctx = B.Context(params_for(B, cam, **KW_SMALL))
+        ctx = B.Context(params_for(B, cam, **KW_TRACK))
         if source == "device":
             dev = ctx.upload_frames(seq)
             got = run_stream(ctx, dev, range(len(seq)), npx)
@@ -350,11 +325,11 @@ def test_blank_frames_in_a_stream(orc_mod, B, small_stream, monkeypatch):
             got.extend(ctx.flush())
         assert len(got) == len(want), (source, len(got))
         for k, (out, n) in enumerate(got):
-            wg = _record_words(out)
+            wg = record_words(out)
             assert np.array_equal(want[k], wg), (source, k, np.flatnonzero(want[k] != wg)[:8])
             assert n == sizes[k + 1], (source, k, n, sizes[k + 1])
         bg, w_bg = ctx.gyro_state()
-        assert _bits_equal(bg, gyro[0]) and _bits_equal(w_bg, gyro[1]), source
+        assert bits_equal(bg, gyro[0]) and bits_equal(w_bg, gyro[1]), source
         ctx.close()
 
 
@@ -364,9 +339,9 @@ class _Stage:
 
     def __init__(self, orc_mod, B, small_stream):
         frames, cam = small_stream
-        self.orc = orc_mod.Oracle(params_for(orc_mod, cam, **KW_SMALL))
+        self.orc = orc_mod.Oracle(params_for(orc_mod, cam, **KW_TRACK))
         self.orc.set_sum_order("device")
-        self.ctx = B.Context(params_for(B, cam, **KW_SMALL))
+        self.ctx = B.Context(params_for(B, cam, **KW_TRACK))
         blank = np.full_like(frames[0], GREY)
         maps = []
         for k, f in enumerate([frames[0], frames[1], blank, frames[2]]):
@@ -387,7 +362,7 @@ def _lm_stage_equal(S, old, new, what):
     ro, rg = S.orc.minimize_vel(old[0]), S.ctx.minimize_vel(old[1])
     assert ro["accept_mask"] == rg["accept_mask"], (what, ro["accept_mask"], rg["accept_mask"])
     for k in ("vel", "F", "Rvel", "sigma_rho_min"):
-        assert np.array_equal(_words(ro[k]), _words(rg[k])), (what, k, ro[k], rg[k])
+        assert np.array_equal(words(ro[k]), words(rg[k])), (what, k, ro[k], rg[k])
     assert np.array_equal(old[0].keylines()["match_id_forward"], old[1].keylines()["match_id_forward"]), what
     S.orc.forward_match(old[0], new[0])
     S.ctx.forward_match(old[1], new[1])
@@ -397,7 +372,7 @@ def _lm_stage_equal(S, old, new, what):
         eo, eg = S.orc.ext_rot_vel(vel), S.ctx.ext_rot_vel(vel)
         assert eo["ok"] == eg["ok"], (what, eo["ok"], eg["ok"])
         for k in ("Wx", "JtF", "X"):
-            assert np.array_equal(_words(eo[k]), _words(eg[k])), (what, k, eo[k], eg[k])
+            assert np.array_equal(words(eo[k]), words(eg[k])), (what, k, eo[k], eg[k])
     return ro
 
 
@@ -482,7 +457,6 @@ def test_carry_of_the_last_fi_in_try_vel_and_minimize_vel(orc_mod, B, small_stre
     unmatched runs: residuals, match_id_forward, the score and the sums of JtJ / JtF. Preconditions on the oracle alone: no
     keyline of a run has a forward match, and after the first evaluation a carried residual inside a run exceeds
     reweight_distance (2.0537 against 2.0 in the run [1100, 1164) of frames 1 -> 2)."""
-    from test_parity_gpu import Pair
     set_forms(monkeypatch)
     frames, cam = small_stream
     for name, (runs_of, over) in CARRY_CASES.items():
@@ -514,11 +488,11 @@ def test_carry_of_the_last_fi_in_try_vel_and_minimize_vel(orc_mod, B, small_stre
                 assert res_o[inside].max() > P.orc.p.reweight_distance, (name, res_o[inside].max())  # precondition
             matched_outside.append(int((fo[~inside] >= 0).sum()))
             sg, Jg, Fg = P.ctx.try_vel(gm_old, vel, srm, res_g)
-            assert _bits_equal(res_o, res_g), (name, vel, np.flatnonzero(res_o.view(np.uint32) != res_g.view(np.uint32))[:8])
+            assert bits_equal(res_o, res_g), (name, vel, np.flatnonzero(res_o.view(np.uint32) != res_g.view(np.uint32))[:8])
             assert np.array_equal(fo, gm_old.keylines()["match_id_forward"]), (name, vel)
-            assert _bits_equal(np.float32([so]), np.float32([sg])), (name, vel, so, sg)
-            assert _bits_equal(np.float32(Jo), np.float32(Jg)), (name, vel, Jo, Jg)
-            assert _bits_equal(np.float32(Fo), np.float32(Fg)), (name, vel, Fo, Fg)
+            assert bits_equal(np.float32([so]), np.float32([sg])), (name, vel, so, sg)
+            assert bits_equal(np.float32(Jo), np.float32(Jg)), (name, vel, Jo, Jg)
+            assert bits_equal(np.float32(Fo), np.float32(Fg)), (name, vel, Fo, Fg)
         assert matched_outside[0] > 100, (name, matched_outside)   # there are matches to carry from
         om_old.set_keylines(kl)
         gm_old.upload(kl)
@@ -527,7 +501,7 @@ def test_carry_of_the_last_fi_in_try_vel_and_minimize_vel(orc_mod, B, small_stre
         assert (fo[inside] < 0).all() and (fo[~inside] >= 0).sum() > 100, name                # precondition
         assert ro["accept_mask"] == rg["accept_mask"], (name, ro["accept_mask"], rg["accept_mask"])
         for k in ("vel", "F", "Rvel", "sigma_rho_min"):
-            assert _bits_equal(np.float32(ro[k]), np.float32(rg[k])), (name, k, ro[k], rg[k])
+            assert bits_equal(np.float32(ro[k]), np.float32(rg[k])), (name, k, ro[k], rg[k])
         assert np.array_equal(fo, gm_old.keylines()["match_id_forward"]), name
         P.ctx.close()
 
@@ -545,13 +519,13 @@ def test_carry_of_the_last_fi_in_a_whole_pair(orc_mod, B, small_stream, monkeypa
     set_forms(monkeypatch, *form)
     frames, cam = small_stream
     runs_of, over = CARRY_CASES[name]
-    kw = dict(KW_SMALL, **over)
+    kw = dict(KW_TRACK, **over)
     orc = orc_mod.Oracle(params_for(orc_mod, cam, **kw))
     orc.set_sum_order("device")
     ctx = B.Context(params_for(B, cam, **kw))
     mo = [orc.detect_u8(frames[k], k * 50000) for k in range(2)]
     mg = [ctx.detect_u8(frames[k], k * 50000) for k in range(2)]
-    wo, wg = _record_words(orc.track_pair(mo[0], mo[1])), _record_words(ctx.track_pair(mg[0], mg[1]))
+    wo, wg = record_words(orc.track_pair(mo[0], mo[1])), record_words(ctx.track_pair(mg[0], mg[1]))
     assert np.array_equal(wo, wg), (name, form, "the pair in front")
     mo.append(orc.detect_u8(frames[2], 100000))
     mg.append(ctx.detect_u8(frames[2], 100000))
@@ -561,7 +535,7 @@ def test_carry_of_the_last_fi_in_a_whole_pair(orc_mod, B, small_stream, monkeypa
     po, pg = orc.track_pair(mo[1], mo[2]), ctx.track_pair(mg[1], mg[2])
     fo = mo[1].keylines()["match_id_forward"]
     assert po.status == 0 and (fo[inside] < 0).all() and (fo[~inside] >= 0).sum() > 100, (name, po.status)   # preconditions
-    wo, wg = _record_words(po), _record_words(pg)
+    wo, wg = record_words(po), record_words(pg)
     assert np.array_equal(wo, wg), (name, form, np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
     assert np.array_equal(fo, mg[1].keylines()["match_id_forward"]), (name, form)
     assert_keylines_equal(mo[2].keylines(), mg[2].keylines(), what=f"{name} {form}: new map")
@@ -592,34 +566,33 @@ def test_batch_with_empty_and_tiny_lanes(orc_mod, B, small_stream, monkeypatch, 
     wait: every workgroup of a lane polls its own lane's words only, workgroup 0 runs the LM loop over zero groups and publishes the
     final velocity the others wait for, and the glue waits for ceil(n_new / 256) = 0 extRotVel groups."""
     set_forms(monkeypatch)
-    monkeypatch.delenv("REBVIO_HIP_BATCH_DM_HEAD", raising=False)
     streams, cam = batch_streams(small_stream, lanes)
     npx = cam.width * cam.height
-    want = [oracle_pairs(orc_mod, ("batch", s), streams[s], cam, KW_SMALL) for s in range(lanes)]
+    want = [oracle_pairs(orc_mod, ("batch", s), streams[s], cam, KW_TRACK) for s in range(lanes)]
     assert all(n == 0 for n in want[1][0]) and all(r.status == 1 for r in want[1][1])          # the empty lane
     assert all(r.status == 0 and r.klm_num > 1000 for r in want[0][1])                          # the full lane
     assert min(want[2][0]) < 64 and {r.status for r in want[2][1]} == {0, 1, 2}                # the cut lane
-    bat = B.Batch(params_for(B, cam, **KW_SMALL), lanes)
+    bat = B.Batch(params_for(B, cam, **KW_TRACK), lanes)
     devs = [bat.lanes[s].upload_frames(streams[s]) for s in range(lanes)]
     got = [[] for _ in range(lanes)]
     for k in range(BATCH_STEPS):
         outs, nks = bat.push_u8_device([d + k * npx for d in devs], k * 50000)
         for s in range(lanes):
             if outs[s].status >= 0:
-                got[s].append((_record_words(outs[s]), int(nks[s])))
+                got[s].append((record_words(outs[s]), int(nks[s])))
     for outs, nks in bat.flush():
         for s in range(lanes):
-            got[s].append((_record_words(outs[s]), int(nks[s])))
+            got[s].append((record_words(outs[s]), int(nks[s])))
     bat.close()
     for s in range(lanes):
-        ctx = B.Context(params_for(B, cam, **KW_SMALL))
+        ctx = B.Context(params_for(B, cam, **KW_TRACK))
         dev = ctx.upload_frames(streams[s])
-        alone = [(_record_words(o), nk) for o, nk in run_stream(ctx, dev, range(BATCH_STEPS), npx)]
+        alone = [(record_words(o), nk) for o, nk in run_stream(ctx, dev, range(BATCH_STEPS), npx)]
         ctx.close()
         sizes, recs, _ = want[s]
         assert len(got[s]) == len(alone) == len(recs) == BATCH_STEPS - 1, (s, len(got[s]), len(alone))
         for k in range(BATCH_STEPS - 1):
-            wo = _record_words(recs[k])
+            wo = record_words(recs[k])
             assert np.array_equal(got[s][k][0], alone[k][0]), ("stand-alone", s, k, np.flatnonzero(got[s][k][0] != alone[k][0])[:8])
             assert np.array_equal(got[s][k][0], wo), ("oracle", s, k, np.flatnonzero(got[s][k][0] != wo)[:8])
             assert got[s][k][1] == alone[k][1] == sizes[k + 1], (s, k, got[s][k][1], alone[k][1], sizes[k + 1])

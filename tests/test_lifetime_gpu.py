@@ -10,20 +10,12 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_parity_gpu import EUROC_D
-from test_point_cloud_gpu import vision_only_fusion
+from support import B  # noqa: F401
+from support import EUROC_D, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
 
 KW = dict(keylines_ref=2500, keylines_max=3500, global_min_matches_threshold=50)  # as tests/cpp/test_map_lifetime.cpp
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as test_parity_gpu.py: torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
 
 
 def _plain_round(B, frames, cam):

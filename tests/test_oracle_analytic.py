@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import params_for
+from support import EUROC_D
 
 
 def test_integral_image_of_ones(orc_mod):
@@ -264,7 +265,6 @@ def test_sum_orders_differ_by_rounding_only(orc_mod, small_stream):
 
 
 # ---- front end: convertTo(CV_32F, 3.0) + cv::undistort -------------------------------------------------
-EUROC_D = [-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.0]  # camera.hpp:31-35
 
 
 def _numpy_undistort(img, fm, cx, cy, D):

@@ -18,94 +18,13 @@ import numpy as np
 import pytest
 
 from conftest import params_for
+from support import B  # noqa: F401
+from support import (EUROC_D, KW_C2, Pair, assert_keylines_equal, assert_pipeline_bit_identical, bits_equal, pair_tuple, record_words,
+                     run_stream, set_forms, vision_only_fusion, warm)
 
 pytestmark = pytest.mark.gpu
 
 REL_SUM = 2e-4   # relative tolerance of a 15k-term fp32 sum, sequential vs tree order
-KW_C2 = dict(keylines_ref=15000, keylines_max=16000)
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (the bench process has torch's HIP runtime loaded first; do the same here)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
-
-
-def _bits_equal(a, b):
-    a = np.ascontiguousarray(a)
-    b = np.ascontiguousarray(b)
-    if a.dtype.kind == "f":
-        return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    return np.array_equal(a, b)
-
-
-def assert_keylines_equal(ko, kg, fields=None, what=""):
-    assert len(ko) == len(kg), f"{what}: size {len(ko)} vs {len(kg)}"
-    for f in (fields or ko.dtype.names):
-        if not _bits_equal(ko[f], kg[f]):
-            bad = np.nonzero((ko[f] != kg[f]).reshape(len(ko), -1).any(1))[0]
-            raise AssertionError(f"{what}: field {f} differs at {len(bad)} keylines, first {bad[:5]}: "
-                                 f"{ko[f][bad[:3]]} vs {kg[f][bad[:3]]}")
-
-
-def run_stream(ctx, dev, order, npx, k0=0, ts_step=50000):
-    """Push order[] through the streaming driver and flush: every pair's (record, keyline count), in pair order - len(order) - 1
-    of them. Records come back several pushes late (the pair step runs on the device from end to end, pairs are queued in
-    groups and the host reads them up to fifteen pairs behind); the flush tracks the pairs not started yet and delivers the
-    rest."""
-    recs = []
-    for k, i in enumerate(order):
-        out, n = ctx.push_frame_u8_device(dev + int(i) * npx, (k0 + k) * ts_step)
-        if out.status >= 0:
-            recs.append((out, n))
-    recs.extend(ctx.flush())
-    return recs
-
-
-def pair_tuple(out, n=None):
-    t = (tuple(out.Vg), tuple(out.P_Vg), out.F, tuple(out.Xv), tuple(out.W_Xv), tuple(out.Xgv), tuple(out.V), tuple(out.R),
-         tuple(out.P_V), out.sigma_rho_min, out.ext_ok, out.klm_num, out.kf_matches, out.reg_num, out.lm_accept_mask, out.status)
-    return t if n is None else t + (n,)
-
-
-class Pair:
-    """Oracle and GPU contexts driven over the same frames; keeps the last two maps of each."""
-
-    def __init__(self, O, B, frames, cam, **kw):
-        self.O, self.B = O, B
-        self.frames, self.cam = frames, cam
-        self.orc = O.Oracle(params_for(O, cam, **kw))
-        self.ctx = B.Context(params_for(B, cam, **kw))
-        self.om = []
-        self.gm = []
-
-    def detect(self, i):
-        om = self.orc.detect_u8(self.frames[i], i * 50000)
-        gm = self.ctx.detect_u8(self.frames[i], i * 50000)
-        self.om.append(om)
-        self.gm.append(gm)
-        if len(self.om) > 2:
-            self.om.pop(0)
-            self.gm.pop(0).release()
-        return om, gm
-
-    def sync_gpu_from_oracle(self):
-        for om, gm in zip(self.om, self.gm):
-            gm.upload(om.keylines())
-
-
-def warm(O, B, frames, cam, n_pairs, **kw):
-    """Run n_pairs oracle tracking steps so that depths/matches are realistic; the GPU only detects."""
-    P = Pair(O, B, frames, cam, **kw)
-    P.detect(0)
-    for i in range(1, n_pairs + 1):
-        P.detect(i)
-        P.orc.track_pair(P.om[0], P.om[1])
-    P.detect(n_pairs + 1)  # pair under test: om[0] (tracked once as "new"), om[1] fresh
-    P.sync_gpu_from_oracle()
-    return P
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -117,7 +36,7 @@ def test_scale_space_bit_exact(orc_mod, B, c2_stream):
         img = frames[i].astype(np.float32) * np.float32(3.0)
         so, sg = orc.scale_space(img), ctx.scale_space(img)
         for k in ("scale0", "scale1", "dog", "mag"):
-            assert _bits_equal(so[k], sg[k]), f"{k} differs in {(so[k] != sg[k]).sum()} pixels"
+            assert bits_equal(so[k], sg[k]), f"{k} differs in {(so[k] != sg[k]).sum()} pixels"
 
 
 @pytest.mark.parametrize("sigma,n", [(3.56359, 1), (3.56359, 2), (2.2, 4), (3.0, 5), (4.49, 3)])
@@ -132,7 +51,7 @@ def test_fast_gaussian_with_any_number_of_box_passes(orc_mod, B, c2_stream, sigm
     so, widths = orc.smooth(img, sigma, n)
     assert len(widths) == n and all(3 <= w <= 11 and w % 2 == 1 for w in widths), widths
     sg = ctx.smooth(img, widths)
-    assert _bits_equal(so, sg), f"n = {n}, widths {widths}: {(so != sg).sum()} pixels differ"
+    assert bits_equal(so, sg), f"n = {n}, widths {widths}: {(so != sg).sum()} pixels differ"
     with pytest.raises(B.HipError, match="3..11"):
         ctx.smooth(img, [13] * n)
 
@@ -168,7 +87,7 @@ def test_scale_space_ragged_sizes(orc_mod, B, shape):
     pB = B.default_params(h, w)
     so, sg = orc_mod.Oracle(pO).scale_space(img), B.Context(pB).scale_space(img)
     for k in ("scale0", "scale1", "dog", "mag"):
-        assert _bits_equal(so[k], sg[k]), k
+        assert bits_equal(so[k], sg[k]), k
 
 
 def test_detect_sequence_bit_exact(orc_mod, B, c2_stream):
@@ -288,7 +207,7 @@ def test_try_vel_parity(orc_mod, B, c2_stream):
         sg, Jg, Fg = P.ctx.try_vel(gm_old, vel, srm, res_g)
         ko, kg = om_old.keylines(), gm_old.keylines()
         assert np.array_equal(ko["match_id_forward"], kg["match_id_forward"])
-        assert _bits_equal(res_o, res_g), f"residuals differ at {(res_o != res_g).sum()}"
+        assert bits_equal(res_o, res_g), f"residuals differ at {(res_o != res_g).sum()}"
         assert abs(so - sg) <= REL_SUM * abs(so)
         # off-diagonal / signed sums cancel: scale by the diagonal magnitude
         _sums_close(Jo, Jg, scale=np.abs(np.diag(Jo)).max())
@@ -363,15 +282,15 @@ def test_lm_sums_in_device_order_are_bit_exact(orc_mod, B, c2_stream, c3_stream,
     rg = P.ctx.minimize_vel(gm_old)
     assert ro["accept_mask"] == rg["accept_mask"]
     for k in ("vel", "F", "Rvel", "sigma_rho_min"):
-        assert _bits_equal(np.float32(ro[k]), np.float32(rg[k])), (k, ro[k], rg[k])
+        assert bits_equal(np.float32(ro[k]), np.float32(rg[k])), (k, ro[k], rg[k])
     assert np.array_equal(om_old.keylines()["match_id_forward"], gm_old.keylines()["match_id_forward"])
     P.orc.forward_match(om_old, om_new)
     P.ctx.forward_match(gm_old, gm_new)
     assert_keylines_equal(om_new.keylines(), gm_new.keylines(), what="forwardMatch")
     eo = P.orc.ext_rot_vel(ro["vel"])
     eg = P.ctx.ext_rot_vel(ro["vel"])
-    assert _bits_equal(np.float32(eo["Wx"]), np.float32(eg["Wx"])), np.abs(eo["Wx"] - eg["Wx"]).max()
-    assert _bits_equal(np.float32(eo["JtF"]), np.float32(eg["JtF"])), (eo["JtF"], eg["JtF"])
+    assert bits_equal(np.float32(eo["Wx"]), np.float32(eg["Wx"])), np.abs(eo["Wx"] - eg["Wx"]).max()
+    assert bits_equal(np.float32(eo["JtF"]), np.float32(eg["JtF"])), (eo["JtF"], eg["JtF"])
     # single evaluations, residuals carried from one to the next on both sides
     srm = P.orc.quantile(om_old)
     res_o = np.zeros(n, np.float32)
@@ -379,10 +298,10 @@ def test_lm_sums_in_device_order_are_bit_exact(orc_mod, B, c2_stream, c3_stream,
     for vel in ([0, 0, 0], [-0.011, -0.005, -0.003], [0.02, 0.01, -0.9]):
         so, Jo, Fo = P.orc.try_vel(om_old, vel, srm, res_o)
         sg, Jg, Fg = P.ctx.try_vel(gm_old, vel, srm, res_g)
-        assert _bits_equal(res_o, res_g)
-        assert _bits_equal(np.float32([so]), np.float32([sg])), (vel, so, sg)
-        assert _bits_equal(np.float32(Jo), np.float32(Jg)), (vel, Jo, Jg)
-        assert _bits_equal(np.float32(Fo), np.float32(Fg)), (vel, Fo, Fg)
+        assert bits_equal(res_o, res_g)
+        assert bits_equal(np.float32([so]), np.float32([sg])), (vel, so, sg)
+        assert bits_equal(np.float32(Jo), np.float32(Jg)), (vel, Jo, Jg)
+        assert bits_equal(np.float32(Fo), np.float32(Fg)), (vel, Fo, Fg)
 
 
 @pytest.fixture(scope="module")
@@ -405,10 +324,7 @@ def test_directed_match_regularize_ekf_bit_exact(orc_mod, B, c2_stream, c3_strea
     on a 64 000-keyline map of config 3 (1280x960)."""
     frames, cam = c2_stream if config == "c2" else c3_stream
     kw = KW_C2 if config == "c2" else KW_C3
-    if head:
-        monkeypatch.setenv("REBVIO_HIP_DM_HEAD", head)
-    else:
-        monkeypatch.delenv("REBVIO_HIP_DM_HEAD", raising=False)
+    set_forms(monkeypatch, head=head)
     P = warm(orc_mod, B, frames, cam, 3, **kw)
     om_old, om_new = P.om
     gm_old, gm_new = P.gm
@@ -444,10 +360,7 @@ def test_directed_match_beyond_one_probe_window(orc_mod, B, c2_stream, monkeypat
     owners' registers, a keyline found in one window is not probed in the next - in every instantiation. Bit-exact against the
     oracle, like the one-window case of test_directed_match_regularize_ekf_bit_exact."""
     frames, cam = c2_stream
-    if head:
-        monkeypatch.setenv("REBVIO_HIP_DM_HEAD", head)
-    else:
-        monkeypatch.delenv("REBVIO_HIP_DM_HEAD", raising=False)
+    set_forms(monkeypatch, head=head)
     P = warm(orc_mod, B, frames, cam, 3, **KW_C2)
     om_old, om_new = P.om
     gm_old, gm_new = P.gm
@@ -524,73 +437,6 @@ def test_track_pair_sequence(orc_mod, B, c2_stream):
         both = (ko["match_id"] == kg["match_id"]) & (ko["match_id"] >= 0)
         rel = np.abs(ko["rho"][both] - kg["rho"][both]) / np.abs(ko["rho"][both])
         assert np.median(rel) < 1e-3
-
-
-def _record_words(po):
-    """every field of a pair record as raw 32-bit words (floats by their bits)"""
-    out = []
-    for name, _ in type(po)._fields_:
-        v = getattr(po, name)
-        a = np.array(v) if hasattr(v, "__len__") else np.array([v])
-        if a.dtype.kind == "f":
-            a = a.astype(np.float32)
-            a[np.isnan(a)] = np.float32(np.nan)  # (a NaN is a NaN: sign and payload of one are not part of the result)
-            out.append(a.view(np.uint32))
-        else:
-            out.append(a.astype(np.int64).astype(np.uint32))
-    return np.concatenate(out)
-
-
-def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, what, every_pair_tracks=False, expect_status=None):
-    """frames[order] through the oracle (keyline sums in the kernels' order) and through the library, the state carried
-    independently on both sides: every word of every pair record equal through the per-pair API and through the streaming
-    driver, every keyline field of the newest map equal after the last pair. every_pair_tracks: a precondition on the oracle
-    alone - each pair ends with status 0 and at least global_min_matches_threshold LM matches (a real pair, not a failure
-    path); without it only the last pair is asked for motion and more than min_klm matches. expect_status: the oracle's pair
-    statuses, one per pair - asked for in place of that closing condition, for streams whose pairs are meant to fail."""
-    W, H, npairs = cam.width, cam.height, len(order) - 1
-    p_o = params_for(orc_mod, cam, **kw)
-    orc = orc_mod.Oracle(p_o)
-    orc.set_sum_order("device")
-    gpu = B.Context(params_for(B, cam, **kw))
-    mo, mg, rec_o, status_o = [], [], [], []
-    for k, i in enumerate(order):
-        mo.append(orc.detect_u8(frames[i], k * 50000))
-        mg.append(gpu.detect_u8(frames[i], k * 50000))
-        if len(mo) > 2:
-            mo.pop(0)
-            mg.pop(0).release()
-        if k == 0:
-            continue
-        po = orc.track_pair(mo[0], mo[1])
-        if every_pair_tracks:
-            assert po.status == 0 and po.klm_num >= p_o.global_min_matches_threshold, (what, k, po.status, po.klm_num)
-        pg = gpu.track_pair(mg[0], mg[1])
-        wo, wg = _record_words(po), _record_words(pg)
-        assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
-        rec_o.append(wo)
-        status_o.append(po.status)
-    if expect_status is None:
-        assert rec_o[-1][0] != 0 and po.klm_num > min_klm
-    else:
-        assert status_o == list(expect_status), (what, status_o)
-    # the map that carries the state into the next pair (the older one is dropped after its pair, rebvio.cpp:136-139)
-    assert_keylines_equal(mo[1].keylines(), mg[1].keylines(), what=f"{what}: newest map after {npairs} pairs")
-    gpu.close()
-    # the streaming driver on the same frames: device glue, persistent speculative LM kernel, pairs queued in groups
-    ctx = B.Context(params_for(B, cam, **kw))
-    dev = ctx.upload_frames(frames)
-    got = []
-    for k, i in enumerate(order):
-        out, _ = ctx.push_frame_u8_device(dev + int(i) * W * H, k * 50000)
-        if out.status >= 0:
-            got.append(_record_words(out))
-    for out, _ in ctx.flush():
-        got.append(_record_words(out))
-    ctx.close()
-    assert len(got) == len(rec_o) == npairs
-    for k, (wo, wg) in enumerate(zip(rec_o, got)):
-        assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8])
 
 
 @pytest.mark.parametrize("stream_id,config", [(0, "c2"), (1, "c2"), (2, "c2"), (0, "c3")],
@@ -691,7 +537,6 @@ def test_full_size_properties(B):
 
 
 # ---- front end: u8 -> x3 -> undistort on the device ----------------------------------------------------
-EUROC_D = [-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.0]  # camera.hpp:31-35
 
 
 def test_front_end_undistort_bit_exact(orc_mod, B, c2_stream):
@@ -703,7 +548,7 @@ def test_front_end_undistort_bit_exact(orc_mod, B, c2_stream):
         for i in (0, 3):
             want = orc.front_end_u8(frames[i], cam.fm, cam.fm, cam.cx, cam.cy, D)
             got = ctx.front_end_u8(frames[i])
-            assert _bits_equal(want, got), f"D={D} frame {i}: {np.abs(want - got).max()}"
+            assert bits_equal(want, got), f"D={D} frame {i}: {np.abs(want - got).max()}"
 
 
 def test_detect_through_device_front_end(orc_mod, B, c2_stream):
@@ -752,8 +597,7 @@ def test_persistent_lm_kernel_equals_per_call_kernels(B, c2_stream, monkeypatch)
     frames, cam = c2_stream
 
     def run(mode, threads):
-        monkeypatch.setenv("REBVIO_HIP_LM", mode)
-        monkeypatch.setenv("REBVIO_HIP_LM_THREADS", str(threads))
+        set_forms(monkeypatch, lm=mode, threads=threads)
         ctx = B.Context(params_for(B, cam, **KW_C2))
         maps = [ctx.detect_u8(frames[i], i * 50000) for i in range(len(frames))]
         outs = [pair_tuple(ctx.track_pair(maps[i - 1], maps[i])) for i in range(1, len(frames))]
@@ -789,10 +633,7 @@ def test_device_glue_equals_host_glue(B, c2_stream, monkeypatch):
     order = list(range(n)) + list(range(n - 2, -1, -1)) + list(range(1, n))
     npx = cam.width * cam.height
     for head in ("", "compact1"):
-        if head:
-            monkeypatch.setenv("REBVIO_HIP_DM_HEAD", head)
-        else:
-            monkeypatch.delenv("REBVIO_HIP_DM_HEAD", raising=False)
+        set_forms(monkeypatch, head=head or None)
         ctx = B.Context(params_for(B, cam, **KW_C2))
         dev = ctx.upload_frames(frames)
         maps = [ctx.detect_u8_device(dev + int(i) * npx, k * 50000) for k, i in enumerate(order)]
@@ -890,7 +731,7 @@ def test_speculative_lm_kernel_rolls_back_when_a_later_step_is_accepted(B, monke
     streams = [synth.render_stream(640, 480, 12, stream_id=sid) for sid in (0, 1)]
 
     def run(mode):
-        monkeypatch.setenv("REBVIO_HIP_LM", mode)   # read when the context is created
+        set_forms(monkeypatch, lm=mode)   # read when the context is created
         res = {}
         for sid, variant, kw in [(sid, v, kw) for sid in (0, 1) for v, kw in (("default", {}), ("sr10", dict(search_range=10.0)),
                                                                             ("it7", dict(iterations=7)), ("it3", dict(iterations=3)))]:
@@ -921,20 +762,8 @@ def test_speculative_lm_kernel_rolls_back_when_a_later_step_is_accepted(B, monke
             if k[1] == "it3" and which == "spec3":
                 continue  # (three iterations leave one evaluation behind index 3: that context runs the sequential kernel)
             assert x[k][0] == b[k][0], (which, k)
-            assert _bits_equal(x[k][1], b[k][1]), (which, k)
-            assert np.array_equal(x[k][2], b[k][2]) and _bits_equal(x[k][3], b[k][3]), (which, k)
-
-
-def _vision_only_fusion(mid):
-    """rebvio.cpp:195-203,225-233 without the inertial filter, in numpy (only has to be the SAME in every call order below)."""
-    from scipy.spatial.transform import Rotation
-    Xgv = np.array(mid.Xgv, np.float64)
-    R = np.array(mid.R, np.float64).reshape(3, 3)
-    R0 = Rotation.from_rotvec(Xgv[3:]).as_matrix()
-    R = (R0 @ R.T).T
-    V = R0 @ np.array(mid.Vg, np.float64) + Xgv[:3]
-    P = np.linalg.inv(np.array(mid.W_Xgv, np.float64).reshape(6, 6))[:3, :3]
-    return V.astype(np.float32), P.astype(np.float32), R.astype(np.float32), R0.astype(np.float32)
+            assert bits_equal(x[k][1], b[k][1]), (which, k)
+            assert np.array_equal(x[k][2], b[k][2]) and bits_equal(x[k][3], b[k][3]), (which, k)
 
 
 def test_pair_halves_report_the_same_counters_in_every_call_order(B, c2_stream):
@@ -957,20 +786,20 @@ def test_pair_halves_report_the_same_counters_in_every_call_order(B, c2_stream):
                     res.append(ctx.track_pair_result())
                 if hint and k + 2 < n:
                     ctx.track_pair_hint_next(maps[k + 2])
-                ctx.track_pair_finish_async(maps[k], maps[k + 1], *_vision_only_fusion(mid))
+                ctx.track_pair_finish_async(maps[k], maps[k + 1], *vision_only_fusion(mid))
                 pending = True
             res.append(ctx.track_pair_result())
         elif order == "serial":        # begin(k), finish_async(k), result(k): _result copies
             for k in range(n - 1):
                 mid = ctx.track_pair_begin(maps[k], maps[k + 1])
-                ctx.track_pair_finish_async(maps[k], maps[k + 1], *_vision_only_fusion(mid))
+                ctx.track_pair_finish_async(maps[k], maps[k + 1], *vision_only_fusion(mid))
                 res.append(ctx.track_pair_result())
         else:                          # every other pair restarts from fresh maps: _begin queues the copy
             for k in range(0, n - 1, 2):
                 mid = ctx.track_pair_begin(maps[k], maps[k + 1])
                 if res or k:
                     res.append(ctx.track_pair_result())
-                ctx.track_pair_finish_async(maps[k], maps[k + 1], *_vision_only_fusion(mid))
+                ctx.track_pair_finish_async(maps[k], maps[k + 1], *vision_only_fusion(mid))
             res.append(ctx.track_pair_result())
         kl = maps[n - 1].keylines() if order != "disjoint" else maps[n - 1 - (n % 2)].keylines()
         for m in maps:
@@ -991,7 +820,7 @@ def test_pair_halves_report_the_same_counters_in_every_call_order(B, c2_stream):
     maps = [ctx.detect_u8(frames[i], i * 50000) for i in range(n)]
     for k in range(0, n - 1, 2):
         mid = ctx.track_pair_begin(maps[k], maps[k + 1])
-        ctx.track_pair_finish_async(maps[k], maps[k + 1], *_vision_only_fusion(mid))
+        ctx.track_pair_finish_async(maps[k], maps[k + 1], *vision_only_fusion(mid))
         e.append(ctx.track_pair_result())
     for m in maps:
         m.release()
@@ -1003,7 +832,7 @@ def test_pair_halves_report_the_same_counters_in_every_call_order(B, c2_stream):
     maps = [ctx.detect_u8(frames[i], i * 50000) for i in range(n)]
     for k in range(0, n - 1, 2):
         mid = ctx.track_pair_begin(maps[k], maps[k + 1])
-        ctx.track_pair_finish_async(maps[k], maps[k + 1], *_vision_only_fusion(mid))
+        ctx.track_pair_finish_async(maps[k], maps[k + 1], *vision_only_fusion(mid))
         maps[k + 1].release()
         maps[k].release()
         f.append(ctx.track_pair_result())
@@ -1021,10 +850,7 @@ def test_streaming_records_do_not_depend_on_the_lm_kernel_choice(B, c2_stream, m
     npx = cam.width * cam.height
 
     def run(mode):
-        if mode is None:
-            monkeypatch.delenv("REBVIO_HIP_LM", raising=False)
-        else:
-            monkeypatch.setenv("REBVIO_HIP_LM", mode)
+        set_forms(monkeypatch, lm=mode)
         ctx = B.Context(params_for(B, cam, **KW_C2))
         dev = ctx.upload_frames(frames)
         rec = [(o.status, o.lm_accept_mask, tuple(o.Vg), tuple(o.Xv), o.klm_num, o.reg_num, n) for o, n in run_stream(ctx, dev, order, npx)]
@@ -1123,19 +949,9 @@ def test_streaming_results_do_not_depend_on_pipeline_depth(B, c2_stream, monkeyp
     npx = cam.width * cam.height
 
     def run(lead, group, prio=None, stamps=False, extra=None):
-        monkeypatch.setenv("REBVIO_HIP_LEAD", str(lead))
-        monkeypatch.setenv("REBVIO_HIP_GROUP", str(group))
-        monkeypatch.delenv("REBVIO_HIP_GYRO_PRE", raising=False)
-        for name, val in (extra or {}).items():
-            monkeypatch.setenv(name, val)
-        if prio:
-            monkeypatch.setenv("REBVIO_HIP_PRIO", prio)
-        else:
-            monkeypatch.delenv("REBVIO_HIP_PRIO", raising=False)
-        if stamps:
-            monkeypatch.setenv("REBVIO_HIP_LM_STAMPS", "1")
-        else:
-            monkeypatch.delenv("REBVIO_HIP_LM_STAMPS", raising=False)
+        env = dict(REBVIO_HIP_LEAD=lead, REBVIO_HIP_GROUP=group, REBVIO_HIP_GYRO_PRE=None, REBVIO_HIP_PRIO=prio or None,
+                   REBVIO_HIP_LM_STAMPS="1" if stamps else None)
+        set_forms(monkeypatch, **dict(env, **(extra or {})))
         ctx = B.Context(params_for(B, cam, **KW_C2))
         dev = ctx.upload_frames(frames)
         rec = [pair_tuple(o, n) for o, n in run_stream(ctx, dev, order, npx)]
@@ -1367,12 +1183,12 @@ def test_prior_promise_broken_is_reported(B, c2_stream):
     a = 0.002
     Rn = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]], np.float32)
     mid = ctx.track_pair_begin(maps[0], maps[1])
-    ctx.track_pair_finish_async(maps[0], maps[1], *_vision_only_fusion(mid), R_prior_next=Rn)
+    ctx.track_pair_finish_async(maps[0], maps[1], *vision_only_fusion(mid), R_prior_next=Rn)
     assert ctx.track_pair_result()[3] == 0
     with pytest.raises(B.HipError, match="R_prior"):
         ctx.track_pair_begin(maps[1], maps[2], R_prior=np.eye(3, dtype=np.float32))
     mid = ctx.track_pair_begin(maps[1], maps[2], R_prior=Rn)     # the promised prior: accepted
-    ctx.track_pair_finish_async(maps[1], maps[2], *_vision_only_fusion(mid), R_prior_next=Rn)
+    ctx.track_pair_finish_async(maps[1], maps[2], *vision_only_fusion(mid), R_prior_next=Rn)
     assert ctx.track_pair_result()[3] == 0
     bg, w = ctx.gyro_state()
     ctx.set_gyro_state(bg + np.float32(1e-3), w)                  # a re-initialised bias between the pairs
@@ -1462,12 +1278,9 @@ def test_batched_lanes_equal_stand_alone_streams(B, c2_stream, monkeypatch, L, e
     n = 36
     streams = [c2_stream[0]] + [synth.render_stream(cam.width, cam.height, 8, stream_id=s)[0] for s in range(1, L)]
     order = synth.pingpong_indices(8, n)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_forms(monkeypatch, **env)
     got = _batch_records(B, cam, streams, order)
-    for k in env:
-        if k.startswith("REBVIO_HIP_BATCH"):
-            monkeypatch.delenv(k)
+    set_forms(monkeypatch, **{k: None if k.startswith("REBVIO_HIP_BATCH") else v for k, v in env.items()})
     want = [_stand_alone_records(B, cam, streams[s], order) for s in range(L)]
     for s in range(L):
         assert len(want[s]) == n - 1 == len(got[s]), (s, len(got[s]), len(want[s]))
@@ -1498,10 +1311,10 @@ def test_batched_lanes_are_bit_identical_to_the_oracle_with_the_sums_in_one_orde
         outs, _ = bat.push_u8_device([d + int(i) * npx for d in devs], k * 50000)
         for s in range(L):
             if outs[s].status >= 0:
-                got[s].append(_record_words(outs[s]))
+                got[s].append(record_words(outs[s]))
     for outs, _ in bat.flush():
         for s in range(L):
-            got[s].append(_record_words(outs[s]))
+            got[s].append(record_words(outs[s]))
     bat.close()
     for s in range(L):
         orc = orc_mod.Oracle(params_for(orc_mod, cam, **KW_C2))
@@ -1513,7 +1326,7 @@ def test_batched_lanes_are_bit_identical_to_the_oracle_with_the_sums_in_one_orde
             else:
                 m = orc.detect(orc.front_end_u8(streams[s][i], cam.fm, cam.fm, cam.cx, cam.cy, lens), k * 50000)
             if prev is not None:
-                want.append(_record_words(orc.track_pair(prev, m)))
+                want.append(record_words(orc.track_pair(prev, m)))
             prev = m
         assert len(got[s]) == len(want) == n - 1
         for k, (wo, wg) in enumerate(zip(want, got[s])):

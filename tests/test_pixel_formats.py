@@ -7,12 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
-INC = ["-I", os.path.join(ROOT, "include")]
-
-GRAY8, RGB8, BGR8, RGBA8, BGRA8, YUYV, UYVY = range(7)
-BPP = (1, 3, 3, 4, 4, 2, 2)
+from support import BGR8, BGRA8, BPP, BUILD, GRAY8, INC, RGB8, RGBA8, ROOT, UYVY, YUYV
 
 
 def luma(r, g, b):

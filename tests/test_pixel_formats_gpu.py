@@ -12,55 +12,13 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_parity_gpu import EUROC_D, KW_C2, _bits_equal, _record_words, assert_keylines_equal
+from support import B, host_lib  # noqa: F401
+from support import (BGR8, BPP, EUROC_D, INC, KW_C2, NAMES, RGB8, RGBA8, ROOT, UYVY, YUYV, assert_keylines_equal, bits_equal, c2_order,
+                     colourise, rec)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
-INC = ["-I", os.path.join(ROOT, "include")]
-GRAY8, RGB8, BGR8, RGBA8, BGRA8, YUYV, UYVY = range(7)
 FMTS = list(range(7))
-NAMES = ["GRAY8", "RGB8", "BGR8", "RGBA8", "BGRA8", "YUYV", "UYVY"]
-BPP = (1, 3, 3, 4, 4, 2, 2)
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as test_parity_gpu.py: torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
-
-
-def luma(rgb):
-    r, g, b = (rgb[..., k].astype(np.int64) for k in range(3))
-    return ((r * 4899 + g * 9617 + b * 1868 + 8192) >> 14).astype(np.uint8)
-
-
-def colourise(grey, seed):
-    """grey [n, H, W] -> {fmt: (frames [n, H, W, bpp] or [n, H, W], the grey frames the grey path gets)}"""
-    rng = np.random.default_rng(seed)
-    n, H, W = grey.shape
-    g = grey.astype(np.int16)
-    yy, xx = np.mgrid[0:H, 0:W]
-    smooth = (40 * np.sin(xx / 37.0) * np.cos(yy / 23.0)).astype(np.int16)             # smooth chroma
-    rgb = np.stack([g + rng.integers(-40, 41, g.shape, dtype=np.int16),                 # random per-pixel chroma
-                    g + smooth[None],
-                    g - smooth[None] + rng.integers(-25, 26, g.shape, dtype=np.int16)], -1)
-    rgb = np.clip(rgb, 0, 255).astype(np.uint8)
-    alpha = rng.integers(0, 256, (n, H, W, 1), dtype=np.uint8)
-    grey_rgb = luma(rgb)
-    chroma = rng.integers(0, 256, (n, H, W), dtype=np.uint8)
-    return {
-        GRAY8: (grey, grey),
-        RGB8: (rgb, grey_rgb),
-        BGR8: (np.ascontiguousarray(rgb[..., ::-1]), grey_rgb),
-        RGBA8: (np.concatenate([rgb, alpha], -1), grey_rgb),
-        BGRA8: (np.concatenate([rgb[..., ::-1], alpha], -1), grey_rgb),
-        YUYV: (np.stack([grey, chroma], -1), grey),      # bytes Y0 U Y1 V
-        UYVY: (np.stack([chroma, grey], -1), grey),      # bytes U Y0 V Y1
-    }
 
 
 @pytest.fixture(scope="module")
@@ -85,8 +43,8 @@ def _stream_words(ctx, push, order):
     for k, i in enumerate(order):
         out, n = push(k, int(i))
         if out.status >= 0:
-            got.append(np.append(_record_words(out), np.uint32(n)))
-    got.extend(np.append(_record_words(o), np.uint32(n)) for o, n in ctx.flush())
+            got.append(rec(out, n))
+    got.extend(rec(o, n) for o, n in ctx.flush())
     return got, ctx.detector_state()
 
 
@@ -95,7 +53,7 @@ def _assert_same_stream(want, got, what):
     assert len(rw) == len(rg), (what, len(rw), len(rg))
     for k, (a, b) in enumerate(zip(rw, rg)):
         assert np.array_equal(a, b), (what, k, np.flatnonzero(a != b)[:8])
-    assert all(_bits_equal(np.float32(a), np.float32(b)) for a, b in zip(sw, sg)), (what, sw, sg)
+    assert all(bits_equal(np.float32(a), np.float32(b)) for a, b in zip(sw, sg)), (what, sw, sg)
     assert rw[-1][-1] > 1000 and any(w[0] != 0 for w in rw), what   # a real stream: keylines and motion
 
 
@@ -110,11 +68,6 @@ def _grey_stream(B, cam, grey, order, dist=None):
     return r
 
 
-def _order():
-    from rebvio_amd import synth
-    return synth.pingpong_indices(8, 16)
-
-
 @pytest.mark.parametrize("lens", [False, True], ids=["pinhole", "radtan"])
 @pytest.mark.parametrize("fmt", FMTS, ids=NAMES)
 def test_streaming_device_frames_equal_the_grey_stream(B, px_stream, fmt, lens):
@@ -122,7 +75,7 @@ def test_streaming_device_frames_equal_the_grey_stream(B, px_stream, fmt, lens):
     (the front end's gather converts each of its four taps)."""
     px, cam = px_stream
     frames, grey = px[fmt]
-    order = _order()
+    order = c2_order()
     dist = EUROC_D if lens else None
     want = _grey_stream(B, cam, grey, order, dist)
     ctx = B.Context(params_for(B, cam, **KW_C2))
@@ -141,7 +94,7 @@ def test_streaming_host_frames_with_a_padded_pitch(B, px_stream, fmt):
     after each push, == the grey stream."""
     px, cam = px_stream
     frames, grey = px[fmt]
-    order = _order()
+    order = c2_order()
     want = _grey_stream(B, cam, grey, order)
     rng = np.random.default_rng(fmt)
     ctx = B.Context(params_for(B, cam, **KW_C2))
@@ -169,9 +122,9 @@ def test_front_end_px_equals_the_grey_front_end(B, px_stream, fmt):
         ctx.set_undistort(cam.fm, cam.fm, cam.cx, cam.cy, D)
         for i in (0, 5):
             want = ctx.front_end_u8(grey[i])
-            assert _bits_equal(want, ctx.front_end_px(frames[i], fmt)), (NAMES[fmt], D, i)
+            assert bits_equal(want, ctx.front_end_px(frames[i], fmt)), (NAMES[fmt], D, i)
             view, _ = _padded(frames[i], 20, rng)
-            assert _bits_equal(want, ctx.front_end_px(view, fmt)), (NAMES[fmt], D, i, "padded")
+            assert bits_equal(want, ctx.front_end_px(view, fmt)), (NAMES[fmt], D, i, "padded")
     ctx.close()
 
 
@@ -221,7 +174,7 @@ def test_format_changes_every_frame_host_and_device_mixed(B, px_stream, lens):
     """5: one stream, frame k in format k mod 7, host (padded) and device frames alternating: the records of the all-grey
     stream. A colour host frame after grey ones changes the device staging frame it goes through, mid-stream."""
     px, cam = px_stream
-    order = _order()
+    order = c2_order()
     fmts = [k % 7 for k in range(len(order))]
     dist = EUROC_D if lens else None
     ref = B.Context(params_for(B, cam, **KW_C2))
@@ -277,7 +230,7 @@ def test_batch_px_rotating_formats(B, lens):
         def take(outs, ns):
             for l in range(L):
                 if outs[l].status >= 0:
-                    recs[l].append(np.append(_record_words(outs[l]), np.uint32(ns[l])))
+                    recs[l].append(rec(outs[l], ns[l]))
 
         for k, i in enumerate(order):
             f = fmts[k]
@@ -358,13 +311,6 @@ def test_px_entries_refuse_bad_arguments(B, px_stream):
     assert m.size() > 1000
     m.release()
     ctx.close()
-
-
-@pytest.fixture(scope="module")
-def host_lib():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "csrc")], check=True)
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "host")], check=True)
-    return BUILD
 
 
 def _read_edge_frames(path):

@@ -1,4 +1,4 @@
-"""Point clouds without a GPU: the numpy restatement the GPU tests compare against (tests/test_point_cloud_gpu.py: np_cloud),
+"""Point clouds without a GPU: the numpy restatement the GPU tests compare against (tests/support.py: np_cloud),
 checked against hand-computed cases, and the PLY writer of rebvio::io round-tripped through tests/cpp/test_point_cloud_ply.cpp."""
 import os
 import subprocess
@@ -6,11 +6,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_point_cloud_gpu import CLOUD_DTYPE, np_cloud, np_passes
+from support import BUILD, CLOUD_DTYPE, F32, ROOT, np_cloud, np_passes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
-F32 = np.float32
 OPEN = (0, 1.0, 1e-3, 20.0)
 
 

@@ -1,7 +1,7 @@
 """The point cloud of a map's depth-bearing keylines (rebvio_hip_map_point_cloud / _async) on the GPU.
 
-The expected cloud is always np_cloud() below - a numpy fp32 restatement of the definition in include/rebvio_hip.h, every
-operation one rounded fp32 operation in the header's order - applied to Map.keylines() downloaded immediately before the
+The expected cloud is always np_cloud() of tests/support.py - a numpy fp32 restatement of the definition in include/rebvio_hip.h,
+every operation one rounded fp32 operation in the header's order - applied to Map.keylines() downloaded immediately before the
 extraction: the code under test never produces its own expectation. tests/test_point_cloud.py checks np_cloud() itself against
 hand-computed cases."""
 import ctypes as C
@@ -10,58 +10,12 @@ import numpy as np
 import pytest
 
 from conftest import params_for
+from support import B  # noqa: F401
+from support import CLOUD_DTYPE, F32, KW_C2, enlarged_stream, np_cloud, np_passes, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-KW_C2 = dict(keylines_ref=15000, keylines_max=16000)   # the bench configuration of the 640x480 stream
 KW_SMALL = dict(keylines_ref=2000, keylines_max=3000)
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
-
-
-# ---- the definition, in numpy ---------------------------------------------------------------------------------------
-CLOUD_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("rho", "<f4"), ("sigma_rho", "<f4"), ("gradient_norm", "<f4"),
-                        ("keyline", "<i4"), ("matches", "<u4")])
-IDENTITY = (np.eye(3, dtype=F32), np.zeros(3, F32), F32(1.0))
-
-
-def np_passes(kl, min_matches, max_rel_sigma, rho_min, rho_max):
-    """The filter: positive tests (a NaN fails them); sigma_rho <= max_rel_sigma * rho with one rounded fp32 multiply."""
-    rho, sig = kl["rho"].astype(F32), kl["sigma_rho"].astype(F32)
-    with np.errstate(all="ignore"):
-        bound = (F32(max_rel_sigma) * rho).astype(F32)
-        return (kl["matches"] >= np.uint32(min_matches)) & (rho >= F32(rho_min)) & (rho <= F32(rho_max)) & (sig <= bound)
-
-
-def np_cloud(kl, fm, flt, pose=None):
-    """flt = (min_matches, max_rel_sigma, rho_min, rho_max); pose = (R[3, 3], t[3], scale) or None. Returns CLOUD_DTYPE records in
-    ascending keyline index."""
-    R, t, scale = IDENTITY if pose is None else pose
-    R = np.asarray(R, F32).reshape(9)
-    t = np.asarray(t, F32).reshape(3)
-    idx = np.flatnonzero(np_passes(kl, *flt))
-    k = kl[idx]
-    out = np.zeros(len(idx), CLOUD_DTYPE)
-    fm = F32(fm)
-    with np.errstate(all="ignore"):
-        u = (k["pos_img"][:, 0].astype(F32) / fm).astype(F32)
-        v = (k["pos_img"][:, 1].astype(F32) / fm).astype(F32)
-        z = (F32(scale) / k["rho"].astype(F32)).astype(F32)
-        xc, yc = (u * z).astype(F32), (v * z).astype(F32)
-        for i in range(3):
-            a = ((R[3 * i] * xc).astype(F32) + (R[3 * i + 1] * yc).astype(F32)).astype(F32)
-            b = (a + (R[3 * i + 2] * z).astype(F32)).astype(F32)
-            out["xyz"][:, i] = (b + t[i]).astype(F32)
-    out["rho"], out["sigma_rho"], out["gradient_norm"] = k["rho"], k["sigma_rho"], k["gradient_norm"]
-    out["keyline"], out["matches"] = idx, k["matches"]
-    return out
 
 
 def assert_cloud_equal(got, want, what):
@@ -97,23 +51,6 @@ def crafted(kl, seed):
     kl["rho"] = np.exp(rng.uniform(np.log(2e-3), np.log(15.0), n)).astype(F32)
     kl["sigma_rho"] = (kl["rho"] * rng.uniform(0.0, 1.0, n).astype(F32)).astype(F32)
     return kl
-
-
-def vision_only_fusion(mid):
-    """rebvio.cpp:195-203,225-233 without the inertial filter, in numpy (it only has to be the same in every run compared)."""
-    Xgv = np.array(mid.Xgv, np.float64)
-    R = np.array(mid.R, np.float64).reshape(3, 3)
-    w = Xgv[3:]
-    th = np.linalg.norm(w)
-    if th > 0:
-        K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / th
-        R0 = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
-    else:
-        R0 = np.eye(3)
-    R = (R0 @ R.T).T
-    V = R0 @ np.array(mid.Vg, np.float64) + Xgv[:3]
-    P = np.linalg.inv(np.array(mid.W_Xgv, np.float64).reshape(6, 6))[:3, :3]
-    return V.astype(F32), P.astype(F32), R.astype(F32), R0.astype(F32)
 
 
 # ---- 1: a tracked map ---------------------------------------------------------------------------------------------------
@@ -233,17 +170,6 @@ def test_small_and_odd_map_sizes(B, small_stream, kmax):
     assert len(q.wait()) == 0
     q.release()
     ctx.close()
-
-
-def enlarged_stream(width, height, n, factor=4):
-    """n frames of the synthetic stream rendered at 1/factor of the size and enlarged (every pixel a factor x factor block); the
-    camera of the enlarged frames."""
-    from rebvio_amd import synth
-    qw, qh = -(-width // factor), -(-height // factor)
-    small, qcam = synth.render_stream(qw, qh, n)
-    big = np.kron(small, np.ones((1, factor, factor), np.uint8))[:, :height, :width]
-    off = 0.5 * (factor - 1)
-    return np.ascontiguousarray(big), synth.Camera(width, height, qcam.fm * factor, qcam.cx * factor + off, qcam.cy * factor + off)
 
 
 def test_a_map_that_fills_the_keyline_envelope(B):

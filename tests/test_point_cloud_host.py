@@ -7,18 +7,11 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "rebvio_amd", "_build")
+from support import host_lib  # noqa: F401
+from support import ROOT
+
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def host_lib():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "csrc")], check=True)
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "host")], check=True)
-    assert os.path.exists(os.path.join(BUILD, "librebvio.so"))
-    return BUILD
 
 
 def _write_imu(path, ts, gyro, acc):

@@ -2,18 +2,11 @@
 rebvio_hip_gyro_integrate - one step of IntegratedImu::add (types/imu.hpp:72), R <- R * exp(gyro * dt) - follows a float64
 Rodrigues product."""
 import ctypes
-import os
 
 import numpy as np
-import pytest
 
-
-@pytest.fixture(scope="module")
-def backend():
-    from rebvio_amd import backend as B
-    if not os.path.exists(B.LIB_PATH):
-        B.build()
-    return B
+from support import backend  # noqa: F401
+from support import rodrigues
 
 
 NEW_SYMBOLS = ("rebvio_hip_push_frame_px_gyro_device", "rebvio_hip_push_frame_px_gyro", "rebvio_hip_batch_push_px_gyro_device",
@@ -29,15 +22,6 @@ def test_gyro_entries_are_exported_and_bound(backend):
     for name in ("push_frame_px_gyro_device", "push_frame_px_gyro"):
         assert callable(getattr(backend.Context, name))
     assert callable(backend.Batch.push_px_gyro_device) and callable(backend.gyro_integrate)
-
-
-def rodrigues(w):
-    w = np.asarray(w, np.float64)
-    th = np.sqrt((w * w).sum())
-    if th == 0:
-        return np.eye(3)
-    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]], np.float64)
-    return np.eye(3) + (np.sin(th) / th) * K + ((1 - np.cos(th)) / (th * th)) * (K @ K)
 
 
 def test_gyro_integrate_follows_a_float64_rodrigues_product(backend):

@@ -12,72 +12,15 @@ import numpy as np
 import pytest
 
 from conftest import params_for
+from support import B  # noqa: F401
+from support import TS, gyro_rotations, rec, record_words, rodrigues, same_records, set_forms, state_words
 
 pytestmark = pytest.mark.gpu
 
-TS = 50000                       # microseconds between frames: frame_dt = 0.05 on both APIs
 STREAMS = {                      # fixture, ping-pong order (base, total), the oracle's smallest klm_num over the stream's pairs
     "small": ("small_stream", (12, 16), 2321),
     "c2": ("c2_stream", (8, 13), 9726),
 }
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as test_parity_gpu.py: torch's HIP runtime loaded first, like the bench process)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
-
-
-def _record_words(po):
-    """every field of a pair record as raw 32-bit words (floats by their bits; a NaN is a NaN)"""
-    out = []
-    for name, _ in type(po)._fields_:
-        v = getattr(po, name)
-        a = np.array(v) if hasattr(v, "__len__") else np.array([v])
-        if a.dtype.kind == "f":
-            a = a.astype(np.float32)
-            a[np.isnan(a)] = np.float32(np.nan)
-            out.append(a.view(np.uint32))
-        else:
-            out.append(a.astype(np.int64).astype(np.uint32))
-    return np.concatenate(out)
-
-
-def _rec(out, n):
-    return np.append(_record_words(out), np.uint32(n))
-
-
-def _same(a, b, what):
-    assert len(a) == len(b), (what, len(a), len(b))
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(x, y), (what, k, np.flatnonzero(x != y)[:8])
-
-
-def _state_words(st):
-    return np.concatenate([np.asarray(st[0], np.float32).view(np.uint32), np.asarray(st[1], np.float32).reshape(-1).view(np.uint32)])
-
-
-def rodrigues(w):
-    w = np.asarray(w, np.float64)
-    th = np.sqrt((w * w).sum())
-    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]], np.float64)
-    return np.eye(3) + (np.sin(th) / th) * K + ((1 - np.cos(th)) / (th * th)) * (K @ K)
-
-
-def gyro_rotations(order, seed, stream_id=0):
-    """One rotation per frame of order[]: [k] spans frame order[k-1] -> order[k]. [0] belongs to no pair (the drivers ignore a
-    first frame's rotation): a rotation of its own, far from the identity, so that using it anywhere shows."""
-    from rebvio_amd import synth
-    scene = synth.make_scene(stream_id, 1.0)
-    rng = np.random.Generator(np.random.PCG64(seed))
-    out = [rodrigues([0.3, -0.2, 0.1]).astype(np.float32)]
-    for i, j in zip(order[:-1], order[1:]):
-        Ri, Rj = synth.pose(scene, int(i))[0], synth.pose(scene, int(j))[0]
-        w = rng.uniform(-0.004, 0.004, 3)
-        out.append(((Ri.T @ Rj).T @ rodrigues(w)).astype(np.float32))
-    return out
 
 
 # ---- the three runners: oracle, per-pair API, streaming driver ----------------------------------------------------------------
@@ -109,10 +52,10 @@ def lib_pairs(B, cam, seq, R, mask=None, **kw):
         if len(maps) > 2:
             maps.pop(0).release()
         if k:
-            recs.append(_rec(ctx.track_pair(maps[0], maps[1], R_prior=R[k]), maps[1].size()))
+            recs.append(rec(ctx.track_pair(maps[0], maps[1], R_prior=R[k]), maps[1].size()))
     st = ctx.gyro_state()
     ctx.close()
-    return recs, _state_words(st)
+    return recs, state_words(st)
 
 
 def lib_stream(B, cam, seq, R, mask=None, host=False, flush_after=(), entry="gyro", profile=False, **kw):
@@ -135,11 +78,11 @@ def lib_stream(B, cam, seq, R, mask=None, host=False, flush_after=(), entry="gyr
         else:
             out, n = ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, R[k], mdev, k * TS)
         if out.status >= 0:
-            recs.append(_rec(out, n))
+            recs.append(rec(out, n))
         if k + 1 in flush_after:
-            recs.extend(_rec(o, n) for o, n in ctx.flush())
-    recs.extend(_rec(o, n) for o, n in ctx.flush())
-    st = _state_words(ctx.gyro_state())
+            recs.extend(rec(o, n) for o, n in ctx.flush())
+    recs.extend(rec(o, n) for o, n in ctx.flush())
+    st = state_words(ctx.gyro_state())
     launches = None
     if profile:
         launches = {name: calls for name, (_, calls) in ctx.profile_read().items()}
@@ -168,7 +111,7 @@ def case(request, orc_mod, B, name):
             assert po.status == 0 and po.klm_num >= min_klm and po.klm_num >= gate, (name, k, po.status, po.klm_num)
             assert not np.array_equal(np.array(po.R, np.float32).view(np.uint32), np.array(pn.R, np.float32).view(np.uint32)), (name, k)
         pairs, state = lib_pairs(B, cam, seq, R)
-        _cache[name] = dict(cam=cam, seq=seq, order=order, R=R, oracle=[_rec(po, n) for po, n in with_prior], pairs=pairs, state=state)
+        _cache[name] = dict(cam=cam, seq=seq, order=order, R=R, oracle=[rec(po, n) for po, n in with_prior], pairs=pairs, state=state)
     return _cache[name]
 
 
@@ -176,9 +119,9 @@ def case(request, orc_mod, B, name):
 @pytest.mark.parametrize("name", ["small", "c2"])
 def test_oracle_per_pair_api_and_gyro_stream_are_bit_identical(request, orc_mod, B, name):
     c = case(request, orc_mod, B, name)
-    _same(c["oracle"], c["pairs"], f"{name}: oracle vs track_pair(R_prior)")
+    same_records(c["oracle"], c["pairs"], f"{name}: oracle vs track_pair(R_prior)")
     got, st = lib_stream(B, c["cam"], c["seq"], c["R"])
-    _same(c["pairs"], got, f"{name}: track_pair(R_prior) vs push_frame_px_gyro_device")
+    same_records(c["pairs"], got, f"{name}: track_pair(R_prior) vs push_frame_px_gyro_device")
     assert np.array_equal(st, c["state"]), (name, st, c["state"])
     assert np.abs(c["state"][:3].view(np.float32)).max() > 0     # the bias filter moved
 
@@ -190,10 +133,9 @@ def test_oracle_per_pair_api_and_gyro_stream_are_bit_identical(request, orc_mod,
                          ids=["lead3-group1", "lead5-group4", "lead8-group2", "lead12-group6", "gyro-pre-off", "lm-seq", "lm-spec"])
 def test_gyro_stream_does_not_depend_on_the_pipeline_shape(request, orc_mod, B, monkeypatch, env):
     c = case(request, orc_mod, B, "c2")
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_forms(monkeypatch, **env)
     got, st = lib_stream(B, c["cam"], c["seq"], c["R"])
-    _same(c["pairs"], got, str(env))
+    same_records(c["pairs"], got, str(env))
     assert np.array_equal(st, c["state"])
 
 
@@ -207,7 +149,7 @@ def test_null_and_identity_rotations_equal_the_existing_entry(request, B):
     assert len(want) == len(seq) - 1 and all(w[-2] == 0 for w in want)   # (status: the record's last word, in front of the keyline count)
     for what, R in (("NULL", [None] * len(seq)), ("identity", [eye] * len(seq)), ("alternating", [eye if k % 2 else None for k in range(len(seq))])):
         got, sg, lg = lib_stream(B, cam, seq, R, profile=True)
-        _same(want, got, what)
+        same_records(want, got, what)
         assert np.array_equal(st, sg), what
         assert lg == launches and sum(lg.values()) > 4 * len(seq), (what, lg, launches)   # the same kernel launches per frame
 
@@ -219,11 +161,11 @@ def test_gyro_stream_continues_across_a_flush(request, orc_mod, B, name):
     its own rotation and the host's filter state; the concatenated records are the per-pair records."""
     c = case(request, orc_mod, B, name)
     got, st = lib_stream(B, c["cam"], c["seq"], c["R"], flush_after=(6,))
-    _same(c["pairs"], got, f"{name}: flush after six frames")
+    same_records(c["pairs"], got, f"{name}: flush after six frames")
     assert np.array_equal(st, c["state"])
     if name == "small":   # flushes wherever the pipeline is shallow or full: after the first frame, two in a row, near the end
         got, st = lib_stream(B, c["cam"], c["seq"], c["R"], flush_after=(1, 2, 3, 9, 15))
-        _same(c["pairs"], got, "small: many flushes")
+        same_records(c["pairs"], got, "small: many flushes")
         assert np.array_equal(st, c["state"])
 
 
@@ -241,11 +183,11 @@ def test_rotation_after_a_flush_without_rotations_is_refused(request, B):
         for k in range(6):
             out, n = ctx.push_frame_u8_device(dev + k * npx, k * TS)
             if out.status >= 0:
-                recs.append(_rec(out, n))
-        recs.extend(_rec(o, n) for o, n in ctx.flush())
+                recs.append(rec(out, n))
+        recs.extend(rec(o, n) for o, n in ctx.flush())
         second_half(ctx, dev, recs)
-        recs.extend(_rec(o, n) for o, n in ctx.flush())
-        st = _state_words(ctx.gyro_state())
+        recs.extend(rec(o, n) for o, n in ctx.flush())
+        st = state_words(ctx.gyro_state())
         ctx.close()
         return recs, st
 
@@ -253,7 +195,7 @@ def test_rotation_after_a_flush_without_rotations_is_refused(request, B):
         for k in range(6, len(seq)):
             out, n = ctx.push_frame_u8_device(dev + k * npx, k * TS)
             if out.status >= 0:
-                recs.append(_rec(out, n))
+                recs.append(rec(out, n))
 
     def refused_then_identity(ctx, dev, recs):
         with pytest.raises(B.HipError, match=r"error -7.*R_gyro"):
@@ -261,12 +203,12 @@ def test_rotation_after_a_flush_without_rotations_is_refused(request, B):
         for k in range(6, len(seq)):   # the identity is accepted; the stream behind it may carry rotations again - here: none
             out, n = ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, np.eye(3, dtype=np.float32), None, k * TS)
             if out.status >= 0:
-                recs.append(_rec(out, n))
+                recs.append(rec(out, n))
 
     want, st = run(plain)
     assert len(want) == 5 + 9                        # a stream without rotations ends at its flush, as it always has
     got, sg = run(refused_then_identity)
-    _same(want, got, "identity after a rotation-free flush")
+    same_records(want, got, "identity after a rotation-free flush")
     assert np.array_equal(st, sg)
 
 
@@ -274,7 +216,7 @@ def test_rotation_after_a_flush_without_rotations_is_refused(request, B):
 def test_host_frames_equal_device_frames(request, orc_mod, B):
     c = case(request, orc_mod, B, "small")
     got, st = lib_stream(B, c["cam"], c["seq"], c["R"], host=True)
-    _same(c["pairs"], got, "push_frame_px_gyro (host frames)")
+    same_records(c["pairs"], got, "push_frame_px_gyro (host frames)")
     assert np.array_equal(st, c["state"])
 
 
@@ -284,7 +226,7 @@ def test_per_frame_mask_with_rotations_equals_masked_detect_and_track_pair(reque
     mask = (np.random.default_rng(3).random((cam.height, cam.width)) < 0.7).astype(np.uint8)
     want, st = lib_pairs(B, cam, c["seq"], c["R"], mask=mask)
     got, sg = lib_stream(B, cam, c["seq"], c["R"], mask=mask)
-    _same(want, got, "masked")
+    same_records(want, got, "masked")
     assert np.array_equal(st, sg)
     assert not all(np.array_equal(x, y) for x, y in zip(want, c["pairs"]))   # the mask matters
     assert all(w[-2] == 0 for w in want) and want[-1][-1] > 1000                # ... and the masked stream still tracks
@@ -303,9 +245,9 @@ def test_blank_frame_inside_a_gyro_stream(request, orc_mod, B):
     assert orc[6][1] == 0 and [po.status for po, _ in orc] == [0] * 6 + [1, 1] + [0] * 7
     assert all(po.klm_num >= 2000 for po, _ in orc[8:])          # the pairs behind the blank frame track again
     want, st = lib_pairs(B, cam, seq, R)
-    _same([_rec(po, n) for po, n in orc], want, "oracle vs track_pair(R_prior)")
+    same_records([rec(po, n) for po, n in orc], want, "oracle vs track_pair(R_prior)")
     got, sg = lib_stream(B, cam, seq, R)
-    _same(want, got, "track_pair(R_prior) vs gyro stream")
+    same_records(want, got, "track_pair(R_prior) vs gyro stream")
     assert np.array_equal(st, sg)
 
 
@@ -318,12 +260,12 @@ def test_too_few_matches_in_every_pair_of_a_gyro_stream(request, orc_mod, B):
     orc = oracle_pairs(orc_mod, cam, seq, R, **kw)
     assert [po.status for po, _ in orc] == [2] * (len(seq) - 1) and all(po.klm_num > 1000 for po, _ in orc)
     want, st = lib_pairs(B, cam, seq, R, **kw)
-    _same([_rec(po, n) for po, n in orc], want, "oracle vs track_pair(R_prior)")
+    same_records([rec(po, n) for po, n in orc], want, "oracle vs track_pair(R_prior)")
     got, sg = lib_stream(B, cam, seq, R, **kw)
-    _same(want, got, "track_pair(R_prior) vs gyro stream")
+    same_records(want, got, "track_pair(R_prior) vs gyro stream")
     assert np.array_equal(st, sg)
     got, sg = lib_stream(B, cam, seq, R, flush_after=(5,), **kw)
-    _same(want, got, "with a flush")
+    same_records(want, got, "with a flush")
     assert np.array_equal(st, sg)
 
 
@@ -366,7 +308,7 @@ def test_host_and_device_glue_agree_for_a_next_rotation(B):
             Rn = rodrigues(rng.standard_normal(3) * [0.004, 0.05, 0.5][trial % 3]).astype(np.float32)
             ctx.test_glue_set_next(Rn, has_next)
             (od, sd, gd), (oh, sh, gh) = ctx.test_glue(*args)
-            assert np.array_equal(words(_record_words(od)), words(_record_words(oh))), trial
+            assert np.array_equal(words(record_words(od)), words(record_words(oh))), trial
             assert np.array_equal(words(sd), words(sh)) and np.array_equal(words(gd), words(gh)), trial
             assert gh.view(np.int32)[43] == int(has_next), trial
             R_state, RT_next = sh[12:21].reshape(3, 3), gh[33:42].reshape(3, 3)
@@ -396,7 +338,7 @@ def test_batch_lanes_with_rotations_equal_stand_alone_contexts(B):
         def take(outs, ns):
             for l in range(L):
                 if outs[l].status >= 0:
-                    recs[l].append(_rec(outs[l], ns[l]))
+                    recs[l].append(rec(outs[l], ns[l]))
 
         for k in range(len(order)):
             fr = [devs[l] + k * W * H for l in range(L)]
@@ -406,7 +348,7 @@ def test_batch_lanes_with_rotations_equal_stand_alone_contexts(B):
                 take(*b.push_u8_device(fr, k * TS))
         for outs, ns in b.flush():
             take(outs, ns)
-        states = [_state_words(c.gyro_state()) for c in b.lanes]
+        states = [state_words(c.gyro_state()) for c in b.lanes]
         b.close()
         return recs, states
 
@@ -414,10 +356,10 @@ def test_batch_lanes_with_rotations_equal_stand_alone_contexts(B):
     plain, _ = batch(False)
     for l in range(L):
         want, st = lib_stream(B, cam, seqs[l], rots[l])
-        _same(want, got[l], f"lane {l} vs a stand-alone context")
+        same_records(want, got[l], f"lane {l} vs a stand-alone context")
         assert np.array_equal(st, states[l]), l
         assert len(want) == len(order) - 1 and all(w[-2] == 0 for w in want), l
-    _same(plain[2], got[2], "the lane without rotations vs a lane of the existing batch entry")
+    same_records(plain[2], got[2], "the lane without rotations vs a lane of the existing batch entry")
     assert not all(np.array_equal(x, y) for x, y in zip(plain[0], got[0]))      # ... and the rotations of the others are live
     assert not all(np.array_equal(x, y) for x, y in zip(plain[1], got[1]))
 
@@ -439,7 +381,7 @@ def test_batch_flush_ends_every_lanes_stream(B):
     def take(outs, ns):
         for l in range(L):
             if outs[l].status >= 0:
-                recs[l].append(_rec(outs[l], ns[l]))
+                recs[l].append(rec(outs[l], ns[l]))
 
     for k in range(len(order)):
         take(*b.push_px_gyro_device([devs[l] + k * W * H for l in range(L)], B.PX_GRAY8, [rots[l][k] for l in range(L)], None, k * TS))
@@ -459,15 +401,15 @@ def test_batch_flush_ends_every_lanes_stream(B):
         for k in range(len(order)):
             out, n = ctx.push_frame_px_gyro_device(dev + k * W * H, B.PX_GRAY8, rots[l][k], None, k * TS)
             if out.status >= 0:
-                want.append(_rec(out, n))
+                want.append(rec(out, n))
             if k + 1 == cut:
-                want.extend(_rec(o, n) for o, n in ctx.flush())
+                want.extend(rec(o, n) for o, n in ctx.flush())
                 bg, wbg = ctx.gyro_state()
                 ctx.reset_state()
                 ctx.set_gyro_state(bg, wbg)
-        want.extend(_rec(o, n) for o, n in ctx.flush())
+        want.extend(rec(o, n) for o, n in ctx.flush())
         ctx.close()
-        _same(want, recs[l], f"lane {l}")
+        same_records(want, recs[l], f"lane {l}")
 
 
 # ---- 8. refusals --------------------------------------------------------------------------------------------------------------------------
@@ -494,11 +436,11 @@ def test_non_finite_rotations_are_refused_and_leave_no_trace(request, orc_mod, B
                 ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, Rb, None, k * TS)
         out, n = ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, R[k], None, k * TS)
         if out.status >= 0:
-            got.append(_rec(out, n))
-    got.extend(_rec(o, n) for o, n in ctx.flush())
-    st = _state_words(ctx.gyro_state())
+            got.append(rec(out, n))
+    got.extend(rec(o, n) for o, n in ctx.flush())
+    st = state_words(ctx.gyro_state())
     ctx.close()
-    _same(c["pairs"], got, "stream around refused calls")
+    same_records(c["pairs"], got, "stream around refused calls")
     assert np.array_equal(st, c["state"])
     # the batch entry: refused before any lane is touched, the batch stays usable and in lock-step
     b = B.Batch(params_for(B, cam), 2)
@@ -512,8 +454,8 @@ def test_non_finite_rotations_are_refused_and_leave_no_trace(request, orc_mod, B
     for k in range(len(seq)):
         outs, ns = b.push_px_gyro_device([devs[l] + k * npx for l in range(2)], B.PX_GRAY8, [R[k], R[k]], None, k * TS)
         if outs[1].status >= 0:
-            recs.append(_rec(outs[1], ns[1]))
+            recs.append(rec(outs[1], ns[1]))
     for outs, ns in b.flush():
-        recs.append(_rec(outs[1], ns[1]))
+        recs.append(rec(outs[1], ns[1]))
     b.close()
-    _same(c["pairs"], recs, "batch lane around a refused call")
+    same_records(c["pairs"], recs, "batch lane around a refused call")

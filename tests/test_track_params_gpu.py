@@ -10,28 +10,13 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from test_parity_gpu import (Pair, warm, assert_keylines_equal, assert_pipeline_bit_identical, _record_words,  # noqa: F401
-                             run_stream)
+from support import B  # noqa: F401
+from support import (KW_TRACK, RHO_MAX, RHO_MIN, Pair, assert_keylines_equal, assert_pipeline_bit_identical, f32, matching_stage,
+                     record_words, run_stream, set_forms, set_new_map)
 
 pytestmark = pytest.mark.gpu
 
-KW = dict(keylines_ref=1500, keylines_max=2500, global_min_matches_threshold=1)
-RHO_MIN, RHO_MAX, RHO_INIT = np.float32(1e-3), np.float32(20.0), np.float32(1.0)  # types/keyline.hpp:13-15
-
-
-@pytest.fixture(scope="module")
-def B():
-    import torch  # noqa: F401  (as in test_parity_gpu: torch's HIP runtime first)
-    from rebvio_amd import backend
-    backend.lib()
-    return backend
-
-
-def _head(monkeypatch, head):
-    if head:
-        monkeypatch.setenv("REBVIO_HIP_DM_HEAD", head)
-    else:
-        monkeypatch.delenv("REBVIO_HIP_DM_HEAD", raising=False)
+RHO_INIT = np.float32(1.0)  # types/keyline.hpp:15
 
 
 def cvtt(x):
@@ -61,30 +46,8 @@ def small_rotation(a=0.0007):
     return np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]], np.float32)
 
 
-def matching_stage(O, B, stream, n_warm=3, **kw):
-    """n_warm oracle pairs, then the pair under test up to forwardMatch on the oracle; both sides hold the oracle's maps."""
-    frames, cam = stream
-    P = warm(O, B, frames, cam, n_warm, **dict(KW, **kw))
-    om_old, om_new = P.om
-    P.orc.build_distance_field(om_new)
-    P.ctx.build_distance_field(P.gm[1])
-    ro = P.orc.minimize_vel(om_old)
-    P.orc.forward_match(om_old, om_new)
-    P.sync_gpu_from_oracle()
-    return P, ro
-
-
-def set_new_map(P, kl):
-    """the same crafted array into the newest map of both sides (true size, through rebvio_hip_map_upload)"""
-    assert len(kl) == P.om[1].size()
-    for f, n in (("id_prev", len(kl)), ("id_next", len(kl)), ("match_id", P.om[0].size())):  # (match_id: of the older map)
-        assert (kl[f] >= -1).all() and (kl[f] < n).all(), f
-    P.om[1].set_keylines(kl)
-    P.gm[1].upload(kl)
-
-
 def nan_canonical(kl):
-    """keylines with every NaN of a float field replaced by the one quiet NaN (as _record_words does for records)"""
+    """keylines with every NaN of a float field replaced by the one quiet NaN (as record_words does for records)"""
     kl = kl.copy()
     for f in kl.dtype.names:
         if kl.dtype[f].base.kind == "f":
@@ -135,7 +98,7 @@ def test_long_searches_under_pixel_uncertainty_match(orc_mod, B, small_stream, m
     For pu >= 3 at least 20 such matches are required of the oracle before the library is looked at; with the old bound these
     cases fail (directedMatch's count and match fields differ) for pu 3, 5 and 8 in every form. Then: counts and every keyline
     field of directedMatch, the single-keyline entry on 200 evenly spaced keylines, regularize1Iter and the depth filter."""
-    _head(monkeypatch, head)
+    set_forms(monkeypatch, head=head)
     radius = LONG_RADIUS[pu]
     P, ro = matching_stage(orc_mod, B, small_stream, pixel_uncertainty_match=float(pu))
     om_old, om_new = P.om
@@ -251,7 +214,7 @@ N_FRAMES = 6
 
 def pipeline_kw(cam, over):
     """parameter overrides of a case: the camera entries are given relative to the stream's camera"""
-    kw = dict(KW)
+    kw = dict(KW_TRACK)
     for k, v in over.items():
         if k == "cx_off":
             kw["cx"] = cam.cx + v
@@ -274,13 +237,13 @@ def oracle_run(O, frames, cam, kw, n=N_FRAMES):
         if k:
             po = orc.track_pair(maps[-2], maps[-1])
             status.append(po.status)
-    return _record_words(po), maps[-1].keylines(), status, po.klm_num
+    return record_words(po), maps[-1].keylines(), status, po.klm_num
 
 
 @pytest.fixture(scope="module")
 def default_run(orc_mod, small_stream):
     frames, cam = small_stream
-    return oracle_run(orc_mod, frames, cam, dict(KW))
+    return oracle_run(orc_mod, frames, cam, dict(KW_TRACK))
 
 
 def moved_off_default(run, default_run):
@@ -335,7 +298,7 @@ def test_batch_lanes_equal_stand_alone_streams_with_every_parameter_moved(B, sma
     for s in streams:
         ctx = B.Context(params_for(B, cam, **kw))
         dev = ctx.upload_frames(s)
-        alone.append([(_record_words(o), n) for o, n in run_stream(ctx, dev, order, npx)])
+        alone.append([(record_words(o), n) for o, n in run_stream(ctx, dev, order, npx)])
         ctx.close()
     bat = B.Batch(params_for(B, cam, **kw), 2)
     devs = [bat.lanes[s].upload_frames(streams[s]) for s in range(2)]
@@ -344,10 +307,10 @@ def test_batch_lanes_equal_stand_alone_streams_with_every_parameter_moved(B, sma
         outs, nks = bat.push_u8_device([d + i * npx for d in devs], k * 50000)
         for s in range(2):
             if outs[s].status >= 0:
-                got[s].append((_record_words(outs[s]), nks[s]))
+                got[s].append((record_words(outs[s]), nks[s]))
     for outs, nks in bat.flush():
         for s in range(2):
-            got[s].append((_record_words(outs[s]), nks[s]))
+            got[s].append((record_words(outs[s]), nks[s]))
     bat.close()
     for s in range(2):
         assert len(got[s]) == len(alone[s]) == N_FRAMES - 1
@@ -357,8 +320,6 @@ def test_batch_lanes_equal_stand_alone_streams_with_every_parameter_moved(B, sma
 
 
 # ---- 4. crafted depth states -----------------------------------------------------------------------------------------
-def f32(x):
-    return np.float32(x)
 
 
 def one_ulp_pair(rp, sn, sp):
@@ -546,9 +507,9 @@ def test_crafted_depth_states_through_whole_pairs(orc_mod, B, small_stream):
     350 at kRhoMax, 257 reset behind a zero gradient, 14 sigma_rho > 20, no NaN left."""
     frames, cam = small_stream
     thr = 0.5
-    P = Pair(orc_mod, B, frames, cam, **KW)
+    P = Pair(orc_mod, B, frames, cam, **KW_TRACK)
     P.orc.set_sum_order("device")
-    ctl = orc_mod.Oracle(params_for(orc_mod, cam, **KW))   # the control of the alpha count
+    ctl = orc_mod.Oracle(params_for(orc_mod, cam, **KW_TRACK))   # the control of the alpha count
     ctl.set_sum_order("device")
     cm = [ctl.detect_u8(frames[0], 0)]
     P.detect(0)
@@ -587,7 +548,7 @@ def test_crafted_depth_states_through_whole_pairs(orc_mod, B, small_stream):
     assert po.reg_num - pc.reg_num == len(made["alpha_at"]) == 24, (po.reg_num, pc.reg_num)
     # the library
     pg = P.ctx.track_pair(P.gm[0], P.gm[1])
-    assert np.array_equal(_record_words(po), _record_words(pg)), np.flatnonzero(_record_words(po) != _record_words(pg))[:8]
+    assert np.array_equal(record_words(po), record_words(pg)), np.flatnonzero(record_words(po) != record_words(pg))[:8]
     assert_keylines_equal_nan(ko, P.gm[1].keylines(), what="newest map after the pair on crafted maps")
     # the next pair starts from the histogram the fused kernel has binned
     P.detect(5)
@@ -595,7 +556,7 @@ def test_crafted_depth_states_through_whole_pairs(orc_mod, B, small_stream):
     pg2 = P.ctx.track_pair(P.gm[0], P.gm[1])
     assert po2.status == 0
     assert f32(po2.sigma_rho_min).view(np.uint32) == f32(pg2.sigma_rho_min).view(np.uint32), (po2.sigma_rho_min, pg2.sigma_rho_min)
-    assert np.array_equal(_record_words(po2), _record_words(pg2))
+    assert np.array_equal(record_words(po2), record_words(pg2))
     assert_keylines_equal_nan(P.om[1].keylines(), P.gm[1].keylines(), what="newest map after the following pair")
 
 
@@ -641,7 +602,7 @@ def test_quantile_corners(orc_mod, B, small_stream, corner, bins, pct):
     pct 0, 0.9 and 1. The expected value is worked out from the definition; the oracle is held to it first, then the stand-alone
     entry (a lone lane's loop) and the sigma_rho_min of a pair (the wave form at the head of the LM kernel)."""
     frames, cam = small_stream
-    P = Pair(orc_mod, B, frames, cam, **dict(KW, quantile_cutoff=pct, quantile_num_bins=bins))
+    P = Pair(orc_mod, B, frames, cam, **dict(KW_TRACK, quantile_cutoff=pct, quantile_num_bins=bins))
     P.orc.set_sum_order("device")
     P.detect(0)
     P.detect(1)
@@ -659,5 +620,5 @@ def test_quantile_corners(orc_mod, B, small_stream, corner, bins, pct):
     po = P.orc.track_pair(P.om[0], P.om[1])
     assert f32(po.sigma_rho_min).view(np.uint32) == want.view(np.uint32), (po.sigma_rho_min, want)
     pg = P.ctx.track_pair(P.gm[0], P.gm[1])
-    assert np.array_equal(_record_words(po), _record_words(pg)), (po.sigma_rho_min, pg.sigma_rho_min, po.status, pg.status)
+    assert np.array_equal(record_words(po), record_words(pg)), (po.sigma_rho_min, pg.sigma_rho_min, po.status, pg.status)
     assert_keylines_equal_nan(P.om[1].keylines(), P.gm[1].keylines(), what=f"newest map, {corner} {bins} {pct}")
