@@ -14,8 +14,37 @@
 
 struct rebvio_hip_map;
 struct rebvio_hip_ctx;
+struct rebvio_hip_kf_snapshot;
 
 namespace rebvio {
+
+// A keyframe as it was when the snapshot was taken (EdgeMap::keyframeSnapshot): owns the backend's handle and releases it; the
+// handle's device memory goes with its context at the latest. Move-only.
+class KeyframeSnapshot {
+ public:
+  KeyframeSnapshot() = default;
+  KeyframeSnapshot(rebvio_hip_kf_snapshot* handle, std::shared_ptr<void> keepalive) : keepalive_(std::move(keepalive)), handle_(handle) {}
+  ~KeyframeSnapshot() { reset(); }
+  KeyframeSnapshot(KeyframeSnapshot&& o) noexcept : keepalive_(std::move(o.keepalive_)), handle_(o.handle_) { o.handle_ = nullptr; }
+  KeyframeSnapshot& operator=(KeyframeSnapshot&& o) noexcept {
+    if (this != &o) {
+      reset();
+      keepalive_ = std::move(o.keepalive_);
+      handle_ = o.handle_;
+      o.handle_ = nullptr;
+    }
+    return *this;
+  }
+  KeyframeSnapshot(const KeyframeSnapshot&) = delete;
+  KeyframeSnapshot& operator=(const KeyframeSnapshot&) = delete;
+  void reset();
+  explicit operator bool() const { return handle_ != nullptr; }
+  rebvio_hip_kf_snapshot* handle() const { return handle_; }
+
+ private:
+  std::shared_ptr<void> keepalive_;  // the backend context the handle belongs to (as EdgeMap's)
+  rebvio_hip_kf_snapshot* handle_ = nullptr;
+};
 
 struct EdgeMapConfig {
   types::Float pixel_uncertainty_match{2.0};
@@ -64,6 +93,13 @@ class EdgeMap {
   // (synchronous, from the tracking thread, like pointCloud).
   void markKeyframe();
   std::vector<rebvio::types::KfMatch> keyframeMatches(int kf_size);
+  // keyframeSnapshot keeps this map's keylines as they are now, in its own camera frame (queued on the track stream; take it where
+  // the map is marked). keyframePose(snapshot): this map's pose relative to that keyframe, X_cur = R X_kf + t, estimated on the
+  // device from the correspondences (rebvio_hip_map_keyframe_pose; synchronous, from the tracking thread). guess: the pose to
+  // start from (its R and t; null: the identity), e.g. the previous result.
+  rebvio::KeyframeSnapshot keyframeSnapshot();
+  rebvio::types::KfPose keyframePose(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfPoseOpts& opts = rebvio::types::KfPoseOpts(),
+                                     const rebvio::types::KfPose* guess = nullptr);
 
   // --- backend plumbing (not part of the reference surface) ---
   // `keepalive` owns the backend context the handle belongs to (backend::Session): a map kept by an edge-image consumer

@@ -58,6 +58,16 @@ class Rebvio {
   // without them.
   void requestKeyframe() { keyframe_requested_ = true; }
   void registerKeyframeCallback(std::function<void(uint64_t ts_us, int kf_matches, int keylines)> cb);
+  // addition: the pose of every tracked map relative to the keyframe, X_cur = R X_kf + t in keyframe depth units, estimated on the
+  // device from the keyframe correspondences (EdgeMap::keyframePose; rebvio_hip.h defines it). While a pose callback is registered,
+  // requestKeyframe also snapshots the keyframe right behind its mark (EdgeMap::keyframeSnapshot; the previous snapshot is dropped),
+  // and from that pair on the state-estimation thread computes the new map's pose behind every pair's second half - warm-started
+  // from the previous result, from the identity behind a new snapshot - and publishes it once per odometry record, right after the
+  // keyframe callbacks: the record's stamp and the pose (the keyframe's own record carries the identity). As with a point-cloud
+  // callback the next pair's first rotation is then not fused into this pair's last kernel, and the thread waits for the second
+  // half before it goes on; the odometry does not change by a digit. Without one the thread runs exactly the calls it ran.
+  // Register before the first frame is handed in.
+  void registerKeyframePoseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfPose&)> cb);
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -96,6 +106,7 @@ class Rebvio {
   };
   std::vector<PointCloudCallback> point_cloud_callbacks_;
   std::vector<std::function<void(uint64_t, int, int)>> keyframe_callbacks_;
+  std::vector<std::function<void(uint64_t, const rebvio::types::KfPose&)>> keyframe_pose_callbacks_;
   std::atomic<bool> keyframe_requested_{false};
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };

@@ -46,6 +46,23 @@ struct KfMatch {
 };
 static_assert(sizeof(KfMatch) == 32, "KfMatch must stay layout-compatible with rebvio_hip_kf_match");
 
+// Options and result of EdgeMap::keyframePose, layout-compatible with the C-ABI's rebvio_hip_kf_pose_opts / rebvio_hip_kf_pose
+// (rebvio_hip.h defines every term of the estimate). The defaults are rebvio_hip_default_kf_pose_opts's.
+struct KfPoseOpts {
+  CloudFilter kf_filter;  // applied to the keyframe side of a correspondence
+  double huber_px{2.0};
+  int max_iter{8};        // 0..32; 0: the sums at the guess only
+  int min_used{12};
+};
+static_assert(sizeof(KfPoseOpts) == 32, "KfPoseOpts must stay layout-compatible with rebvio_hip_kf_pose_opts");
+struct KfPose {
+  double R[9]{1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3]{0, 0, 0};  // X_cur = R X_kf + t, in keyframe depth units (1 / rho)
+  double H[36]{}, g[6]{}, cost{0};                        // J' W J, J' W e and the Huber cost at that pose
+  int candidates{0}, used{0}, iterations{0};
+  int status{0};  // 0 ok, 2 H not positive definite, 3 fewer than min_used terms at the first evaluation
+};
+static_assert(sizeof(KfPose) == 55 * 8 + 16, "KfPose must stay layout-compatible with rebvio_hip_kf_pose");
+
 // What a point-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
   uint64_t ts_us;            // the odometry record's stamp (= the map's)

@@ -27,7 +27,9 @@ extern "C" {
  *    rebvio_hip_test_live_resources; the gyro-rotation entries of the streaming and batch drivers rebvio_hip_push_frame_px_gyro(_device),
  *    rebvio_hip_batch_push_px_gyro_device, the host helper rebvio_hip_gyro_integrate and the test hook rebvio_hip_test_glue_set_next;
  *    the keyframe entries rebvio_hip_map_mark_keyframe, rebvio_hip_keyframe_next, rebvio_hip_map_keyframe_matches and their struct
- *    rebvio_hip_kf_match. */
+ *    rebvio_hip_kf_match; the keyframe snapshot and pose entries rebvio_hip_map_keyframe_snapshot, rebvio_hip_kf_snapshot_release,
+ *    rebvio_hip_kf_snapshot_download, rebvio_hip_default_kf_pose_opts, rebvio_hip_map_keyframe_pose, their structs
+ *    rebvio_hip_kf_pose_opts / rebvio_hip_kf_pose and the test hook rebvio_hip_test_kf_pose_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -305,6 +307,80 @@ typedef struct rebvio_hip_kf_match { /* 32 bytes */
   float pos_img[2];     /* winner's, as stored */
 } rebvio_hip_kf_match;
 int rebvio_hip_map_keyframe_matches(rebvio_hip_map* map, int kf_size, rebvio_hip_kf_match* out_host, int cap, int* count);
+
+/* Keyframe snapshot. A map that serves as a pair's old map is rotated in place, pair after pair, so the keyframe's keylines in the
+ * keyframe's OWN camera frame are gone once tracking has moved on. A snapshot keeps them: pos_img, (rho, sigma_rho) and matches of
+ * every keyline i < size, and the size, copied by one kernel into buffers the handle owns (16 bytes + 4 bytes per keyline).
+ * rebvio_hip_map_keyframe_snapshot queues that kernel on the TRACK stream in call order and waits for nothing on the host, as
+ * rebvio_hip_map_mark_keyframe does, and follows its calling rules. The snapshot holds the keylines as they are when the kernel runs
+ * in stream order: take it where the mark is made, after the map has been a pair's new map and before it serves as an old one. A
+ * map promised to R_prior_next is already rotated for the next pair and is refused (-7), like its cloud. -3, before the device is
+ * touched: null context, map or output, a map of another context; -10: the context has been destroyed.
+ * rebvio_hip_kf_snapshot_download (synchronous, track-side): *n = the keyframe's size; min(n, cap) records of prs4 = (pos_img.x,
+ * pos_img.y, rho, sigma_rho) and of matches are written (either may be NULL with cap 0). -3: null snapshot or n, negative cap, a
+ * null buffer with cap > 0; -10: the context has been destroyed.
+ * rebvio_hip_kf_snapshot_release: exactly once per handle; safe after rebvio_hip_destroy (which frees the buffers). */
+typedef struct rebvio_hip_kf_snapshot rebvio_hip_kf_snapshot;
+int rebvio_hip_map_keyframe_snapshot(rebvio_hip_ctx* ctx, rebvio_hip_map* map, rebvio_hip_kf_snapshot** out);
+void rebvio_hip_kf_snapshot_release(rebvio_hip_kf_snapshot* snap);
+int rebvio_hip_kf_snapshot_download(rebvio_hip_kf_snapshot* snap, float* prs4, unsigned* matches, int cap, int* n);
+
+/* Pose of a map relative to its keyframe, X_cur = R X_kf + t in keyframe depth units (a keyframe keyline of inverse depth rho lies
+ * at depth 1 / rho, as in a cloud of scale 1), estimated on the device from the keyframe correspondences by Gauss-Newton on the
+ * edge-normal reprojection error with Huber weights; fp64 from the loads on, every + - * / and sqrt one IEEE operation, in the
+ * order written here.
+ * Candidates: the records of rebvio_hip_map_keyframe_matches(map, kf_size = the snapshot's size), left in device memory;
+ * `candidates` is their number. For a record (j = kf_keyline, i = keyline), with fm of the context's parameters, pos_img_j, rho_j,
+ * sigma_rho_j, matches_j of the snapshot and pos_img_i, gradient_i = (gx, gy) of the map:
+ *   a = (double)(pos_img_j.x / fm);  b = (double)(pos_img_j.y / fm);  rho = (double)rho_j       (fp32 divisions, as rotateKeylines)
+ *   q.x = (double)(pos_img_i.x / fm);  q.y = (double)(pos_img_i.y / fm)
+ *   g2 = gx * gx + gy * gy;  gn = sqrt(g2);  n.x = gx / gn;  n.y = gy / gn
+ *   Z[r] = (R[3r] * a + R[3r+1] * b) + R[3r+2];  Y[r] = Z[r] + rho * t[r]                       (r = 0, 1, 2 = x, y, z)
+ *   p.x = Y.x / Y.z;  p.y = Y.y / Y.z;  e = fm * (n.x * (p.x - q.x) + n.y * (p.y - q.y))        (pixels along the gradient)
+ *   c.x = (fm * n.x) / Y.z;  c.y = (fm * n.y) / Y.z;  c.z = -(c.x * p.x + c.y * p.y)
+ *   J = (rho * c.x, rho * c.y, rho * c.z,  Z.y * c.z - Z.z * c.y,  Z.z * c.x - Z.x * c.z,  Z.x * c.y - Z.y * c.x)
+ *       (the derivative of e for t <- t + dt, R <- exp(dw) R)
+ *   |e| <= huber_px:  w = 1, cost = (e * e) / 2;   otherwise  w = huber_px / |e|, cost = huber_px * (|e| - huber_px / 2)
+ * The term is used when ALL of these hold (positive tests: a NaN skips it): keyframe keyline j passes kf_filter (matches_j >=
+ * min_matches, rho_j >= rho_min, rho_j <= rho_max, sigma_rho_j <= max_rel_sigma * rho_j in fp32, the point cloud's test); g2 > 0 and
+ * g2 < infinity; Y.z > 0. The 28 sums over the used terms: (w * J[a]) * J[b] for a <= b (H, returned as the full symmetric 6x6,
+ * row-major), (w * J[a]) * e (g), cost; `used` counts the terms. Summation order: the 64 lanes of a wave by a butterfly (lane l
+ * adds lane l ^ 32, then ^ 16, ... ^ 1), the four waves of a workgroup of 256 records as (w0 + w1) + (w2 + w3), the workgroups in
+ * ascending order from 0.0 - a fixed tree and no floating-point atomic: the same bits on every run.
+ * One evaluation = these sums at the current pose. Behind every evaluation but the last, H d = -g is solved by Cholesky (H = L L',
+ * column by column; forward, then back substitution) and t[r] += d[r], R = E R with w = d[3..5], th2 = (w.x * w.x + w.y * w.y) +
+ * w.z * w.z, K = [w]x, E = (I + A K) + B (K K), A = sin(th) / th, B = (1 - cos(th)) / th2, th = sqrt(th2) - and A = 1, B = 0
+ * when th2 < 1e-16. max_iter + 1 evaluations are queued back to back on the track stream (2 * max_iter + 2 launches behind the
+ * three of the correspondences), with no host wait in between and no early exit; the result is copied once. H, g, cost and used
+ * are those of the LAST evaluation, i.e. at the returned pose; iterations = steps applied.
+ * status 0: ok. 3: used < min_used at the first evaluation; 2: a pivot of the factorisation was not > 0 or not finite. In both
+ * cases the pose stays what it was at that point (3: the guess) and the remaining steps change nothing. max_iter 0 evaluates the
+ * sums at the guess only. A snapshot of size 0: candidates 0, used 0, status 3, pose = guess, zero sums; no kernel is launched.
+ * Synchronous and track-side with the calling rules of rebvio_hip_map_keyframe_matches; the map counts as used by the tracker
+ * afterwards. -3, before the device is touched: null map, snapshot or output, a non-finite R0 or t0, an invalid kf_filter (the
+ * point cloud's rules), huber_px not > 0, max_iter outside 0..32, min_used outside 0..65536, a snapshot of another context;
+ * -10: the context has been destroyed; -7: the map is promised to R_prior_next.
+ * rebvio_hip_test_kf_pose_host (test hook, touches no device) runs the same statements on the host from caller arrays - the
+ * snapshot's prs4 / matches (kf_size keyframe keylines), the current map's pos_img / gradient (n_cur x 2 floats each), n_rec
+ * candidate records of which kf_keyline and keyline are read - and sums the terms in record order. -3: a null array, a record
+ * whose indices lie outside the arrays, or options / a guess the device entry refuses. */
+typedef struct rebvio_hip_kf_pose_opts { /* defaults from rebvio_hip_default_kf_pose_opts */
+  rebvio_hip_cloud_filter kf_filter;     /* applied to the KEYFRAME side of a correspondence; default = default cloud filter */
+  double huber_px;                       /* default 2.0 */
+  int max_iter;                          /* 0..32, default 8; 0 = evaluate the sums at the guess only */
+  int min_used;                          /* default 12 */
+} rebvio_hip_kf_pose_opts;
+typedef struct rebvio_hip_kf_pose {
+  double R[9], t[3];                     /* X_cur = R X_kf + t, keyframe depth units (1/rho, as a cloud of scale 1) */
+  double H[36], g[6], cost;              /* sums at the RETURNED pose: J^T W J, J^T W e, sum of Huber costs */
+  int candidates, used, iterations, status; /* status 0 ok, 2 H not positive definite, 3 used < min_used at the first evaluation */
+} rebvio_hip_kf_pose;
+void rebvio_hip_default_kf_pose_opts(rebvio_hip_kf_pose_opts* opts);
+int rebvio_hip_map_keyframe_pose(rebvio_hip_map* map, rebvio_hip_kf_snapshot* snap, const rebvio_hip_kf_pose_opts* opts,
+                                 const double R0[9] /*NULL = identity*/, const double t0[3] /*NULL = 0*/, rebvio_hip_kf_pose* out);
+int rebvio_hip_test_kf_pose_host(float fm, const float* snap_prs4, const unsigned* snap_matches, int kf_size, const float* cur_pos_img,
+                                 const float* cur_gradient, int n_cur, const rebvio_hip_kf_match* records, int n_rec,
+                                 const rebvio_hip_kf_pose_opts* opts, const double R0[9], const double t0[3], rebvio_hip_kf_pose* out);
 
 /* Test hook: overwrite the device keylines (count must equal the map size). */
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n);

@@ -76,9 +76,21 @@ class KfMatch(C.Structure):
                 ("sigma_rho", C.c_float), ("pos_img", C.c_float * 2)]
 
 
+class KfPoseOpts(C.Structure):
+    """rebvio_hip_kf_pose_opts (Map.keyframe_pose); defaults from default_kf_pose_opts"""
+    _fields_ = [("kf_filter", CloudFilter), ("huber_px", C.c_double), ("max_iter", C.c_int), ("min_used", C.c_int)]
+
+
+class KfPose(C.Structure):
+    """rebvio_hip_kf_pose: X_cur = R X_kf + t, the sums at that pose, and the counters"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("H", C.c_double * 36), ("g", C.c_double * 6), ("cost", C.c_double),
+                ("candidates", C.c_int), ("used", C.c_int), ("iterations", C.c_int), ("status", C.c_int)]
+
+
 # every symbol include/rebvio_hip.h declares: (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
+_dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 SIGNATURES = {
     "rebvio_hip_abi_version": (C.c_int, []),
@@ -110,6 +122,13 @@ SIGNATURES = {
     "rebvio_hip_cloud_release": (None, [_vp]),
     "rebvio_hip_map_mark_keyframe": (C.c_int, [_vp, _vp]),
     "rebvio_hip_map_keyframe_matches": (C.c_int, [_vp, C.c_int, C.POINTER(KfMatch), C.c_int, _ip]),
+    "rebvio_hip_map_keyframe_snapshot": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "rebvio_hip_kf_snapshot_release": (None, [_vp]),
+    "rebvio_hip_kf_snapshot_download": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint), C.c_int, _ip]),
+    "rebvio_hip_default_kf_pose_opts": (None, [C.POINTER(KfPoseOpts)]),
+    "rebvio_hip_map_keyframe_pose": (C.c_int, [_vp, _vp, C.POINTER(KfPoseOpts), _dp, _dp, C.POINTER(KfPose)]),
+    "rebvio_hip_test_kf_pose_host": (C.c_int, [C.c_float, _fp, C.POINTER(C.c_uint), C.c_int, _fp, _fp, C.c_int, C.POINTER(KfMatch),
+                                               C.c_int, C.POINTER(KfPoseOpts), _dp, _dp, C.POINTER(KfPose)]),
     "rebvio_hip_map_upload": (C.c_int, [_vp, _vp, C.c_int]),
     "rebvio_hip_map_release": (None, [_vp]),
     "rebvio_hip_build_distance_field": (C.c_int, [_vp, _vp]),
@@ -316,6 +335,76 @@ def _cloud_pose(pose):
     return cloud_pose(*pose)
 
 
+def default_kf_pose_opts(**over) -> KfPoseOpts:
+    """The library's defaults (rebvio_hip_default_kf_pose_opts); kf_filter takes a CloudFilter or a dict of its fields to change."""
+    o = KfPoseOpts()
+    lib().rebvio_hip_default_kf_pose_opts(C.byref(o))
+    for k, v in over.items():
+        if k == "kf_filter" and not isinstance(v, CloudFilter):
+            for fk, fv in v.items():
+                setattr(o.kf_filter, fk, fv)
+        else:
+            setattr(o, k, v)
+    return o
+
+
+def _guess(a, n):
+    """(keep-alive array, pointer) of a pose guess: n doubles, or (None, NULL) for None."""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(n))
+    return a, a.ctypes.data_as(_dp)
+
+
+def kf_pose_host(fm, prs4, kf_matches, cur_pos_img, cur_gradient, records, opts=None, R0=None, t0=None) -> KfPose:
+    """The solve of Map.keyframe_pose on the host, from arrays (rebvio_hip_test_kf_pose_host): a snapshot's download, the current
+    map's pos_img / gradient, KF_MATCH_DTYPE records. Touches no device; the terms are summed in record order."""
+    prs4 = np.ascontiguousarray(prs4, np.float32).reshape(-1, 4)
+    kf_matches = np.ascontiguousarray(kf_matches, np.uint32)
+    q = np.ascontiguousarray(cur_pos_img, np.float32).reshape(-1, 2)
+    g = np.ascontiguousarray(cur_gradient, np.float32).reshape(-1, 2)
+    rec = np.ascontiguousarray(records, KF_MATCH_DTYPE)
+    assert len(prs4) == len(kf_matches) and len(q) == len(g)
+    (kR, pR), (kt, pt) = _guess(R0, 9), _guess(t0, 3)
+    out = KfPose()
+    up = C.POINTER(C.c_uint)
+    _chk(lib().rebvio_hip_test_kf_pose_host(float(fm), prs4.ctypes.data_as(_fp) if len(prs4) else None,
+                                            kf_matches.ctypes.data_as(up) if len(prs4) else None, len(prs4),
+                                            q.ctypes.data_as(_fp) if len(q) else None, g.ctypes.data_as(_fp) if len(q) else None, len(q),
+                                            rec.ctypes.data_as(C.POINTER(KfMatch)) if len(rec) else None, len(rec), opts, pR, pt,
+                                            C.byref(out)))
+    del kR, kt
+    return out
+
+
+class KfSnapshot:
+    """A keyframe as it was when marked (rebvio_hip_map_keyframe_snapshot): download() its keylines, release() when done."""
+
+    def __init__(self, h):
+        self.h = h
+
+    def download(self):
+        """(prs4 float32 [n, 4] = pos_img.x, pos_img.y, rho, sigma_rho; matches uint32 [n]) of the keyframe's n keylines"""
+        n = C.c_int()
+        _chk(lib().rebvio_hip_kf_snapshot_download(self.h, None, None, 0, C.byref(n)))
+        prs, mt = np.zeros((n.value, 4), np.float32), np.zeros(n.value, np.uint32)
+        if n.value:
+            _chk(lib().rebvio_hip_kf_snapshot_download(self.h, prs.ctypes.data_as(_fp), mt.ctypes.data_as(C.POINTER(C.c_uint)), n.value,
+                                                       C.byref(n)))
+        return prs, mt
+
+    def release(self):
+        if self.h:
+            lib().rebvio_hip_kf_snapshot_release(self.h)  # safe after the context is closed too
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 class Cloud:
     """A queued point cloud (rebvio_hip_map_point_cloud_async): wait() for the records, release() when done with them."""
 
@@ -441,6 +530,23 @@ class Map:
                                                    C.byref(n)))
         out = out[:min(n.value, cap)]
         return (out, n.value) if return_count else out
+
+    def keyframe_snapshot(self) -> KfSnapshot:
+        """Keeps this map's keylines as they are now, in its own camera frame (rebvio_hip_map_keyframe_snapshot; queued on the track
+        stream, returns at once). Take it where the map is marked: after it has been a pair's new map, before it is an old one."""
+        h = _vp()
+        _chk(lib().rebvio_hip_map_keyframe_snapshot(self.ctx.h, self.h, C.byref(h)))
+        return KfSnapshot(h)
+
+    def keyframe_pose(self, snap: KfSnapshot, opts=None, R0=None, t0=None) -> KfPose:
+        """Pose of this map relative to the keyframe `snap` was taken from, X_cur = R X_kf + t, estimated on the device from the
+        keyframe correspondences (rebvio_hip_map_keyframe_pose). opts: a KfPoseOpts or None for the defaults; R0 / t0: the guess
+        (None: identity / zero), e.g. the previous result."""
+        (kR, pR), (kt, pt) = _guess(R0, 9), _guess(t0, 3)
+        out = KfPose()
+        _chk(lib().rebvio_hip_map_keyframe_pose(self.h, snap.h, opts, pR, pt, C.byref(out)))
+        del kR, kt
+        return out
 
     def upload(self, kl: np.ndarray):
         kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)

@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "glue.hpp"
 #include "hostmath.hpp"
+#include "kf_pose.hpp"
 #include "owned.hpp"
 #include "pixel_format.hpp"
 
@@ -270,6 +271,20 @@ struct rebvio_hip_cloud {
   bool in_use = false;
 };
 
+// A keyframe snapshot (rebvio_hip_map_keyframe_snapshot): one device buffer - ceil(keylines_max / 256) * 256 records of 16 bytes
+// (pos_img, rho, sigma_rho), as many matches words, the size - written by k_kf_snapshot on the track stream. Listed in its
+// context, which frees the buffer when it is destroyed; like a map handle it may outlive the context as a husk.
+struct rebvio_hip_kf_snapshot {
+  rebvio_hip_ctx* ctx = nullptr;
+  std::shared_ptr<LifeBlock> life;
+  Owned own;                   // the buffer
+  char* buf = nullptr;
+  void* prs = nullptr;         // views into buf
+  unsigned* matches = nullptr;
+  int* n_dev = nullptr;
+  int n_host = -1;             // the size, once a synchronous entry has fetched it
+};
+
 // A finished pair's record as the caller gets it.
 struct PairRec {
   rebvio_hip_pair_out out;
@@ -482,6 +497,14 @@ struct rebvio_hip_ctx {
   int* kf_claimants = nullptr;  // (views into kf_key's allocation)
   int* kf_blk = nullptr;
   rebvio_hip_kf_match* kf_rec = nullptr;
+  // keyframe snapshots that are out (snap_mu: rebvio_hip_kf_snapshot_release may come from any thread), and the scratch of
+  // rebvio_hip_map_keyframe_pose (allocated on first use, kept; a track-side entry): the result block the kernels iterate on,
+  // then kMaxRecBlocks partials of 28 doubles and as many used counts
+  std::mutex snap_mu;
+  std::vector<rebvio_hip_kf_snapshot*> snaps;
+  rebvio_hip_kf_pose* kfp_state = nullptr;
+  double* kfp_part = nullptr;  // (views into kfp_state's allocation)
+  int* kfp_used = nullptr;
 };
 
 namespace {
@@ -1382,6 +1405,12 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
     free_cloud_device(cl);
     if (!cl->in_use) delete cl;  // (else: the handle is still out; its release deletes the husk)
   }
+  for (auto* sn : c->snaps) {  // every listed snapshot is out: its release deletes the husk
+    sn->own.release();
+    sn->buf = nullptr;
+    sn->ctx = nullptr;
+  }
+  c->snaps.clear();
   c->own.release();
   delete c;
 }
@@ -1609,6 +1638,17 @@ int check_cloud_args(const char* who, const rebvio_hip_cloud_filter* f, const re
   return 0;
 }
 
+// Scratch of the keyframe correspondences (rebvio_hip_map_keyframe_matches, rebvio_hip_map_keyframe_pose), allocated on first use
+int kf_scratch(rebvio_hip_ctx* c) {
+  if (c->kf_rec) return 0;
+  const size_t slots = (size_t)div_up(c->P.keylines_max, 256) * 256;
+  if (!c->kf_key) HIPCHK(c->own.device_bytes(&c->kf_key, slots * (sizeof(unsigned long long) + sizeof(int)) + (kMaxRecBlocks + 1) * sizeof(int)));
+  c->kf_claimants = reinterpret_cast<int*>(c->kf_key + slots);
+  c->kf_blk = c->kf_claimants + slots;
+  HIPCHK(c->own.device(&c->kf_rec, (size_t)c->P.keylines_max));
+  return 0;
+}
+
 static_assert(sizeof(rebvio_hip_cloud_point) == 32 && sizeof(CloudHdr) == 64, "a cloud record is two 16-byte stores behind a 64-byte head");
 
 int alloc_cloud(rebvio_hip_ctx* c, rebvio_hip_cloud* cl) {
@@ -1816,13 +1856,7 @@ int rebvio_hip_map_keyframe_matches(rebvio_hip_map* m, int kf_size, rebvio_hip_k
                     "its correspondences are available again once the next track_pair_begin has run", -7);
   if (kf_size == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  const size_t slots = (size_t)div_up(c->P.keylines_max, 256) * 256;
-  if (!c->kf_rec) {
-    if (!c->kf_key) HIPCHK(c->own.device_bytes(&c->kf_key, slots * (sizeof(unsigned long long) + sizeof(int)) + (kMaxRecBlocks + 1) * sizeof(int)));
-    c->kf_claimants = reinterpret_cast<int*>(c->kf_key + slots);
-    c->kf_blk = c->kf_claimants + slots;
-    HIPCHK(c->own.device(&c->kf_rec, (size_t)c->P.keylines_max));
-  }
+  { const int rc_sc = kf_scratch(c); if (rc_sc) return rc_sc; }
   if (cap > c->P.keylines_max) cap = c->P.keylines_max;  // (no more slots than that can hold a claimant)
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
@@ -1840,6 +1874,219 @@ int rebvio_hip_map_keyframe_matches(rebvio_hip_map* m, int kf_size, rebvio_hip_k
     if (rc_ts) return rc_ts;
   }
   *count = n;
+  return 0;
+}
+
+int rebvio_hip_map_keyframe_snapshot(rebvio_hip_ctx* c, rebvio_hip_map* m, rebvio_hip_kf_snapshot** out) {
+  if (out) *out = nullptr;
+  if (!c || !m || !out) return fail_msg("map_keyframe_snapshot: null context, map or output", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (m->ctx != c) return fail_msg("map_keyframe_snapshot: map of another context", -3);
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg("map_keyframe_snapshot: the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
+                    "take the snapshot before that call, or once the next track_pair_begin has run", -7);
+  HIPCHK(hipSetDevice(c->device));
+  auto* sn = new rebvio_hip_kf_snapshot;
+  sn->ctx = c;
+  sn->life = c->life;
+  const size_t M = (size_t)div_up(c->P.keylines_max, 256) * 256;
+  const hipError_t e = sn->own.device_bytes(&sn->buf, M * (sizeof(float4) + sizeof(unsigned)) + 16);
+  if (e != hipSuccess) {
+    delete sn;
+    return fail("map_keyframe_snapshot: device buffer", e);
+  }
+  sn->prs = sn->buf;
+  sn->matches = reinterpret_cast<unsigned*>(sn->buf + M * sizeof(float4));
+  sn->n_dev = reinterpret_cast<int*>(sn->matches + M);
+  {
+    std::lock_guard<std::mutex> lk(c->snap_mu);
+    c->snaps.push_back(sn);
+  }
+  *out = sn;  // (from here on the caller's release gives the buffer back, whatever fails below)
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  launch_kf_snapshot(c->s_trk, c->K, m->d, sn->prs, sn->matches, sn->n_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+void rebvio_hip_kf_snapshot_release(rebvio_hip_kf_snapshot* sn) {
+  if (!sn) return;
+  {
+    const std::shared_ptr<LifeBlock> life = sn->life;
+    std::shared_lock<std::shared_mutex> lk(life->mu);
+    if (!life->dead.load(std::memory_order_acquire)) {  // (else: the context is gone, its destroy freed the buffer)
+      rebvio_hip_ctx* c = sn->ctx;
+      (void)hipSetDevice(c->device);
+      {
+        std::lock_guard<std::mutex> sl(c->snap_mu);
+        for (size_t i = 0; i < c->snaps.size(); ++i)
+          if (c->snaps[i] == sn) {
+            c->snaps.erase(c->snaps.begin() + (std::ptrdiff_t)i);
+            break;
+          }
+      }
+      sn->own.release();  // (hipFree waits for the kernels that still use the buffer)
+    }
+  }
+  delete sn;
+}
+
+namespace {
+// the keyframe's size on the host: fetched once, behind the snapshot kernel in stream order
+int snapshot_size(rebvio_hip_ctx* c, rebvio_hip_kf_snapshot* sn) {
+  if (sn->n_host >= 0) return 0;
+  int n = 0;
+  HIPCHK(hipMemcpyAsync(&n, sn->n_dev, sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  const int rc = trk_sync(c);
+  if (rc) return rc;
+  sn->n_host = n;
+  return 0;
+}
+
+int check_kf_pose_args(const char* who, const rebvio_hip_kf_pose_opts& o, const double* R0, const double* t0) {
+  const int rc = check_cloud_args(who, &o.kf_filter, nullptr);
+  if (rc) return rc;
+  if (!(o.huber_px > 0.0)) return fail_msg((std::string(who) + ": huber_px must be > 0").c_str(), -3);
+  if (o.max_iter < 0 || o.max_iter > 32) return fail_msg((std::string(who) + ": max_iter outside 0..32").c_str(), -3);
+  if (o.min_used < 0 || o.min_used > 65536) return fail_msg((std::string(who) + ": min_used outside 0..65536").c_str(), -3);
+  bool fin = true;
+  for (int i = 0; R0 && i < 9; ++i) fin = fin && std::isfinite(R0[i]);
+  for (int i = 0; t0 && i < 3; ++i) fin = fin && std::isfinite(t0[i]);
+  if (!fin) return fail_msg((std::string(who) + ": non-finite R0 or t0").c_str(), -3);
+  return 0;
+}
+
+// the result block before the first evaluation: the guess, everything else zero
+void kf_pose_start(rebvio_hip_kf_pose* o, const double* R0, const double* t0) {
+  std::memset(o, 0, sizeof(*o));
+  for (int i = 0; i < 9; ++i) o->R[i] = R0 ? R0[i] : (i % 4 == 0 ? 1.0 : 0.0);
+  for (int i = 0; i < 3; ++i) o->t[i] = t0 ? t0[i] : 0.0;
+}
+}  // namespace
+
+int rebvio_hip_kf_snapshot_download(rebvio_hip_kf_snapshot* sn, float* prs4, unsigned* matches, int cap, int* n) {
+  if (!sn || !n) return fail_msg("kf_snapshot_download: null snapshot or n", -3);
+  if (cap < 0 || (cap > 0 && (!prs4 || !matches))) return fail_msg("kf_snapshot_download: cap records need both output buffers (cap >= 0)", -3);
+  *n = 0;
+  const std::shared_ptr<LifeBlock> life = sn->life;
+  std::shared_lock<std::shared_mutex> lk(life->mu);
+  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  rebvio_hip_ctx* c = sn->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  int rc = snapshot_size(c, sn);
+  if (rc) return rc;
+  const int k = sn->n_host < cap ? sn->n_host : cap;
+  if (k > 0) {
+    HIPCHK(hipMemcpyAsync(prs4, sn->prs, (size_t)k * sizeof(float4), hipMemcpyDeviceToHost, c->s_trk));
+    HIPCHK(hipMemcpyAsync(matches, sn->matches, (size_t)k * sizeof(unsigned), hipMemcpyDeviceToHost, c->s_trk));
+    rc = trk_sync(c);
+    if (rc) return rc;
+  }
+  *n = sn->n_host;
+  return 0;
+}
+
+void rebvio_hip_default_kf_pose_opts(rebvio_hip_kf_pose_opts* o) {
+  rebvio_hip_default_cloud_filter(&o->kf_filter);
+  o->huber_px = 2.0;
+  o->max_iter = 8;
+  o->min_used = 12;
+}
+
+static_assert(sizeof(rebvio_hip_kf_pose) == 55 * 8 + 16, "the result block is copied as it is");
+
+int rebvio_hip_map_keyframe_pose(rebvio_hip_map* m, rebvio_hip_kf_snapshot* sn, const rebvio_hip_kf_pose_opts* opts, const double* R0,
+                                 const double* t0, rebvio_hip_kf_pose* out) {
+  if (!m || !sn || !out) return fail_msg("map_keyframe_pose: null map, snapshot or output", -3);
+  rebvio_hip_kf_pose_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_kf_pose_opts(&o);
+  int rc = check_kf_pose_args("map_keyframe_pose", o, R0, t0);
+  if (rc) return rc;
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (sn->life != m->life) {
+    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+    return fail_msg("map_keyframe_pose: snapshot of another context", -3);
+  }
+  rebvio_hip_ctx* c = m->ctx;
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg("map_keyframe_pose: the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
+                    "its pose is available again once the next track_pair_begin has run", -7);
+  HIPCHK(hipSetDevice(c->device));
+  rc = snapshot_size(c, sn);
+  if (rc) return rc;
+  const int kf_size = sn->n_host;
+  rebvio_hip_kf_pose start;
+  kf_pose_start(&start, R0, t0);
+  if (kf_size == 0) {  // no candidates: nothing is launched
+    start.status = 3;
+    *out = start;
+    return 0;
+  }
+  // scratch of the correspondences and of the solve
+  rc = kf_scratch(c);
+  if (rc) return rc;
+  if (!c->kfp_state) {
+    const size_t head = (sizeof(rebvio_hip_kf_pose) + 63) / 64 * 64, part = (size_t)kMaxRecBlocks * kfp::kSums * sizeof(double);
+    char* b = nullptr;
+    HIPCHK(c->own.device_bytes(&b, head + part + kMaxRecBlocks * sizeof(int)));
+    c->kfp_state = reinterpret_cast<rebvio_hip_kf_pose*>(b);
+    c->kfp_part = reinterpret_cast<double*>(b + head);
+    c->kfp_used = reinterpret_cast<int*>(b + head + part);
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  int* count_dev = c->kf_blk + kMaxRecBlocks;
+  HIPCHK((hipError_t)launch_kf_matches(c->s_trk, c->K, m->d, kf_size, c->P.keylines_max, c->kf_key, c->kf_claimants, c->kf_blk, count_dev, c->kf_rec));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c->kfp_state, &start, sizeof(start), hipMemcpyHostToDevice, c->s_trk));
+  for (int it = 0; it <= o.max_iter; ++it)
+    launch_kf_pose_eval(c->s_trk, c->K, m->d, kf_size, c->kf_rec, count_dev, sn->prs, sn->matches, o.kf_filter, o.huber_px, it == 0,
+                        it == o.max_iter, o.min_used, c->kfp_state, c->kfp_part, c->kfp_used);
+  HIPCHK(hipGetLastError());
+  rebvio_hip_kf_pose res;
+  HIPCHK(hipMemcpyAsync(&res, c->kfp_state, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  *out = res;
+  return 0;
+}
+
+int rebvio_hip_test_kf_pose_host(float fm, const float* snap_prs4, const unsigned* snap_matches, int kf_size, const float* cur_pos_img,
+                                 const float* cur_gradient, int n_cur, const rebvio_hip_kf_match* records, int n_rec,
+                                 const rebvio_hip_kf_pose_opts* opts, const double* R0, const double* t0, rebvio_hip_kf_pose* out) {
+  if (!out || kf_size < 0 || n_cur < 0 || n_rec < 0 || (kf_size > 0 && (!snap_prs4 || !snap_matches)) ||
+      (n_cur > 0 && (!cur_pos_img || !cur_gradient)) || (n_rec > 0 && !records))
+    return fail_msg("test_kf_pose_host: null array or negative size", -3);
+  rebvio_hip_kf_pose_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_kf_pose_opts(&o);
+  const int rc = check_kf_pose_args("test_kf_pose_host", o, R0, t0);
+  if (rc) return rc;
+  for (int r = 0; r < n_rec; ++r)
+    if (records[r].kf_keyline < 0 || records[r].kf_keyline >= kf_size || records[r].keyline < 0 || records[r].keyline >= n_cur)
+      return fail_msg("test_kf_pose_host: a record's indices lie outside the arrays", -3);
+  rebvio_hip_kf_pose res;
+  kf_pose_start(&res, R0, t0);
+  res.candidates = n_rec;
+  if (kf_size == 0) res.status = 3;
+  for (int it = 0; kf_size > 0 && it <= o.max_iter; ++it) {
+    double S[kfp::kSums] = {}, v[kfp::kSums], ws[48];
+    int used = 0;
+    for (int r = 0; r < n_rec; ++r) {
+      const int j = records[r].kf_keyline, i = records[r].keyline;
+      const float* k4 = snap_prs4 + 4 * (size_t)j;
+      if (!kfp::filter_pass(o.kf_filter, k4[2], k4[3], snap_matches[j])) continue;
+      if (!kfp::term(fm, k4[0], k4[1], k4[2], cur_pos_img[2 * (size_t)i], cur_pos_img[2 * (size_t)i + 1], cur_gradient[2 * (size_t)i],
+                     cur_gradient[2 * (size_t)i + 1], res.R, res.t, o.huber_px, v))
+        continue;
+      for (int k = 0; k < kfp::kSums; ++k) S[k] = S[k] + v[k];
+      ++used;
+    }
+    kfp::step(S, used, it == 0, it == o.max_iter, o.min_used, ws, &res);
+  }
+  *out = res;
   return 0;
 }
 

@@ -329,6 +329,16 @@ void launch_mark_keyframe(hipStream_t s, const KParams& p, const MapDev& m);
 int launch_kf_matches(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, int cap, unsigned long long* key, int* claimants,
                       int* blk_cnt, int* count_dev, void* records_dev);
 
+// k_kf_snapshot on stream s (rebvio_hip_map_keyframe_snapshot): 16-byte (pos_img, rho, sigma_rho) records and matches of the keylines
+// of m into prs / matches (ceil(kmax / 256) * 256 entries each), the map's size into *n_out
+void launch_kf_snapshot(hipStream_t s, const KParams& p, const MapDev& m, void* prs, unsigned* matches, int* n_out);
+// One evaluation of rebvio_hip_map_keyframe_pose on stream s: k_kf_pose_sums over the records launch_kf_matches(kf_size) left
+// (records_dev, *count_dev) against a snapshot's buffers, then k_kf_pose_step. state_dev = the result block (pose in, pose out);
+// part / part_used = kMaxRecBlocks * 28 doubles / kMaxRecBlocks ints. kf_size in 1..kmax.
+void launch_kf_pose_eval(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const void* records_dev, const int* count_dev,
+                         const void* snap_prs, const unsigned* snap_matches, const rebvio_hip_cloud_filter& flt, double huber, int first,
+                         int last, int min_used, rebvio_hip_kf_pose* state_dev, double* part, int* part_used);
+
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
 // ---- several camera streams ("lanes") of one GPU advanced in lock-step by batched launches (rebvio_hip_batch_*) --------

@@ -10,6 +10,7 @@
 // no dense contraction exists on this path (largest product is 6x6), so MFMA does not apply.
 #include "common.hpp"
 #include "glue_dev.hpp"
+#include "kf_pose.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -3350,6 +3351,118 @@ int launch_kf_matches(hipStream_t s, const KParams& p, const MapDev& m, int kf_s
   RH_LAUNCH(k_kf_emit, grid, dim3(256), 0, s, m, kf_size, cap, (const unsigned long long*)key, (const int*)claimants, (const int*)blk_cnt,
             count_dev, reinterpret_cast<float4*>(records_dev));
   return 0;
+}
+
+// ---- keyframe snapshot and keyframe-to-current pose (rebvio_hip_map_keyframe_snapshot, rebvio_hip_map_keyframe_pose) ------------
+// k_kf_snapshot keeps what the pose needs of a keyframe in the keyframe's own frame: (pos_img, rho, sigma_rho) as one 16-byte
+// record per keyline - one 16-byte store per lane - matches as a dword array, and the size. One workgroup per 256 keylines, the
+// size read on the device; only the map's own n records are written.
+__global__ __launch_bounds__(256) void k_kf_snapshot(MapDev m, float4* __restrict__ prs, unsigned* __restrict__ matches, int* __restrict__ n_out) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const float2 pi = m.pos_img[idx];  // bound-free early loads (the arrays are padded to the launch grid)
+  const float2 rs = m.rs[idx];
+  const unsigned mt = m.matches[idx];
+  const int n = m.st->n;
+  if (idx == 0) *n_out = n;
+  if (idx < n) {
+    prs[idx] = make_float4(pi.x, pi.y, rs.x, rs.y);
+    matches[idx] = mt;
+  }
+}
+
+void launch_kf_snapshot(hipStream_t s, const KParams& p, const MapDev& m, void* prs, unsigned* matches, int* n_out) {
+  RH_LAUNCH(k_kf_snapshot, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, m, reinterpret_cast<float4*>(prs), matches, n_out);
+}
+
+// One evaluation of the pose's normal equations (kf_pose.hpp: kfp::term is the definition's per-record statement). One thread per
+// candidate record of k_kf_emit, the record count and the current pose read from device memory. The 28 addends of a lane are
+// reduced by a FIXED tree: an fp64 butterfly over the wave (every lane ends with the same total: a + b == b + a), the four wave
+// totals through LDS as (w0 + w1) + (w2 + w3). One partial of 28 doubles and the count of used terms per workgroup; no
+// floating-point atomic anywhere, so the sums are the same bit for bit on every run. A workgroup behind the last record writes zeros.
+__global__ __launch_bounds__(256) void k_kf_pose_sums(KParams p, MapDev m, const float4* __restrict__ rec, const int* __restrict__ count,
+                                                      const float4* __restrict__ prs, const unsigned* __restrict__ kf_matches,
+                                                      rebvio_hip_cloud_filter flt, double huber, const rebvio_hip_kf_pose* __restrict__ st,
+                                                      double* __restrict__ part, int* __restrict__ part_used) {
+  __shared__ double sh[4][kfp::kSums];
+  __shared__ int sh_used[4];
+  const int tid = threadIdx.x, r = blockIdx.x * 256 + tid, wv = tid >> 6;
+  double v[kfp::kSums];
+#pragma unroll
+  for (int k = 0; k < kfp::kSums; ++k) v[k] = 0.0;
+  bool used = false;
+  if (r < *count) {
+    const float4 r0 = rec[2 * (size_t)r];  // kf_keyline, keyline, claimants, matches (k_kf_emit: both below their maps' sizes)
+    const int j = __float_as_int(r0.x), i = __float_as_int(r0.y);
+    const float4 k4 = prs[j];
+    const unsigned kmt = kf_matches[j];
+    const float2 q = m.pos_img[i];
+    const float2 g = m.grad[i];
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = st->R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = st->t[k];
+    used = kfp::filter_pass(flt, k4.z, k4.w, kmt) && kfp::term(p.fm, k4.x, k4.y, k4.z, q.x, q.y, g.x, g.y, R, t, huber, v);
+  }
+#pragma unroll
+  for (int k = 0; k < kfp::kSums; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
+  }
+  const int nu = __popcll(__ballot(used));
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kfp::kSums; ++k) sh[wv][k] = v[k];
+    sh_used[wv] = nu;
+  }
+  __syncthreads();
+  if (tid < kfp::kSums) part[(size_t)blockIdx.x * kfp::kSums + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
+  if (tid == 0) part_used[blockIdx.x] = (sh_used[0] + sh_used[1]) + (sh_used[2] + sh_used[3]);
+}
+
+// The end of one evaluation, one workgroup of 64: lane k < 28 adds the nb (<= kMaxRecBlocks) partials of sum k in index order, lane 28
+// the used counts; lane 0 then runs kfp::step - H, g, cost, used into the result block, and unless this is the last evaluation the
+// 6x6 Cholesky solve and the SE3 update, workspace in LDS.
+__global__ __launch_bounds__(64) void k_kf_pose_step(const double* __restrict__ part, const int* __restrict__ part_used, int nb,
+                                                     const int* __restrict__ count, int first, int last, int min_used,
+                                                     rebvio_hip_kf_pose* __restrict__ st) {
+  __shared__ double S[kfp::kSums];
+  __shared__ double ws[48];
+  __shared__ int sh_used;
+  const int tid = threadIdx.x;
+  if (tid < kfp::kSums) {
+    // eight loads in flight, added in index order (one dependent load per partial took 72 us for 256 partials)
+    double s = 0.0;
+    int b = 0;
+    for (; b + 8 <= nb; b += 8) {
+      double x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(b + u) * kfp::kSums + tid];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s = s + x[u];
+    }
+    for (; b < nb; ++b) s = s + part[(size_t)b * kfp::kSums + tid];
+    S[tid] = s;
+  } else if (tid == kfp::kSums) {
+    int u = 0;
+    for (int b = 0; b < nb; ++b) u += part_used[b];
+    sh_used = u;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (first) st->candidates = *count;
+    kfp::step(S, sh_used, first, last, min_used, ws, st);
+  }
+}
+
+void launch_kf_pose_eval(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const void* records_dev, const int* count_dev,
+                         const void* snap_prs, const unsigned* snap_matches, const rebvio_hip_cloud_filter& flt, double huber, int first,
+                         int last, int min_used, rebvio_hip_kf_pose* state_dev, double* part, int* part_used) {
+  const int nb = div_up(kf_size, 256);  // (the records number at most kf_size <= kmax: nb <= kMaxRecBlocks)
+  RH_LAUNCH(k_kf_pose_sums, dim3(nb), dim3(256), 0, s, p, m, reinterpret_cast<const float4*>(records_dev), count_dev,
+            reinterpret_cast<const float4*>(snap_prs), snap_matches, flt, huber, (const rebvio_hip_kf_pose*)state_dev, part, part_used);
+  RH_LAUNCH(k_kf_pose_step, dim3(1), dim3(64), 0, s, (const double*)part, (const int*)part_used, nb, count_dev, first, last, min_used,
+            state_dev);
 }
 
 }  // namespace rh

@@ -159,4 +159,32 @@ std::vector<rebvio::types::KfMatch> EdgeMap::keyframeMatches(int kf_size) {
   return out;
 }
 
+void KeyframeSnapshot::reset() {
+  if (handle_) rebvio_hip_kf_snapshot_release(handle_);
+  handle_ = nullptr;
+  keepalive_.reset();
+}
+
+rebvio::KeyframeSnapshot EdgeMap::keyframeSnapshot() {
+  rebvio_hip_kf_snapshot* h = nullptr;
+  const int rc = rebvio_hip_map_keyframe_snapshot(ctx_, handle_, &h);
+  rebvio::KeyframeSnapshot snap(h, keepalive_);  // (a handle that came with an error is still the caller's to release)
+  check("rebvio_hip_map_keyframe_snapshot", rc);
+  return snap;
+}
+
+rebvio::types::KfPose EdgeMap::keyframePose(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfPoseOpts& opts,
+                                            const rebvio::types::KfPose* guess) {
+  static_assert(sizeof(types::KfPose) == sizeof(rebvio_hip_kf_pose) && sizeof(types::KfPoseOpts) == sizeof(rebvio_hip_kf_pose_opts) &&
+                    offsetof(types::KfPose, status) == offsetof(rebvio_hip_kf_pose, status) &&
+                    offsetof(types::KfPose, cost) == offsetof(rebvio_hip_kf_pose, cost) &&
+                    offsetof(types::KfPoseOpts, min_used) == offsetof(rebvio_hip_kf_pose_opts, min_used),
+                "keyframe pose types mirror the C-ABI's");
+  rebvio::types::KfPose out;
+  check("rebvio_hip_map_keyframe_pose",
+        rebvio_hip_map_keyframe_pose(handle_, snapshot.handle(), reinterpret_cast<const rebvio_hip_kf_pose_opts*>(&opts),
+                                     guess ? guess->R : nullptr, guess ? guess->t : nullptr, reinterpret_cast<rebvio_hip_kf_pose*>(&out)));
+  return out;
+}
+
 }  // namespace rebvio

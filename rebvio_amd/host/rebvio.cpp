@@ -107,6 +107,10 @@ void Rebvio::registerOdometryCallback(std::function<void(rebvio::types::Odometry
 
 void Rebvio::registerKeyframeCallback(std::function<void(uint64_t ts_us, int kf_matches, int keylines)> cb) { keyframe_callbacks_.push_back(cb); }
 
+void Rebvio::registerKeyframePoseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfPose&)> cb) {
+  keyframe_pose_callbacks_.push_back(cb);
+}
+
 void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
   point_cloud_callbacks_.push_back({cb, filter});
 }
@@ -329,7 +333,13 @@ void Rebvio::stateEstimationProcess() {
     types::CloudPose cloud_pose;
     std::vector<rebvio_hip_cloud*> clouds;
     int kf_matches = 0;    // of the pair, for the keyframe callbacks
+    bool have_kf_pose = false;  // keyframe-pose callbacks: the new map's pose relative to the keyframe
+    types::KfPose kf_pose;
   } pending;
+  // keyframe-pose callbacks: the snapshot of the current keyframe and the last pose estimated against it (the next one's guess)
+  rebvio::KeyframeSnapshot kf_snapshot;
+  types::KfPose kf_pose_last;
+  bool kf_pose_warm = false;
   // Two steps: the counters (and with them the stop conditions of rebvio.cpp:236-252) are fetched as soon as the next pair's
   // first half is back; the callbacks run after that pair's second half has been launched, off the path between its halves.
   auto publish_pending = [&]() {
@@ -340,6 +350,8 @@ void Rebvio::stateEstimationProcess() {
       const int keylines = pending.new_map->size();
       for (auto& cb : keyframe_callbacks_) cb(pending.odometry.ts_us, pending.kf_matches, keylines);
     }
+    if (pending.have_kf_pose)
+      for (auto& cb : keyframe_pose_callbacks_) cb(pending.odometry.ts_us, pending.kf_pose);
     // every cloud goes back to its pool, also when a callback (or the wait) throws
     struct CloudsBack {
       std::vector<rebvio_hip_cloud*>& v;
@@ -543,6 +555,7 @@ void Rebvio::stateEstimationProcess() {
       }
     };
     const bool want_cloud = !point_cloud_callbacks_.empty();
+    const bool want_kf_pose = !keyframe_pose_callbacks_.empty();
     std::vector<rebvio_hip_cloud*> clouds;
     types::CloudPose cloud_pose;
     if (want_cloud) integrate_pose();
@@ -550,6 +563,7 @@ void Rebvio::stateEstimationProcess() {
     // pair's prior: that pair's first rotateKeylines then rides in this pair's last kernel. Only once the gyro bias is
     // initialised (until then the bias still changes between pairs, rebvio.cpp:146-160). Not with a point-cloud callback: the
     // cloud shows the new map in THIS pair's frame, so the next pair's _begin launches its rotation itself.
+    // Nor with a keyframe-pose callback: snapshot and pose take the new map in this pair's frame as well.
     float Rnext[9];
     bool have_next = false;
     rebvio::EdgeMap::SharedPtr next_map;
@@ -557,7 +571,7 @@ void Rebvio::stateEstimationProcess() {
       std::lock_guard<std::mutex> guard(edge_map_buffer_mutex_);
       if (edge_map_buffer_.size() >= 2) {
         next_map = edge_map_buffer_[1];
-        if (imu_state_.initialized && !want_cloud) {
+        if (imu_state_.initialized && !want_cloud && !want_kf_pose) {
           store3(next_map->imu().R(), Rnext);
           have_next = true;
         }
@@ -582,8 +596,21 @@ void Rebvio::stateEstimationProcess() {
     }
     // Rebvio::requestKeyframe: the new map is marked behind this pair's second half (which writes the previous keyframe's ids into
     // it), in front of the next pair's first half (which hands the ids on)
-    if (keyframe_requested_.exchange(false)) new_edge_map->markKeyframe();
+    if (keyframe_requested_.exchange(false)) {
+      new_edge_map->markKeyframe();
+      if (want_kf_pose) {  // the keyframe as it is now, right behind its mark; the previous one goes
+        kf_snapshot = new_edge_map->keyframeSnapshot();
+        kf_pose_warm = false;
+      }
+    }
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
+    // keyframe-pose callbacks: the new map against the keyframe, behind this pair's second half (the call waits for it)
+    bool have_kf_pose = false;
+    if (want_kf_pose && kf_snapshot) {
+      kf_pose_last = new_edge_map->keyframePose(kf_snapshot, types::KfPoseOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
+      kf_pose_warm = kf_pose_last.status == 0;
+      have_kf_pose = true;
+    }
     timers.lap(2);
 
     if (!want_cloud) integrate_pose();
@@ -600,6 +627,8 @@ void Rebvio::stateEstimationProcess() {
     pending.new_map = new_edge_map;
     pending.cloud_pose = cloud_pose;
     pending.clouds = clouds;
+    pending.have_kf_pose = have_kf_pose;
+    pending.kf_pose = kf_pose_last;
     timers.lap(3);
     timers.end_pair();
     timers.n++;

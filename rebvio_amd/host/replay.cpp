@@ -11,6 +11,9 @@
 // little-endian PLY file PREFIX<ts_us>.ply with the vertex properties x, y, z, intensity (io::writePointCloudPly).
 // --cloud-dry: the callback is registered and counts points, no file is written (what the callback costs the pipeline:
 // tools/cloud_rate.py).
+// --kf-pose FILE [--kf-every N]: the pose of every tracked map relative to the keyframe (Rebvio::registerKeyframePoseCallback), one
+// line per record that has one: ts_us status used R (9 values, row-major) t (3 values). A keyframe is requested before the first
+// frame and again after every N-th record (default 10).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -23,7 +26,8 @@
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
-  std::string asl, raw, imu, out, mask_png, cloud_prefix;
+  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path;
+  int kf_every = 10;
   int W = 0, H = 0;
   size_t first = 0, count = (size_t)-1;
   uint64_t dt = 50000;
@@ -32,7 +36,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] --out file\n", argv[0]);
+                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [--kf-pose FILE [--kf-every N]] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -60,6 +64,8 @@ int main(int argc, char** argv) {
     }
     else if (a == "--cloud") cloud_prefix = next();
     else if (a == "--cloud-dry") cloud_dry = true;
+    else if (a == "--kf-pose") kf_pose_path = next();
+    else if (a == "--kf-every") kf_every = std::atoi(next());
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
     else if (a == "--camera") {
@@ -71,7 +77,7 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if ((asl.empty() == raw.empty()) || out.empty()) return usage();
+  if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1) return usage();
   try {
     std::unique_ptr<rebvio::io::StreamSource> src;
     if (!asl.empty()) src.reset(new rebvio::io::EurocReader(asl, "cam0", "imu0", colour));
@@ -123,7 +129,25 @@ int main(int argc, char** argv) {
       t_last = std::chrono::steady_clock::now();
       if (n_odo == 0) t_first = t_last;
       ++n_odo;
+      if (!kf_pose_path.empty() && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
     });
+    std::FILE* kf_pose_file = nullptr;
+    size_t n_poses = 0;
+    if (!kf_pose_path.empty()) {
+      kf_pose_file = std::fopen(kf_pose_path.c_str(), "w");
+      if (!kf_pose_file) {
+        std::fprintf(stderr, "error: cannot write %s\n", kf_pose_path.c_str());
+        return 1;
+      }
+      rebvio.registerKeyframePoseCallback([&](uint64_t ts_us, const rebvio::types::KfPose& p) {
+        std::fprintf(kf_pose_file, "%llu %d %d", (unsigned long long)ts_us, p.status, p.used);
+        for (double v : p.R) std::fprintf(kf_pose_file, " %.17g", v);
+        for (double v : p.t) std::fprintf(kf_pose_file, " %.17g", v);
+        std::fprintf(kf_pose_file, "\n");
+        ++n_poses;
+      });
+      rebvio.requestKeyframe();
+    }
     size_t n_clouds = 0, n_points = 0;
     if (!cloud_prefix.empty() || cloud_dry)
       rebvio.registerPointCloudCallback([&](const rebvio::types::PointCloud& pc) {
@@ -137,6 +161,10 @@ int main(int argc, char** argv) {
     rebvio.waitIdle();
     std::fprintf(stderr, "frames=%zu odometry=%zu running=%d\n", n, n_odo, (int)rebvio.running());
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
+    if (kf_pose_file) {
+      std::fclose(kf_pose_file);
+      std::fprintf(stderr, "kf_poses=%zu\n", n_poses);
+    }
     if (n_odo > 1) {  // wall clock between the first and the last published odometry: the whole class, input thread included
       const double sec = std::chrono::duration<double>(t_last - t_first).count();
       std::fprintf(stderr, "[replay] %zu odometry records in %.3f s = %.0f frames/s (wall clock, first to last record)\n", n_odo, sec,
