@@ -5,7 +5,7 @@
  * order and its float/double promotion rules. Build with -ffp-contract=off (no FMA fusing) so
  * results are machine independent and bit-comparable with the HIP parity path.
  *
- * PARITY UNPINNED (no reference golden vectors exist for this path).
+ * Pinned bit for bit by the reference's own compiled hot-path sources (tests/test_reference_pin.py).
  *
  * Decisions for undefined behaviour in the reference, applied here AND in the
  * HIP kernels:

@@ -5,11 +5,12 @@
  * hot path (baumlin/rebvio: scale_space.cpp, edge_detector.cpp, edge_map.cpp, core.hpp
  * DistanceField, core.cpp:33-262,417-456, and the call order of rebvio.cpp:119-292).
  *
- * PARITY UNPINNED: the reference holds no golden vector / KAT for this path (its only
- * fixture is an absent git-LFS bag) and cannot be compiled here (TooN,
- * OpenCV, spdlog absent). The oracle is therefore pinned only by (i) the analytic cases in
- * tests/test_oracle_analytic.py and (ii) the one reference KAT that exists
- * (rebvio/test/test_rebvio.cpp:8-17, estimateLs4Acceleration — host glue, not hot path).
+ * PINNED BY THE REFERENCE'S OWN CODE for the hot path: tests/test_reference_pin.py compares this library, bit for bit, with
+ * oracle/_ref/librebvio_ref.so - the reference's scale_space.cpp, edge_detector.cpp, edge_map.cpp and core.cpp compiled unmodified
+ * against the stand-in headers of oracle/ref_shim/ (oracle/Makefile, target ref). What stays unpinned - TooN's and OpenCV's
+ * arithmetic as the stand-ins restate it, the SVD solve, rebvio.cpp's pair glue and threading, sab_estimator.cpp, the effect of the
+ * reference's -march=native - is listed in DESIGN.md section 2. The glue keeps the pins it had: the analytic cases in
+ * tests/test_oracle_analytic.py and the one reference KAT that exists (rebvio/test/test_rebvio.cpp:8-17, estimateLs4Acceleration).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
  */

@@ -208,6 +208,24 @@ def assert_crowded_and_sparse(om, rows, cols, search_range=40, what=""):
     return lb
 
 
+def half_pixel_keylines(kl, W, H):
+    """kl (at least 48 keylines of a W x H frame) with its first 48 keylines moved onto half-integer positions at and near the four borders, gradients along the axes: every
+    cell coordinate pos + r * unit is then a tie of std::round (getIndex, core.hpp:66-71), -0.5 (which rounds away from zero, out of
+    the image) and rows - 0.5 / cols - 0.5 among them."""
+    out = kl.copy()
+    k = np.arange(48)
+    side = k % 4
+    along = (5 + 3 * (k // 4)).astype(np.float32) + np.float32(0.5)
+    x = np.where(side == 0, 0.5, np.where(side == 1, W - 1.5, along)).astype(np.float32)
+    y = np.where(side == 2, 0.5, np.where(side == 3, H - 1.5, along)).astype(np.float32)
+    g = (1.0 + 0.25 * (k % 5)).astype(np.float32)
+    out["pos"][:48, 0], out["pos"][:48, 1] = x, y
+    out["gradient"][:48, 0] = np.where(side < 2, np.where(k % 8 < 4, g, -g), 0)
+    out["gradient"][:48, 1] = np.where(side >= 2, np.where(k % 8 < 4, g, -g), 0)
+    out["gradient_norm"][:48] = g
+    return out
+
+
 def noise_frames(W, H, n, seed):
     rng = np.random.default_rng(seed)
     return rng.integers(0, 256, (n, H, W)).astype(np.uint8)
@@ -759,6 +777,21 @@ def B():
     from rebvio_amd import backend
     backend.lib()
     return backend
+
+
+@pytest.fixture(scope="session")
+def ref_mod():
+    """oracle/ref_py with oracle/_ref/librebvio_ref.so loaded: the reference's own hot-path sources, compiled. Where the reference
+    checkout is present the library is (re)built from it and a failing build fails the test; where it is absent a library that
+    travelled with the tree is used as it is. Skips only when there is neither."""
+    from oracle import ref_py
+    if ref_py.have_reference():
+        ref_py.build()
+        assert os.path.exists(ref_py.LIB_PATH), "make -C oracle ref left no library"
+    elif not os.path.exists(ref_py.LIB_PATH):
+        pytest.skip("neither oracle/_ref/librebvio_ref.so nor a reference checkout to build it from")
+    ref_py.lib()
+    return ref_py
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,6 @@
 """CPU tests of the oracle against analytically known answers and the one KAT the reference
-holds (rebvio/test/test_rebvio.cpp:8-17). The reference has no golden vectors for the hot path ("parity unpinned"):
-these cases are what pins the restatement."""
+holds (rebvio/test/test_rebvio.cpp:8-17). The reference has no golden vectors for the hot path; these cases pin the
+restatement independently of tests/test_reference_pin.py, which compares it with the reference's compiled sources."""
 import numpy as np
 import pytest
 
