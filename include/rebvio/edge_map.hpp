@@ -18,6 +18,8 @@ struct rebvio_hip_kf_snapshot;
 
 namespace rebvio {
 
+class EdgeMap;
+
 // A keyframe as it was when the snapshot was taken (EdgeMap::keyframeSnapshot): owns the backend's handle and releases it; the
 // handle's device memory goes with its context at the latest. Move-only.
 class KeyframeSnapshot {
@@ -38,6 +40,9 @@ class KeyframeSnapshot {
   KeyframeSnapshot(const KeyframeSnapshot&) = delete;
   KeyframeSnapshot& operator=(const KeyframeSnapshot&) = delete;
   void reset();
+  // keeps gradient / gradient_norm of `map`'s keylines next to the snapshot, for the gradient test of EdgeMap::keyframeAlign
+  // (rebvio_hip_kf_snapshot_add_normals; queued on the track stream). `map` is the map the snapshot was taken from, where it was taken.
+  void addNormals(const rebvio::EdgeMap& map);
   explicit operator bool() const { return handle_ != nullptr; }
   rebvio_hip_kf_snapshot* handle() const { return handle_; }
 
@@ -100,6 +105,12 @@ class EdgeMap {
   rebvio::KeyframeSnapshot keyframeSnapshot();
   rebvio::types::KfPose keyframePose(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfPoseOpts& opts = rebvio::types::KfPoseOpts(),
                                      const rebvio::types::KfPose* guess = nullptr);
+  // keyframeAlign(snapshot): the same pose, with the associations taken from THIS map's distance field instead of the
+  // correspondence chain (rebvio_hip_map_keyframe_align; synchronous, from the tracking thread): any detected map of the
+  // snapshot's context can be aligned, whatever has happened to the chain. assoc: per keyframe keyline the keyline of this map it
+  // was associated with at the returned pose, or -1.
+  rebvio::types::KfPose keyframeAlign(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfAlignOpts& opts = rebvio::types::KfAlignOpts(),
+                                      const rebvio::types::KfPose* guess = nullptr, std::vector<int>* assoc = nullptr);
 
   // --- backend plumbing (not part of the reference surface) ---
   // `keepalive` owns the backend context the handle belongs to (backend::Session): a map kept by an edge-image consumer

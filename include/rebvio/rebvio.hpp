@@ -68,6 +68,12 @@ class Rebvio {
   // half before it goes on; the odometry does not change by a digit. Without one the thread runs exactly the calls it ran.
   // Register before the first frame is handed in.
   void registerKeyframePoseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfPose&)> cb);
+  // addition: while this is on (default: off) and a keyframe-pose callback is registered, requestKeyframe also keeps the keyframe's
+  // normals behind the snapshot (KeyframeSnapshot::addNormals) and the pose handed to the callback is the alignment of the snapshot
+  // to the new map through the new map's distance field (EdgeMap::keyframeAlign; rebvio_hip.h defines it) instead of the pose from
+  // the correspondence chain, warm-started exactly as that one is: it does not thin out with the chain. Off, the thread runs
+  // exactly the calls it runs without this; the odometry does not change by a digit either way. Callable from any thread.
+  void setKeyframeAlign(bool on) { keyframe_align_ = on; }
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -108,6 +114,7 @@ class Rebvio {
   std::vector<std::function<void(uint64_t, int, int)>> keyframe_callbacks_;
   std::vector<std::function<void(uint64_t, const rebvio::types::KfPose&)>> keyframe_pose_callbacks_;
   std::atomic<bool> keyframe_requested_{false};
+  std::atomic<bool> keyframe_align_{false};
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };
 

@@ -63,6 +63,18 @@ struct KfPose {
 };
 static_assert(sizeof(KfPose) == 55 * 8 + 16, "KfPose must stay layout-compatible with rebvio_hip_kf_pose");
 
+// Options of EdgeMap::keyframeAlign, layout-compatible with the C-ABI's rebvio_hip_kf_align_opts (rebvio_hip.h defines every term). The
+// defaults are rebvio_hip_default_kf_align_opts's; max_dist -1 stands for the context's search_range (EdgeMap::keyframeAlign fills it in).
+struct KfAlignOpts {
+  CloudFilter kf_filter;  // applied to the keyframe keylines
+  double huber_px{2.0};
+  double min_cos{0.9};    // the gradient test, where the snapshot has a non-zero normal; -1 disables it
+  int max_dist{-1};       // 0..search_range cells between the projection and the keyline that owns its cell
+  int max_iter{8};        // 0..32; 0: the sums at the guess only
+  int min_used{12};
+};
+static_assert(sizeof(KfAlignOpts) == 48, "KfAlignOpts must stay layout-compatible with rebvio_hip_kf_align_opts");
+
 // What a point-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
   uint64_t ts_us;            // the odometry record's stamp (= the map's)

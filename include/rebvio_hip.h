@@ -29,7 +29,9 @@ extern "C" {
  *    the keyframe entries rebvio_hip_map_mark_keyframe, rebvio_hip_keyframe_next, rebvio_hip_map_keyframe_matches and their struct
  *    rebvio_hip_kf_match; the keyframe snapshot and pose entries rebvio_hip_map_keyframe_snapshot, rebvio_hip_kf_snapshot_release,
  *    rebvio_hip_kf_snapshot_download, rebvio_hip_default_kf_pose_opts, rebvio_hip_map_keyframe_pose, their structs
- *    rebvio_hip_kf_pose_opts / rebvio_hip_kf_pose and the test hook rebvio_hip_test_kf_pose_host. */
+ *    rebvio_hip_kf_pose_opts / rebvio_hip_kf_pose and the test hook rebvio_hip_test_kf_pose_host; the snapshot normals
+ *    rebvio_hip_kf_snapshot_add_normals / _download_normals and the alignment entries rebvio_hip_default_kf_align_opts,
+ *    rebvio_hip_map_keyframe_align, their struct rebvio_hip_kf_align_opts and the test hook rebvio_hip_test_kf_align_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -381,6 +383,74 @@ int rebvio_hip_map_keyframe_pose(rebvio_hip_map* map, rebvio_hip_kf_snapshot* sn
 int rebvio_hip_test_kf_pose_host(float fm, const float* snap_prs4, const unsigned* snap_matches, int kf_size, const float* cur_pos_img,
                                  const float* cur_gradient, int n_cur, const rebvio_hip_kf_match* records, int n_rec,
                                  const rebvio_hip_kf_pose_opts* opts, const double R0[9], const double t0[3], rebvio_hip_kf_pose* out);
+
+/* Normals for a snapshot. rebvio_hip_kf_snapshot_add_normals queues one kernel (k_kf_snapshot_normals, one workgroup of 256 per 256
+ * keylines, both sizes read on the device) on the TRACK stream in call order and waits for nothing on the host: for
+ * i < min(map size, snapshot size)  n_i = (gradient_i.x / gradient_norm_i, gradient_i.y / gradient_norm_i), two fp32 IEEE divisions,
+ * and (0, 0) for every other slot and wherever gradient_norm_i is not > 0. The first call gives the snapshot one more device buffer
+ * (8 bytes per slot, one more live resource, freed with the snapshot or its context); a later call overwrites it. The calling rules
+ * are the snapshot's: take the normals where the mark and the snapshot are taken, from the map the snapshot was taken from (the
+ * caller's contract). -7: the map is promised to R_prior_next (its gradients are already rotated); -3, before the device is touched:
+ * null snapshot or map, a map of another context; -10: the context has been destroyed.
+ * rebvio_hip_kf_snapshot_download_normals (synchronous, track-side): *n = the snapshot's size, min(n, cap) pairs written to n2.
+ * -7: no normals were added; -3: null snapshot or n, negative cap, null n2 with cap > 0; -10. */
+int rebvio_hip_kf_snapshot_add_normals(rebvio_hip_kf_snapshot* snap, rebvio_hip_map* map);
+int rebvio_hip_kf_snapshot_download_normals(rebvio_hip_kf_snapshot* snap, float* n2, int cap, int* n);
+
+/* Alignment of a keyframe snapshot to a map through the map's distance field: the pose X_cur = R X_kf + t of
+ * rebvio_hip_map_keyframe_pose, but with the associations found as Core::tryVel finds them (rebvio/src/core.cpp) - a keyframe keyline
+ * is projected under the current pose and takes the keyline of the map that owns the cell it lands in - instead of the
+ * match_id_keyframe chain. Only the map's distance field, pos and gradient / gradient_norm as DistanceField::build formed it are
+ * read: tracking never writes them, so any detected map of the snapshot's context can be aligned at any time, a map promised to
+ * R_prior_next included. fp64 behind the loads, every + - * / sqrt and floor one IEEE operation in the order written here.
+ * One term per keyframe keyline j < size (`candidates` = the snapshot's size), with fm, cx, cy, rows, cols, search_range of the
+ * context, (R, t) the current pose and pos_img_j, rho_j, sigma_rho_j, matches_j, and the normal (nx_j, ny_j) where normals were
+ * added, of the snapshot. The term is used when ALL of these hold (positive tests: a NaN skips it):
+ *   1. keyframe keyline j passes kf_filter (the test of rebvio_hip_map_keyframe_pose).
+ *   2. a, b, rho, Z, Y as in rebvio_hip_map_keyframe_pose;  Y.z > 0.
+ *   3. p.x = Y.x / Y.z;  p.y = Y.y / Y.z;  u = (double)fm * p.x + (double)cx;  v = (double)fm * p.y + (double)cy;
+ *      x = floor(u + 0.5);  y = floor(v + 0.5);  1 <= x <= cols - 2  and  1 <= y <= rows - 2  (tested in double, before any conversion).
+ *   4. key = df[y * cols + x] is not empty; i = the owning keyline and dist = its distance in cells, as rebvio_hip_map_distance_field
+ *      reports them; dist <= max_dist.
+ *   5. n_i = unit_i (the map's gradient_i / gradient_norm_i as the field was built from). Where the snapshot has normals and
+ *      min_cos > -1:  m.x = R[0] * nx_j + R[1] * ny_j;  m.y = R[3] * nx_j + R[4] * ny_j;  mm = m.x * m.x + m.y * m.y;
+ *      nn = n_i.x * n_i.x + n_i.y * n_i.y;  when mm > 0 and nn > 0:  m.x * n_i.x + m.y * n_i.y >= (min_cos * sqrt(mm)) * sqrt(nn).
+ *      Otherwise (no normals, min_cos == -1, a zero normal on either side) no gate is applied.
+ *   6. q.x = pos_i.x - cx;  q.y = pos_i.y - cy  (fp32 subtractions); then the term of rebvio_hip_map_keyframe_pose with q for
+ *      pos_img_i and n_i for gradient_i, with its own skips (g2 > 0 and < infinity, Y.z > 0).
+ * assoc[j] = i when the term is used, -1 otherwise; every evaluation writes all of it, and assoc_host (NULL, or room for the
+ * snapshot's size) gets the last evaluation's, i.e. the associations at the returned pose.
+ * The 28 sums, their summation tree (one thread per keyframe keyline, workgroups of 256), the Gauss-Newton step, status 0 / 2 / 3,
+ * H, g, cost, used and iterations are those of rebvio_hip_map_keyframe_pose: max_iter + 1 evaluations queued back to back,
+ * 2 * max_iter + 2 launches (none for correspondences), no host wait in between and no early exit. The associations change from
+ * evaluation to evaluation; used is tested against min_used at the first one only, and a later H that does not factor gives 2.
+ * A snapshot of size 0: status 3, pose = guess, nothing launched.
+ * Synchronous and track-side; the map counts as used by the tracker afterwards; the context's scratch (one allocation) is made at
+ * the first call. -3, before the device is touched: null map, snapshot or output, a non-finite R0 or t0, an invalid kf_filter,
+ * huber_px not > 0, min_cos outside [-1, 1] or NaN, max_dist outside 0..search_range, max_iter outside 0..32, min_used outside
+ * 0..65536, a snapshot of another context; -10: the context has been destroyed; -7: the map's field is not detection's (none built,
+ * or the keylines were uploaded: unit is detection's).
+ * rebvio_hip_test_kf_align_host (test hook, touches no device) runs the same statements on the host from caller arrays - the
+ * camera, the snapshot's prs4 / matches and normals (or NULL) for kf_size keyframe keylines, the map's pos and unit (n_cur x 2 floats
+ * each), the field as rebvio_hip_map_distance_field returns it (rows * cols ids, -1 = empty, and distances) - and sums the terms in
+ * index order; opts NULL = the defaults with max_dist = search_range (opts->max_dist is tested against search_range). -3: a null
+ * array, a field id outside the keyline arrays, or options / a guess the device entry refuses. */
+typedef struct rebvio_hip_kf_align_opts { /* defaults from rebvio_hip_default_kf_align_opts */
+  rebvio_hip_cloud_filter kf_filter;     /* keyframe side, as in rebvio_hip_kf_pose_opts */
+  double huber_px;                       /* default 2.0 */
+  double min_cos;                        /* default 0.9; used only where the snapshot has a non-zero normal; -1 disables */
+  int max_dist;                          /* 0..search_range cells; default = the context's search_range (no gate) */
+  int max_iter, min_used;                /* as rebvio_hip_kf_pose_opts: 0..32 default 8; 0..65536 default 12 */
+} rebvio_hip_kf_align_opts;
+void rebvio_hip_default_kf_align_opts(rebvio_hip_ctx* ctx /*NULL: max_dist = 40, the default search_range*/, rebvio_hip_kf_align_opts* opts);
+int rebvio_hip_map_keyframe_align(rebvio_hip_map* map, rebvio_hip_kf_snapshot* snap, const rebvio_hip_kf_align_opts* opts,
+                                  const double R0[9] /*NULL = identity*/, const double t0[3] /*NULL = 0*/, rebvio_hip_kf_pose* out,
+                                  int* assoc_host /*NULL or snapshot-size ints*/);
+int rebvio_hip_test_kf_align_host(float fm, float cx, float cy, int rows, int cols, int search_range, const float* snap_prs4,
+                                  const unsigned* snap_matches, const float* snap_normals /*NULL: none*/, int kf_size,
+                                  const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
+                                  const rebvio_hip_kf_align_opts* opts, const double R0[9], const double t0[3], rebvio_hip_kf_pose* out,
+                                  int* assoc /*NULL or kf_size ints*/);
 
 /* Test hook: overwrite the device keylines (count must equal the map size). */
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n);

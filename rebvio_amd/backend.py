@@ -81,6 +81,12 @@ class KfPoseOpts(C.Structure):
     _fields_ = [("kf_filter", CloudFilter), ("huber_px", C.c_double), ("max_iter", C.c_int), ("min_used", C.c_int)]
 
 
+class KfAlignOpts(C.Structure):
+    """rebvio_hip_kf_align_opts (Map.keyframe_align); defaults from default_kf_align_opts"""
+    _fields_ = [("kf_filter", CloudFilter), ("huber_px", C.c_double), ("min_cos", C.c_double), ("max_dist", C.c_int),
+                ("max_iter", C.c_int), ("min_used", C.c_int)]
+
+
 class KfPose(C.Structure):
     """rebvio_hip_kf_pose: X_cur = R X_kf + t, the sums at that pose, and the counters"""
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("H", C.c_double * 36), ("g", C.c_double * 6), ("cost", C.c_double),
@@ -127,6 +133,13 @@ SIGNATURES = {
     "rebvio_hip_kf_snapshot_download": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint), C.c_int, _ip]),
     "rebvio_hip_default_kf_pose_opts": (None, [C.POINTER(KfPoseOpts)]),
     "rebvio_hip_map_keyframe_pose": (C.c_int, [_vp, _vp, C.POINTER(KfPoseOpts), _dp, _dp, C.POINTER(KfPose)]),
+    "rebvio_hip_kf_snapshot_add_normals": (C.c_int, [_vp, _vp]),
+    "rebvio_hip_kf_snapshot_download_normals": (C.c_int, [_vp, _fp, C.c_int, _ip]),
+    "rebvio_hip_default_kf_align_opts": (None, [_vp, C.POINTER(KfAlignOpts)]),
+    "rebvio_hip_map_keyframe_align": (C.c_int, [_vp, _vp, C.POINTER(KfAlignOpts), _dp, _dp, C.POINTER(KfPose), _ip]),
+    "rebvio_hip_test_kf_align_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
+                                                C.c_int, _fp, _fp, C.c_int, _ip, _ip, C.POINTER(KfAlignOpts), _dp, _dp,
+                                                C.POINTER(KfPose), _ip]),
     "rebvio_hip_test_kf_pose_host": (C.c_int, [C.c_float, _fp, C.POINTER(C.c_uint), C.c_int, _fp, _fp, C.c_int, C.POINTER(KfMatch),
                                                C.c_int, C.POINTER(KfPoseOpts), _dp, _dp, C.POINTER(KfPose)]),
     "rebvio_hip_map_upload": (C.c_int, [_vp, _vp, C.c_int]),
@@ -377,6 +390,49 @@ def kf_pose_host(fm, prs4, kf_matches, cur_pos_img, cur_gradient, records, opts=
     return out
 
 
+def default_kf_align_opts(ctx=None, **over) -> KfAlignOpts:
+    """The library's defaults (rebvio_hip_default_kf_align_opts): max_dist is ctx's search_range (40, the default one, without a
+    context); kf_filter takes a CloudFilter or a dict of its fields to change."""
+    o = KfAlignOpts()
+    lib().rebvio_hip_default_kf_align_opts(ctx.h if ctx is not None else None, C.byref(o))
+    for k, v in over.items():
+        if k == "kf_filter" and not isinstance(v, CloudFilter):
+            for fk, fv in v.items():
+                setattr(o.kf_filter, fk, fv)
+        else:
+            setattr(o, k, v)
+    return o
+
+
+def kf_align_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normals, cur_pos, cur_unit, df_id, df_dist, opts=None, R0=None,
+                  t0=None):
+    """The solve of Map.keyframe_align on the host, from arrays (rebvio_hip_test_kf_align_host): the camera, a snapshot's download and
+    normals (or None), the map's pos / unit and its distance field as Map.distance_field returns it. Touches no device; the terms
+    are summed in index order. Returns (KfPose, assoc int32 [kf_size])."""
+    prs4 = np.ascontiguousarray(prs4, np.float32).reshape(-1, 4)
+    kf_matches = np.ascontiguousarray(kf_matches, np.uint32)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 2)
+    q = np.ascontiguousarray(cur_pos, np.float32).reshape(-1, 2)
+    u = np.ascontiguousarray(cur_unit, np.float32).reshape(-1, 2)
+    ids = np.ascontiguousarray(df_id, np.int32).reshape(-1)
+    dists = np.ascontiguousarray(df_dist, np.int32).reshape(-1)
+    assert len(prs4) == len(kf_matches) and len(q) == len(u) and (nrm is None or len(nrm) == len(prs4))
+    assert len(ids) == len(dists) == int(rows) * int(cols)
+    (kR, pR), (kt, pt) = _guess(R0, 9), _guess(t0, 3)
+    out = KfPose()
+    assoc = np.full(len(prs4), -1, np.int32)
+    up = C.POINTER(C.c_uint)
+    _chk(lib().rebvio_hip_test_kf_align_host(float(fm), float(cx), float(cy), int(rows), int(cols), int(search_range),
+                                             prs4.ctypes.data_as(_fp) if len(prs4) else None,
+                                             kf_matches.ctypes.data_as(up) if len(prs4) else None,
+                                             nrm.ctypes.data_as(_fp) if nrm is not None and len(nrm) else None, len(prs4),
+                                             q.ctypes.data_as(_fp) if len(q) else None, u.ctypes.data_as(_fp) if len(q) else None, len(q),
+                                             ids.ctypes.data_as(_ip) if len(ids) else None, dists.ctypes.data_as(_ip) if len(ids) else None,
+                                             opts, pR, pt, C.byref(out), assoc.ctypes.data_as(_ip) if len(assoc) else None))
+    del kR, kt
+    return out, assoc
+
+
 class KfSnapshot:
     """A keyframe as it was when marked (rebvio_hip_map_keyframe_snapshot): download() its keylines, release() when done."""
 
@@ -392,6 +448,21 @@ class KfSnapshot:
             _chk(lib().rebvio_hip_kf_snapshot_download(self.h, prs.ctypes.data_as(_fp), mt.ctypes.data_as(C.POINTER(C.c_uint)), n.value,
                                                        C.byref(n)))
         return prs, mt
+
+    def add_normals(self, map):
+        """Keeps gradient / gradient_norm of `map`'s keylines next to the snapshot (rebvio_hip_kf_snapshot_add_normals; queued on the
+        track stream, returns at once): the gradient test of Map.keyframe_align. `map` is the map the snapshot was taken from, where
+        it was taken."""
+        _chk(lib().rebvio_hip_kf_snapshot_add_normals(self.h, map.h))
+
+    def normals(self):
+        """float32 [n, 2]: the normals add_normals kept (error -7 when none were added)"""
+        n = C.c_int()
+        _chk(lib().rebvio_hip_kf_snapshot_download_normals(self.h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 2), np.float32)
+        if n.value:
+            _chk(lib().rebvio_hip_kf_snapshot_download_normals(self.h, out.ctypes.data_as(_fp), n.value, C.byref(n)))
+        return out
 
     def release(self):
         if self.h:
@@ -547,6 +618,23 @@ class Map:
         _chk(lib().rebvio_hip_map_keyframe_pose(self.h, snap.h, opts, pR, pt, C.byref(out)))
         del kR, kt
         return out
+
+    def keyframe_align(self, snap: KfSnapshot, opts=None, R0=None, t0=None, want_assoc=False):
+        """Aligns the keyframe `snap` to this map through this map's distance field, X_cur = R X_kf + t
+        (rebvio_hip_map_keyframe_align): no correspondence chain is needed, any detected map of the snapshot's context will do.
+        opts: a KfAlignOpts or None for the defaults; R0 / t0: the guess (None: identity / zero). want_assoc: also the int32 array of
+        the keyline of this map every keyframe keyline was associated with at the returned pose (-1: none)."""
+        (kR, pR), (kt, pt) = _guess(R0, 9), _guess(t0, 3)
+        out = KfPose()
+        assoc = None
+        if want_assoc:
+            n = C.c_int()
+            _chk(lib().rebvio_hip_kf_snapshot_download(snap.h, None, None, 0, C.byref(n)))
+            assoc = np.full(n.value, -1, np.int32)
+        _chk(lib().rebvio_hip_map_keyframe_align(self.h, snap.h, opts, pR, pt, C.byref(out),
+                                                 assoc.ctypes.data_as(_ip) if want_assoc and len(assoc) else None))
+        del kR, kt
+        return (out, assoc) if want_assoc else out
 
     def upload(self, kl: np.ndarray):
         kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)

@@ -283,6 +283,12 @@ struct rebvio_hip_kf_snapshot {
   unsigned* matches = nullptr;
   int* n_dev = nullptr;
   int n_host = -1;             // the size, once a synchronous entry has fetched it
+  // rebvio_hip_kf_snapshot_add_normals: a second buffer of `own`, one float2 per slot, made at the first call (normals_buf) and
+  // handed to its readers (normals) only once a kernel that fills it has been queued: a call that fails in between leaves a
+  // snapshot without normals, not one with uninitialised ones. nor_mu guards both pointers in every entry that touches them.
+  std::mutex nor_mu;
+  void* normals_buf = nullptr;
+  void* normals = nullptr;
 };
 
 // A finished pair's record as the caller gets it.
@@ -505,6 +511,12 @@ struct rebvio_hip_ctx {
   rebvio_hip_kf_pose* kfp_state = nullptr;
   double* kfp_part = nullptr;  // (views into kfp_state's allocation)
   int* kfp_used = nullptr;
+  // scratch of rebvio_hip_map_keyframe_align (ONE allocation on first use, kept; a track-side entry): the result block, kMaxRecBlocks
+  // partials of 28 doubles, as many used counts, keylines_max association words
+  rebvio_hip_kf_pose* kfa_state = nullptr;
+  double* kfa_part = nullptr;  // (views into kfa_state's allocation)
+  int* kfa_used = nullptr;
+  int* kfa_assoc = nullptr;
 };
 
 namespace {
@@ -2081,6 +2093,194 @@ int rebvio_hip_test_kf_pose_host(float fm, const float* snap_prs4, const unsigne
       if (!kfp::term(fm, k4[0], k4[1], k4[2], cur_pos_img[2 * (size_t)i], cur_pos_img[2 * (size_t)i + 1], cur_gradient[2 * (size_t)i],
                      cur_gradient[2 * (size_t)i + 1], res.R, res.t, o.huber_px, v))
         continue;
+      for (int k = 0; k < kfp::kSums; ++k) S[k] = S[k] + v[k];
+      ++used;
+    }
+    kfp::step(S, used, it == 0, it == o.max_iter, o.min_used, ws, &res);
+  }
+  *out = res;
+  return 0;
+}
+
+int rebvio_hip_kf_snapshot_add_normals(rebvio_hip_kf_snapshot* sn, rebvio_hip_map* m) {
+  if (!sn || !m) return fail_msg("kf_snapshot_add_normals: null snapshot or map", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (sn->life != m->life) {
+    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+    return fail_msg("kf_snapshot_add_normals: map of another context", -3);
+  }
+  rebvio_hip_ctx* c = m->ctx;
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg("kf_snapshot_add_normals: the map was handed to track_pair_finish_async with R_prior_next and its gradients are rotated "
+                    "for the next pair; add the normals where the snapshot is taken", -7);
+  HIPCHK(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(sn->nor_mu);
+  if (!sn->normals_buf) {
+    char* b = nullptr;
+    const hipError_t e = sn->own.device_bytes(&b, (size_t)div_up(c->P.keylines_max, 256) * 256 * sizeof(float2));
+    if (e != hipSuccess) return fail("kf_snapshot_add_normals: device buffer", e);
+    sn->normals_buf = b;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  launch_kf_snapshot_normals(c->s_trk, c->K, m->d, sn->n_dev, sn->normals_buf);
+  HIPCHK(hipGetLastError());
+  sn->normals = sn->normals_buf;  // (every slot is written by the kernel just queued, in front of any reader on the track stream)
+  return 0;
+}
+
+int rebvio_hip_kf_snapshot_download_normals(rebvio_hip_kf_snapshot* sn, float* n2, int cap, int* n) {
+  if (!sn || !n) return fail_msg("kf_snapshot_download_normals: null snapshot or n", -3);
+  if (cap < 0 || (cap > 0 && !n2)) return fail_msg("kf_snapshot_download_normals: cap pairs need an output buffer (cap >= 0)", -3);
+  *n = 0;
+  const std::shared_ptr<LifeBlock> life = sn->life;
+  std::shared_lock<std::shared_mutex> lk(life->mu);
+  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  rebvio_hip_ctx* c = sn->ctx;
+  const void* normals;
+  {
+    std::lock_guard<std::mutex> nl(sn->nor_mu);
+    normals = sn->normals;
+  }
+  if (!normals) return fail_msg("kf_snapshot_download_normals: no normals were added to this snapshot (rebvio_hip_kf_snapshot_add_normals)", -7);
+  HIPCHK(hipSetDevice(c->device));
+  int rc = snapshot_size(c, sn);
+  if (rc) return rc;
+  const int k = sn->n_host < cap ? sn->n_host : cap;
+  if (k > 0) {
+    HIPCHK(hipMemcpyAsync(n2, normals, (size_t)k * sizeof(float2), hipMemcpyDeviceToHost, c->s_trk));
+    rc = trk_sync(c);
+    if (rc) return rc;
+  }
+  *n = sn->n_host;
+  return 0;
+}
+
+void rebvio_hip_default_kf_align_opts(rebvio_hip_ctx* c, rebvio_hip_kf_align_opts* o) {
+  std::memset(o, 0, sizeof(*o));
+  rebvio_hip_default_cloud_filter(&o->kf_filter);
+  o->huber_px = 2.0;
+  o->min_cos = 0.9;
+  o->max_dist = c ? (int)c->P.search_range : 40;
+  o->max_iter = 8;
+  o->min_used = 12;
+}
+
+namespace {
+int check_kf_align_args(const char* who, const rebvio_hip_kf_align_opts& o, int search_range, const double* R0, const double* t0) {
+  rebvio_hip_kf_pose_opts po;
+  po.kf_filter = o.kf_filter;
+  po.huber_px = o.huber_px;
+  po.max_iter = o.max_iter;
+  po.min_used = o.min_used;
+  const int rc = check_kf_pose_args(who, po, R0, t0);
+  if (rc) return rc;
+  if (!(o.min_cos >= -1.0 && o.min_cos <= 1.0)) return fail_msg((std::string(who) + ": min_cos outside [-1, 1]").c_str(), -3);
+  if (o.max_dist < 0 || o.max_dist > search_range) return fail_msg((std::string(who) + ": max_dist outside 0..search_range").c_str(), -3);
+  return 0;
+}
+}  // namespace
+
+static_assert(sizeof(rebvio_hip_kf_align_opts) == 48, "filter, two doubles, three ints, padding");
+
+int rebvio_hip_map_keyframe_align(rebvio_hip_map* m, rebvio_hip_kf_snapshot* sn, const rebvio_hip_kf_align_opts* opts, const double* R0,
+                                  const double* t0, rebvio_hip_kf_pose* out, int* assoc_host) {
+  if (!m || !sn || !out) return fail_msg("map_keyframe_align: null map, snapshot or output", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (sn->life != m->life) {
+    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+    return fail_msg("map_keyframe_align: snapshot of another context", -3);
+  }
+  rebvio_hip_ctx* c = m->ctx;
+  rebvio_hip_kf_align_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_kf_align_opts(c, &o);
+  int rc = check_kf_align_args("map_keyframe_align", o, (int)c->P.search_range, R0, t0);
+  if (rc) return rc;
+  if (!m->df_built || !m->raster_order)
+    return fail_msg("map_keyframe_align: the map's distance field is not detection's (none was built, or its keylines were uploaded)", -7);
+  HIPCHK(hipSetDevice(c->device));
+  rc = snapshot_size(c, sn);
+  if (rc) return rc;
+  const int kf_size = sn->n_host;
+  rebvio_hip_kf_pose start;
+  kf_pose_start(&start, R0, t0);
+  if (kf_size == 0) {  // nothing to align: nothing is launched
+    start.status = 3;
+    *out = start;
+    return 0;
+  }
+  if (!c->kfa_state) {
+    const size_t head = (sizeof(rebvio_hip_kf_pose) + 63) / 64 * 64, part = (size_t)kMaxRecBlocks * kfp::kSums * sizeof(double);
+    char* b = nullptr;
+    HIPCHK(c->own.device_bytes(&b, head + part + kMaxRecBlocks * sizeof(int) + (size_t)c->P.keylines_max * sizeof(int)));
+    c->kfa_state = reinterpret_cast<rebvio_hip_kf_pose*>(b);
+    c->kfa_part = reinterpret_cast<double*>(b + head);
+    c->kfa_used = reinterpret_cast<int*>(b + head + part);
+    c->kfa_assoc = c->kfa_used + kMaxRecBlocks;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready(c->s_trk, m));
+  HIPCHK(hipMemcpyAsync(c->kfa_state, &start, sizeof(start), hipMemcpyHostToDevice, c->s_trk));
+  const void* normals;
+  {
+    std::lock_guard<std::mutex> lk(sn->nor_mu);
+    normals = sn->normals;
+  }
+  for (int it = 0; it <= o.max_iter; ++it)
+    launch_kf_align_eval(c->s_trk, c->K, m->d, kf_size, sn->n_dev, sn->prs, sn->matches, normals, o.kf_filter, o.huber_px, o.min_cos,
+                         o.max_dist, it == 0, it == o.max_iter, o.min_used, c->kfa_state, c->kfa_part, c->kfa_used, c->kfa_assoc);
+  HIPCHK(hipGetLastError());
+  rebvio_hip_kf_pose res;
+  HIPCHK(hipMemcpyAsync(&res, c->kfa_state, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, c->kfa_assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  *out = res;
+  return 0;
+}
+
+int rebvio_hip_test_kf_align_host(float fm, float cx, float cy, int rows, int cols, int search_range, const float* snap_prs4,
+                                  const unsigned* snap_matches, const float* snap_normals, int kf_size, const float* cur_pos,
+                                  const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
+                                  const rebvio_hip_kf_align_opts* opts, const double* R0, const double* t0, rebvio_hip_kf_pose* out,
+                                  int* assoc) {
+  if (!out || kf_size < 0 || n_cur < 0 || rows < 0 || cols < 0 || (kf_size > 0 && (!snap_prs4 || !snap_matches)) ||
+      (n_cur > 0 && (!cur_pos || !cur_unit)) || ((size_t)rows * (size_t)cols > 0 && (!df_id || !df_dist)))
+    return fail_msg("test_kf_align_host: null array or negative size", -3);
+  rebvio_hip_kf_align_opts o;
+  if (opts) {
+    o = *opts;
+  } else {
+    rebvio_hip_default_kf_align_opts(nullptr, &o);
+    o.max_dist = search_range;
+  }
+  const int rc = check_kf_align_args("test_kf_align_host", o, search_range, R0, t0);
+  if (rc) return rc;
+  const size_t Pn = (size_t)rows * (size_t)cols;
+  for (size_t k = 0; k < Pn; ++k)
+    if (df_id[k] >= n_cur) return fail_msg("test_kf_align_host: a field id lies outside the keyline arrays", -3);
+  kfp::AlignMap am;
+  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
+  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
+  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
+  am.cap = n_cur;
+  rebvio_hip_kf_pose res;
+  kf_pose_start(&res, R0, t0);
+  res.candidates = kf_size;
+  if (kf_size == 0) res.status = 3;
+  for (int it = 0; kf_size > 0 && it <= o.max_iter; ++it) {
+    double S[kfp::kSums] = {}, v[kfp::kSums], ws[48];
+    int used = 0;
+    for (int j = 0; j < kf_size; ++j) {
+      const float* k4 = snap_prs4 + 4 * (size_t)j;
+      int i = -1;
+      if (kfp::filter_pass(o.kf_filter, k4[2], k4[3], snap_matches[j]))
+        i = kfp::align_term(am, k4[0], k4[1], k4[2], snap_normals != nullptr, snap_normals ? snap_normals[2 * (size_t)j] : 0.0f,
+                            snap_normals ? snap_normals[2 * (size_t)j + 1] : 0.0f, o.min_cos, o.max_dist, res.R, res.t, o.huber_px, v);
+      if (assoc) assoc[j] = i;
+      if (i < 0) continue;
       for (int k = 0; k < kfp::kSums; ++k) S[k] = S[k] + v[k];
       ++used;
     }

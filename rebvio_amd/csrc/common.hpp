@@ -338,6 +338,16 @@ void launch_kf_snapshot(hipStream_t s, const KParams& p, const MapDev& m, void* 
 void launch_kf_pose_eval(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const void* records_dev, const int* count_dev,
                          const void* snap_prs, const unsigned* snap_matches, const rebvio_hip_cloud_filter& flt, double huber, int first,
                          int last, int min_used, rebvio_hip_kf_pose* state_dev, double* part, int* part_used);
+// k_kf_snapshot_normals on stream s (rebvio_hip_kf_snapshot_add_normals): ceil(kmax / 256) * 256 float2 slots, gradient /
+// gradient_norm below min(map size, *snap_n), zeros elsewhere.
+void launch_kf_snapshot_normals(hipStream_t s, const KParams& p, const MapDev& m, const int* snap_n, void* normals);
+// One evaluation of rebvio_hip_map_keyframe_align on stream s: k_kf_align_sums over the kf_size (1..kmax) keylines of a snapshot
+// (snap_normals may be null) against m's distance field, pos and unit, then k_kf_pose_step. kf_size_dev = the same size in device
+// memory (the step stores it as `candidates`); state_dev / part / part_used as launch_kf_pose_eval; assoc = kmax ints.
+void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const int* kf_size_dev, const void* snap_prs,
+                          const unsigned* snap_matches, const void* snap_normals, const rebvio_hip_cloud_filter& flt, double huber,
+                          double min_cos, int max_dist, int first, int last, int min_used, rebvio_hip_kf_pose* state_dev, double* part,
+                          int* part_used, int* assoc);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 

@@ -63,6 +63,64 @@ RH_HD inline bool term(float fm, float kx, float ky, float rho_f, float qx_f, fl
   return true;
 }
 
+// ---- alignment through the distance field (rebvio_hip_map_keyframe_align; include/rebvio_hip.h is the definition) ----------------
+// What a term's lookup reads of the current map. The field either as the device keeps it (df: keys, decoded as k_df_decode does) or
+// as rebvio_hip_map_distance_field hands it out (df null: ids with -1 for an empty cell, distances) - the host hook's form.
+struct alignas(8) AlignF2 {  // one 8-byte load
+  float x, y;
+};
+struct AlignMap {
+  float fm, cx, cy;
+  int rows, cols;
+  const unsigned* df;
+  int df_nr;
+  const int* ids;
+  const int* dists;
+  const AlignF2* pos;   // KeyLine::pos
+  const AlignF2* unit;  // gradient / gradient_norm
+  int cap;              // slots of pos / unit: an id at or above it is skipped (detection's field holds none: the gathers stay inside)
+};
+
+// One term of the alignment: steps 2..6 of the definition for the keyframe keyline (kx, ky, rho_f; has_n: its normal knx, kny is
+// there). -1: skipped, v untouched; otherwise the owning keyline i and v = the term's 28 addends.
+RH_HD inline int align_term(const AlignMap& c, float kx, float ky, float rho_f, bool has_n, float knx, float kny, double min_cos,
+                            int max_dist, const double* R, const double* t, double huber, double* v) {
+  const double a = (double)(kx / c.fm), b = (double)(ky / c.fm), rho = (double)rho_f;
+  const double Zx = (R[0] * a + R[1] * b) + R[2];
+  const double Zy = (R[3] * a + R[4] * b) + R[5];
+  const double Zz = (R[6] * a + R[7] * b) + R[8];
+  const double Yx = Zx + rho * t[0], Yy = Zy + rho * t[1], Yz = Zz + rho * t[2];
+  if (!(Yz > 0.0)) return -1;
+  const double px = Yx / Yz, py = Yy / Yz;
+  const double pu = (double)c.fm * px + (double)c.cx, pv = (double)c.fm * py + (double)c.cy;
+  const double x = floor(pu + 0.5), y = floor(pv + 0.5);
+  if (!(x >= 1.0 && x <= (double)(c.cols - 2) && y >= 1.0 && y <= (double)(c.rows - 2))) return -1;
+  const size_t cell = (size_t)(int)y * (size_t)c.cols + (size_t)(int)x;
+  int i, dist;
+  if (c.df) {
+    const unsigned key = c.df[cell];
+    if (key == 0xFFFFFFFFu) return -1;  // (kDfEmpty)
+    i = (int)((((1u << 23) - 1u) - (key & ((1u << 23) - 1u))) / (unsigned)c.df_nr);  // (kDfSeqMask, kDfSeqBits)
+    dist = (int)(key >> 23);
+  } else {
+    i = c.ids[cell];
+    dist = c.dists[cell];
+    if (i < 0) return -1;
+  }
+  if (!(dist <= max_dist) || i >= c.cap) return -1;
+  // pos[i] and unit[i]: two independent 8-byte gathers
+  const AlignF2 ps = c.pos[i], un = c.unit[i];
+  const float qx_f = ps.x - c.cx, qy_f = ps.y - c.cy;
+  const float ux_f = un.x, uy_f = un.y;
+  if (has_n && min_cos > -1.0) {
+    const double nx = (double)knx, ny = (double)kny, ux = (double)ux_f, uy = (double)uy_f;
+    const double mx = R[0] * nx + R[1] * ny, my = R[3] * nx + R[4] * ny;
+    const double mm = mx * mx + my * my, nn = ux * ux + uy * uy;
+    if (mm > 0.0 && nn > 0.0 && !(mx * ux + my * uy >= (min_cos * sqrt(mm)) * sqrt(nn))) return -1;
+  }
+  return term(c.fm, kx, ky, rho_f, qx_f, qy_f, ux_f, uy_f, R, t, huber, v) ? i : -1;
+}
+
 // exp(w) * R -> R: Rodrigues, the first-order form I + [w]x below theta^2 < 1e-16
 RH_HD inline void rotate_left(const double* w, double* R) {
   const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];

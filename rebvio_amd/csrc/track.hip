@@ -3465,4 +3465,83 @@ void launch_kf_pose_eval(hipStream_t s, const KParams& p, const MapDev& m, int k
             state_dev);
 }
 
+// ---- alignment of a snapshot through a map's distance field (rebvio_hip_kf_snapshot_add_normals, rebvio_hip_map_keyframe_align) --
+// k_kf_snapshot_normals: gradient / gradient_norm of the keylines below both sizes (read on the device), zeros in every other slot
+// of the launch grid (= the buffer) and where gradient_norm is not > 0. One 8-byte store per lane.
+__global__ __launch_bounds__(256) void k_kf_snapshot_normals(MapDev m, const int* __restrict__ snap_n, float2* __restrict__ out) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const float2 g = m.grad[idx];  // bound-free early loads (the arrays are padded to the launch grid)
+  const float gn = m.gnorm[idx];
+  const int n = min(m.st->n, *snap_n);
+  out[idx] = idx < n && gn > 0.0f ? make_float2(g.x / gn, g.y / gn) : make_float2(0.f, 0.f);
+}
+
+void launch_kf_snapshot_normals(hipStream_t s, const KParams& p, const MapDev& m, const int* snap_n, void* normals) {
+  RH_LAUNCH(k_kf_snapshot_normals, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, m, snap_n, reinterpret_cast<float2*>(normals));
+}
+
+// One evaluation of the alignment's normal equations (kf_pose.hpp: kfp::align_term is the definition's per-keyline statement). One
+// thread per keyframe keyline: one 16-byte snapshot load and the 8-byte normal, then two dependent gathers - the field cell, then
+// pos and unit of its owner together. assoc[j] is written by every thread below kf_size. The reduction is k_kf_pose_sums' tree,
+// copied: butterfly over the wave, (w0 + w1) + (w2 + w3) through LDS, one partial and one count per workgroup, no atomic.
+__global__ __launch_bounds__(256) void k_kf_align_sums(KParams p, MapDev m, int kf_size, const float4* __restrict__ prs,
+                                                       const unsigned* __restrict__ kf_matches, const float2* __restrict__ normals,
+                                                       rebvio_hip_cloud_filter flt, double huber, double min_cos, int max_dist,
+                                                       const rebvio_hip_kf_pose* __restrict__ st, double* __restrict__ part,
+                                                       int* __restrict__ part_used, int* __restrict__ assoc) {
+  __shared__ double sh[4][kfp::kSums];
+  __shared__ int sh_used[4];
+  const int tid = threadIdx.x, j = blockIdx.x * 256 + tid, wv = tid >> 6;
+  double v[kfp::kSums];
+#pragma unroll
+  for (int k = 0; k < kfp::kSums; ++k) v[k] = 0.0;
+  bool used = false;
+  if (j < kf_size) {
+    const float4 k4 = prs[j];
+    const unsigned kmt = kf_matches[j];
+    const float2 kn = normals ? normals[j] : make_float2(0.f, 0.f);
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = st->R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = st->t[k];
+    kfp::AlignMap c;
+    c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
+    c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
+    c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
+    c.cap = p.kmax;
+    int i = -1;
+    if (kfp::filter_pass(flt, k4.z, k4.w, kmt))
+      i = kfp::align_term(c, k4.x, k4.y, k4.z, normals != nullptr, kn.x, kn.y, min_cos, max_dist, R, t, huber, v);
+    used = i >= 0;
+    assoc[j] = i;
+  }
+#pragma unroll
+  for (int k = 0; k < kfp::kSums; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
+  }
+  const int nu = __popcll(__ballot(used));
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kfp::kSums; ++k) sh[wv][k] = v[k];
+    sh_used[wv] = nu;
+  }
+  __syncthreads();
+  if (tid < kfp::kSums) part[(size_t)blockIdx.x * kfp::kSums + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
+  if (tid == 0) part_used[blockIdx.x] = (sh_used[0] + sh_used[1]) + (sh_used[2] + sh_used[3]);
+}
+
+void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const int* kf_size_dev, const void* snap_prs,
+                          const unsigned* snap_matches, const void* snap_normals, const rebvio_hip_cloud_filter& flt, double huber,
+                          double min_cos, int max_dist, int first, int last, int min_used, rebvio_hip_kf_pose* state_dev, double* part,
+                          int* part_used, int* assoc) {
+  const int nb = div_up(kf_size, 256);  // (kf_size <= kmax: nb <= kMaxRecBlocks)
+  RH_LAUNCH(k_kf_align_sums, dim3(nb), dim3(256), 0, s, p, m, kf_size, reinterpret_cast<const float4*>(snap_prs), snap_matches,
+            reinterpret_cast<const float2*>(snap_normals), flt, huber, min_cos, max_dist, (const rebvio_hip_kf_pose*)state_dev, part,
+            part_used, assoc);
+  RH_LAUNCH(k_kf_pose_step, dim3(1), dim3(64), 0, s, (const double*)part, (const int*)part_used, nb, kf_size_dev, first, last, min_used,
+            state_dev);
+}
+
 }  // namespace rh

@@ -187,4 +187,36 @@ rebvio::types::KfPose EdgeMap::keyframePose(const rebvio::KeyframeSnapshot& snap
   return out;
 }
 
+void KeyframeSnapshot::addNormals(const rebvio::EdgeMap& map) {
+  check("rebvio_hip_kf_snapshot_add_normals", rebvio_hip_kf_snapshot_add_normals(handle_, map.handle()));
+}
+
+rebvio::types::KfPose EdgeMap::keyframeAlign(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfAlignOpts& opts,
+                                             const rebvio::types::KfPose* guess, std::vector<int>* assoc) {
+  static_assert(sizeof(types::KfAlignOpts) == sizeof(rebvio_hip_kf_align_opts) &&
+                    offsetof(types::KfAlignOpts, huber_px) == offsetof(rebvio_hip_kf_align_opts, huber_px) &&
+                    offsetof(types::KfAlignOpts, min_cos) == offsetof(rebvio_hip_kf_align_opts, min_cos) &&
+                    offsetof(types::KfAlignOpts, max_dist) == offsetof(rebvio_hip_kf_align_opts, max_dist) &&
+                    offsetof(types::KfAlignOpts, max_iter) == offsetof(rebvio_hip_kf_align_opts, max_iter) &&
+                    offsetof(types::KfAlignOpts, min_used) == offsetof(rebvio_hip_kf_align_opts, min_used),
+                "keyframe alignment options mirror the C-ABI's");
+  rebvio_hip_kf_align_opts o;
+  std::memcpy(&o, &opts, sizeof(o));
+  if (o.max_dist < 0) {  // the context's search_range
+    rebvio_hip_kf_align_opts def;
+    rebvio_hip_default_kf_align_opts(ctx_, &def);
+    o.max_dist = def.max_dist;
+  }
+  if (assoc) {
+    int n = 0;
+    check("rebvio_hip_kf_snapshot_download", snapshot.handle() ? rebvio_hip_kf_snapshot_download(snapshot.handle(), nullptr, nullptr, 0, &n) : 0);
+    assoc->assign((size_t)n, -1);
+  }
+  rebvio::types::KfPose out;
+  check("rebvio_hip_map_keyframe_align",
+        rebvio_hip_map_keyframe_align(handle_, snapshot.handle(), &o, guess ? guess->R : nullptr, guess ? guess->t : nullptr,
+                                      reinterpret_cast<rebvio_hip_kf_pose*>(&out), assoc && !assoc->empty() ? assoc->data() : nullptr));
+  return out;
+}
+
 }  // namespace rebvio

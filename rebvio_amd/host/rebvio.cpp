@@ -600,6 +600,7 @@ void Rebvio::stateEstimationProcess() {
       new_edge_map->markKeyframe();
       if (want_kf_pose) {  // the keyframe as it is now, right behind its mark; the previous one goes
         kf_snapshot = new_edge_map->keyframeSnapshot();
+        if (keyframe_align_) kf_snapshot.addNormals(*new_edge_map);  // (setKeyframeAlign: the alignment's gradient test)
         kf_pose_warm = false;
       }
     }
@@ -607,7 +608,10 @@ void Rebvio::stateEstimationProcess() {
     // keyframe-pose callbacks: the new map against the keyframe, behind this pair's second half (the call waits for it)
     bool have_kf_pose = false;
     if (want_kf_pose && kf_snapshot) {
-      kf_pose_last = new_edge_map->keyframePose(kf_snapshot, types::KfPoseOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
+      if (keyframe_align_)
+        kf_pose_last = new_edge_map->keyframeAlign(kf_snapshot, types::KfAlignOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
+      else
+        kf_pose_last = new_edge_map->keyframePose(kf_snapshot, types::KfPoseOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
       kf_pose_warm = kf_pose_last.status == 0;
       have_kf_pose = true;
     }

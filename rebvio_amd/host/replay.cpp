@@ -14,6 +14,8 @@
 // --kf-pose FILE [--kf-every N]: the pose of every tracked map relative to the keyframe (Rebvio::registerKeyframePoseCallback), one
 // line per record that has one: ts_us status used R (9 values, row-major) t (3 values). A keyframe is requested before the first
 // frame and again after every N-th record (default 10).
+// --kf-align FILE [--kf-every N]: the same file, from the alignment of the keyframe to every tracked map through the map's distance
+// field (Rebvio::setKeyframeAlign) instead of the correspondence chain. One of --kf-pose and --kf-align.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +29,7 @@
 
 int main(int argc, char** argv) {
   std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path;
+  bool kf_align = false;
   int kf_every = 10;
   int W = 0, H = 0;
   size_t first = 0, count = (size_t)-1;
@@ -36,7 +39,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [--kf-pose FILE [--kf-every N]] --out file\n", argv[0]);
+                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -64,7 +67,11 @@ int main(int argc, char** argv) {
     }
     else if (a == "--cloud") cloud_prefix = next();
     else if (a == "--cloud-dry") cloud_dry = true;
-    else if (a == "--kf-pose") kf_pose_path = next();
+    else if (a == "--kf-pose" || a == "--kf-align") {
+      if (!kf_pose_path.empty()) return usage();  // one of the two, once
+      kf_align = a == "--kf-align";
+      kf_pose_path = next();
+    }
     else if (a == "--kf-every") kf_every = std::atoi(next());
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
@@ -146,6 +153,7 @@ int main(int argc, char** argv) {
         std::fprintf(kf_pose_file, "\n");
         ++n_poses;
       });
+      rebvio.setKeyframeAlign(kf_align);
       rebvio.requestKeyframe();
     }
     size_t n_clouds = 0, n_points = 0;
