@@ -43,6 +43,12 @@ class KeyframeSnapshot {
   // keeps gradient / gradient_norm of `map`'s keylines next to the snapshot, for the gradient test of EdgeMap::keyframeAlign
   // (rebvio_hip_kf_snapshot_add_normals; queued on the track stream). `map` is the map the snapshot was taken from, where it was taken.
   void addNormals(const rebvio::EdgeMap& map);
+  // folds `map`, seen from `pose` (X_cur = R X_kf + t, e.g. what EdgeMap::keyframeAlign returned for it), into this snapshot's rho /
+  // sigma_rho: one scalar Kalman update per keyline that finds an owner in map's distance field (rebvio_hip_kf_snapshot_fuse_depth;
+  // synchronous, from the tracking thread). assoc: per keyframe keyline the owner i when fused, -1 - i when gated or flat, INT_MIN
+  // when not associated. Fusing one map twice counts its pixels twice.
+  rebvio::types::KfFuse fuseDepth(const rebvio::EdgeMap& map, const rebvio::types::KfPose& pose,
+                                  const rebvio::types::KfFuseOpts& opts = rebvio::types::KfFuseOpts(), std::vector<int>* assoc = nullptr);
   explicit operator bool() const { return handle_ != nullptr; }
   rebvio_hip_kf_snapshot* handle() const { return handle_; }
 

@@ -74,6 +74,14 @@ class Rebvio {
   // the correspondence chain, warm-started exactly as that one is: it does not thin out with the chain. Off, the thread runs
   // exactly the calls it runs without this; the odometry does not change by a digit either way. Callable from any thread.
   void setKeyframeAlign(bool on) { keyframe_align_ = on; }
+  // addition: while this is on (default: off), setKeyframeAlign is on and a keyframe-pose callback is registered, every new map
+  // whose alignment came back with status 0 is fused into the snapshot at the returned pose (KeyframeSnapshot::fuseDepth;
+  // rebvio_hip.h defines it): the keyframe's rho / sigma_rho tighten with every aligned view, and the next alignment solves against
+  // them. The map the keyframe was marked on is not fused into itself. The counts go to the keyframe-fuse callbacks, once per such
+  // record, right after the keyframe-pose callbacks, with the record's stamp. Off, the thread runs exactly the calls it runs
+  // without this; the odometry does not change by a digit either way. Callable from any thread.
+  void setKeyframeDepthFusion(bool on) { keyframe_depth_fusion_ = on; }
+  void registerKeyframeFuseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfFuse&)> cb);
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -115,6 +123,8 @@ class Rebvio {
   std::vector<std::function<void(uint64_t, const rebvio::types::KfPose&)>> keyframe_pose_callbacks_;
   std::atomic<bool> keyframe_requested_{false};
   std::atomic<bool> keyframe_align_{false};
+  std::vector<std::function<void(uint64_t, const rebvio::types::KfFuse&)>> keyframe_fuse_callbacks_;
+  std::atomic<bool> keyframe_depth_fusion_{false};
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };
 

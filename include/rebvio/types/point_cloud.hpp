@@ -75,6 +75,31 @@ struct KfAlignOpts {
 };
 static_assert(sizeof(KfAlignOpts) == 48, "KfAlignOpts must stay layout-compatible with rebvio_hip_kf_align_opts");
 
+// Options of KeyframeSnapshot::fuseDepth, layout-compatible with the C-ABI's rebvio_hip_kf_fuse_opts (rebvio_hip.h defines every term).
+// The defaults are rebvio_hip_default_kf_fuse_opts's; pixel_sigma <= 0 stands for the context's pixel_uncertainty and max_dist -1 for
+// its search_range (fuseDepth fills them in).
+struct KfFuseOpts {
+  CloudFilter kf_filter;   // applied to the keyframe keylines
+  double min_cos{0.9};     // the gradient test, where the snapshot has a non-zero normal; -1 disables it
+  double pixel_sigma{0.0};
+  double gate_sigma{3.0};  // innovation gate in standard deviations
+  double q_abs{0.0};       // added in quadrature to sigma_rho before the update
+  int max_dist{-1};        // 0..search_range cells between the projection and the keyline that owns its cell
+  int reserved{0};
+};
+static_assert(sizeof(KfFuseOpts) == 56, "KfFuseOpts must stay layout-compatible with rebvio_hip_kf_fuse_opts");
+
+// What KeyframeSnapshot::fuseDepth returns, layout-compatible with rebvio_hip_kf_fuse: associated = fused + gated + flat.
+struct KfFuse {
+  int candidates{0};  // the snapshot's size
+  int associated{0};  // keylines that found an owner in the map's distance field
+  int fused{0};       // ... and were updated
+  int gated{0};       // ... failed the innovation gate or gave a non-finite update (left as they were)
+  int flat{0};        // ... carried no information (left as they were)
+  int clamped{0};     // among fused: rho ran into RHO_MIN or RHO_MAX
+};
+static_assert(sizeof(KfFuse) == 24, "KfFuse must stay layout-compatible with rebvio_hip_kf_fuse");
+
 // What a point-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
   uint64_t ts_us;            // the odometry record's stamp (= the map's)

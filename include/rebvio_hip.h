@@ -31,7 +31,9 @@ extern "C" {
  *    rebvio_hip_kf_snapshot_download, rebvio_hip_default_kf_pose_opts, rebvio_hip_map_keyframe_pose, their structs
  *    rebvio_hip_kf_pose_opts / rebvio_hip_kf_pose and the test hook rebvio_hip_test_kf_pose_host; the snapshot normals
  *    rebvio_hip_kf_snapshot_add_normals / _download_normals and the alignment entries rebvio_hip_default_kf_align_opts,
- *    rebvio_hip_map_keyframe_align, their struct rebvio_hip_kf_align_opts and the test hook rebvio_hip_test_kf_align_host. */
+ *    rebvio_hip_map_keyframe_align, their struct rebvio_hip_kf_align_opts and the test hook rebvio_hip_test_kf_align_host; the
+ *    depth fusion rebvio_hip_default_kf_fuse_opts, rebvio_hip_kf_snapshot_fuse_depth, their structs rebvio_hip_kf_fuse_opts /
+ *    rebvio_hip_kf_fuse and the test hook rebvio_hip_test_kf_fuse_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -451,6 +453,64 @@ int rebvio_hip_test_kf_align_host(float fm, float cx, float cy, int rows, int co
                                   const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
                                   const rebvio_hip_kf_align_opts* opts, const double R0[9], const double t0[3], rebvio_hip_kf_pose* out,
                                   int* assoc /*NULL or kf_size ints*/);
+
+/* Depth fusion into a keyframe snapshot: every map aligned to a snapshot is a new view of the keyframe's edges from a known pose,
+ * and rebvio_hip_kf_snapshot_fuse_depth folds that view into the snapshot's rho / sigma_rho with one scalar Kalman update per
+ * associated keyline, as Core::updateInverseDepth does per pair (rebvio/src/core.cpp) - without its propagation and rescaling,
+ * since the keyframe's frame does not move. The measurement is the pixel position of the map's keyline along its gradient, never
+ * the map's rho (which descends from the keyframe's own through the forward matches). (R, t) is the pose X_cur = R X_kf + t, e.g.
+ * the one rebvio_hip_map_keyframe_align returned. Fusing the same map twice counts its pixels twice: the caller's contract.
+ * fp64 behind the loads, every + - * / and sqrt one IEEE operation in the order written. Per keyframe keyline j < size:
+ *   1. steps 1..6 of rebvio_hip_map_keyframe_align at (R, t), with kf_filter, min_cos and max_dist of these options, give the owner
+ *      i - or the keyline is not associated.
+ *   2. e, c.x, c.y, c.z of the term of rebvio_hip_map_keyframe_pose; no Huber weight.
+ *   3. h = (c.x * t[0] + c.y * t[1]) + c.z * t[2]                  (de/drho, since dY/drho = t)
+ *   4. s = (double)sigma_rho_j;  v = s * s + q_abs * q_abs;  hv = h * v;  info = hv * h;   flat unless info > 0.
+ *   5. S = info + pixel_sigma * pixel_sigma;   gated unless e * e <= (gate_sigma * gate_sigma) * S.
+ *   6. K = hv / S;  rho_n = rho - K * e;  v_n = (1.0 - K * h) * v;  sig_n = sqrt(v_n);   gated unless rho_n, v_n and sig_n are
+ *      finite and v_n >= 0 (positive tests: a NaN gates).
+ *   7. rho_n < RHO_MIN:  sig_n = sig_n + (RHO_MIN - rho_n);  rho_n = RHO_MIN;   else rho_n > RHO_MAX:  rho_n = RHO_MAX;   either
+ *      counts as clamped. RHO_MIN = (double)1e-3f and RHO_MAX = 20 are what the tracker clamps to.
+ *   8. the snapshot gets (float)rho_n, (float)sig_n and matches_j + 1 (saturating at 0xFFFFFFFF). pos_img and the normals are never
+ *      written; a keyline that is not fused keeps all its bits.
+ * assoc[j] = i when fused, -1 - i when gated or flat, INT_MIN when not associated. associated = fused + gated + flat.
+ * One kernel (k_kf_fuse_depth: one thread per keyframe keyline, workgroups of 256, at most 256 of them with a stride loop behind;
+ * sizes read on the device), one clear of the count block and one copy back; the counts are integer sums, no floating-point value
+ * crosses threads: every output word is the same on every run. Synchronous and track-side; map acceptance as
+ * rebvio_hip_map_keyframe_align (any detected map of the snapshot's context, promised or not; -7 where the field is not
+ * detection's). The first call gives the context one more device allocation (the counts and keylines_max association words: one
+ * more live resource, kept until the context goes). A snapshot of size 0: all counts zero, nothing launched or allocated.
+ * -3, before the device is touched: null snapshot, map, R, t or output, a non-finite R or t, an invalid kf_filter, pixel_sigma or
+ * gate_sigma not > 0, q_abs < 0 or NaN, min_cos outside [-1, 1], max_dist outside 0..search_range, reserved != 0, a snapshot of
+ * another context; -10: the context has been destroyed. opts NULL = the defaults.
+ * rebvio_hip_test_kf_fuse_host (test hook, touches no device): the same statements on the host over the arrays of
+ * rebvio_hip_test_kf_align_host, snap_prs4 and snap_matches updated in place; opts NULL = the defaults with max_dist = search_range. */
+typedef struct rebvio_hip_kf_fuse_opts {   /* defaults from rebvio_hip_default_kf_fuse_opts */
+  rebvio_hip_cloud_filter kf_filter;       /* keyframe side, as in rebvio_hip_kf_align_opts; default = default cloud filter */
+  double min_cos;                          /* as in rebvio_hip_kf_align_opts, default 0.9 */
+  double pixel_sigma;                      /* > 0; default = the context's pixel_uncertainty (NULL ctx: its default value) */
+  double gate_sigma;                       /* > 0; default 3.0: innovation gate in standard deviations */
+  double q_abs;                            /* >= 0; default 0: added in quadrature to sigma_rho before the update */
+  int max_dist;                            /* 0..search_range, default search_range */
+  int reserved;                            /* 0 */
+} rebvio_hip_kf_fuse_opts;
+typedef struct rebvio_hip_kf_fuse {
+  int candidates;   /* the snapshot's size */
+  int associated;   /* keylines that passed steps 1..6 of the alignment's definition */
+  int fused;        /* ...and were updated */
+  int gated;        /* ...failed the innovation gate or gave a non-finite update (left as they were) */
+  int flat;         /* ...carried no information: !(h * v * h > 0) (left as they were) */
+  int clamped;      /* among fused: rho ran into RHO_MIN or RHO_MAX */
+} rebvio_hip_kf_fuse;
+void rebvio_hip_default_kf_fuse_opts(rebvio_hip_ctx* ctx /*NULL: pixel_sigma = 1, max_dist = 40, the defaults*/, rebvio_hip_kf_fuse_opts* opts);
+int rebvio_hip_kf_snapshot_fuse_depth(rebvio_hip_kf_snapshot* snap, rebvio_hip_map* map, const rebvio_hip_kf_fuse_opts* opts,
+                                      const double R[9], const double t[3], rebvio_hip_kf_fuse* out,
+                                      int* assoc_host /*NULL or snapshot-size ints*/);
+int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int cols, int search_range, float* snap_prs4 /*in/out*/,
+                                 unsigned* snap_matches /*in/out*/, const float* snap_normals /*NULL: none*/, int kf_size,
+                                 const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
+                                 const rebvio_hip_kf_fuse_opts* opts, const double R[9], const double t[3], rebvio_hip_kf_fuse* out,
+                                 int* assoc /*NULL or kf_size ints*/);
 
 /* Test hook: overwrite the device keylines (count must equal the map size). */
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n);

@@ -87,6 +87,18 @@ class KfAlignOpts(C.Structure):
                 ("max_iter", C.c_int), ("min_used", C.c_int)]
 
 
+class KfFuseOpts(C.Structure):
+    """rebvio_hip_kf_fuse_opts (KfSnapshot.fuse_depth); defaults from default_kf_fuse_opts"""
+    _fields_ = [("kf_filter", CloudFilter), ("min_cos", C.c_double), ("pixel_sigma", C.c_double), ("gate_sigma", C.c_double),
+                ("q_abs", C.c_double), ("max_dist", C.c_int), ("reserved", C.c_int)]
+
+
+class KfFuse(C.Structure):
+    """rebvio_hip_kf_fuse: the counts of one depth fusion; associated = fused + gated + flat"""
+    _fields_ = [("candidates", C.c_int), ("associated", C.c_int), ("fused", C.c_int), ("gated", C.c_int), ("flat", C.c_int),
+                ("clamped", C.c_int)]
+
+
 class KfPose(C.Structure):
     """rebvio_hip_kf_pose: X_cur = R X_kf + t, the sums at that pose, and the counters"""
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("H", C.c_double * 36), ("g", C.c_double * 6), ("cost", C.c_double),
@@ -140,6 +152,11 @@ SIGNATURES = {
     "rebvio_hip_test_kf_align_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
                                                 C.c_int, _fp, _fp, C.c_int, _ip, _ip, C.POINTER(KfAlignOpts), _dp, _dp,
                                                 C.POINTER(KfPose), _ip]),
+    "rebvio_hip_default_kf_fuse_opts": (None, [_vp, C.POINTER(KfFuseOpts)]),
+    "rebvio_hip_kf_snapshot_fuse_depth": (C.c_int, [_vp, _vp, C.POINTER(KfFuseOpts), _dp, _dp, C.POINTER(KfFuse), _ip]),
+    "rebvio_hip_test_kf_fuse_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
+                                               C.c_int, _fp, _fp, C.c_int, _ip, _ip, C.POINTER(KfFuseOpts), _dp, _dp,
+                                               C.POINTER(KfFuse), _ip]),
     "rebvio_hip_test_kf_pose_host": (C.c_int, [C.c_float, _fp, C.POINTER(C.c_uint), C.c_int, _fp, _fp, C.c_int, C.POINTER(KfMatch),
                                                C.c_int, C.POINTER(KfPoseOpts), _dp, _dp, C.POINTER(KfPose)]),
     "rebvio_hip_map_upload": (C.c_int, [_vp, _vp, C.c_int]),
@@ -433,6 +450,48 @@ def kf_align_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normal
     return out, assoc
 
 
+def default_kf_fuse_opts(ctx=None, **over) -> KfFuseOpts:
+    """The library's defaults (rebvio_hip_default_kf_fuse_opts): pixel_sigma is ctx's pixel_uncertainty and max_dist its search_range
+    (1 and 40, the default ones, without a context); kf_filter takes a CloudFilter or a dict of its fields to change."""
+    o = KfFuseOpts()
+    lib().rebvio_hip_default_kf_fuse_opts(ctx.h if ctx is not None else None, C.byref(o))
+    for k, v in over.items():
+        if k == "kf_filter" and not isinstance(v, CloudFilter):
+            for fk, fv in v.items():
+                setattr(o.kf_filter, fk, fv)
+        else:
+            setattr(o, k, v)
+    return o
+
+
+def kf_fuse_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normals, cur_pos, cur_unit, df_id, df_dist, opts=None, R=None,
+                 t=None):
+    """KfSnapshot.fuse_depth on the host, from arrays (rebvio_hip_test_kf_fuse_host; the arrays of kf_align_host). Touches no device
+    and leaves its inputs alone. Returns (KfFuse, new prs4 float32 [n, 4], new matches uint32 [n], assoc int32 [n])."""
+    prs4 = np.array(prs4, np.float32).reshape(-1, 4)            # (copies: the hook updates them in place)
+    kf_matches = np.array(kf_matches, np.uint32).reshape(-1)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 2)
+    q = np.ascontiguousarray(cur_pos, np.float32).reshape(-1, 2)
+    u = np.ascontiguousarray(cur_unit, np.float32).reshape(-1, 2)
+    ids = np.ascontiguousarray(df_id, np.int32).reshape(-1)
+    dists = np.ascontiguousarray(df_dist, np.int32).reshape(-1)
+    assert len(prs4) == len(kf_matches) and len(q) == len(u) and (nrm is None or len(nrm) == len(prs4))
+    assert len(ids) == len(dists) == int(rows) * int(cols)
+    (kR, pR), (kt, pt) = _guess(R, 9), _guess(t, 3)
+    out = KfFuse()
+    assoc = np.full(len(prs4), -2 ** 31, np.int32)
+    up = C.POINTER(C.c_uint)
+    _chk(lib().rebvio_hip_test_kf_fuse_host(float(fm), float(cx), float(cy), int(rows), int(cols), int(search_range),
+                                            prs4.ctypes.data_as(_fp) if len(prs4) else None,
+                                            kf_matches.ctypes.data_as(up) if len(prs4) else None,
+                                            nrm.ctypes.data_as(_fp) if nrm is not None and len(nrm) else None, len(prs4),
+                                            q.ctypes.data_as(_fp) if len(q) else None, u.ctypes.data_as(_fp) if len(q) else None, len(q),
+                                            ids.ctypes.data_as(_ip) if len(ids) else None, dists.ctypes.data_as(_ip) if len(ids) else None,
+                                            opts, pR, pt, C.byref(out), assoc.ctypes.data_as(_ip) if len(assoc) else None))
+    del kR, kt
+    return out, prs4, kf_matches, assoc
+
+
 class KfSnapshot:
     """A keyframe as it was when marked (rebvio_hip_map_keyframe_snapshot): download() its keylines, release() when done."""
 
@@ -463,6 +522,23 @@ class KfSnapshot:
         if n.value:
             _chk(lib().rebvio_hip_kf_snapshot_download_normals(self.h, out.ctypes.data_as(_fp), n.value, C.byref(n)))
         return out
+
+    def fuse_depth(self, map, R, t, opts=None, want_assoc=False):
+        """Folds `map`, seen from the pose X_cur = R X_kf + t (e.g. Map.keyframe_align's), into this snapshot's rho / sigma_rho: one
+        scalar Kalman update per associated keyline (rebvio_hip_kf_snapshot_fuse_depth; synchronous). opts: a KfFuseOpts or None
+        for the defaults. Returns the KfFuse counts; want_assoc: also the int32 array with, per keyframe keyline, the owner i when
+        fused, -1 - i when gated or flat, INT_MIN when not associated. Fusing one map twice counts its pixels twice."""
+        (kR, pR), (kt, pt) = _guess(R, 9), _guess(t, 3)
+        out = KfFuse()
+        assoc = None
+        if want_assoc:
+            n = C.c_int()
+            _chk(lib().rebvio_hip_kf_snapshot_download(self.h, None, None, 0, C.byref(n)))
+            assoc = np.full(n.value, -2 ** 31, np.int32)
+        _chk(lib().rebvio_hip_kf_snapshot_fuse_depth(self.h, map.h, opts, pR, pt, C.byref(out),
+                                                     assoc.ctypes.data_as(_ip) if want_assoc and len(assoc) else None))
+        del kR, kt
+        return (out, assoc) if want_assoc else out
 
     def release(self):
         if self.h:

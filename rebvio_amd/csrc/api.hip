@@ -517,6 +517,10 @@ struct rebvio_hip_ctx {
   double* kfa_part = nullptr;  // (views into kfa_state's allocation)
   int* kfa_used = nullptr;
   int* kfa_assoc = nullptr;
+  // scratch of rebvio_hip_kf_snapshot_fuse_depth (ONE allocation on first use, kept; a track-side entry): 8 count words (the six of
+  // rebvio_hip_kf_fuse in front), then keylines_max association words
+  int* kff_cnt = nullptr;
+  int* kff_assoc = nullptr;  // (a view into kff_cnt's allocation)
 };
 
 namespace {
@@ -2285,6 +2289,136 @@ int rebvio_hip_test_kf_align_host(float fm, float cx, float cy, int rows, int co
       ++used;
     }
     kfp::step(S, used, it == 0, it == o.max_iter, o.min_used, ws, &res);
+  }
+  *out = res;
+  return 0;
+}
+
+void rebvio_hip_default_kf_fuse_opts(rebvio_hip_ctx* c, rebvio_hip_kf_fuse_opts* o) {
+  std::memset(o, 0, sizeof(*o));
+  rebvio_hip_default_cloud_filter(&o->kf_filter);
+  o->min_cos = 0.9;
+  o->pixel_sigma = c ? (double)c->P.pixel_uncertainty : 1.0;
+  o->gate_sigma = 3.0;
+  o->q_abs = 0.0;
+  o->max_dist = c ? (int)c->P.search_range : 40;
+}
+
+namespace {
+int check_kf_fuse_args(const char* who, const rebvio_hip_kf_fuse_opts& o, int search_range, const double* R, const double* t) {
+  const std::string w(who);
+  if (!R || !t) return fail_msg((w + ": null R or t").c_str(), -3);
+  const int rc = check_cloud_args(who, &o.kf_filter, nullptr);
+  if (rc) return rc;
+  bool fin = true;
+  for (int i = 0; i < 9; ++i) fin = fin && std::isfinite(R[i]);
+  for (int i = 0; i < 3; ++i) fin = fin && std::isfinite(t[i]);
+  if (!fin) return fail_msg((w + ": non-finite R or t").c_str(), -3);
+  if (!(o.pixel_sigma > 0.0)) return fail_msg((w + ": pixel_sigma must be > 0").c_str(), -3);
+  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
+  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
+  if (!(o.min_cos >= -1.0 && o.min_cos <= 1.0)) return fail_msg((w + ": min_cos outside [-1, 1]").c_str(), -3);
+  if (o.max_dist < 0 || o.max_dist > search_range) return fail_msg((w + ": max_dist outside 0..search_range").c_str(), -3);
+  if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
+  return 0;
+}
+}  // namespace
+
+static_assert(sizeof(rebvio_hip_kf_fuse_opts) == 56, "filter, four doubles, two ints");
+static_assert(sizeof(rebvio_hip_kf_fuse) == 24, "six ints");
+
+int rebvio_hip_kf_snapshot_fuse_depth(rebvio_hip_kf_snapshot* sn, rebvio_hip_map* m, const rebvio_hip_kf_fuse_opts* opts, const double* R,
+                                      const double* t, rebvio_hip_kf_fuse* out, int* assoc_host) {
+  if (!sn || !m || !out) return fail_msg("kf_snapshot_fuse_depth: null snapshot, map or output", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (sn->life != m->life) {
+    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+    return fail_msg("kf_snapshot_fuse_depth: snapshot of another context", -3);
+  }
+  rebvio_hip_ctx* c = m->ctx;
+  rebvio_hip_kf_fuse_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_kf_fuse_opts(c, &o);
+  int rc = check_kf_fuse_args("kf_snapshot_fuse_depth", o, (int)c->P.search_range, R, t);
+  if (rc) return rc;
+  if (!m->df_built || !m->raster_order)
+    return fail_msg("kf_snapshot_fuse_depth: the map's distance field is not detection's (none was built, or its keylines were uploaded)", -7);
+  HIPCHK(hipSetDevice(c->device));
+  rc = snapshot_size(c, sn);
+  if (rc) return rc;
+  const int kf_size = sn->n_host;
+  std::memset(out, 0, sizeof(*out));
+  if (kf_size == 0) return 0;  // nothing to fuse: nothing is launched
+  if (!c->kff_cnt) {
+    char* b = nullptr;
+    HIPCHK(c->own.device_bytes(&b, (8 + (size_t)c->P.keylines_max) * sizeof(int)));
+    c->kff_cnt = reinterpret_cast<int*>(b);
+    c->kff_assoc = c->kff_cnt + 8;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready(c->s_trk, m));
+  rebvio_hip_kf_fuse res;
+  {
+    std::lock_guard<std::mutex> lk(sn->nor_mu);  // (the snapshot is this call's from the clear to the kernel, as in add_normals)
+    HIPCHK(hipMemsetAsync(c->kff_cnt, 0, 8 * sizeof(int), c->s_trk));
+    launch_kf_fuse_depth(c->s_trk, c->K, m->d, kf_size, sn->n_dev, sn->prs, sn->matches, sn->normals, o, R, t, c->kff_cnt, c->kff_assoc);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(&res, c->kff_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, c->kff_assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  *out = res;
+  return 0;
+}
+
+int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int cols, int search_range, float* snap_prs4, unsigned* snap_matches,
+                                 const float* snap_normals, int kf_size, const float* cur_pos, const float* cur_unit, int n_cur,
+                                 const int* df_id, const int* df_dist, const rebvio_hip_kf_fuse_opts* opts, const double* R, const double* t,
+                                 rebvio_hip_kf_fuse* out, int* assoc) {
+  if (!out || kf_size < 0 || n_cur < 0 || rows < 0 || cols < 0 || (kf_size > 0 && (!snap_prs4 || !snap_matches)) ||
+      (n_cur > 0 && (!cur_pos || !cur_unit)) || ((size_t)rows * (size_t)cols > 0 && (!df_id || !df_dist)))
+    return fail_msg("test_kf_fuse_host: null array or negative size", -3);
+  rebvio_hip_kf_fuse_opts o;
+  if (opts) {
+    o = *opts;
+  } else {
+    rebvio_hip_default_kf_fuse_opts(nullptr, &o);
+    o.max_dist = search_range;
+  }
+  const int rc = check_kf_fuse_args("test_kf_fuse_host", o, search_range, R, t);
+  if (rc) return rc;
+  const size_t Pn = (size_t)rows * (size_t)cols;
+  for (size_t k = 0; k < Pn; ++k)
+    if (df_id[k] >= n_cur) return fail_msg("test_kf_fuse_host: a field id lies outside the keyline arrays", -3);
+  kfp::AlignMap am;
+  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
+  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
+  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
+  am.cap = n_cur;
+  rebvio_hip_kf_fuse res;
+  std::memset(&res, 0, sizeof(res));
+  res.candidates = kf_size;
+  for (int j = 0; j < kf_size; ++j) {
+    float* k4 = snap_prs4 + 4 * (size_t)j;
+    int outcome = kfp::kFuseNone, i = 0;
+    float rho_n = 0.f, sig_n = 0.f;
+    bool clamped = false;
+    if (kfp::filter_pass(o.kf_filter, k4[2], k4[3], snap_matches[j]))
+      outcome = kfp::fuse_term(am, k4[0], k4[1], k4[2], k4[3], snap_normals != nullptr, snap_normals ? snap_normals[2 * (size_t)j] : 0.0f,
+                               snap_normals ? snap_normals[2 * (size_t)j + 1] : 0.0f, o.min_cos, o.max_dist, R, t, o.pixel_sigma,
+                               o.gate_sigma, o.q_abs, &i, &rho_n, &sig_n, &clamped);
+    if (assoc) assoc[j] = outcome == kfp::kFuseNone ? std::numeric_limits<int>::min() : outcome == kfp::kFuseFused ? i : -1 - i;
+    if (outcome == kfp::kFuseNone) continue;
+    ++res.associated;
+    if (outcome == kfp::kFuseGated) ++res.gated;
+    if (outcome == kfp::kFuseFlat) ++res.flat;
+    if (outcome != kfp::kFuseFused) continue;
+    ++res.fused;
+    if (clamped) ++res.clamped;
+    k4[2] = rho_n;
+    k4[3] = sig_n;
+    if (snap_matches[j] != 0xFFFFFFFFu) ++snap_matches[j];
   }
   *out = res;
   return 0;

@@ -348,6 +348,14 @@ void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int 
                           const unsigned* snap_matches, const void* snap_normals, const rebvio_hip_cloud_filter& flt, double huber,
                           double min_cos, int max_dist, int first, int last, int min_used, rebvio_hip_kf_pose* state_dev, double* part,
                           int* part_used, int* assoc);
+// k_kf_fuse_depth on stream s (rebvio_hip_kf_snapshot_fuse_depth): the kf_size (1..kmax; kf_size_dev = the same size in device
+// memory, which the kernel reads) keylines of a snapshot against m's distance field, pos and unit at the pose (R, t); rho, sigma_rho
+// and matches of the fused ones are rewritten in place. cnt = 8 ints, cleared by the caller in front of the launch (the kernel
+// leaves the six words of rebvio_hip_kf_fuse there); assoc = kmax ints. The grid is min(ceil(kf_size / 256), kMaxRecBlocks)
+// workgroups, k_kf_align_sums' cap, with a stride loop behind it.
+void launch_kf_fuse_depth(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const int* kf_size_dev, void* snap_prs,
+                          unsigned* snap_matches, const void* snap_normals, const rebvio_hip_kf_fuse_opts& o, const double* R, const double* t,
+                          int* cnt, int* assoc);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 

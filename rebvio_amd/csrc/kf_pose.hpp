@@ -121,6 +121,92 @@ RH_HD inline int align_term(const AlignMap& c, float kx, float ky, float rho_f, 
   return term(c.fm, kx, ky, rho_f, qx_f, qy_f, ux_f, uy_f, R, t, huber, v) ? i : -1;
 }
 
+// ---- depth fusion into a snapshot (rebvio_hip_kf_snapshot_fuse_depth; include/rebvio_hip.h is the definition) --------------------
+constexpr float kRhoMin = 1e-3f;  // types/keyline.hpp:18: what the tracker clamps rho to (track.hip)
+constexpr float kRhoMax = 20.0f;  // types/keyline.hpp:17
+
+enum FuseOutcome { kFuseNone = 0, kFuseFused = 1, kFuseGated = 2, kFuseFlat = 3 };
+
+// One keyframe keyline's scalar Kalman update: steps 2..7 of the definition (step 1, the filter, is the caller's). The lookup is
+// align_term's, copied (a shared helper would have to leave every existing kernel's instructions as they are); e and c are the
+// expressions of term(), without its Huber weight. kFuseNone: not associated, nothing written. Otherwise *owner = i, and for
+// kFuseFused *rho_out / *sig_out = the new pair, *clamped = whether rho ran into kRhoMin / kRhoMax.
+RH_HD inline int fuse_term(const AlignMap& c, float kx, float ky, float rho_f, float sig_f, bool has_n, float knx, float kny,
+                           double min_cos, int max_dist, const double* R, const double* t, double pixel_sigma, double gate_sigma,
+                           double q_abs, int* owner, float* rho_out, float* sig_out, bool* clamped) {
+  const double a = (double)(kx / c.fm), b = (double)(ky / c.fm), rho = (double)rho_f;
+  const double Zx = (R[0] * a + R[1] * b) + R[2];
+  const double Zy = (R[3] * a + R[4] * b) + R[5];
+  const double Zz = (R[6] * a + R[7] * b) + R[8];
+  const double Yx = Zx + rho * t[0], Yy = Zy + rho * t[1], Yz = Zz + rho * t[2];
+  if (!(Yz > 0.0)) return kFuseNone;
+  const double px = Yx / Yz, py = Yy / Yz;
+  const double pu = (double)c.fm * px + (double)c.cx, pv = (double)c.fm * py + (double)c.cy;
+  const double x = floor(pu + 0.5), y = floor(pv + 0.5);
+  if (!(x >= 1.0 && x <= (double)(c.cols - 2) && y >= 1.0 && y <= (double)(c.rows - 2))) return kFuseNone;
+  const size_t cell = (size_t)(int)y * (size_t)c.cols + (size_t)(int)x;
+  int i, dist;
+  if (c.df) {
+    const unsigned key = c.df[cell];
+    if (key == 0xFFFFFFFFu) return kFuseNone;  // (kDfEmpty)
+    i = (int)((((1u << 23) - 1u) - (key & ((1u << 23) - 1u))) / (unsigned)c.df_nr);  // (kDfSeqMask, kDfSeqBits)
+    dist = (int)(key >> 23);
+  } else {
+    i = c.ids[cell];
+    dist = c.dists[cell];
+    if (i < 0) return kFuseNone;
+  }
+  if (!(dist <= max_dist) || i >= c.cap) return kFuseNone;
+  // pos[i] and unit[i]: two independent 8-byte gathers
+  const AlignF2 ps = c.pos[i], un = c.unit[i];
+  const float qx_f = ps.x - c.cx, qy_f = ps.y - c.cy;
+  if (has_n && min_cos > -1.0) {
+    const double nx = (double)knx, ny = (double)kny, ux = (double)un.x, uy = (double)un.y;
+    const double mx = R[0] * nx + R[1] * ny, my = R[3] * nx + R[4] * ny;
+    const double mm = mx * mx + my * my, nn = ux * ux + uy * uy;
+    if (mm > 0.0 && nn > 0.0 && !(mx * ux + my * uy >= (min_cos * sqrt(mm)) * sqrt(nn))) return kFuseNone;
+  }
+  // e and c of term()
+  const double qx = (double)(qx_f / c.fm), qy = (double)(qy_f / c.fm);
+  const double gx = (double)un.x, gy = (double)un.y;
+  const double g2 = gx * gx + gy * gy;
+  if (!(g2 > 0.0 && g2 < HUGE_VAL)) return kFuseNone;
+  const double gn = sqrt(g2);
+  const double nx = gx / gn, ny = gy / gn;
+  const double f = (double)c.fm;
+  const double e = f * (nx * (px - qx) + ny * (py - qy));
+  const double cx = (f * nx) / Yz, cy = (f * ny) / Yz;
+  const double cz = -(cx * px + cy * py);
+  *owner = i;
+  // the update: de/drho = c . t
+  const double h = (cx * t[0] + cy * t[1]) + cz * t[2];
+  const double s = (double)sig_f;
+  const double v = s * s + q_abs * q_abs;
+  const double hv = h * v;
+  const double info = hv * h;
+  if (!(info > 0.0)) return kFuseFlat;
+  const double S = info + pixel_sigma * pixel_sigma;
+  if (!(e * e <= (gate_sigma * gate_sigma) * S)) return kFuseGated;
+  const double K = hv / S;
+  double rho_n = rho - K * e;
+  const double v_n = (1.0 - K * h) * v;
+  double sig_n = sqrt(v_n);
+  if (!(fabs(rho_n) < HUGE_VAL && v_n >= 0.0 && v_n < HUGE_VAL && fabs(sig_n) < HUGE_VAL)) return kFuseGated;
+  const double lo = (double)kRhoMin, hi = (double)kRhoMax;
+  *clamped = false;
+  if (rho_n < lo) {
+    sig_n = sig_n + (lo - rho_n);
+    rho_n = lo;
+    *clamped = true;
+  } else if (rho_n > hi) {
+    rho_n = hi;
+    *clamped = true;
+  }
+  *rho_out = (float)rho_n;
+  *sig_out = (float)sig_n;
+  return kFuseFused;
+}
+
 // exp(w) * R -> R: Rodrigues, the first-order form I + [w]x below theta^2 < 1e-16
 RH_HD inline void rotate_left(const double* w, double* R) {
   const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];

@@ -3544,4 +3544,80 @@ void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int 
             state_dev);
 }
 
+// ---- depth fusion into a snapshot (rebvio_hip_kf_snapshot_fuse_depth) ------------------------------------------------------------
+// kfp::fuse_term (kf_pose.hpp) is the definition's per-keyline statement. One thread per keyframe keyline, a stride loop behind the
+// grid's cap: the 16-byte record, the matches word and the 8-byte normal, then the two dependent gathers of the lookup; a fused
+// keyline stores its record and matches word back, every keyline its assoc word. The pose comes as kernel arguments (SGPRs). The
+// five counts are ballots summed per wave over the loop; lane 0 of each wave leaves them in LDS and five threads add the
+// workgroup's non-zero sums to cnt[1..5] with integer atomics (same-address atomics run one after the other at the memory side: one
+// set per workgroup, not per wave) - no floating-point value crosses threads. The size is read on the device (behind the snapshot
+// kernel in stream order), the stride from the grid.
+struct KfFusePose {
+  double R[9], t[3];
+};
+__global__ __launch_bounds__(256) void k_kf_fuse_depth(KParams p, MapDev m, const int* __restrict__ snap_n, float4* __restrict__ prs,
+                                                       unsigned* __restrict__ kf_matches, const float2* __restrict__ normals,
+                                                       rebvio_hip_cloud_filter flt, double min_cos, int max_dist, KfFusePose pose,
+                                                       double pixel_sigma, double gate_sigma, double q_abs, int* __restrict__ cnt,
+                                                       int* __restrict__ assoc) {
+  __shared__ int sh_cnt[4][5];
+  const int tid = threadIdx.x;
+  const int n = min(*snap_n, p.kmax), stride = (int)gridDim.x * 256;
+  kfp::AlignMap c;
+  c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
+  c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
+  c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
+  c.cap = p.kmax;
+  int n_assoc = 0, n_fused = 0, n_gated = 0, n_flat = 0, n_clamped = 0;
+  for (int base = blockIdx.x * 256; base < n; base += stride) {  // (uniform over the workgroup: the ballots see whole waves)
+    const int j = base + tid;
+    int outcome = kfp::kFuseNone;
+    bool clamped = false;
+    if (j < n) {
+      const float4 k4 = prs[j];
+      const unsigned kmt = kf_matches[j];
+      const float2 kn = normals ? normals[j] : make_float2(0.f, 0.f);
+      int i = 0;
+      float rho_n = 0.f, sig_n = 0.f;
+      if (kfp::filter_pass(flt, k4.z, k4.w, kmt))
+        outcome = kfp::fuse_term(c, k4.x, k4.y, k4.z, k4.w, normals != nullptr, kn.x, kn.y, min_cos, max_dist, pose.R, pose.t, pixel_sigma,
+                                 gate_sigma, q_abs, &i, &rho_n, &sig_n, &clamped);
+      if (outcome == kfp::kFuseFused) {
+        prs[j] = make_float4(k4.x, k4.y, rho_n, sig_n);
+        kf_matches[j] = kmt == 0xFFFFFFFFu ? kmt : kmt + 1u;
+      } else {
+        clamped = false;
+      }
+      assoc[j] = outcome == kfp::kFuseNone ? (int)0x80000000 : outcome == kfp::kFuseFused ? i : -1 - i;
+    }
+    n_assoc += __popcll(__ballot(outcome != kfp::kFuseNone));
+    n_fused += __popcll(__ballot(outcome == kfp::kFuseFused));
+    n_gated += __popcll(__ballot(outcome == kfp::kFuseGated));
+    n_flat += __popcll(__ballot(outcome == kfp::kFuseFlat));
+    n_clamped += __popcll(__ballot(clamped));
+  }
+  if ((tid & 63) == 0) {
+    int* w = sh_cnt[tid >> 6];
+    w[0] = n_assoc; w[1] = n_fused; w[2] = n_gated; w[3] = n_flat; w[4] = n_clamped;
+  }
+  __syncthreads();
+  if (tid < 5) {
+    const int sum = (sh_cnt[0][tid] + sh_cnt[1][tid]) + (sh_cnt[2][tid] + sh_cnt[3][tid]);
+    if (sum) atomicAdd(cnt + 1 + tid, sum);
+  }
+  if (blockIdx.x == 0 && tid == 0) cnt[0] = n;
+}
+
+void launch_kf_fuse_depth(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const int* kf_size_dev, void* snap_prs,
+                          unsigned* snap_matches, const void* snap_normals, const rebvio_hip_kf_fuse_opts& o, const double* R, const double* t,
+                          int* cnt, int* assoc) {
+  KfFusePose pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
+  const int want = div_up(kf_size, 256), nb = want < kMaxRecBlocks ? want : kMaxRecBlocks;  // (k_kf_align_sums' cap)
+  RH_LAUNCH(k_kf_fuse_depth, dim3(nb), dim3(256), 0, s, p, m, kf_size_dev, reinterpret_cast<float4*>(snap_prs), snap_matches,
+            reinterpret_cast<const float2*>(snap_normals), o.kf_filter, o.min_cos, o.max_dist, pose, o.pixel_sigma, o.gate_sigma, o.q_abs, cnt,
+            assoc);
+}
+
 }  // namespace rh

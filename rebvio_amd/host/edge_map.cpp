@@ -1,6 +1,7 @@
 #include "rebvio/edge_map.hpp"
 
 #include <cstring>
+#include <limits>
 
 #include "session.hpp"
 
@@ -189,6 +190,40 @@ rebvio::types::KfPose EdgeMap::keyframePose(const rebvio::KeyframeSnapshot& snap
 
 void KeyframeSnapshot::addNormals(const rebvio::EdgeMap& map) {
   check("rebvio_hip_kf_snapshot_add_normals", rebvio_hip_kf_snapshot_add_normals(handle_, map.handle()));
+}
+
+rebvio::types::KfFuse KeyframeSnapshot::fuseDepth(const rebvio::EdgeMap& map, const rebvio::types::KfPose& pose,
+                                                  const rebvio::types::KfFuseOpts& opts, std::vector<int>* assoc) {
+  static_assert(sizeof(types::KfFuseOpts) == sizeof(rebvio_hip_kf_fuse_opts) &&
+                    offsetof(types::KfFuseOpts, min_cos) == offsetof(rebvio_hip_kf_fuse_opts, min_cos) &&
+                    offsetof(types::KfFuseOpts, pixel_sigma) == offsetof(rebvio_hip_kf_fuse_opts, pixel_sigma) &&
+                    offsetof(types::KfFuseOpts, gate_sigma) == offsetof(rebvio_hip_kf_fuse_opts, gate_sigma) &&
+                    offsetof(types::KfFuseOpts, q_abs) == offsetof(rebvio_hip_kf_fuse_opts, q_abs) &&
+                    offsetof(types::KfFuseOpts, max_dist) == offsetof(rebvio_hip_kf_fuse_opts, max_dist) &&
+                    offsetof(types::KfFuseOpts, reserved) == offsetof(rebvio_hip_kf_fuse_opts, reserved),
+                "depth fusion options mirror the C-ABI's");
+  static_assert(sizeof(types::KfFuse) == sizeof(rebvio_hip_kf_fuse) && offsetof(types::KfFuse, associated) == offsetof(rebvio_hip_kf_fuse, associated) &&
+                    offsetof(types::KfFuse, fused) == offsetof(rebvio_hip_kf_fuse, fused) && offsetof(types::KfFuse, gated) == offsetof(rebvio_hip_kf_fuse, gated) &&
+                    offsetof(types::KfFuse, flat) == offsetof(rebvio_hip_kf_fuse, flat) && offsetof(types::KfFuse, clamped) == offsetof(rebvio_hip_kf_fuse, clamped),
+                "depth fusion counts mirror the C-ABI's");
+  rebvio_hip_kf_fuse_opts o;
+  std::memcpy(&o, &opts, sizeof(o));
+  if (!(o.pixel_sigma > 0.0) || o.max_dist < 0) {  // the context's pixel_uncertainty / search_range
+    rebvio_hip_kf_fuse_opts def;
+    rebvio_hip_default_kf_fuse_opts(map.ctx(), &def);
+    if (!(o.pixel_sigma > 0.0)) o.pixel_sigma = def.pixel_sigma;
+    if (o.max_dist < 0) o.max_dist = def.max_dist;
+  }
+  if (assoc) {
+    int n = 0;
+    check("rebvio_hip_kf_snapshot_download", handle_ ? rebvio_hip_kf_snapshot_download(handle_, nullptr, nullptr, 0, &n) : 0);
+    assoc->assign((size_t)n, std::numeric_limits<int>::min());
+  }
+  rebvio::types::KfFuse out;
+  check("rebvio_hip_kf_snapshot_fuse_depth",
+        rebvio_hip_kf_snapshot_fuse_depth(handle_, map.handle(), &o, pose.R, pose.t, reinterpret_cast<rebvio_hip_kf_fuse*>(&out),
+                                          assoc && !assoc->empty() ? assoc->data() : nullptr));
+  return out;
 }
 
 rebvio::types::KfPose EdgeMap::keyframeAlign(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfAlignOpts& opts,

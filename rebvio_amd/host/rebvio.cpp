@@ -111,6 +111,10 @@ void Rebvio::registerKeyframePoseCallback(std::function<void(uint64_t ts_us, con
   keyframe_pose_callbacks_.push_back(cb);
 }
 
+void Rebvio::registerKeyframeFuseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfFuse&)> cb) {
+  keyframe_fuse_callbacks_.push_back(cb);
+}
+
 void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
   point_cloud_callbacks_.push_back({cb, filter});
 }
@@ -335,11 +339,14 @@ void Rebvio::stateEstimationProcess() {
     int kf_matches = 0;    // of the pair, for the keyframe callbacks
     bool have_kf_pose = false;  // keyframe-pose callbacks: the new map's pose relative to the keyframe
     types::KfPose kf_pose;
+    bool have_kf_fuse = false;  // setKeyframeDepthFusion: the counts of the new map's fusion into the snapshot
+    types::KfFuse kf_fuse;
   } pending;
   // keyframe-pose callbacks: the snapshot of the current keyframe and the last pose estimated against it (the next one's guess)
   rebvio::KeyframeSnapshot kf_snapshot;
   types::KfPose kf_pose_last;
   bool kf_pose_warm = false;
+  bool kf_marked_here = false;  // this pair's new map is the one the snapshot was taken from: it is not fused into itself
   // Two steps: the counters (and with them the stop conditions of rebvio.cpp:236-252) are fetched as soon as the next pair's
   // first half is back; the callbacks run after that pair's second half has been launched, off the path between its halves.
   auto publish_pending = [&]() {
@@ -352,6 +359,8 @@ void Rebvio::stateEstimationProcess() {
     }
     if (pending.have_kf_pose)
       for (auto& cb : keyframe_pose_callbacks_) cb(pending.odometry.ts_us, pending.kf_pose);
+    if (pending.have_kf_fuse)
+      for (auto& cb : keyframe_fuse_callbacks_) cb(pending.odometry.ts_us, pending.kf_fuse);
     // every cloud goes back to its pool, also when a callback (or the wait) throws
     struct CloudsBack {
       std::vector<rebvio_hip_cloud*>& v;
@@ -596,12 +605,14 @@ void Rebvio::stateEstimationProcess() {
     }
     // Rebvio::requestKeyframe: the new map is marked behind this pair's second half (which writes the previous keyframe's ids into
     // it), in front of the next pair's first half (which hands the ids on)
+    kf_marked_here = false;
     if (keyframe_requested_.exchange(false)) {
       new_edge_map->markKeyframe();
       if (want_kf_pose) {  // the keyframe as it is now, right behind its mark; the previous one goes
         kf_snapshot = new_edge_map->keyframeSnapshot();
         if (keyframe_align_) kf_snapshot.addNormals(*new_edge_map);  // (setKeyframeAlign: the alignment's gradient test)
         kf_pose_warm = false;
+        kf_marked_here = true;
       }
     }
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
@@ -614,6 +625,13 @@ void Rebvio::stateEstimationProcess() {
         kf_pose_last = new_edge_map->keyframePose(kf_snapshot, types::KfPoseOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
       kf_pose_warm = kf_pose_last.status == 0;
       have_kf_pose = true;
+    }
+    // setKeyframeDepthFusion: behind an alignment of status 0 the new map is one more view of the keyframe's edges from a known pose
+    bool have_kf_fuse = false;
+    types::KfFuse kf_fuse;
+    if (have_kf_pose && keyframe_align_ && keyframe_depth_fusion_ && !kf_marked_here && kf_pose_last.status == 0) {
+      kf_fuse = kf_snapshot.fuseDepth(*new_edge_map, kf_pose_last);
+      have_kf_fuse = true;
     }
     timers.lap(2);
 
@@ -633,6 +651,8 @@ void Rebvio::stateEstimationProcess() {
     pending.clouds = clouds;
     pending.have_kf_pose = have_kf_pose;
     pending.kf_pose = kf_pose_last;
+    pending.have_kf_fuse = have_kf_fuse;
+    pending.kf_fuse = kf_fuse;
     timers.lap(3);
     timers.end_pair();
     timers.n++;

@@ -16,6 +16,9 @@
 // frame and again after every N-th record (default 10).
 // --kf-align FILE [--kf-every N]: the same file, from the alignment of the keyframe to every tracked map through the map's distance
 // field (Rebvio::setKeyframeAlign) instead of the correspondence chain. One of --kf-pose and --kf-align.
+// --kf-fuse FILE [--kf-every N]: implies the alignment (with or without --kf-align FILE; not with --kf-pose) and fuses every aligned
+// map into the keyframe snapshot (Rebvio::setKeyframeDepthFusion), one line per fusion, i.e. per pose record of status 0 other than
+// the keyframe's own: ts_us candidates associated fused gated flat clamped.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +31,7 @@
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
-  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path;
+  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path;
   bool kf_align = false;
   int kf_every = 10;
   int W = 0, H = 0;
@@ -39,7 +42,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] --out file\n", argv[0]);
+                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -72,6 +75,10 @@ int main(int argc, char** argv) {
       kf_align = a == "--kf-align";
       kf_pose_path = next();
     }
+    else if (a == "--kf-fuse") {
+      if (!kf_fuse_path.empty()) return usage();
+      kf_fuse_path = next();
+    }
     else if (a == "--kf-every") kf_every = std::atoi(next());
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
@@ -85,6 +92,10 @@ int main(int argc, char** argv) {
     }
   }
   if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1) return usage();
+  if (!kf_fuse_path.empty()) {  // the fusion runs behind the alignment only
+    if (!kf_pose_path.empty() && !kf_align) return usage();
+    kf_align = true;
+  }
   try {
     std::unique_ptr<rebvio::io::StreamSource> src;
     if (!asl.empty()) src.reset(new rebvio::io::EurocReader(asl, "cam0", "imu0", colour));
@@ -128,6 +139,7 @@ int main(int argc, char** argv) {
       rebvio.setDetectionMask(m.data);
     }
     std::mutex mu;
+    const bool want_kf = !kf_pose_path.empty() || !kf_fuse_path.empty();
     size_t n_odo = 0;
     std::chrono::steady_clock::time_point t_first, t_last;
     rebvio.registerOdometryCallback([&](rebvio::types::Odometry& o) {
@@ -136,23 +148,35 @@ int main(int argc, char** argv) {
       t_last = std::chrono::steady_clock::now();
       if (n_odo == 0) t_first = t_last;
       ++n_odo;
-      if (!kf_pose_path.empty() && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
+      if (want_kf && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
     });
-    std::FILE* kf_pose_file = nullptr;
-    size_t n_poses = 0;
-    if (!kf_pose_path.empty()) {
-      kf_pose_file = std::fopen(kf_pose_path.c_str(), "w");
-      if (!kf_pose_file) {
-        std::fprintf(stderr, "error: cannot write %s\n", kf_pose_path.c_str());
-        return 1;
+    std::FILE *kf_pose_file = nullptr, *kf_fuse_file = nullptr;
+    size_t n_poses = 0, n_fusions = 0;
+    if (want_kf) {
+      for (auto pf : {std::make_pair(&kf_pose_path, &kf_pose_file), std::make_pair(&kf_fuse_path, &kf_fuse_file)}) {
+        if (pf.first->empty()) continue;
+        *pf.second = std::fopen(pf.first->c_str(), "w");
+        if (!*pf.second) {
+          std::fprintf(stderr, "error: cannot write %s\n", pf.first->c_str());
+          return 1;
+        }
       }
       rebvio.registerKeyframePoseCallback([&](uint64_t ts_us, const rebvio::types::KfPose& p) {
+        ++n_poses;
+        if (!kf_pose_file) return;  // (--kf-fuse alone: the callback is what makes the thread align)
         std::fprintf(kf_pose_file, "%llu %d %d", (unsigned long long)ts_us, p.status, p.used);
         for (double v : p.R) std::fprintf(kf_pose_file, " %.17g", v);
         for (double v : p.t) std::fprintf(kf_pose_file, " %.17g", v);
         std::fprintf(kf_pose_file, "\n");
-        ++n_poses;
       });
+      if (kf_fuse_file) {
+        rebvio.registerKeyframeFuseCallback([&](uint64_t ts_us, const rebvio::types::KfFuse& f) {
+          std::fprintf(kf_fuse_file, "%llu %d %d %d %d %d %d\n", (unsigned long long)ts_us, f.candidates, f.associated, f.fused, f.gated, f.flat,
+                       f.clamped);
+          ++n_fusions;
+        });
+        rebvio.setKeyframeDepthFusion(true);
+      }
       rebvio.setKeyframeAlign(kf_align);
       rebvio.requestKeyframe();
     }
@@ -169,9 +193,11 @@ int main(int argc, char** argv) {
     rebvio.waitIdle();
     std::fprintf(stderr, "frames=%zu odometry=%zu running=%d\n", n, n_odo, (int)rebvio.running());
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
-    if (kf_pose_file) {
-      std::fclose(kf_pose_file);
-      std::fprintf(stderr, "kf_poses=%zu\n", n_poses);
+    if (kf_pose_file) std::fclose(kf_pose_file);
+    if (want_kf) std::fprintf(stderr, "kf_poses=%zu\n", n_poses);
+    if (kf_fuse_file) {
+      std::fclose(kf_fuse_file);
+      std::fprintf(stderr, "kf_fusions=%zu\n", n_fusions);
     }
     if (n_odo > 1) {  // wall clock between the first and the last published odometry: the whole class, input thread included
       const double sec = std::chrono::duration<double>(t_last - t_first).count();
