@@ -33,7 +33,7 @@ extern "C" {
  *    rebvio_hip_kf_snapshot_add_normals / _download_normals and the alignment entries rebvio_hip_default_kf_align_opts,
  *    rebvio_hip_map_keyframe_align, their struct rebvio_hip_kf_align_opts and the test hook rebvio_hip_test_kf_align_host; the
  *    depth fusion rebvio_hip_default_kf_fuse_opts, rebvio_hip_kf_snapshot_fuse_depth, their structs rebvio_hip_kf_fuse_opts /
- *    rebvio_hip_kf_fuse and the test hook rebvio_hip_test_kf_fuse_host. */
+ *    rebvio_hip_kf_fuse and the test hook rebvio_hip_test_kf_fuse_host; the test hook rebvio_hip_test_handover_counters. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -771,6 +771,13 @@ int rebvio_hip_test_glue_set_next(rebvio_hip_ctx* ctx, const float* R_next, int 
  * like to the reader. */
 int rebvio_hip_test_forge_record_stamp(rebvio_hip_ctx* ctx);
 int rebvio_hip_batch_test_forge_record_stamp(rebvio_hip_batch* b);
+
+/* Test hook for the streaming driver's hand-over between its streams (REBVIO_HIP_HANDOVER): counts since the context
+ * was created. out[3 * s + 0 .. 2], s = 0 track / 1 scan / 2 keyline stream: event waits queued on the stream, waits left out
+ * because the host knew their reason gone (keyline stream: the release token of the edge map it reuses had been observed), events
+ * recorded on the stream; out[9]: reuses of an edge map whose release token the host had not observed yet (an event is recorded
+ * on the track stream then and waited for). */
+int rebvio_hip_test_handover_counters(rebvio_hip_ctx* ctx, unsigned long long out[10]);
 
 /* Test hook for leaks: the device buffers, pinned host buffers, events and streams that the contexts, edge maps, point clouds and
  * batches of this process hold right now, as one exact count (not bytes). Creating any of them raises it, destroying a context

@@ -215,6 +215,7 @@ SIGNATURES = {
     "rebvio_hip_test_forge_record_stamp": (C.c_int, [_vp]),
     "rebvio_hip_batch_test_forge_record_stamp": (C.c_int, [_vp]),
     "rebvio_hip_test_live_resources": (C.c_long, []),
+    "rebvio_hip_test_handover_counters": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "rebvio_hip_profile_enable": (C.c_int, [_vp, C.c_int]),
     "rebvio_hip_profile_select": (C.c_int, [_vp, C.c_char_p]),
     "rebvio_hip_profile_reset": (C.c_int, [_vp]),
@@ -1066,6 +1067,16 @@ class Context:
     def pairs_started(self) -> int:
         """Frame pairs the streaming driver has queued on the device so far."""
         return int(lib().rebvio_hip_pairs_started(self.h))
+
+    def handover_counters(self) -> dict:
+        """The streaming driver's hand-over counters since the context was created (rebvio_hip_test_handover_counters): per stream
+        ("track", "scan", "keyline") a dict of waits "queued", waits "skipped" and "events" recorded, and "reuse_fallbacks"."""
+        v = (C.c_ulonglong * 10)()
+        _chk(lib().rebvio_hip_test_handover_counters(self.h, v))
+        d = {s: dict(queued=int(v[3 * i]), skipped=int(v[3 * i + 1]), events=int(v[3 * i + 2]))
+             for i, s in enumerate(("track", "scan", "keyline"))}
+        d["reuse_fallbacks"] = int(v[9])
+        return d
 
     def keyframe_next(self):
         """The next frame pushed becomes a keyframe (rebvio_hip_keyframe_next): its map is marked between the pair that ends at it

@@ -228,6 +228,9 @@ struct rebvio_hip_map {
   hipEvent_t done{};   // last track-stream consumer finished, recorded at release
   hipEvent_t done_ref{};  // ... or (streaming driver) the result-slot event of the pair that used the map last: no packet of its own
   bool has_done = false;
+  // ... or (streaming driver, stamp hand-over) no event at all: the map's last consumer has finished once the pair queue has proven
+  // this many steps complete (PairQueue::proven). 0: none, `done` / `done_ref` hold.
+  uint64_t done_token = 0;
   uint64_t release_seq = 0;  // order of release (pool reuse is oldest-first)
   bool df_built = false;
   bool raster_order = false;  // keylines + row_start as detection left them (false after map_upload)
@@ -305,13 +308,24 @@ struct PairQueue {
     rebvio_hip_map* nm[kMaxLanes];  // each lane's new map
     uint32_t seq = 0;               // the step's sequence stamp (all lanes)
     int slot = -1;
-    int ev_slot = -1;               // the slot whose event stands for this step's completion (its group's last step)
+    int ev_slot = -1;               // the slot whose event stands for this step's completion (its group's last step); -1: none,
+                                    // the successor's record stamp does (streaming driver, see harvest)
+    uint64_t idx = 0;               // steps queued before this one
   };
   Step ring[kPairSlots];
   int head = 0, count = 0;
+  uint64_t pushed = 0;               // steps queued so far
+  // Steps the HOST knows to be complete: it has read their records. Every kernel of step k < proven has ended; maps released with
+  // the token k + 1 are idle once proven reaches it (release_map). Written by the tracking thread, read by whoever detects.
+  std::atomic<uint64_t> proven{0};
   Step& operator[](int i) { return ring[(head + i) % kPairSlots]; }
-  void push_back(const Step& st) { ring[(head + count++) % kPairSlots] = st; }
+  void push_back(const Step& st) {
+    Step& d = ring[(head + count++) % kPairSlots];
+    d = st;
+    d.idx = pushed++;
+  }
   void pop_front() {
+    proven.store(ring[head].idx + 1, std::memory_order_release);
     head = (head + 1) % kPairSlots;
     --count;
   }
@@ -421,6 +435,16 @@ struct rebvio_hip_ctx {
   hm::M3 gs_R{};                  // host mirror of the device state's prior rotation (with Bg / W_Bg above)
   int min_pool = 0;               // edge maps to allocate before one is reused (see acquire_map)
   int lead = 5;                   // detected frames queued when a pair is started (REBVIO_HIP_LEAD 3..12, see push_frame)
+  // How the streaming driver's track stream hands pairs to the host and maps back to the detect stage. Default: it records no
+  // event - harvest reads the successor's record stamp, a pair's old map is released with a token. REBVIO_HIP_HANDOVER=events:
+  // one event per group of pairs (and per pair queued alone), event-based harvest and release.
+  bool handover_events = false;
+  // [stream: track, scan, keyline] waits queued / waits left out because the host knew their reason gone (a map's release token
+  // observed) / events recorded, and the reuses of a map whose token the host had not observed yet
+  // (rebvio_hip_test_handover_counters; printed by flush with REBVIO_HIP_DEBUG)
+  struct Handover {
+    std::atomic<uint64_t> queued[3]{}, skipped[3]{}, events[3]{}, reuse_fallbacks{0};
+  } ho;
   int group = 4;                  // pairs queued together (REBVIO_HIP_GROUP 1..6, see stream_enqueue_group)
   // Sequence stamps of the host-visible records (PairSlot::seq, GlueRec::seq_gs / seq_out): every pair that is queued takes
   // the next non-zero value, its kernels store it behind everything else they write into the records, and whoever reads a
@@ -524,7 +548,7 @@ struct rebvio_hip_ctx {
 };
 
 namespace {
-void release_map(rebvio_hip_map* m, hipEvent_t done_ref = nullptr, bool record_done = true);
+void release_map(rebvio_hip_map* m, hipEvent_t done_ref = nullptr, bool record_done = true, uint64_t done_token = 0);
 void free_cloud_device(rebvio_hip_cloud* cl);
 // the map a flushed stream with gyro rotations would continue from (rebvio_hip_ctx::carry) goes back to the pool
 inline void drop_carry(rebvio_hip_ctx* c) {
@@ -700,6 +724,19 @@ hipError_t trk_wait_ready(hipStream_t s, rebvio_hip_map* m) {
   }
   return hipStreamWaitEvent(s, m->ready, 0);
 }
+// The streaming driver's waits and records, counted (`on`: kOnTrk / kOnScan / kOnKey, the stream s of context c). A wait on an
+// event that has completed is not asked about first: the runtime drops such a wait itself (tools/handover_probe.hip: no packet,
+// 0.14 us of the caller, as much as the hipEventQuery that would replace it). A record is what costs: 2.9 us between the two
+// kernels it stands between and 1.1 - 1.4 us of the launching thread.
+enum { kOnTrk = 0, kOnScan = 1, kOnKey = 2 };
+hipError_t wait_counted(rebvio_hip_ctx* c, int on, hipStream_t s, hipEvent_t e) {
+  c->ho.queued[on].fetch_add(1, std::memory_order_relaxed);
+  return hipStreamWaitEvent(s, e, 0);
+}
+hipError_t record_counted(rebvio_hip_ctx* c, int on, hipStream_t s, hipEvent_t e) {
+  c->ho.events[on].fetch_add(1, std::memory_order_relaxed);
+  return hipEventRecord(e, s);
+}
 // The same, once per map and context stream: every wait is a barrier packet of its own between two kernels of the track
 // stream (~2 us each on the pair-to-pair critical path); `ready` is recorded once per detection, a second wait adds nothing.
 hipError_t trk_wait_ready_once(rebvio_hip_ctx* c, rebvio_hip_map* m) {
@@ -731,7 +768,7 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
     HIPCHK(hipEventRecord(c->pin_ev[j.pin_slot], c->s_det));
   }
   // scans of this frame (s_det); its DoG / gradient buffers were last read by the candidate kernel two frames ago
-  if (c->prev_ready[b]) HIPCHK(hipStreamWaitEvent(c->s_det, c->prev_ready[b], 0));
+  if (c->prev_ready[b]) HIPCHK(wait_counted(c, kOnScan, c->s_det, c->prev_ready[b]));
   const void* img = j.img;
   int is_u8 = j.is_u8;
   int fmt = is_u8 ? j.fmt : 0;
@@ -749,17 +786,28 @@ int detect_launch(rebvio_hip_ctx* c, const rebvio_hip_ctx::DetJob& j) {
   // Their inputs sb.a[] are then read while the scan stream already works on the next frame, hence the pair per parity;
   // the frame after next waits for this frame's `ready` event (prev_ready[b]) above.
   launch_scale_space(c->s_det, c->K, img, is_u8, sb, c->widths, db.rowcount, 1, fmt);
-  HIPCHK(hipEventRecord(c->ev_scan[b], c->s_det));
+  HIPCHK(record_counted(c, kOnScan, c->s_det, c->ev_scan[b]));
   // keyline extraction + chaining (s_key), overlapping the next frame's scans
-  HIPCHK(hipStreamWaitEvent(c->s_key, c->ev_scan[b], 0));
+  HIPCHK(wait_counted(c, kOnKey, c->s_key, c->ev_scan[b]));
   launch_scale_space(c->s_key, c->K, img, is_u8, sb, c->widths, db.rowcount, 2);
-  if (m->has_done) HIPCHK(hipStreamWaitEvent(c->s_key, m->done_ref ? m->done_ref : m->done, 0));
+  // the map's previous life: its last consumer on the track stream
+  if (m->has_done && m->done_token == 0) {
+    HIPCHK(wait_counted(c, kOnKey, c->s_key, m->done_ref ? m->done_ref : m->done));
+  } else if (m->has_done && c->q.proven.load(std::memory_order_acquire) >= m->done_token) {
+    c->ho.skipped[kOnKey].fetch_add(1, std::memory_order_relaxed);  // the host has read the records that prove it idle
+  } else if (m->has_done) {
+    // Released with a token the host has not observed yet (rare: the pool hands out the oldest release first). Every consumer of
+    // the map was queued before its release and the track stream is in order: an event recorded there now stands for the last.
+    c->ho.reuse_fallbacks.fetch_add(1, std::memory_order_relaxed);
+    HIPCHK(record_counted(c, kOnTrk, c->s_trk, m->done));
+    HIPCHK(wait_counted(c, kOnKey, c->s_key, m->done));
+  }
   launch_keylines(c->s_key, c->K, sb, db, m->d, j.det_in, j.det_out, j.prev_st, c->widths, j.mask_static, j.mask_frame);
   HIPCHK(hipGetLastError());
   // distance field of this map, behind its keylines on the same stream (stream order is the dependency)
   launch_df_build(c->s_key, c->K, m->d, j.det_out, true);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(m->ready, c->s_key));
+  HIPCHK(record_counted(c, kOnKey, c->s_key, m->ready));
   c->prev_ready[b] = m->ready;  // (pooled maps and their events live as long as the context)
   return 0;
 }
@@ -935,6 +983,17 @@ uint32_t next_stamp(uint32_t* counter) {
 constexpr int kStaleRecord = -12;
 const char* const kStaleRecordMsg = "a pair's record was read before the device had written it (sequence stamp mismatch)";
 
+// A result slot counts once its stamp AND its checksum fit: the words are re-read on every try (writes to host memory may arrive
+// out of order; a torn read fails the sum and is simply repeated).
+bool slot_complete(const PairSlot* slot, uint32_t seq) {
+  static_assert(offsetof(PairSlot, seq) == sizeof(LmState) + 2 * sizeof(MapState), "PairSlot::sum covers lm, new_st, old_st");
+  const volatile unsigned* w = reinterpret_cast<const volatile unsigned*>(slot);
+  if (*reinterpret_cast<const volatile unsigned*>(&slot->seq) != seq) return false;
+  unsigned x = 0u;
+  for (size_t i = 0; i < offsetof(PairSlot, seq) / sizeof(unsigned); ++i) x ^= w[i];
+  return (x ^ seq) == *reinterpret_cast<const volatile unsigned*>(&slot->sum);
+}
+
 // Waits for a pair's host records (per-pair API: the result slot and the extRotVel block records behind it) by polling their
 // sequence stamps. The stream is queried now and then so that a device-side failure ends the wait with its error; after two
 // seconds without the stamps the stream is synchronised and the stamps decide (-12).
@@ -957,17 +1016,7 @@ int poll_pair_records(rebvio_hip_ctx* c, const PairSlot* slot, uint32_t seq) {
     }
     return 0;
   };
-  // A record counts once its stamp AND its checksum fit: the words are re-read on every try (writes to host memory may arrive out
-  // of order; a torn read fails the sum and is simply repeated).
-  auto slot_ok = [&]() -> bool {
-    const volatile unsigned* w = reinterpret_cast<const volatile unsigned*>(slot);
-    if (*reinterpret_cast<const volatile unsigned*>(&slot->seq) != seq) return false;
-    unsigned x = 0u;
-    for (size_t i = 0; i < offsetof(PairSlot, seq) / sizeof(unsigned); ++i) x ^= w[i];
-    return (x ^ seq) == *reinterpret_cast<const volatile unsigned*>(&slot->sum);
-  };
-  static_assert(offsetof(PairSlot, seq) == sizeof(LmState) + 2 * sizeof(MapState), "PairSlot::sum covers lm, new_st, old_st");
-  while (!slot_ok()) {
+  while (!slot_complete(slot, seq)) {
     const int e = wait_step();
     if (e) return e;
   }
@@ -1361,6 +1410,7 @@ int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
   HIPCHK(c->own.pinned(&c->h_gstate, 2, false));
   if (const char* l = std::getenv("REBVIO_HIP_LEAD")) c->lead = std::min(12, std::max(3, std::atoi(l)));
   if (const char* g = std::getenv("REBVIO_HIP_GROUP")) c->group = std::min(6, std::max(1, std::atoi(g)));
+  if (const char* e = std::getenv("REBVIO_HIP_HANDOVER")) c->handover_events = std::strcmp(e, "events") == 0;
   if (const char* e = std::getenv("REBVIO_HIP_LM_THREADS")) {
     const int v = std::atoi(e);
     if (v == 256 || v == 512 || v == 1024) c->lm_threads = v;
@@ -2467,7 +2517,8 @@ namespace {
 // done_ref: an event already recorded behind the map's last consumer. Null: one is recorded here on the track stream, unless
 // record_done is false (a batch releases a step's maps at one point of the track stream, and only its last lane's is marked:
 // the detect stage waits for that one event).
-void release_map(rebvio_hip_map* m, hipEvent_t done_ref, bool record_done) {
+// done_token: no event; the map is idle once its context's pair queue has proven that many steps complete (PairQueue::proven).
+void release_map(rebvio_hip_map* m, hipEvent_t done_ref, bool record_done, uint64_t done_token) {
   if (!m || !m->in_use) return;
   rebvio_hip_ctx* c = m->ctx;
   wait_enqueued(m);
@@ -2480,11 +2531,12 @@ void release_map(rebvio_hip_map* m, hipEvent_t done_ref, bool record_done) {
       c->bf_copy_queued[r] = true;
   }
   std::lock_guard<std::mutex> pool_lk(c->pool_mu);
-  m->done_ref = done_ref;
-  if (done_ref) {
+  m->done_ref = done_token ? nullptr : done_ref;
+  m->done_token = done_token;
+  if (done_ref || done_token) {
     m->has_done = true;
   } else if (record_done) {
-    (void)hipEventRecord(m->done, c->s_trk);
+    (void)record_counted(c, kOnTrk, c->s_trk, m->done);
     m->has_done = true;
   }
   if (c->df_map == m) c->df_map = nullptr;
@@ -3089,14 +3141,53 @@ int finish_step(PairQueue& q, const LaneSet& L, const PairQueue::Step& a, const 
   return 0;
 }
 
+// Has step n, queued without an event, left its result slots? 1: every lane's slot carries n's stamp and adds up; 0: not yet
+// (block == false). The stamp is stored by the last wave of n's directedMatch launch, which started only after the kernels of
+// the step in front of n had ended: it proves that step complete, records and maps. block: polls the slots; the track stream is
+// queried every few thousand polls, and once it is idle - n's kernels have run, nothing can arrive any more - the slots get one
+// last look: the records, or -12 (a forged or lost stamp). The wait is bounded by the stream's own work, not by a time-out.
+int step_stamped(PairQueue& q, const LaneSet& L, const PairQueue::Step& n, bool block) {
+  auto all_lanes = [&]() -> bool {
+    for (int l = 0; l < L.n; ++l)
+      if (!slot_complete(L.c[l]->slot[n.slot], n.seq)) return false;
+    return true;
+  };
+  if (!all_lanes()) {
+    if (!block) return 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 1;; ++spins) {
+      __builtin_ia32_pause();
+      if (all_lanes()) break;
+      if ((spins & 0xFFFu) != 0u) continue;
+      const hipError_t e = hipStreamQuery(L.c[0]->s_trk);  // (the lanes of a batch share its track stream)
+      if (e == hipErrorNotReady) continue;
+      if (e != hipSuccess) return fail("track stream", e);
+      if (all_lanes()) break;
+      for (int l = 0; l < L.n; ++l) {
+        const int rc = lm_timed_out(L.c[l], L.device, L.owner, L.who);
+        if (rc) return rc;
+      }
+      return fail_msg(kStaleRecordMsg, kStaleRecord);
+    }
+    q.t_wait += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return 1;
+}
+
 // Reports the steps whose successor has completed (a step's match counters ride in its successor's slots: the successor's first
-// kernel copies its old maps' state records); `need` > 0: blocks until at least that many have been reported.
+// kernel copies its old maps' state records); `need` > 0: blocks until at least that many have been reported. The successor's
+// completion is its group's event where it has one (batch driver, REBVIO_HIP_HANDOVER=events), else its record stamp (step_stamped).
 int harvest(PairQueue& q, const LaneSet& L, int need) {
   MapState st[kMaxLanes];
   while (q.count >= 2) {
     const PairQueue::Step& a = q[0];
     const PairQueue::Step& n = q[1];
-    if (need > 0) {
+    if (n.ev_slot < 0) {
+      const int w = step_stamped(q, L, n, need > 0);
+      if (w < 0) return w;
+      if (w == 0) break;
+    } else if (need > 0) {
       const auto t0 = std::chrono::steady_clock::now();
       HIPCHK(hipEventSynchronize(q.slot_ev[n.ev_slot]));
       q.t_wait += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
@@ -3127,7 +3218,10 @@ int drain(PairQueue& q, const LaneSet& L) {
   if (rc) return rc;
   if (q.count == 1) {
     const PairQueue::Step& a = q[0];
-    HIPCHK(hipEventSynchronize(q.slot_ev[a.ev_slot]));
+    if (a.ev_slot >= 0)
+      HIPCHK(hipEventSynchronize(q.slot_ev[a.ev_slot]));
+    else
+      HIPCHK(hipStreamSynchronize(L.c[0]->s_trk));
     for (int l = 0; l < L.n; ++l) {
       rebvio_hip_ctx* c = L.c[l];
       rc = lm_timed_out(c, L.device, L.owner, L.who);
@@ -3189,9 +3283,11 @@ LaneSet stream_lanes(rebvio_hip_ctx* const& c) { return LaneSet{&c, 1, c->device
 // `npairs` consecutive pairs (frames[0..npairs]) as ONE group on the track stream. Every stream operation between two
 // kernels is a packet of its own for the command processor, and with the kernels queued back to back those packets are what
 // is left between them (measured with in-kernel stamps: ~6 us per event record / event wait on the pair-to-pair path). A group
-// carries two of them whatever its size: one wait for the detection of its NEWEST map (the keyline stream is in order, so the
-// maps before it are ready too) and one event behind its last kernel, which stands for every pair's completion and for the
-// release of every old map.
+// carries one of them whatever its size: the wait for the detection of its NEWEST map (the keyline stream is in order, so the
+// maps before it are ready too; the runtime drops the wait where that detection has finished). With REBVIO_HIP_HANDOVER=events
+// a second one: an event behind its last kernel, which stands for every pair's completion and for the release of every old map.
+// Without it nothing is recorded: harvest learns a pair's completion from its successor's record stamp, and the old maps go back
+// to the pool with the number of pairs the host has to have read by then.
 int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
   // the slot of pair k is reused by pair k + kSlots: its record (and its successor's) must have been read
   while (c->q.count + npairs > rebvio_hip_ctx::kSlots - 1) {
@@ -3201,12 +3297,14 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
   hipStream_t s = c->s_trk;
   if (!c->frames[0]->trk_waited) {  // first group of a stream
     wait_enqueued(c->frames[0]);
+    c->ho.queued[kOnTrk].fetch_add(1, std::memory_order_relaxed);
     HIPCHK(trk_wait_ready(s, c->frames[0]));
     c->frames[0]->trk_waited = true;
   }
   {
     rebvio_hip_map* newest = c->frames[(size_t)npairs];
     wait_enqueued(newest);
+    c->ho.queued[kOnTrk].fetch_add(1, std::memory_order_relaxed);
     HIPCHK(trk_wait_ready(s, newest));
     for (int g = 1; g <= npairs; ++g) {
       c->frames[(size_t)g]->trk_waited = true;
@@ -3266,10 +3364,17 @@ int stream_enqueue_group(rebvio_hip_ctx* c, int npairs) {
     last_slot = slot;
     c->pair_seq++;
   }
-  HIPCHK(hipEventRecord(c->q.slot_ev[last_slot], s));
-  for (int g = 0; g < npairs; ++g) {
-    c->q[c->q.count - 1 - g].ev_slot = last_slot;
-    release_map(c->frames[(size_t)g], c->q.slot_ev[last_slot]);  // stream-ordered: reusable once the group has drained
+  if (c->handover_events) {
+    HIPCHK(record_counted(c, kOnTrk, s, c->q.slot_ev[last_slot]));
+    for (int g = 0; g < npairs; ++g) {
+      c->q[c->q.count - 1 - g].ev_slot = last_slot;
+      release_map(c->frames[(size_t)g], c->q.slot_ev[last_slot]);  // stream-ordered: reusable once the group has drained
+    }
+  } else {
+    // No event: pair k's old map is idle once the host has read pair k's records (harvest: the stamp of pair k + 1), and whoever
+    // reuses it earlier records an event then (detect_launch).
+    for (int g = 0; g < npairs; ++g)
+      release_map(c->frames[(size_t)g], nullptr, false, c->q[c->q.count - npairs + g].idx + 1);
   }
   c->frames.erase(c->frames.begin(), c->frames.begin() + npairs);
   return 0;
@@ -3299,6 +3404,11 @@ int push_frame(rebvio_hip_ctx* c, const uint8_t* frame_dev, const uint8_t* frame
   }
   if (keylines) *keylines = -1;
   c->min_pool = c->lead + 3 * c->group + 3;
+  // Stamp hand-over: a map is reused without a wait only once the host has read its last pair's records, and the queue holds up
+  // to kSlots - 1 pairs the host has not read. With kSlots free maps between a release and its reuse (oldest first) that pair has
+  // always left the queue: no event and no wait in steady state. (Fewer maps work too, through the fall-back of detect_launch -
+  // whose event stands behind EVERY pair queued by then, so the keyline stream waits longer than the map needs.)
+  if (!c->handover_events) c->min_pool = std::max(c->min_pool, c->lead + c->group + rebvio_hip_ctx::kSlots + 1);
   int rc;
   if (frame_host) {
     const size_t rowb = (size_t)c->P.cols * px::bytes_per_pixel(fmt);
@@ -3434,6 +3544,18 @@ int rebvio_hip_test_forge_record_stamp(rebvio_hip_ctx* c) {
 }
 
 
+// Test hook: the hand-over counters of the context's streams since it was created (rebvio_hip_ctx::ho).
+int rebvio_hip_test_handover_counters(rebvio_hip_ctx* c, unsigned long long out[10]) {
+  if (!c || !out) return -3;
+  for (int i = 0; i < 3; ++i) {
+    out[3 * i] = c->ho.queued[i].load(std::memory_order_relaxed);
+    out[3 * i + 1] = c->ho.skipped[i].load(std::memory_order_relaxed);
+    out[3 * i + 2] = c->ho.events[i].load(std::memory_order_relaxed);
+  }
+  out[9] = c->ho.reuse_fallbacks.load(std::memory_order_relaxed);
+  return 0;
+}
+
 int rebvio_hip_next_record(rebvio_hip_ctx* c, rebvio_hip_pair_out* out, int* keylines) { return pop_records(c->q, 1, out, keylines); }
 
 int rebvio_hip_flush(rebvio_hip_ctx* c) {
@@ -3513,6 +3635,13 @@ int rebvio_hip_flush(rebvio_hip_ctx* c) {
     if (c->t_det_n)
       std::fprintf(stderr, "[rebvio_hip] detect: %.1f us of launches per frame over %llu frames\n", c->t_det_launch / (double)c->t_det_n,
                    (unsigned long long)c->t_det_n);
+    static const char* const on[3] = {"track", "scan", "keyline"};
+    for (int i = 0; i < 3; ++i)
+      std::fprintf(stderr, "[rebvio_hip] %s stream since create: waits queued %llu, skipped %llu, events recorded %llu%s", on[i],
+                   (unsigned long long)c->ho.queued[i].load(), (unsigned long long)c->ho.skipped[i].load(),
+                   (unsigned long long)c->ho.events[i].load(), i < 2 ? "\n" : "");
+    std::fprintf(stderr, " | map reuse fall-backs %llu (hand-over: %s)\n", (unsigned long long)c->ho.reuse_fallbacks.load(),
+                 c->handover_events ? "events" : "stamps");
     // (the counters start again: a caller that flushes between phases reads each phase on its own)
     c->t_detect_enq = c->t_enq = c->q.t_wait = c->t_queued = 0;
     c->t_frames = 0;
