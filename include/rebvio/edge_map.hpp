@@ -49,6 +49,12 @@ class KeyframeSnapshot {
   // when not associated. Fusing one map twice counts its pixels twice.
   rebvio::types::KfFuse fuseDepth(const rebvio::EdgeMap& map, const rebvio::types::KfPose& pose,
                                   const rebvio::types::KfFuseOpts& opts = rebvio::types::KfFuseOpts(), std::vector<int>* assoc = nullptr);
+  // the snapshot's depth-bearing keylines - as marked, or as fuseDepth has refined them - as a point cloud, filtered and posed on
+  // the device (rebvio_hip_kf_snapshot_point_cloud says exactly which keylines and where; synchronous, from the tracking thread).
+  // The default pose is the keyframe's own frame in keyframe depth units; `keyline` is the index in the snapshot and
+  // gradient_norm is 0: a snapshot does not keep it.
+  std::vector<rebvio::types::CloudPoint> pointCloud(const rebvio::types::CloudFilter& filter = rebvio::types::CloudFilter(),
+                                                    const rebvio::types::CloudPose& pose = rebvio::types::CloudPose()) const;
   explicit operator bool() const { return handle_ != nullptr; }
   rebvio_hip_kf_snapshot* handle() const { return handle_; }
 

@@ -82,6 +82,21 @@ class Rebvio {
   // without this; the odometry does not change by a digit either way. Callable from any thread.
   void setKeyframeDepthFusion(bool on) { keyframe_depth_fusion_ = on; }
   void registerKeyframeFuseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfFuse&)> cb);
+  // addition: every keyframe's depth-bearing keylines as one point cloud, handed out as the keyframe is retired
+  // (KeyframeSnapshot::pointCloud; rebvio_hip.h defines it). While such a callback is registered requestKeyframe snapshots the
+  // keyframe behind its mark as a keyframe-pose callback makes it do, and remembers R_global, Pos, K of the odometry record of the map
+  // it was marked on. The next requestKeyframe replaces that snapshot; before it does, the outgoing keyframe's cloud is queued on the
+  // device with that remembered pose - metric and in the odometry's frame, like the per-map clouds - and it is delivered with the
+  // record of the pair whose new map takes over as keyframe (the next record published), right after the other keyframe callbacks,
+  // on the state-estimation thread: ts_us is the retired keyframe's own stamp, pose the remembered one, `keyline` the index in the
+  // keyframe, gradient_norm 0; the points are valid during the call. One cloud per retired keyframe is the unit a mapping consumer
+  // concatenates. With setKeyframeAlign and setKeyframeDepthFusion on (and the keyframe-pose callback they need) it is the refined
+  // keyframe, every aligned view folded in; without them the keyframe as marked. The keyframe that is still current when
+  // processing ends is not handed out: one more requestKeyframe before the last frames retires it. As with a point-cloud callback
+  // the next pair's first rotation is then not fused into this pair's last kernel; the odometry does not change by a digit.
+  // Without one the thread runs exactly the calls it ran. Register before the first frame is handed in.
+  void registerKeyframeCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb,
+                                     rebvio::types::CloudFilter filter = rebvio::types::CloudFilter());
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -119,6 +134,7 @@ class Rebvio {
     rebvio::types::CloudFilter filter;
   };
   std::vector<PointCloudCallback> point_cloud_callbacks_;
+  std::vector<PointCloudCallback> keyframe_cloud_callbacks_;
   std::vector<std::function<void(uint64_t, int, int)>> keyframe_callbacks_;
   std::vector<std::function<void(uint64_t, const rebvio::types::KfPose&)>> keyframe_pose_callbacks_;
   std::atomic<bool> keyframe_requested_{false};

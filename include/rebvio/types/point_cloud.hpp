@@ -100,9 +100,9 @@ struct KfFuse {
 };
 static_assert(sizeof(KfFuse) == 24, "KfFuse must stay layout-compatible with rebvio_hip_kf_fuse");
 
-// What a point-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
+// What a point-cloud or keyframe-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
-  uint64_t ts_us;            // the odometry record's stamp (= the map's)
+  uint64_t ts_us;            // the odometry record's stamp (= the map's); keyframe cloud: the stamp of the record the keyframe was marked on
   CloudPose pose;            // R_global, Pos, K of that record: the points are metric, in the odometry's frame
   const CloudPoint* points;
   size_t size;

@@ -33,7 +33,8 @@ extern "C" {
  *    rebvio_hip_kf_snapshot_add_normals / _download_normals and the alignment entries rebvio_hip_default_kf_align_opts,
  *    rebvio_hip_map_keyframe_align, their struct rebvio_hip_kf_align_opts and the test hook rebvio_hip_test_kf_align_host; the
  *    depth fusion rebvio_hip_default_kf_fuse_opts, rebvio_hip_kf_snapshot_fuse_depth, their structs rebvio_hip_kf_fuse_opts /
- *    rebvio_hip_kf_fuse and the test hook rebvio_hip_test_kf_fuse_host; the test hook rebvio_hip_test_handover_counters. */
+ *    rebvio_hip_kf_fuse and the test hook rebvio_hip_test_kf_fuse_host; the test hook rebvio_hip_test_handover_counters;
+ *    the snapshot point cloud rebvio_hip_kf_snapshot_point_cloud(_async) and the test hook rebvio_hip_test_kf_cloud_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -511,6 +512,40 @@ int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int col
                                  const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
                                  const rebvio_hip_kf_fuse_opts* opts, const double R[9], const double t[3], rebvio_hip_kf_fuse* out,
                                  int* assoc /*NULL or kf_size ints*/);
+
+/* Point cloud of a keyframe snapshot: its depth-bearing keylines - as marked, or as rebvio_hip_kf_snapshot_fuse_depth has refined
+ * them - filtered and posed on the device by kernels of their own (the compaction of rebvio_hip_map_point_cloud over the snapshot's
+ * buffers; nothing of the map's kernels changes). Per snapshot keyline j < size, with pos_img_j, rho_j, sigma_rho_j, matches_j as the
+ * snapshot holds them when the extraction runs in track-stream order (every fusion queued before it is seen, none queued after it):
+ *   filter    the test of rebvio_hip_map_point_cloud, term for term: matches >= min_matches, rho >= rho_min, rho <= rho_max,
+ *             sigma_rho <= max_rel_sigma * rho (one rounded fp32 multiply); a NaN fails; invalid filters are refused by its rules
+ *   position  its formula, operation for operation, fp32, no contraction, fm of the context's parameters:
+ *               u = pos_img[0] / fm;  v = pos_img[1] / fm;  z = scale / rho;  xc = u * z;  yc = v * z;
+ *               xyz[i] = ((R[3i] * xc + R[3i+1] * yc) + R[3i+2] * z) + t[i]
+ *             pose NULL = identity, zero, 1: the cloud in the keyframe's own frame in keyframe depth units, the units of
+ *             rebvio_hip_kf_pose::t
+ *   record    rebvio_hip_cloud_point: rho, sigma_rho, matches as stored in the snapshot; keyline = j, strictly increasing, and the
+ *             index into rebvio_hip_kf_snapshot_download / _download_normals (a consumer joins the normals through it);
+ *             gradient_norm = +0.0f: a snapshot does not keep the gradient norm
+ * *count = keylines that pass; min(count, cap) records are written (a cap below count is no error). No atomic decides a place:
+ * the cloud is reproducible bit for bit.
+ * Both entries are track-side and follow the calling rules of rebvio_hip_map_keyframe_snapshot; the queued one is allowed between
+ * _finish_async(k) and _begin(k+1) and waits for nothing on the host (the size is read on the device: a snapshot of size 0 gives
+ * count 0). It returns a handle of the kind rebvio_hip_map_point_cloud_async returns: rebvio_hip_cloud_wait / _release serve it
+ * unchanged (device_points, -12, -10), and buffers, stream and stamps are the context's cloud pool, whichever kind of cloud made
+ * them. A snapshot has no R_prior_next state: there is no -7. The snapshot may be released right after the queued call.
+ * -3, before the device is touched: null snapshot / count / out, negative cap, null points with cap > 0, an invalid filter, NaN in
+ * the pose; -10: the context has been destroyed.
+ * rebvio_hip_test_kf_cloud_host (test hook, touches no device): the same per-record statement on the host over caller arrays
+ * (snap_prs4 = kf_size records of pos_img.x, pos_img.y, rho, sigma_rho) in index order; -3 for null arrays (kf_size > 0), a negative
+ * size and whatever the device entry refuses. */
+int rebvio_hip_kf_snapshot_point_cloud(rebvio_hip_kf_snapshot* snap, const rebvio_hip_cloud_filter* filter,
+                                       const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud_point* points_host, int cap, int* count);
+int rebvio_hip_kf_snapshot_point_cloud_async(rebvio_hip_kf_snapshot* snap, const rebvio_hip_cloud_filter* filter,
+                                             const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud** out);
+int rebvio_hip_test_kf_cloud_host(float fm, const float* snap_prs4, const unsigned* snap_matches, int kf_size,
+                                  const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose,
+                                  rebvio_hip_cloud_point* points, int cap, int* count);
 
 /* Test hook: overwrite the device keylines (count must equal the map size). */
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n);

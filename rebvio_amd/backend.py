@@ -157,6 +157,10 @@ SIGNATURES = {
     "rebvio_hip_test_kf_fuse_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
                                                C.c_int, _fp, _fp, C.c_int, _ip, _ip, C.POINTER(KfFuseOpts), _dp, _dp,
                                                C.POINTER(KfFuse), _ip]),
+    "rebvio_hip_kf_snapshot_point_cloud": (C.c_int, [_vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), _vp, C.c_int, _ip]),
+    "rebvio_hip_kf_snapshot_point_cloud_async": (C.c_int, [_vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), C.POINTER(_vp)]),
+    "rebvio_hip_test_kf_cloud_host": (C.c_int, [C.c_float, _fp, C.POINTER(C.c_uint), C.c_int, C.POINTER(CloudFilter), C.POINTER(CloudPose),
+                                                _vp, C.c_int, _ip]),
     "rebvio_hip_test_kf_pose_host": (C.c_int, [C.c_float, _fp, C.POINTER(C.c_uint), C.c_int, _fp, _fp, C.c_int, C.POINTER(KfMatch),
                                                C.c_int, C.POINTER(KfPoseOpts), _dp, _dp, C.POINTER(KfPose)]),
     "rebvio_hip_map_upload": (C.c_int, [_vp, _vp, C.c_int]),
@@ -493,6 +497,23 @@ def kf_fuse_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normals
     return out, prs4, kf_matches, assoc
 
 
+def kf_cloud_host(fm, prs4, kf_matches, filter=None, pose=None, cap=None, return_count=False):
+    """KfSnapshot.point_cloud on the host, from arrays (rebvio_hip_test_kf_cloud_host): prs4 float32 [n, 4] and matches uint32 [n] as
+    KfSnapshot.download returns them. Touches no device. Returns the CLOUD_POINT_DTYPE array (and the count with return_count)."""
+    prs4 = np.ascontiguousarray(prs4, np.float32).reshape(-1, 4)
+    kf_matches = np.ascontiguousarray(kf_matches, np.uint32).reshape(-1)
+    assert len(prs4) == len(kf_matches)
+    if cap is None:
+        cap = len(prs4)
+    out = np.zeros(cap, CLOUD_POINT_DTYPE)
+    n = C.c_int()
+    _chk(lib().rebvio_hip_test_kf_cloud_host(float(fm), prs4.ctypes.data_as(_fp) if len(prs4) else None,
+                                             kf_matches.ctypes.data_as(C.POINTER(C.c_uint)) if len(prs4) else None, len(prs4),
+                                             _cloud_filter(filter), _cloud_pose(pose), out.ctypes.data if cap else None, cap, C.byref(n)))
+    out = out[:min(n.value, cap)]
+    return (out, n.value) if return_count else out
+
+
 class KfSnapshot:
     """A keyframe as it was when marked (rebvio_hip_map_keyframe_snapshot): download() its keylines, release() when done."""
 
@@ -540,6 +561,28 @@ class KfSnapshot:
                                                      assoc.ctypes.data_as(_ip) if want_assoc and len(assoc) else None))
         del kR, kt
         return (out, assoc) if want_assoc else out
+
+    def point_cloud(self, filter=None, pose=None, cap=None, return_count=False):
+        """The snapshot's depth-bearing keylines - as marked, or as fuse_depth has refined them - as a CLOUD_POINT_DTYPE array
+        (rebvio_hip_kf_snapshot_point_cloud; synchronous; filter / pose as Map.point_cloud, pose None = the keyframe's own frame in
+        keyframe depth units). `keyline` indexes download() / normals(); gradient_norm is 0. cap: at most this many records (default:
+        the snapshot's size); return_count: also the number of keylines that passed, which may exceed cap."""
+        n = C.c_int()
+        if cap is None:
+            _chk(lib().rebvio_hip_kf_snapshot_download(self.h, None, None, 0, C.byref(n)))
+            cap = n.value
+        out = np.zeros(cap, CLOUD_POINT_DTYPE)
+        _chk(lib().rebvio_hip_kf_snapshot_point_cloud(self.h, _cloud_filter(filter), _cloud_pose(pose), out.ctypes.data if cap else None,
+                                                      cap, C.byref(n)))
+        out = out[:min(n.value, cap)]
+        return (out, n.value) if return_count else out
+
+    def point_cloud_async(self, filter=None, pose=None) -> "Cloud":
+        """Queues the extraction on the track stream and returns at once (rebvio_hip_kf_snapshot_point_cloud_async; allowed between
+        track_pair_finish_async(k) and track_pair_begin(k+1)). The Cloud is the kind Context.point_cloud_async returns."""
+        h = _vp()
+        _chk(lib().rebvio_hip_kf_snapshot_point_cloud_async(self.h, _cloud_filter(filter), _cloud_pose(pose), C.byref(h)))
+        return Cloud(h)
 
     def release(self):
         if self.h:

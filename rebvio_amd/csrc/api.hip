@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "glue.hpp"
 #include "hostmath.hpp"
+#include "kf_cloud.hpp"
 #include "kf_pose.hpp"
 #include "owned.hpp"
 #include "pixel_format.hpp"
@@ -1743,14 +1744,8 @@ void release_cloud(rebvio_hip_cloud* cl) {
   cl->in_use = false;
 }
 
-// Queues one extraction on the track stream; the caller holds the map's life block. cap < 0: the buffer's capacity.
-int enqueue_cloud(const char* who, rebvio_hip_map* m, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose, int cap,
-                  rebvio_hip_cloud** out) {
-  rebvio_hip_ctx* c = m->ctx;
-  if (m->promised.load(std::memory_order_acquire))
-    return fail_msg((std::string(who) + ": the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
-                     "its cloud is available again once the next track_pair_begin has run").c_str(), -7);
-  HIPCHK(hipSetDevice(c->device));
+// Filter, pose and capacity of one extraction as the kernels take them. cap < 0: the buffer's capacity.
+CloudArgs cloud_args(const rebvio_hip_ctx* c, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose, int cap) {
   rebvio_hip_cloud_filter f;
   if (filter) f = *filter; else rebvio_hip_default_cloud_filter(&f);
   CloudArgs a{};
@@ -1762,7 +1757,12 @@ int enqueue_cloud(const char* who, rebvio_hip_map* m, const rebvio_hip_cloud_fil
   for (int i = 0; i < 3; ++i) a.t[i] = pose ? pose->t[i] : 0.0f;
   a.scale = pose ? pose->scale : 1.0f;
   a.cap = (cap < 0 || cap > c->P.keylines_max) ? c->P.keylines_max : cap;
-  std::lock_guard<std::mutex> lk(c->cloud_mu);
+  return a;
+}
+
+// A cloud's buffer for one extraction, of a map or of a snapshot (the caller holds cloud_mu): the scratch and the cloud stream at
+// the context's first cloud, a free buffer of the pool or a new one, the wait the re-use rule asks for, and the stamp (into a and *out).
+int cloud_take(const char* who, rebvio_hip_ctx* c, CloudArgs& a, rebvio_hip_cloud** out) {
   if (!c->cloud_scratch) {
     HIPCHK(c->own.device(&c->cloud_scratch, kMaxRecBlocks + 1, 0));
     HIPCHK(hipStreamSynchronize(nullptr));  // (hipMemset returns before the fill has run: alloc_map)
@@ -1789,12 +1789,16 @@ int enqueue_cloud(const char* who, rebvio_hip_map* m, const rebvio_hip_cloud_fil
   if (++c->cloud_seq == 0) ++c->cloud_seq;  // non-zero: a fresh buffer's head reads 0
   a.seq = cl->seq = c->cloud_seq;
   cl->cap = a.cap;
-  wait_enqueued(m);
-  HIPCHK(trk_wait_ready_once(c, m));
+  *out = cl;
+  return 0;
+}
+
+// Behind the extraction kernels just queued on the track stream (the caller holds cloud_mu): the copy to the host on the cloud
+// stream, and the two events. The handle counts as out from here on.
+int cloud_queue_copy(rebvio_hip_ctx* c, rebvio_hip_cloud* cl, const CloudArgs& a) {
+  HIPCHK(hipGetLastError());
   void* hdr_host_dev = nullptr;  // the host-visible buffer as the device addresses it
   HIPCHK(hipHostGetDevicePointer(&hdr_host_dev, cl->hdr, 0));
-  launch_point_cloud(c->s_trk, c->K, m->d, a, c->cloud_scratch, reinterpret_cast<int*>(cl->dev_buf), cl->dev);
-  HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(cl->extracted, c->s_trk));
   HIPCHK(hipStreamWaitEvent(c->s_cloud, cl->extracted, 0));
   launch_point_cloud_copy(c->s_cloud, c->K, cl->dev, reinterpret_cast<const int*>(cl->dev_buf), a,
@@ -1803,6 +1807,44 @@ int enqueue_cloud(const char* who, rebvio_hip_map* m, const rebvio_hip_cloud_fil
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(cl->done, c->s_cloud));
   cl->in_use = true;
+  return 0;
+}
+
+// Queues one extraction on the track stream; the caller holds the map's life block. cap < 0: the buffer's capacity.
+int enqueue_cloud(const char* who, rebvio_hip_map* m, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose, int cap,
+                  rebvio_hip_cloud** out) {
+  rebvio_hip_ctx* c = m->ctx;
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg((std::string(who) + ": the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
+                     "its cloud is available again once the next track_pair_begin has run").c_str(), -7);
+  HIPCHK(hipSetDevice(c->device));
+  CloudArgs a = cloud_args(c, filter, pose, cap);
+  std::lock_guard<std::mutex> lk(c->cloud_mu);
+  rebvio_hip_cloud* cl = nullptr;
+  int rc = cloud_take(who, c, a, &cl);
+  if (rc) return rc;
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  launch_point_cloud(c->s_trk, c->K, m->d, a, c->cloud_scratch, reinterpret_cast<int*>(cl->dev_buf), cl->dev);
+  rc = cloud_queue_copy(c, cl, a);
+  if (rc) return rc;
+  *out = cl;
+  return 0;
+}
+
+// The same for a snapshot (the caller holds its life block): the size is read on the device, so nothing is fetched or waited for.
+int enqueue_kf_cloud(const char* who, rebvio_hip_kf_snapshot* sn, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose,
+                     int cap, rebvio_hip_cloud** out) {
+  rebvio_hip_ctx* c = sn->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  CloudArgs a = cloud_args(c, filter, pose, cap);
+  std::lock_guard<std::mutex> lk(c->cloud_mu);
+  rebvio_hip_cloud* cl = nullptr;
+  int rc = cloud_take(who, c, a, &cl);
+  if (rc) return rc;
+  launch_kf_point_cloud(c->s_trk, c->K, sn->prs, sn->matches, sn->n_dev, a, c->cloud_scratch, reinterpret_cast<int*>(cl->dev_buf), cl->dev);
+  rc = cloud_queue_copy(c, cl, a);
+  if (rc) return rc;
   *out = cl;
   return 0;
 }
@@ -2051,6 +2093,57 @@ int rebvio_hip_kf_snapshot_download(rebvio_hip_kf_snapshot* sn, float* prs4, uns
     if (rc) return rc;
   }
   *n = sn->n_host;
+  return 0;
+}
+
+int rebvio_hip_kf_snapshot_point_cloud(rebvio_hip_kf_snapshot* sn, const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose,
+                                       rebvio_hip_cloud_point* points, int cap, int* count) {
+  if (!sn) return fail_msg("kf_snapshot_point_cloud: null snapshot", -3);
+  if (!count) return fail_msg("kf_snapshot_point_cloud: null count", -3);
+  if (cap < 0 || (cap > 0 && !points)) return fail_msg("kf_snapshot_point_cloud: cap records need a points buffer (cap >= 0)", -3);
+  int rc = check_cloud_args("kf_snapshot_point_cloud", filter, pose);
+  if (rc) return rc;
+  *count = 0;
+  const std::shared_ptr<LifeBlock> life = sn->life;
+  std::shared_lock<std::shared_mutex> lk(life->mu);
+  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  rebvio_hip_cloud* cl = nullptr;
+  rc = enqueue_kf_cloud("kf_snapshot_point_cloud", sn, filter, pose, cap, &cl);
+  if (rc) return rc;
+  rc = wait_cloud(cl, count);
+  if (rc == 0) {
+    const int k = *count < cl->cap ? *count : cl->cap;
+    if (k > 0) std::memcpy(points, reinterpret_cast<const char*>(cl->hdr) + sizeof(CloudHdr), (size_t)k * sizeof(rebvio_hip_cloud_point));
+  }
+  release_cloud(cl);
+  return rc;
+}
+
+int rebvio_hip_kf_snapshot_point_cloud_async(rebvio_hip_kf_snapshot* sn, const rebvio_hip_cloud_filter* filter,
+                                             const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud** out) {
+  if (out) *out = nullptr;
+  if (!sn || !out) return fail_msg("kf_snapshot_point_cloud_async: null snapshot or output", -3);
+  const int rc = check_cloud_args("kf_snapshot_point_cloud_async", filter, pose);
+  if (rc) return rc;
+  const std::shared_ptr<LifeBlock> life = sn->life;
+  std::shared_lock<std::shared_mutex> lk(life->mu);
+  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  return enqueue_kf_cloud("kf_snapshot_point_cloud_async", sn, filter, pose, -1, out);
+}
+
+int rebvio_hip_test_kf_cloud_host(float fm, const float* snap_prs4, const unsigned* snap_matches, int kf_size,
+                                  const rebvio_hip_cloud_filter* filter, const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud_point* points,
+                                  int cap, int* count) {
+  if (!count || kf_size < 0 || (kf_size > 0 && (!snap_prs4 || !snap_matches)))
+    return fail_msg("test_kf_cloud_host: null array or count, or a negative size", -3);
+  if (cap < 0 || (cap > 0 && !points)) return fail_msg("test_kf_cloud_host: cap records need a points buffer (cap >= 0)", -3);
+  const int rc = check_cloud_args("test_kf_cloud_host", filter, pose);
+  if (rc) return rc;
+  rebvio_hip_cloud_filter f;
+  if (filter) f = *filter; else rebvio_hip_default_cloud_filter(&f);
+  const float eye[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f}, zero[3] = {0.0f, 0.0f, 0.0f};
+  kfc::extract_host(fm, snap_prs4, snap_matches, kf_size, f, pose ? pose->R : eye, pose ? pose->t : zero, pose ? pose->scale : 1.0f, points,
+                    cap, count);
   return 0;
 }
 

@@ -356,6 +356,10 @@ void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int 
 void launch_kf_fuse_depth(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const int* kf_size_dev, void* snap_prs,
                           unsigned* snap_matches, const void* snap_normals, const rebvio_hip_kf_fuse_opts& o, const double* R, const double* t,
                           int* cnt, int* assoc);
+// k_kf_cloud_count + k_kf_cloud_emit on stream s (rebvio_hip_kf_snapshot_point_cloud*): launch_point_cloud over a snapshot's buffers
+// (ceil(kmax / 256) * 256 slots each; snap_n = its size in device memory). blk_cnt / count_dev / records_dev as there.
+void launch_kf_point_cloud(hipStream_t s, const KParams& p, const void* snap_prs, const unsigned* snap_matches, const int* snap_n,
+                           const CloudArgs& a, int* blk_cnt, int* count_dev, void* records_dev);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 

@@ -10,6 +10,7 @@
 // no dense contraction exists on this path (largest product is 6x6), so MFMA does not apply.
 #include "common.hpp"
 #include "glue_dev.hpp"
+#include "kf_cloud.hpp"
 #include "kf_pose.hpp"
 
 #include <cstdlib>
@@ -3618,6 +3619,67 @@ void launch_kf_fuse_depth(hipStream_t s, const KParams& p, const MapDev& m, int 
   RH_LAUNCH(k_kf_fuse_depth, dim3(nb), dim3(256), 0, s, p, m, kf_size_dev, reinterpret_cast<float4*>(snap_prs), snap_matches,
             reinterpret_cast<const float2*>(snap_normals), o.kf_filter, o.min_cos, o.max_dist, pose, o.pixel_sigma, o.gate_sigma, o.q_abs, cnt,
             assoc);
+}
+
+// ---- point cloud of a snapshot (rebvio_hip_kf_snapshot_point_cloud*) -------------------------------------------------------------
+// The compaction of k_cloud_count / k_cloud_emit over a snapshot's buffers (bodies copied, not shared: the map's kernels stay as
+// they are): one 16-byte prs load and the matches word per lane, bound-free (the buffers cover the launch grid), the size read on
+// the device. kf_cloud.hpp's kfc::record is the per-record statement; a record's gradient_norm is +0.0f (a snapshot keeps none).
+__global__ __launch_bounds__(256) void k_kf_cloud_count(const float4* __restrict__ prs, const unsigned* __restrict__ matches,
+                                                        const int* __restrict__ n_dev, rebvio_hip_cloud_filter flt,
+                                                        int* __restrict__ blk_cnt) {
+  __shared__ int sh[4];
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const float4 k = prs[idx];
+  const unsigned mt = matches[idx];
+  const int n = *n_dev;
+  const int2 w = wave_place(idx < n && kfp::filter_pass(flt, k.z, k.w, mt));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w.y;
+  __syncthreads();
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void k_kf_cloud_emit(float fm, const float4* __restrict__ prs, const unsigned* __restrict__ matches,
+                                                       const int* __restrict__ n_dev, CloudArgs a, const int* __restrict__ blk_cnt,
+                                                       int* __restrict__ count_out, float4* __restrict__ out) {
+  __shared__ int sh_w[4], sh_lo[4], sh_all[4];
+  const int tid = threadIdx.x, idx = blockIdx.x * 256 + tid, wv = tid >> 6;
+  const float4 k = prs[idx];
+  const unsigned mt = matches[idx];
+  const int n = *n_dev;
+  // every workgroup's count, one per thread (gridDim.x <= kMaxRecBlocks = 256)
+  const int c = tid < (int)gridDim.x ? blk_cnt[tid] : 0;
+  const int lo = wave_sum_i(tid < (int)blockIdx.x ? c : 0), all = wave_sum_i(c);
+  const rebvio_hip_cloud_filter flt{a.min_matches, a.max_rel_sigma, a.rho_min, a.rho_max};
+  float q[3] = {0.0f, 0.0f, 0.0f};
+  const bool pass = kfc::record(fm, flt, a.R, a.t, a.scale, k.x, k.y, k.z, k.w, mt, q) && idx < n;
+  const int2 w = wave_place(pass);
+  if ((tid & 63) == 0) {
+    sh_w[wv] = w.y;
+    sh_lo[wv] = lo;
+    sh_all[wv] = all;
+  }
+  __syncthreads();
+  int rank = (sh_lo[0] + sh_lo[1]) + (sh_lo[2] + sh_lo[3]) + w.x;
+  for (int i = 0; i < wv; ++i) rank += sh_w[i];
+  if (blockIdx.x == 0 && tid == 0) *count_out = (sh_all[0] + sh_all[1]) + (sh_all[2] + sh_all[3]);
+  if (pass && rank < a.cap) {
+    // two 16-byte stores per record, as k_cloud_emit
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) volatile v4f* GRec;
+    GRec rec = (GRec)(out + 2 * (size_t)rank);
+    rec[0] = v4f{q[0], q[1], q[2], k.z};
+    rec[1] = v4f{k.w, 0.0f, __int_as_float(idx), __uint_as_float(mt)};
+  }
+}
+
+void launch_kf_point_cloud(hipStream_t s, const KParams& p, const void* snap_prs, const unsigned* snap_matches, const int* snap_n,
+                           const CloudArgs& a, int* blk_cnt, int* count_dev, void* records_dev) {
+  const dim3 grid(div_up(p.kmax, 256));
+  const rebvio_hip_cloud_filter flt{a.min_matches, a.max_rel_sigma, a.rho_min, a.rho_max};
+  RH_LAUNCH(k_kf_cloud_count, grid, dim3(256), 0, s, reinterpret_cast<const float4*>(snap_prs), snap_matches, snap_n, flt, blk_cnt);
+  RH_LAUNCH(k_kf_cloud_emit, grid, dim3(256), 0, s, p.fm, reinterpret_cast<const float4*>(snap_prs), snap_matches, snap_n, a,
+            (const int*)blk_cnt, count_dev, reinterpret_cast<float4*>(records_dev));
 }
 
 }  // namespace rh

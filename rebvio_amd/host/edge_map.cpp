@@ -192,6 +192,20 @@ void KeyframeSnapshot::addNormals(const rebvio::EdgeMap& map) {
   check("rebvio_hip_kf_snapshot_add_normals", rebvio_hip_kf_snapshot_add_normals(handle_, map.handle()));
 }
 
+std::vector<rebvio::types::CloudPoint> KeyframeSnapshot::pointCloud(const rebvio::types::CloudFilter& filter,
+                                                                    const rebvio::types::CloudPose& pose) const {
+  const rebvio_hip_cloud_filter* f = reinterpret_cast<const rebvio_hip_cloud_filter*>(&filter);
+  const rebvio_hip_cloud_pose* p = reinterpret_cast<const rebvio_hip_cloud_pose*>(&pose);
+  int count = 0;  // the count first: a snapshot's size lives on the device
+  check("rebvio_hip_kf_snapshot_point_cloud", rebvio_hip_kf_snapshot_point_cloud(handle_, f, p, nullptr, 0, &count));
+  std::vector<rebvio::types::CloudPoint> points((size_t)count);
+  if (count > 0)
+    check("rebvio_hip_kf_snapshot_point_cloud",
+          rebvio_hip_kf_snapshot_point_cloud(handle_, f, p, reinterpret_cast<rebvio_hip_cloud_point*>(points.data()), count, &count));
+  points.resize((size_t)count);
+  return points;
+}
+
 rebvio::types::KfFuse KeyframeSnapshot::fuseDepth(const rebvio::EdgeMap& map, const rebvio::types::KfPose& pose,
                                                   const rebvio::types::KfFuseOpts& opts, std::vector<int>* assoc) {
   static_assert(sizeof(types::KfFuseOpts) == sizeof(rebvio_hip_kf_fuse_opts) &&

@@ -119,6 +119,10 @@ void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::
   point_cloud_callbacks_.push_back({cb, filter});
 }
 
+void Rebvio::registerKeyframeCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
+  keyframe_cloud_callbacks_.push_back({cb, filter});
+}
+
 void Rebvio::waitIdle() {
   while (run_) {
     const unsigned imgs = num_images_;
@@ -336,6 +340,11 @@ void Rebvio::stateEstimationProcess() {
     // the pair's counters are)
     types::CloudPose cloud_pose;
     std::vector<rebvio_hip_cloud*> clouds;
+    // keyframe-cloud callbacks: the cloud of the keyframe this pair's new map replaced, one queued cloud per callback, with the
+    // stamp and the pose remembered where that keyframe was marked
+    std::vector<rebvio_hip_cloud*> kf_clouds;
+    types::CloudPose kf_cloud_pose;
+    uint64_t kf_cloud_ts = 0;
     int kf_matches = 0;    // of the pair, for the keyframe callbacks
     bool have_kf_pose = false;  // keyframe-pose callbacks: the new map's pose relative to the keyframe
     types::KfPose kf_pose;
@@ -347,6 +356,9 @@ void Rebvio::stateEstimationProcess() {
   types::KfPose kf_pose_last;
   bool kf_pose_warm = false;
   bool kf_marked_here = false;  // this pair's new map is the one the snapshot was taken from: it is not fused into itself
+  // keyframe-cloud callbacks: stamp and odometry pose (R_global, Pos, K) of the record on whose map the snapshot was taken
+  uint64_t kf_ts = 0;
+  types::CloudPose kf_odometry_pose;
   // Two steps: the counters (and with them the stop conditions of rebvio.cpp:236-252) are fetched as soon as the next pair's
   // first half is back; the callbacks run after that pair's second half has been launched, off the path between its halves.
   auto publish_pending = [&]() {
@@ -368,7 +380,14 @@ void Rebvio::stateEstimationProcess() {
         for (rebvio_hip_cloud* cl : v) rebvio_hip_cloud_release(cl);
         v.clear();
       }
-    } clouds_back{pending.clouds};
+    } clouds_back{pending.clouds}, kf_clouds_back{pending.kf_clouds};
+    for (size_t i = 0; i < pending.kf_clouds.size(); ++i) {  // the keyframe this record's map replaced
+      const rebvio_hip_cloud_point* pts = nullptr;
+      int n = 0;
+      backend::check("rebvio_hip_cloud_wait", rebvio_hip_cloud_wait(pending.kf_clouds[i], &pts, &n, nullptr));  // (has run: fetch_pending)
+      const types::PointCloud pc{pending.kf_cloud_ts, pending.kf_cloud_pose, reinterpret_cast<const types::CloudPoint*>(pts), (size_t)n};
+      keyframe_cloud_callbacks_[i].cb(pc);
+    }
     for (size_t i = 0; i < pending.clouds.size(); ++i) {
       const rebvio_hip_cloud_point* pts = nullptr;
       int n = 0;
@@ -387,6 +406,10 @@ void Rebvio::stateEstimationProcess() {
     int klm_num = 0, kf_matches = 0, reg_num = 0, status = 0;
     backend::check("rebvio_hip_track_pair_result", rebvio_hip_track_pair_result(ctx, &klm_num, &kf_matches, &reg_num, &status));
     for (rebvio_hip_cloud* cl : pending.clouds) {  // queued right behind that second half
+      int n = 0;
+      backend::check("rebvio_hip_cloud_wait", rebvio_hip_cloud_wait(cl, nullptr, &n, nullptr));
+    }
+    for (rebvio_hip_cloud* cl : pending.kf_clouds) {  // ... and so was a retired keyframe's
       int n = 0;
       backend::check("rebvio_hip_cloud_wait", rebvio_hip_cloud_wait(cl, nullptr, &n, nullptr));
     }
@@ -550,7 +573,8 @@ void Rebvio::stateEstimationProcess() {
     store3(R_second, r2);
     timers.lap(1);
     // gravity-aligned pose integration (rebvio.cpp:263-271): needs nothing from the device. With a point-cloud callback it runs
-    // ahead of the hand-over, because the pair's cloud is queued with this pose right behind the second half.
+    // ahead of the hand-over, because the pair's cloud is queued with this pose right behind the second half; with a keyframe-cloud
+    // callback too, which remembers this pose where a keyframe is marked.
     auto integrate_pose = [&]() {
       if (num_frames_ > 4u + (unsigned)config_.imu_state.init_bias_frame_num) {
         imu_state_.u_est = Rgva.T() * imu_state_.u_est;
@@ -565,14 +589,16 @@ void Rebvio::stateEstimationProcess() {
     };
     const bool want_cloud = !point_cloud_callbacks_.empty();
     const bool want_kf_pose = !keyframe_pose_callbacks_.empty();
-    std::vector<rebvio_hip_cloud*> clouds;
-    types::CloudPose cloud_pose;
-    if (want_cloud) integrate_pose();
+    const bool want_kf_cloud = !keyframe_cloud_callbacks_.empty();
+    std::vector<rebvio_hip_cloud*> clouds, kf_clouds;
+    types::CloudPose cloud_pose, kf_cloud_pose;
+    uint64_t kf_cloud_ts = 0;
+    if (want_cloud || want_kf_cloud) integrate_pose();
     // If the following frame is already queued, its gyro pre-integration (complete before the map was queued) is the next
     // pair's prior: that pair's first rotateKeylines then rides in this pair's last kernel. Only once the gyro bias is
     // initialised (until then the bias still changes between pairs, rebvio.cpp:146-160). Not with a point-cloud callback: the
     // cloud shows the new map in THIS pair's frame, so the next pair's _begin launches its rotation itself.
-    // Nor with a keyframe-pose callback: snapshot and pose take the new map in this pair's frame as well.
+    // Nor with a keyframe-pose or keyframe-cloud callback: snapshot and pose take the new map in this pair's frame as well.
     float Rnext[9];
     bool have_next = false;
     rebvio::EdgeMap::SharedPtr next_map;
@@ -580,7 +606,7 @@ void Rebvio::stateEstimationProcess() {
       std::lock_guard<std::mutex> guard(edge_map_buffer_mutex_);
       if (edge_map_buffer_.size() >= 2) {
         next_map = edge_map_buffer_[1];
-        if (imu_state_.initialized && !want_cloud && !want_kf_pose) {
+        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud) {
           store3(next_map->imu().R(), Rnext);
           have_next = true;
         }
@@ -608,8 +634,23 @@ void Rebvio::stateEstimationProcess() {
     kf_marked_here = false;
     if (keyframe_requested_.exchange(false)) {
       new_edge_map->markKeyframe();
-      if (want_kf_pose) {  // the keyframe as it is now, right behind its mark; the previous one goes
+      if (want_kf_pose || want_kf_cloud) {  // the keyframe as it is now, right behind its mark; the previous one goes
+        if (want_kf_cloud && kf_snapshot) {  // ... as a cloud, queued before its snapshot is released (which is safe right behind)
+          kf_cloud_pose = kf_odometry_pose;
+          kf_cloud_ts = kf_ts;
+          for (const PointCloudCallback& pcc : keyframe_cloud_callbacks_) {
+            rebvio_hip_cloud* cl = nullptr;
+            backend::check("rebvio_hip_kf_snapshot_point_cloud_async",
+                           rebvio_hip_kf_snapshot_point_cloud_async(kf_snapshot.handle(), reinterpret_cast<const rebvio_hip_cloud_filter*>(&pcc.filter),
+                                                                    reinterpret_cast<const rebvio_hip_cloud_pose*>(&kf_cloud_pose), &cl));
+            kf_clouds.push_back(cl);
+          }
+        }
         kf_snapshot = new_edge_map->keyframeSnapshot();
+        kf_ts = new_edge_map->ts_us();
+        store3(R_global, kf_odometry_pose.R);
+        for (int i = 0; i < 3; ++i) kf_odometry_pose.t[i] = Pos[i];
+        kf_odometry_pose.scale = K;
         if (keyframe_align_) kf_snapshot.addNormals(*new_edge_map);  // (setKeyframeAlign: the alignment's gradient test)
         kf_pose_warm = false;
         kf_marked_here = true;
@@ -635,7 +676,7 @@ void Rebvio::stateEstimationProcess() {
     }
     timers.lap(2);
 
-    if (!want_cloud) integrate_pose();
+    if (!want_cloud && !want_kf_cloud) integrate_pose();
     types::Odometry odometry;
     odometry.ts_us = new_edge_map->ts_us();
     odometry.orientation = TooN::SO3<types::Float>(R_global).ln();
@@ -649,6 +690,9 @@ void Rebvio::stateEstimationProcess() {
     pending.new_map = new_edge_map;
     pending.cloud_pose = cloud_pose;
     pending.clouds = clouds;
+    pending.kf_clouds = kf_clouds;
+    pending.kf_cloud_pose = kf_cloud_pose;
+    pending.kf_cloud_ts = kf_cloud_ts;
     pending.have_kf_pose = have_kf_pose;
     pending.kf_pose = kf_pose_last;
     pending.have_kf_fuse = have_kf_fuse;

@@ -19,6 +19,9 @@
 // --kf-fuse FILE [--kf-every N]: implies the alignment (with or without --kf-align FILE; not with --kf-pose) and fuses every aligned
 // map into the keyframe snapshot (Rebvio::setKeyframeDepthFusion), one line per fusion, i.e. per pose record of status 0 other than
 // the keyframe's own: ts_us candidates associated fused gated flat clamped.
+// --kf-cloud PREFIX [--kf-every N]: every retired keyframe's point cloud (Rebvio::registerKeyframeCloudCallback, default filter) as
+// PREFIX<ts_us>.ply, ts_us the keyframe's own stamp, through the same PLY writer; keyframes are requested as for --kf-pose. Alone it
+// writes the keyframes as marked; with --kf-fuse (and --kf-align) the refined ones. The keyframe current at the end is not written.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -31,7 +34,7 @@
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
-  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path;
+  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix;
   bool kf_align = false;
   int kf_every = 10;
   int W = 0, H = 0;
@@ -42,7 +45,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] --out file\n", argv[0]);
+                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -79,6 +82,7 @@ int main(int argc, char** argv) {
       if (!kf_fuse_path.empty()) return usage();
       kf_fuse_path = next();
     }
+    else if (a == "--kf-cloud") kf_cloud_prefix = next();
     else if (a == "--kf-every") kf_every = std::atoi(next());
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
@@ -148,7 +152,7 @@ int main(int argc, char** argv) {
       t_last = std::chrono::steady_clock::now();
       if (n_odo == 0) t_first = t_last;
       ++n_odo;
-      if (want_kf && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
+      if ((want_kf || !kf_cloud_prefix.empty()) && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
     });
     std::FILE *kf_pose_file = nullptr, *kf_fuse_file = nullptr;
     size_t n_poses = 0, n_fusions = 0;
@@ -180,6 +184,15 @@ int main(int argc, char** argv) {
       rebvio.setKeyframeAlign(kf_align);
       rebvio.requestKeyframe();
     }
+    size_t n_kf_clouds = 0, n_kf_points = 0;
+    if (!kf_cloud_prefix.empty()) {
+      rebvio.registerKeyframeCloudCallback([&](const rebvio::types::PointCloud& pc) {
+        rebvio::io::writePointCloudPly(kf_cloud_prefix + std::to_string(pc.ts_us) + ".ply", pc.points, pc.size, pc.ts_us);
+        ++n_kf_clouds;
+        n_kf_points += pc.size;
+      });
+      if (!want_kf) rebvio.requestKeyframe();
+    }
     size_t n_clouds = 0, n_points = 0;
     if (!cloud_prefix.empty() || cloud_dry)
       rebvio.registerPointCloudCallback([&](const rebvio::types::PointCloud& pc) {
@@ -193,6 +206,7 @@ int main(int argc, char** argv) {
     rebvio.waitIdle();
     std::fprintf(stderr, "frames=%zu odometry=%zu running=%d\n", n, n_odo, (int)rebvio.running());
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
+    if (!kf_cloud_prefix.empty()) std::fprintf(stderr, "kf_clouds=%zu kf_points=%zu\n", n_kf_clouds, n_kf_points);
     if (kf_pose_file) std::fclose(kf_pose_file);
     if (want_kf) std::fprintf(stderr, "kf_poses=%zu\n", n_poses);
     if (kf_fuse_file) {
