@@ -63,6 +63,14 @@ class KeyframeSnapshot {
   rebvio_hip_kf_snapshot* handle_ = nullptr;
 };
 
+// the best of keyframeAlignMany's results (rebvio_hip_kf_align_best): status 0 and inliers >= min_inliers; the most inliers, then the
+// smaller cost, then the lower index; -1 when none qualifies
+int keyframeAlignBest(const std::vector<rebvio::types::KfHypResult>& results, int min_inliers = 0);
+// 13 starts around the guess (R, t) for `snapshot` (rebvio_hip_kf_hypotheses_around): the guess, +- rot_step about x, y, z,
+// +- trans_step along x, y, z
+std::vector<rebvio::types::KfHypothesis> keyframeHypothesesAround(const rebvio::KeyframeSnapshot& snapshot, const double R[9], const double t[3],
+                                                                  double rot_step, double trans_step);
+
 struct EdgeMapConfig {
   types::Float pixel_uncertainty_match{2.0};
   types::Float match_threshold_norm{1.0};
@@ -123,6 +131,13 @@ class EdgeMap {
   // was associated with at the returned pose, or -1.
   rebvio::types::KfPose keyframeAlign(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfAlignOpts& opts = rebvio::types::KfAlignOpts(),
                                       const rebvio::types::KfPose* guess = nullptr, std::vector<int>* assoc = nullptr);
+
+  // keyframeAlignMany(hypotheses): every (snapshot, guess) of the list aligned to THIS map in one set of launches
+  // (rebvio_hip_map_keyframe_align_many; synchronous, from the tracking thread; 1..64 hypotheses, the same snapshot any number of
+  // times). result[h].pose is keyframeAlign's for the same snapshot, guess and options, bit for bit; there are no associations: run
+  // keyframeAlign on the winner (keyframeAlignBest) for them.
+  std::vector<rebvio::types::KfHypResult> keyframeAlignMany(const std::vector<rebvio::types::KfHypothesis>& hypotheses,
+                                                            const rebvio::types::KfAlignOpts& opts = rebvio::types::KfAlignOpts());
 
   // --- backend plumbing (not part of the reference surface) ---
   // `keepalive` owns the backend context the handle belongs to (backend::Session): a map kept by an edge-image consumer

@@ -82,6 +82,19 @@ class Rebvio {
   // without this; the odometry does not change by a digit either way. Callable from any thread.
   void setKeyframeDepthFusion(bool on) { keyframe_depth_fusion_ = on; }
   void registerKeyframeFuseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfFuse&)> cb);
+  // addition: a window of the last n (0..15, default 0: none; values outside are clamped) retired keyframes. It is active only while
+  // setKeyframeAlign is on and a keyframe-pose callback is registered. A keyframe that requestKeyframe retires - after its cloud has been
+  // queued, so the keyframe-cloud callbacks see what they saw - then keeps its snapshot (and normals) and enters the window with its
+  // stamp and its last status-0 pose, the oldest member leaving when there are more than n. Behind every pair the current keyframe AND
+  // the members are aligned to the new map in ONE EdgeMap::keyframeAlignMany call (rebvio_hip.h defines it: the launches do not grow
+  // with the members), each warm-started from its own last status-0 pose; a member whose result is not status 0 is reported once and
+  // leaves. The pose handed to the keyframe-pose callbacks, and everything behind it (fusion, clouds), is the current keyframe's result:
+  // bit for bit the pose of a run without a window. The keyframe-window callbacks get, once per such record and right after the
+  // keyframe-fuse callbacks on the state-estimation thread, the record's stamp and one entry per aligned keyframe: the current one
+  // first, then the members, newest first. With the window at 0 the thread runs exactly the calls it runs without this; the odometry
+  // does not change by a digit either way. setKeyframeWindow is callable from any thread; register before the first frame is handed in.
+  void setKeyframeWindow(int n) { keyframe_window_ = n < 0 ? 0 : (n > 15 ? 15 : n); }
+  void registerKeyframeWindowCallback(std::function<void(uint64_t ts_us, const std::vector<rebvio::types::KfWindowPose>&)> cb);
   // addition: every keyframe's depth-bearing keylines as one point cloud, handed out as the keyframe is retired
   // (KeyframeSnapshot::pointCloud; rebvio_hip.h defines it). While such a callback is registered requestKeyframe snapshots the
   // keyframe behind its mark as a keyframe-pose callback makes it do, and remembers R_global, Pos, K of the odometry record of the map
@@ -141,6 +154,8 @@ class Rebvio {
   std::atomic<bool> keyframe_align_{false};
   std::vector<std::function<void(uint64_t, const rebvio::types::KfFuse&)>> keyframe_fuse_callbacks_;
   std::atomic<bool> keyframe_depth_fusion_{false};
+  std::vector<std::function<void(uint64_t, const std::vector<rebvio::types::KfWindowPose>&)>> keyframe_window_callbacks_;
+  std::atomic<int> keyframe_window_{0};
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };
 

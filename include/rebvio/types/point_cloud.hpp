@@ -7,6 +7,7 @@
 #include <cstdint>
 
 namespace rebvio {
+class KeyframeSnapshot;  // edge_map.hpp
 namespace types {
 
 struct CloudPoint {
@@ -74,6 +75,31 @@ struct KfAlignOpts {
   int min_used{12};
 };
 static_assert(sizeof(KfAlignOpts) == 48, "KfAlignOpts must stay layout-compatible with rebvio_hip_kf_align_opts");
+
+// One hypothesis and one result of EdgeMap::keyframeAlignMany, laid out like the C-ABI's rebvio_hip_kf_hypothesis /
+// rebvio_hip_kf_hyp_result (rebvio_hip.h defines every term): a snapshot (which the caller keeps alive) and the guess to start from;
+// the pose EdgeMap::keyframeAlign returns for the same snapshot, guess and options, bit for bit, and the number of used terms with
+// |e| <= huber_px at that pose.
+struct KfHypothesis {
+  const rebvio::KeyframeSnapshot* snapshot{nullptr};
+  double R0[9]{1, 0, 0, 0, 1, 0, 0, 0, 1}, t0[3]{0, 0, 0};
+};
+static_assert(sizeof(KfHypothesis) == 104 && offsetof(KfHypothesis, R0) == 8 && offsetof(KfHypothesis, t0) == 80,
+              "KfHypothesis must stay laid out like rebvio_hip_kf_hypothesis");
+struct KfHypResult {
+  KfPose pose;
+  int inliers{0};
+  int reserved{0};
+};
+static_assert(sizeof(KfHypResult) == sizeof(KfPose) + 8 && offsetof(KfHypResult, inliers) == sizeof(KfPose),
+              "KfHypResult must stay layout-compatible with rebvio_hip_kf_hyp_result");
+// One entry of a keyframe-window callback of rebvio::Rebvio: a keyframe (by the stamp of the map it was marked on), its pose relative
+// to the record's map and the inliers of that alignment.
+struct KfWindowPose {
+  uint64_t kf_ts_us{0};
+  KfPose pose;
+  int inliers{0};
+};
 
 // Options of KeyframeSnapshot::fuseDepth, layout-compatible with the C-ABI's rebvio_hip_kf_fuse_opts (rebvio_hip.h defines every term).
 // The defaults are rebvio_hip_default_kf_fuse_opts's; pixel_sigma <= 0 stands for the context's pixel_uncertainty and max_dist -1 for

@@ -34,7 +34,9 @@ extern "C" {
  *    rebvio_hip_map_keyframe_align, their struct rebvio_hip_kf_align_opts and the test hook rebvio_hip_test_kf_align_host; the
  *    depth fusion rebvio_hip_default_kf_fuse_opts, rebvio_hip_kf_snapshot_fuse_depth, their structs rebvio_hip_kf_fuse_opts /
  *    rebvio_hip_kf_fuse and the test hook rebvio_hip_test_kf_fuse_host; the test hook rebvio_hip_test_handover_counters;
- *    the snapshot point cloud rebvio_hip_kf_snapshot_point_cloud(_async) and the test hook rebvio_hip_test_kf_cloud_host. */
+ *    the snapshot point cloud rebvio_hip_kf_snapshot_point_cloud(_async) and the test hook rebvio_hip_test_kf_cloud_host; the
+ *    batched alignment rebvio_hip_map_keyframe_align_many, its structs rebvio_hip_kf_hypothesis / rebvio_hip_kf_hyp_result, the host
+ *    helpers rebvio_hip_kf_align_best / rebvio_hip_kf_hypotheses_around and the test hook rebvio_hip_test_kf_align_many_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -454,6 +456,56 @@ int rebvio_hip_test_kf_align_host(float fm, float cx, float cy, int rows, int co
                                   const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
                                   const rebvio_hip_kf_align_opts* opts, const double R0[9], const double t0[3], rebvio_hip_kf_pose* out,
                                   int* assoc /*NULL or kf_size ints*/);
+
+/* Many hypotheses against one map in one set of launches. A hypothesis is a snapshot and a guess (R0, t0); for every h < n,
+ * out[h].pose is BIT FOR BIT what rebvio_hip_map_keyframe_align(map, hyp[h].snap, opts, hyp[h].R0, hyp[h].t0, &p, NULL) returns for
+ * the same arguments - every field, status 2 and 3 included: the per-keyline statement, the summation tree and the step are that
+ * entry's, and a hypothesis's sums never meet another's. One options block (NULL = the defaults) serves all hypotheses. The same
+ * snapshot may appear any number of times (several starts around one guess), snapshots with and without normals may be mixed, and
+ * a snapshot of size 0 behaves as it does there (status 3, pose = guess, zero sums, inliers 0 - for min_used 0 too).
+ * inliers = the number of used terms with |e| <= huber_px (the first branch of the Huber test) at the evaluation whose H, g, cost
+ * and used the result carries; an integer count. There is NO assoc output: a caller that wants the winner's associations runs
+ * rebvio_hip_map_keyframe_align on it, from the guess (the same pose, bit for bit) or from the returned pose with max_iter 0.
+ * Launches: max_iter + 1 evaluations of two kernels each, 2 * max_iter + 2 on the track stream WHATEVER n is - k_kf_align_sums_many
+ * over a grid of (the largest ceil(size / 256) of the list, n) workgroups of 256, where a workgroup behind its own hypothesis's last
+ * keyline leaves at once, and k_kf_pose_step_many, one workgroup of 64 per hypothesis. In front of them ONE upload (the table of n
+ * descriptors and the n start states), behind them ONE copy of the n results; no host wait in between, no early exit. A list whose
+ * snapshots are all of size 0 launches nothing. Synchronous and track-side under the calling rules of rebvio_hip_map_keyframe_align;
+ * the map counts as used by the tracker afterwards. The context's scratch for this entry (one allocation, one more live resource:
+ * REBVIO_HIP_KF_HYP_MAX x (descriptor + result block + 256 partials of 28 doubles + 256 used counts + 256 inlier counts)) is made at the
+ * first call that reaches the device and kept.
+ * -3, before the device is touched: null map, hyp or out; n outside 1..REBVIO_HIP_KF_HYP_MAX; a null snapshot; a snapshot of another
+ * context; a non-finite guess; options rebvio_hip_map_keyframe_align refuses. -10 and -7: exactly as that entry.
+ * rebvio_hip_kf_align_best (host only, a pure function): the index of the best result among those with pose.status == 0 and
+ * inliers >= min_inliers - the most inliers, then the smaller pose.cost, then the lower index; -1 when none qualifies; -3: null
+ * array or n < 1.
+ * rebvio_hip_kf_hypotheses_around (host only, touches no device): 13 starts around (R, t) for `snap` (stored as given, may be NULL).
+ * out[0] = (R, t) exactly. out[1 + 2a + s], a = 0, 1, 2, s = 0, 1: R <- E R with w = (s ? -rot_step : +rot_step) e_a and the
+ * E = (I + A K) + B (K K) of the Gauss-Newton step above (its statements, in fp64), t unchanged. out[7 + 2a + s]: t[a] + trans_step
+ * (s = 0) or t[a] - trans_step (s = 1), R unchanged. -3: null R, t or out, a non-finite R, t or step, a negative step.
+ * rebvio_hip_test_kf_align_many_host (test hook, touches no device): rebvio_hip_test_kf_align_host's statements for n guesses
+ * R0s[9 n], t0s[3 n] against ONE snapshot's arrays; out[h].pose is that hook's result byte for byte, out[h].inliers the count above
+ * from the same term values. -3: what that hook refuses, a null R0s, t0s or out, n outside 1..REBVIO_HIP_KF_HYP_MAX. */
+#define REBVIO_HIP_KF_HYP_MAX 64
+typedef struct rebvio_hip_kf_hypothesis { /* 104 bytes */
+  rebvio_hip_kf_snapshot* snap;
+  double R0[9], t0[3];                   /* the guess: X_cur = R0 X_kf + t0 */
+} rebvio_hip_kf_hypothesis;
+typedef struct rebvio_hip_kf_hyp_result { /* sizeof(rebvio_hip_kf_pose) + 8 */
+  rebvio_hip_kf_pose pose;
+  int inliers;                           /* used terms with |e| <= huber_px at the returned pose */
+  int reserved;                          /* 0 */
+} rebvio_hip_kf_hyp_result;
+int rebvio_hip_map_keyframe_align_many(rebvio_hip_map* map, const rebvio_hip_kf_hypothesis* hyp, int n,
+                                       const rebvio_hip_kf_align_opts* opts, rebvio_hip_kf_hyp_result* out /* n */);
+int rebvio_hip_kf_align_best(const rebvio_hip_kf_hyp_result* res, int n, int min_inliers);
+int rebvio_hip_kf_hypotheses_around(rebvio_hip_kf_snapshot* snap, const double R[9], const double t[3], double rot_step,
+                                    double trans_step, rebvio_hip_kf_hypothesis out[13]);
+int rebvio_hip_test_kf_align_many_host(float fm, float cx, float cy, int rows, int cols, int search_range, const float* snap_prs4,
+                                       const unsigned* snap_matches, const float* snap_normals /*NULL: none*/, int kf_size,
+                                       const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
+                                       const rebvio_hip_kf_align_opts* opts, const double* R0s /*9 n*/, const double* t0s /*3 n*/, int n,
+                                       rebvio_hip_kf_hyp_result* out /* n */);
 
 /* Depth fusion into a keyframe snapshot: every map aligned to a snapshot is a new view of the keyframe's edges from a known pose,
  * and rebvio_hip_kf_snapshot_fuse_depth folds that view into the snapshot's rho / sigma_rho with one scalar Kalman update per

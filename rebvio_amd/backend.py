@@ -105,6 +105,19 @@ class KfPose(C.Structure):
                 ("candidates", C.c_int), ("used", C.c_int), ("iterations", C.c_int), ("status", C.c_int)]
 
 
+KF_HYP_MAX = 64  # REBVIO_HIP_KF_HYP_MAX
+
+
+class KfHypothesis(C.Structure):
+    """rebvio_hip_kf_hypothesis: a snapshot's handle and a guess (Map.keyframe_align_many; kf_hypothesis builds one)"""
+    _fields_ = [("snap", C.c_void_p), ("R0", C.c_double * 9), ("t0", C.c_double * 3)]
+
+
+class KfHypResult(C.Structure):
+    """rebvio_hip_kf_hyp_result: the pose of one hypothesis and its count of used terms with |e| <= huber_px"""
+    _fields_ = [("pose", KfPose), ("inliers", C.c_int), ("reserved", C.c_int)]
+
+
 # every symbol include/rebvio_hip.h declares: (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
@@ -152,6 +165,13 @@ SIGNATURES = {
     "rebvio_hip_test_kf_align_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
                                                 C.c_int, _fp, _fp, C.c_int, _ip, _ip, C.POINTER(KfAlignOpts), _dp, _dp,
                                                 C.POINTER(KfPose), _ip]),
+    "rebvio_hip_map_keyframe_align_many": (C.c_int, [_vp, C.POINTER(KfHypothesis), C.c_int, C.POINTER(KfAlignOpts),
+                                                     C.POINTER(KfHypResult)]),
+    "rebvio_hip_kf_align_best": (C.c_int, [C.POINTER(KfHypResult), C.c_int, C.c_int]),
+    "rebvio_hip_kf_hypotheses_around": (C.c_int, [_vp, _dp, _dp, C.c_double, C.c_double, C.POINTER(KfHypothesis)]),
+    "rebvio_hip_test_kf_align_many_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint),
+                                                     _fp, C.c_int, _fp, _fp, C.c_int, _ip, _ip, C.POINTER(KfAlignOpts), _dp, _dp, C.c_int,
+                                                     C.POINTER(KfHypResult)]),
     "rebvio_hip_default_kf_fuse_opts": (None, [_vp, C.POINTER(KfFuseOpts)]),
     "rebvio_hip_kf_snapshot_fuse_depth": (C.c_int, [_vp, _vp, C.POINTER(KfFuseOpts), _dp, _dp, C.POINTER(KfFuse), _ip]),
     "rebvio_hip_test_kf_fuse_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
@@ -455,6 +475,72 @@ def kf_align_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normal
     return out, assoc
 
 
+def kf_hypothesis(snap, R0=None, t0=None) -> KfHypothesis:
+    """One hypothesis for Map.keyframe_align_many: a KfSnapshot (or None, for the host helpers) and a guess (None: identity / zero)"""
+    h = KfHypothesis()
+    h.snap = snap.h if snap is not None else None
+    h.R0[:] = (np.eye(3) if R0 is None else np.asarray(R0, np.float64)).reshape(9)
+    h.t0[:] = np.zeros(3) if t0 is None else np.asarray(t0, np.float64).reshape(3)
+    return h
+
+
+def _hyp_array(items, ctype):
+    arr = (ctype * len(items))()
+    for k, x in enumerate(items):
+        C.memmove(C.byref(arr, k * C.sizeof(ctype)), C.byref(x), C.sizeof(ctype))
+    return arr
+
+
+def kf_align_best(results, min_inliers=0) -> int:
+    """Index of the best result (rebvio_hip_kf_align_best): status 0 and inliers >= min_inliers; the most inliers, then the smaller
+    cost, then the lower index. -1: none qualifies."""
+    results = list(results)
+    arr = _hyp_array(results, KfHypResult)
+    rc = lib().rebvio_hip_kf_align_best(arr if results else None, len(results), int(min_inliers))
+    if rc < -1:
+        _chk(rc)
+    return rc
+
+
+def kf_hypotheses_around(snap, R, t, rot_step, trans_step):
+    """13 starts around the guess (R, t) for `snap` (rebvio_hip_kf_hypotheses_around): the guess itself, +- rot_step about x, y and z,
+    +- trans_step along x, y and z. Returns a list of KfHypothesis; touches no device."""
+    (kR, pR), (kt, pt) = _guess(R, 9), _guess(t, 3)
+    out = (KfHypothesis * 13)()
+    _chk(lib().rebvio_hip_kf_hypotheses_around(snap.h if snap is not None else None, pR, pt, float(rot_step), float(trans_step), out))
+    del kR, kt
+    return [KfHypothesis.from_buffer_copy(out[k]) for k in range(13)]
+
+
+def kf_align_many_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normals, cur_pos, cur_unit, df_id, df_dist, R0s, t0s,
+                       opts=None):
+    """kf_align_host for n guesses against one snapshot's arrays (rebvio_hip_test_kf_align_many_host): R0s [n, 3, 3], t0s [n, 3].
+    Returns a list of n KfHypResult - pose byte for byte kf_align_host's, inliers counted from the same terms. Touches no device."""
+    prs4 = np.ascontiguousarray(prs4, np.float32).reshape(-1, 4)
+    kf_matches = np.ascontiguousarray(kf_matches, np.uint32)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 2)
+    q = np.ascontiguousarray(cur_pos, np.float32).reshape(-1, 2)
+    u = np.ascontiguousarray(cur_unit, np.float32).reshape(-1, 2)
+    ids = np.ascontiguousarray(df_id, np.int32).reshape(-1)
+    dists = np.ascontiguousarray(df_dist, np.int32).reshape(-1)
+    Rs = np.ascontiguousarray(R0s, np.float64).reshape(-1, 9)
+    ts = np.ascontiguousarray(t0s, np.float64).reshape(-1, 3)
+    assert len(prs4) == len(kf_matches) and len(q) == len(u) and (nrm is None or len(nrm) == len(prs4)) and len(Rs) == len(ts)
+    assert len(ids) == len(dists) == int(rows) * int(cols)
+    n = len(Rs)
+    out = (KfHypResult * max(n, 1))()
+    up = C.POINTER(C.c_uint)
+    _chk(lib().rebvio_hip_test_kf_align_many_host(float(fm), float(cx), float(cy), int(rows), int(cols), int(search_range),
+                                                  prs4.ctypes.data_as(_fp) if len(prs4) else None,
+                                                  kf_matches.ctypes.data_as(up) if len(prs4) else None,
+                                                  nrm.ctypes.data_as(_fp) if nrm is not None and len(nrm) else None, len(prs4),
+                                                  q.ctypes.data_as(_fp) if len(q) else None, u.ctypes.data_as(_fp) if len(q) else None,
+                                                  len(q), ids.ctypes.data_as(_ip) if len(ids) else None,
+                                                  dists.ctypes.data_as(_ip) if len(ids) else None, opts, Rs.ctypes.data_as(_dp),
+                                                  ts.ctypes.data_as(_dp), n, out))
+    return [KfHypResult.from_buffer_copy(out[k]) for k in range(n)]
+
+
 def default_kf_fuse_opts(ctx=None, **over) -> KfFuseOpts:
     """The library's defaults (rebvio_hip_default_kf_fuse_opts): pixel_sigma is ctx's pixel_uncertainty and max_dist its search_range
     (1 and 40, the default ones, without a context); kf_filter takes a CloudFilter or a dict of its fields to change."""
@@ -755,6 +841,17 @@ class Map:
                                                  assoc.ctypes.data_as(_ip) if want_assoc and len(assoc) else None))
         del kR, kt
         return (out, assoc) if want_assoc else out
+
+    def keyframe_align_many(self, hyps, opts=None):
+        """Aligns every hypothesis of `hyps` (KfHypothesis: kf_hypothesis(snap, R0, t0), kf_hypotheses_around) to this map in one set
+        of launches (rebvio_hip_map_keyframe_align_many). Returns a list of KfHypResult whose pose is bit for bit keyframe_align's for
+        the same snapshot, guess and options; there are no associations - run keyframe_align on the winner (kf_align_best) for them.
+        The snapshots behind the hypotheses must be kept alive by the caller."""
+        hyps = list(hyps)
+        arr = _hyp_array(hyps, KfHypothesis)
+        out = (KfHypResult * max(len(hyps), 1))()
+        _chk(lib().rebvio_hip_map_keyframe_align_many(self.h, arr if hyps else None, len(hyps), opts, out))
+        return [KfHypResult.from_buffer_copy(out[k]) for k in range(len(hyps))]
 
     def upload(self, kl: np.ndarray):
         kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)

@@ -22,6 +22,7 @@
 #include "glue.hpp"
 #include "hostmath.hpp"
 #include "kf_cloud.hpp"
+#include "kf_many.hpp"
 #include "kf_pose.hpp"
 #include "owned.hpp"
 #include "pixel_format.hpp"
@@ -542,6 +543,14 @@ struct rebvio_hip_ctx {
   double* kfa_part = nullptr;  // (views into kfa_state's allocation)
   int* kfa_used = nullptr;
   int* kfa_assoc = nullptr;
+  // scratch of rebvio_hip_map_keyframe_align_many (ONE allocation on first use, kept; a track-side entry): REBVIO_HIP_KF_HYP_MAX
+  // descriptors, then as many result blocks (uploaded together), then per hypothesis kMaxRecBlocks partials of 28 doubles, used
+  // counts and inlier counts
+  KfHypDesc* kfm_desc = nullptr;
+  rebvio_hip_kf_hyp_result* kfm_res = nullptr;  // (views into kfm_desc's allocation)
+  double* kfm_part = nullptr;
+  int* kfm_used = nullptr;
+  int* kfm_inl = nullptr;
   // scratch of rebvio_hip_kf_snapshot_fuse_depth (ONE allocation on first use, kept; a track-side entry): 8 count words (the six of
   // rebvio_hip_kf_fuse in front), then keylines_max association words
   int* kff_cnt = nullptr;
@@ -2434,6 +2443,164 @@ int rebvio_hip_test_kf_align_host(float fm, float cx, float cy, int rows, int co
     kfp::step(S, used, it == 0, it == o.max_iter, o.min_used, ws, &res);
   }
   *out = res;
+  return 0;
+}
+
+static_assert(sizeof(rebvio_hip_kf_hypothesis) == 104 && offsetof(rebvio_hip_kf_hypothesis, R0) == 8 &&
+                  offsetof(rebvio_hip_kf_hypothesis, t0) == 80,
+              "a pointer, twelve doubles");
+static_assert(sizeof(rebvio_hip_kf_hyp_result) == sizeof(rebvio_hip_kf_pose) + 8 && offsetof(rebvio_hip_kf_hyp_result, pose) == 0 &&
+                  offsetof(rebvio_hip_kf_hyp_result, inliers) == sizeof(rebvio_hip_kf_pose) && sizeof(rebvio_hip_kf_pose) == 456,
+              "the pose, two ints");
+
+int rebvio_hip_map_keyframe_align_many(rebvio_hip_map* m, const rebvio_hip_kf_hypothesis* hyp, int n, const rebvio_hip_kf_align_opts* opts,
+                                       rebvio_hip_kf_hyp_result* out) {
+  if (!m || !hyp || !out) return fail_msg("map_keyframe_align_many: null map, hypothesis list or output", -3);
+  if (n < 1 || n > REBVIO_HIP_KF_HYP_MAX) return fail_msg("map_keyframe_align_many: n outside 1..REBVIO_HIP_KF_HYP_MAX", -3);
+  for (int h = 0; h < n; ++h)
+    if (!hyp[h].snap) return fail_msg("map_keyframe_align_many: null snapshot in the list", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  for (int h = 0; h < n; ++h) {
+    const rebvio_hip_kf_snapshot* sn = hyp[h].snap;
+    if (sn->life == m->life) continue;
+    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+    return fail_msg("map_keyframe_align_many: snapshot of another context", -3);
+  }
+  rebvio_hip_ctx* c = m->ctx;
+  rebvio_hip_kf_align_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_kf_align_opts(c, &o);
+  int rc = 0;
+  for (int h = 0; h < n && !rc; ++h)
+    rc = check_kf_align_args("map_keyframe_align_many", o, (int)c->P.search_range, hyp[h].R0, hyp[h].t0);
+  if (rc) return rc;
+  if (!m->df_built || !m->raster_order)
+    return fail_msg("map_keyframe_align_many: the map's distance field is not detection's (none was built, or its keylines were uploaded)",
+                    -7);
+  HIPCHK(hipSetDevice(c->device));
+  // sizes and normals: each distinct snapshot is asked once (its mutex taken once, never inside another's)
+  const void* normals[REBVIO_HIP_KF_HYP_MAX];
+  int nb_max = 0;
+  for (int h = 0; h < n; ++h) {
+    rebvio_hip_kf_snapshot* sn = hyp[h].snap;
+    int seen = -1;
+    for (int k = 0; k < h && seen < 0; ++k)
+      if (hyp[k].snap == sn) seen = k;
+    if (seen >= 0) {
+      normals[h] = normals[seen];
+      continue;
+    }
+    rc = snapshot_size(c, sn);
+    if (rc) return rc;
+    if (sn->n_host > (int)c->P.keylines_max) return fail_msg("map_keyframe_align_many: a snapshot larger than keylines_max", -2);
+    {
+      std::lock_guard<std::mutex> lk(sn->nor_mu);
+      normals[h] = sn->normals;
+    }
+    const int nb = div_up(sn->n_host, 256);
+    if (nb > nb_max) nb_max = nb;
+  }
+  struct Stage {
+    KfHypDesc desc[REBVIO_HIP_KF_HYP_MAX];
+    rebvio_hip_kf_hyp_result res[REBVIO_HIP_KF_HYP_MAX];
+  };
+  static_assert(offsetof(Stage, res) == sizeof(KfHypDesc) * REBVIO_HIP_KF_HYP_MAX, "the results follow the table without a gap");
+  std::unique_ptr<Stage> stage(new Stage);
+  std::memset(stage.get(), 0, sizeof(Stage));
+  for (int h = 0; h < n; ++h) {
+    kf_pose_start(&stage->res[h].pose, hyp[h].R0, hyp[h].t0);
+    if (hyp[h].snap->n_host == 0) stage->res[h].pose.status = 3;  // nothing to align: neither kernel touches it
+  }
+  if (nb_max == 0) {  // every snapshot is empty: nothing is launched
+    for (int h = 0; h < n; ++h) out[h] = stage->res[h];
+    return 0;
+  }
+  if (!c->kfm_desc) {
+    const size_t head = sizeof(Stage), part = (size_t)kMaxRecBlocks * kfp::kSums * sizeof(double), cnt = (size_t)kMaxRecBlocks * sizeof(int);
+    static_assert(sizeof(Stage) % 64 == 0, "the partials start on a 64-byte line");
+    char* b = nullptr;
+    HIPCHK(c->own.device_bytes(&b, head + REBVIO_HIP_KF_HYP_MAX * (part + 2 * cnt)));
+    c->kfm_desc = reinterpret_cast<KfHypDesc*>(b);
+    c->kfm_res = reinterpret_cast<rebvio_hip_kf_hyp_result*>(b + offsetof(Stage, res));
+    c->kfm_part = reinterpret_cast<double*>(b + head);
+    c->kfm_used = reinterpret_cast<int*>(b + head + REBVIO_HIP_KF_HYP_MAX * part);
+    c->kfm_inl = c->kfm_used + (size_t)REBVIO_HIP_KF_HYP_MAX * kMaxRecBlocks;
+  }
+  for (int h = 0; h < n; ++h) {
+    const rebvio_hip_kf_snapshot* sn = hyp[h].snap;
+    KfHypDesc& d = stage->desc[h];
+    d.prs = sn->prs;
+    d.matches = sn->matches;
+    d.normals = normals[h];
+    d.res = c->kfm_res + h;
+    d.part = c->kfm_part + (size_t)h * kMaxRecBlocks * kfp::kSums;
+    d.part_used = c->kfm_used + (size_t)h * kMaxRecBlocks;
+    d.part_inl = c->kfm_inl + (size_t)h * kMaxRecBlocks;
+    d.size = sn->n_host;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready(c->s_trk, m));
+  // ONE upload: the whole table and the first n result blocks lie next to each other
+  HIPCHK(hipMemcpyAsync(c->kfm_desc, stage.get(), offsetof(Stage, res) + (size_t)n * sizeof(rebvio_hip_kf_hyp_result), hipMemcpyHostToDevice,
+                        c->s_trk));
+  for (int it = 0; it <= o.max_iter; ++it)
+    launch_kf_align_many_eval(c->s_trk, c->K, m->d, c->kfm_desc, n, nb_max, o.kf_filter, o.huber_px, o.min_cos, o.max_dist, it == 0,
+                              it == o.max_iter, o.min_used);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(stage->res, c->kfm_res, (size_t)n * sizeof(rebvio_hip_kf_hyp_result), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  for (int h = 0; h < n; ++h) out[h] = stage->res[h];
+  return 0;
+}
+
+int rebvio_hip_kf_align_best(const rebvio_hip_kf_hyp_result* res, int n, int min_inliers) {
+  if (!res || n < 1) return fail_msg("kf_align_best: null array or n < 1", -3);
+  return kfm::best(res, n, min_inliers);
+}
+
+int rebvio_hip_kf_hypotheses_around(rebvio_hip_kf_snapshot* snap, const double* R, const double* t, double rot_step, double trans_step,
+                                    rebvio_hip_kf_hypothesis* out) {
+  if (!R || !t || !out) return fail_msg("kf_hypotheses_around: null R, t or output", -3);
+  bool fin = std::isfinite(rot_step) && std::isfinite(trans_step);
+  for (int i = 0; i < 9; ++i) fin = fin && std::isfinite(R[i]);
+  for (int i = 0; i < 3; ++i) fin = fin && std::isfinite(t[i]);
+  if (!fin) return fail_msg("kf_hypotheses_around: non-finite R, t or step", -3);
+  if (rot_step < 0.0 || trans_step < 0.0) return fail_msg("kf_hypotheses_around: negative step", -3);
+  kfm::around(snap, R, t, rot_step, trans_step, out);
+  return 0;
+}
+
+int rebvio_hip_test_kf_align_many_host(float fm, float cx, float cy, int rows, int cols, int search_range, const float* snap_prs4,
+                                       const unsigned* snap_matches, const float* snap_normals, int kf_size, const float* cur_pos,
+                                       const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
+                                       const rebvio_hip_kf_align_opts* opts, const double* R0s, const double* t0s, int n,
+                                       rebvio_hip_kf_hyp_result* out) {
+  if (!out || !R0s || !t0s || kf_size < 0 || n_cur < 0 || rows < 0 || cols < 0 || (kf_size > 0 && (!snap_prs4 || !snap_matches)) ||
+      (n_cur > 0 && (!cur_pos || !cur_unit)) || ((size_t)rows * (size_t)cols > 0 && (!df_id || !df_dist)))
+    return fail_msg("test_kf_align_many_host: null array or negative size", -3);
+  if (n < 1 || n > REBVIO_HIP_KF_HYP_MAX) return fail_msg("test_kf_align_many_host: n outside 1..REBVIO_HIP_KF_HYP_MAX", -3);
+  rebvio_hip_kf_align_opts o;
+  if (opts) {
+    o = *opts;
+  } else {
+    rebvio_hip_default_kf_align_opts(nullptr, &o);
+    o.max_dist = search_range;
+  }
+  for (int h = 0; h < n; ++h) {
+    const int rc = check_kf_align_args("test_kf_align_many_host", o, search_range, R0s + 9 * (size_t)h, t0s + 3 * (size_t)h);
+    if (rc) return rc;
+  }
+  const size_t Pn = (size_t)rows * (size_t)cols;
+  for (size_t k = 0; k < Pn; ++k)
+    if (df_id[k] >= n_cur) return fail_msg("test_kf_align_many_host: a field id lies outside the keyline arrays", -3);
+  kfp::AlignMap am;
+  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
+  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
+  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
+  am.cap = n_cur;
+  for (int h = 0; h < n; ++h)
+    kfm::align_host(am, snap_prs4, snap_matches, snap_normals, kf_size, o, R0s + 9 * (size_t)h, t0s + 3 * (size_t)h, &out[h]);
   return 0;
 }
 

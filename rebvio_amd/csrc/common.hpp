@@ -348,6 +348,27 @@ void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int 
                           const unsigned* snap_matches, const void* snap_normals, const rebvio_hip_cloud_filter& flt, double huber,
                           double min_cos, int max_dist, int first, int last, int min_used, rebvio_hip_kf_pose* state_dev, double* part,
                           int* part_used, int* assoc);
+// One hypothesis of rebvio_hip_map_keyframe_align_many as its two kernels read it from device memory (64 bytes, one scalar load):
+// the snapshot's buffers and size, the hypothesis's result block (pose in, pose and inliers out) and its kMaxRecBlocks partials of
+// 28 doubles, used counts and inlier counts.
+struct KfHypDesc {
+  const void* prs;
+  const unsigned* matches;
+  const void* normals;  // null: the snapshot has none
+  rebvio_hip_kf_hyp_result* res;
+  double* part;
+  int* part_used;
+  int* part_inl;
+  int size;  // 0..kmax; 0: neither kernel touches this hypothesis
+  int pad;
+};
+static_assert(sizeof(KfHypDesc) == 64, "seven pointers, the size, padding");
+// One evaluation of rebvio_hip_map_keyframe_align_many on stream s: k_kf_align_sums_many over a grid of (nb_max, n) workgroups -
+// nb_max = the largest ceil(size / 256) of the n (1..REBVIO_HIP_KF_HYP_MAX) descriptors at desc_dev, at least 1 - then
+// k_kf_pose_step_many, one workgroup per hypothesis.
+void launch_kf_align_many_eval(hipStream_t s, const KParams& p, const MapDev& m, const KfHypDesc* desc_dev, int n, int nb_max,
+                               const rebvio_hip_cloud_filter& flt, double huber, double min_cos, int max_dist, int first, int last,
+                               int min_used);
 // k_kf_fuse_depth on stream s (rebvio_hip_kf_snapshot_fuse_depth): the kf_size (1..kmax; kf_size_dev = the same size in device
 // memory, which the kernel reads) keylines of a snapshot against m's distance field, pos and unit at the pose (R, t); rho, sigma_rho
 // and matches of the fused ones are rewritten in place. cnt = 8 ints, cleared by the caller in front of the launch (the kernel

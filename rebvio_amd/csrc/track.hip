@@ -3545,6 +3545,120 @@ void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int 
             state_dev);
 }
 
+// ---- many hypotheses against one map (rebvio_hip_map_keyframe_align_many) -----------------------------------------------------------
+// k_kf_align_sums for a list of (snapshot, pose) hypotheses in one launch: blockIdx.y is the hypothesis, blockIdx.x its workgroup.
+// The descriptor (64 bytes at a workgroup-uniform address: scalar loads) names the snapshot's buffers and size and the hypothesis's
+// result block and partials. A workgroup behind its own hypothesis's last keyline leaves before any vector load and before the
+// barrier - the whole workgroup takes that branch. The per-thread statement is kfp::align_term_in (align_term, copied, with the
+// Huber test's outcome as one more output) and the reduction is k_kf_align_sums' tree, copied: a hypothesis's partials are the
+// bits the single kernel writes for the same snapshot and pose. The inlier count goes the way of `used`: ballot, popcount, LDS.
+// No assoc is written.
+__global__ __launch_bounds__(256) void k_kf_align_sums_many(KParams p, MapDev m, const KfHypDesc* __restrict__ desc,
+                                                            rebvio_hip_cloud_filter flt, double huber, double min_cos, int max_dist) {
+  __shared__ double sh[4][kfp::kSums];
+  __shared__ int sh_used[4];
+  __shared__ int sh_inl[4];
+  const KfHypDesc d = desc[blockIdx.y];
+  if ((int)blockIdx.x * 256 >= d.size) return;
+  const float4* __restrict__ prs = reinterpret_cast<const float4*>(d.prs);
+  const float2* __restrict__ normals = reinterpret_cast<const float2*>(d.normals);
+  const rebvio_hip_kf_pose* __restrict__ st = &d.res->pose;
+  const int tid = threadIdx.x, j = blockIdx.x * 256 + tid, wv = tid >> 6;
+  double v[kfp::kSums];
+#pragma unroll
+  for (int k = 0; k < kfp::kSums; ++k) v[k] = 0.0;
+  bool used = false, inl = false;
+  if (j < d.size) {
+    const float4 k4 = prs[j];
+    const unsigned kmt = d.matches[j];
+    const float2 kn = normals ? normals[j] : make_float2(0.f, 0.f);
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = st->R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = st->t[k];
+    kfp::AlignMap c;
+    c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
+    c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
+    c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
+    c.cap = p.kmax;
+    int i = -1;
+    bool in = false;
+    if (kfp::filter_pass(flt, k4.z, k4.w, kmt))
+      i = kfp::align_term_in(c, k4.x, k4.y, k4.z, normals != nullptr, kn.x, kn.y, min_cos, max_dist, R, t, huber, v, &in);
+    used = i >= 0;
+    inl = used && in;
+  }
+#pragma unroll
+  for (int k = 0; k < kfp::kSums; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
+  }
+  const int nu = __popcll(__ballot(used)), ni = __popcll(__ballot(inl));
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kfp::kSums; ++k) sh[wv][k] = v[k];
+    sh_used[wv] = nu;
+    sh_inl[wv] = ni;
+  }
+  __syncthreads();
+  if (tid < kfp::kSums) d.part[(size_t)blockIdx.x * kfp::kSums + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
+  if (tid == 0) {
+    d.part_used[blockIdx.x] = (sh_used[0] + sh_used[1]) + (sh_used[2] + sh_used[3]);
+    d.part_inl[blockIdx.x] = (sh_inl[0] + sh_inl[1]) + (sh_inl[2] + sh_inl[3]);
+  }
+}
+
+// k_kf_pose_step for the list, one workgroup of 64 per hypothesis: lane k < 28 adds that hypothesis's first ceil(size / 256)
+// partials of sum k in index order from 0.0 (eight loads in flight, as k_kf_pose_step), lane 28 the used counts, lane 29 the inlier
+// counts; lane 0 then runs kfp::step_m (kfp::step, copied) on the hypothesis's result block and leaves the inlier count behind it. A hypothesis of size
+// 0 is left as the host wrote it.
+__global__ __launch_bounds__(64) void k_kf_pose_step_many(const KfHypDesc* __restrict__ desc, int first, int last, int min_used) {
+  __shared__ double S[kfp::kSums];
+  __shared__ double ws[48];
+  __shared__ int sh_used, sh_inl;
+  const KfHypDesc d = desc[blockIdx.x];
+  if (d.size <= 0) return;
+  const int nb = (d.size + 255) >> 8;
+  const double* __restrict__ part = d.part;
+  const int tid = threadIdx.x;
+  if (tid < kfp::kSums) {
+    double s = 0.0;
+    int b = 0;
+    for (; b + 8 <= nb; b += 8) {
+      double x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(b + u) * kfp::kSums + tid];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s = s + x[u];
+    }
+    for (; b < nb; ++b) s = s + part[(size_t)b * kfp::kSums + tid];
+    S[tid] = s;
+  } else if (tid == kfp::kSums) {
+    int u = 0;
+    for (int b = 0; b < nb; ++b) u += d.part_used[b];
+    sh_used = u;
+  } else if (tid == kfp::kSums + 1) {
+    int u = 0;
+    for (int b = 0; b < nb; ++b) u += d.part_inl[b];
+    sh_inl = u;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    rebvio_hip_kf_pose* st = &d.res->pose;
+    if (first) st->candidates = d.size;
+    kfp::step_m(S, sh_used, first, last, min_used, ws, st);
+    d.res->inliers = sh_inl;
+  }
+}
+
+void launch_kf_align_many_eval(hipStream_t s, const KParams& p, const MapDev& m, const KfHypDesc* desc_dev, int n, int nb_max,
+                               const rebvio_hip_cloud_filter& flt, double huber, double min_cos, int max_dist, int first, int last,
+                               int min_used) {
+  RH_LAUNCH(k_kf_align_sums_many, dim3(nb_max, n), dim3(256), 0, s, p, m, desc_dev, flt, huber, min_cos, max_dist);
+  RH_LAUNCH(k_kf_pose_step_many, dim3(n), dim3(64), 0, s, desc_dev, first, last, min_used);
+}
+
 // ---- depth fusion into a snapshot (rebvio_hip_kf_snapshot_fuse_depth) ------------------------------------------------------------
 // kfp::fuse_term (kf_pose.hpp) is the definition's per-keyline statement. One thread per keyframe keyline, a stride loop behind the
 // grid's cap: the 16-byte record, the matches word and the 8-byte normal, then the two dependent gathers of the lookup; a fused

@@ -268,4 +268,51 @@ rebvio::types::KfPose EdgeMap::keyframeAlign(const rebvio::KeyframeSnapshot& sna
   return out;
 }
 
+std::vector<rebvio::types::KfHypResult> EdgeMap::keyframeAlignMany(const std::vector<rebvio::types::KfHypothesis>& hypotheses,
+                                                                   const rebvio::types::KfAlignOpts& opts) {
+  static_assert(sizeof(types::KfHypResult) == sizeof(rebvio_hip_kf_hyp_result) &&
+                    offsetof(types::KfHypResult, inliers) == offsetof(rebvio_hip_kf_hyp_result, inliers) &&
+                    sizeof(types::KfHypothesis) == sizeof(rebvio_hip_kf_hypothesis) &&
+                    offsetof(types::KfHypothesis, R0) == offsetof(rebvio_hip_kf_hypothesis, R0) &&
+                    offsetof(types::KfHypothesis, t0) == offsetof(rebvio_hip_kf_hypothesis, t0),
+                "batched alignment types mirror the C-ABI's");
+  rebvio_hip_kf_align_opts o;
+  std::memcpy(&o, &opts, sizeof(o));
+  if (o.max_dist < 0) {  // the context's search_range
+    rebvio_hip_kf_align_opts def;
+    rebvio_hip_default_kf_align_opts(ctx_, &def);
+    o.max_dist = def.max_dist;
+  }
+  std::vector<rebvio_hip_kf_hypothesis> hyp(hypotheses.size());
+  for (size_t h = 0; h < hyp.size(); ++h) {
+    hyp[h].snap = hypotheses[h].snapshot ? hypotheses[h].snapshot->handle() : nullptr;
+    std::memcpy(hyp[h].R0, hypotheses[h].R0, sizeof(hyp[h].R0));
+    std::memcpy(hyp[h].t0, hypotheses[h].t0, sizeof(hyp[h].t0));
+  }
+  std::vector<rebvio::types::KfHypResult> out(hyp.size());
+  check("rebvio_hip_map_keyframe_align_many",
+        rebvio_hip_map_keyframe_align_many(handle_, hyp.empty() ? nullptr : hyp.data(), (int)hyp.size(), &o,
+                                           reinterpret_cast<rebvio_hip_kf_hyp_result*>(out.data())));
+  return out;
+}
+
+int keyframeAlignBest(const std::vector<rebvio::types::KfHypResult>& results, int min_inliers) {
+  const int rc = rebvio_hip_kf_align_best(reinterpret_cast<const rebvio_hip_kf_hyp_result*>(results.data()), (int)results.size(), min_inliers);
+  if (rc < -1) check("rebvio_hip_kf_align_best", rc);
+  return rc;
+}
+
+std::vector<rebvio::types::KfHypothesis> keyframeHypothesesAround(const rebvio::KeyframeSnapshot& snapshot, const double R[9], const double t[3],
+                                                                  double rot_step, double trans_step) {
+  rebvio_hip_kf_hypothesis h13[13];
+  check("rebvio_hip_kf_hypotheses_around", rebvio_hip_kf_hypotheses_around(snapshot.handle(), R, t, rot_step, trans_step, h13));
+  std::vector<rebvio::types::KfHypothesis> out(13);
+  for (int k = 0; k < 13; ++k) {
+    out[k].snapshot = &snapshot;
+    std::memcpy(out[k].R0, h13[k].R0, sizeof(h13[k].R0));
+    std::memcpy(out[k].t0, h13[k].t0, sizeof(h13[k].t0));
+  }
+  return out;
+}
+
 }  // namespace rebvio

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <limits>
 
@@ -105,6 +106,9 @@ void Rebvio::registerEdgeImageCallback(std::function<void(cv::Mat&, rebvio::Edge
 
 void Rebvio::registerOdometryCallback(std::function<void(rebvio::types::Odometry&)> cb) { odometry_callbacks_.push_back(cb); }
 
+void Rebvio::registerKeyframeWindowCallback(std::function<void(uint64_t ts_us, const std::vector<rebvio::types::KfWindowPose>&)> cb) {
+  keyframe_window_callbacks_.push_back(cb);
+}
 void Rebvio::registerKeyframeCallback(std::function<void(uint64_t ts_us, int kf_matches, int keylines)> cb) { keyframe_callbacks_.push_back(cb); }
 
 void Rebvio::registerKeyframePoseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfPose&)> cb) {
@@ -350,11 +354,21 @@ void Rebvio::stateEstimationProcess() {
     types::KfPose kf_pose;
     bool have_kf_fuse = false;  // setKeyframeDepthFusion: the counts of the new map's fusion into the snapshot
     types::KfFuse kf_fuse;
+    std::vector<types::KfWindowPose> kf_window;  // setKeyframeWindow: the current keyframe and the members against the new map (empty: none)
   } pending;
   // keyframe-pose callbacks: the snapshot of the current keyframe and the last pose estimated against it (the next one's guess)
   rebvio::KeyframeSnapshot kf_snapshot;
   types::KfPose kf_pose_last;
   bool kf_pose_warm = false;
+  // setKeyframeWindow: the retired keyframes that are still aligned to every new map, newest first - snapshot, stamp, and the last
+  // status-0 pose (the next alignment's guess; warm: there is one)
+  struct KfWindowMember {
+    rebvio::KeyframeSnapshot snapshot;
+    uint64_t ts_us;
+    types::KfPose last;
+    bool warm;
+  };
+  std::deque<KfWindowMember> kf_window;
   bool kf_marked_here = false;  // this pair's new map is the one the snapshot was taken from: it is not fused into itself
   // keyframe-cloud callbacks: stamp and odometry pose (R_global, Pos, K) of the record on whose map the snapshot was taken
   uint64_t kf_ts = 0;
@@ -373,6 +387,8 @@ void Rebvio::stateEstimationProcess() {
       for (auto& cb : keyframe_pose_callbacks_) cb(pending.odometry.ts_us, pending.kf_pose);
     if (pending.have_kf_fuse)
       for (auto& cb : keyframe_fuse_callbacks_) cb(pending.odometry.ts_us, pending.kf_fuse);
+    if (!pending.kf_window.empty())
+      for (auto& cb : keyframe_window_callbacks_) cb(pending.odometry.ts_us, pending.kf_window);
     // every cloud goes back to its pool, also when a callback (or the wait) throws
     struct CloudsBack {
       std::vector<rebvio_hip_cloud*>& v;
@@ -646,6 +662,10 @@ void Rebvio::stateEstimationProcess() {
             kf_clouds.push_back(cl);
           }
         }
+        // setKeyframeWindow: the outgoing keyframe stays, behind its cloud; the oldest member makes room
+        const int kf_window_n = (want_kf_pose && keyframe_align_) ? keyframe_window_.load() : 0;
+        if (kf_window_n > 0 && kf_snapshot) kf_window.push_front(KfWindowMember{std::move(kf_snapshot), kf_ts, kf_pose_last, kf_pose_warm});
+        while ((int)kf_window.size() > kf_window_n) kf_window.pop_back();
         kf_snapshot = new_edge_map->keyframeSnapshot();
         kf_ts = new_edge_map->ts_us();
         store3(R_global, kf_odometry_pose.R);
@@ -659,10 +679,33 @@ void Rebvio::stateEstimationProcess() {
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
     // keyframe-pose callbacks: the new map against the keyframe, behind this pair's second half (the call waits for it)
     bool have_kf_pose = false;
+    std::vector<types::KfWindowPose> kf_window_poses;
     if (want_kf_pose && kf_snapshot) {
-      if (keyframe_align_)
+      if (keyframe_align_ && keyframe_window_ > 0) {
+        // the current keyframe and the window's members against the new map, in one set of launches
+        std::vector<types::KfHypothesis> hyp(1 + kf_window.size());
+        auto start = [](types::KfHypothesis& h, const rebvio::KeyframeSnapshot& sn, const types::KfPose* guess) {
+          h.snapshot = &sn;
+          if (!guess) return;
+          std::memcpy(h.R0, guess->R, sizeof(h.R0));
+          std::memcpy(h.t0, guess->t, sizeof(h.t0));
+        };
+        start(hyp[0], kf_snapshot, kf_pose_warm ? &kf_pose_last : nullptr);
+        for (size_t k = 0; k < kf_window.size(); ++k) start(hyp[1 + k], kf_window[k].snapshot, kf_window[k].warm ? &kf_window[k].last : nullptr);
+        const std::vector<types::KfHypResult> res = new_edge_map->keyframeAlignMany(hyp, types::KfAlignOpts());
+        kf_pose_last = res[0].pose;
+        kf_window_poses.push_back(types::KfWindowPose{kf_ts, res[0].pose, res[0].inliers});
+        for (size_t k = 0; k < kf_window.size(); ++k) {
+          kf_window_poses.push_back(types::KfWindowPose{kf_window[k].ts_us, res[1 + k].pose, res[1 + k].inliers});
+          kf_window[k].last = res[1 + k].pose;
+          kf_window[k].warm = res[1 + k].pose.status == 0;
+        }
+        for (size_t k = kf_window.size(); k-- > 0;)  // a member that was lost leaves (reported once, above)
+          if (!kf_window[k].warm) kf_window.erase(kf_window.begin() + (std::ptrdiff_t)k);
+      } else if (keyframe_align_) {
+        if (!kf_window.empty()) kf_window.clear();  // (the window was set to 0 with members in it)
         kf_pose_last = new_edge_map->keyframeAlign(kf_snapshot, types::KfAlignOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
-      else
+      } else
         kf_pose_last = new_edge_map->keyframePose(kf_snapshot, types::KfPoseOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
       kf_pose_warm = kf_pose_last.status == 0;
       have_kf_pose = true;
@@ -697,6 +740,7 @@ void Rebvio::stateEstimationProcess() {
     pending.kf_pose = kf_pose_last;
     pending.have_kf_fuse = have_kf_fuse;
     pending.kf_fuse = kf_fuse;
+    pending.kf_window = std::move(kf_window_poses);
     timers.lap(3);
     timers.end_pair();
     timers.n++;

@@ -16,6 +16,10 @@
 // frame and again after every N-th record (default 10).
 // --kf-align FILE [--kf-every N]: the same file, from the alignment of the keyframe to every tracked map through the map's distance
 // field (Rebvio::setKeyframeAlign) instead of the correspondence chain. One of --kf-pose and --kf-align.
+// --kf-window N FILE: needs --kf-align. Keeps the last N (1..15) retired keyframes aligned to every tracked map next to the current one
+// (Rebvio::setKeyframeWindow, Rebvio::registerKeyframeWindowCallback) and writes one line per (record, keyframe) - the current keyframe
+// first, then the window's members, newest first: ts_us kf_ts_us status used inliers R (9 values, row-major) t (3 values), doubles
+// as %.17g. The odometry file and the --kf-align file are what they are without it.
 // --kf-fuse FILE [--kf-every N]: implies the alignment (with or without --kf-align FILE; not with --kf-pose) and fuses every aligned
 // map into the keyframe snapshot (Rebvio::setKeyframeDepthFusion), one line per fusion, i.e. per pose record of status 0 other than
 // the keyframe's own: ts_us candidates associated fused gated flat clamped.
@@ -34,7 +38,8 @@
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
-  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix;
+  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix, kf_window_path;
+  int kf_window = 0;
   bool kf_align = false;
   int kf_every = 10;
   int W = 0, H = 0;
@@ -82,6 +87,11 @@ int main(int argc, char** argv) {
       if (!kf_fuse_path.empty()) return usage();
       kf_fuse_path = next();
     }
+    else if (a == "--kf-window") {
+      if (!kf_window_path.empty()) return usage();
+      kf_window = std::atoi(next());
+      kf_window_path = next();
+    }
     else if (a == "--kf-cloud") kf_cloud_prefix = next();
     else if (a == "--kf-every") kf_every = std::atoi(next());
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
@@ -96,6 +106,7 @@ int main(int argc, char** argv) {
     }
   }
   if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1) return usage();
+  if (!kf_window_path.empty() && (!kf_align || kf_pose_path.empty() || kf_window < 1 || kf_window > 15)) return usage();  // needs --kf-align FILE
   if (!kf_fuse_path.empty()) {  // the fusion runs behind the alignment only
     if (!kf_pose_path.empty() && !kf_align) return usage();
     kf_align = true;
@@ -154,10 +165,11 @@ int main(int argc, char** argv) {
       ++n_odo;
       if ((want_kf || !kf_cloud_prefix.empty()) && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
     });
-    std::FILE *kf_pose_file = nullptr, *kf_fuse_file = nullptr;
-    size_t n_poses = 0, n_fusions = 0;
+    std::FILE *kf_pose_file = nullptr, *kf_fuse_file = nullptr, *kf_window_file = nullptr;
+    size_t n_poses = 0, n_fusions = 0, n_window = 0;
     if (want_kf) {
-      for (auto pf : {std::make_pair(&kf_pose_path, &kf_pose_file), std::make_pair(&kf_fuse_path, &kf_fuse_file)}) {
+      for (auto pf : {std::make_pair(&kf_pose_path, &kf_pose_file), std::make_pair(&kf_fuse_path, &kf_fuse_file),
+                      std::make_pair(&kf_window_path, &kf_window_file)}) {
         if (pf.first->empty()) continue;
         *pf.second = std::fopen(pf.first->c_str(), "w");
         if (!*pf.second) {
@@ -180,6 +192,19 @@ int main(int argc, char** argv) {
           ++n_fusions;
         });
         rebvio.setKeyframeDepthFusion(true);
+      }
+      if (kf_window_file) {
+        rebvio.registerKeyframeWindowCallback([&](uint64_t ts_us, const std::vector<rebvio::types::KfWindowPose>& w) {
+          for (const rebvio::types::KfWindowPose& e : w) {
+            std::fprintf(kf_window_file, "%llu %llu %d %d %d", (unsigned long long)ts_us, (unsigned long long)e.kf_ts_us, e.pose.status, e.pose.used,
+                         e.inliers);
+            for (double v : e.pose.R) std::fprintf(kf_window_file, " %.17g", v);
+            for (double v : e.pose.t) std::fprintf(kf_window_file, " %.17g", v);
+            std::fprintf(kf_window_file, "\n");
+            ++n_window;
+          }
+        });
+        rebvio.setKeyframeWindow(kf_window);
       }
       rebvio.setKeyframeAlign(kf_align);
       rebvio.requestKeyframe();
@@ -209,6 +234,10 @@ int main(int argc, char** argv) {
     if (!kf_cloud_prefix.empty()) std::fprintf(stderr, "kf_clouds=%zu kf_points=%zu\n", n_kf_clouds, n_kf_points);
     if (kf_pose_file) std::fclose(kf_pose_file);
     if (want_kf) std::fprintf(stderr, "kf_poses=%zu\n", n_poses);
+    if (kf_window_file) {
+      std::fclose(kf_window_file);
+      std::fprintf(stderr, "kf_window_lines=%zu\n", n_window);
+    }
     if (kf_fuse_file) {
       std::fclose(kf_fuse_file);
       std::fprintf(stderr, "kf_fusions=%zu\n", n_fusions);
