@@ -49,6 +49,14 @@ class KeyframeSnapshot {
   // when not associated. Fusing one map twice counts its pixels twice.
   rebvio::types::KfFuse fuseDepth(const rebvio::EdgeMap& map, const rebvio::types::KfPose& pose,
                                   const rebvio::types::KfFuseOpts& opts = rebvio::types::KfFuseOpts(), std::vector<int>* assoc = nullptr);
+  // takes over the refined depths of `src`, the outgoing keyframe's snapshot, where they are better than this snapshot's own
+  // (rebvio_hip_kf_snapshot_handover_depth; synchronous, from the tracking thread). This snapshot must have been taken from `map`;
+  // `pose` is X_cur = R X_kf + t of src against map (e.g. what EdgeMap::keyframeAlign returned for it). src is only read; the two
+  // estimates of a slot are never combined. assoc: per src keyline the slot i when it won an adopted slot, -1 - i for any other
+  // associated keyline, INT_MIN when not associated.
+  rebvio::types::KfHandover handoverDepth(const rebvio::KeyframeSnapshot& src, const rebvio::EdgeMap& map, const rebvio::types::KfPose& pose,
+                                          const rebvio::types::KfHandoverOpts& opts = rebvio::types::KfHandoverOpts(),
+                                          std::vector<int>* assoc = nullptr);
   // the snapshot's depth-bearing keylines - as marked, or as fuseDepth has refined them - as a point cloud, filtered and posed on
   // the device (rebvio_hip_kf_snapshot_point_cloud says exactly which keylines and where; synchronous, from the tracking thread).
   // The default pose is the keyframe's own frame in keyframe depth units; `keyline` is the index in the snapshot and

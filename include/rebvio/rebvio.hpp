@@ -82,6 +82,18 @@ class Rebvio {
   // without this; the odometry does not change by a digit either way. Callable from any thread.
   void setKeyframeDepthFusion(bool on) { keyframe_depth_fusion_ = on; }
   void registerKeyframeFuseCallback(std::function<void(uint64_t ts_us, const rebvio::types::KfFuse&)> cb);
+  // addition: hand a retiring keyframe's refined depths on to its successor. Default off; it acts only while setKeyframeAlign is on
+  // and a keyframe-pose callback is registered, at a requestKeyframe mark that retires a snapshot whose last pose had status 0. The
+  // outgoing snapshot is aligned to the newly marked map - behind the previous record's callbacks, warm-started from its last pose;
+  // with a keyframe window it is the window's own result for its newest member, no second alignment - and on status 0
+  // KeyframeSnapshot::handoverDepth writes its depths into the new snapshot where they are better than the tracker's raw ones
+  // (rebvio_hip_kf_snapshot_handover_depth says exactly how; the two estimates are never combined). The mark's own keyframe-pose
+  // record is computed in front of it and is what it is without the switch; the outgoing keyframe's cloud was queued earlier and
+  // sees what it saw. The counts go to the keyframe-handover callbacks, once per hand-over, right after the keyframe-fuse callbacks:
+  // the record's stamp, the outgoing keyframe's stamp, the counts. Off, the thread runs exactly the calls it runs without this; the
+  // odometry does not change by a digit either way. Callable from any thread.
+  void setKeyframeDepthHandover(bool on) { keyframe_depth_handover_ = on; }
+  void registerKeyframeHandoverCallback(std::function<void(uint64_t ts_us, uint64_t kf_ts_us, const rebvio::types::KfHandover&)> cb);
   // addition: a window of the last n (0..15, default 0: none; values outside are clamped) retired keyframes. It is active only while
   // setKeyframeAlign is on and a keyframe-pose callback is registered. A keyframe that requestKeyframe retires - after its cloud has been
   // queued, so the keyframe-cloud callbacks see what they saw - then keeps its snapshot (and normals) and enters the window with its
@@ -154,6 +166,8 @@ class Rebvio {
   std::atomic<bool> keyframe_align_{false};
   std::vector<std::function<void(uint64_t, const rebvio::types::KfFuse&)>> keyframe_fuse_callbacks_;
   std::atomic<bool> keyframe_depth_fusion_{false};
+  std::vector<std::function<void(uint64_t, uint64_t, const rebvio::types::KfHandover&)>> keyframe_handover_callbacks_;
+  std::atomic<bool> keyframe_depth_handover_{false};
   std::vector<std::function<void(uint64_t, const std::vector<rebvio::types::KfWindowPose>&)>> keyframe_window_callbacks_;
   std::atomic<int> keyframe_window_{0};
   std::thread data_acquisition_thread_, state_estimation_thread_;

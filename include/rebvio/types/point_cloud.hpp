@@ -126,6 +126,31 @@ struct KfFuse {
 };
 static_assert(sizeof(KfFuse) == 24, "KfFuse must stay layout-compatible with rebvio_hip_kf_fuse");
 
+// Options of KeyframeSnapshot::handoverDepth, layout-compatible with the C-ABI's rebvio_hip_kf_handover_opts (rebvio_hip.h defines
+// every term). The defaults are rebvio_hip_default_kf_handover_opts's; max_dist -1 stands for the context's search_range
+// (handoverDepth fills it in).
+struct KfHandoverOpts {
+  CloudFilter kf_filter;   // applied to the outgoing keyframe's keylines
+  double min_cos{0.9};     // the gradient test, where the outgoing snapshot has a non-zero normal; -1 disables it
+  double gate_sigma{3.0};  // conflict gate in standard deviations
+  double q_abs{0.0};       // added in quadrature to sigma_rho before it is propagated
+  int max_dist{-1};        // 0..search_range cells between the projection and the keyline that owns its cell
+  int reserved{0};
+};
+static_assert(sizeof(KfHandoverOpts) == 48, "KfHandoverOpts must stay layout-compatible with rebvio_hip_kf_handover_opts");
+
+// What KeyframeSnapshot::handoverDepth returns, layout-compatible with rebvio_hip_kf_handover: claimed = adopted + kept + conflicts.
+struct KfHandover {
+  int candidates{0};    // the outgoing snapshot's size
+  int associated{0};    // its keylines with an owner below the successor's size
+  int out_of_range{0};  // ... whose propagated depth is not a usable one (they claim nothing)
+  int claimed{0};       // successor slots with at least one claimant
+  int adopted{0};       // ... that took the winner's depth
+  int kept{0};          // ... that agreed with it and were no worse
+  int conflicts{0};     // ... that disagreed with it beyond the gate
+};
+static_assert(sizeof(KfHandover) == 28, "KfHandover must stay layout-compatible with rebvio_hip_kf_handover");
+
 // What a point-cloud or keyframe-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
   uint64_t ts_us;            // the odometry record's stamp (= the map's); keyframe cloud: the stamp of the record the keyframe was marked on

@@ -36,7 +36,9 @@ extern "C" {
  *    rebvio_hip_kf_fuse and the test hook rebvio_hip_test_kf_fuse_host; the test hook rebvio_hip_test_handover_counters;
  *    the snapshot point cloud rebvio_hip_kf_snapshot_point_cloud(_async) and the test hook rebvio_hip_test_kf_cloud_host; the
  *    batched alignment rebvio_hip_map_keyframe_align_many, its structs rebvio_hip_kf_hypothesis / rebvio_hip_kf_hyp_result, the host
- *    helpers rebvio_hip_kf_align_best / rebvio_hip_kf_hypotheses_around and the test hook rebvio_hip_test_kf_align_many_host. */
+ *    helpers rebvio_hip_kf_align_best / rebvio_hip_kf_hypotheses_around and the test hook rebvio_hip_test_kf_align_many_host; the depth
+ *    hand-over rebvio_hip_default_kf_handover_opts, rebvio_hip_kf_snapshot_handover_depth, their structs rebvio_hip_kf_handover_opts /
+ *    rebvio_hip_kf_handover and the test hook rebvio_hip_test_kf_handover_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -564,6 +566,80 @@ int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int col
                                  const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
                                  const rebvio_hip_kf_fuse_opts* opts, const double R[9], const double t[3], rebvio_hip_kf_fuse* out,
                                  int* assoc /*NULL or kf_size ints*/);
+
+/* Depth hand-over between keyframe snapshots: what the fusion above has made of a retiring keyframe's rho / sigma_rho is lost when
+ * the next keyframe is marked - the successor's snapshot is cut from the tracker's map and starts with the tracker's raw depths.
+ * rebvio_hip_kf_snapshot_handover_depth carries the refined depths over, as forwardMatch + updateInverseDepth carry depth from map
+ * to map per pair (rebvio/src/edge_map.cpp, core.cpp): `src`, the outgoing snapshot, is looked up in the distance field of `map`,
+ * the map the new keyframe was marked on; through those associations its depths are propagated into the map's camera frame and
+ * written into `dst`, the successor's snapshot, where they are better than what it has. dst must have been taken from `map` (the
+ * caller's contract, as for the normals: keyline i of the map is slot i of dst). src is never written. (R, t) is the pose
+ * X_cur = R X_kf + t of src against map, e.g. the one rebvio_hip_map_keyframe_align returned. Its uncertainty is NOT propagated:
+ * sig_c below is the keyline's own sigma seen from the new frame, nothing more.
+ * The two estimates of a slot are NEVER combined: both descend from the tracker's filter (the keyframe's through its mark, the
+ * map's through the forward matches), and a Kalman merge would count that ancestry twice - the reason the fusion above refuses the
+ * map's rho as a measurement. The better one stands, whole.
+ * fp64 behind the loads, every + - * / and sqrt one IEEE operation in the order written. RHO_MIN / RHO_MAX are the fusion's.
+ * Pass 1, per src keyline j < src size:
+ *   1. steps 1..6 of rebvio_hip_map_keyframe_align at (R, t), with kf_filter, min_cos and max_dist of these options, give the owner
+ *      i - or the keyline is not associated. It is not associated either when !(i < dst size) (read on the device).
+ *   2. with Z, Y, rho of the term of rebvio_hip_map_keyframe_pose:
+ *        rho_c = rho / Y.z                                   (the keyline's inverse depth in the map's frame)
+ *        d     = Z.z / (Y.z * Y.z)                           (d rho_c / d rho, since Y.z = Z.z + rho t.z)
+ *        s     = (double)sigma_rho_j;   sig_c = fabs(d) * sqrt(s * s + q_abs * q_abs)
+ *      out of range unless rho_c and sig_c are finite, sig_c >= 0 and RHO_MIN <= rho_c <= RHO_MAX (positive tests: a NaN drops it).
+ *   3. (float)rho_c, (float)sig_c and matches_j are staged, and the keyline claims slot i with a 64-bit integer minimum of
+ *      (bits of (float)sig_c) << 32 | j: the smallest propagated sigma wins, the smallest j among equals.
+ * Pass 2, per dst keyline i < dst size whose slot was claimed, rc and sc the winner's staged floats, rho_i / sigma_i the slot's:
+ *   4. dr = (double)rc - (double)rho_i;   conflict unless dr * dr <= (gate_sigma * gate_sigma) * ((double)sc * sc + (double)sigma_i *
+ *      sigma_i) (a positive test: a NaN in dst is a conflict). Two estimates of one edge that disagree beyond their sigmas are two edges.
+ *   5. adopted when sc < sigma_i (fp32, strictly): dst gets rho = rc, sigma_rho = sc, matches = max(matches_i, matches_j).
+ *      Otherwise kept.
+ *   6. pos_img and the normals of dst are never written; a slot that is not adopted keeps all its bits.
+ * assoc[j] = i for the winner of an adopted slot; -1 - i for a loser, for out of range and for the winner of a kept or conflicting
+ * slot; INT_MIN when not associated. claimed counts slots: claimed = adopted + kept + conflicts, and associated - out_of_range -
+ * claimed is the number of losers. Only integer atomics, no floating-point value crosses threads: every output word is the same
+ * on every run.
+ * Two kernels on the track stream (k_kf_handover_claim: one thread per src keyline; k_kf_handover_apply: one per dst keyline;
+ * workgroups of 256, at most 256 of them with a stride loop behind, sizes read on the device). In front of them one all-ones fill of
+ * the claim words and one clear of the count block, behind them one copy back (two with assoc_host). Queued while both snapshots'
+ * locks are held. Synchronous and track-side; map acceptance as rebvio_hip_kf_snapshot_fuse_depth (-7 where the field is not
+ * detection's). The first call that reaches the device gives the context ONE more device allocation (keylines_max claim words,
+ * staging records and association words, and the counts: one more live resource, kept until the context goes); none per call. A src
+ * of size 0: all counts zero, nothing launched or allocated.
+ * -3, before the device is touched: null dst, src, map, R, t or out; dst == src; snapshots or a map of different contexts; a
+ * non-finite R or t; an invalid kf_filter; gate_sigma not > 0; q_abs < 0 or NaN; min_cos outside [-1, 1]; max_dist outside
+ * 0..search_range; reserved != 0. -10: the context has been destroyed. opts NULL = the defaults.
+ * rebvio_hip_test_kf_handover_host (test hook, touches no device): the same statements on the host, in index order, over the arrays of
+ * rebvio_hip_test_kf_fuse_host for src (read only) and dst_prs4 / dst_matches (dst_size records, updated in place); opts NULL = the
+ * defaults with max_dist = search_range. */
+typedef struct rebvio_hip_kf_handover_opts { /* defaults from rebvio_hip_default_kf_handover_opts */
+  rebvio_hip_cloud_filter kf_filter;         /* src side, as in rebvio_hip_kf_align_opts; default = default cloud filter */
+  double min_cos;                            /* as in rebvio_hip_kf_align_opts, default 0.9 */
+  double gate_sigma;                         /* > 0; default 3.0: the conflict gate in standard deviations */
+  double q_abs;                              /* >= 0; default 0: added in quadrature to sigma_rho before it is propagated */
+  int max_dist;                              /* 0..search_range, default search_range */
+  int reserved;                              /* 0 */
+} rebvio_hip_kf_handover_opts;
+typedef struct rebvio_hip_kf_handover {
+  int candidates;     /* src's size */
+  int associated;     /* src keylines with an owner below dst's size */
+  int out_of_range;   /* ...whose propagated depth is not a usable one (they claim nothing) */
+  int claimed;        /* dst slots with at least one claimant */
+  int adopted;        /* ...that took the winner's depth */
+  int kept;           /* ...that agreed with it and were no worse */
+  int conflicts;      /* ...that disagreed with it beyond the gate */
+} rebvio_hip_kf_handover;
+void rebvio_hip_default_kf_handover_opts(rebvio_hip_ctx* ctx /*NULL: max_dist = 40, the default*/, rebvio_hip_kf_handover_opts* opts);
+int rebvio_hip_kf_snapshot_handover_depth(rebvio_hip_kf_snapshot* dst, rebvio_hip_kf_snapshot* src, rebvio_hip_map* map,
+                                          const rebvio_hip_kf_handover_opts* opts, const double R[9], const double t[3],
+                                          rebvio_hip_kf_handover* out, int* assoc_host /*NULL or src-size ints*/);
+int rebvio_hip_test_kf_handover_host(float fm, float cx, float cy, int rows, int cols, int search_range, const float* src_prs4,
+                                     const unsigned* src_matches, const float* src_normals /*NULL: none*/, int kf_size,
+                                     const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
+                                     float* dst_prs4 /*in/out*/, unsigned* dst_matches /*in/out*/, int dst_size,
+                                     const rebvio_hip_kf_handover_opts* opts, const double R[9], const double t[3],
+                                     rebvio_hip_kf_handover* out, int* assoc /*NULL or kf_size ints*/);
 
 /* Point cloud of a keyframe snapshot: its depth-bearing keylines - as marked, or as rebvio_hip_kf_snapshot_fuse_depth has refined
  * them - filtered and posed on the device by kernels of their own (the compaction of rebvio_hip_map_point_cloud over the snapshot's

@@ -99,6 +99,18 @@ class KfFuse(C.Structure):
                 ("clamped", C.c_int)]
 
 
+class KfHandoverOpts(C.Structure):
+    """rebvio_hip_kf_handover_opts (KfSnapshot.handover_depth); defaults from default_kf_handover_opts"""
+    _fields_ = [("kf_filter", CloudFilter), ("min_cos", C.c_double), ("gate_sigma", C.c_double), ("q_abs", C.c_double),
+                ("max_dist", C.c_int), ("reserved", C.c_int)]
+
+
+class KfHandover(C.Structure):
+    """rebvio_hip_kf_handover: the counts of one depth hand-over; claimed = adopted + kept + conflicts"""
+    _fields_ = [("candidates", C.c_int), ("associated", C.c_int), ("out_of_range", C.c_int), ("claimed", C.c_int), ("adopted", C.c_int),
+                ("kept", C.c_int), ("conflicts", C.c_int)]
+
+
 class KfPose(C.Structure):
     """rebvio_hip_kf_pose: X_cur = R X_kf + t, the sums at that pose, and the counters"""
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("H", C.c_double * 36), ("g", C.c_double * 6), ("cost", C.c_double),
@@ -177,6 +189,11 @@ SIGNATURES = {
     "rebvio_hip_test_kf_fuse_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
                                                C.c_int, _fp, _fp, C.c_int, _ip, _ip, C.POINTER(KfFuseOpts), _dp, _dp,
                                                C.POINTER(KfFuse), _ip]),
+    "rebvio_hip_default_kf_handover_opts": (None, [_vp, C.POINTER(KfHandoverOpts)]),
+    "rebvio_hip_kf_snapshot_handover_depth": (C.c_int, [_vp, _vp, _vp, C.POINTER(KfHandoverOpts), _dp, _dp, C.POINTER(KfHandover), _ip]),
+    "rebvio_hip_test_kf_handover_host": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(C.c_uint), _fp,
+                                                   C.c_int, _fp, _fp, C.c_int, _ip, _ip, _fp, C.POINTER(C.c_uint), C.c_int,
+                                                   C.POINTER(KfHandoverOpts), _dp, _dp, C.POINTER(KfHandover), _ip]),
     "rebvio_hip_kf_snapshot_point_cloud": (C.c_int, [_vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), _vp, C.c_int, _ip]),
     "rebvio_hip_kf_snapshot_point_cloud_async": (C.c_int, [_vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), C.POINTER(_vp)]),
     "rebvio_hip_test_kf_cloud_host": (C.c_int, [C.c_float, _fp, C.POINTER(C.c_uint), C.c_int, C.POINTER(CloudFilter), C.POINTER(CloudPose),
@@ -583,6 +600,53 @@ def kf_fuse_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normals
     return out, prs4, kf_matches, assoc
 
 
+def default_kf_handover_opts(ctx=None, **over) -> KfHandoverOpts:
+    """The library's defaults (rebvio_hip_default_kf_handover_opts): max_dist is ctx's search_range (40, the default one, without a
+    context); kf_filter takes a CloudFilter or a dict of its fields to change."""
+    o = KfHandoverOpts()
+    lib().rebvio_hip_default_kf_handover_opts(ctx.h if ctx is not None else None, C.byref(o))
+    for k, v in over.items():
+        if k == "kf_filter" and not isinstance(v, CloudFilter):
+            for fk, fv in v.items():
+                setattr(o.kf_filter, fk, fv)
+        else:
+            setattr(o, k, v)
+    return o
+
+
+def kf_handover_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normals, cur_pos, cur_unit, df_id, df_dist, dst_prs4,
+                     dst_matches, opts=None, R=None, t=None):
+    """KfSnapshot.handover_depth on the host, from arrays (rebvio_hip_test_kf_handover_host; the arrays of kf_fuse_host for the outgoing
+    snapshot, dst_prs4 / dst_matches for the successor). Touches no device and leaves its inputs alone. Returns (KfHandover, new
+    dst_prs4 float32 [m, 4], new dst_matches uint32 [m], assoc int32 [n])."""
+    prs4 = np.ascontiguousarray(prs4, np.float32).reshape(-1, 4)
+    kf_matches = np.ascontiguousarray(kf_matches, np.uint32).reshape(-1)
+    dst_prs4 = np.array(dst_prs4, np.float32).reshape(-1, 4)    # (copies: the hook updates them in place)
+    dst_matches = np.array(dst_matches, np.uint32).reshape(-1)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 2)
+    q = np.ascontiguousarray(cur_pos, np.float32).reshape(-1, 2)
+    u = np.ascontiguousarray(cur_unit, np.float32).reshape(-1, 2)
+    ids = np.ascontiguousarray(df_id, np.int32).reshape(-1)
+    dists = np.ascontiguousarray(df_dist, np.int32).reshape(-1)
+    assert len(prs4) == len(kf_matches) and len(q) == len(u) and (nrm is None or len(nrm) == len(prs4))
+    assert len(dst_prs4) == len(dst_matches) and len(ids) == len(dists) == int(rows) * int(cols)
+    (kR, pR), (kt, pt) = _guess(R, 9), _guess(t, 3)
+    out = KfHandover()
+    assoc = np.full(len(prs4), -2 ** 31, np.int32)
+    up = C.POINTER(C.c_uint)
+    _chk(lib().rebvio_hip_test_kf_handover_host(float(fm), float(cx), float(cy), int(rows), int(cols), int(search_range),
+                                                prs4.ctypes.data_as(_fp) if len(prs4) else None,
+                                                kf_matches.ctypes.data_as(up) if len(prs4) else None,
+                                                nrm.ctypes.data_as(_fp) if nrm is not None and len(nrm) else None, len(prs4),
+                                                q.ctypes.data_as(_fp) if len(q) else None, u.ctypes.data_as(_fp) if len(q) else None, len(q),
+                                                ids.ctypes.data_as(_ip) if len(ids) else None, dists.ctypes.data_as(_ip) if len(ids) else None,
+                                                dst_prs4.ctypes.data_as(_fp) if len(dst_prs4) else None,
+                                                dst_matches.ctypes.data_as(up) if len(dst_prs4) else None, len(dst_prs4),
+                                                opts, pR, pt, C.byref(out), assoc.ctypes.data_as(_ip) if len(assoc) else None))
+    del kR, kt
+    return out, dst_prs4, dst_matches, assoc
+
+
 def kf_cloud_host(fm, prs4, kf_matches, filter=None, pose=None, cap=None, return_count=False):
     """KfSnapshot.point_cloud on the host, from arrays (rebvio_hip_test_kf_cloud_host): prs4 float32 [n, 4] and matches uint32 [n] as
     KfSnapshot.download returns them. Touches no device. Returns the CLOUD_POINT_DTYPE array (and the count with return_count)."""
@@ -645,6 +709,25 @@ class KfSnapshot:
             assoc = np.full(n.value, -2 ** 31, np.int32)
         _chk(lib().rebvio_hip_kf_snapshot_fuse_depth(self.h, map.h, opts, pR, pt, C.byref(out),
                                                      assoc.ctypes.data_as(_ip) if want_assoc and len(assoc) else None))
+        del kR, kt
+        return (out, assoc) if want_assoc else out
+
+    def handover_depth(self, src, map, R, t, opts=None, want_assoc=False):
+        """Takes over the refined depths of `src`, the outgoing keyframe's snapshot, where they are better than this snapshot's own
+        (rebvio_hip_kf_snapshot_handover_depth; synchronous). This snapshot must have been taken from `map`; (R, t) is the pose
+        X_cur = R X_kf + t of src against map (e.g. Map.keyframe_align's). src is only read; the two estimates of a slot are never
+        combined. opts: a KfHandoverOpts or None for the defaults. Returns the KfHandover counts; want_assoc: also the int32 array
+        with, per src keyline, the slot i when it won an adopted slot, -1 - i for any other associated keyline, INT_MIN when not
+        associated."""
+        (kR, pR), (kt, pt) = _guess(R, 9), _guess(t, 3)
+        out = KfHandover()
+        assoc = None
+        if want_assoc:
+            n = C.c_int()
+            _chk(lib().rebvio_hip_kf_snapshot_download(src.h, None, None, 0, C.byref(n)))
+            assoc = np.full(n.value, -2 ** 31, np.int32)
+        _chk(lib().rebvio_hip_kf_snapshot_handover_depth(self.h, src.h if src is not None else None, map.h if map is not None else None, opts,
+                                                         pR, pt, C.byref(out), assoc.ctypes.data_as(_ip) if want_assoc and len(assoc) else None))
         del kR, kt
         return (out, assoc) if want_assoc else out
 

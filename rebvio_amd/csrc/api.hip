@@ -10,6 +10,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -22,6 +23,7 @@
 #include "glue.hpp"
 #include "hostmath.hpp"
 #include "kf_cloud.hpp"
+#include "kf_handover.hpp"
 #include "kf_many.hpp"
 #include "kf_pose.hpp"
 #include "owned.hpp"
@@ -555,6 +557,13 @@ struct rebvio_hip_ctx {
   // rebvio_hip_kf_fuse in front), then keylines_max association words
   int* kff_cnt = nullptr;
   int* kff_assoc = nullptr;  // (a view into kff_cnt's allocation)
+  // scratch of rebvio_hip_kf_snapshot_handover_depth (ONE allocation on first use, kept; a track-side entry): keylines_max claim
+  // words, keylines_max 8-byte staging records, 8 count words (the seven of rebvio_hip_kf_handover in front), keylines_max
+  // association words
+  unsigned long long* kfh_key = nullptr;
+  void* kfh_stage = nullptr;  // (views into kfh_key's allocation)
+  int* kfh_cnt = nullptr;
+  int* kfh_assoc = nullptr;
 };
 
 namespace {
@@ -2730,6 +2739,138 @@ int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int col
     k4[3] = sig_n;
     if (snap_matches[j] != 0xFFFFFFFFu) ++snap_matches[j];
   }
+  *out = res;
+  return 0;
+}
+
+void rebvio_hip_default_kf_handover_opts(rebvio_hip_ctx* c, rebvio_hip_kf_handover_opts* o) {
+  std::memset(o, 0, sizeof(*o));
+  rebvio_hip_default_cloud_filter(&o->kf_filter);
+  o->min_cos = 0.9;
+  o->gate_sigma = 3.0;
+  o->q_abs = 0.0;
+  o->max_dist = c ? (int)c->P.search_range : 40;
+}
+
+namespace {
+int check_kf_handover_args(const char* who, const rebvio_hip_kf_handover_opts& o, int search_range, const double* R, const double* t) {
+  const std::string w(who);
+  if (!R || !t) return fail_msg((w + ": null R or t").c_str(), -3);
+  const int rc = check_cloud_args(who, &o.kf_filter, nullptr);
+  if (rc) return rc;
+  bool fin = true;
+  for (int i = 0; i < 9; ++i) fin = fin && std::isfinite(R[i]);
+  for (int i = 0; i < 3; ++i) fin = fin && std::isfinite(t[i]);
+  if (!fin) return fail_msg((w + ": non-finite R or t").c_str(), -3);
+  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
+  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
+  if (!(o.min_cos >= -1.0 && o.min_cos <= 1.0)) return fail_msg((w + ": min_cos outside [-1, 1]").c_str(), -3);
+  if (o.max_dist < 0 || o.max_dist > search_range) return fail_msg((w + ": max_dist outside 0..search_range").c_str(), -3);
+  if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
+  return 0;
+}
+}  // namespace
+
+static_assert(sizeof(rebvio_hip_kf_handover_opts) == 48, "filter, three doubles, two ints");
+static_assert(sizeof(rebvio_hip_kf_handover) == 28, "seven ints");
+static_assert(sizeof(kfp::HandoverStage) == 8, "one 8-byte store");
+
+int rebvio_hip_kf_snapshot_handover_depth(rebvio_hip_kf_snapshot* dst, rebvio_hip_kf_snapshot* src, rebvio_hip_map* m,
+                                          const rebvio_hip_kf_handover_opts* opts, const double* R, const double* t,
+                                          rebvio_hip_kf_handover* out, int* assoc_host) {
+  if (!dst || !src || !m || !out) return fail_msg("kf_snapshot_handover_depth: null snapshot, map or output", -3);
+  if (dst == src) return fail_msg("kf_snapshot_handover_depth: dst and src are the same snapshot", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  for (rebvio_hip_kf_snapshot* sn : {dst, src})
+    if (sn->life != m->life) {
+      if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+      return fail_msg("kf_snapshot_handover_depth: snapshot of another context", -3);
+    }
+  rebvio_hip_ctx* c = m->ctx;
+  rebvio_hip_kf_handover_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_kf_handover_opts(c, &o);
+  int rc = check_kf_handover_args("kf_snapshot_handover_depth", o, (int)c->P.search_range, R, t);
+  if (rc) return rc;
+  if (!m->df_built || !m->raster_order)
+    return fail_msg("kf_snapshot_handover_depth: the map's distance field is not detection's (none was built, or its keylines were uploaded)", -7);
+  HIPCHK(hipSetDevice(c->device));
+  rc = snapshot_size(c, src);
+  if (rc) return rc;
+  const int kf_size = src->n_host;
+  std::memset(out, 0, sizeof(*out));
+  if (kf_size == 0) return 0;  // nothing to hand over: nothing is launched
+  rc = snapshot_size(c, dst);
+  if (rc) return rc;
+  const int dst_size = dst->n_host;
+  const size_t kmax = (size_t)c->P.keylines_max;
+  if (!c->kfh_key) {
+    char* b = nullptr;
+    HIPCHK(c->own.device_bytes(&b, kmax * (sizeof(unsigned long long) + sizeof(kfp::HandoverStage) + sizeof(int)) + 8 * sizeof(int)));
+    c->kfh_key = reinterpret_cast<unsigned long long*>(b);
+    c->kfh_stage = b + kmax * sizeof(unsigned long long);
+    c->kfh_cnt = reinterpret_cast<int*>(b + kmax * (sizeof(unsigned long long) + sizeof(kfp::HandoverStage)));
+    c->kfh_assoc = c->kfh_cnt + 8;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready(c->s_trk, m));
+  rebvio_hip_kf_handover res;
+  {
+    // both snapshots are this call's from the clears to the kernels; in address order: std::mutex is not recursive (dst != src) and
+    // two threads may name the pair in opposite roles
+    std::mutex* first = &dst->nor_mu;
+    std::mutex* second = &src->nor_mu;
+    if (std::less<std::mutex*>()(second, first)) std::swap(first, second);
+    std::lock_guard<std::mutex> l1(*first);
+    std::lock_guard<std::mutex> l2(*second);
+    if (dst_size > 0) HIPCHK(hipMemsetAsync(c->kfh_key, 0xFF, (size_t)dst_size * sizeof(unsigned long long), c->s_trk));
+    HIPCHK(hipMemsetAsync(c->kfh_cnt, 0, 8 * sizeof(int), c->s_trk));
+    launch_kf_handover(c->s_trk, c->K, m->d, kf_size, src->n_dev, dst_size, dst->n_dev, src->prs, src->matches, src->normals, dst->prs,
+                       dst->matches, o, R, t, c->kfh_key, c->kfh_stage, c->kfh_cnt, c->kfh_assoc);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(&res, c->kfh_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, c->kfh_assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  *out = res;
+  return 0;
+}
+
+int rebvio_hip_test_kf_handover_host(float fm, float cx, float cy, int rows, int cols, int search_range, const float* src_prs4,
+                                     const unsigned* src_matches, const float* src_normals, int kf_size, const float* cur_pos,
+                                     const float* cur_unit, int n_cur, const int* df_id, const int* df_dist, float* dst_prs4,
+                                     unsigned* dst_matches, int dst_size, const rebvio_hip_kf_handover_opts* opts, const double* R,
+                                     const double* t, rebvio_hip_kf_handover* out, int* assoc) {
+  if (!out || kf_size < 0 || n_cur < 0 || dst_size < 0 || rows < 0 || cols < 0 || (kf_size > 0 && (!src_prs4 || !src_matches)) ||
+      (dst_size > 0 && (!dst_prs4 || !dst_matches)) || (n_cur > 0 && (!cur_pos || !cur_unit)) ||
+      ((size_t)rows * (size_t)cols > 0 && (!df_id || !df_dist)))
+    return fail_msg("test_kf_handover_host: null array or negative size", -3);
+  rebvio_hip_kf_handover_opts o;
+  if (opts) {
+    o = *opts;
+  } else {
+    rebvio_hip_default_kf_handover_opts(nullptr, &o);
+    o.max_dist = search_range;
+  }
+  const int rc = check_kf_handover_args("test_kf_handover_host", o, search_range, R, t);
+  if (rc) return rc;
+  const size_t Pn = (size_t)rows * (size_t)cols;
+  for (size_t k = 0; k < Pn; ++k)
+    if (df_id[k] >= n_cur) return fail_msg("test_kf_handover_host: a field id lies outside the keyline arrays", -3);
+  kfp::AlignMap am;
+  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
+  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
+  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
+  am.cap = n_cur;
+  rebvio_hip_kf_handover res;
+  std::vector<unsigned long long> key((size_t)dst_size);
+  std::vector<kfp::HandoverStage> stage((size_t)kf_size);
+  std::vector<int> as((size_t)kf_size);
+  kfp::handover_host(am, src_prs4, src_matches, src_normals, kf_size, dst_prs4, dst_matches, dst_size, o, R, t, key.data(), stage.data(),
+                     as.data(), &res);
+  if (assoc)
+    for (int j = 0; j < kf_size; ++j) assoc[j] = as[(size_t)j];
   *out = res;
   return 0;
 }

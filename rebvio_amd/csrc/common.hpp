@@ -377,6 +377,17 @@ void launch_kf_align_many_eval(hipStream_t s, const KParams& p, const MapDev& m,
 void launch_kf_fuse_depth(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const int* kf_size_dev, void* snap_prs,
                           unsigned* snap_matches, const void* snap_normals, const rebvio_hip_kf_fuse_opts& o, const double* R, const double* t,
                           int* cnt, int* assoc);
+// k_kf_handover_claim + k_kf_handover_apply on stream s (rebvio_hip_kf_snapshot_handover_depth): the src_size (1..kmax) keylines of
+// the outgoing snapshot against m's distance field and unit at the pose (R, t), then the dst_size (0..kmax) keylines of the
+// successor, whose rho, sigma_rho and matches are rewritten where a claim is adopted; src is only read. *_size_dev = the same
+// sizes in device memory, which the kernels read. key = kmax claim words, all-ones over the first dst_size by the caller in front of
+// the launches; stage = kmax 8-byte records; cnt = 8 ints, cleared by the caller (the kernels leave the seven words of
+// rebvio_hip_kf_handover there); assoc = kmax ints. Each grid is min(ceil(size / 256), kMaxRecBlocks) workgroups, at least one, with a
+// stride loop behind it.
+void launch_kf_handover(hipStream_t s, const KParams& p, const MapDev& m, int src_size, const int* src_size_dev, int dst_size,
+                        const int* dst_size_dev, const void* src_prs, const unsigned* src_matches, const void* src_normals, void* dst_prs,
+                        unsigned* dst_matches, const rebvio_hip_kf_handover_opts& o, const double* R, const double* t,
+                        unsigned long long* key, void* stage, int* cnt, int* assoc);
 // k_kf_cloud_count + k_kf_cloud_emit on stream s (rebvio_hip_kf_snapshot_point_cloud*): launch_point_cloud over a snapshot's buffers
 // (ceil(kmax / 256) * 256 slots each; snap_n = its size in device memory). blk_cnt / count_dev / records_dev as there.
 void launch_kf_point_cloud(hipStream_t s, const KParams& p, const void* snap_prs, const unsigned* snap_matches, const int* snap_n,

@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "glue_dev.hpp"
 #include "kf_cloud.hpp"
+#include "kf_handover.hpp"
 #include "kf_pose.hpp"
 
 #include <cstdlib>
@@ -3794,6 +3795,130 @@ void launch_kf_point_cloud(hipStream_t s, const KParams& p, const void* snap_prs
   RH_LAUNCH(k_kf_cloud_count, grid, dim3(256), 0, s, reinterpret_cast<const float4*>(snap_prs), snap_matches, snap_n, flt, blk_cnt);
   RH_LAUNCH(k_kf_cloud_emit, grid, dim3(256), 0, s, p.fm, reinterpret_cast<const float4*>(snap_prs), snap_matches, snap_n, a,
             (const int*)blk_cnt, count_dev, reinterpret_cast<float4*>(records_dev));
+}
+
+// ---- depth hand-over between snapshots (rebvio_hip_kf_snapshot_handover_depth) -----------------------------------------------------
+// kfp::handover_claim_term / handover_apply_term (kf_handover.hpp) are the definition's per-keyline statements.
+//   k_kf_handover_claim  one thread per src keyline, a stride loop behind the grid's cap, as k_kf_fuse_depth: the 16-byte record,
+//                        the matches word and the 8-byte normal, then the dependent gathers of the lookup (the field's cell, the
+//                        owner's unit). A surviving keyline stores its 8-byte staging record (rho_c, matches; the bits of sig_c ride
+//                        in the key) and issues ONE 64-bit atomicMin on its owner's claim word: independent of the order the claims
+//                        arrive in. Claimants of one owner hit one address and are served one after the other at the memory side -
+//                        the price of a collision, paid only by the colliding keylines; the atomic returns nothing the thread waits
+//                        for. Every keyline writes its assoc word: INT_MIN when not associated, -1 - i otherwise - the word of every
+//                        outcome but one, the winner of an adopted slot, which the apply pass overwrites (stream order puts that
+//                        store behind this one). So no pass compares a loser's key with its slot's.
+//   k_kf_handover_apply  one thread per dst keyline, the same cap and loop: the claim word, nothing more for an empty slot; else the
+//                        winner's staging record (one 8-byte gather) and the slot's record and matches word; steps 4..6.
+// Counts: ballots summed per wave over the loop, lane 0 of each wave leaves them in LDS, one integer atomic per workgroup and
+// non-zero count (k_kf_fuse_depth's form). No floating-point value crosses threads. Sizes are read on the device.
+__global__ __launch_bounds__(256) void k_kf_handover_claim(KParams p, MapDev m, const int* __restrict__ src_n, const int* __restrict__ dst_n,
+                                                           const float4* __restrict__ prs, const unsigned* __restrict__ kf_matches,
+                                                           const float2* __restrict__ normals, rebvio_hip_cloud_filter flt, double min_cos,
+                                                           int max_dist, KfFusePose pose, double q_abs,
+                                                           unsigned long long* __restrict__ key, kfp::HandoverStage* __restrict__ stage,
+                                                           int* __restrict__ cnt, int* __restrict__ assoc) {
+  __shared__ int sh_cnt[4][2];
+  const int tid = threadIdx.x;
+  const int n = min(*src_n, p.kmax), nd = min(*dst_n, p.kmax), stride = (int)gridDim.x * 256;
+  kfp::AlignMap c;
+  c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
+  c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
+  c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
+  c.cap = p.kmax;
+  int n_assoc = 0, n_range = 0;
+  for (int base = blockIdx.x * 256; base < n; base += stride) {  // (uniform over the workgroup: the ballots see whole waves)
+    const int j = base + tid;
+    int outcome = kfp::kHoNone;
+    if (j < n) {
+      const float4 k4 = prs[j];
+      const unsigned kmt = kf_matches[j];
+      const float2 kn = normals ? normals[j] : make_float2(0.f, 0.f);
+      int i = 0;
+      float rho_c = 0.f, sig_c = 0.f;
+      if (kfp::filter_pass(flt, k4.z, k4.w, kmt))
+        outcome = kfp::handover_claim_term(c, nd, k4.x, k4.y, k4.z, k4.w, normals != nullptr, kn.x, kn.y, min_cos, max_dist, pose.R, pose.t,
+                                           q_abs, &i, &rho_c, &sig_c);
+      if (outcome == kfp::kHoClaim) {  // (i < nd <= kmax, j < n <= kmax: inside the scratch)
+        stage[j] = kfp::HandoverStage{rho_c, kmt};
+        atomicMin(key + i, kfp::handover_key(sig_c, j));
+      }
+      assoc[j] = outcome == kfp::kHoNone ? (int)0x80000000 : -1 - i;
+    }
+    n_assoc += __popcll(__ballot(outcome != kfp::kHoNone));
+    n_range += __popcll(__ballot(outcome == kfp::kHoOutOfRange));
+  }
+  if ((tid & 63) == 0) {
+    sh_cnt[tid >> 6][0] = n_assoc;
+    sh_cnt[tid >> 6][1] = n_range;
+  }
+  __syncthreads();
+  if (tid < 2) {
+    const int sum = (sh_cnt[0][tid] + sh_cnt[1][tid]) + (sh_cnt[2][tid] + sh_cnt[3][tid]);
+    if (sum) atomicAdd(cnt + 1 + tid, sum);
+  }
+  if (blockIdx.x == 0 && tid == 0) cnt[0] = n;
+}
+
+__global__ __launch_bounds__(256) void k_kf_handover_apply(int kmax, const int* __restrict__ src_n, const int* __restrict__ dst_n,
+                                                           float4* __restrict__ prs, unsigned* __restrict__ dst_matches, double gate_sigma,
+                                                           const unsigned long long* __restrict__ key,
+                                                           const kfp::HandoverStage* __restrict__ stage, int* __restrict__ cnt,
+                                                           int* __restrict__ assoc) {
+  __shared__ int sh_cnt[4][4];
+  const int tid = threadIdx.x;
+  const int n = min(*src_n, kmax), nd = min(*dst_n, kmax), stride = (int)gridDim.x * 256;
+  int n_claimed = 0, n_adopted = 0, n_kept = 0, n_conflict = 0;
+  for (int base = blockIdx.x * 256; base < nd; base += stride) {
+    const int i = base + tid;
+    int slot = kfp::kHoEmpty;
+    if (i < nd) {
+      const unsigned long long k = key[i];
+      const int win = (int)(unsigned)k;
+      if (k != kfp::kHoEmptyKey && win < n) {  // (a claimant's index is below src's size: the test only keeps the gather inside)
+        const kfp::HandoverStage st = stage[win];
+        const float4 d4 = prs[i];
+        const unsigned dmt = dst_matches[i];
+        unsigned mt_n = dmt;
+        const float sc = kfp::handover_key_sigma(k);
+        slot = kfp::handover_apply_term(st.rho_c, sc, st.matches, d4.z, d4.w, dmt, gate_sigma, &mt_n);
+        if (slot == kfp::kHoAdopted) {
+          prs[i] = make_float4(d4.x, d4.y, st.rho_c, sc);
+          dst_matches[i] = mt_n;
+          assoc[win] = i;
+        }
+      }
+    }
+    n_claimed += __popcll(__ballot(slot != kfp::kHoEmpty));
+    n_adopted += __popcll(__ballot(slot == kfp::kHoAdopted));
+    n_kept += __popcll(__ballot(slot == kfp::kHoKept));
+    n_conflict += __popcll(__ballot(slot == kfp::kHoConflict));
+  }
+  if ((tid & 63) == 0) {
+    int* w = sh_cnt[tid >> 6];
+    w[0] = n_claimed; w[1] = n_adopted; w[2] = n_kept; w[3] = n_conflict;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    const int sum = (sh_cnt[0][tid] + sh_cnt[1][tid]) + (sh_cnt[2][tid] + sh_cnt[3][tid]);
+    if (sum) atomicAdd(cnt + 3 + tid, sum);
+  }
+}
+
+void launch_kf_handover(hipStream_t s, const KParams& p, const MapDev& m, int src_size, const int* src_size_dev, int dst_size,
+                        const int* dst_size_dev, const void* src_prs, const unsigned* src_matches, const void* src_normals, void* dst_prs,
+                        unsigned* dst_matches, const rebvio_hip_kf_handover_opts& o, const double* R, const double* t,
+                        unsigned long long* key, void* stage, int* cnt, int* assoc) {
+  KfFusePose pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
+  const int want = div_up(src_size, 256), nb = want < kMaxRecBlocks ? want : kMaxRecBlocks;  // (k_kf_fuse_depth's cap)
+  RH_LAUNCH(k_kf_handover_claim, dim3(nb), dim3(256), 0, s, p, m, src_size_dev, dst_size_dev, reinterpret_cast<const float4*>(src_prs),
+            src_matches, reinterpret_cast<const float2*>(src_normals), o.kf_filter, o.min_cos, o.max_dist, pose, o.q_abs, key,
+            reinterpret_cast<kfp::HandoverStage*>(stage), cnt, assoc);
+  const int want_d = div_up(dst_size > 0 ? dst_size : 1, 256), nbd = want_d < kMaxRecBlocks ? want_d : kMaxRecBlocks;
+  RH_LAUNCH(k_kf_handover_apply, dim3(nbd), dim3(256), 0, s, p.kmax, src_size_dev, dst_size_dev, reinterpret_cast<float4*>(dst_prs),
+            dst_matches, o.gate_sigma, (const unsigned long long*)key, reinterpret_cast<const kfp::HandoverStage*>(stage), cnt, assoc);
 }
 
 }  // namespace rh

@@ -240,6 +240,44 @@ rebvio::types::KfFuse KeyframeSnapshot::fuseDepth(const rebvio::EdgeMap& map, co
   return out;
 }
 
+rebvio::types::KfHandover KeyframeSnapshot::handoverDepth(const rebvio::KeyframeSnapshot& src, const rebvio::EdgeMap& map,
+                                                          const rebvio::types::KfPose& pose, const rebvio::types::KfHandoverOpts& opts,
+                                                          std::vector<int>* assoc) {
+  static_assert(sizeof(types::KfHandoverOpts) == sizeof(rebvio_hip_kf_handover_opts) &&
+                    offsetof(types::KfHandoverOpts, min_cos) == offsetof(rebvio_hip_kf_handover_opts, min_cos) &&
+                    offsetof(types::KfHandoverOpts, gate_sigma) == offsetof(rebvio_hip_kf_handover_opts, gate_sigma) &&
+                    offsetof(types::KfHandoverOpts, q_abs) == offsetof(rebvio_hip_kf_handover_opts, q_abs) &&
+                    offsetof(types::KfHandoverOpts, max_dist) == offsetof(rebvio_hip_kf_handover_opts, max_dist) &&
+                    offsetof(types::KfHandoverOpts, reserved) == offsetof(rebvio_hip_kf_handover_opts, reserved),
+                "depth hand-over options mirror the C-ABI's");
+  static_assert(sizeof(types::KfHandover) == sizeof(rebvio_hip_kf_handover) &&
+                    offsetof(types::KfHandover, associated) == offsetof(rebvio_hip_kf_handover, associated) &&
+                    offsetof(types::KfHandover, out_of_range) == offsetof(rebvio_hip_kf_handover, out_of_range) &&
+                    offsetof(types::KfHandover, claimed) == offsetof(rebvio_hip_kf_handover, claimed) &&
+                    offsetof(types::KfHandover, adopted) == offsetof(rebvio_hip_kf_handover, adopted) &&
+                    offsetof(types::KfHandover, kept) == offsetof(rebvio_hip_kf_handover, kept) &&
+                    offsetof(types::KfHandover, conflicts) == offsetof(rebvio_hip_kf_handover, conflicts),
+                "depth hand-over counts mirror the C-ABI's");
+  rebvio_hip_kf_handover_opts o;
+  std::memcpy(&o, &opts, sizeof(o));
+  if (o.max_dist < 0) {  // the context's search_range
+    rebvio_hip_kf_handover_opts def;
+    rebvio_hip_default_kf_handover_opts(map.ctx(), &def);
+    o.max_dist = def.max_dist;
+  }
+  if (assoc) {
+    int n = 0;
+    check("rebvio_hip_kf_snapshot_download", src.handle() ? rebvio_hip_kf_snapshot_download(src.handle(), nullptr, nullptr, 0, &n) : 0);
+    assoc->assign((size_t)n, std::numeric_limits<int>::min());
+  }
+  rebvio::types::KfHandover out;
+  check("rebvio_hip_kf_snapshot_handover_depth",
+        rebvio_hip_kf_snapshot_handover_depth(handle_, src.handle(), map.handle(), &o, pose.R, pose.t,
+                                              reinterpret_cast<rebvio_hip_kf_handover*>(&out),
+                                              assoc && !assoc->empty() ? assoc->data() : nullptr));
+  return out;
+}
+
 rebvio::types::KfPose EdgeMap::keyframeAlign(const rebvio::KeyframeSnapshot& snapshot, const rebvio::types::KfAlignOpts& opts,
                                              const rebvio::types::KfPose* guess, std::vector<int>* assoc) {
   static_assert(sizeof(types::KfAlignOpts) == sizeof(rebvio_hip_kf_align_opts) &&

@@ -119,6 +119,10 @@ void Rebvio::registerKeyframeFuseCallback(std::function<void(uint64_t ts_us, con
   keyframe_fuse_callbacks_.push_back(cb);
 }
 
+void Rebvio::registerKeyframeHandoverCallback(std::function<void(uint64_t ts_us, uint64_t kf_ts_us, const rebvio::types::KfHandover&)> cb) {
+  keyframe_handover_callbacks_.push_back(cb);
+}
+
 void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
   point_cloud_callbacks_.push_back({cb, filter});
 }
@@ -354,6 +358,9 @@ void Rebvio::stateEstimationProcess() {
     types::KfPose kf_pose;
     bool have_kf_fuse = false;  // setKeyframeDepthFusion: the counts of the new map's fusion into the snapshot
     types::KfFuse kf_fuse;
+    bool have_kf_handover = false;  // setKeyframeDepthHandover: the counts of the retired keyframe's hand-over into the new snapshot
+    types::KfHandover kf_handover;
+    uint64_t kf_handover_ts = 0;    // ... and the retired keyframe's stamp
     std::vector<types::KfWindowPose> kf_window;  // setKeyframeWindow: the current keyframe and the members against the new map (empty: none)
   } pending;
   // keyframe-pose callbacks: the snapshot of the current keyframe and the last pose estimated against it (the next one's guess)
@@ -387,6 +394,8 @@ void Rebvio::stateEstimationProcess() {
       for (auto& cb : keyframe_pose_callbacks_) cb(pending.odometry.ts_us, pending.kf_pose);
     if (pending.have_kf_fuse)
       for (auto& cb : keyframe_fuse_callbacks_) cb(pending.odometry.ts_us, pending.kf_fuse);
+    if (pending.have_kf_handover)
+      for (auto& cb : keyframe_handover_callbacks_) cb(pending.odometry.ts_us, pending.kf_handover_ts, pending.kf_handover);
     if (!pending.kf_window.empty())
       for (auto& cb : keyframe_window_callbacks_) cb(pending.odometry.ts_us, pending.kf_window);
     // every cloud goes back to its pool, also when a callback (or the wait) throws
@@ -648,6 +657,12 @@ void Rebvio::stateEstimationProcess() {
     // Rebvio::requestKeyframe: the new map is marked behind this pair's second half (which writes the previous keyframe's ids into
     // it), in front of the next pair's first half (which hands the ids on)
     kf_marked_here = false;
+    // setKeyframeDepthHandover: the keyframe this mark retires, where its depths are to go on to the new one - as the window's newest
+    // member (handover_in_window), or kept here until its alignment behind publish_pending()
+    bool handover_in_window = false;
+    rebvio::KeyframeSnapshot handover_outgoing;
+    types::KfPose handover_guess;
+    uint64_t handover_ts = 0;
     if (keyframe_requested_.exchange(false)) {
       new_edge_map->markKeyframe();
       if (want_kf_pose || want_kf_cloud) {  // the keyframe as it is now, right behind its mark; the previous one goes
@@ -664,6 +679,13 @@ void Rebvio::stateEstimationProcess() {
         }
         // setKeyframeWindow: the outgoing keyframe stays, behind its cloud; the oldest member makes room
         const int kf_window_n = (want_kf_pose && keyframe_align_) ? keyframe_window_.load() : 0;
+        const bool handover = want_kf_pose && keyframe_align_ && keyframe_depth_handover_ && kf_snapshot && kf_pose_warm;
+        if (handover) {
+          handover_ts = kf_ts;
+          handover_guess = kf_pose_last;
+          handover_in_window = kf_window_n > 0;
+          if (!handover_in_window) handover_outgoing = std::move(kf_snapshot);
+        }
         if (kf_window_n > 0 && kf_snapshot) kf_window.push_front(KfWindowMember{std::move(kf_snapshot), kf_ts, kf_pose_last, kf_pose_warm});
         while ((int)kf_window.size() > kf_window_n) kf_window.pop_back();
         kf_snapshot = new_edge_map->keyframeSnapshot();
@@ -679,6 +701,8 @@ void Rebvio::stateEstimationProcess() {
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
     // keyframe-pose callbacks: the new map against the keyframe, behind this pair's second half (the call waits for it)
     bool have_kf_pose = false;
+    bool have_kf_handover = false;
+    types::KfHandover kf_handover;
     std::vector<types::KfWindowPose> kf_window_poses;
     if (want_kf_pose && kf_snapshot) {
       if (keyframe_align_ && keyframe_window_ > 0) {
@@ -700,6 +724,11 @@ void Rebvio::stateEstimationProcess() {
           kf_window[k].last = res[1 + k].pose;
           kf_window[k].warm = res[1 + k].pose.status == 0;
         }
+        // setKeyframeDepthHandover: the window's own result for its newest member is the outgoing keyframe against the new map
+        if (handover_in_window && !kf_window.empty() && kf_window[0].ts_us == handover_ts && res[1].pose.status == 0) {
+          kf_handover = kf_snapshot.handoverDepth(kf_window[0].snapshot, *new_edge_map, res[1].pose);
+          have_kf_handover = true;
+        }
         for (size_t k = kf_window.size(); k-- > 0;)  // a member that was lost leaves (reported once, above)
           if (!kf_window[k].warm) kf_window.erase(kf_window.begin() + (std::ptrdiff_t)k);
       } else if (keyframe_align_) {
@@ -709,6 +738,18 @@ void Rebvio::stateEstimationProcess() {
         kf_pose_last = new_edge_map->keyframePose(kf_snapshot, types::KfPoseOpts(), kf_pose_warm ? &kf_pose_last : nullptr);
       kf_pose_warm = kf_pose_last.status == 0;
       have_kf_pose = true;
+    }
+    // setKeyframeDepthHandover without a window: one alignment of the outgoing keyframe to the newly marked map, warm-started from its
+    // last pose, behind the mark's own pose above (which so is what it is without the switch); then the outgoing snapshot goes
+    if (handover_outgoing) {
+      if (have_kf_pose && keyframe_align_) {
+        const types::KfPose ho = new_edge_map->keyframeAlign(handover_outgoing, types::KfAlignOpts(), &handover_guess);
+        if (ho.status == 0) {
+          kf_handover = kf_snapshot.handoverDepth(handover_outgoing, *new_edge_map, ho);
+          have_kf_handover = true;
+        }
+      }
+      handover_outgoing.reset();
     }
     // setKeyframeDepthFusion: behind an alignment of status 0 the new map is one more view of the keyframe's edges from a known pose
     bool have_kf_fuse = false;
@@ -740,6 +781,9 @@ void Rebvio::stateEstimationProcess() {
     pending.kf_pose = kf_pose_last;
     pending.have_kf_fuse = have_kf_fuse;
     pending.kf_fuse = kf_fuse;
+    pending.have_kf_handover = have_kf_handover;
+    pending.kf_handover = kf_handover;
+    pending.kf_handover_ts = handover_ts;
     pending.kf_window = std::move(kf_window_poses);
     timers.lap(3);
     timers.end_pair();

@@ -23,6 +23,9 @@
 // --kf-fuse FILE [--kf-every N]: implies the alignment (with or without --kf-align FILE; not with --kf-pose) and fuses every aligned
 // map into the keyframe snapshot (Rebvio::setKeyframeDepthFusion), one line per fusion, i.e. per pose record of status 0 other than
 // the keyframe's own: ts_us candidates associated fused gated flat clamped.
+// --kf-handover FILE: needs --kf-align. Hands every retired keyframe's refined depths on to its successor
+// (Rebvio::setKeyframeDepthHandover, Rebvio::registerKeyframeHandoverCallback), one line per hand-over: ts_us kf_ts_us candidates
+// associated out_of_range claimed adopted kept conflicts - ts_us the record's stamp, kf_ts_us the retired keyframe's own.
 // --kf-cloud PREFIX [--kf-every N]: every retired keyframe's point cloud (Rebvio::registerKeyframeCloudCallback, default filter) as
 // PREFIX<ts_us>.ply, ts_us the keyframe's own stamp, through the same PLY writer; keyframes are requested as for --kf-pose. Alone it
 // writes the keyframes as marked; with --kf-fuse (and --kf-align) the refined ones. The keyframe current at the end is not written.
@@ -38,7 +41,7 @@
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
-  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix, kf_window_path;
+  std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix, kf_window_path, kf_handover_path;
   int kf_window = 0;
   bool kf_align = false;
   int kf_every = 10;
@@ -50,7 +53,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
+                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -87,6 +90,10 @@ int main(int argc, char** argv) {
       if (!kf_fuse_path.empty()) return usage();
       kf_fuse_path = next();
     }
+    else if (a == "--kf-handover") {
+      if (!kf_handover_path.empty()) return usage();
+      kf_handover_path = next();
+    }
     else if (a == "--kf-window") {
       if (!kf_window_path.empty()) return usage();
       kf_window = std::atoi(next());
@@ -107,6 +114,7 @@ int main(int argc, char** argv) {
   }
   if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1) return usage();
   if (!kf_window_path.empty() && (!kf_align || kf_pose_path.empty() || kf_window < 1 || kf_window > 15)) return usage();  // needs --kf-align FILE
+  if (!kf_handover_path.empty() && (!kf_align || kf_pose_path.empty())) return usage();  // needs --kf-align FILE
   if (!kf_fuse_path.empty()) {  // the fusion runs behind the alignment only
     if (!kf_pose_path.empty() && !kf_align) return usage();
     kf_align = true;
@@ -165,11 +173,11 @@ int main(int argc, char** argv) {
       ++n_odo;
       if ((want_kf || !kf_cloud_prefix.empty()) && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
     });
-    std::FILE *kf_pose_file = nullptr, *kf_fuse_file = nullptr, *kf_window_file = nullptr;
-    size_t n_poses = 0, n_fusions = 0, n_window = 0;
+    std::FILE *kf_pose_file = nullptr, *kf_fuse_file = nullptr, *kf_window_file = nullptr, *kf_handover_file = nullptr;
+    size_t n_poses = 0, n_fusions = 0, n_window = 0, n_handovers = 0;
     if (want_kf) {
       for (auto pf : {std::make_pair(&kf_pose_path, &kf_pose_file), std::make_pair(&kf_fuse_path, &kf_fuse_file),
-                      std::make_pair(&kf_window_path, &kf_window_file)}) {
+                      std::make_pair(&kf_window_path, &kf_window_file), std::make_pair(&kf_handover_path, &kf_handover_file)}) {
         if (pf.first->empty()) continue;
         *pf.second = std::fopen(pf.first->c_str(), "w");
         if (!*pf.second) {
@@ -192,6 +200,14 @@ int main(int argc, char** argv) {
           ++n_fusions;
         });
         rebvio.setKeyframeDepthFusion(true);
+      }
+      if (kf_handover_file) {
+        rebvio.registerKeyframeHandoverCallback([&](uint64_t ts_us, uint64_t kf_ts_us, const rebvio::types::KfHandover& h) {
+          std::fprintf(kf_handover_file, "%llu %llu %d %d %d %d %d %d %d\n", (unsigned long long)ts_us, (unsigned long long)kf_ts_us, h.candidates,
+                       h.associated, h.out_of_range, h.claimed, h.adopted, h.kept, h.conflicts);
+          ++n_handovers;
+        });
+        rebvio.setKeyframeDepthHandover(true);
       }
       if (kf_window_file) {
         rebvio.registerKeyframeWindowCallback([&](uint64_t ts_us, const std::vector<rebvio::types::KfWindowPose>& w) {
@@ -241,6 +257,10 @@ int main(int argc, char** argv) {
     if (kf_fuse_file) {
       std::fclose(kf_fuse_file);
       std::fprintf(stderr, "kf_fusions=%zu\n", n_fusions);
+    }
+    if (kf_handover_file) {
+      std::fclose(kf_handover_file);
+      std::fprintf(stderr, "kf_handovers=%zu\n", n_handovers);
     }
     if (n_odo > 1) {  // wall clock between the first and the last published odometry: the whole class, input thread included
       const double sec = std::chrono::duration<double>(t_last - t_first).count();
