@@ -98,6 +98,20 @@ def assert_keylines_equal(ko, kg, what="", skip=()):
                                  f"{ko[f][bad[:3]]} vs {kg[f][bad[:3]]}")
 
 
+def nan_canonical(kl):
+    """keylines with every NaN of a float field replaced by the one quiet NaN (as record_words does for records)"""
+    kl = kl.copy()
+    for f in kl.dtype.names:
+        if kl.dtype[f].base.kind == "f":
+            a = kl[f]
+            a[np.isnan(a)] = np.float32(np.nan)
+    return kl
+
+
+def assert_keylines_equal_nan(ko, kg, what=""):
+    assert_keylines_equal(nan_canonical(ko), nan_canonical(kg), what=what)
+
+
 # ---- numpy reference models ---------------------------------------------------------------------------------------------
 # the point cloud (include/rebvio_hip.h; checked by hand in tests/test_point_cloud.py)
 def np_passes(kl, min_matches, max_rel_sigma, rho_min, rho_max):
@@ -759,6 +773,217 @@ def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, w
     assert len(got) == len(rec_o) == npairs
     for k, (wo, wg) in enumerate(zip(rec_o, got)):
         assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8])
+
+
+# ---- the three runners of a stream with per-frame rotations: oracle, per-pair API, streaming driver -----------------------
+def oracle_pairs(orc_mod, cam, seq, R, keep=(), **kw):
+    """seq[] through the CPU oracle alone, keyline sums in the kernels' order; R = None: no priors. (records, keyline counts);
+    keep: pair numbers after which the keylines of both maps are kept - [(records, keyline counts), {pair: (old, new)}]"""
+    orc = orc_mod.Oracle(params_for(orc_mod, cam, **kw))
+    orc.set_sum_order("device")
+    recs, prev, kept = [], None, {}
+    for k, f in enumerate(seq):
+        m = orc.detect_u8(f, k * TS)
+        if prev is not None:
+            recs.append((orc.track_pair(prev, m, R_prior=None if R is None else R[k]), m.size()))
+            if k - 1 in keep:
+                kept[k - 1] = (prev.keylines(), m.keylines())
+        prev = m
+    return (recs, kept) if keep else recs
+
+
+def lib_pairs(B, cam, seq, R, mask=None, keep=(), **kw):
+    """per-pair API: detect (+ per-frame mask) and rebvio_hip_track_pair(R_prior = R[k]); (records as words, gyro state);
+    keep: as oracle_pairs - (records as words, gyro state, {pair: (old, new)})"""
+    ctx = B.Context(params_for(B, cam, **kw))
+    npx = cam.width * cam.height
+    dev = ctx.upload_frames(seq)
+    mdev = ctx.upload_frames(mask[None]) if mask is not None else None
+    maps, recs, kept = [], [], {}
+    for k in range(len(seq)):
+        if mdev is None:
+            maps.append(ctx.detect_u8_device(dev + k * npx, k * TS))
+        else:
+            maps.append(ctx.detect_px_masked_device(dev + k * npx, B.PX_GRAY8, mdev, k * TS))
+        if len(maps) > 2:
+            maps.pop(0).release()
+        if k:
+            recs.append(rec(ctx.track_pair(maps[0], maps[1], R_prior=None if R is None else R[k]), maps[1].size()))
+            if k - 1 in keep:
+                kept[k - 1] = (maps[0].keylines(), maps[1].keylines())
+    st = ctx.gyro_state()
+    ctx.close()
+    return (recs, state_words(st), kept) if keep else (recs, state_words(st))
+
+
+def lib_stream(B, cam, seq, R, mask=None, host=False, flush_after=(), entry="gyro", profile=False, **kw):
+    """streaming driver: seq[k] pushed with R[k] (None: NULL) through the gyro entries (entry = "u8": the existing
+    push_frame_u8_device, R unused); flush_after: frame counts after which rebvio_hip_flush is called mid-stream.
+    (records as words, gyro state after the closing flush[, kernel launches counted by the profiler])"""
+    ctx = B.Context(params_for(B, cam, **kw))
+    npx = cam.width * cam.height
+    dev = ctx.upload_frames(seq)
+    mdev = ctx.upload_frames(mask[None]) if mask is not None else None
+    if profile:
+        ctx.profile_reset()
+        ctx.profile(True)
+    recs = []
+    for k in range(len(seq)):
+        if entry == "u8":
+            out, n = ctx.push_frame_u8_device(dev + k * npx, k * TS)
+        elif host:
+            out, n = ctx.push_frame_px_gyro(np.ascontiguousarray(seq[k]), B.PX_GRAY8, R[k], k * TS)
+        else:
+            out, n = ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, R[k], mdev, k * TS)
+        if out.status >= 0:
+            recs.append(rec(out, n))
+        if k + 1 in flush_after:
+            recs.extend(rec(o, n) for o, n in ctx.flush())
+    recs.extend(rec(o, n) for o, n in ctx.flush())
+    st = state_words(ctx.gyro_state())
+    launches = None
+    if profile:
+        launches = {name: calls for name, (_, calls) in ctx.profile_read().items()}
+        ctx.profile(False)
+    ctx.close()
+    return (recs, st, launches) if profile else (recs, st)
+
+
+# ---- large and wrong rotation priors (tests/test_large_rotations.py holds the oracle to what is written here; the GPU file
+# runs the library against it) ------------------------------------------------------------------------------------------
+N_TURN = 8             # frames of every stream of these tests (192x144, KW_TRACK)
+BAD_PAIR = 3           # the pair 3 -> 4 takes the wrong prior
+# w (rad) of the wrong prior rodrigues(w).astype(float32) -> the oracle's status of that pair and its klm_num with the other pairs
+# run (a) without a prior, (b) with gyro_rotations(order, 5). Sums in device order. In every row the three pairs behind the bad
+# one end with status 0 and at least 1881 (a) / 1906 (b) matches.
+WRONG_PRIORS = {
+    (0.0, 0.05, 0.0): (0, 1704, 1736),
+    (0.02, 0.3, -0.1): (0, 149, 105),
+    (0.0, 0.8, 0.0): (0, 72, 61),
+    (0.0, np.pi / 2, 0.0): (1, 0, 0),
+    (0.3, 1.5, 0.2): (1, 0, 0),
+    (0.0, np.pi, 0.0): (1, 0, 0),
+    (0.0, 0.0, np.pi / 2): (0, 151, 196),
+    (0.0, 0.0, 3.0): (0, 198, 176),
+}
+ROT90_Y = np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], F32)   # the exact fp32 matrices of 90 degrees about y and about x
+ROT90_X = np.array([[1, 0, 0], [0, 0, -1], [0, 1, 0]], F32)
+# No rotation by +-90 degrees gives a rotated z of -0: the product is summed from +0.0 in double, and +0 + -0 = +0. This matrix
+# (no rotation; rotateKeylines takes any) does: z = -2^-100 * (pos_img.x / fm), which for a denormal quotient lies below the
+# smallest fp32 denormal and rounds to -0 (to +0 for a negative quotient); every other keyline gets a z around 1e-31.
+UNDERFLOW_Z = np.array([[1, 0, 0], [0, 1, 0], [-2.0 ** -100, 0, 0]], F32)
+CRAFT_ROTATIONS = {"y90": ROT90_Y, "x90": ROT90_X, "underflow": UNDERFLOW_Z}
+# three wrong priors in a row, pairs 2 -> 3, 3 -> 4, 4 -> 5 (the others gyro_rotations(order, 5)): the oracle's status and klm_num
+CONSECUTIVE = {2: (0.0, np.pi / 2, 0.0), 3: (0.0, np.pi, 0.0), 4: (0.0, 0.8, 0.0)}
+CONSECUTIVE_PAIRS = [(0, 2028), (0, 1995), (1, 0), (1, 0), (0, 217), (0, 1878), (0, 1843)]
+# yaw (degrees per frame) of the fast-turn streams -> the oracle's klm_num per pair with the true prior, without a prior (every
+# status 0). +6: every pair with the prior has 700 or more, five of seven without it have fewer. No stream of -6, -5 or -4
+# degrees meets those bars (with the true prior: -6 below; -5: 214 194 198 [status 1] 315 323 143; -4: 936 326 432 722 439 417 420),
+# so the -6 stream stands here with what the oracle gives for it and claims no more than status 0 on every pair.
+FAST_TURNS = {
+    6.0: ([805, 1052, 1238, 1364, 1327, 1384, 1227], [1335, 348, 603, 625, 594, 498, 422]),
+    -6.0: ([704, 495, 541, 428, 217, 352, 273], [1547, 498, 478, 747, 456, 382, 223]),
+}
+TURN_MIN_KLM = 700
+DEPTH_VALUES = (0.0, -1.0, np.inf, np.nan, RHO_MIN, RHO_MAX)   # what the crafted maps put into rho and sigma_rho
+CRAFT_SIZES = (1, 63, 64, 65, 256, 257)
+
+
+def w_id(w):
+    return ",".join(f"{v:.3g}" for v in w)
+
+
+def wrong_prior_rotations(bad, n=N_TURN, stream_id=0, elsewhere="gyro"):
+    """gyro_rotations(range(n), 5) - elsewhere = None: no prior - with the prior of pair k -> k + 1 replaced by rodrigues(bad[k])
+    for every k of `bad`"""
+    R = gyro_rotations(list(range(n)), 5, stream_id) if elsewhere == "gyro" else [None] * n
+    for k, w in bad.items():
+        R[k + 1] = rodrigues(w).astype(F32)
+    return R
+
+
+_turn_cache = {}
+
+
+def turn_stream(yaw_deg=None, stream_id=0):
+    """(frames [N_TURN, 144, 192], camera, rotations): stream `stream_id` as render_stream gives it (yaw_deg None; rotations
+    gyro_rotations(order, 5)), or its scene turning by yaw_deg per frame with the same translation and the true relative
+    rotations as priors. Rendered once."""
+    key = (yaw_deg, stream_id)
+    if key not in _turn_cache:
+        from rebvio_amd import synth
+        if yaw_deg is None:
+            frames, cam = synth.render_stream(192, 144, N_TURN, stream_id=stream_id)
+            R = gyro_rotations(list(range(N_TURN)), 5, stream_id)
+        else:
+            cam = synth.Camera.for_size(192, 144)
+            scene = synth.make_scene(stream_id, 1.0)
+            scene.yaw_deg = yaw_deg
+            frames = np.stack([synth.render_frame(scene, cam, float(t), noise_seed=stream_id * 100003 + t) for t in range(N_TURN)])
+            R = [np.eye(3, dtype=F32)]
+            for t in range(1, N_TURN):
+                Ri, Rj = synth.pose(scene, t - 1)[0], synth.pose(scene, t)[0]
+                R.append(((Ri.T @ Rj).T).astype(F32))
+        frames = np.ascontiguousarray(frames)
+        frames.setflags(write=False)
+        _turn_cache[key] = (frames, cam, R)
+    return _turn_cache[key]
+
+
+def craft_rotation_map(kl, n):
+    """The first n keylines of a detected map with the inputs that put rotateKeylines (edge_map.cpp:58-71) on its edges under
+    ROT90_Y (rotated z = -pos_img.x / fm) and ROT90_X (rotated z = pos_img.y / fm). Keyline i, by i % 8: pos_img.x = +0, -0;
+    pos_img.y = +0, -0; pos_img.x, pos_img.y a denormal (so is the quotient by fm); 6, 7 as detected (both signs occur).
+    rho = DEPTH_VALUES[i % 7] and sigma_rho = DEPTH_VALUES[(i // 7) % 7], index 6 = as detected."""
+    out = kl[:n].copy()
+    assert len(out) == n
+    i = np.arange(n)
+    c = i % 8
+    x, y = out["pos_img"][:, 0], out["pos_img"][:, 1]
+    x[c == 0], x[c == 1], y[c == 2], y[c == 3] = F32(0.0), F32(-0.0), F32(0.0), F32(-0.0)
+    tiny = np.where((i // 8) % 2 == 0, F32(3e-39), F32(-3e-39)).astype(F32)
+    x[c == 4] = tiny[c == 4]
+    y[c == 5] = tiny[c == 5]
+    for f, sel in (("rho", i % 7), ("sigma_rho", (i // 7) % 7)):
+        for v in range(6):
+            out[f][sel == v] = F32(DEPTH_VALUES[v])
+    return out
+
+
+def rotated_z(kl, R, fm):
+    """the third component of rotateKeylines' rotated vector: accumulated in double from 0.0, rounded to fp32 once
+    (TooN's makeVector(float, float, 1.0) is a vector of doubles)"""
+    with np.errstate(all="ignore"):
+        v0 = (kl["pos_img"][:, 0] / F32(fm)).astype(F32).astype(np.float64)
+        v1 = (kl["pos_img"][:, 1] / F32(fm)).astype(F32).astype(np.float64)
+        R = np.asarray(R, F32).astype(np.float64)
+        s = np.zeros(len(kl), np.float64)
+        s = s + R[2, 0] * v0
+        s = s + R[2, 1] * v1
+        s = s + R[2, 2] * 1.0
+        return s.astype(F32)
+
+
+def rotation_classes(kl, R, fm):
+    """how many keylines of the crafted map land on each edge of rotateKeylines under R"""
+    z = rotated_z(kl, R, fm)
+    tiny = np.finfo(F32).tiny
+    zero = z == 0
+    return dict(plus_zero=int((zero & ~np.signbit(z)).sum()), minus_zero=int((zero & np.signbit(z)).sum()),
+                denormal=int(((np.abs(z) > 0) & (np.abs(z) < tiny)).sum()), negative=int((z < 0).sum()),
+                **{f"{f}={v}": int((np.isnan(kl[f]) if np.isnan(v) else kl[f] == F32(v)).sum())
+                   for f in ("rho", "sigma_rho") for v in DEPTH_VALUES})
+
+
+def oracle_fusion(orc_mod, po):
+    """What the oracle's own glue hands to the second half of a pair (rebvio.cpp:195-203, 225-233): V, P_V, the corrected
+    rotation and R0 = SO3::exp of the rotational part of Xgv - the inputs of rebvio_hip_track_pair_finish_async."""
+    import ctypes as C
+    w = np.array(po.Xgv, F32)[3:].copy()
+    R0 = np.zeros(9, F32)
+    fp = C.POINTER(C.c_float)
+    orc_mod.lib().orc_so3_exp(w.ctypes.data_as(fp), R0.ctypes.data_as(fp))
+    return np.array(po.V, F32), np.array(po.P_V, F32), np.array(po.R, F32), R0
 
 
 # ---- fixtures -----------------------------------------------------------------------------------------------------------

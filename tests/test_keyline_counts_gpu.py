@@ -38,8 +38,8 @@ import pytest
 
 from conftest import params_for
 from support import B  # noqa: F401
-from support import (FORMS, KW_TRACK, Pair, assert_keylines_equal, assert_pipeline_bit_identical, bits_equal, record_words, run_stream,
-                     set_forms, vision_only_fusion, words)
+from support import (FORMS, KW_TRACK, Pair, assert_keylines_equal, assert_pipeline_bit_identical, bits_equal, oracle_fusion, record_words,
+                     run_stream, set_forms, vision_only_fusion, words)
 
 pytestmark = pytest.mark.gpu
 
@@ -196,17 +196,6 @@ def test_sparse_maps_next_to_full_ones(orc_mod, B, small_stream, monkeypatch, na
     assert_pipeline_bit_identical(orc_mod, B, seq, cam, np.arange(len(seq)), KW_TRACK, 0, name, expect_status=status)
 
 
-def _oracle_fusion(orc_mod, po):
-    """What the oracle's own glue hands to the second half of the pair (rebvio.cpp:195-203, 225-233): V, P_V, the corrected
-    rotation and R0 = SO3::exp of the rotational part of Xgv - the inputs of rebvio_hip_track_pair_finish_async."""
-    import ctypes as C
-    w = np.array(po.Xgv, np.float32)[3:].copy()
-    R0 = np.zeros(9, np.float32)
-    fp = C.POINTER(C.c_float)
-    orc_mod.lib().orc_so3_exp(w.ctypes.data_as(fp), R0.ctypes.data_as(fp))
-    return np.array(po.V, np.float32), np.array(po.P_V, np.float32), np.array(po.R, np.float32), R0
-
-
 def _guarded_vision_only_fusion(mid):
     """vision_only_fusion where it is defined; a pair without a velocity or with a singular information matrix hands NaN on
     (status 1: the second half is skipped), the same in every call order."""
@@ -256,7 +245,7 @@ def test_sparse_maps_through_the_split_api(orc_mod, B, small_stream, monkeypatch
     set_forms(monkeypatch)
     seq, cam, status, recs, last = cut_case(orc_mod, small_stream, name)
     for overlapped in (False, True):
-        mids, res, kl = _split_run(B, cam, seq, lambda k, mid: _oracle_fusion(orc_mod, recs[k]), overlapped)
+        mids, res, kl = _split_run(B, cam, seq, lambda k, mid: oracle_fusion(orc_mod, recs[k]), overlapped)
         for k, (mid, po) in enumerate(zip(mids, recs)):
             for f in MID_FIELDS:
                 assert np.array_equal(words(getattr(mid, f)), words(getattr(po, f))), (name, overlapped, k, f)

@@ -13,7 +13,8 @@ import pytest
 
 from conftest import params_for
 from support import B  # noqa: F401
-from support import TS, gyro_rotations, rec, record_words, rodrigues, same_records, set_forms, state_words
+from support import (TS, gyro_rotations, lib_pairs, lib_stream, oracle_pairs, rec, record_words, rodrigues, same_records, set_forms,
+                     state_words)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,74 +22,6 @@ STREAMS = {                      # fixture, ping-pong order (base, total), the o
     "small": ("small_stream", (12, 16), 2321),
     "c2": ("c2_stream", (8, 13), 9726),
 }
-
-
-# ---- the three runners: oracle, per-pair API, streaming driver ----------------------------------------------------------------
-def oracle_pairs(orc_mod, cam, seq, R, **kw):
-    """seq[] through the CPU oracle alone, keyline sums in the kernels' order; R = None: no priors. (records, keyline counts)"""
-    orc = orc_mod.Oracle(params_for(orc_mod, cam, **kw))
-    orc.set_sum_order("device")
-    recs, prev = [], None
-    for k, f in enumerate(seq):
-        m = orc.detect_u8(f, k * TS)
-        if prev is not None:
-            recs.append((orc.track_pair(prev, m, R_prior=None if R is None else R[k]), m.size()))
-        prev = m
-    return recs
-
-
-def lib_pairs(B, cam, seq, R, mask=None, **kw):
-    """per-pair API: detect (+ per-frame mask) and rebvio_hip_track_pair(R_prior = R[k]); (records as words, gyro state)"""
-    ctx = B.Context(params_for(B, cam, **kw))
-    npx = cam.width * cam.height
-    dev = ctx.upload_frames(seq)
-    mdev = ctx.upload_frames(mask[None]) if mask is not None else None
-    maps, recs = [], []
-    for k in range(len(seq)):
-        if mdev is None:
-            maps.append(ctx.detect_u8_device(dev + k * npx, k * TS))
-        else:
-            maps.append(ctx.detect_px_masked_device(dev + k * npx, B.PX_GRAY8, mdev, k * TS))
-        if len(maps) > 2:
-            maps.pop(0).release()
-        if k:
-            recs.append(rec(ctx.track_pair(maps[0], maps[1], R_prior=R[k]), maps[1].size()))
-    st = ctx.gyro_state()
-    ctx.close()
-    return recs, state_words(st)
-
-
-def lib_stream(B, cam, seq, R, mask=None, host=False, flush_after=(), entry="gyro", profile=False, **kw):
-    """streaming driver: seq[k] pushed with R[k] (None: NULL) through the gyro entries (entry = "u8": the existing
-    push_frame_u8_device, R unused); flush_after: frame counts after which rebvio_hip_flush is called mid-stream.
-    (records as words, gyro state after the closing flush[, kernel launches counted by the profiler])"""
-    ctx = B.Context(params_for(B, cam, **kw))
-    npx = cam.width * cam.height
-    dev = ctx.upload_frames(seq)
-    mdev = ctx.upload_frames(mask[None]) if mask is not None else None
-    if profile:
-        ctx.profile_reset()
-        ctx.profile(True)
-    recs = []
-    for k in range(len(seq)):
-        if entry == "u8":
-            out, n = ctx.push_frame_u8_device(dev + k * npx, k * TS)
-        elif host:
-            out, n = ctx.push_frame_px_gyro(np.ascontiguousarray(seq[k]), B.PX_GRAY8, R[k], k * TS)
-        else:
-            out, n = ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, R[k], mdev, k * TS)
-        if out.status >= 0:
-            recs.append(rec(out, n))
-        if k + 1 in flush_after:
-            recs.extend(rec(o, n) for o, n in ctx.flush())
-    recs.extend(rec(o, n) for o, n in ctx.flush())
-    st = state_words(ctx.gyro_state())
-    launches = None
-    if profile:
-        launches = {name: calls for name, (_, calls) in ctx.profile_read().items()}
-        ctx.profile(False)
-    ctx.close()
-    return (recs, st, launches) if profile else (recs, st)
 
 
 _cache = {}

@@ -11,8 +11,8 @@ import pytest
 
 from conftest import params_for
 from support import B  # noqa: F401
-from support import (KW_TRACK, RHO_MAX, RHO_MIN, Pair, assert_keylines_equal, assert_pipeline_bit_identical, f32, matching_stage,
-                     record_words, run_stream, set_forms, set_new_map)
+from support import (KW_TRACK, RHO_MAX, RHO_MIN, Pair, assert_keylines_equal, assert_keylines_equal_nan, assert_pipeline_bit_identical, f32,
+                     matching_stage, record_words, run_stream, set_forms, set_new_map)
 
 pytestmark = pytest.mark.gpu
 
@@ -44,20 +44,6 @@ def rotate_inputs(vel, Rvel, Rb):
 
 def small_rotation(a=0.0007):
     return np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]], np.float32)
-
-
-def nan_canonical(kl):
-    """keylines with every NaN of a float field replaced by the one quiet NaN (as record_words does for records)"""
-    kl = kl.copy()
-    for f in kl.dtype.names:
-        if kl.dtype[f].base.kind == "f":
-            a = kl[f]
-            a[np.isnan(a)] = np.float32(np.nan)
-    return kl
-
-
-def assert_keylines_equal_nan(ko, kg, what=""):
-    assert_keylines_equal(nan_canonical(ko), nan_canonical(kg), what=what)
 
 
 # ---- 1. long searches ------------------------------------------------------------------------------------------------
