@@ -4,6 +4,7 @@
 // nobody pays a device->host copy unless they look.
 #pragma once
 
+#include <array>
 #include <memory>
 #include <unordered_map>
 #include <vector>
@@ -120,6 +121,22 @@ class EdgeMap {
   // exactly which keylines and where; the synchronous form: it waits for everything queued that concerns this map)
   std::vector<rebvio::types::CloudPoint> pointCloud(const rebvio::types::CloudFilter& filter = rebvio::types::CloudFilter(),
                                                     const rebvio::types::CloudPose& pose = rebvio::types::CloudPose());
+  // addition: the map's joined keylines as ordered edge chains and as 3D polylines (rebvio_hip_map_edge_chains /
+  // rebvio_hip_map_edge_polylines define them; synchronous, from the tracking thread, like pointCloud). edgeChains: one record per
+  // keyline, the keylines in chain order and the chains' first slots (starts.size() = chains + 1). edgePolylines: the kept slots as
+  // points in slot order, {head, rank} per point, and one record per line.
+  struct EdgeChains {
+    std::vector<rebvio::types::ChainRef> refs;
+    std::vector<int> order, starts;
+  };
+  struct EdgePolylines {
+    std::vector<rebvio::types::CloudPoint> points;
+    std::vector<std::array<int, 2>> refs;
+    std::vector<rebvio::types::Polyline> lines;
+  };
+  EdgeChains edgeChains();
+  EdgePolylines edgePolylines(const rebvio::types::PolylineOpts& opts = rebvio::types::PolylineOpts(),
+                              const rebvio::types::CloudPose& pose = rebvio::types::CloudPose());
   // addition: keyframes (rebvio_hip.h "Keyframes"). markKeyframe makes this map the keyframe: match_id_keyframe[i] = i for every
   // keyline, queued on the track stream - call it after the map has been a pair's new map and before it serves as an old map.
   // keyframeMatches(kf_size): which keylines of a keyframe of kf_size keylines live on in this map, in ascending kf_keyline

@@ -104,6 +104,18 @@ struct PlyVertex {
   float x, y, z, intensity;
 };
 std::vector<PlyVertex> readPointCloudPly(const std::string& path, uint64_t* ts_us = nullptr);
+// Polylines (EdgeMap::edgePolylines) as a PLY file of the same format: the cloud's vertex element, one vertex per point in slot
+// order, then `element edge` with the int properties vertex1, vertex2 - one edge per consecutive pair of points of a line, and the
+// closing edge (last point, first point) of a closed line. Lines that reach past `n` points (a capped extraction) are cut there and
+// not closed. Throws std::runtime_error when the file cannot be written.
+void writePolylinesPly(const std::string& path, const rebvio::types::CloudPoint* points, size_t n, const rebvio::types::Polyline* lines,
+                       size_t n_lines, uint64_t ts_us = 0);
+// Reads such a file back: the vertices as readPointCloudPly returns them, and the edges. Accepts what writePolylinesPly writes,
+// nothing else (an edge that names a vertex outside the file is refused). Throws std::runtime_error.
+struct PlyEdge {
+  int vertex1, vertex2;
+};
+std::vector<PlyVertex> readPolylinesPly(const std::string& path, std::vector<PlyEdge>* edges, uint64_t* ts_us = nullptr);
 
 // Plays frames [first, first+count) in time order: every IMU sample with ts <= the frame's stamp is delivered before the
 // frame (a time-ordered bag delivers them that way, ros_rebvio.cpp:108-121). Returns the number of frames delivered.

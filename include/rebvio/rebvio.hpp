@@ -49,6 +49,15 @@ class Rebvio {
   // (one launch more per pair); the odometry does not change by a digit. Register before the first frame is handed in.
   void registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb,
                                   rebvio::types::CloudFilter filter = rebvio::types::CloudFilter());
+  // addition: the joined keylines of every published pair's new map as ordered 3D polylines (EdgeMap::edgePolylines;
+  // rebvio_hip_map_edge_polylines defines a line), metric and in the odometry's frame with the pose of a point-cloud callback.
+  // Called once per published odometry record, behind the point-cloud callbacks, on the state-estimation thread; the arrays are
+  // valid during the call. The extraction is synchronous: the thread runs it behind the previous record's callbacks and waits for
+  // this pair's second half there. As with a point-cloud callback the next pair's first rotation is then not fused into this
+  // pair's last kernel; the odometry does not change by a digit. Without one the thread runs exactly the calls it ran. Register
+  // before the first frame is handed in.
+  void registerEdgePolylineCallback(std::function<void(const rebvio::types::EdgePolylines&)> cb,
+                                    rebvio::types::PolylineOpts opts = rebvio::types::PolylineOpts());
   // addition: keyframes (rebvio_hip.h "Keyframes"). requestKeyframe: the newest tracked map becomes the keyframe - it is marked
   // (EdgeMap::markKeyframe) behind the second half of the pair being tracked when the request is seen, in front of the next pair's
   // first half; callable from any thread. The keyframe callback is called once per published odometry record, right after the
@@ -160,6 +169,11 @@ class Rebvio {
   };
   std::vector<PointCloudCallback> point_cloud_callbacks_;
   std::vector<PointCloudCallback> keyframe_cloud_callbacks_;
+  struct EdgePolylineCallback {
+    std::function<void(const rebvio::types::EdgePolylines&)> cb;
+    rebvio::types::PolylineOpts opts;
+  };
+  std::vector<EdgePolylineCallback> edge_polyline_callbacks_;
   std::vector<std::function<void(uint64_t, int, int)>> keyframe_callbacks_;
   std::vector<std::function<void(uint64_t, const rebvio::types::KfPose&)>> keyframe_pose_callbacks_;
   std::atomic<bool> keyframe_requested_{false};

@@ -151,12 +151,46 @@ struct KfHandover {
 };
 static_assert(sizeof(KfHandover) == 28, "KfHandover must stay layout-compatible with rebvio_hip_kf_handover");
 
+// Edge chains and polylines of a map (EdgeMap::edgeChains / edgePolylines), layout-compatible with the C-ABI's rebvio_hip_chain_ref,
+// rebvio_hip_polyline_opts and rebvio_hip_polyline; rebvio_hip.h defines succ / pred, head, rank, the chain table and a line exactly.
+struct ChainRef {
+  int head;    // a path's member without a predecessor; a cycle's smallest member index
+  int rank;    // succ steps from head
+  int length;  // members of the chain
+  int flags;   // bit 0: the chain is cyclic
+};
+static_assert(sizeof(ChainRef) == 16, "ChainRef must stay layout-compatible with rebvio_hip_chain_ref");
+struct PolylineOpts {
+  CloudFilter filter;       // the cloud filter, applied per keyline
+  int min_chain_length{8};  // >= 1: chains with fewer members give no line
+  int reserved{0};
+};
+static_assert(sizeof(PolylineOpts) == 24, "PolylineOpts must stay layout-compatible with rebvio_hip_polyline_opts");
+struct Polyline {
+  int first_point;  // index of the line's first point in EdgePolylines::points
+  int points;       // its number of points, consecutive along the edge
+  int head;         // head of its chain
+  int flags;        // bit 0: closed (the chain is cyclic and the line is all of it)
+};
+static_assert(sizeof(Polyline) == 16, "Polyline must stay layout-compatible with rebvio_hip_polyline");
+
 // What a point-cloud or keyframe-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
   uint64_t ts_us;            // the odometry record's stamp (= the map's); keyframe cloud: the stamp of the record the keyframe was marked on
   CloudPose pose;            // R_global, Pos, K of that record: the points are metric, in the odometry's frame
   const CloudPoint* points;
   size_t size;
+};
+
+// What an edge-polyline callback of rebvio::Rebvio receives; the arrays are valid during the callback only.
+struct EdgePolylines {
+  uint64_t ts_us;            // the odometry record's stamp (= the map's)
+  CloudPose pose;            // R_global, Pos, K of that record: the points are metric, in the odometry's frame
+  const CloudPoint* points;  // in slot order: the points of a line are consecutive, ordered along the edge
+  const int* refs;           // {head, rank} per point, two ints each
+  size_t size;
+  const Polyline* lines;
+  size_t num_lines;
 };
 
 }  // namespace types

@@ -38,7 +38,10 @@ extern "C" {
  *    batched alignment rebvio_hip_map_keyframe_align_many, its structs rebvio_hip_kf_hypothesis / rebvio_hip_kf_hyp_result, the host
  *    helpers rebvio_hip_kf_align_best / rebvio_hip_kf_hypotheses_around and the test hook rebvio_hip_test_kf_align_many_host; the depth
  *    hand-over rebvio_hip_default_kf_handover_opts, rebvio_hip_kf_snapshot_handover_depth, their structs rebvio_hip_kf_handover_opts /
- *    rebvio_hip_kf_handover and the test hook rebvio_hip_test_kf_handover_host. */
+ *    rebvio_hip_kf_handover and the test hook rebvio_hip_test_kf_handover_host; the edge chains and polylines
+ *    rebvio_hip_map_edge_chains, rebvio_hip_default_polyline_opts, rebvio_hip_map_edge_polylines, their structs rebvio_hip_chain_ref /
+ *    rebvio_hip_polyline_opts / rebvio_hip_polyline and the test hooks rebvio_hip_test_edge_chains_host /
+ *    rebvio_hip_test_edge_polylines_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -280,6 +283,69 @@ int rebvio_hip_map_point_cloud_async(rebvio_hip_ctx* ctx, rebvio_hip_map* map, c
                                      const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud** out);
 int rebvio_hip_cloud_wait(rebvio_hip_cloud* cloud, const rebvio_hip_cloud_point** points, int* count, const void** device_points);
 void rebvio_hip_cloud_release(rebvio_hip_cloud* cloud);
+
+/* Edge chains. joinEdges links every keyline to its neighbours along the edge (id_prev / id_next, edge_detector.cpp:125-165), but the
+ * links are not a clean list: id_next is many-to-one, id_prev keeps one claimant, closed contours exist, and an uploaded map
+ * (rebvio_hip_map_upload) may hold any integers in the two fields. With n the map's size:
+ *   succ(i) = id_next[i] when 0 <= id_next[i] < n, id_next[i] != i and id_prev[id_next[i]] == i; otherwise succ(i) = -1.
+ *   pred(j) = the unique i with succ(i) == j, otherwise -1.
+ * The components of succ are simple paths and simple cycles; no out-of-range value is ever used as an index. One record per keyline:
+ *   head    for a path the member with pred == -1; for a cycle the smallest member index
+ *   rank    the number of succ steps from head
+ *   length  the number of members
+ *   flags   bit 0: the chain is cyclic
+ * Chain table: chains are numbered c = 0..C-1 by ascending head; starts[c] = the sum of the lengths in front of chain c,
+ * starts[C] = n; order[starts[c] + rank] = keyline; order is a permutation of 0..n-1.
+ * rebvio_hip_map_edge_chains: *n_keylines = n, *n_chains = C (either may be NULL); min(n, cap_keylines) records of refs_host and of
+ * order_host and min(C + 1, cap_chains) entries of starts_host are written (cap_chains counts the ints of starts_host; any output
+ * pointer may be NULL, a cap below the count is no error). -3: null map, a negative cap.
+ * Synchronous and track-side, exactly as rebvio_hip_map_point_cloud: the track stream, its state rule, -7 for a map promised to
+ * R_prior_next, -10 after rebvio_hip_destroy (the chains read only the two link fields, which tracking never writes; the rules are
+ * kept the same for simplicity). Everything is integer work and reproducible bit for bit.
+ * Launches, fixed per context whatever n and the links are (an empty map launches the same): with R = ceil(log2(keylines_max))
+ *   rebvio_hip_map_edge_chains     1 k_chain_link + R k_chain_round + k_chain_rank + k_chain_count + k_chain_emit + k_chain_order = R + 5
+ *   rebvio_hip_map_edge_polylines  the same R + 5, then k_poly_count + k_poly_emit + k_poly_lines                                 = R + 8
+ * No workgroup waits for another inside a kernel; every dependency is a kernel boundary; sizes are read on the device. Scratch is one
+ * allocation per context, made at the first call of either entry that reaches the device (about 124 bytes per keylines_max). */
+typedef struct rebvio_hip_chain_ref { /* 16 bytes */
+  int head, rank, length, flags;
+} rebvio_hip_chain_ref;
+int rebvio_hip_map_edge_chains(rebvio_hip_map* map, rebvio_hip_chain_ref* refs_host, int cap_keylines, int* order_host, int* starts_host,
+                               int cap_chains, int* n_keylines, int* n_chains);
+/* Polylines: the chains as ordered 3D curves. Slot s = starts[c] + rank is kept when its keyline passes the cloud filter (the test of
+ * rebvio_hip_map_point_cloud, bit for bit) and its chain's length >= min_chain_length. A line is a maximal run of kept, consecutive
+ * slots of one chain; a run never wraps from a cyclic chain's last rank to rank 0. Points come out in slot order as
+ * rebvio_hip_cloud_point, with the formula, operation order and `keyline` field of a map's cloud: a point is byte-identical to that
+ * keyline's record from rebvio_hip_map_point_cloud under the same filter and pose. refs2_host (may be NULL) takes {head, rank} per
+ * point, two ints each. One record per line; first_point indexes the full sequence of points (cap_points does not shift it); bit 0 of
+ * flags is "closed": the chain is cyclic and the line is all of it.
+ * *n_points / *n_lines = all of them; min(n_points, cap_points) points and min(n_lines, cap_lines) lines are written. opts NULL = the
+ * defaults (the default cloud filter, min_chain_length 8); pose NULL = identity. -3, before the device is touched: null map, n_points
+ * or n_lines, min_chain_length < 1, an invalid filter, a NaN in the pose, a negative cap, null points_host with cap_points > 0, null
+ * lines_host with cap_lines > 0. Otherwise the rules of rebvio_hip_map_edge_chains (and the "State" rule of the cloud: -7). */
+typedef struct rebvio_hip_polyline_opts {
+  rebvio_hip_cloud_filter filter;
+  int min_chain_length;
+  int reserved;
+} rebvio_hip_polyline_opts;
+typedef struct rebvio_hip_polyline { /* 16 bytes */
+  int first_point; /* index of the line's first point */
+  int points;      /* its number of points */
+  int head;        /* head of its chain */
+  int flags;       /* bit 0: closed */
+} rebvio_hip_polyline;
+void rebvio_hip_default_polyline_opts(rebvio_hip_polyline_opts* o);
+int rebvio_hip_map_edge_polylines(rebvio_hip_map* map, const rebvio_hip_polyline_opts* opts, const rebvio_hip_cloud_pose* pose,
+                                  rebvio_hip_cloud_point* points_host, int* refs2_host, int cap_points, rebvio_hip_polyline* lines_host,
+                                  int cap_lines, int* n_points, int* n_lines);
+/* Test hooks: the same per-step statements on the host (rebvio_amd/csrc/edge_chains.hpp), from plain arrays, no device. The
+ * arguments and results of the two entries above, with id_prev / id_next (n ints each) or n keylines in place of the map, and fm in
+ * place of the context's. -3 as there, and for a negative n or a null input with n > 0. */
+int rebvio_hip_test_edge_chains_host(const int* id_prev, const int* id_next, int n, rebvio_hip_chain_ref* refs, int cap_keylines,
+                                     int* order, int* starts, int cap_chains, int* n_keylines, int* n_chains);
+int rebvio_hip_test_edge_polylines_host(float fm, const rebvio_hip_keyline* keylines, int n, const rebvio_hip_polyline_opts* opts,
+                                        const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud_point* points, int* refs2, int cap_points,
+                                        rebvio_hip_polyline* lines, int cap_lines, int* n_points, int* n_lines);
 
 /* Keyframes. Every keyline carries match_id_keyframe, "ID of the matching keyline in the last keyframe" (types/keyline.hpp:39):
  * forwardMatch and directedMatch copy it from the matched keyline of the old map (edge_map.cpp:93,210) and directedMatch counts the

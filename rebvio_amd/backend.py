@@ -32,6 +32,14 @@ KF_MATCH_DTYPE = np.dtype([("kf_keyline", "<i4"), ("keyline", "<i4"), ("claimant
                            ("sigma_rho", "<f4"), ("pos_img", "<f4", (2,))])
 assert KF_MATCH_DTYPE.itemsize == 32
 
+# rebvio_hip_chain_ref: one keyline's place in its edge chain (Map.edge_chains)
+CHAIN_REF_DTYPE = np.dtype([("head", "<i4"), ("rank", "<i4"), ("length", "<i4"), ("flags", "<i4")])
+assert CHAIN_REF_DTYPE.itemsize == 16
+
+# rebvio_hip_polyline: one line of Map.edge_polylines; bit 0 of flags = closed
+POLYLINE_DTYPE = np.dtype([("first_point", "<i4"), ("points", "<i4"), ("head", "<i4"), ("flags", "<i4")])
+assert POLYLINE_DTYPE.itemsize == 16
+
 
 class Params(C.Structure):
     _fields_ = [
@@ -69,6 +77,11 @@ class CloudFilter(C.Structure):
 
 class CloudPose(C.Structure):
     _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("scale", C.c_float)]
+
+
+class PolylineOpts(C.Structure):
+    """rebvio_hip_polyline_opts (Map.edge_polylines); defaults from default_polyline_opts"""
+    _fields_ = [("filter", CloudFilter), ("min_chain_length", C.c_int), ("reserved", C.c_int)]
 
 
 class KfMatch(C.Structure):
@@ -163,6 +176,13 @@ SIGNATURES = {
     "rebvio_hip_map_point_cloud_async": (C.c_int, [_vp, _vp, C.POINTER(CloudFilter), C.POINTER(CloudPose), C.POINTER(_vp)]),
     "rebvio_hip_cloud_wait": (C.c_int, [_vp, C.POINTER(_vp), _ip, C.POINTER(_vp)]),
     "rebvio_hip_cloud_release": (None, [_vp]),
+    "rebvio_hip_map_edge_chains": (C.c_int, [_vp, _vp, C.c_int, _ip, _ip, C.c_int, _ip, _ip]),
+    "rebvio_hip_default_polyline_opts": (None, [C.POINTER(PolylineOpts)]),
+    "rebvio_hip_map_edge_polylines": (C.c_int, [_vp, C.POINTER(PolylineOpts), C.POINTER(CloudPose), _vp, _ip, C.c_int, _vp, C.c_int, _ip,
+                                                _ip]),
+    "rebvio_hip_test_edge_chains_host": (C.c_int, [_ip, _ip, C.c_int, _vp, C.c_int, _ip, _ip, C.c_int, _ip, _ip]),
+    "rebvio_hip_test_edge_polylines_host": (C.c_int, [C.c_float, _vp, C.c_int, C.POINTER(PolylineOpts), C.POINTER(CloudPose), _vp, _ip,
+                                                      C.c_int, _vp, C.c_int, _ip, _ip]),
     "rebvio_hip_map_mark_keyframe": (C.c_int, [_vp, _vp]),
     "rebvio_hip_map_keyframe_matches": (C.c_int, [_vp, C.c_int, C.POINTER(KfMatch), C.c_int, _ip]),
     "rebvio_hip_map_keyframe_snapshot": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -405,6 +425,56 @@ def _cloud_pose(pose):
     if pose is None or isinstance(pose, CloudPose):
         return pose
     return cloud_pose(*pose)
+
+
+def default_polyline_opts(**over) -> PolylineOpts:
+    """The library's defaults (rebvio_hip_default_polyline_opts): the default cloud filter, min_chain_length 8; filter takes a
+    CloudFilter or a dict of its fields to change."""
+    o = PolylineOpts()
+    lib().rebvio_hip_default_polyline_opts(C.byref(o))
+    for k, v in over.items():
+        if k == "filter" and not isinstance(v, CloudFilter):
+            for fk, fv in v.items():
+                setattr(o.filter, fk, fv)
+        else:
+            setattr(o, k, v)
+    return o
+
+
+def edge_chains_host(id_prev, id_next, cap_keylines=None, cap_chains=None):
+    """Map.edge_chains on the host, from the two link arrays (rebvio_hip_test_edge_chains_host). Touches no device. Returns (refs
+    CHAIN_REF_DTYPE, order int32, starts int32, n_keylines, n_chains), the arrays cut to what the caps let through."""
+    idp = np.ascontiguousarray(id_prev, np.int32).reshape(-1)
+    idn = np.ascontiguousarray(id_next, np.int32).reshape(-1)
+    assert len(idp) == len(idn)
+    n = len(idp)
+    ck = n if cap_keylines is None else cap_keylines
+    cc = n + 1 if cap_chains is None else cap_chains
+    refs, order, starts = np.zeros(max(ck, 0), CHAIN_REF_DTYPE), np.zeros(max(ck, 0), np.int32), np.zeros(max(cc, 0), np.int32)
+    nk, nc = C.c_int(), C.c_int()
+    _chk(lib().rebvio_hip_test_edge_chains_host(idp.ctypes.data_as(_ip) if n else None, idn.ctypes.data_as(_ip) if n else None, n,
+                                                refs.ctypes.data if len(refs) else None, ck, order.ctypes.data_as(_ip) if len(order) else None,
+                                                starts.ctypes.data_as(_ip) if len(starts) else None, cc, C.byref(nk), C.byref(nc)))
+    return refs[:min(nk.value, ck)], order[:min(nk.value, ck)], starts[:min(nc.value + 1, cc)], nk.value, nc.value
+
+
+def _polylines_call(fn, head_args, n_hint, opts, pose, cap_points, cap_lines):
+    cp = n_hint if cap_points is None else cap_points
+    cl = n_hint if cap_lines is None else cap_lines
+    pts, refs2 = np.zeros(max(cp, 0), CLOUD_POINT_DTYPE), np.zeros((max(cp, 0), 2), np.int32)
+    lines = np.zeros(max(cl, 0), POLYLINE_DTYPE)
+    npts, nl = C.c_int(), C.c_int()
+    _chk(fn(*head_args, opts, _cloud_pose(pose), pts.ctypes.data if len(pts) else None, refs2.ctypes.data_as(_ip) if len(pts) else None, cp,
+            lines.ctypes.data if len(lines) else None, cl, C.byref(npts), C.byref(nl)))
+    return pts[:min(npts.value, cp)], refs2[:min(npts.value, cp)], lines[:min(nl.value, cl)], npts.value, nl.value
+
+
+def edge_polylines_host(fm, keylines, opts=None, pose=None, cap_points=None, cap_lines=None):
+    """Map.edge_polylines on the host, from a KEYLINE_DTYPE array (rebvio_hip_test_edge_polylines_host). Touches no device. Returns
+    (points CLOUD_POINT_DTYPE, refs2 int32 [k, 2] = head, rank, lines POLYLINE_DTYPE, n_points, n_lines)."""
+    kl = np.ascontiguousarray(keylines, KEYLINE_DTYPE)
+    return _polylines_call(lib().rebvio_hip_test_edge_polylines_host, (float(fm), kl.ctypes.data if len(kl) else None, len(kl)), len(kl),
+                           opts, pose, cap_points, cap_lines)
 
 
 def default_kf_pose_opts(**over) -> KfPoseOpts:
@@ -871,6 +941,26 @@ class Map:
                                               cap, C.byref(n)))
         out = out[:min(n.value, cap)]
         return (out, n.value) if return_count else out
+
+    def edge_chains(self, cap_keylines=None, cap_chains=None):
+        """Every keyline's edge chain and the chain table (rebvio_hip_map_edge_chains; include/rebvio_hip.h is the definition).
+        Returns (refs CHAIN_REF_DTYPE, order int32, starts int32, n_keylines, n_chains); the caps (default: everything) cut the
+        arrays, never the counts."""
+        n = self.ctx.p.keylines_max
+        ck = n if cap_keylines is None else cap_keylines
+        cc = n + 1 if cap_chains is None else cap_chains
+        refs, order, starts = np.zeros(max(ck, 0), CHAIN_REF_DTYPE), np.zeros(max(ck, 0), np.int32), np.zeros(max(cc, 0), np.int32)
+        nk, nc = C.c_int(), C.c_int()
+        _chk(lib().rebvio_hip_map_edge_chains(self.h, refs.ctypes.data if len(refs) else None, ck,
+                                              order.ctypes.data_as(_ip) if len(order) else None,
+                                              starts.ctypes.data_as(_ip) if len(starts) else None, cc, C.byref(nk), C.byref(nc)))
+        return refs[:min(nk.value, ck)], order[:min(nk.value, ck)], starts[:min(nc.value + 1, cc)], nk.value, nc.value
+
+    def edge_polylines(self, opts=None, pose=None, cap_points=None, cap_lines=None):
+        """The map's edge chains as ordered 3D polylines (rebvio_hip_map_edge_polylines). opts: a PolylineOpts or None for the
+        defaults; pose: see _cloud_pose. Returns (points CLOUD_POINT_DTYPE in slot order, refs2 int32 [k, 2] = head, rank per point,
+        lines POLYLINE_DTYPE, n_points, n_lines); the caps (default: everything) cut the arrays, never the counts."""
+        return _polylines_call(lib().rebvio_hip_map_edge_polylines, (self.h,), self.ctx.p.keylines_max, opts, pose, cap_points, cap_lines)
 
     def mark_keyframe(self):
         """Makes this map the keyframe: match_id_keyframe[i] = i for every keyline (rebvio_hip_map_mark_keyframe; queued on the track

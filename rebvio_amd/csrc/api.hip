@@ -23,6 +23,7 @@
 #include "glue.hpp"
 #include "hostmath.hpp"
 #include "kf_cloud.hpp"
+#include "edge_chains.hpp"
 #include "kf_handover.hpp"
 #include "kf_many.hpp"
 #include "kf_pose.hpp"
@@ -564,6 +565,9 @@ struct rebvio_hip_ctx {
   void* kfh_stage = nullptr;  // (views into kfh_key's allocation)
   int* kfh_cnt = nullptr;
   int* kfh_assoc = nullptr;
+  // scratch of rebvio_hip_map_edge_chains / _edge_polylines (ONE allocation on first use, kept; track-side entries): views into it
+  char* ech_buf = nullptr;
+  ChainDev ech{};
 };
 
 namespace {
@@ -2872,6 +2876,190 @@ int rebvio_hip_test_kf_handover_host(float fm, float cx, float cy, int rows, int
   if (assoc)
     for (int j = 0; j < kf_size; ++j) assoc[j] = as[(size_t)j];
   *out = res;
+  return 0;
+}
+
+}  // extern "C"
+
+namespace {
+static_assert(sizeof(rebvio_hip_chain_ref) == 16 && sizeof(rebvio_hip_polyline) == 16 && sizeof(ech::ChainNode) == 16,
+              "16-byte records: one load, one store");
+static_assert(sizeof(rebvio_hip_polyline_opts) == 24, "filter, two ints");
+
+// Scratch of the edge chains and polylines, allocated at the first call that reaches the device
+int ech_scratch(rebvio_hip_ctx* c) {
+  if (c->ech_buf) return 0;
+  const size_t kp = (size_t)div_up(c->P.keylines_max, 256) * 256;
+  // 16-byte records first, then the 8-byte ones, then the ints
+  const size_t bytes = kp * (2 * sizeof(ech::ChainNode) + sizeof(rebvio_hip_chain_ref) + sizeof(rebvio_hip_cloud_point) +
+                             sizeof(rebvio_hip_polyline) + sizeof(int2) + 4 * sizeof(int)) +
+                       (kp + 4 + 4 * (size_t)kMaxRecBlocks + kChainWords) * sizeof(int);
+  HIPCHK(c->own.device_bytes(&c->ech_buf, bytes));
+  char* b = c->ech_buf;
+  ChainDev& d = c->ech;
+  d.node[0] = b; b += kp * sizeof(ech::ChainNode);
+  d.node[1] = b; b += kp * sizeof(ech::ChainNode);
+  d.refs = reinterpret_cast<rebvio_hip_chain_ref*>(b); b += kp * sizeof(rebvio_hip_chain_ref);
+  d.points = b; b += kp * sizeof(rebvio_hip_cloud_point);
+  d.lines = reinterpret_cast<rebvio_hip_polyline*>(b); b += kp * sizeof(rebvio_hip_polyline);
+  d.refs2 = reinterpret_cast<int2*>(b); b += kp * sizeof(int2);
+  d.succ = reinterpret_cast<int*>(b); b += kp * sizeof(int);
+  d.len = reinterpret_cast<int*>(b); b += kp * sizeof(int);
+  d.start_of = reinterpret_cast<int*>(b); b += kp * sizeof(int);
+  d.order = reinterpret_cast<int*>(b); b += kp * sizeof(int);
+  d.starts = reinterpret_cast<int*>(b); b += (kp + 4) * sizeof(int);
+  d.blk = reinterpret_cast<int*>(b); b += 4 * (size_t)kMaxRecBlocks * sizeof(int);
+  d.words = reinterpret_cast<int*>(b);
+  return 0;
+}
+
+// What both entries do up to their launches: the state rule, the scratch, the waits. The caller holds the map's life block.
+int ech_begin(const char* who, rebvio_hip_map* m) {
+  rebvio_hip_ctx* c = m->ctx;
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg((std::string(who) + ": the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
+                     "it is available again once the next track_pair_begin has run").c_str(), -7);
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = ech_scratch(c);
+  if (rc) return rc;
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  return 0;
+}
+
+int check_polyline_args(const char* who, const rebvio_hip_polyline_opts* o, const rebvio_hip_cloud_pose* pose, const void* points,
+                        int cap_points, const void* lines, int cap_lines, const int* n_points, const int* n_lines) {
+  if (!n_points || !n_lines) return fail_msg((std::string(who) + ": null n_points or n_lines").c_str(), -3);
+  if (cap_points < 0 || (cap_points > 0 && !points))
+    return fail_msg((std::string(who) + ": cap_points records need a points buffer (cap_points >= 0)").c_str(), -3);
+  if (cap_lines < 0 || (cap_lines > 0 && !lines))
+    return fail_msg((std::string(who) + ": cap_lines records need a lines buffer (cap_lines >= 0)").c_str(), -3);
+  if (o && o->min_chain_length < 1) return fail_msg((std::string(who) + ": min_chain_length must be >= 1").c_str(), -3);
+  return check_cloud_args(who, o ? &o->filter : nullptr, pose);
+}
+}  // namespace
+
+extern "C" {
+
+int rebvio_hip_map_edge_chains(rebvio_hip_map* m, rebvio_hip_chain_ref* refs_host, int cap_keylines, int* order_host, int* starts_host,
+                               int cap_chains, int* n_keylines, int* n_chains) {
+  if (!m) return fail_msg("map_edge_chains: null map", -3);
+  if (cap_keylines < 0 || cap_chains < 0) return fail_msg("map_edge_chains: negative cap", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = m->ctx;
+  if (n_keylines) *n_keylines = 0;
+  if (n_chains) *n_chains = 0;
+  int rc = ech_begin("map_edge_chains", m);
+  if (rc) return rc;
+  launch_edge_chains(c->s_trk, c->K, m->d, c->ech, ech::chain_rounds(c->P.keylines_max));
+  HIPCHK(hipGetLastError());
+  // the counts first; then copies of exactly what exists
+  int w[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(w, c->ech.words, sizeof(w), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  const int n = w[0], nc = w[1];
+  const size_t kn = (size_t)(n < cap_keylines ? n : cap_keylines), ks = (size_t)(nc + 1 < cap_chains ? nc + 1 : cap_chains);
+  if (refs_host && kn) HIPCHK(hipMemcpyAsync(refs_host, c->ech.refs, kn * sizeof(rebvio_hip_chain_ref), hipMemcpyDeviceToHost, c->s_trk));
+  if (order_host && kn) HIPCHK(hipMemcpyAsync(order_host, c->ech.order, kn * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  if (starts_host && ks) HIPCHK(hipMemcpyAsync(starts_host, c->ech.starts, ks * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  if (n_keylines) *n_keylines = n;
+  if (n_chains) *n_chains = nc;
+  return 0;
+}
+
+void rebvio_hip_default_polyline_opts(rebvio_hip_polyline_opts* o) {
+  rebvio_hip_default_cloud_filter(&o->filter);
+  o->min_chain_length = 8;
+  o->reserved = 0;
+}
+
+int rebvio_hip_map_edge_polylines(rebvio_hip_map* m, const rebvio_hip_polyline_opts* opts, const rebvio_hip_cloud_pose* pose,
+                                  rebvio_hip_cloud_point* points_host, int* refs2_host, int cap_points, rebvio_hip_polyline* lines_host,
+                                  int cap_lines, int* n_points, int* n_lines) {
+  if (!m) return fail_msg("map_edge_polylines: null map", -3);
+  int rc = check_polyline_args("map_edge_polylines", opts, pose, points_host, cap_points, lines_host, cap_lines, n_points, n_lines);
+  if (rc) return rc;
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = m->ctx;
+  *n_points = *n_lines = 0;
+  rc = ech_begin("map_edge_polylines", m);
+  if (rc) return rc;
+  rebvio_hip_polyline_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_polyline_opts(&o);
+  const CloudArgs a = cloud_args(c, &o.filter, pose, cap_points);
+  if (cap_lines > c->P.keylines_max) cap_lines = c->P.keylines_max;  // (no more lines than keylines)
+  launch_edge_chains(c->s_trk, c->K, m->d, c->ech, ech::chain_rounds(c->P.keylines_max));
+  launch_edge_polylines(c->s_trk, c->K, m->d, c->ech, a, o.min_chain_length, cap_lines);
+  HIPCHK(hipGetLastError());
+  int w[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(w, c->ech.words, sizeof(w), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  const int np = w[2], nl = w[3];
+  const size_t kp = (size_t)(np < a.cap ? np : a.cap), kl = (size_t)(nl < cap_lines ? nl : cap_lines);
+  if (kp) HIPCHK(hipMemcpyAsync(points_host, c->ech.points, kp * sizeof(rebvio_hip_cloud_point), hipMemcpyDeviceToHost, c->s_trk));
+  if (kp && refs2_host) HIPCHK(hipMemcpyAsync(refs2_host, c->ech.refs2, kp * sizeof(int2), hipMemcpyDeviceToHost, c->s_trk));
+  if (kl) HIPCHK(hipMemcpyAsync(lines_host, c->ech.lines, kl * sizeof(rebvio_hip_polyline), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  *n_points = np;
+  *n_lines = nl;
+  return 0;
+}
+
+int rebvio_hip_test_edge_chains_host(const int* id_prev, const int* id_next, int n, rebvio_hip_chain_ref* refs, int cap_keylines, int* order,
+                                     int* starts, int cap_chains, int* n_keylines, int* n_chains) {
+  if (n < 0 || (n > 0 && (!id_prev || !id_next))) return fail_msg("test_edge_chains_host: negative n or null links", -3);
+  if (cap_keylines < 0 || cap_chains < 0) return fail_msg("test_edge_chains_host: negative cap", -3);
+  const size_t N = (size_t)n;
+  std::vector<ech::ChainNode> a(N), b(N);
+  std::vector<int> succ(N), len(N), start_of(N), ord(N), st(N + 1);
+  std::vector<rebvio_hip_chain_ref> rf(N);
+  int nc = 0;
+  ech::chains_host(id_prev, id_next, n, a.data(), b.data(), succ.data(), len.data(), start_of.data(), rf.data(), ord.data(), st.data(), &nc);
+  const size_t kn = (size_t)(n < cap_keylines ? n : cap_keylines), ks = (size_t)(nc + 1 < cap_chains ? nc + 1 : cap_chains);
+  if (refs && kn) std::memcpy(refs, rf.data(), kn * sizeof(rebvio_hip_chain_ref));
+  if (order && kn) std::memcpy(order, ord.data(), kn * sizeof(int));
+  if (starts && ks) std::memcpy(starts, st.data(), ks * sizeof(int));
+  if (n_keylines) *n_keylines = n;
+  if (n_chains) *n_chains = nc;
+  return 0;
+}
+
+int rebvio_hip_test_edge_polylines_host(float fm, const rebvio_hip_keyline* keylines, int n, const rebvio_hip_polyline_opts* opts,
+                                        const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud_point* points, int* refs2, int cap_points,
+                                        rebvio_hip_polyline* lines, int cap_lines, int* n_points, int* n_lines) {
+  if (n < 0 || (n > 0 && !keylines)) return fail_msg("test_edge_polylines_host: negative n or null keylines", -3);
+  const int rc = check_polyline_args("test_edge_polylines_host", opts, pose, points, cap_points, lines, cap_lines, n_points, n_lines);
+  if (rc) return rc;
+  rebvio_hip_polyline_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_polyline_opts(&o);
+  const size_t N = (size_t)n;
+  std::vector<int> idp(N), idn(N), succ(N), len(N), start_of(N), ord(N), st(N + 1);
+  std::vector<float> pos_img(2 * N), rs(2 * N), gn(N);
+  std::vector<unsigned> mt(N);
+  for (size_t i = 0; i < N; ++i) {
+    const rebvio_hip_keyline& k = keylines[i];
+    idp[i] = k.id_prev; idn[i] = k.id_next;
+    pos_img[2 * i] = k.pos_img[0]; pos_img[2 * i + 1] = k.pos_img[1];
+    rs[2 * i] = k.rho; rs[2 * i + 1] = k.sigma_rho;
+    gn[i] = k.gradient_norm;
+    mt[i] = k.matches;
+  }
+  std::vector<ech::ChainNode> a(N), b(N);
+  std::vector<rebvio_hip_chain_ref> rf(N);
+  int nc = 0;
+  ech::chains_host(idp.data(), idn.data(), n, a.data(), b.data(), succ.data(), len.data(), start_of.data(), rf.data(), ord.data(), st.data(), &nc);
+  float R[9], t[3];
+  for (int i = 0; i < 9; ++i) R[i] = pose ? pose->R[i] : (i % 4 == 0 ? 1.0f : 0.0f);
+  for (int i = 0; i < 3; ++i) t[i] = pose ? pose->t[i] : 0.0f;
+  ech::polylines_host(fm, pos_img.data(), rs.data(), gn.data(), mt.data(), n, rf.data(), ord.data(), o, R, t, pose ? pose->scale : 1.0f, points,
+                      refs2, cap_points, lines, cap_lines, n_points, n_lines);
   return 0;
 }
 

@@ -393,6 +393,30 @@ void launch_kf_handover(hipStream_t s, const KParams& p, const MapDev& m, int sr
 void launch_kf_point_cloud(hipStream_t s, const KParams& p, const void* snap_prs, const unsigned* snap_matches, const int* snap_n,
                            const CloudArgs& a, int* blk_cnt, int* count_dev, void* records_dev);
 
+// Scratch of the edge chains and polylines (rebvio_hip_map_edge_chains / _edge_polylines): views into one allocation of the context.
+// Arrays per keyline hold ceil(kmax / 256) * 256 entries.
+constexpr int kChainWords = 32;  // [0] n  [1] chains  [2] points  [3] lines  [8 + k] "something moved in front of round k"
+struct ChainDev {
+  void* node[2];   // ech::ChainNode, the rounds' two buffers
+  int* succ;
+  int* len;        // by head: the chain's length
+  int* start_of;   // by head: the chain's first slot
+  rebvio_hip_chain_ref* refs;
+  int* order;
+  int* starts;     // entries per keyline + 1
+  int* blk;        // [4][kMaxRecBlocks] workgroup counts: heads, head lengths, kept slots, line begins
+  int* words;      // [kChainWords]
+  void* points;    // rebvio_hip_cloud_point per kept slot
+  int2* refs2;     // {head, rank} per kept slot
+  rebvio_hip_polyline* lines;
+};
+// k_chain_link, `rounds` k_chain_round, k_chain_rank, k_chain_count, k_chain_emit, k_chain_order on stream s: rounds + 5 launches of
+// ceil(kmax / 256) workgroups whatever the map holds (its size is read on the device).
+void launch_edge_chains(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, int rounds);
+// k_poly_count, k_poly_emit, k_poly_lines on stream s behind launch_edge_chains: a = filter, pose and the points' cap.
+void launch_edge_polylines(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, const CloudArgs& a, int min_chain_length,
+                           int cap_lines);
+
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
 // ---- several camera streams ("lanes") of one GPU advanced in lock-step by batched launches (rebvio_hip_batch_*) --------

@@ -9,6 +9,7 @@
 // Bound: HBM/L2 gather bandwidth (keyline SoA streams + distance-field / mask / matched-keyline gathers);
 // no dense contraction exists on this path (largest product is 6x6), so MFMA does not apply.
 #include "common.hpp"
+#include "edge_chains.hpp"
 #include "glue_dev.hpp"
 #include "kf_cloud.hpp"
 #include "kf_handover.hpp"
@@ -3919,6 +3920,237 @@ void launch_kf_handover(hipStream_t s, const KParams& p, const MapDev& m, int sr
   const int want_d = div_up(dst_size > 0 ? dst_size : 1, 256), nbd = want_d < kMaxRecBlocks ? want_d : kMaxRecBlocks;
   RH_LAUNCH(k_kf_handover_apply, dim3(nbd), dim3(256), 0, s, p.kmax, src_size_dev, dst_size_dev, reinterpret_cast<float4*>(dst_prs),
             dst_matches, o.gate_sigma, (const unsigned long long*)key, reinterpret_cast<const kfp::HandoverStage*>(stage), cnt, assoc);
+}
+
+// ---- edge chains and polylines (rebvio_hip_map_edge_chains / rebvio_hip_map_edge_polylines) ----------------------------------------
+// List ranking over succ / pred by pointer jumping; ech::* (edge_chains.hpp) are the definition's per-keyline statements. One thread
+// per keyline (or slot), ceil(kmax / 256) workgroups per launch, the map's size read on the device. No workgroup waits for another:
+// every dependency between workgroups is a kernel boundary.
+//   k_chain_link   succ, and the first state of every keyline from pred; workgroup 0 leaves the size and the "moved" words
+//   k_chain_round  x ceil(log2(kmax)): state k + 1 of every keyline from state k of itself and of its ancestor (two buffers, all reads
+//                  from the previous one). A round stores words[8 + k + 1] = 1 when a state changed (every writer stores the same
+//                  value); the round behind one that changed nothing returns at once: that round copied every state as it was, so
+//                  both buffers hold the final states whichever round was the last to run.
+//   k_chain_rank   head, rank, cyclic per keyline; the chain's last member - one writer per chain - stores rank + 1 as len[head]
+//   k_chain_count  length per keyline (len[head]); per workgroup the number of heads and the sum of their lengths
+//   k_chain_emit   the two fixed-order integer scans over the head flags: chain number and first slot of every head -> starts, start_of
+//   k_chain_order  order[start_of[head] + rank] = keyline: a scatter, one writer per slot
+//   k_poly_count / k_poly_emit / k_poly_lines  kept and line-begin flags per slot in one pass, their scans, points and line records;
+//                  the last kernel turns a line's (first point, end) into its number of points and its "closed" bit
+// No atomics at all; every sum is an integer sum in a fixed order.
+__device__ __forceinline__ int chain_size(const MapDev& m, int kmax) {
+  const int n = m.st->n;
+  return n < 0 ? 0 : (n < kmax ? n : kmax);
+}
+// (sum of blk[0 .. blockIdx.x), sum of all gridDim.x <= kMaxRecBlocks entries); sh = 8 ints of LDS; ends behind a barrier
+__device__ __forceinline__ int2 chain_blk_sums(const int* __restrict__ blk, int* sh) {
+  const int tid = threadIdx.x;
+  const int c = tid < (int)gridDim.x ? blk[tid] : 0;
+  const int lo = wave_sum_i(tid < (int)blockIdx.x ? c : 0), all = wave_sum_i(c);
+  if ((tid & 63) == 0) {
+    sh[tid >> 6] = lo;
+    sh[4 + (tid >> 6)] = all;
+  }
+  __syncthreads();
+  return make_int2((sh[0] + sh[1]) + (sh[2] + sh[3]), (sh[4] + sh[5]) + (sh[6] + sh[7]));
+}
+// exclusive prefix of v over the workgroup's 256 threads in thread order; sh = 4 ints of LDS; ends behind a barrier
+__device__ __forceinline__ int chain_block_scan(int v, int* sh) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  int x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) sh[tid >> 6] = x;
+  __syncthreads();
+  int base = 0;
+  for (int k = 0; k < (tid >> 6); ++k) base += sh[k];
+  return base + x - v;
+}
+// the workgroup's sum of v -> out[blockIdx.x]; sh = 4 ints of LDS; ends behind a barrier
+__device__ __forceinline__ void chain_block_sum(int v, int* sh, int* __restrict__ out) {
+  const int s = wave_sum_i(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void k_chain_link(int kmax, MapDev m, ChainDev c, int rounds) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int n = chain_size(m, kmax);
+  if (blockIdx.x == 0 && (int)threadIdx.x <= rounds) {
+    if (threadIdx.x == 0) c.words[0] = n;
+    c.words[8 + threadIdx.x] = threadIdx.x == 0 ? 1 : 0;
+  }
+  if (idx >= n) return;
+  c.succ[idx] = ech::chain_succ(m.id_prev, m.id_next, n, idx);
+  reinterpret_cast<ech::ChainNode*>(c.node[0])[idx] = ech::chain_init(idx, ech::chain_pred(m.id_prev, m.id_next, n, idx));
+}
+
+__global__ __launch_bounds__(256) void k_chain_round(ChainDev c, int k) {
+  if (c.words[8 + k] == 0) return;  // nothing moved in the round in front: both buffers hold the final states
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int n = c.words[0];
+  const ech::ChainNode* in = reinterpret_cast<const ech::ChainNode*>(c.node[k & 1]);
+  ech::ChainNode* out = reinterpret_cast<ech::ChainNode*>(c.node[(k + 1) & 1]);
+  bool moved = false;
+  if (idx < n) out[idx] = ech::chain_round(in, idx, n, &moved);
+  if (__ballot(moved) != 0ull && (threadIdx.x & 63) == 0) c.words[8 + k + 1] = 1;
+}
+
+__global__ __launch_bounds__(256) void k_chain_rank(ChainDev c, int rounds) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int n = c.words[0];
+  if (idx >= n) return;
+  int head, rank, cyc;
+  ech::chain_resolve(reinterpret_cast<const ech::ChainNode*>(c.node[rounds & 1]), idx, &head, &rank, &cyc);
+  c.refs[idx] = rebvio_hip_chain_ref{head, rank, 0, cyc};
+  if (ech::chain_is_last(c.succ[idx], head)) c.len[head] = rank + 1;
+}
+
+__global__ __launch_bounds__(256) void k_chain_count(ChainDev c) {
+  __shared__ int sh[8];
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int n = c.words[0];
+  int is_head = 0, len = 0;
+  if (idx < n) {
+    const int head = c.refs[idx].head;
+    len = c.len[head];
+    c.refs[idx].length = len;
+    is_head = head == idx;
+  }
+  chain_block_sum(is_head, sh, c.blk);
+  chain_block_sum(is_head ? len : 0, sh + 4, c.blk + kMaxRecBlocks);
+}
+
+__global__ __launch_bounds__(256) void k_chain_emit(ChainDev c) {
+  __shared__ int sh[24];
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int n = c.words[0];
+  int is_head = 0, len = 0;
+  if (idx < n) {
+    const rebvio_hip_chain_ref r = c.refs[idx];
+    is_head = r.head == idx;
+    len = is_head ? r.length : 0;
+  }
+  const int2 heads = chain_blk_sums(c.blk, sh);
+  const int2 lens = chain_blk_sums(c.blk + kMaxRecBlocks, sh + 8);
+  const int cno = heads.x + chain_block_scan(is_head, sh + 16);
+  const int start = lens.x + chain_block_scan(len, sh + 20);
+  if (is_head) {  // (cno < chains <= n, start < n)
+    c.starts[cno] = start;
+    c.start_of[idx] = start;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    c.words[1] = heads.y;
+    c.starts[heads.y] = n;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_chain_order(ChainDev c) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int n = c.words[0];
+  if (idx >= n) return;
+  const rebvio_hip_chain_ref r = c.refs[idx];
+  const int slot = c.start_of[r.head] + r.rank;
+  if ((unsigned)slot < (unsigned)n) c.order[slot] = idx;  // (always: the test only keeps the scatter inside)
+}
+
+// kept / begin / end of slot s < n (k = its keyline, r = its record)
+__device__ __forceinline__ bool poly_slot_kept(const MapDev& m, const rebvio_hip_cloud_filter& f, int min_len, int k, int length) {
+  const float2 rs = m.rs[k];
+  return ech::poly_kept(f, min_len, rs.x, rs.y, m.matches[k], length);
+}
+
+__global__ __launch_bounds__(256) void k_poly_count(MapDev m, ChainDev c, rebvio_hip_cloud_filter f, int min_len) {
+  __shared__ int sh[8];
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  const int n = c.words[0];
+  int kept = 0, begin = 0;
+  if (s < n) {
+    const int k = c.order[s];
+    const rebvio_hip_chain_ref r = c.refs[k];
+    kept = poly_slot_kept(m, f, min_len, k, r.length);
+    begin = kept && (r.rank == 0 || !poly_slot_kept(m, f, min_len, c.order[s - 1], r.length));
+  }
+  chain_block_sum(kept, sh, c.blk + 2 * kMaxRecBlocks);
+  chain_block_sum(begin, sh + 4, c.blk + 3 * kMaxRecBlocks);
+}
+
+__global__ __launch_bounds__(256) void k_poly_emit(KParams p, MapDev m, ChainDev c, CloudArgs a, int min_len, int cap_lines) {
+  __shared__ int sh[24];
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  const int n = c.words[0];
+  const rebvio_hip_cloud_filter f{a.min_matches, a.max_rel_sigma, a.rho_min, a.rho_max};
+  int kept = 0, begin = 0, end = 0, k = 0;
+  rebvio_hip_chain_ref r{0, 0, 0, 0};
+  if (s < n) {
+    k = c.order[s];
+    r = c.refs[k];
+    kept = poly_slot_kept(m, f, min_len, k, r.length);
+    begin = kept && (r.rank == 0 || !poly_slot_kept(m, f, min_len, c.order[s - 1], r.length));
+    end = kept && !(r.rank + 1 < r.length && poly_slot_kept(m, f, min_len, c.order[s + 1], r.length));
+  }
+  const int2 pts = chain_blk_sums(c.blk + 2 * kMaxRecBlocks, sh);
+  const int2 lns = chain_blk_sums(c.blk + 3 * kMaxRecBlocks, sh + 8);
+  const int pidx = pts.x + chain_block_scan(kept, sh + 16);
+  const int lidx = lns.x + chain_block_scan(begin, sh + 20) + begin - 1;  // the line of a kept slot: begins up to and with it, less one
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    c.words[2] = pts.y;
+    c.words[3] = lns.y;
+  }
+  if (!kept) return;
+  if (pidx < a.cap) {
+    const float2 pi = m.pos_img[k];
+    const float2 rs = m.rs[k];
+    float q[3];
+    ech::poly_xyz(p.fm, a.R, a.t, a.scale, pi.x, pi.y, rs.x, q);
+    // two 16-byte stores per record, as k_cloud_emit
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) volatile v4f* GRec;
+    GRec rec = (GRec)(reinterpret_cast<float4*>(c.points) + 2 * (size_t)pidx);
+    rec[0] = v4f{q[0], q[1], q[2], rs.x};
+    rec[1] = v4f{rs.y, m.gnorm[k], __int_as_float(k), __uint_as_float(m.matches[k])};
+    c.refs2[pidx] = make_int2(r.head, r.rank);
+  }
+  if (lidx >= 0 && lidx < cap_lines) {  // the line's first and last slot fill its record between them (ech::poly_line_finish ends it)
+    if (begin) {
+      c.lines[lidx].first_point = pidx;
+      c.lines[lidx].head = r.head;
+      c.lines[lidx].flags = (r.flags & 1) ? r.length : 0;
+    }
+    if (end) c.lines[lidx].points = pidx + 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_poly_lines(ChainDev c, int cap_lines) {
+  const int l = blockIdx.x * 256 + threadIdx.x;
+  const int nl = c.words[3];
+  if (l >= nl || l >= cap_lines) return;
+  rebvio_hip_polyline rec = c.lines[l];
+  ech::poly_line_finish(&rec);
+  c.lines[l] = rec;
+}
+
+void launch_edge_chains(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, int rounds) {
+  const dim3 grid(div_up(p.kmax, 256));
+  RH_LAUNCH(k_chain_link, grid, dim3(256), 0, s, p.kmax, m, c, rounds);
+  for (int k = 0; k < rounds; ++k) RH_LAUNCH(k_chain_round, grid, dim3(256), 0, s, c, k);
+  RH_LAUNCH(k_chain_rank, grid, dim3(256), 0, s, c, rounds);
+  RH_LAUNCH(k_chain_count, grid, dim3(256), 0, s, c);
+  RH_LAUNCH(k_chain_emit, grid, dim3(256), 0, s, c);
+  RH_LAUNCH(k_chain_order, grid, dim3(256), 0, s, c);
+}
+
+void launch_edge_polylines(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, const CloudArgs& a, int min_chain_length,
+                           int cap_lines) {
+  const dim3 grid(div_up(p.kmax, 256));
+  const rebvio_hip_cloud_filter f{a.min_matches, a.max_rel_sigma, a.rho_min, a.rho_max};
+  RH_LAUNCH(k_poly_count, grid, dim3(256), 0, s, m, c, f, min_chain_length);
+  RH_LAUNCH(k_poly_emit, grid, dim3(256), 0, s, p, m, c, a, min_chain_length, cap_lines);
+  RH_LAUNCH(k_poly_lines, grid, dim3(256), 0, s, c, cap_lines);
 }
 
 }  // namespace rh

@@ -145,6 +145,45 @@ std::vector<rebvio::types::CloudPoint> EdgeMap::pointCloud(const rebvio::types::
   return points;
 }
 
+EdgeMap::EdgeChains EdgeMap::edgeChains() {
+  static_assert(sizeof(types::ChainRef) == sizeof(rebvio_hip_chain_ref) && offsetof(types::ChainRef, flags) == offsetof(rebvio_hip_chain_ref, flags),
+                "chain records mirror the C-ABI's");
+  EdgeChains out;
+  const size_t n = (size_t)size();
+  out.refs.resize(n);
+  out.order.resize(n);
+  out.starts.resize(n + 1);
+  int nk = 0, nc = 0;
+  check("rebvio_hip_map_edge_chains",
+        rebvio_hip_map_edge_chains(handle_, reinterpret_cast<rebvio_hip_chain_ref*>(out.refs.data()), (int)n, out.order.data(), out.starts.data(),
+                                   (int)n + 1, &nk, &nc));
+  out.refs.resize((size_t)nk);  // (nk = the map's size)
+  out.order.resize((size_t)nk);
+  out.starts.resize((size_t)nc + 1);
+  return out;
+}
+
+EdgeMap::EdgePolylines EdgeMap::edgePolylines(const rebvio::types::PolylineOpts& opts, const rebvio::types::CloudPose& pose) {
+  static_assert(sizeof(types::PolylineOpts) == sizeof(rebvio_hip_polyline_opts) && sizeof(types::Polyline) == sizeof(rebvio_hip_polyline) &&
+                    offsetof(types::PolylineOpts, min_chain_length) == offsetof(rebvio_hip_polyline_opts, min_chain_length) &&
+                    offsetof(types::Polyline, head) == offsetof(rebvio_hip_polyline, head), "polyline types mirror the C-ABI's");
+  EdgePolylines out;
+  const size_t n = (size_t)size();
+  out.points.resize(n);
+  out.refs.resize(n);
+  out.lines.resize(n);
+  int np = 0, nl = 0;
+  check("rebvio_hip_map_edge_polylines",
+        rebvio_hip_map_edge_polylines(handle_, reinterpret_cast<const rebvio_hip_polyline_opts*>(&opts),
+                                      reinterpret_cast<const rebvio_hip_cloud_pose*>(&pose), reinterpret_cast<rebvio_hip_cloud_point*>(out.points.data()),
+                                      reinterpret_cast<int*>(out.refs.data()), (int)n, reinterpret_cast<rebvio_hip_polyline*>(out.lines.data()), (int)n,
+                                      &np, &nl));
+  out.points.resize((size_t)np);  // (np, nl <= the map's size: nothing was cut)
+  out.refs.resize((size_t)np);
+  out.lines.resize((size_t)nl);
+  return out;
+}
+
 void EdgeMap::markKeyframe() {
   check("rebvio_hip_map_mark_keyframe", rebvio_hip_map_mark_keyframe(ctx_, handle_));
   invalidateMirror();

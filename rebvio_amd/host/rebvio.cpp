@@ -123,6 +123,10 @@ void Rebvio::registerKeyframeHandoverCallback(std::function<void(uint64_t ts_us,
   keyframe_handover_callbacks_.push_back(cb);
 }
 
+void Rebvio::registerEdgePolylineCallback(std::function<void(const rebvio::types::EdgePolylines&)> cb, rebvio::types::PolylineOpts opts) {
+  edge_polyline_callbacks_.push_back({cb, opts});
+}
+
 void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
   point_cloud_callbacks_.push_back({cb, filter});
 }
@@ -362,6 +366,9 @@ void Rebvio::stateEstimationProcess() {
     types::KfHandover kf_handover;
     uint64_t kf_handover_ts = 0;    // ... and the retired keyframe's stamp
     std::vector<types::KfWindowPose> kf_window;  // setKeyframeWindow: the current keyframe and the members against the new map (empty: none)
+    // edge-polyline callbacks: the new map's polylines, one extraction per callback, with the pose they were extracted at
+    std::vector<rebvio::EdgeMap::EdgePolylines> polylines;
+    types::CloudPose polyline_pose;
   } pending;
   // keyframe-pose callbacks: the snapshot of the current keyframe and the last pose estimated against it (the next one's guess)
   rebvio::KeyframeSnapshot kf_snapshot;
@@ -420,6 +427,13 @@ void Rebvio::stateEstimationProcess() {
       const types::PointCloud pc{pending.odometry.ts_us, pending.cloud_pose, reinterpret_cast<const types::CloudPoint*>(pts), (size_t)n};
       point_cloud_callbacks_[i].cb(pc);
     }
+    for (size_t i = 0; i < pending.polylines.size(); ++i) {
+      const rebvio::EdgeMap::EdgePolylines& p = pending.polylines[i];
+      const types::EdgePolylines ep{pending.odometry.ts_us, pending.polyline_pose, p.points.data(), reinterpret_cast<const int*>(p.refs.data()),
+                                    p.points.size(), p.lines.data(), p.lines.size()};
+      edge_polyline_callbacks_[i].cb(ep);
+    }
+    pending.polylines.clear();
     pending.old_map.reset();
     pending.new_map.reset();
     ++num_published_;
@@ -615,10 +629,11 @@ void Rebvio::stateEstimationProcess() {
     const bool want_cloud = !point_cloud_callbacks_.empty();
     const bool want_kf_pose = !keyframe_pose_callbacks_.empty();
     const bool want_kf_cloud = !keyframe_cloud_callbacks_.empty();
+    const bool want_polylines = !edge_polyline_callbacks_.empty();
     std::vector<rebvio_hip_cloud*> clouds, kf_clouds;
     types::CloudPose cloud_pose, kf_cloud_pose;
     uint64_t kf_cloud_ts = 0;
-    if (want_cloud || want_kf_cloud) integrate_pose();
+    if (want_cloud || want_kf_cloud || want_polylines) integrate_pose();
     // If the following frame is already queued, its gyro pre-integration (complete before the map was queued) is the next
     // pair's prior: that pair's first rotateKeylines then rides in this pair's last kernel. Only once the gyro bias is
     // initialised (until then the bias still changes between pairs, rebvio.cpp:146-160). Not with a point-cloud callback: the
@@ -631,7 +646,7 @@ void Rebvio::stateEstimationProcess() {
       std::lock_guard<std::mutex> guard(edge_map_buffer_mutex_);
       if (edge_map_buffer_.size() >= 2) {
         next_map = edge_map_buffer_[1];
-        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud) {
+        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud && !want_polylines) {
           store3(next_map->imu().R(), Rnext);
           have_next = true;
         }
@@ -699,6 +714,15 @@ void Rebvio::stateEstimationProcess() {
       }
     }
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
+    // edge-polyline callbacks: the new map's polylines in this pair's frame, behind this pair's second half (the call waits for it)
+    std::vector<rebvio::EdgeMap::EdgePolylines> polylines;
+    types::CloudPose polyline_pose;
+    if (want_polylines) {
+      store3(R_global, polyline_pose.R);
+      for (int i = 0; i < 3; ++i) polyline_pose.t[i] = Pos[i];
+      polyline_pose.scale = K;
+      for (const EdgePolylineCallback& epc : edge_polyline_callbacks_) polylines.push_back(new_edge_map->edgePolylines(epc.opts, polyline_pose));
+    }
     // keyframe-pose callbacks: the new map against the keyframe, behind this pair's second half (the call waits for it)
     bool have_kf_pose = false;
     bool have_kf_handover = false;
@@ -760,7 +784,7 @@ void Rebvio::stateEstimationProcess() {
     }
     timers.lap(2);
 
-    if (!want_cloud && !want_kf_cloud) integrate_pose();
+    if (!want_cloud && !want_kf_cloud && !want_polylines) integrate_pose();
     types::Odometry odometry;
     odometry.ts_us = new_edge_map->ts_us();
     odometry.orientation = TooN::SO3<types::Float>(R_global).ln();
@@ -785,6 +809,8 @@ void Rebvio::stateEstimationProcess() {
     pending.kf_handover = kf_handover;
     pending.kf_handover_ts = handover_ts;
     pending.kf_window = std::move(kf_window_poses);
+    pending.polylines = std::move(polylines);
+    pending.polyline_pose = polyline_pose;
     timers.lap(3);
     timers.end_pair();
     timers.n++;

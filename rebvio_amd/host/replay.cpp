@@ -11,6 +11,8 @@
 // little-endian PLY file PREFIX<ts_us>.ply with the vertex properties x, y, z, intensity (io::writePointCloudPly).
 // --cloud-dry: the callback is registered and counts points, no file is written (what the callback costs the pipeline:
 // tools/cloud_rate.py).
+// --polylines PREFIX [--min-chain N]: every published record's edge polylines (Rebvio::registerEdgePolylineCallback, default filter,
+// chains of at least N members, default 8) as PREFIX<ts_us>.ply: the cloud's vertex element plus `element edge` (io::writePolylinesPly).
 // --kf-pose FILE [--kf-every N]: the pose of every tracked map relative to the keyframe (Rebvio::registerKeyframePoseCallback), one
 // line per record that has one: ts_us status used R (9 values, row-major) t (3 values). A keyframe is requested before the first
 // frame and again after every N-th record (default 10).
@@ -42,6 +44,8 @@
 
 int main(int argc, char** argv) {
   std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix, kf_window_path, kf_handover_path;
+  std::string polylines_prefix;
+  int min_chain = 8;
   int kf_window = 0;
   bool kf_align = false;
   int kf_every = 10;
@@ -53,7 +57,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
+                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -81,6 +85,11 @@ int main(int argc, char** argv) {
     }
     else if (a == "--cloud") cloud_prefix = next();
     else if (a == "--cloud-dry") cloud_dry = true;
+    else if (a == "--polylines") {
+      if (!polylines_prefix.empty()) return usage();
+      polylines_prefix = next();
+    }
+    else if (a == "--min-chain") min_chain = std::atoi(next());
     else if (a == "--kf-pose" || a == "--kf-align") {
       if (!kf_pose_path.empty()) return usage();  // one of the two, once
       kf_align = a == "--kf-align";
@@ -112,7 +121,7 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1) return usage();
+  if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1 || min_chain < 1) return usage();
   if (!kf_window_path.empty() && (!kf_align || kf_pose_path.empty() || kf_window < 1 || kf_window > 15)) return usage();  // needs --kf-align FILE
   if (!kf_handover_path.empty() && (!kf_align || kf_pose_path.empty())) return usage();  // needs --kf-align FILE
   if (!kf_fuse_path.empty()) {  // the fusion runs behind the alignment only
@@ -241,6 +250,17 @@ int main(int argc, char** argv) {
         ++n_clouds;
         n_points += pc.size;
       });
+    size_t n_polyline_files = 0, n_lines = 0, n_line_points = 0;
+    if (!polylines_prefix.empty()) {
+      rebvio::types::PolylineOpts po;
+      po.min_chain_length = min_chain;
+      rebvio.registerEdgePolylineCallback([&](const rebvio::types::EdgePolylines& ep) {
+        rebvio::io::writePolylinesPly(polylines_prefix + std::to_string(ep.ts_us) + ".ply", ep.points, ep.size, ep.lines, ep.num_lines, ep.ts_us);
+        ++n_polyline_files;
+        n_lines += ep.num_lines;
+        n_line_points += ep.size;
+      }, po);
+    }
     const size_t n = rebvio::io::replay(
         *src, [&](rebvio::types::Image&& im) { rebvio.imageCallback(std::move(im)); },
         [&](rebvio::types::Imu&& s) { rebvio.imuCallback(std::move(s)); }, first, count);
@@ -248,6 +268,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "frames=%zu odometry=%zu running=%d\n", n, n_odo, (int)rebvio.running());
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
     if (!kf_cloud_prefix.empty()) std::fprintf(stderr, "kf_clouds=%zu kf_points=%zu\n", n_kf_clouds, n_kf_points);
+    if (!polylines_prefix.empty()) std::fprintf(stderr, "polyline_files=%zu lines=%zu line_points=%zu\n", n_polyline_files, n_lines, n_line_points);
     if (kf_pose_file) std::fclose(kf_pose_file);
     if (want_kf) std::fprintf(stderr, "kf_poses=%zu\n", n_poses);
     if (kf_window_file) {

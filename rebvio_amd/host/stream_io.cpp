@@ -305,6 +305,100 @@ std::vector<PlyVertex> readPointCloudPly(const std::string& path, uint64_t* ts_u
   return out;
 }
 
+namespace {
+void put_le32(std::vector<unsigned char>& body, size_t at, uint32_t w) {
+  for (int b = 0; b < 4; ++b) body[at + b] = (unsigned char)(w >> (8 * b));  // little-endian on any host
+}
+uint32_t get_le32(const std::vector<unsigned char>& body, size_t at) {
+  uint32_t w = 0;
+  for (int b = 0; b < 4; ++b) w |= (uint32_t)body[at + b] << (8 * b);
+  return w;
+}
+}  // namespace
+
+void writePolylinesPly(const std::string& path, const rebvio::types::CloudPoint* points, size_t n, const rebvio::types::Polyline* lines,
+                       size_t n_lines, uint64_t ts_us) {
+  std::vector<PlyEdge> edges;
+  for (size_t l = 0; l < n_lines; ++l) {
+    const rebvio::types::Polyline& ln = lines[l];
+    if (ln.first_point < 0 || ln.points < 1 || (size_t)ln.first_point >= n) continue;
+    const size_t first = (size_t)ln.first_point, whole = first + (size_t)ln.points, end = std::min(whole, n);
+    for (size_t k = first; k + 1 < end; ++k) edges.push_back(PlyEdge{(int)k, (int)k + 1});
+    if ((ln.flags & 1) && end == whole && ln.points >= 2) edges.push_back(PlyEdge{(int)end - 1, (int)first});
+  }
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) bad("cannot create " + path);
+  std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment rebvio polylines ts_us %llu\nelement vertex %zu\n"
+               "property float x\nproperty float y\nproperty float z\nproperty float intensity\nelement edge %zu\n"
+               "property int vertex1\nproperty int vertex2\nend_header\n",
+               (unsigned long long)ts_us, n, edges.size());
+  std::vector<unsigned char> body(n * 16 + edges.size() * 8);
+  for (size_t i = 0; i < n; ++i) {
+    const float v[4] = {points[i].xyz[0], points[i].xyz[1], points[i].xyz[2], points[i].gradient_norm};
+    for (int k = 0; k < 4; ++k) {
+      uint32_t w;
+      std::memcpy(&w, &v[k], 4);
+      put_le32(body, i * 16 + (size_t)k * 4, w);
+    }
+  }
+  for (size_t e = 0; e < edges.size(); ++e) {
+    put_le32(body, n * 16 + e * 8, (uint32_t)edges[e].vertex1);
+    put_le32(body, n * 16 + e * 8 + 4, (uint32_t)edges[e].vertex2);
+  }
+  const bool ok = body.empty() || std::fwrite(body.data(), 1, body.size(), f) == body.size();
+  if (std::fclose(f) != 0 || !ok) bad("cannot write " + path);
+}
+
+std::vector<PlyVertex> readPolylinesPly(const std::string& path, std::vector<PlyEdge>* edges, uint64_t* ts_us) {
+  std::FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) bad("cannot open " + path);
+  std::vector<std::string> lines;
+  std::string line;
+  for (int c; (c = std::fgetc(f)) != EOF;) {
+    if (c != '\n') {
+      line.push_back((char)c);
+      if (line.size() > 200) break;
+      continue;
+    }
+    lines.push_back(line);
+    if (line == "end_header" || lines.size() > 12) break;
+    line.clear();
+  }
+  unsigned long long ts = 0, n = 0, m = 0;
+  const bool header_ok = lines.size() == 12 && lines[0] == "ply" && lines[1] == "format binary_little_endian 1.0" &&
+                         std::sscanf(lines[2].c_str(), "comment rebvio polylines ts_us %llu", &ts) == 1 &&
+                         std::sscanf(lines[3].c_str(), "element vertex %llu", &n) == 1 && lines[4] == "property float x" &&
+                         lines[5] == "property float y" && lines[6] == "property float z" && lines[7] == "property float intensity" &&
+                         std::sscanf(lines[8].c_str(), "element edge %llu", &m) == 1 && lines[9] == "property int vertex1" &&
+                         lines[10] == "property int vertex2" && lines[11] == "end_header" && n <= (1ull << 31) && m <= (1ull << 31);
+  if (!header_ok) {
+    std::fclose(f);
+    bad(path + ": not a polyline PLY file of writePolylinesPly");
+  }
+  std::vector<unsigned char> body((size_t)n * 16 + (size_t)m * 8);
+  const bool ok = (body.empty() || std::fread(body.data(), 1, body.size(), f) == body.size()) && std::fgetc(f) == EOF;
+  std::fclose(f);
+  if (!ok) bad(path + ": the vertex and edge data do not match the header's counts");
+  std::vector<PlyVertex> out((size_t)n);
+  for (size_t i = 0; i < out.size(); ++i) {
+    float v[4];
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t w = get_le32(body, i * 16 + (size_t)k * 4);
+      std::memcpy(&v[k], &w, 4);
+    }
+    out[i] = PlyVertex{v[0], v[1], v[2], v[3]};
+  }
+  std::vector<PlyEdge> es((size_t)m);
+  for (size_t e = 0; e < es.size(); ++e) {
+    es[e] = PlyEdge{(int)get_le32(body, (size_t)n * 16 + e * 8), (int)get_le32(body, (size_t)n * 16 + e * 8 + 4)};
+    if (es[e].vertex1 < 0 || es[e].vertex2 < 0 || (unsigned long long)es[e].vertex1 >= n || (unsigned long long)es[e].vertex2 >= n)
+      bad(path + ": an edge names a vertex outside the file");
+  }
+  if (edges) *edges = std::move(es);
+  if (ts_us) *ts_us = ts;
+  return out;
+}
+
 size_t replay(StreamSource& src, const std::function<void(rebvio::types::Image&&)>& image_cb,
               const std::function<void(rebvio::types::Imu&&)>& imu_cb, size_t first, size_t count) {
   const auto& imu = src.imu();
