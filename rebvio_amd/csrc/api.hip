@@ -2259,8 +2259,9 @@ int rebvio_hip_test_kf_pose_host(float fm, const float* snap_prs4, const unsigne
       const int j = records[r].kf_keyline, i = records[r].keyline;
       const float* k4 = snap_prs4 + 4 * (size_t)j;
       if (!kfp::filter_pass(o.kf_filter, k4[2], k4[3], snap_matches[j])) continue;
+      bool in;
       if (!kfp::term(fm, k4[0], k4[1], k4[2], cur_pos_img[2 * (size_t)i], cur_pos_img[2 * (size_t)i + 1], cur_gradient[2 * (size_t)i],
-                     cur_gradient[2 * (size_t)i + 1], res.R, res.t, o.huber_px, v))
+                     cur_gradient[2 * (size_t)i + 1], res.R, res.t, o.huber_px, v, &in))
         continue;
       for (int k = 0; k < kfp::kSums; ++k) S[k] = S[k] + v[k];
       ++used;
@@ -2430,32 +2431,8 @@ int rebvio_hip_test_kf_align_host(float fm, float cx, float cy, int rows, int co
   const size_t Pn = (size_t)rows * (size_t)cols;
   for (size_t k = 0; k < Pn; ++k)
     if (df_id[k] >= n_cur) return fail_msg("test_kf_align_host: a field id lies outside the keyline arrays", -3);
-  kfp::AlignMap am;
-  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
-  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
-  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
-  am.cap = n_cur;
-  rebvio_hip_kf_pose res;
-  kf_pose_start(&res, R0, t0);
-  res.candidates = kf_size;
-  if (kf_size == 0) res.status = 3;
-  for (int it = 0; kf_size > 0 && it <= o.max_iter; ++it) {
-    double S[kfp::kSums] = {}, v[kfp::kSums], ws[48];
-    int used = 0;
-    for (int j = 0; j < kf_size; ++j) {
-      const float* k4 = snap_prs4 + 4 * (size_t)j;
-      int i = -1;
-      if (kfp::filter_pass(o.kf_filter, k4[2], k4[3], snap_matches[j]))
-        i = kfp::align_term(am, k4[0], k4[1], k4[2], snap_normals != nullptr, snap_normals ? snap_normals[2 * (size_t)j] : 0.0f,
-                            snap_normals ? snap_normals[2 * (size_t)j + 1] : 0.0f, o.min_cos, o.max_dist, res.R, res.t, o.huber_px, v);
-      if (assoc) assoc[j] = i;
-      if (i < 0) continue;
-      for (int k = 0; k < kfp::kSums; ++k) S[k] = S[k] + v[k];
-      ++used;
-    }
-    kfp::step(S, used, it == 0, it == o.max_iter, o.min_used, ws, &res);
-  }
-  *out = res;
+  const kfp::AlignMap am = kfp::host_map(fm, cx, cy, rows, cols, df_id, df_dist, cur_pos, cur_unit, n_cur);
+  kfm::align_host(am, snap_prs4, snap_matches, snap_normals, kf_size, o, R0, t0, out, assoc, nullptr);
   return 0;
 }
 
@@ -2607,13 +2584,12 @@ int rebvio_hip_test_kf_align_many_host(float fm, float cx, float cy, int rows, i
   const size_t Pn = (size_t)rows * (size_t)cols;
   for (size_t k = 0; k < Pn; ++k)
     if (df_id[k] >= n_cur) return fail_msg("test_kf_align_many_host: a field id lies outside the keyline arrays", -3);
-  kfp::AlignMap am;
-  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
-  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
-  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
-  am.cap = n_cur;
-  for (int h = 0; h < n; ++h)
-    kfm::align_host(am, snap_prs4, snap_matches, snap_normals, kf_size, o, R0s + 9 * (size_t)h, t0s + 3 * (size_t)h, &out[h]);
+  const kfp::AlignMap am = kfp::host_map(fm, cx, cy, rows, cols, df_id, df_dist, cur_pos, cur_unit, n_cur);
+  for (int h = 0; h < n; ++h) {
+    std::memset(&out[h], 0, sizeof(out[h]));
+    kfm::align_host(am, snap_prs4, snap_matches, snap_normals, kf_size, o, R0s + 9 * (size_t)h, t0s + 3 * (size_t)h, &out[h].pose, nullptr,
+                    &out[h].inliers);
+  }
   return 0;
 }
 
@@ -2714,11 +2690,7 @@ int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int col
   const size_t Pn = (size_t)rows * (size_t)cols;
   for (size_t k = 0; k < Pn; ++k)
     if (df_id[k] >= n_cur) return fail_msg("test_kf_fuse_host: a field id lies outside the keyline arrays", -3);
-  kfp::AlignMap am;
-  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
-  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
-  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
-  am.cap = n_cur;
+  const kfp::AlignMap am = kfp::host_map(fm, cx, cy, rows, cols, df_id, df_dist, cur_pos, cur_unit, n_cur);
   rebvio_hip_kf_fuse res;
   std::memset(&res, 0, sizeof(res));
   res.candidates = kf_size;
@@ -2862,11 +2834,7 @@ int rebvio_hip_test_kf_handover_host(float fm, float cx, float cy, int rows, int
   const size_t Pn = (size_t)rows * (size_t)cols;
   for (size_t k = 0; k < Pn; ++k)
     if (df_id[k] >= n_cur) return fail_msg("test_kf_handover_host: a field id lies outside the keyline arrays", -3);
-  kfp::AlignMap am;
-  am.fm = fm; am.cx = cx; am.cy = cy; am.rows = rows; am.cols = cols;
-  am.df = nullptr; am.df_nr = 1; am.ids = df_id; am.dists = df_dist;
-  am.pos = reinterpret_cast<const kfp::AlignF2*>(cur_pos); am.unit = reinterpret_cast<const kfp::AlignF2*>(cur_unit);
-  am.cap = n_cur;
+  const kfp::AlignMap am = kfp::host_map(fm, cx, cy, rows, cols, df_id, df_dist, cur_pos, cur_unit, n_cur);
   rebvio_hip_kf_handover res;
   std::vector<unsigned long long> key((size_t)dst_size);
   std::vector<kfp::HandoverStage> stage((size_t)kf_size);

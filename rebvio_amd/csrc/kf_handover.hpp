@@ -2,11 +2,11 @@
 // is the definition): the two per-keyline statements, and the two passes over them in index order. One source for the device
 // (k_kf_handover_claim / k_kf_handover_apply, track.hip) and the host (handover_host: rebvio_hip_test_kf_handover_host, api.hip, and
 // the stand-alone tests/cpp/kf_handover_host_check.cpp). fp64 behind the loads; every
-// + - * / and sqrt is an operation of its own (-ffp-contract=off). The lookup is align_term's (kf_pose.hpp), copied: a shared helper
-// would have to leave every existing kernel's instructions as they are.
+// + - * / and sqrt is an operation of its own (-ffp-contract=off). The lookup is kfp::lookup (kf_pose.hpp), the alignment's and the
+// fusion's as well.
 #pragma once
 
-#include "kf_pose.hpp"  // AlignMap, filter_pass, kRhoMin / kRhoMax
+#include "kf_pose.hpp"  // AlignMap, lookup, direction, filter_pass, kRhoMin / kRhoMax
 
 namespace rh {
 namespace kfp {
@@ -42,44 +42,16 @@ RH_HD inline float handover_key_sigma(unsigned long long key) {
 
 // Pass 1 for one src keyline that passed the filter (the caller's test): steps 1..3 of the definition. kHoNone: not associated,
 // nothing written. Otherwise *owner = i < dst_size; kHoClaim: *rho_out / *sig_out = (float)rho_c / (float)sig_c.
-RH_HD inline int handover_claim_term(const AlignMap& c, int dst_size, float kx, float ky, float rho_f, float sig_f, bool has_n, float knx,
-                                     float kny, double min_cos, int max_dist, const double* R, const double* t, double q_abs, int* owner,
-                                     float* rho_out, float* sig_out) {
-  const double a = (double)(kx / c.fm), b = (double)(ky / c.fm), rho = (double)rho_f;
-  const double Zx = (R[0] * a + R[1] * b) + R[2];
-  const double Zy = (R[3] * a + R[4] * b) + R[5];
-  const double Zz = (R[6] * a + R[7] * b) + R[8];
-  const double Yx = Zx + rho * t[0], Yy = Zy + rho * t[1], Yz = Zz + rho * t[2];
-  if (!(Yz > 0.0)) return kHoNone;
-  const double px = Yx / Yz, py = Yy / Yz;
-  const double pu = (double)c.fm * px + (double)c.cx, pv = (double)c.fm * py + (double)c.cy;
-  const double x = floor(pu + 0.5), y = floor(pv + 0.5);
-  if (!(x >= 1.0 && x <= (double)(c.cols - 2) && y >= 1.0 && y <= (double)(c.rows - 2))) return kHoNone;
-  const size_t cell = (size_t)(int)y * (size_t)c.cols + (size_t)(int)x;
-  int i, dist;
-  if (c.df) {
-    const unsigned key = c.df[cell];
-    if (key == 0xFFFFFFFFu) return kHoNone;  // (kDfEmpty)
-    i = (int)((((1u << 23) - 1u) - (key & ((1u << 23) - 1u))) / (unsigned)c.df_nr);  // (kDfSeqMask, kDfSeqBits)
-    dist = (int)(key >> 23);
-  } else {
-    i = c.ids[cell];
-    dist = c.dists[cell];
-    if (i < 0) return kHoNone;
-  }
-  if (!(dist <= max_dist) || i >= c.cap) return kHoNone;
-  // unit[i]: one 8-byte gather behind the field's (pos[i] serves the residual only, which the hand-over does not form)
-  const AlignF2 un = c.unit[i];
-  if (has_n && min_cos > -1.0) {
-    const double nx = (double)knx, ny = (double)kny, ux = (double)un.x, uy = (double)un.y;
-    const double mx = R[0] * nx + R[1] * ny, my = R[3] * nx + R[4] * ny;
-    const double mm = mx * mx + my * my, nn = ux * ux + uy * uy;
-    if (mm > 0.0 && nn > 0.0 && !(mx * ux + my * uy >= (min_cos * sqrt(mm)) * sqrt(nn))) return kHoNone;
-  }
+RH_KF int handover_claim_term(const AlignMap& c, int dst_size, float kx, float ky, float rho_f, float sig_f, bool has_n, float knx, float kny,
+                             double min_cos, int max_dist, const double* R, const double* t, double q_abs, int* owner, float* rho_out,
+                             float* sig_out) {
+  Lookup l;
+  if (!lookup<false>(c, kx, ky, rho_f, has_n, knx, kny, min_cos, max_dist, R, t, &l)) return kHoNone;
   // step 6's own skip: the owner's gradient
-  const double gx = (double)un.x, gy = (double)un.y;
-  const double g2 = gx * gx + gy * gy;
-  if (!(g2 > 0.0 && g2 < HUGE_VAL)) return kHoNone;
+  double nx, ny;
+  if (!direction(l.ux, l.uy, &nx, &ny)) return kHoNone;
+  const int i = l.owner;
+  const double rho = l.p.rho, Zz = l.p.Zz, Yz = l.p.Yz;
   if (!(i < dst_size)) return kHoNone;  // the successor has no such keyline
   *owner = i;
   // 2. propagate into the map's frame

@@ -3377,18 +3377,93 @@ void launch_kf_snapshot(hipStream_t s, const KParams& p, const MapDev& m, void* 
   RH_LAUNCH(k_kf_snapshot, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, m, reinterpret_cast<float4*>(prs), matches, n_out);
 }
 
+// What the keyframe solvers' kernels share (each inlined into its kernel).
+// the pose of a result block in registers
+__device__ __forceinline__ void kf_load_pose(const rebvio_hip_kf_pose* __restrict__ st, double* R, double* t) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = st->R[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t[k] = st->t[k];
+}
+// the field, pos and unit of a map as kfp::lookup reads them
+__device__ __forceinline__ kfp::AlignMap kf_align_map(const KParams& p, const MapDev& m) {
+  kfp::AlignMap c;
+  c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
+  c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
+  c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
+  c.cap = p.kmax;
+  return c;
+}
+// The 28 addends of every lane of a workgroup of 256 reduced by a FIXED tree: an fp64 butterfly over the wave (every lane ends
+// with the same total: a + b == b + a), the four wave totals through LDS as (w0 + w1) + (w2 + w3) -> part[blockIdx.x]; the lanes
+// with `used` counted by ballot the same way -> part_used[blockIdx.x]. No floating-point atomic anywhere, so the sums are the same
+// bit for bit on every run. kInl: the lanes with `inl` are counted as well, through sh_inl into part_inl (unused without it). sh:
+// 4 x 28 doubles, sh_used / sh_inl: 4 ints of LDS each.
+template <bool kInl>
+__device__ __forceinline__ void kf_block_sums(double* v, bool used, bool inl, double (*sh)[kfp::kSums], int* sh_used, int* sh_inl,
+                                              double* __restrict__ part, int* __restrict__ part_used, int* __restrict__ part_inl) {
+  const int tid = threadIdx.x, wv = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < kfp::kSums; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
+  }
+  const int nu = __popcll(__ballot(used)), ni = kInl ? __popcll(__ballot(inl)) : 0;
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kfp::kSums; ++k) sh[wv][k] = v[k];
+    sh_used[wv] = nu;
+    if (kInl) sh_inl[wv] = ni;
+  }
+  __syncthreads();
+  if (tid < kfp::kSums) part[(size_t)blockIdx.x * kfp::kSums + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
+  if (tid == 0) {
+    part_used[blockIdx.x] = (sh_used[0] + sh_used[1]) + (sh_used[2] + sh_used[3]);
+    if (kInl) part_inl[blockIdx.x] = (sh_inl[0] + sh_inl[1]) + (sh_inl[2] + sh_inl[3]);
+  }
+}
+// sum k = tid < 28 of the first nb partials, added in index order from 0.0 with eight loads in flight (one dependent load per
+// partial took 72 us for 256 partials)
+__device__ __forceinline__ double kf_partial_sum(const double* __restrict__ part, int nb, int tid) {
+  double s = 0.0;
+  int b = 0;
+  for (; b + 8 <= nb; b += 8) {
+    double x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(b + u) * kfp::kSums + tid];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s = s + x[u];
+  }
+  for (; b < nb; ++b) s = s + part[(size_t)b * kfp::kSums + tid];
+  return s;
+}
+// N per-wave counts of a workgroup of 256 (n: the same in every lane of a wave) added to cnt[0 .. N): lane 0 of each wave leaves them
+// in LDS and N threads add the workgroup's non-zero sums with integer atomics (same-address atomics run one after the other at the
+// memory side: one set per workgroup, not per wave). sh: 4 x N ints of LDS.
+template <int N>
+__device__ __forceinline__ void kf_add_counts(const int (&n)[N], int (*sh)[N], int* __restrict__ cnt) {
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) sh[tid >> 6][k] = n[k];
+  }
+  __syncthreads();
+  if (tid < N) {
+    const int sum = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
+    if (sum) atomicAdd(cnt + tid, sum);
+  }
+}
+
 // One evaluation of the pose's normal equations (kf_pose.hpp: kfp::term is the definition's per-record statement). One thread per
-// candidate record of k_kf_emit, the record count and the current pose read from device memory. The 28 addends of a lane are
-// reduced by a FIXED tree: an fp64 butterfly over the wave (every lane ends with the same total: a + b == b + a), the four wave
-// totals through LDS as (w0 + w1) + (w2 + w3). One partial of 28 doubles and the count of used terms per workgroup; no
-// floating-point atomic anywhere, so the sums are the same bit for bit on every run. A workgroup behind the last record writes zeros.
+// candidate record of k_kf_emit, the record count and the current pose read from device memory. kf_block_sums leaves one partial of
+// 28 doubles and the count of used terms per workgroup. A workgroup behind the last record writes zeros.
 __global__ __launch_bounds__(256) void k_kf_pose_sums(KParams p, MapDev m, const float4* __restrict__ rec, const int* __restrict__ count,
                                                       const float4* __restrict__ prs, const unsigned* __restrict__ kf_matches,
                                                       rebvio_hip_cloud_filter flt, double huber, const rebvio_hip_kf_pose* __restrict__ st,
                                                       double* __restrict__ part, int* __restrict__ part_used) {
   __shared__ double sh[4][kfp::kSums];
   __shared__ int sh_used[4];
-  const int tid = threadIdx.x, r = blockIdx.x * 256 + tid, wv = tid >> 6;
+  const int r = blockIdx.x * 256 + threadIdx.x;
   double v[kfp::kSums];
 #pragma unroll
   for (int k = 0; k < kfp::kSums; ++k) v[k] = 0.0;
@@ -3401,26 +3476,11 @@ __global__ __launch_bounds__(256) void k_kf_pose_sums(KParams p, MapDev m, const
     const float2 q = m.pos_img[i];
     const float2 g = m.grad[i];
     double R[9], t[3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = st->R[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = st->t[k];
-    used = kfp::filter_pass(flt, k4.z, k4.w, kmt) && kfp::term(p.fm, k4.x, k4.y, k4.z, q.x, q.y, g.x, g.y, R, t, huber, v);
+    kf_load_pose(st, R, t);
+    bool in;
+    used = kfp::filter_pass(flt, k4.z, k4.w, kmt) && kfp::term(p.fm, k4.x, k4.y, k4.z, q.x, q.y, g.x, g.y, R, t, huber, v, &in);
   }
-#pragma unroll
-  for (int k = 0; k < kfp::kSums; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
-  }
-  const int nu = __popcll(__ballot(used));
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kfp::kSums; ++k) sh[wv][k] = v[k];
-    sh_used[wv] = nu;
-  }
-  __syncthreads();
-  if (tid < kfp::kSums) part[(size_t)blockIdx.x * kfp::kSums + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
-  if (tid == 0) part_used[blockIdx.x] = (sh_used[0] + sh_used[1]) + (sh_used[2] + sh_used[3]);
+  kf_block_sums<false>(v, used, false, sh, sh_used, nullptr, part, part_used, nullptr);
 }
 
 // The end of one evaluation, one workgroup of 64: lane k < 28 adds the nb (<= kMaxRecBlocks) partials of sum k in index order, lane 28
@@ -3434,18 +3494,7 @@ __global__ __launch_bounds__(64) void k_kf_pose_step(const double* __restrict__ 
   __shared__ int sh_used;
   const int tid = threadIdx.x;
   if (tid < kfp::kSums) {
-    // eight loads in flight, added in index order (one dependent load per partial took 72 us for 256 partials)
-    double s = 0.0;
-    int b = 0;
-    for (; b + 8 <= nb; b += 8) {
-      double x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(b + u) * kfp::kSums + tid];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s = s + x[u];
-    }
-    for (; b < nb; ++b) s = s + part[(size_t)b * kfp::kSums + tid];
-    S[tid] = s;
+    S[tid] = kf_partial_sum(part, nb, tid);
   } else if (tid == kfp::kSums) {
     int u = 0;
     for (int b = 0; b < nb; ++b) u += part_used[b];
@@ -3485,8 +3534,8 @@ void launch_kf_snapshot_normals(hipStream_t s, const KParams& p, const MapDev& m
 
 // One evaluation of the alignment's normal equations (kf_pose.hpp: kfp::align_term is the definition's per-keyline statement). One
 // thread per keyframe keyline: one 16-byte snapshot load and the 8-byte normal, then two dependent gathers - the field cell, then
-// pos and unit of its owner together. assoc[j] is written by every thread below kf_size. The reduction is k_kf_pose_sums' tree,
-// copied: butterfly over the wave, (w0 + w1) + (w2 + w3) through LDS, one partial and one count per workgroup, no atomic.
+// pos and unit of its owner together. assoc[j] is written by every thread below kf_size. The reduction is kf_block_sums: one partial
+// and one count per workgroup, no atomic.
 __global__ __launch_bounds__(256) void k_kf_align_sums(KParams p, MapDev m, int kf_size, const float4* __restrict__ prs,
                                                        const unsigned* __restrict__ kf_matches, const float2* __restrict__ normals,
                                                        rebvio_hip_cloud_filter flt, double huber, double min_cos, int max_dist,
@@ -3494,7 +3543,7 @@ __global__ __launch_bounds__(256) void k_kf_align_sums(KParams p, MapDev m, int 
                                                        int* __restrict__ part_used, int* __restrict__ assoc) {
   __shared__ double sh[4][kfp::kSums];
   __shared__ int sh_used[4];
-  const int tid = threadIdx.x, j = blockIdx.x * 256 + tid, wv = tid >> 6;
+  const int j = blockIdx.x * 256 + threadIdx.x;
   double v[kfp::kSums];
 #pragma unroll
   for (int k = 0; k < kfp::kSums; ++k) v[k] = 0.0;
@@ -3504,35 +3553,16 @@ __global__ __launch_bounds__(256) void k_kf_align_sums(KParams p, MapDev m, int 
     const unsigned kmt = kf_matches[j];
     const float2 kn = normals ? normals[j] : make_float2(0.f, 0.f);
     double R[9], t[3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = st->R[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = st->t[k];
-    kfp::AlignMap c;
-    c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
-    c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
-    c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
-    c.cap = p.kmax;
+    kf_load_pose(st, R, t);
+    const kfp::AlignMap c = kf_align_map(p, m);
     int i = -1;
+    bool in;
     if (kfp::filter_pass(flt, k4.z, k4.w, kmt))
-      i = kfp::align_term(c, k4.x, k4.y, k4.z, normals != nullptr, kn.x, kn.y, min_cos, max_dist, R, t, huber, v);
+      i = kfp::align_term(c, k4.x, k4.y, k4.z, normals != nullptr, kn.x, kn.y, min_cos, max_dist, R, t, huber, v, &in);
     used = i >= 0;
     assoc[j] = i;
   }
-#pragma unroll
-  for (int k = 0; k < kfp::kSums; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
-  }
-  const int nu = __popcll(__ballot(used));
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kfp::kSums; ++k) sh[wv][k] = v[k];
-    sh_used[wv] = nu;
-  }
-  __syncthreads();
-  if (tid < kfp::kSums) part[(size_t)blockIdx.x * kfp::kSums + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
-  if (tid == 0) part_used[blockIdx.x] = (sh_used[0] + sh_used[1]) + (sh_used[2] + sh_used[3]);
+  kf_block_sums<false>(v, used, false, sh, sh_used, nullptr, part, part_used, nullptr);
 }
 
 void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int kf_size, const int* kf_size_dev, const void* snap_prs,
@@ -3551,10 +3581,9 @@ void launch_kf_align_eval(hipStream_t s, const KParams& p, const MapDev& m, int 
 // k_kf_align_sums for a list of (snapshot, pose) hypotheses in one launch: blockIdx.y is the hypothesis, blockIdx.x its workgroup.
 // The descriptor (64 bytes at a workgroup-uniform address: scalar loads) names the snapshot's buffers and size and the hypothesis's
 // result block and partials. A workgroup behind its own hypothesis's last keyline leaves before any vector load and before the
-// barrier - the whole workgroup takes that branch. The per-thread statement is kfp::align_term_in (align_term, copied, with the
-// Huber test's outcome as one more output) and the reduction is k_kf_align_sums' tree, copied: a hypothesis's partials are the
-// bits the single kernel writes for the same snapshot and pose. The inlier count goes the way of `used`: ballot, popcount, LDS.
-// No assoc is written.
+// barrier - the whole workgroup takes that branch. The per-thread statement is kfp::align_term, here with the Huber test's outcome
+// kept, and the reduction is kf_block_sums, k_kf_align_sums' own: a hypothesis's partials are the bits the single kernel writes for
+// the same snapshot and pose. The inlier count goes the way of `used`: ballot, popcount, LDS. No assoc is written.
 __global__ __launch_bounds__(256) void k_kf_align_sums_many(KParams p, MapDev m, const KfHypDesc* __restrict__ desc,
                                                             rebvio_hip_cloud_filter flt, double huber, double min_cos, int max_dist) {
   __shared__ double sh[4][kfp::kSums];
@@ -3565,7 +3594,7 @@ __global__ __launch_bounds__(256) void k_kf_align_sums_many(KParams p, MapDev m,
   const float4* __restrict__ prs = reinterpret_cast<const float4*>(d.prs);
   const float2* __restrict__ normals = reinterpret_cast<const float2*>(d.normals);
   const rebvio_hip_kf_pose* __restrict__ st = &d.res->pose;
-  const int tid = threadIdx.x, j = blockIdx.x * 256 + tid, wv = tid >> 6;
+  const int j = blockIdx.x * 256 + threadIdx.x;
   double v[kfp::kSums];
 #pragma unroll
   for (int k = 0; k < kfp::kSums; ++k) v[k] = 0.0;
@@ -3575,46 +3604,22 @@ __global__ __launch_bounds__(256) void k_kf_align_sums_many(KParams p, MapDev m,
     const unsigned kmt = d.matches[j];
     const float2 kn = normals ? normals[j] : make_float2(0.f, 0.f);
     double R[9], t[3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = st->R[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = st->t[k];
-    kfp::AlignMap c;
-    c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
-    c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
-    c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
-    c.cap = p.kmax;
+    kf_load_pose(st, R, t);
+    const kfp::AlignMap c = kf_align_map(p, m);
     int i = -1;
     bool in = false;
     if (kfp::filter_pass(flt, k4.z, k4.w, kmt))
-      i = kfp::align_term_in(c, k4.x, k4.y, k4.z, normals != nullptr, kn.x, kn.y, min_cos, max_dist, R, t, huber, v, &in);
+      i = kfp::align_term(c, k4.x, k4.y, k4.z, normals != nullptr, kn.x, kn.y, min_cos, max_dist, R, t, huber, v, &in);
     used = i >= 0;
     inl = used && in;
   }
-#pragma unroll
-  for (int k = 0; k < kfp::kSums; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
-  }
-  const int nu = __popcll(__ballot(used)), ni = __popcll(__ballot(inl));
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kfp::kSums; ++k) sh[wv][k] = v[k];
-    sh_used[wv] = nu;
-    sh_inl[wv] = ni;
-  }
-  __syncthreads();
-  if (tid < kfp::kSums) d.part[(size_t)blockIdx.x * kfp::kSums + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
-  if (tid == 0) {
-    d.part_used[blockIdx.x] = (sh_used[0] + sh_used[1]) + (sh_used[2] + sh_used[3]);
-    d.part_inl[blockIdx.x] = (sh_inl[0] + sh_inl[1]) + (sh_inl[2] + sh_inl[3]);
-  }
+  kf_block_sums<true>(v, used, inl, sh, sh_used, sh_inl, d.part, d.part_used, d.part_inl);
 }
 
 // k_kf_pose_step for the list, one workgroup of 64 per hypothesis: lane k < 28 adds that hypothesis's first ceil(size / 256)
-// partials of sum k in index order from 0.0 (eight loads in flight, as k_kf_pose_step), lane 28 the used counts, lane 29 the inlier
-// counts; lane 0 then runs kfp::step_m (kfp::step, copied) on the hypothesis's result block and leaves the inlier count behind it. A hypothesis of size
-// 0 is left as the host wrote it.
+// partials of sum k in index order from 0.0 (kf_partial_sum, as k_kf_pose_step), lane 28 the used counts, lane 29 the inlier
+// counts; lane 0 then runs kfp::step on the hypothesis's result block and leaves the inlier count behind it. A hypothesis of size 0
+// is left as the host wrote it.
 __global__ __launch_bounds__(64) void k_kf_pose_step_many(const KfHypDesc* __restrict__ desc, int first, int last, int min_used) {
   __shared__ double S[kfp::kSums];
   __shared__ double ws[48];
@@ -3625,17 +3630,7 @@ __global__ __launch_bounds__(64) void k_kf_pose_step_many(const KfHypDesc* __res
   const double* __restrict__ part = d.part;
   const int tid = threadIdx.x;
   if (tid < kfp::kSums) {
-    double s = 0.0;
-    int b = 0;
-    for (; b + 8 <= nb; b += 8) {
-      double x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(b + u) * kfp::kSums + tid];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s = s + x[u];
-    }
-    for (; b < nb; ++b) s = s + part[(size_t)b * kfp::kSums + tid];
-    S[tid] = s;
+    S[tid] = kf_partial_sum(part, nb, tid);
   } else if (tid == kfp::kSums) {
     int u = 0;
     for (int b = 0; b < nb; ++b) u += d.part_used[b];
@@ -3649,7 +3644,7 @@ __global__ __launch_bounds__(64) void k_kf_pose_step_many(const KfHypDesc* __res
   if (tid == 0) {
     rebvio_hip_kf_pose* st = &d.res->pose;
     if (first) st->candidates = d.size;
-    kfp::step_m(S, sh_used, first, last, min_used, ws, st);
+    kfp::step(S, sh_used, first, last, min_used, ws, st);
     d.res->inliers = sh_inl;
   }
 }
@@ -3665,10 +3660,9 @@ void launch_kf_align_many_eval(hipStream_t s, const KParams& p, const MapDev& m,
 // kfp::fuse_term (kf_pose.hpp) is the definition's per-keyline statement. One thread per keyframe keyline, a stride loop behind the
 // grid's cap: the 16-byte record, the matches word and the 8-byte normal, then the two dependent gathers of the lookup; a fused
 // keyline stores its record and matches word back, every keyline its assoc word. The pose comes as kernel arguments (SGPRs). The
-// five counts are ballots summed per wave over the loop; lane 0 of each wave leaves them in LDS and five threads add the
-// workgroup's non-zero sums to cnt[1..5] with integer atomics (same-address atomics run one after the other at the memory side: one
-// set per workgroup, not per wave) - no floating-point value crosses threads. The size is read on the device (behind the snapshot
-// kernel in stream order), the stride from the grid.
+// five counts (associated, fused, gated, flat, clamped) are ballots summed per wave over the loop, which kf_add_counts adds to
+// cnt[1..5] - no floating-point value crosses threads. The size is read on the device (behind the snapshot kernel in stream order),
+// the stride from the grid.
 struct KfFusePose {
   double R[9], t[3];
 };
@@ -3680,12 +3674,8 @@ __global__ __launch_bounds__(256) void k_kf_fuse_depth(KParams p, MapDev m, cons
   __shared__ int sh_cnt[4][5];
   const int tid = threadIdx.x;
   const int n = min(*snap_n, p.kmax), stride = (int)gridDim.x * 256;
-  kfp::AlignMap c;
-  c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
-  c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
-  c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
-  c.cap = p.kmax;
-  int n_assoc = 0, n_fused = 0, n_gated = 0, n_flat = 0, n_clamped = 0;
+  const kfp::AlignMap c = kf_align_map(p, m);
+  int nc[5] = {0, 0, 0, 0, 0};
   for (int base = blockIdx.x * 256; base < n; base += stride) {  // (uniform over the workgroup: the ballots see whole waves)
     const int j = base + tid;
     int outcome = kfp::kFuseNone;
@@ -3707,21 +3697,13 @@ __global__ __launch_bounds__(256) void k_kf_fuse_depth(KParams p, MapDev m, cons
       }
       assoc[j] = outcome == kfp::kFuseNone ? (int)0x80000000 : outcome == kfp::kFuseFused ? i : -1 - i;
     }
-    n_assoc += __popcll(__ballot(outcome != kfp::kFuseNone));
-    n_fused += __popcll(__ballot(outcome == kfp::kFuseFused));
-    n_gated += __popcll(__ballot(outcome == kfp::kFuseGated));
-    n_flat += __popcll(__ballot(outcome == kfp::kFuseFlat));
-    n_clamped += __popcll(__ballot(clamped));
+    nc[0] += __popcll(__ballot(outcome != kfp::kFuseNone));
+    nc[1] += __popcll(__ballot(outcome == kfp::kFuseFused));
+    nc[2] += __popcll(__ballot(outcome == kfp::kFuseGated));
+    nc[3] += __popcll(__ballot(outcome == kfp::kFuseFlat));
+    nc[4] += __popcll(__ballot(clamped));
   }
-  if ((tid & 63) == 0) {
-    int* w = sh_cnt[tid >> 6];
-    w[0] = n_assoc; w[1] = n_fused; w[2] = n_gated; w[3] = n_flat; w[4] = n_clamped;
-  }
-  __syncthreads();
-  if (tid < 5) {
-    const int sum = (sh_cnt[0][tid] + sh_cnt[1][tid]) + (sh_cnt[2][tid] + sh_cnt[3][tid]);
-    if (sum) atomicAdd(cnt + 1 + tid, sum);
-  }
+  kf_add_counts(nc, sh_cnt, cnt + 1);
   if (blockIdx.x == 0 && tid == 0) cnt[0] = n;
 }
 
@@ -3811,8 +3793,8 @@ void launch_kf_point_cloud(hipStream_t s, const KParams& p, const void* snap_prs
 //                        store behind this one). So no pass compares a loser's key with its slot's.
 //   k_kf_handover_apply  one thread per dst keyline, the same cap and loop: the claim word, nothing more for an empty slot; else the
 //                        winner's staging record (one 8-byte gather) and the slot's record and matches word; steps 4..6.
-// Counts: ballots summed per wave over the loop, lane 0 of each wave leaves them in LDS, one integer atomic per workgroup and
-// non-zero count (k_kf_fuse_depth's form). No floating-point value crosses threads. Sizes are read on the device.
+// Counts: ballots summed per wave over the loop, then kf_add_counts (associated, out of range -> cnt[1..2]; claimed, adopted, kept,
+// conflict -> cnt[3..6]). No floating-point value crosses threads. Sizes are read on the device.
 __global__ __launch_bounds__(256) void k_kf_handover_claim(KParams p, MapDev m, const int* __restrict__ src_n, const int* __restrict__ dst_n,
                                                            const float4* __restrict__ prs, const unsigned* __restrict__ kf_matches,
                                                            const float2* __restrict__ normals, rebvio_hip_cloud_filter flt, double min_cos,
@@ -3822,12 +3804,8 @@ __global__ __launch_bounds__(256) void k_kf_handover_claim(KParams p, MapDev m, 
   __shared__ int sh_cnt[4][2];
   const int tid = threadIdx.x;
   const int n = min(*src_n, p.kmax), nd = min(*dst_n, p.kmax), stride = (int)gridDim.x * 256;
-  kfp::AlignMap c;
-  c.fm = p.fm; c.cx = p.cx; c.cy = p.cy; c.rows = p.rows; c.cols = p.cols;
-  c.df = m.df; c.df_nr = p.df_nr; c.ids = nullptr; c.dists = nullptr;
-  c.pos = reinterpret_cast<const kfp::AlignF2*>(m.pos); c.unit = reinterpret_cast<const kfp::AlignF2*>(m.unit);
-  c.cap = p.kmax;
-  int n_assoc = 0, n_range = 0;
+  const kfp::AlignMap c = kf_align_map(p, m);
+  int nc[2] = {0, 0};
   for (int base = blockIdx.x * 256; base < n; base += stride) {  // (uniform over the workgroup: the ballots see whole waves)
     const int j = base + tid;
     int outcome = kfp::kHoNone;
@@ -3846,18 +3824,10 @@ __global__ __launch_bounds__(256) void k_kf_handover_claim(KParams p, MapDev m, 
       }
       assoc[j] = outcome == kfp::kHoNone ? (int)0x80000000 : -1 - i;
     }
-    n_assoc += __popcll(__ballot(outcome != kfp::kHoNone));
-    n_range += __popcll(__ballot(outcome == kfp::kHoOutOfRange));
+    nc[0] += __popcll(__ballot(outcome != kfp::kHoNone));
+    nc[1] += __popcll(__ballot(outcome == kfp::kHoOutOfRange));
   }
-  if ((tid & 63) == 0) {
-    sh_cnt[tid >> 6][0] = n_assoc;
-    sh_cnt[tid >> 6][1] = n_range;
-  }
-  __syncthreads();
-  if (tid < 2) {
-    const int sum = (sh_cnt[0][tid] + sh_cnt[1][tid]) + (sh_cnt[2][tid] + sh_cnt[3][tid]);
-    if (sum) atomicAdd(cnt + 1 + tid, sum);
-  }
+  kf_add_counts(nc, sh_cnt, cnt + 1);
   if (blockIdx.x == 0 && tid == 0) cnt[0] = n;
 }
 
@@ -3869,7 +3839,7 @@ __global__ __launch_bounds__(256) void k_kf_handover_apply(int kmax, const int* 
   __shared__ int sh_cnt[4][4];
   const int tid = threadIdx.x;
   const int n = min(*src_n, kmax), nd = min(*dst_n, kmax), stride = (int)gridDim.x * 256;
-  int n_claimed = 0, n_adopted = 0, n_kept = 0, n_conflict = 0;
+  int nc[4] = {0, 0, 0, 0};
   for (int base = blockIdx.x * 256; base < nd; base += stride) {
     const int i = base + tid;
     int slot = kfp::kHoEmpty;
@@ -3890,20 +3860,12 @@ __global__ __launch_bounds__(256) void k_kf_handover_apply(int kmax, const int* 
         }
       }
     }
-    n_claimed += __popcll(__ballot(slot != kfp::kHoEmpty));
-    n_adopted += __popcll(__ballot(slot == kfp::kHoAdopted));
-    n_kept += __popcll(__ballot(slot == kfp::kHoKept));
-    n_conflict += __popcll(__ballot(slot == kfp::kHoConflict));
+    nc[0] += __popcll(__ballot(slot != kfp::kHoEmpty));
+    nc[1] += __popcll(__ballot(slot == kfp::kHoAdopted));
+    nc[2] += __popcll(__ballot(slot == kfp::kHoKept));
+    nc[3] += __popcll(__ballot(slot == kfp::kHoConflict));
   }
-  if ((tid & 63) == 0) {
-    int* w = sh_cnt[tid >> 6];
-    w[0] = n_claimed; w[1] = n_adopted; w[2] = n_kept; w[3] = n_conflict;
-  }
-  __syncthreads();
-  if (tid < 4) {
-    const int sum = (sh_cnt[0][tid] + sh_cnt[1][tid]) + (sh_cnt[2][tid] + sh_cnt[3][tid]);
-    if (sum) atomicAdd(cnt + 3 + tid, sum);
-  }
+  kf_add_counts(nc, sh_cnt, cnt + 3);
 }
 
 void launch_kf_handover(hipStream_t s, const KParams& p, const MapDev& m, int src_size, const int* src_size_dev, int dst_size,

@@ -85,8 +85,10 @@ int main() {
       rh::kfm::around(nullptr, I, t, field % 2 ? 0.03 : 1.5, field % 2 ? 0.12 : 40.0, h13);
       std::vector<rebvio_hip_kf_hyp_result> res(13), again(13);
       for (int h = 0; h < 13; ++h) {
-        rh::kfm::align_host(am, prs4.get(), mt.get(), field % 4 == 3 ? nullptr : nrm.get(), n, o, h13[h].R0, h13[h].t0, &res[(size_t)h]);
-        rh::kfm::align_host(am, prs4.get(), mt.get(), field % 4 == 3 ? nullptr : nrm.get(), n, o, h13[h].R0, h13[h].t0, &again[(size_t)h]);
+        rh::kfm::align_host(am, prs4.get(), mt.get(), field % 4 == 3 ? nullptr : nrm.get(), n, o, h13[h].R0, h13[h].t0, &res[(size_t)h].pose, nullptr,
+                             &res[(size_t)h].inliers);
+        rh::kfm::align_host(am, prs4.get(), mt.get(), field % 4 == 3 ? nullptr : nrm.get(), n, o, h13[h].R0, h13[h].t0, &again[(size_t)h].pose, nullptr,
+                             &again[(size_t)h].inliers);
         const rebvio_hip_kf_hyp_result& r = res[(size_t)h];
         CHECK(std::memcmp(&r, &again[(size_t)h], sizeof(r)) == 0);
         CHECK(r.pose.candidates == n && r.pose.used >= 0 && r.pose.used <= n && r.inliers >= 0 && r.inliers <= r.pose.used && r.reserved == 0);

@@ -8,6 +8,7 @@ from support import F32, KF_MATCH_DTYPE, rodrigues
 
 GUARD = 1e-9      # no term may come this close to a cell edge (px), to the gate or to the Huber switch where two sides are compared
 OFFSETS = ((0.005, 0.02), (0.02, 0.08))      # (rad along (1, -1, 1), units along (-1, 1, 1)) off the crafted motion
+LOOKUP_EXITS = ("Y.z", "border", "empty cell", "max_dist", "min_cos", "zero gradient")      # where a keyline can leave steps 2..6
 
 
 def unit_of(kl):
@@ -28,7 +29,8 @@ def offset_guess(rot, trans, sign=1.0):
 
 
 def _lookup(cam, prs4, normals, cur_pos, cur_unit, ids, dists, R, t, min_cos, max_dist):
-    """steps 2..5 of the definition for every keyframe keyline: (ok mask, owner i (0 where not ok), guards)"""
+    """steps 2..5 of the definition for every keyframe keyline: (ok mask, owner i (0 where not ok), guards); guards["why"] = the step
+    a keyline left at (LOOKUP_EXITS' order, 1-based; 0 where ok)"""
     fm, cx, cy, rows, cols = cam
     fm, cx, cy = F32(fm), F32(cx), F32(cy)
     R = np.asarray(R, np.float64).reshape(9)
@@ -46,6 +48,7 @@ def _lookup(cam, prs4, normals, cur_pos, cur_unit, ids, dists, R, t, min_cos, ma
         Z = [(R[3 * r] * a + R[3 * r + 1] * b) + R[3 * r + 2] for r in range(3)]
         Y = [Z[r] + rho * t[r] for r in range(3)]
         ok = Y[2] > 0
+        why = np.where(ok, 0, 1)
         px, py = Y[0] / Y[2], Y[1] / Y[2]
         u = np.float64(fm) * px + np.float64(cx)
         v = np.float64(fm) * py + np.float64(cy)
@@ -53,11 +56,14 @@ def _lookup(cam, prs4, normals, cur_pos, cur_unit, ids, dists, R, t, min_cos, ma
         x, y = np.floor(uh), np.floor(vh)
         projected = ok.copy()
         ok &= (x >= 1) & (x <= cols - 2) & (y >= 1) & (y <= rows - 2)
+        why[(why == 0) & ~ok] = 2
         cell = np.where(ok, y * cols + x, 0).astype(np.int64)
         i = ids[cell] if len(ids) else np.zeros(n, np.int64)
         d = dists[cell] if len(ids) else np.zeros(n, np.int64)
         ok &= i >= 0
+        why[(why == 0) & ~ok] = 3
         ok &= d <= max_dist
+        why[(why == 0) & ~ok] = 4
         i = np.where(ok, i, 0)
         ni = unit[i].astype(np.float64) if len(unit) else np.zeros((n, 2))
         gate_d = np.full(n, np.inf)
@@ -72,10 +78,11 @@ def _lookup(cam, prs4, normals, cur_pos, cur_unit, ids, dists, R, t, min_cos, ma
             gated = ok & (mm > 0) & (nn > 0)
             gate_d[gated] = np.abs(dot - bound)[gated]
             ok &= ~gated | (dot >= bound)
+            why[(why == 0) & ~ok] = 5
         # distance of u + 0.5 / v + 0.5 from the nearest integer: how close the projection is to a cell edge (all projected terms)
         edge = np.minimum(np.abs(uh - np.rint(uh)), np.abs(vh - np.rint(vh)))
         edge = np.where(projected & np.isfinite(edge), edge, np.inf)
-    return ok, i, dict(edge=edge, gate=gate_d)
+    return ok, i, dict(edge=edge, gate=gate_d, why=why)
 
 
 def _residual(fm, prs4, q, unit, i, R, t):
@@ -244,3 +251,67 @@ def craft_kf_keylines(base, A, n=None):
     kf["gradient"][:n] = (F32(10.0) * A["normals"][:n]).astype(F32)
     kf["gradient_norm"][:n] = F32(10.0)
     return kf
+
+
+def lookup_case(cam, pos, unit, ids, dists, A, room, zero_gradient):
+    """The keyframe keylines of `A` (craft_against) with one planted keyline per exit of LOOKUP_EXITS behind them, `room` keylines
+    at the most, for the crafted motion and the default filter. The plants are made like the crafted keylines: the point of a
+    current pixel, 0.2 px off its cell's centre, at depth 1, taken back through the crafted motion.
+      Y.z            pos_img = (-30 fm, 0): Z.z = R[2, 0] (-30) + R[2, 2] < 0, and rho 0.5 adds only 0.05
+      border         a pixel of column 0
+      empty cell     the first cell inside the border that no keyline reaches
+      max_dist       the cell inside the border farthest from its owner, at max_dist = that distance less one
+      min_cos        the cell of a keyline that owns it, with the normal turned by a quarter
+      zero gradient  no plant: the unit of one crafted keyline's owner is set to zero in the returned copy of `unit`. Only where the
+                     caller hands the arrays over itself (zero_gradient): a detected map has no such keyline.
+    Returns dict(prs4, kf_matches, normals, pos, unit, ids, dists, max_dist, plants {exit: keyframe keyline})."""
+    fm, cx, cy, rows, cols = cam
+    R, t = true_motion()
+    ids2, dists2 = np.asarray(ids).reshape(rows, cols), np.asarray(dists).reshape(rows, cols)
+    pos, unit = np.asarray(pos, F32).reshape(-1, 2), np.array(unit, F32).reshape(-1, 2)
+    inner = np.zeros((rows, cols), bool)
+    inner[1:rows - 1, 1:cols - 1] = True
+    ey, ex = np.argwhere((ids2 < 0) & inner)[0]
+    far = np.where((ids2 >= 0) & inner, dists2, -1)
+    fy, fx = np.unravel_index(far.argmax(), far.shape)
+    max_dist = int(dists2[fy, fx]) - 1
+    assert max_dist >= 1
+    own = A["owner"]
+    centred = [k for k, i in enumerate(own) if np.abs(pos[i] - np.round(pos[i])).max() < 0.3]
+    k_cos, k_zero = centred[0], centred[1]
+    gx, gy = np.round(pos[own[k_cos]]).astype(int)
+    un = unit[own[k_cos]].astype(np.float64)
+
+    def onto(x, y, normal):
+        ray = np.array([(x + 0.2 - np.float64(F32(cx))) / np.float64(F32(fm)), (y - 0.2 - np.float64(F32(cy))) / np.float64(F32(fm)), 1.0])
+        X = R.T @ (ray - t)
+        n = R[:2, :2].T @ np.asarray(normal, np.float64)
+        return [fm * X[0] / X[2], fm * X[1] / X[2], 1.0 / X[2], 0.05 / X[2]], n / np.linalg.norm(n)
+
+    made = {"Y.z": ([-30.0 * fm, 0.0, 0.5, 0.025], un), "border": onto(0, rows // 2, un), "empty cell": onto(ex, ey, un),
+            "max_dist": onto(fx, fy, unit[ids2[fy, fx]].astype(np.float64)), "min_cos": onto(gx, gy, (-un[1], un[0]))}
+    n = min(len(A["prs4"]), room - len(made))
+    assert n > k_zero
+    plants = {name: n + k for k, name in enumerate(made)}
+    if zero_gradient:
+        unit[own[k_zero]] = 0
+        plants["zero gradient"] = k_zero
+    return dict(prs4=np.concatenate([A["prs4"][:n], np.array([m[0] for m in made.values()], F32)]).astype(F32),
+                kf_matches=np.full(n + len(made), 3, np.uint32),
+                normals=np.concatenate([A["normals"][:n], np.array([m[1] for m in made.values()], F32)]).astype(F32),
+                pos=pos, unit=unit, ids=np.asarray(ids).reshape(-1), dists=np.asarray(dists).reshape(-1), max_dist=max_dist, plants=plants)
+
+
+def assert_lookup_case_is_not_vacuous(cam, prs4, normals, pos, unit, ids, dists, max_dist, plants, flt_ok):
+    """On the restatement, at the crafted motion and min_cos 0.9: every planted keyline leaves the lookup at its own exit and at least
+    half of all keyframe keylines (flt_ok: those that pass the filter) come through with an owner whose gradient has a direction.
+    Returns that mask."""
+    R, t = true_motion()
+    ok, i, g = _lookup(cam, prs4, normals, pos, unit, ids, dists, R, t, 0.9, max_dist)
+    zero = ok & ~((np.asarray(unit, F32).reshape(-1, 2)[i].astype(np.float64) ** 2).sum(1) > 0)
+    why = np.where(zero, 6, g["why"])
+    for name, j in plants.items():
+        assert flt_ok[j] and why[j] == 1 + LOOKUP_EXITS.index(name), (name, j, int(why[j]))
+    assoc = ok & ~zero & flt_ok
+    assert 2 * int(assoc.sum()) >= len(prs4), (int(assoc.sum()), len(prs4))
+    return assoc
