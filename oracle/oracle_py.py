@@ -133,6 +133,9 @@ def lib(path: str | None = None):
         "orc_regularize_cfg": (C.c_int, [vp, vp]),
         "orc_update_inverse_depth": (None, [vp, fp]),
         "orc_reset_state": (None, [vp]),
+        "orc_gyro_state": (None, [vp, fp, fp]),
+        "orc_set_gyro_state": (None, [vp, fp, fp]),
+        "orc_gyro_bias_correction": (None, [fp, fp, fp, fp, fp, fp]),
         "orc_track_pair": (C.c_int, [vp, vp, vp, fp, C.c_float, C.POINTER(PairOut)]),
         "orc_vio_reset": (None, [vp, fp, fp]),
         "orc_vio_add_imu": (None, [vp, vp, C.c_uint64, fp, fp]),
@@ -174,6 +177,18 @@ def default_params(rows: int, cols: int, **over) -> Params:
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def gyro_bias_correction(X, Wx, Wb, Rg, Rb):
+    """The oracle's Core::gyroBiasCorrection on copies of the inputs: (X[6], Wx[6, 6], Wb[3, 3], dgbias[3]) afterwards."""
+    X, px = _f(np.array(X, np.float32).reshape(6))
+    Wx, pwx = _f(np.array(Wx, np.float32).reshape(36))
+    Wb, pwb = _f(np.array(Wb, np.float32).reshape(9))
+    Rg, prg = _f(np.asarray(Rg).reshape(9))
+    Rb, prb = _f(np.asarray(Rb).reshape(9))
+    dg = np.zeros(3, np.float32)
+    lib().orc_gyro_bias_correction(px, pwx, pwb, prg, prb, dg.ctypes.data_as(C.POINTER(C.c_float)))
+    return X, Wx.reshape(6, 6), Wb.reshape(3, 3), dg
 
 
 class Map:
@@ -385,6 +400,19 @@ class Oracle:
 
     def reset_state(self):
         self.L.orc_reset_state(self.h)
+
+    def gyro_state(self):
+        """(Bg[3], W_Bg[3, 3]) of the pair glue's gyro-bias filter, as backend.Context.gyro_state"""
+        bg = np.zeros(3, np.float32)
+        w = np.zeros(9, np.float32)
+        fp = C.POINTER(C.c_float)
+        self.L.orc_gyro_state(self.h, bg.ctypes.data_as(fp), w.ctypes.data_as(fp))
+        return bg, w.reshape(3, 3)
+
+    def set_gyro_state(self, bg, w_bg):
+        bg, pb = _f(np.asarray(bg).reshape(3))
+        w, pw = _f(np.asarray(w_bg).reshape(9))
+        self.L.orc_set_gyro_state(self.h, pb, pw)
 
     def track_pair(self, old: Map, new: Map, R_prior=None, frame_dt=0.05) -> PairOut:
         out = PairOut()

@@ -1612,6 +1612,22 @@ void orc_reset_state(orc_ctx* c) {
   orc_ls4_reset(c);
 }
 
+void orc_gyro_state(orc_ctx* c, float Bg[3], float W_Bg[9]) {
+  for (int i = 0; i < 3; ++i) Bg[i] = c->Bg[i];
+  m3_to(c->W_Bg, W_Bg);
+}
+
+void orc_set_gyro_state(orc_ctx* c, const float Bg[3], const float W_Bg[9]) {
+  for (int i = 0; i < 3; ++i) c->Bg[i] = Bg[i];
+  c->W_Bg = m3_from(W_Bg);
+}
+
+void orc_gyro_bias_correction(float X[6], float Wx[36], float Wb[9], const float Rg[9], const float Rb[9], float dgbias[3]) {
+  M3 W = m3_from(Wb);
+  gyro_bias_correction(X, Wx, W, m3_from(Rg), m3_from(Rb), dgbias);
+  m3_to(W, Wb);
+}
+
 static std::string g_orc_err;
 const char* orc_last_error(void) { return g_orc_err.c_str(); }
 

@@ -156,6 +156,12 @@ void orc_smooth_n(orc_ctx* c, const float* img, float sigma, int n, float* out, 
 
 /* Persistent gyro-bias state of the glue (imu.hpp:180-183): reset to the reference's initial values */
 void orc_reset_state(orc_ctx* c);
+/* ... read and replaced: Bg and W_Bg (row-major), what rebvio_hip_get_gyro_state / rebvio_hip_set_gyro_state hand over */
+void orc_gyro_state(orc_ctx* c, float Bg[3], float W_Bg[9]);
+void orc_set_gyro_state(orc_ctx* c, const float Bg[3], const float W_Bg[9]);
+/* Core::gyroBiasCorrection (core.cpp:264-284) as orc_track_pair calls it: X, Wx, Wb in and out, Rg / Rb the two observation
+ * noise matrices, dgbias the returned bias increment. Matrices row-major. */
+void orc_gyro_bias_correction(float X[6], float Wx[36], float Wb[9], const float Rg[9], const float Rb[9], float dgbias[3]);
 /* One frame pair: rebvio.cpp:142-259 without the accelerometer/SAB fusion (the branch taken for the
  * first 4+init_bias_frame_num frames). R_prior = IMU inter-frame rotation (NULL = identity). */
 int orc_track_pair(orc_ctx* c, orc_map* old_map, orc_map* new_map, const float* R_prior, float frame_dt,

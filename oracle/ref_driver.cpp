@@ -237,6 +237,26 @@ void ref_update_inverse_depth(ref_ctx* c, const float vel[3]) {
   c->core->updateInverseDepth(v);
 }
 
+/* ---- inertial glue: the one function of it that is public and keeps no state between calls ---- */
+void ref_gyro_bias_correction(ref_ctx* c, float X[6], float Wx[36], float Wb[9], const float Rg[9], const float Rb[9], float dgbias[3]) {
+  rebvio::types::Vector6f x;
+  rebvio::types::Matrix6f W;
+  for (int i = 0; i < 6; ++i) {
+    x[i] = X[i];
+    for (int j = 0; j < 6; ++j) W(i, j) = Wx[i * 6 + j];
+  }
+  rebvio::types::Matrix3f B = mat3(Wb);
+  const rebvio::types::Vector3f d = c->core->gyroBiasCorrection(x, W, B, mat3(Rg), mat3(Rb));
+  for (int i = 0; i < 6; ++i) {
+    X[i] = x[i];
+    for (int j = 0; j < 6; ++j) Wx[i * 6 + j] = W(i, j);
+  }
+  for (int i = 0; i < 3; ++i) {
+    dgbias[i] = d[i];
+    for (int j = 0; j < 3; ++j) Wb[i * 3 + j] = B(i, j);
+  }
+}
+
 /* ---- single-keyline forms ---- */
 int ref_search_match(ref_ctx*, ref_map* searched, const orc_keyline* query, const float vel[3], const float Rvel[9],
                      const float Rback[9], float max_radius) {

@@ -1,7 +1,10 @@
 // Stand-in for <TooN/Cholesky.h> (TEST INFRASTRUCTURE, see TooN/TooN.h). TooN documents Cholesky<N> as the square-root-free
 // decomposition A = L D L^T of a symmetric matrix, computed column by column in one square array (the unit-lower L below the
 // diagonal, D on it), and get_inverse() as the back-substitution of the identity, column by column: forward through L, the
-// division by D, backward through L^T. No test compares a value computed here (only Core's inertial glue calls it).
+// division by D, backward through L^T. Only Core's inertial glue calls it. What is computed here is compared since
+// Core::gyroBiasCorrection is (tests/test_reference_pin.py, tests/test_reference_pin_gpu.py): the oracle's, the host's and the
+// device's 6x6 inverse have to give the floats of get_inverse() below. That pins them to THIS reading of TooN's Cholesky, which
+// the reference library shares with them - not to TooN's own file, which is not here to be compiled.
 #ifndef REBVIO_REF_SHIM_TOON_CHOLESKY_H_
 #define REBVIO_REF_SHIM_TOON_CHOLESKY_H_
 

@@ -633,6 +633,99 @@ def assert_donor_pair(po, old_after, idx, varied):
 
 
 # ---- stream and pair drivers --------------------------------------------------------------------------------------------
+# frame stamps off the one interval TS (tests/test_frame_interval_gpu.py, tests/test_reference_pin.py): the steps in microseconds
+# between the twelve frames of small_stream. On the CPU oracle (KW_TRACK, sums in device order) all eleven pairs end with status 0.
+STEPS_HEALTHY = (50000, 33333, 33334, 100000, 20000, 5000, 1000000, 40000, 1000, 200000, 50000)
+EUROC_T0 = 1403636579763555      # an absolute stamp of the size EuRoC's are
+# the frame intervals (s) the gyroBiasCorrection cases run at: the last two are a repeated stamp and a stamp that goes back by
+# 40 ms (the uint64 difference as a float)
+DT_GRID = (1, 0.2, 0.1, 0.05, 0.0333333, 0.02, 0.005, 0.001, 2e-4, 1.9e-4, 1.5e-4, 1e-6, 0, 1.8446744e13)
+
+
+def stamps_from(steps, t0=0):
+    """frame stamps (python ints, microseconds): t0, then one step further per frame"""
+    out = [int(t0)]
+    for d in steps:
+        out.append(out[-1] + int(d))
+    return out
+
+
+def default_stamps(n, stamps=None):
+    """the stamps of n frames: k * TS unless a list is given"""
+    if stamps is None:
+        return [k * TS for k in range(n)]
+    assert len(stamps) == n, (len(stamps), n)
+    return [int(t) for t in stamps]
+
+
+def frame_dt_of(ts_old, ts_new):
+    """The interval between two stamps as the reference forms it (rebvio.cpp:183): the uint64 difference (it wraps when the
+    stamps go back), to float, divided by 1e6 in double, to float."""
+    d = np.uint64((int(ts_new) - int(ts_old)) % (1 << 64))
+    return float(np.float32(np.float64(np.float32(d)) / 1000000.0))
+
+
+def gyro_noise(p, frame_dt):
+    """(s_g, s_b): the diagonals of RGyro and RGBias (rebvio.cpp:186-187) in fp32, std_dev * std_dev * dt * dt from left to right;
+    p: a parameter record of either library."""
+    with np.errstate(all="ignore"):
+        dt = F32(frame_dt)
+        a, b = F32(p.gyro_std_dev), F32(p.gyro_bias_std_dev)
+        return F32(F32(F32(a * a) * dt) * dt), F32(F32(F32(b * b) * dt) * dt)
+
+
+# the input families of the glue probe (tests/test_parity_gpu.py: test_glue_probe_random_inputs), one fixed draw each; the last one
+# runs at every decade of W_Bg
+GLUE_FAMILIES = ("well-conditioned", "rank-deficient", "zero-rotation", "nan-entry", "wbg-decades")
+WBG_DECADES = tuple(range(-2, 7))
+
+
+def glue_family(name, decade=4):
+    """One extRotVel system of a family, as the pair glue takes it and as gyroBiasCorrection takes it. Block records xrv[nb, 32]
+    (21 upper-triangle sums, 6 of JtF, the count) for n_new keylines; Wx[6, 6] and X[6]: their sum in fp32 and the least-squares
+    solution in double, rounded (the device forms its own from xrv); minimizeVel's vel and JtJ6; Bg; a symmetric W_Bg around
+    10^decade; a prior rotation."""
+    k = GLUE_FAMILIES.index(name)
+    rng = np.random.default_rng(100 + k)
+    n_new = 700 + 37 * k
+    nb = (n_new + 255) // 256
+    rows = rng.standard_normal((nb, 300, 6)) * np.array([400.0, 400.0, 200.0, 500.0, 500.0, 300.0])
+    if name == "rank-deficient":
+        rows[:, :, 5] = rows[:, :, 4] * 2.0
+    if name == "zero-rotation":
+        rows[:, :, 3:] = 0.0
+    Y = rng.standard_normal((nb, 300)) * 0.3
+    xrv = np.zeros((nb, 32), F32)
+    iu = np.triu_indices(6)
+    for b in range(nb):
+        xrv[b, :21] = (rows[b].T @ rows[b])[iu]
+        xrv[b, 21:27] = rows[b].T @ Y[b]
+        xrv[b, 27] = 300
+    if name == "nan-entry":
+        xrv[0, 2] = np.nan
+    acc = xrv.astype(np.float64).sum(0)
+    Wx = np.zeros((6, 6))
+    Wx[iu] = acc[:21]
+    Wx = (Wx + np.triu(Wx, 1).T).astype(F32)
+    with np.errstate(all="ignore"):
+        X = (np.linalg.pinv(Wx.astype(np.float64)) @ acc[21:27] if np.isfinite(Wx).all() else np.full(6, np.nan)).astype(F32)
+    J = rng.standard_normal((200, 3)) * [300.0, 300.0, 150.0]
+    JtJ = J.T @ J
+    W_Bg = np.eye(3) * 10.0 ** decade * rng.uniform(1, 3) + rng.standard_normal((3, 3)) * 1e-3
+    return dict(xrv=xrv, n_new=n_new, Wx=Wx, X=X, vel=(rng.standard_normal(3) * 0.01).astype(F32),
+                JtJ6=np.array([JtJ[0, 0], JtJ[1, 1], JtJ[2, 2], JtJ[0, 1], JtJ[0, 2], JtJ[1, 2]], F32),
+                Bg=(rng.standard_normal(3) * 3e-4).astype(F32), W_Bg=((W_Bg + W_Bg.T) / 2).astype(F32),
+                R_prior=rodrigues(rng.standard_normal(3) * 1e-2).astype(F32))
+
+
+GLUE_GBC = os.path.join(ROOT, "tests", "golden", "glue_gbc_reference.npz")   # tests/golden/make_glue_gbc.py
+
+
+def glue_family_cases():
+    """(family, decade of W_Bg) for every case of the gyroBiasCorrection grids"""
+    return [(f, 4) for f in GLUE_FAMILIES[:-1]] + [(GLUE_FAMILIES[-1], d) for d in WBG_DECADES]
+
+
 def set_forms(monkeypatch, lm=None, threads=None, head=None, batch_head=None, **env):
     """The kernel forms a context reads when it is created, and any further variables by name (env); None = the library's default."""
     forms = dict(REBVIO_HIP_LM=lm, REBVIO_HIP_LM_THREADS=threads, REBVIO_HIP_DM_HEAD=head, REBVIO_HIP_BATCH_DM_HEAD=batch_head)
@@ -643,14 +736,14 @@ def set_forms(monkeypatch, lm=None, threads=None, head=None, batch_head=None, **
             monkeypatch.setenv(name, str(v))
 
 
-def run_stream(ctx, dev, order, npx, k0=0, ts_step=50000):
+def run_stream(ctx, dev, order, npx, k0=0, ts_step=50000, stamps=None):
     """Push order[] through the streaming driver and flush: every pair's (record, keyline count), in pair order - len(order) - 1
     of them. Records come back several pushes late (the pair step runs on the device from end to end, pairs are queued in
     groups and the host reads them up to fifteen pairs behind); the flush tracks the pairs not started yet and delivers the
-    rest."""
+    rest. stamps: one per frame, in place of (k0 + k) * ts_step."""
     recs = []
     for k, i in enumerate(order):
-        out, n = ctx.push_frame_u8_device(dev + int(i) * npx, (k0 + k) * ts_step)
+        out, n = ctx.push_frame_u8_device(dev + int(i) * npx, (k0 + k) * ts_step if stamps is None else int(stamps[k]))
         if out.status >= 0:
             recs.append((out, n))
     recs.extend(ctx.flush())
@@ -723,31 +816,36 @@ def set_new_map(P, kl):
     P.gm[1].upload(kl)
 
 
-def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, what, every_pair_tracks=False, expect_status=None):
+def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, what, every_pair_tracks=False, expect_status=None,
+                                  stamps=None):
     """frames[order] through the oracle (keyline sums in the kernels' order) and through the library, the state carried
     independently on both sides: every word of every pair record equal through the per-pair API and through the streaming
     driver, every keyline field of the newest map equal after the last pair. every_pair_tracks: a precondition on the oracle
     alone - each pair ends with status 0 and at least global_min_matches_threshold LM matches (a real pair, not a failure
     path); without it only the last pair is asked for motion and more than min_klm matches. expect_status: the oracle's pair
-    statuses, one per pair - asked for in place of that closing condition, for streams whose pairs are meant to fail."""
+    statuses, one per pair - asked for in place of that closing condition, for streams whose pairs are meant to fail. stamps:
+    one per frame in place of k * TS - the oracle and the per-pair API get frame_dt_of the pair's two stamps, the streaming
+    driver the stamps alone. Returns the oracle's records as words."""
     W, H, npairs = cam.width, cam.height, len(order) - 1
+    ts = default_stamps(len(order), stamps)
     p_o = params_for(orc_mod, cam, **kw)
     orc = orc_mod.Oracle(p_o)
     orc.set_sum_order("device")
     gpu = B.Context(params_for(B, cam, **kw))
     mo, mg, rec_o, status_o = [], [], [], []
     for k, i in enumerate(order):
-        mo.append(orc.detect_u8(frames[i], k * 50000))
-        mg.append(gpu.detect_u8(frames[i], k * 50000))
+        mo.append(orc.detect_u8(frames[i], ts[k]))
+        mg.append(gpu.detect_u8(frames[i], ts[k]))
         if len(mo) > 2:
             mo.pop(0)
             mg.pop(0).release()
         if k == 0:
             continue
-        po = orc.track_pair(mo[0], mo[1])
+        dt = frame_dt_of(ts[k - 1], ts[k])
+        po = orc.track_pair(mo[0], mo[1], frame_dt=dt)
         if every_pair_tracks:
             assert po.status == 0 and po.klm_num >= p_o.global_min_matches_threshold, (what, k, po.status, po.klm_num)
-        pg = gpu.track_pair(mg[0], mg[1])
+        pg = gpu.track_pair(mg[0], mg[1], frame_dt=dt)
         wo, wg = record_words(po), record_words(pg)
         assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8], np.array(po.Vg), np.array(pg.Vg))
         rec_o.append(wo)
@@ -764,7 +862,7 @@ def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, w
     dev = ctx.upload_frames(frames)
     got = []
     for k, i in enumerate(order):
-        out, _ = ctx.push_frame_u8_device(dev + int(i) * W * H, k * 50000)
+        out, _ = ctx.push_frame_u8_device(dev + int(i) * W * H, ts[k])
         if out.status >= 0:
             got.append(record_words(out))
     for out, _ in ctx.flush():
@@ -773,42 +871,47 @@ def assert_pipeline_bit_identical(orc_mod, B, frames, cam, order, kw, min_klm, w
     assert len(got) == len(rec_o) == npairs
     for k, (wo, wg) in enumerate(zip(rec_o, got)):
         assert np.array_equal(wo, wg), (what, k, np.flatnonzero(wo != wg)[:8])
+    return rec_o
 
 
 # ---- the three runners of a stream with per-frame rotations: oracle, per-pair API, streaming driver -----------------------
-def oracle_pairs(orc_mod, cam, seq, R, keep=(), **kw):
+def oracle_pairs(orc_mod, cam, seq, R, keep=(), stamps=None, **kw):
     """seq[] through the CPU oracle alone, keyline sums in the kernels' order; R = None: no priors. (records, keyline counts);
-    keep: pair numbers after which the keylines of both maps are kept - [(records, keyline counts), {pair: (old, new)}]"""
+    keep: pair numbers after which the keylines of both maps are kept - [(records, keyline counts), {pair: (old, new)}];
+    stamps: one per frame in place of k * TS, every pair run at frame_dt_of its two stamps"""
     orc = orc_mod.Oracle(params_for(orc_mod, cam, **kw))
     orc.set_sum_order("device")
+    ts = default_stamps(len(seq), stamps)
     recs, prev, kept = [], None, {}
     for k, f in enumerate(seq):
-        m = orc.detect_u8(f, k * TS)
+        m = orc.detect_u8(f, ts[k])
         if prev is not None:
-            recs.append((orc.track_pair(prev, m, R_prior=None if R is None else R[k]), m.size()))
+            recs.append((orc.track_pair(prev, m, R_prior=None if R is None else R[k], frame_dt=frame_dt_of(ts[k - 1], ts[k])), m.size()))
             if k - 1 in keep:
                 kept[k - 1] = (prev.keylines(), m.keylines())
         prev = m
     return (recs, kept) if keep else recs
 
 
-def lib_pairs(B, cam, seq, R, mask=None, keep=(), **kw):
+def lib_pairs(B, cam, seq, R, mask=None, keep=(), stamps=None, **kw):
     """per-pair API: detect (+ per-frame mask) and rebvio_hip_track_pair(R_prior = R[k]); (records as words, gyro state);
-    keep: as oracle_pairs - (records as words, gyro state, {pair: (old, new)})"""
+    keep: as oracle_pairs - (records as words, gyro state, {pair: (old, new)}); stamps: as oracle_pairs"""
     ctx = B.Context(params_for(B, cam, **kw))
+    ts = default_stamps(len(seq), stamps)
     npx = cam.width * cam.height
     dev = ctx.upload_frames(seq)
     mdev = ctx.upload_frames(mask[None]) if mask is not None else None
     maps, recs, kept = [], [], {}
     for k in range(len(seq)):
         if mdev is None:
-            maps.append(ctx.detect_u8_device(dev + k * npx, k * TS))
+            maps.append(ctx.detect_u8_device(dev + k * npx, ts[k]))
         else:
-            maps.append(ctx.detect_px_masked_device(dev + k * npx, B.PX_GRAY8, mdev, k * TS))
+            maps.append(ctx.detect_px_masked_device(dev + k * npx, B.PX_GRAY8, mdev, ts[k]))
         if len(maps) > 2:
             maps.pop(0).release()
         if k:
-            recs.append(rec(ctx.track_pair(maps[0], maps[1], R_prior=None if R is None else R[k]), maps[1].size()))
+            recs.append(rec(ctx.track_pair(maps[0], maps[1], R_prior=None if R is None else R[k], frame_dt=frame_dt_of(ts[k - 1], ts[k])),
+                            maps[1].size()))
             if k - 1 in keep:
                 kept[k - 1] = (maps[0].keylines(), maps[1].keylines())
     st = ctx.gyro_state()
@@ -816,11 +919,13 @@ def lib_pairs(B, cam, seq, R, mask=None, keep=(), **kw):
     return (recs, state_words(st), kept) if keep else (recs, state_words(st))
 
 
-def lib_stream(B, cam, seq, R, mask=None, host=False, flush_after=(), entry="gyro", profile=False, **kw):
+def lib_stream(B, cam, seq, R, mask=None, host=False, flush_after=(), entry="gyro", profile=False, stamps=None, **kw):
     """streaming driver: seq[k] pushed with R[k] (None: NULL) through the gyro entries (entry = "u8": the existing
     push_frame_u8_device, R unused); flush_after: frame counts after which rebvio_hip_flush is called mid-stream.
+    stamps: one per frame in place of k * TS (the driver forms every interval itself).
     (records as words, gyro state after the closing flush[, kernel launches counted by the profiler])"""
     ctx = B.Context(params_for(B, cam, **kw))
+    ts = default_stamps(len(seq), stamps)
     npx = cam.width * cam.height
     dev = ctx.upload_frames(seq)
     mdev = ctx.upload_frames(mask[None]) if mask is not None else None
@@ -830,11 +935,11 @@ def lib_stream(B, cam, seq, R, mask=None, host=False, flush_after=(), entry="gyr
     recs = []
     for k in range(len(seq)):
         if entry == "u8":
-            out, n = ctx.push_frame_u8_device(dev + k * npx, k * TS)
+            out, n = ctx.push_frame_u8_device(dev + k * npx, ts[k])
         elif host:
-            out, n = ctx.push_frame_px_gyro(np.ascontiguousarray(seq[k]), B.PX_GRAY8, R[k], k * TS)
+            out, n = ctx.push_frame_px_gyro(np.ascontiguousarray(seq[k]), B.PX_GRAY8, None if R is None else R[k], ts[k])
         else:
-            out, n = ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, R[k], mdev, k * TS)
+            out, n = ctx.push_frame_px_gyro_device(dev + k * npx, B.PX_GRAY8, None if R is None else R[k], mdev, ts[k])
         if out.status >= 0:
             recs.append(rec(out, n))
         if k + 1 in flush_after:
@@ -1017,6 +1122,23 @@ def ref_mod():
         pytest.skip("neither oracle/_ref/librebvio_ref.so nor a reference checkout to build it from")
     ref_py.lib()
     return ref_py
+
+
+@pytest.fixture(scope="module")
+def host_math_tool(tmp_path_factory, host_lib):
+    """tests/cpp/host_math_dump.cpp compiled against the host library: run(mode, float32 values) -> its float32 output"""
+    exe = str(tmp_path_factory.mktemp("hostmath") / "host_math_dump")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "host_math_dump.cpp"), "-o", exe, "-L", BUILD, "-lrebvio", "-lrebvio_hip",
+                    f"-Wl,-rpath,{BUILD}", "-pthread"], check=True)
+
+    def run(mode, values, tmp=os.path.dirname(exe)):
+        fi, fo = os.path.join(tmp, "in.f32"), os.path.join(tmp, "out.f32")
+        np.asarray(values, np.float32).tofile(fi)
+        r = subprocess.run([exe, mode, fi, fo], capture_output=True, text=True)
+        assert r.returncode == 0, (mode, r.returncode, r.stderr)
+        return np.fromfile(fo, np.float32)
+    return run
 
 
 @pytest.fixture(scope="module")

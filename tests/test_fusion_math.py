@@ -11,31 +11,18 @@ Everything here is stated in float64 numpy from the mathematical definition, not
     and the defining properties of the minimal rotation.
 Runs on the CPU (host code only)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 from scipy.linalg import expm, logm
 
-from support import BUILD, ROOT
+from support import ROOT
+from support import host_lib, host_math_tool  # noqa: F401
 
 
 @pytest.fixture(scope="module")
-def tool(tmp_path_factory):
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "csrc")], check=True)
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "rebvio_amd", "host")], check=True)
-    exe = str(tmp_path_factory.mktemp("hostmath") / "host_math_dump")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "host_math_dump.cpp"), "-o", exe, "-L", BUILD, "-lrebvio", "-lrebvio_hip",
-                    f"-Wl,-rpath,{BUILD}", "-pthread"], check=True)
-
-    def run(mode, values, tmp=os.path.dirname(exe)):
-        fi, fo = os.path.join(tmp, "in.f32"), os.path.join(tmp, "out.f32")
-        np.asarray(values, np.float32).tofile(fi)
-        r = subprocess.run([exe, mode, fi, fo], capture_output=True, text=True)
-        assert r.returncode == 0, (mode, r.returncode, r.stderr)
-        return np.fromfile(fo, np.float32).astype(np.float64)
-    return run
+def tool(host_math_tool):  # noqa: F811
+    return lambda mode, values: host_math_tool(mode, values).astype(np.float64)
 
 
 def skew(v):

@@ -12,6 +12,12 @@ plane_fit_size is a compile-time constant of the reference (edge_detector.hpp) -
 test_detect_params_gpu cannot change it - and the other function-local statics (the Ls4 and mean-acceleration histories) belong to
 glue that no case here calls. So no case needs a second value of such a static and none runs in a child process.
 
+Of the inertial glue one function is compared: Core::gyroBiasCorrection (core.cpp:264-284; public, no static state) gives the
+expected X, Wx, Wb and dgbias for the oracle's gyro_bias_correction and for the host's (hm::gyro_bias_correction behind the host
+class's Core::gyroBiasCorrection, through tests/cpp/host_math_dump.cpp) - on what a chain of eleven pairs at ten different frame
+intervals feeds it, and on the input families of the device glue's probe at the fourteen intervals of support.DT_GRID. The frame
+interval and the two noise matrices, which the reference forms in rebvio.cpp around the call, are formed here in numpy.
+
 The anchor. Core::tryVel (core.cpp:120-141) stores fabs(fi) as a keyline's residual although calculatefJ leaves fi unset on its
 two early returns; fi is an uninitialised local. For a keyline that comes after a matched one the compiled code finds the matched
 one's value there, which is the oracle's rule too ("Decisions for undefined behaviour"). BEFORE the first matched
@@ -32,18 +38,23 @@ NOT COMPARED, because the reference does not define them or gives no access:
     arguments ScaleSpace gives its own; the detector's dense mask and auto threshold (private): the map's mask() and threshold()
     carry them; Core's DistanceField (private): a DistanceField of the driver's own, built from the same map;
   - minimizeVel's accept mask and quantile, extRotVel's JtF (not handed out); Core::testfk (inline, defined in core.cpp only:
-    reached through calculatefJ); EdgeMapConfig off its defaults (EdgeDetector constructs every map with the defaults).
+    reached through calculatefJ); EdgeMapConfig off its defaults (EdgeDetector constructs every map with the defaults);
+  - rebvio.cpp's statements around gyroBiasCorrection (frame_dt, RGyro, RGBias, Bg += dgbias, the SO3 correction) and the
+    covariance P_V it takes from a Cholesky<6> inverse: rebvio.cpp is not compiled; the Cholesky of oracle/ref_shim, which the
+    reference library and the three implementations compared with it share; Core::estimateBias and the two acceleration
+    estimators (function-local statics; SABEstimator is not part of the library).
 """
 import numpy as np
 import pytest
 
 from conftest import params_for
-from support import ref_mod  # noqa: F401
-from support import (KW_TRACK, RHO_MAX, RHO_MIN, TS, assert_keylines_equal, bits_equal, craft_writers, f32, half_pixel_keylines, noise_frames, preset_targets,
-                     rodrigues, words)
+from support import host_lib, host_math_tool, ref_mod  # noqa: F401
+from support import (DT_GRID, GLUE_GBC, KW_TRACK, RHO_MAX, RHO_MIN, STEPS_HEALTHY, TS, assert_keylines_equal, bits_equal, craft_writers, f32, frame_dt_of, glue_family,
+                     glue_family_cases, gyro_noise, half_pixel_keylines, noise_frames, preset_targets, rodrigues, stamps_from, words)
 
 H, W = 144, 192
 TALLY = dict(keylines=0, pixels=0, scalars=0)
+GBC = dict(calls=0, finite=0, words=0)
 X_REL_MEASURED = 0.0   # largest |X_oracle - X_reference| / max|X_reference| seen by test_ext_rot_vel / the chain, printed by the tally
 
 
@@ -51,7 +62,8 @@ X_REL_MEASURED = 0.0   # largest |X_oracle - X_reference| / max|X_reference| see
 def tally():
     yield
     print(f"\nreference pin: {TALLY['keylines']} keyline records, {TALLY['pixels']} pixels / field cells and {TALLY['scalars']} "
-          f"scalars compared; largest relative deviation of extRotVel's X: {X_REL_MEASURED:.3g}")
+          f"scalars compared; largest relative deviation of extRotVel's X: {X_REL_MEASURED:.3g}; gyroBiasCorrection: {GBC['calls']} calls, "
+          f"{GBC['finite']} with every output finite, {GBC['words']} words compared")
 
 
 # ---- comparisons --------------------------------------------------------------------------------------------------------
@@ -554,3 +566,116 @@ def test_chain_tiny_maps(orc_mod, ref_mod, warmed, n_old, n_new):  # noqa: F811
     fails = []
     pair_body(S, 3, 4, np.eye(3, dtype=np.float32), fails, what=f"tiny {n_old}/{n_new}")
     assert not fails, "\n".join(fails[:12])
+
+
+# ---- gyroBiasCorrection ---------------------------------------------------------------------------------------------------------
+GBC_OUTPUTS = ("X", "Wx", "Wb", "dgbias")
+
+
+def noise_matrices(p, dt):
+    """RGyro, RGBias of a pair at the interval dt (rebvio.cpp:186-187), in numpy"""
+    s_g, s_b = gyro_noise(p, dt)
+    return np.eye(3, dtype=np.float32) * s_g, np.eye(3, dtype=np.float32) * s_b
+
+
+def same_gbc(want, got, what):
+    """X, Wx, Wb and dgbias of two gyroBiasCorrection results, word for word; every difference named at once"""
+    bad = [f"{name}: reference {np.ravel(r)[:6]} got {np.ravel(g)[:6]}" for name, r, g in zip(GBC_OUTPUTS, want, got)
+           if not np.array_equal(words(r), words(g))]
+    assert not bad, f"{what}: " + "; ".join(bad)
+    GBC["words"] += sum(np.size(r) for r in want)
+
+
+def host_gbc(tool, X, Wx, Wb, Rg, Rb):
+    """the host class's Core::gyroBiasCorrection (which is hm::gyro_bias_correction, rebvio_amd/host/core.cpp) through the gbc mode
+    of tests/cpp/host_math_dump.cpp, in the shapes of the two bindings"""
+    out = tool("gbc", np.concatenate([np.ravel(a).astype(np.float32) for a in (X, Wx, Wb, Rg, Rb)]))
+    return out[:6], out[6:42].reshape(6, 6), out[42:51].reshape(3, 3), out[51:54]
+
+
+def test_gyro_bias_correction_on_a_real_chain(orc_mod, ref_mod, small_stream, host_math_tool):  # noqa: F811
+    """Core::gyroBiasCorrection of the reference library against the oracle's and the host's on what a chain of pairs feeds it: Xv and
+    W_Xv of the eleven pairs of small_stream at the intervals of STEPS_HEALTHY (the oracle's track_pair, default sum order), the noise
+    matrices of each pair's interval, W_Bg carried from pair to pair as the REFERENCE leaves it. The oracle's own pair step must have
+    been handed the same: its Xgv and its state after the pair are the reference's X and Wb, its Bg the running sum of dgbias."""
+    frames, cam = small_stream
+    p = params_for(orc_mod, cam, **KW_TRACK)
+    orc, ref = orc_mod.Oracle(p), ref_mod.Ref(p)
+    ts = stamps_from(STEPS_HEALTHY)
+    Bg, W_Bg = orc.gyro_state()
+    prev = None
+    for k in range(len(ts)):
+        m = orc.detect_u8(frames[k], ts[k])
+        if prev is not None:
+            dt = frame_dt_of(ts[k - 1], ts[k])
+            po = orc.track_pair(prev, m, frame_dt=dt)
+            assert po.status == 0 and po.klm_num > 1000, (k, po.status, po.klm_num)
+            Rg, Rb = noise_matrices(p, dt)
+            args = (np.array(po.Xv, np.float32), np.array(po.W_Xv, np.float32), W_Bg, Rg, Rb)
+            want = ref.gyro_bias_correction(*args)
+            assert all(np.isfinite(a).all() for a in want), (k, dt)
+            same_gbc(want, orc_mod.gyro_bias_correction(*args), f"pair {k} (dt {dt}): oracle")
+            same_gbc(want, host_gbc(host_math_tool, *args), f"pair {k} (dt {dt}): host")
+            Bg = (Bg + want[3]).astype(np.float32)
+            W_Bg = want[2]
+            same_words(want[0], po.Xgv, f"pair {k}: Xgv of the oracle's pair record")
+            same_words(W_Bg, orc.gyro_state()[1], f"pair {k}: W_Bg of the oracle's state")
+            same_words(Bg, orc.gyro_state()[0], f"pair {k}: Bg of the oracle's state")
+            GBC["calls"] += 1
+            GBC["finite"] += 1
+        prev = m
+    assert len(set(frame_dt_of(a, b) for a, b in zip(ts, ts[1:]))) == 10   # (ten different intervals in eleven pairs)
+
+
+_gbc_grid = {}
+
+
+def gbc_grid(orc_mod, ref_mod):
+    """the reference's result for every family, decade of W_Bg and dt of the grid - computed once - and the precondition on it:
+    some dt leaves every output of every family but the NaN one finite, and at least three leave a non-finite Wb"""
+    if not _gbc_grid:
+        p = orc_mod.default_params(H, W)
+        ref = ref_mod.Ref(p)
+        for fam, decade in glue_family_cases():
+            g = glue_family(fam, decade)
+            for dt in DT_GRID:
+                args = (g["X"], g["Wx"], g["W_Bg"]) + noise_matrices(p, dt)
+                _gbc_grid[fam, decade, dt] = (args, ref.gyro_bias_correction(*args))
+        finite = {k: all(np.isfinite(a).all() for a in want) for k, (_, want) in _gbc_grid.items()}
+        clean = [dt for dt in DT_GRID if all(v for (fam, _, d), v in finite.items() if d == dt and fam != "nan-entry")]
+        broken = [dt for dt in DT_GRID if any(not np.isfinite(want[2]).all() for (_, _, d), (_, want) in _gbc_grid.items() if d == dt)]
+        assert len(clean) >= 1 and len(broken) >= 3, (clean, broken)
+        assert all(not v for (fam, _, _), v in finite.items() if fam == "nan-entry")
+        GBC["calls"] += len(finite)
+        GBC["finite"] += sum(finite.values())
+    return _gbc_grid
+
+
+@pytest.mark.parametrize("side", ["oracle", "host"])
+def test_gyro_bias_correction_on_the_probe_families(orc_mod, ref_mod, host_math_tool, side):  # noqa: F811
+    """The input families of the device glue's probe (support.glue_family: a well-conditioned system, a rank-deficient one, a zero
+    rotational block, a NaN entry, W_Bg at nine decades) at every interval of DT_GRID, which runs from 1 s through the intervals
+    whose s_g^3 is a denormal or zero in fp32 to a repeated stamp and a stamp that goes back: the oracle's function, and the
+    host's (the one hm::gyro_bias_correction behind Core::gyroBiasCorrection and the per-pair API), against the reference's."""
+    for (fam, decade, dt), (args, want) in gbc_grid(orc_mod, ref_mod).items():
+        got = orc_mod.gyro_bias_correction(*args) if side == "oracle" else host_gbc(host_math_tool, *args)
+        same_gbc(want, got, f"{side}: {fam}, W_Bg ~ 1e{decade}, dt {dt}")
+
+
+def test_recorded_gyro_bias_correction_results_are_the_reference(orc_mod, ref_mod):  # noqa: F811
+    """tests/golden/glue_gbc_reference.npz, which tests/test_reference_pin_gpu.py holds the device glue to where the library cannot
+    be rebuilt: X, Wx, Wb and dgbias recorded there are what the live library returns for the recorded Xv and W_Xv (the device
+    glue's own, which that test checks), and what the oracle's function returns."""
+    rec = np.load(GLUE_GBC)
+    p = orc_mod.default_params(96, 128)
+    ref = ref_mod.Ref(p)
+    cases = [(fam, decade, dt) for fam, decade in glue_family_cases() for dt in DT_GRID]
+    assert len(rec["X"]) == len(cases)
+    for k, (fam, decade, dt) in enumerate(cases):
+        args = (rec["Xv"][k], rec["W_Xv"][k], glue_family(fam, decade)["W_Bg"]) + noise_matrices(p, dt)
+        want = ref.gyro_bias_correction(*args)
+        recorded = (rec["X"][k], rec["Wx"][k].reshape(6, 6), rec["Wb"][k].reshape(3, 3), rec["dgbias"][k])
+        same_gbc(want, recorded, f"recorded: {fam}, W_Bg ~ 1e{decade}, dt {dt}")
+        same_gbc(want, orc_mod.gyro_bias_correction(*args), f"oracle on the device's inputs: {fam}, W_Bg ~ 1e{decade}, dt {dt}")
+        GBC["calls"] += 1
+        GBC["finite"] += int(all(np.isfinite(a).all() for a in want))
