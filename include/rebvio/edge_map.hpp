@@ -11,6 +11,7 @@
 
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/keyline.hpp"
+#include "rebvio/types/depth_image.hpp"
 #include "rebvio/types/point_cloud.hpp"
 
 struct rebvio_hip_map;
@@ -137,6 +138,14 @@ class EdgeMap {
   EdgeChains edgeChains();
   EdgePolylines edgePolylines(const rebvio::types::PolylineOpts& opts = rebvio::types::PolylineOpts(),
                               const rebvio::types::CloudPose& pose = rebvio::types::CloudPose());
+  // addition: a registered depth image folded into this map's rho / sigma_rho, one Kalman update per keyline
+  // (rebvio_hip_map_fuse_depth_image defines it and says where in a stream it belongs: after the map has been a pair's new map -
+  // or right after detection for a stream's first map - and before it serves as an old map; synchronous, from the tracking
+  // thread, like pointCloud). The image is host memory of the context's size; image.unit > 0 replaces opts.unit. outcome: the
+  // outcome word per keyline.
+  rebvio::types::DepthPriorCounts fuseDepthImage(const rebvio::types::DepthImage& image,
+                                                 const rebvio::types::DepthPriorOpts& opts = rebvio::types::DepthPriorOpts(),
+                                                 std::vector<int>* outcome = nullptr);
   // addition: keyframes (rebvio_hip.h "Keyframes"). markKeyframe makes this map the keyframe: match_id_keyframe[i] = i for every
   // keyline, queued on the track stream - call it after the map has been a pair's new map and before it serves as an old map.
   // keyframeMatches(kf_size): which keylines of a keyframe of kf_size keylines live on in this map, in ascending kf_keyline

@@ -17,6 +17,7 @@
 #include "rebvio/edge_detector.hpp"
 #include "rebvio/sab_estimator.hpp"
 #include "rebvio/types/definitions.hpp"
+#include "rebvio/types/depth_image.hpp"
 #include "rebvio/types/image.hpp"
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/odometry.hpp"
@@ -131,6 +132,22 @@ class Rebvio {
   // Without one the thread runs exactly the calls it ran. Register before the first frame is handed in.
   void registerKeyframeCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb,
                                      rebvio::types::CloudFilter filter = rebvio::types::CloudFilter());
+  // addition: registered depth images (RGB-D; rebvio/types/depth_image.hpp, rebvio_hip.h "Depth prior from a registered depth
+  // image"). depthImageCallback copies the image into a small queue (at most 8; a ninth pushes the oldest out, counted as dropped);
+  // callable from any thread - hand it in AHEAD of the imageCallback of the same stamp: an image that arrives after its frame's pair
+  // has been started is never matched and ends as dropped. The state-estimation thread matches an
+  // image to the frame with the SAME ts_us: the image of a pair's new map is folded into that map's rho / sigma_rho by a kernel
+  // queued right behind the pair's second half (the thread does not wait for it), the image of a stream's first map in front of its
+  // first pair; from then on the map's depths, V and the position are metric through the prior. An image older than the frame being
+  // tracked is dropped and counted (depthImagesDropped). While an image is waiting for the pair's new map the next pair's first
+  // rotation is not fused into this pair's last kernel, as with a point-cloud callback. A frame without an image runs exactly the
+  // calls it runs without all this. setDepthPrior: the options of the fusions queued from then on (any thread). The depth-prior
+  // callback gets the frame's stamp and the counts, once per fused frame, behind the odometry callbacks of the record published
+  // next (for the first map: in front of the first record's other callbacks), on the state-estimation thread.
+  void depthImageCallback(rebvio::types::DepthImage&& image);
+  void setDepthPrior(const rebvio::types::DepthPriorOpts& opts);
+  void registerDepthPriorCallback(std::function<void(uint64_t ts_us, const rebvio::types::DepthPriorCounts&)> cb);
+  unsigned int depthImagesDropped() const { return depth_dropped_; }
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -184,6 +201,21 @@ class Rebvio {
   std::atomic<bool> keyframe_depth_handover_{false};
   std::vector<std::function<void(uint64_t, const std::vector<rebvio::types::KfWindowPose>&)>> keyframe_window_callbacks_;
   std::atomic<int> keyframe_window_{0};
+  // depth images: the queue (under depth_mutex_, with the options), what the state-estimation thread keeps on the device for the
+  // queued fusions (two staging frames, used in turn: a frame's image is uploaded while the previous one may still be read)
+  struct QueuedDepth {
+    uint64_t ts_us;
+    int format;
+    double unit;
+    std::vector<unsigned char> bytes;  // dense rows
+  };
+  std::deque<QueuedDepth> depth_queue_;
+  rebvio::types::DepthPriorOpts depth_opts_;
+  std::mutex depth_mutex_;
+  std::atomic<unsigned int> depth_seen_{0}, depth_dropped_{0};
+  std::vector<std::function<void(uint64_t, const rebvio::types::DepthPriorCounts&)>> depth_prior_callbacks_;
+  void* depth_dev_[2] = {nullptr, nullptr};
+  unsigned int depth_dev_turn_ = 0;
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };
 

@@ -41,7 +41,9 @@ extern "C" {
  *    rebvio_hip_kf_handover and the test hook rebvio_hip_test_kf_handover_host; the edge chains and polylines
  *    rebvio_hip_map_edge_chains, rebvio_hip_default_polyline_opts, rebvio_hip_map_edge_polylines, their structs rebvio_hip_chain_ref /
  *    rebvio_hip_polyline_opts / rebvio_hip_polyline and the test hooks rebvio_hip_test_edge_chains_host /
- *    rebvio_hip_test_edge_polylines_host. */
+ *    rebvio_hip_test_edge_polylines_host; the depth prior rebvio_hip_default_depth_prior_opts, rebvio_hip_map_fuse_depth_image(_device,
+ *    _async), rebvio_hip_depth_prior_last_counts, their structs rebvio_hip_depth_prior_opts / rebvio_hip_depth_prior_counts and the
+ *    test hook rebvio_hip_test_depth_prior_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -632,6 +634,94 @@ int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int col
                                  const float* cur_pos, const float* cur_unit, int n_cur, const int* df_id, const int* df_dist,
                                  const rebvio_hip_kf_fuse_opts* opts, const double R[9], const double t[3], rebvio_hip_kf_fuse* out,
                                  int* assoc /*NULL or kf_size ints*/);
+
+/* Depth prior from a registered depth image (RGB-D): rebvio_hip_map_fuse_depth_image folds a sensor's depth for frame k into the
+ * (rho, sigma_rho) of map k's keylines with one scalar Kalman update per keyline - the input side of the depth-bearing products
+ * above. No reference counterpart. Without it a keyline starts at rho = 1, sigma_rho = 20 and earns its depth from motion alone, in
+ * an arbitrary scale; with it the map's depths, and V, are metric.
+ * Geometry: the image has the context's rows x cols and lies in the geometry of the image the detector sees (with a lens model:
+ * behind the front end's undistortion; resampling a raw depth image is the caller's). It holds the depth along the optical axis.
+ * Formats: REBVIO_HIP_DEPTH_U16, z = value * unit (unit: metres per count, default 0.001), a value of 0 is invalid;
+ * REBVIO_HIP_DEPTH_F32, z = value in metres. Rows are pitch_bytes apart (0 = dense; otherwise >= cols * the tap's size and a
+ * multiple of it; the image starts aligned to the tap's size). A tap's depth is valid when z_min <= z && z <= z_max (positive
+ * tests: a NaN fails them).
+ * fp64 behind the loads; every + - * / sqrt and floor one IEEE operation in the order written, no contraction. Per keyline i < size:
+ *   1. px = pos[0], py = pos[1] - the detector's pixel position, NOT pos_img, which earlier pairs may have rotated.
+ *      The direction is usable when gradient_norm > 0 and ux = gradient[0] / gradient_norm, uy = gradient[1] / gradient_norm are
+ *      both finite.
+ *   2. The centre tap is at (x, y) = (px, py). With a usable direction two side taps, s = +1 then s = -1:  d = s * tap_px;
+ *      x = px + d * ux;  y = py + d * uy.  A tap is inside when x + 0.5 >= 0 && x + 0.5 < cols && y + 0.5 >= 0 && y + 0.5 < rows
+ *      (a NaN or infinite position is outside); then xi = (int)floor(x + 0.5), yi = (int)floor(y + 0.5) and the tap reads the image
+ *      at row yi, column xi. z_near = the minimum, z_far = the maximum of the valid taps' z. No valid tap: NO DEPTH, the keyline
+ *      keeps all its bits. jump: z_far - z_near > jump_rel * z_near (an edge is often an occlusion boundary; the nearer surface
+ *      owns an occluding edge, so the measurement is z_near either way).
+ *   3. rho_m = 1.0 / z_near;  s_m = (sigma_z0 * rho_m) * rho_m + sigma_z2   (a sensor with sigma_z = sigma_z0 + sigma_z2 * z^2,
+ *      carried to inverse depth).
+ *   4. s = (double)sigma_rho;  v = s * s + q_abs * q_abs;  e = rho_m - (double)rho;  S = v + s_m * s_m;
+ *      GATED, the keyline left as it was, unless e * e <= (gate_sigma * gate_sigma) * S.
+ *   5. K = v / S;  rho_n = rho + K * e;  v_n = (1.0 - K) * v;  sig_n = sqrt(v_n);  also GATED unless rho_n, v_n and sig_n are finite
+ *      and v_n >= 0 (positive tests). Then step 7 of rebvio_hip_kf_snapshot_fuse_depth: the RHO_MIN / RHO_MAX clamp, counted as clamped.
+ *   6. FUSED: the map gets (float)rho_n and (float)sig_n. matches and every other field are untouched: a sensor depth is not a
+ *      tracking match.
+ * outcome[i] = 0 no depth, 1 fused, 2 gated;  + 16 for a jump (with 1 or 2),  + 32 for clamped (with 1). Counts: candidates = the
+ * map's size, sampled = fused + gated, jumps among the sampled, clamped among the fused - integer sums; no floating-point value
+ * crosses threads, every output word is the same on every run.
+ * Where in a stream: the image of frame k goes into map k AFTER the pair in which k was the new map (directedMatch overwrites a
+ * matched new keyline's depth) - or right after detection for a stream's first map - and BEFORE map k serves as an old map.
+ * Map acceptance: -7 for a map promised to R_prior_next (already rotated for the next pair, like its cloud) and for a map that has
+ * served as the old map of rebvio_hip_track_pair / rebvio_hip_track_pair_begin (its rho lives in a newer frame); -10: the context
+ * has been destroyed; -3, before the device is touched: a null map, image or counts, an unknown format, a bad pitch or alignment,
+ * a map of another context, an invalid option (rebvio_hip_last_error names it).
+ * One kernel per call (k_depth_prior: one thread per keyline, ceil(keylines_max / 256) workgroups of 256, the size read on the
+ * device) behind one clear of the count block, all on the TRACK stream; the entries follow the track-side thread rule of
+ * rebvio_hip_map_point_cloud, and the map counts as used by the tracker afterwards. The first call gives the context one more owned
+ * device allocation (the counts and keylines_max outcome words: one more live resource, kept until the context goes); the first
+ * call of the HOST-image entry one pinned staging frame of its own besides (the detect entries' ring belongs to the detect-side
+ * thread). A map of size 0: all counts zero.
+ *   rebvio_hip_map_fuse_depth_image         host image, copied into the pinned staging frame, which the kernel reads in place;
+ *                                           synchronous. outcome_host: NULL, or room for the map's size.
+ *   rebvio_hip_map_fuse_depth_image_device  the same for an image in device memory; synchronous.
+ *   rebvio_hip_map_fuse_depth_image_async   device image; queued in call order, returns at once - for use between _finish_async(k)
+ *                                           and _begin(k+1). The image must stay unchanged until the kernel has run. The counts stay
+ *                                           in device memory: rebvio_hip_depth_prior_last_counts fetches those of the context's most
+ *                                           recent fusion (any entry) and waits for them; all zero before the first.
+ *   rebvio_hip_test_depth_prior_host        test hook, touches no device: the same statements over n keylines (rho / sigma_rho updated
+ *                                           in place) in index order. -3 as above, and for a negative n or size. */
+#define REBVIO_HIP_DEPTH_U16 0
+#define REBVIO_HIP_DEPTH_F32 1
+typedef struct rebvio_hip_depth_prior_opts { /* defaults from rebvio_hip_default_depth_prior_opts */
+  double tap_px;     /* >= 0, default 2.0: distance of the side taps along the gradient, pixels */
+  double jump_rel;   /* >= 0, default 0.1 */
+  double z_min;      /* > 0, default 0.1 m */
+  double z_max;      /* >= z_min, default 20 m */
+  double sigma_z0;   /* >= 0, default 1e-3 m */
+  double sigma_z2;   /* >= 0, default 2e-3 1/m; sigma_z0 + sigma_z2 > 0 */
+  double gate_sigma; /* > 0, default 3.0: innovation gate in standard deviations */
+  double q_abs;      /* >= 0, default 0: added in quadrature to sigma_rho before the update */
+  double unit;       /* > 0, default 0.001: metres per count of a U16 image */
+  int reserved;      /* 0 */
+} rebvio_hip_depth_prior_opts;
+typedef struct rebvio_hip_depth_prior_counts {
+  int candidates; /* the map's size */
+  int sampled;    /* keylines with at least one valid tap */
+  int fused;      /* ...updated */
+  int gated;      /* ...failed the innovation gate or gave a non-finite update (left as they were) */
+  int jumps;      /* among sampled: z_far - z_near > jump_rel * z_near */
+  int clamped;    /* among fused: rho ran into RHO_MIN or RHO_MAX */
+} rebvio_hip_depth_prior_counts;
+void rebvio_hip_default_depth_prior_opts(rebvio_hip_depth_prior_opts* opts);
+int rebvio_hip_map_fuse_depth_image(rebvio_hip_map* map, const void* depth_host, size_t pitch_bytes, int fmt,
+                                    const rebvio_hip_depth_prior_opts* opts /*NULL = defaults*/, rebvio_hip_depth_prior_counts* counts,
+                                    int* outcome_host /*NULL ok*/);
+int rebvio_hip_map_fuse_depth_image_device(rebvio_hip_map* map, const void* depth_dev, size_t pitch_bytes, int fmt,
+                                           const rebvio_hip_depth_prior_opts* opts, rebvio_hip_depth_prior_counts* counts,
+                                           int* outcome_host /*NULL ok*/);
+int rebvio_hip_map_fuse_depth_image_async(rebvio_hip_ctx* ctx, rebvio_hip_map* map, const void* depth_dev, size_t pitch_bytes, int fmt,
+                                          const rebvio_hip_depth_prior_opts* opts);
+int rebvio_hip_depth_prior_last_counts(rebvio_hip_ctx* ctx, rebvio_hip_depth_prior_counts* counts);
+int rebvio_hip_test_depth_prior_host(int rows, int cols, rebvio_hip_keyline* keylines /*in/out*/, int n, const void* depth,
+                                     size_t pitch_bytes, int fmt, const rebvio_hip_depth_prior_opts* opts,
+                                     rebvio_hip_depth_prior_counts* counts, int* outcome /*NULL or n ints*/);
 
 /* Depth hand-over between keyframe snapshots: what the fusion above has made of a retiring keyframe's rho / sigma_rho is lost when
  * the next keyframe is marked - the successor's snapshot is cut from the tracker's map and starts with the tracker's raw depths.

@@ -112,6 +112,25 @@ class KfFuse(C.Structure):
                 ("clamped", C.c_int)]
 
 
+DEPTH_U16, DEPTH_F32 = 0, 1  # REBVIO_HIP_DEPTH_*: uint16 counts of `unit` metres (0 = invalid) | float32 metres
+
+
+class DepthPriorOpts(C.Structure):
+    """rebvio_hip_depth_prior_opts (Map.fuse_depth_image); defaults from default_depth_prior_opts"""
+    _fields_ = [("tap_px", C.c_double), ("jump_rel", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double),
+                ("sigma_z0", C.c_double), ("sigma_z2", C.c_double), ("gate_sigma", C.c_double), ("q_abs", C.c_double),
+                ("unit", C.c_double), ("reserved", C.c_int)]
+
+
+class DepthPriorCounts(C.Structure):
+    """rebvio_hip_depth_prior_counts: the counts of one depth-image fusion; sampled = fused + gated"""
+    _fields_ = [("candidates", C.c_int), ("sampled", C.c_int), ("fused", C.c_int), ("gated", C.c_int), ("jumps", C.c_int),
+                ("clamped", C.c_int)]
+
+    def as_tuple(self):
+        return (self.candidates, self.sampled, self.fused, self.gated, self.jumps, self.clamped)
+
+
 class KfHandoverOpts(C.Structure):
     """rebvio_hip_kf_handover_opts (KfSnapshot.handover_depth); defaults from default_kf_handover_opts"""
     _fields_ = [("kf_filter", CloudFilter), ("min_cos", C.c_double), ("gate_sigma", C.c_double), ("q_abs", C.c_double),
@@ -275,6 +294,15 @@ SIGNATURES = {
     "rebvio_hip_test_glue_set_next": (C.c_int, [_vp, _fp, C.c_int]),
     "rebvio_hip_test_forge_record_stamp": (C.c_int, [_vp]),
     "rebvio_hip_batch_test_forge_record_stamp": (C.c_int, [_vp]),
+    "rebvio_hip_default_depth_prior_opts": (None, [C.POINTER(DepthPriorOpts)]),
+    "rebvio_hip_map_fuse_depth_image": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(DepthPriorOpts),
+                                                  C.POINTER(DepthPriorCounts), _ip]),
+    "rebvio_hip_map_fuse_depth_image_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(DepthPriorOpts),
+                                                         C.POINTER(DepthPriorCounts), _ip]),
+    "rebvio_hip_map_fuse_depth_image_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.POINTER(DepthPriorOpts)]),
+    "rebvio_hip_depth_prior_last_counts": (C.c_int, [_vp, C.POINTER(DepthPriorCounts)]),
+    "rebvio_hip_test_depth_prior_host": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, C.c_int,
+                                                   C.POINTER(DepthPriorOpts), C.POINTER(DepthPriorCounts), _ip]),
     "rebvio_hip_test_live_resources": (C.c_long, []),
     "rebvio_hip_test_handover_counters": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "rebvio_hip_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -670,6 +698,41 @@ def kf_fuse_host(fm, cx, cy, rows, cols, search_range, prs4, kf_matches, normals
     return out, prs4, kf_matches, assoc
 
 
+def default_depth_prior_opts(**over) -> DepthPriorOpts:
+    """The library's defaults (rebvio_hip_default_depth_prior_opts), with the given fields changed."""
+    o = DepthPriorOpts()
+    lib().rebvio_hip_default_depth_prior_opts(C.byref(o))
+    for k, v in over.items():
+        setattr(o, k, v)
+    return o
+
+
+def _depth_image(depth, fmt, rows, cols):
+    """(array kept alive, address, pitch in bytes, format) of a host depth image: uint16 or float32, [rows, cols], rows any number
+    of bytes apart (a column slice of a wider array keeps its pitch); anything else is copied dense."""
+    depth = np.asarray(depth)
+    if fmt is None:
+        fmt = DEPTH_U16 if depth.dtype == np.uint16 else DEPTH_F32
+    dt = np.uint16 if fmt == DEPTH_U16 else np.float32
+    if depth.dtype != dt or depth.ndim != 2 or depth.strides[1] != depth.itemsize or depth.strides[0] < cols * depth.itemsize:
+        depth = np.ascontiguousarray(depth, dt)
+    assert depth.shape == (rows, cols), (depth.shape, rows, cols)
+    return depth, depth.ctypes.data, depth.strides[0], fmt
+
+
+def depth_prior_host(rows, cols, keylines, depth, fmt=None, opts=None):
+    """Map.fuse_depth_image on the host, from arrays (rebvio_hip_test_depth_prior_host). Touches no device and leaves its inputs
+    alone. Returns (DepthPriorCounts, the updated KEYLINE_DTYPE copy, outcome int32 [n])."""
+    kl = np.array(keylines, KEYLINE_DTYPE).reshape(-1)  # (a copy: the hook updates it in place)
+    keep, addr, pitch, fmt = _depth_image(depth, fmt, rows, cols)
+    out = DepthPriorCounts()
+    outcome = np.zeros(len(kl), np.int32)
+    _chk(lib().rebvio_hip_test_depth_prior_host(int(rows), int(cols), kl.ctypes.data if len(kl) else None, len(kl), addr, pitch, fmt,
+                                                opts, C.byref(out), outcome.ctypes.data_as(_ip) if len(kl) else None))
+    del keep
+    return out, kl, outcome
+
+
 def default_kf_handover_opts(ctx=None, **over) -> KfHandoverOpts:
     """The library's defaults (rebvio_hip_default_kf_handover_opts): max_dist is ctx's search_range (40, the default one, without a
     context); kf_filter takes a CloudFilter or a dict of its fields to change."""
@@ -1026,6 +1089,28 @@ class Map:
         _chk(lib().rebvio_hip_map_keyframe_align_many(self.h, arr if hyps else None, len(hyps), opts, out))
         return [KfHypResult.from_buffer_copy(out[k]) for k in range(len(hyps))]
 
+    def fuse_depth_image(self, depth, fmt=None, opts=None, device=False, queued=False, pitch=None, want_outcome=False):
+        """Folds a registered depth image into this map's (rho, sigma_rho), one Kalman update per keyline (rebvio_hip_map_fuse_depth_image*;
+        include/rebvio_hip.h is the definition and says where in a stream it belongs). depth: a host array [rows, cols], uint16
+        (DEPTH_U16, counts of opts.unit metres) or float32 (DEPTH_F32, metres) - or, with device=True or queued=True, a device address
+        (fmt is then required; pitch in bytes, default dense). Returns the DepthPriorCounts, with want_outcome also the int32 outcome
+        word per keyline; queued=True returns None at once: Context.depth_prior_last_counts fetches the counts."""
+        if device or queued:
+            assert fmt is not None, "a device image needs its format"
+            addr, pb = _vp(int(depth)), int(pitch or 0)
+            if queued:
+                _chk(lib().rebvio_hip_map_fuse_depth_image_async(self.ctx.h, self.h, addr, pb, fmt, opts))
+                return None
+            entry, keep = lib().rebvio_hip_map_fuse_depth_image_device, None
+        else:
+            keep, addr, pb, fmt = _depth_image(depth, fmt, self.ctx.rows, self.ctx.cols)
+            entry = lib().rebvio_hip_map_fuse_depth_image
+        out = DepthPriorCounts()
+        outcome = np.zeros(self.ctx.p.keylines_max, np.int32) if want_outcome else None
+        _chk(entry(self.h, addr, pb, fmt, opts, C.byref(out), outcome.ctypes.data_as(_ip) if want_outcome else None))
+        del keep
+        return (out, outcome[:out.candidates]) if want_outcome else out
+
     def upload(self, kl: np.ndarray):
         kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)
         _chk(lib().rebvio_hip_map_upload(self.h, kl.ctypes.data if kl.size else None, len(kl)))
@@ -1161,6 +1246,18 @@ class Context:
         _chk(lib().rebvio_hip_device_upload(self.h, d, frames_u8.ctypes.data, frames_u8.nbytes))
         self._dev_bufs.append(d)
         return d.value
+
+    def upload_bytes(self, arr: np.ndarray) -> int:
+        """Stage any array's bytes in HBM (e.g. depth images for Map.fuse_depth_image); returns the device address."""
+        arr = np.ascontiguousarray(arr)
+        return self.upload_frames(arr.view(np.uint8).reshape(-1))
+
+    def depth_prior_last_counts(self) -> DepthPriorCounts:
+        """The counts of the context's most recent depth-image fusion, queued ones included; waits for them
+        (rebvio_hip_depth_prior_last_counts). All zero before the first."""
+        out = DepthPriorCounts()
+        _chk(lib().rebvio_hip_depth_prior_last_counts(self.h, C.byref(out)))
+        return out
 
     def detect_u8_device(self, dev_addr: int, ts_us=0) -> Map:
         h = _vp()

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "depth_prior.hpp"
 #include "glue.hpp"
 #include "hostmath.hpp"
 #include "kf_cloud.hpp"
@@ -251,6 +252,9 @@ struct rebvio_hip_map {
   // per-pair API: _finish_async was given R_prior_next for this map and the next _begin has not consumed it yet - the keylines are
   // (or will be, in stream order) in the next pair's frame: the point-cloud entries refuse the map (-7)
   std::atomic<bool> promised{false};
+  // per-pair API: rebvio_hip_track_pair / _begin has taken this map as a pair's OLD map - its rho / sigma_rho have been (or will be,
+  // in stream order) carried into a newer frame: the depth-image entries refuse it (-7). Host-side only; cleared by acquire_map.
+  bool served_old = false;
   // streaming / batch drivers: the gyro rotation the frame was pushed with (interval from the frame pushed before it to this one;
   // rebvio_hip_push_frame_px_gyro*). Not set: the identity.
   bool gyro_set = false;
@@ -568,6 +572,13 @@ struct rebvio_hip_ctx {
   // scratch of rebvio_hip_map_edge_chains / _edge_polylines (ONE allocation on first use, kept; track-side entries): views into it
   char* ech_buf = nullptr;
   ChainDev ech{};
+  // scratch of the depth-image entries (ONE device allocation on first use, kept; track-side entries): 8 count words (the six of
+  // rebvio_hip_depth_prior_counts in front), then keylines_max outcome words. dpr_pin: the host-image entry's pinned staging frame
+  // (rows * cols * 4 bytes, on ITS first use), which the kernel reads in place. dpr_queued: a fusion has been queued.
+  int* dpr_cnt = nullptr;
+  int* dpr_outcome = nullptr;  // (a view into dpr_cnt's allocation)
+  char* dpr_pin = nullptr;
+  bool dpr_queued = false;
 };
 
 namespace {
@@ -697,6 +708,7 @@ rebvio_hip_map* acquire_map(rebvio_hip_ctx* c) {
     m->gyro_set = false;
     m->kf_flag = false;
     m->promised.store(false, std::memory_order_relaxed);
+    m->served_old = false;
     m->n_host = -1;
     m->thr_host = -1.0f;
     m->trk_waited = false;
@@ -2719,6 +2731,192 @@ int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int col
   return 0;
 }
 
+// ---- depth prior from a registered depth image (include/rebvio_hip.h is the definition; depth_prior.hpp the statement) ----------
+void rebvio_hip_default_depth_prior_opts(rebvio_hip_depth_prior_opts* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->tap_px = 2.0;
+  o->jump_rel = 0.1;
+  o->z_min = 0.1;
+  o->z_max = 20.0;
+  o->sigma_z0 = 1e-3;
+  o->sigma_z2 = 2e-3;
+  o->gate_sigma = 3.0;
+  o->q_abs = 0.0;
+  o->unit = 0.001;
+}
+
+namespace {
+static_assert(sizeof(rebvio_hip_depth_prior_opts) == 80, "nine doubles, one int, padding");
+static_assert(sizeof(rebvio_hip_depth_prior_counts) == 24, "six ints");
+
+inline size_t depth_tap_bytes(int fmt) { return fmt == REBVIO_HIP_DEPTH_U16 ? 2 : 4; }
+
+// Everything that is refused before the device is touched: the format, the image's pitch and alignment, the options.
+// *pitch is replaced by the dense pitch where it is 0.
+int check_depth_prior_args(const char* who, const void* depth, size_t* pitch, int fmt, int cols, const rebvio_hip_depth_prior_opts& o) {
+  const std::string w(who);
+  if (!depth) return fail_msg((w + ": null depth image").c_str(), -3);
+  if (fmt != REBVIO_HIP_DEPTH_U16 && fmt != REBVIO_HIP_DEPTH_F32)
+    return fail_msg((w + ": unknown depth format (REBVIO_HIP_DEPTH_U16, REBVIO_HIP_DEPTH_F32)").c_str(), -3);
+  const size_t tb = depth_tap_bytes(fmt), rowb = (size_t)cols * tb;
+  if (*pitch == 0) *pitch = rowb;
+  if (*pitch < rowb || *pitch % tb != 0) return fail_msg((w + ": pitch_bytes below a row's bytes or no multiple of a tap's size").c_str(), -3);
+  if (reinterpret_cast<uintptr_t>(depth) % tb != 0) return fail_msg((w + ": the depth image is not aligned to a tap's size").c_str(), -3);
+  if (!(o.tap_px >= 0.0 && o.tap_px < HUGE_VAL)) return fail_msg((w + ": tap_px must be >= 0 and finite").c_str(), -3);
+  if (!(o.jump_rel >= 0.0)) return fail_msg((w + ": jump_rel must be >= 0").c_str(), -3);
+  if (!(o.z_min > 0.0)) return fail_msg((w + ": z_min must be > 0").c_str(), -3);
+  if (!(o.z_max >= o.z_min)) return fail_msg((w + ": z_max must be >= z_min").c_str(), -3);
+  if (!(o.sigma_z0 >= 0.0)) return fail_msg((w + ": sigma_z0 must be >= 0").c_str(), -3);
+  if (!(o.sigma_z2 >= 0.0)) return fail_msg((w + ": sigma_z2 must be >= 0").c_str(), -3);
+  if (!(o.sigma_z0 + o.sigma_z2 > 0.0)) return fail_msg((w + ": sigma_z0 + sigma_z2 must be > 0").c_str(), -3);
+  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
+  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
+  if (!(o.unit > 0.0)) return fail_msg((w + ": unit must be > 0").c_str(), -3);
+  if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
+  return 0;
+}
+
+// The state rule, the scratch and the waits, then the clear and the kernel on the track stream. The caller holds the map's life
+// block and has checked the arguments. img = the image as the device addresses it.
+int depth_prior_state_rule(const char* who, const rebvio_hip_map* m) {
+  if (m->promised.load(std::memory_order_acquire))
+    return fail_msg((std::string(who) + ": the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair").c_str(), -7);
+  if (m->served_old)
+    return fail_msg((std::string(who) + ": the map has served as a pair's old map; its depths live in a newer frame").c_str(), -7);
+  return 0;
+}
+
+int enqueue_depth_prior(const char* who, rebvio_hip_map* m, const void* img, size_t pitch, int fmt, const rebvio_hip_depth_prior_opts& o) {
+  rebvio_hip_ctx* c = m->ctx;
+  const int rc_state = depth_prior_state_rule(who, m);
+  if (rc_state) return rc_state;
+  if (!c->dpr_cnt) {
+    char* b = nullptr;
+    HIPCHK(c->own.device_bytes(&b, (8 + (size_t)c->P.keylines_max) * sizeof(int)));
+    c->dpr_cnt = reinterpret_cast<int*>(b);
+    c->dpr_outcome = c->dpr_cnt + 8;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  HIPCHK(hipMemsetAsync(c->dpr_cnt, 0, 8 * sizeof(int), c->s_trk));
+  launch_depth_prior(c->s_trk, c->K, m->d, dpr::make_args(img, pitch, c->P.rows, c->P.cols, fmt, o), c->dpr_cnt, c->dpr_outcome);
+  HIPCHK(hipGetLastError());
+  c->dpr_queued = true;
+  return 0;
+}
+
+// Behind enqueue_depth_prior: the counts, then exactly the outcome words that exist.
+int fetch_depth_prior(rebvio_hip_ctx* c, rebvio_hip_depth_prior_counts* counts, int* outcome_host) {
+  rebvio_hip_depth_prior_counts res;
+  HIPCHK(hipMemcpyAsync(&res, c->dpr_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  int rc = trk_sync(c);
+  if (rc) return rc;
+  if (outcome_host && res.candidates > 0) {
+    HIPCHK(hipMemcpyAsync(outcome_host, c->dpr_outcome, (size_t)res.candidates * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+    rc = trk_sync(c);
+    if (rc) return rc;
+  }
+  *counts = res;
+  return 0;
+}
+
+int fuse_depth_image_sync(const char* who, rebvio_hip_map* m, const void* depth, size_t pitch, int fmt, const rebvio_hip_depth_prior_opts* opts,
+                          rebvio_hip_depth_prior_counts* counts, int* outcome_host, bool host_image) {
+  const std::string w(who);
+  if (!m) return fail_msg((w + ": null map").c_str(), -3);
+  if (!counts) return fail_msg((w + ": null counts").c_str(), -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = m->ctx;
+  rebvio_hip_depth_prior_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_depth_prior_opts(&o);
+  int rc = check_depth_prior_args(who, depth, &pitch, fmt, c->P.cols, o);
+  if (rc) return rc;
+  std::memset(counts, 0, sizeof(*counts));
+  HIPCHK(hipSetDevice(c->device));
+  const void* img = depth;
+  if (host_image) {
+    rc = depth_prior_state_rule(who, m);  // (before the staging frame is written or made)
+    if (rc) return rc;
+    const size_t rowb = (size_t)c->P.cols * depth_tap_bytes(fmt);
+    if (!c->dpr_pin) HIPCHK(c->own.pinned_bytes(&c->dpr_pin, (size_t)c->P.rows * c->P.cols * sizeof(float), false));
+    // (the previous call that used the frame was synchronous: nothing reads it any more)
+    const char* src = static_cast<const char*>(depth);
+    for (int r = 0; r < c->P.rows; ++r) std::memcpy(c->dpr_pin + (size_t)r * rowb, src + (size_t)r * pitch, rowb);
+    void* dev_view = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&dev_view, c->dpr_pin, 0));
+    img = dev_view;
+    pitch = rowb;
+  }
+  rc = enqueue_depth_prior(who, m, img, pitch, fmt, o);
+  if (rc) return rc;
+  return fetch_depth_prior(c, counts, outcome_host);
+}
+}  // namespace
+
+int rebvio_hip_map_fuse_depth_image(rebvio_hip_map* m, const void* depth_host, size_t pitch_bytes, int fmt, const rebvio_hip_depth_prior_opts* opts,
+                                    rebvio_hip_depth_prior_counts* counts, int* outcome_host) {
+  return fuse_depth_image_sync("map_fuse_depth_image", m, depth_host, pitch_bytes, fmt, opts, counts, outcome_host, true);
+}
+
+int rebvio_hip_map_fuse_depth_image_device(rebvio_hip_map* m, const void* depth_dev, size_t pitch_bytes, int fmt,
+                                           const rebvio_hip_depth_prior_opts* opts, rebvio_hip_depth_prior_counts* counts, int* outcome_host) {
+  return fuse_depth_image_sync("map_fuse_depth_image_device", m, depth_dev, pitch_bytes, fmt, opts, counts, outcome_host, false);
+}
+
+int rebvio_hip_map_fuse_depth_image_async(rebvio_hip_ctx* c, rebvio_hip_map* m, const void* depth_dev, size_t pitch_bytes, int fmt,
+                                          const rebvio_hip_depth_prior_opts* opts) {
+  if (!c || !m) return fail_msg("map_fuse_depth_image_async: null context or map", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (m->ctx != c) return fail_msg("map_fuse_depth_image_async: map of another context", -3);
+  rebvio_hip_depth_prior_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_depth_prior_opts(&o);
+  const int rc = check_depth_prior_args("map_fuse_depth_image_async", depth_dev, &pitch_bytes, fmt, c->P.cols, o);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  return enqueue_depth_prior("map_fuse_depth_image_async", m, depth_dev, pitch_bytes, fmt, o);
+}
+
+int rebvio_hip_depth_prior_last_counts(rebvio_hip_ctx* c, rebvio_hip_depth_prior_counts* counts) {
+  if (!c || !counts) return fail_msg("depth_prior_last_counts: null context or counts", -3);
+  std::memset(counts, 0, sizeof(*counts));
+  if (!c->dpr_queued) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  return fetch_depth_prior(c, counts, nullptr);
+}
+
+int rebvio_hip_test_depth_prior_host(int rows, int cols, rebvio_hip_keyline* keylines, int n, const void* depth, size_t pitch_bytes, int fmt,
+                                     const rebvio_hip_depth_prior_opts* opts, rebvio_hip_depth_prior_counts* counts, int* outcome) {
+  if (!counts || n < 0 || rows < 0 || cols < 0 || (n > 0 && !keylines))
+    return fail_msg("test_depth_prior_host: null array or negative size", -3);
+  rebvio_hip_depth_prior_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_depth_prior_opts(&o);
+  const int rc = check_depth_prior_args("test_depth_prior_host", depth, &pitch_bytes, fmt, cols, o);
+  if (rc) return rc;
+  const dpr::Args a = dpr::make_args(depth, pitch_bytes, rows, cols, fmt, o);
+  rebvio_hip_depth_prior_counts res;
+  std::memset(&res, 0, sizeof(res));
+  res.candidates = n;
+  for (int i = 0; i < n; ++i) {
+    rebvio_hip_keyline& k = keylines[i];
+    float rho_n = 0.f, sig_n = 0.f;
+    const int oc = dpr::term(a, k.pos[0], k.pos[1], k.gradient[0], k.gradient[1], k.gradient_norm, k.rho, k.sigma_rho, &rho_n, &sig_n);
+    if (outcome) outcome[i] = oc;
+    if (oc == dpr::kNone) continue;
+    ++res.sampled;
+    if (oc & dpr::kJumpBit) ++res.jumps;
+    if ((oc & 3) == dpr::kGated) ++res.gated;
+    if ((oc & 3) != dpr::kFused) continue;
+    ++res.fused;
+    if (oc & dpr::kClampedBit) ++res.clamped;
+    k.rho = rho_n;
+    k.sigma_rho = sig_n;
+  }
+  *counts = res;
+  return 0;
+}
+
 void rebvio_hip_default_kf_handover_opts(rebvio_hip_ctx* c, rebvio_hip_kf_handover_opts* o) {
   std::memset(o, 0, sizeof(*o));
   rebvio_hip_default_cloud_filter(&o->kf_filter);
@@ -3463,6 +3661,7 @@ int rebvio_hip_track_pair(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hip_map*
   HIPCHK(hipSetDevice(c->device));
   std::memset(out, 0, sizeof(*out));
   hipStream_t s = c->s_trk;
+  om->served_old = true;
   HIPCHK(trk_wait_ready(s, om));
   HIPCHK(trk_wait_ready(s, nm));
   int rc = rebvio_hip_build_distance_field(c, nm);  // rebvio.cpp:142 (no-op when detect already built it)
@@ -3515,6 +3714,7 @@ int rebvio_hip_track_pair_begin(rebvio_hip_ctx* c, rebvio_hip_map* om, rebvio_hi
     HIPCHK(hipEventRecord(c->bf_done[pr], s));
     c->bf_copy_queued[pr] = true;
   }
+  om->served_old = true;
   wait_enqueued(om);
   wait_enqueued(nm);
   HIPCHK(trk_wait_ready_once(c, om));

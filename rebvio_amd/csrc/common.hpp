@@ -417,6 +417,14 @@ void launch_edge_chains(hipStream_t s, const KParams& p, const MapDev& m, const 
 void launch_edge_polylines(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, const CloudArgs& a, int min_chain_length,
                            int cap_lines);
 
+// k_depth_prior on stream s (rebvio_hip_map_fuse_depth_image*): one Kalman update of (rho, sigma_rho) per keyline of m from the depth
+// image of a (depth_prior.hpp). cnt = 8 ints, cleared by the caller in front of the launch (the kernel leaves the six words of
+// rebvio_hip_depth_prior_counts there); outcome = kmax ints. ceil(kmax / 256) workgroups whatever the map holds.
+namespace dpr {
+struct Args;
+}
+void launch_depth_prior(hipStream_t s, const KParams& p, const MapDev& m, const dpr::Args& a, int* cnt, int* outcome);
+
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
 // ---- several camera streams ("lanes") of one GPU advanced in lock-step by batched launches (rebvio_hip_batch_*) --------

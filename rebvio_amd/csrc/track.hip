@@ -9,6 +9,7 @@
 // Bound: HBM/L2 gather bandwidth (keyline SoA streams + distance-field / mask / matched-keyline gathers);
 // no dense contraction exists on this path (largest product is 6x6), so MFMA does not apply.
 #include "common.hpp"
+#include "depth_prior.hpp"
 #include "edge_chains.hpp"
 #include "glue_dev.hpp"
 #include "kf_cloud.hpp"
@@ -4113,6 +4114,40 @@ void launch_edge_polylines(hipStream_t s, const KParams& p, const MapDev& m, con
   RH_LAUNCH(k_poly_count, grid, dim3(256), 0, s, m, c, f, min_chain_length);
   RH_LAUNCH(k_poly_emit, grid, dim3(256), 0, s, p, m, c, a, min_chain_length, cap_lines);
   RH_LAUNCH(k_poly_lines, grid, dim3(256), 0, s, c, cap_lines);
+}
+
+// ---- depth prior from a registered depth image (rebvio_hip_map_fuse_depth_image*) --------------------------------------------------
+// dpr::term (depth_prior.hpp) is the definition's per-keyline statement. One thread per keyline, the map's size read on the device:
+// pos, gradient, gradient_norm and (rho, sigma_rho) from the SoA arrays, up to three gathered taps of 2 or 4 bytes, the pair stored
+// back where the keyline is fused, the outcome word for every keyline. The image and the options come as kernel arguments (SGPRs).
+// The five counts (sampled, fused, gated, jumps, clamped) are ballots per wave, which kf_add_counts adds to cnt[1..5] - integer
+// sums, no floating-point value crosses threads. Slots behind the size get outcome 0.
+__global__ __launch_bounds__(256) void k_depth_prior(KParams p, MapDev m, dpr::Args a, int* __restrict__ cnt, int* __restrict__ outcome) {
+  __shared__ int sh_cnt[4][5];
+  const int tid = threadIdx.x;
+  const int n = min(max(m.st->n, 0), p.kmax);
+  const int i = blockIdx.x * 256 + tid;
+  int oc = dpr::kNone;
+  if (i < n) {
+    const float2 pos = m.pos[i], g = m.grad[i], rs = m.rs[i];
+    const float gn = m.gnorm[i];
+    float rho_n = 0.f, sig_n = 0.f;
+    oc = dpr::term(a, pos.x, pos.y, g.x, g.y, gn, rs.x, rs.y, &rho_n, &sig_n);
+    if ((oc & 3) == dpr::kFused) m.rs[i] = make_float2(rho_n, sig_n);
+  }
+  if (i < p.kmax) outcome[i] = oc;
+  int nc[5];
+  nc[0] = __popcll(__ballot(oc != dpr::kNone));
+  nc[1] = __popcll(__ballot((oc & 3) == dpr::kFused));
+  nc[2] = __popcll(__ballot((oc & 3) == dpr::kGated));
+  nc[3] = __popcll(__ballot((oc & dpr::kJumpBit) != 0));
+  nc[4] = __popcll(__ballot((oc & dpr::kClampedBit) != 0));
+  kf_add_counts(nc, sh_cnt, cnt + 1);
+  if (blockIdx.x == 0 && tid == 0) cnt[0] = n;
+}
+
+void launch_depth_prior(hipStream_t s, const KParams& p, const MapDev& m, const dpr::Args& a, int* cnt, int* outcome) {
+  RH_LAUNCH(k_depth_prior, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, p, m, a, cnt, outcome);
 }
 
 }  // namespace rh

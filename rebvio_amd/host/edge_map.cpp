@@ -145,6 +145,28 @@ std::vector<rebvio::types::CloudPoint> EdgeMap::pointCloud(const rebvio::types::
   return points;
 }
 
+rebvio::types::DepthPriorCounts EdgeMap::fuseDepthImage(const rebvio::types::DepthImage& image, const rebvio::types::DepthPriorOpts& opts,
+                                                        std::vector<int>* outcome) {
+  static_assert(sizeof(types::DepthPriorOpts) == sizeof(rebvio_hip_depth_prior_opts) &&
+                    offsetof(types::DepthPriorOpts, unit) == offsetof(rebvio_hip_depth_prior_opts, unit) &&
+                    offsetof(types::DepthPriorOpts, reserved) == offsetof(rebvio_hip_depth_prior_opts, reserved) &&
+                    sizeof(types::DepthPriorCounts) == sizeof(rebvio_hip_depth_prior_counts) &&
+                    offsetof(types::DepthPriorCounts, clamped) == offsetof(rebvio_hip_depth_prior_counts, clamped) &&
+                    (int)types::DEPTH_U16 == REBVIO_HIP_DEPTH_U16 && (int)types::DEPTH_F32 == REBVIO_HIP_DEPTH_F32,
+                "depth-prior types mirror the C-ABI's");
+  if (image.rows != (int)camera_->rows_ || image.cols != (int)camera_->cols_)
+    backend::fail("EdgeMap::fuseDepthImage: the depth image does not have the camera's size", -3);
+  types::DepthPriorOpts o = opts;
+  if (image.unit > 0.0) o.unit = image.unit;
+  if (outcome) outcome->assign((size_t)size(), 0);
+  types::DepthPriorCounts counts;
+  check("rebvio_hip_map_fuse_depth_image",
+        rebvio_hip_map_fuse_depth_image(handle_, image.data, image.pitch, image.format, reinterpret_cast<const rebvio_hip_depth_prior_opts*>(&o),
+                                        reinterpret_cast<rebvio_hip_depth_prior_counts*>(&counts), outcome && !outcome->empty() ? outcome->data() : nullptr));
+  invalidateMirror();
+  return counts;
+}
+
 EdgeMap::EdgeChains EdgeMap::edgeChains() {
   static_assert(sizeof(types::ChainRef) == sizeof(rebvio_hip_chain_ref) && offsetof(types::ChainRef, flags) == offsetof(rebvio_hip_chain_ref, flags),
                 "chain records mirror the C-ABI's");

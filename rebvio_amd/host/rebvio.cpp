@@ -67,6 +67,38 @@ Rebvio::~Rebvio() {
   run_ = false;
   if (data_acquisition_thread_.joinable()) data_acquisition_thread_.join();
   if (state_estimation_thread_.joinable()) state_estimation_thread_.join();
+  for (void*& p : depth_dev_)  // the depth images' device staging frames (the workers have ended: nothing reads them)
+    if (p) {
+      (void)rebvio_hip_device_free(core_.session()->ctx(), p);
+      p = nullptr;
+    }
+}
+
+void Rebvio::depthImageCallback(rebvio::types::DepthImage&& image) {
+  if (!image.data || (image.format != types::DEPTH_U16 && image.format != types::DEPTH_F32) || image.rows != (int)camera_.rows_ ||
+      image.cols != (int)camera_.cols_)
+    backend::fail("Rebvio::depthImageCallback: the depth image must be DEPTH_U16 or DEPTH_F32 of the camera's size", -3);
+  const size_t rowb = (size_t)image.cols * (image.format == types::DEPTH_U16 ? 2 : 4), pitch = image.pitch ? image.pitch : rowb;
+  if (pitch < rowb) backend::fail("Rebvio::depthImageCallback: pitch below a row's bytes", -3);
+  QueuedDepth q{image.ts_us, image.format, image.unit, std::vector<unsigned char>((size_t)image.rows * rowb)};
+  for (int r = 0; r < image.rows; ++r)
+    std::memcpy(q.bytes.data() + (size_t)r * rowb, static_cast<const unsigned char*>(image.data) + (size_t)r * pitch, rowb);
+  std::lock_guard<std::mutex> guard(depth_mutex_);
+  if (depth_queue_.size() >= 8) {
+    depth_queue_.pop_front();
+    ++depth_dropped_;
+  }
+  depth_queue_.push_back(std::move(q));
+  ++depth_seen_;
+}
+
+void Rebvio::setDepthPrior(const rebvio::types::DepthPriorOpts& opts) {
+  std::lock_guard<std::mutex> guard(depth_mutex_);
+  depth_opts_ = opts;
+}
+
+void Rebvio::registerDepthPriorCallback(std::function<void(uint64_t ts_us, const rebvio::types::DepthPriorCounts&)> cb) {
+  depth_prior_callbacks_.push_back(cb);
 }
 
 void Rebvio::imageCallback(rebvio::types::Image&& image) {
@@ -369,7 +401,40 @@ void Rebvio::stateEstimationProcess() {
     // edge-polyline callbacks: the new map's polylines, one extraction per callback, with the pose they were extracted at
     std::vector<rebvio::EdgeMap::EdgePolylines> polylines;
     types::CloudPose polyline_pose;
+    // depth images: a fusion into the new map was queued behind the second half; its counts (fetched where the pair's counters are)
+    bool have_depth = false;
+    types::DepthPriorCounts depth_counts;
   } pending;
+  // depth images. take_depth: the queued image with exactly this stamp (older ones are dropped and counted); nothing is touched
+  // while no image has ever been handed in. queue_depth: the image into one of the two device staging frames, then the fusion on
+  // the track stream in call order. The frame used two fusions ago is free: a pair's first half, which the thread has waited for
+  // by then, runs behind every earlier fusion.
+  auto take_depth = [&](uint64_t ts_us, QueuedDepth* out, types::DepthPriorOpts* opts) -> bool {
+    if (depth_seen_.load() == 0) return false;
+    std::lock_guard<std::mutex> guard(depth_mutex_);
+    while (!depth_queue_.empty() && depth_queue_.front().ts_us < ts_us) {
+      depth_queue_.pop_front();
+      ++depth_dropped_;
+    }
+    if (depth_queue_.empty() || depth_queue_.front().ts_us != ts_us) return false;
+    *out = std::move(depth_queue_.front());
+    depth_queue_.pop_front();
+    *opts = depth_opts_;
+    return true;
+  };
+  auto queue_depth = [&](rebvio::EdgeMap& map, const QueuedDepth& d, types::DepthPriorOpts opts) {
+    void*& dev = depth_dev_[depth_dev_turn_++ & 1u];
+    if (!dev) backend::check("rebvio_hip_device_alloc", rebvio_hip_device_alloc(ctx, (size_t)camera_.rows_ * camera_.cols_ * sizeof(float), &dev));
+    backend::check("rebvio_hip_device_upload", rebvio_hip_device_upload(ctx, dev, d.bytes.data(), d.bytes.size()));
+    if (d.unit > 0.0) opts.unit = d.unit;
+    backend::check("rebvio_hip_map_fuse_depth_image_async",
+                   rebvio_hip_map_fuse_depth_image_async(ctx, map.handle(), dev, 0, d.format, reinterpret_cast<const rebvio_hip_depth_prior_opts*>(&opts)));
+    map.invalidateMirror();
+  };
+  bool first_pair = true;          // the stream's first map takes its image in front of the first pair
+  bool have_first_depth = false;   // ... and its counts go out with the first record
+  uint64_t first_depth_ts = 0;
+  types::DepthPriorCounts first_depth_counts;
   // keyframe-pose callbacks: the snapshot of the current keyframe and the last pose estimated against it (the next one's guess)
   rebvio::KeyframeSnapshot kf_snapshot;
   types::KfPose kf_pose_last;
@@ -393,6 +458,12 @@ void Rebvio::stateEstimationProcess() {
     if (!pending.fetched) return;
     pending.fetched = false;
     for (auto& cb : odometry_callbacks_) cb(pending.odometry);
+    if (have_first_depth) {
+      have_first_depth = false;
+      for (auto& cb : depth_prior_callbacks_) cb(first_depth_ts, first_depth_counts);
+    }
+    if (pending.have_depth)
+      for (auto& cb : depth_prior_callbacks_) cb(pending.odometry.ts_us, pending.depth_counts);
     if (!keyframe_callbacks_.empty()) {
       const int keylines = pending.new_map->size();
       for (auto& cb : keyframe_callbacks_) cb(pending.odometry.ts_us, pending.kf_matches, keylines);
@@ -444,6 +515,9 @@ void Rebvio::stateEstimationProcess() {
     pending.fetched = true;
     int klm_num = 0, kf_matches = 0, reg_num = 0, status = 0;
     backend::check("rebvio_hip_track_pair_result", rebvio_hip_track_pair_result(ctx, &klm_num, &kf_matches, &reg_num, &status));
+    if (pending.have_depth)  // queued right behind that second half, and nothing of the kind since
+      backend::check("rebvio_hip_depth_prior_last_counts",
+                     rebvio_hip_depth_prior_last_counts(ctx, reinterpret_cast<rebvio_hip_depth_prior_counts*>(&pending.depth_counts)));
     for (rebvio_hip_cloud* cl : pending.clouds) {  // queued right behind that second half
       int n = 0;
       backend::check("rebvio_hip_cloud_wait", rebvio_hip_cloud_wait(cl, nullptr, &n, nullptr));
@@ -518,6 +592,20 @@ void Rebvio::stateEstimationProcess() {
         float bg[3] = {imu_state_.Bg[0], imu_state_.Bg[1], imu_state_.Bg[2]}, wb[9];
         store3(imu_state_.W_Bg, wb);
         rebvio_hip_set_gyro_state(ctx, bg, wb);
+      }
+    }
+
+    // depth images: the stream's first map has been no pair's new map - its image goes in right behind its detection
+    QueuedDepth depth_image;
+    types::DepthPriorOpts depth_opts;
+    if (first_pair) {
+      first_pair = false;
+      if (take_depth(old_edge_map->ts_us(), &depth_image, &depth_opts)) {
+        queue_depth(*old_edge_map, depth_image, depth_opts);
+        backend::check("rebvio_hip_depth_prior_last_counts",
+                       rebvio_hip_depth_prior_last_counts(ctx, reinterpret_cast<rebvio_hip_depth_prior_counts*>(&first_depth_counts)));
+        first_depth_ts = old_edge_map->ts_us();
+        have_first_depth = true;
       }
     }
 
@@ -639,6 +727,8 @@ void Rebvio::stateEstimationProcess() {
     // initialised (until then the bias still changes between pairs, rebvio.cpp:146-160). Not with a point-cloud callback: the
     // cloud shows the new map in THIS pair's frame, so the next pair's _begin launches its rotation itself.
     // Nor with a keyframe-pose or keyframe-cloud callback: snapshot and pose take the new map in this pair's frame as well.
+    // Nor while a depth image waits for the new map: it is folded into the map's depths in THIS pair's frame.
+    const bool have_depth = take_depth(new_edge_map->ts_us(), &depth_image, &depth_opts);
     float Rnext[9];
     bool have_next = false;
     rebvio::EdgeMap::SharedPtr next_map;
@@ -646,7 +736,7 @@ void Rebvio::stateEstimationProcess() {
       std::lock_guard<std::mutex> guard(edge_map_buffer_mutex_);
       if (edge_map_buffer_.size() >= 2) {
         next_map = edge_map_buffer_[1];
-        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud && !want_polylines) {
+        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud && !want_polylines && !have_depth) {
           store3(next_map->imu().R(), Rnext);
           have_next = true;
         }
@@ -657,6 +747,9 @@ void Rebvio::stateEstimationProcess() {
     backend::check("rebvio_hip_track_pair_finish_async",
                    rebvio_hip_track_pair_finish_async(ctx, old_edge_map->handle(), new_edge_map->handle(), V, pv, rg, r2,
                                                       have_next ? Rnext : nullptr));
+    // the depth image of the new map's frame, right behind the second half (which has written the map's depths for the last time
+    // as a new map) and in front of everything that reads them: clouds, keyframe snapshots, polylines, the next pair
+    if (have_depth) queue_depth(*new_edge_map, depth_image, depth_opts);
     if (want_cloud) {
       store3(R_global, cloud_pose.R);
       for (int i = 0; i < 3; ++i) cloud_pose.t[i] = Pos[i];
@@ -811,6 +904,7 @@ void Rebvio::stateEstimationProcess() {
     pending.kf_window = std::move(kf_window_poses);
     pending.polylines = std::move(polylines);
     pending.polyline_pose = polyline_pose;
+    pending.have_depth = have_depth;
     timers.lap(3);
     timers.end_pair();
     timers.n++;

@@ -31,6 +31,10 @@
 // --kf-cloud PREFIX [--kf-every N]: every retired keyframe's point cloud (Rebvio::registerKeyframeCloudCallback, default filter) as
 // PREFIX<ts_us>.ply, ts_us the keyframe's own stamp, through the same PLY writer; keyframes are requested as for --kf-pose. Alone it
 // writes the keyframes as marked; with --kf-fuse (and --kf-align) the refined ones. The keyframe current at the end is not written.
+// --depth FILE [--depth-unit U]: registered depth images, one per frame in frame order (frame 0 of the file belongs to frame 0 of the
+// stream, whatever --first is), raw little-endian uint16 counts of U metres (default 0.001; 0 = no depth), W x H each, dense. Every
+// frame's image is handed to Rebvio::depthImageCallback in front of the frame itself; the reader then stays at most seven frames
+// ahead of the tracker, so that none of the eight queued images is pushed out. The summary on stderr counts the images, the fused frames and keylines.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -38,13 +42,16 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <thread>
+#include <vector>
 
 #include "rebvio/io/stream_io.hpp"
 #include "rebvio/rebvio.hpp"
 
 int main(int argc, char** argv) {
   std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix, kf_window_path, kf_handover_path;
-  std::string polylines_prefix;
+  std::string polylines_prefix, depth_path;
+  double depth_unit = 0.001;
   int min_chain = 8;
   int kf_window = 0;
   bool kf_align = false;
@@ -57,7 +64,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
+                 "[--mask mask.png] [--depth FILE [--depth-unit U]] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -83,6 +90,8 @@ int main(int argc, char** argv) {
       if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0) return usage();
       mask_png = argv[++i];
     }
+    else if (a == "--depth") depth_path = next();
+    else if (a == "--depth-unit") depth_unit = std::atof(next());
     else if (a == "--cloud") cloud_prefix = next();
     else if (a == "--cloud-dry") cloud_dry = true;
     else if (a == "--polylines") {
@@ -121,7 +130,7 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1 || min_chain < 1) return usage();
+  if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1 || min_chain < 1 || !(depth_unit > 0.0)) return usage();
   if (!kf_window_path.empty() && (!kf_align || kf_pose_path.empty() || kf_window < 1 || kf_window > 15)) return usage();  // needs --kf-align FILE
   if (!kf_handover_path.empty() && (!kf_align || kf_pose_path.empty())) return usage();  // needs --kf-align FILE
   if (!kf_fuse_path.empty()) {  // the fusion runs behind the alignment only
@@ -261,11 +270,46 @@ int main(int argc, char** argv) {
         n_line_points += ep.size;
       }, po);
     }
+    std::FILE* depth_file = nullptr;
+    size_t n_depth = 0, n_depth_fused = 0, n_depth_handed = 0;
+    std::vector<uint16_t> depth_frame;
+    if (!depth_path.empty()) {
+      depth_file = std::fopen(depth_path.c_str(), "rb");
+      if (!depth_file || std::fseek(depth_file, (long)(first * (size_t)W * H * 2), SEEK_SET) != 0) {
+        std::fprintf(stderr, "error: cannot read %s\n", depth_path.c_str());
+        return 1;
+      }
+      depth_frame.resize((size_t)W * H);
+      rebvio.registerDepthPriorCallback([&](uint64_t, const rebvio::types::DepthPriorCounts& c) {
+        ++n_depth;
+        n_depth_fused += (size_t)c.fused;
+      });
+    }
     const size_t n = rebvio::io::replay(
-        *src, [&](rebvio::types::Image&& im) { rebvio.imageCallback(std::move(im)); },
+        *src,
+        [&](rebvio::types::Image&& im) {
+          if (depth_file && std::fread(depth_frame.data(), 2, depth_frame.size(), depth_file) == depth_frame.size()) {
+            while (n_depth_handed >= (size_t)rebvio.framesProcessed() + 7 && rebvio.running()) std::this_thread::sleep_for(std::chrono::microseconds(100));
+            rebvio::types::DepthImage d;
+            d.data = depth_frame.data();
+            d.rows = H;
+            d.cols = W;
+            d.format = rebvio::types::DEPTH_U16;
+            d.unit = depth_unit;
+            d.ts_us = im.ts_us;
+            rebvio.depthImageCallback(std::move(d));
+            ++n_depth_handed;
+          }
+          rebvio.imageCallback(std::move(im));
+        },
         [&](rebvio::types::Imu&& s) { rebvio.imuCallback(std::move(s)); }, first, count);
     rebvio.waitIdle();
     std::fprintf(stderr, "frames=%zu odometry=%zu running=%d\n", n, n_odo, (int)rebvio.running());
+    if (depth_file) {
+      std::fclose(depth_file);
+      std::fprintf(stderr, "depth_images=%zu depth_fused_frames=%zu depth_fused_keylines=%zu depth_dropped=%u\n", n_depth_handed, n_depth, n_depth_fused,
+                   rebvio.depthImagesDropped());
+    }
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
     if (!kf_cloud_prefix.empty()) std::fprintf(stderr, "kf_clouds=%zu kf_points=%zu\n", n_kf_clouds, n_kf_points);
     if (!polylines_prefix.empty()) std::fprintf(stderr, "polyline_files=%zu lines=%zu line_points=%zu\n", n_polyline_files, n_lines, n_line_points);

@@ -195,6 +195,32 @@ def render_stream(width: int, height: int, n_frames: int, stream_id: int = 0, de
     return frames, cam
 
 
+def render_depth(scene: Scene, cam: Camera, t: float) -> np.ndarray:
+    """Depth along the optical axis, in metres as float32 [height, width], of what frame t sees: the back plane inside a hole, the
+    front plane elsewhere. The hole test is hard (d < r) where render_frame blends over 1.2 pixels; no noise."""
+    R, p = pose(scene, t)
+    X, Y = cam.undistorted_rays()
+    dx = R[0, 0] * X + R[0, 1] * Y + R[0, 2]
+    dy = R[1, 0] * X + R[1, 1] * Y + R[1, 2]
+    dz = R[2, 0] * X + R[2, 1] * Y + R[2, 2]
+    s_front = (scene.z_front - p[2]) / dz  # the ray is s * (X, Y, 1) in the camera's frame: s is the depth along its axis
+    uf = (p[0] + s_front * dx).astype(np.float32)
+    vf = (p[1] + s_front * dy).astype(np.float32)
+    hole = np.zeros(uf.shape, bool)
+    for cu, cv, r in scene.hole_c:
+        hole |= np.sqrt((uf - cu) ** 2 + (vf - cv) ** 2) < r
+    return np.where(hole, (scene.z_back - p[2]) / dz, s_front).astype(np.float32)
+
+
+def render_stream_depth(width: int, height: int, n_frames: int, stream_id: int = 0, density: float = 1.0, dist=None) -> np.ndarray:
+    """The depth images (render_depth) of the frames render_stream gives for the same arguments -> float32 [n, H, W]."""
+    cam = Camera.for_size(width, height)
+    if dist is not None:
+        cam.dist = tuple(float(v) for v in dist)
+    scene = make_scene(stream_id, density)
+    return np.stack([render_depth(scene, cam, float(t)) for t in range(n_frames)])
+
+
 def imu_samples(scene: Scene, n_frames: int, frame_dt_us: int = 50000, rate_hz: int = 200, R_c2i=None, noise_seed: int | None = None,
                 gyro_bias=(0.0, 0.0, 0.0)):
     """Analytic IMU stream of the scene's motion (BASELINE config 5): constant world velocity (zero acceleration) and a
