@@ -13,6 +13,7 @@
 #include "rebvio/types/keyline.hpp"
 #include "rebvio/types/depth_image.hpp"
 #include "rebvio/types/point_cloud.hpp"
+#include "rebvio/types/stereo_prior.hpp"
 
 struct rebvio_hip_map;
 struct rebvio_hip_ctx;
@@ -146,6 +147,12 @@ class EdgeMap {
   rebvio::types::DepthPriorCounts fuseDepthImage(const rebvio::types::DepthImage& image,
                                                  const rebvio::types::DepthPriorOpts& opts = rebvio::types::DepthPriorOpts(),
                                                  std::vector<int>* outcome = nullptr);
+  // addition: the edge map of the rectified right image of the same instant folded into this map's rho / sigma_rho: an epipolar
+  // search in right's mask and one Kalman update per keyline (rebvio_hip_map_fuse_stereo defines it and says where in a stream it
+  // belongs, as fuseDepthImage; synchronous, from the tracking thread). right: a map of this detector or of another one with the
+  // same camera; it is only read. opts.baseline has no default. outcome / winner: the outcome word and the partner per keyline.
+  rebvio::types::StereoPriorCounts fuseStereo(const EdgeMap& right, const rebvio::types::StereoPriorOpts& opts,
+                                              std::vector<int>* outcome = nullptr, std::vector<int>* winner = nullptr);
   // addition: keyframes (rebvio_hip.h "Keyframes"). markKeyframe makes this map the keyframe: match_id_keyframe[i] = i for every
   // keyline, queued on the track stream - call it after the map has been a pair's new map and before it serves as an old map.
   // keyframeMatches(kf_size): which keylines of a keyframe of kf_size keylines live on in this map, in ascending kf_keyline

@@ -21,6 +21,7 @@
 #include "rebvio/types/image.hpp"
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/odometry.hpp"
+#include "rebvio/types/stereo_prior.hpp"
 #include "rebvio/types/point_cloud.hpp"
 
 namespace rebvio {
@@ -148,6 +149,20 @@ class Rebvio {
   void setDepthPrior(const rebvio::types::DepthPriorOpts& opts);
   void registerDepthPriorCallback(std::function<void(uint64_t ts_us, const rebvio::types::DepthPriorCounts&)> cb);
   unsigned int depthImagesDropped() const { return depth_dropped_; }
+  // addition: a rectified stereo partner (rebvio/types/stereo_prior.hpp, rebvio_hip.h "Depth prior from a rectified stereo
+  // partner"). setStereo makes a second, detect-only EdgeDetector with the left one's camera and parameters (a backend context
+  // of its own: the right camera gets its own threshold servo) and sets the options of the fusions queued from then on; call it
+  // before the first right image. rightImageCallback queues the image (at most 8; a ninth pushes the oldest out, counted as
+  // dropped); callable from any thread - hand it in AHEAD of the imageCallback of the same stamp. The right frames are assumed
+  // rectified to the left ones. The state-estimation thread matches an image to the left frame with the SAME ts_us, detects it and
+  // queues the fusion into that frame's map right behind the pair's second half, as a depth image (for a stream's first map: in
+  // front of its first pair); with a depth image for the same frame the depth image goes first. Older images are dropped and
+  // counted (rightImagesDropped). A frame without a partner runs exactly the calls it runs without all this. The stereo-prior
+  // callback gets the frame's stamp and the counts, once per fused frame, where the depth-prior callback gets its own.
+  void setStereo(const rebvio::types::StereoPriorOpts& opts);
+  void rightImageCallback(rebvio::types::Image&& image);
+  void registerStereoPriorCallback(std::function<void(uint64_t ts_us, const rebvio::types::StereoPriorCounts&)> cb);
+  unsigned int rightImagesDropped() const { return right_dropped_; }
   // addition: detection mask (EdgeDetector::setDetectionMask) for the frames handed to imageCallback after this call; frames
   // queued before it keep the mask they were queued with. Safe while the worker threads run. An empty Mat clears it.
   void setDetectionMask(const cv::Mat& mask);
@@ -216,6 +231,16 @@ class Rebvio {
   std::vector<std::function<void(uint64_t, const rebvio::types::DepthPriorCounts&)>> depth_prior_callbacks_;
   void* depth_dev_[2] = {nullptr, nullptr};
   unsigned int depth_dev_turn_ = 0;
+  // the stereo partner: its detector (setStereo), the queue of right images (under stereo_mutex_, with the options), and the two
+  // right maps the queued fusions may still read, kept in turn
+  std::unique_ptr<rebvio::EdgeDetector> right_detector_;
+  std::deque<rebvio::types::Image> right_queue_;
+  rebvio::types::StereoPriorOpts stereo_opts_;
+  std::mutex stereo_mutex_;
+  std::atomic<unsigned int> right_seen_{0}, right_dropped_{0};
+  std::vector<std::function<void(uint64_t, const rebvio::types::StereoPriorCounts&)>> stereo_prior_callbacks_;
+  rebvio::EdgeMap::SharedPtr right_hold_[2];
+  unsigned int right_hold_turn_ = 0;
   std::thread data_acquisition_thread_, state_estimation_thread_;
 };
 

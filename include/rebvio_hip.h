@@ -43,7 +43,9 @@ extern "C" {
  *    rebvio_hip_polyline_opts / rebvio_hip_polyline and the test hooks rebvio_hip_test_edge_chains_host /
  *    rebvio_hip_test_edge_polylines_host; the depth prior rebvio_hip_default_depth_prior_opts, rebvio_hip_map_fuse_depth_image(_device,
  *    _async), rebvio_hip_depth_prior_last_counts, their structs rebvio_hip_depth_prior_opts / rebvio_hip_depth_prior_counts and the
- *    test hook rebvio_hip_test_depth_prior_host. */
+ *    test hook rebvio_hip_test_depth_prior_host; the stereo prior rebvio_hip_default_stereo_prior_opts, rebvio_hip_map_fuse_stereo(_async),
+ *    rebvio_hip_stereo_prior_last_counts, their structs rebvio_hip_stereo_prior_opts / rebvio_hip_stereo_prior_counts and the test
+ *    hooks rebvio_hip_test_stereo_prior_host / rebvio_hip_test_map_set_mask. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -723,6 +725,103 @@ int rebvio_hip_test_depth_prior_host(int rows, int cols, rebvio_hip_keyline* key
                                      size_t pitch_bytes, int fmt, const rebvio_hip_depth_prior_opts* opts,
                                      rebvio_hip_depth_prior_counts* counts, int* outcome /*NULL or n ints*/);
 
+/* Depth prior from a rectified stereo partner: rebvio_hip_map_fuse_stereo searches, for every keyline of the LEFT map, the edge map
+ * detected in the RIGHT image of the same instant along the keyline's row, and folds the disparity it finds into the keyline's
+ * (rho, sigma_rho) with one scalar Kalman update - inverse depth is linear in disparity, rho = d / (fm * baseline). No reference
+ * counterpart. With it the map's depths, and V, are metric from the first frame on.
+ * Geometry: the pair is rectified - both images have the left context's rows x cols, fm, cx, cy, rows are aligned, the right camera
+ * sits at +baseline metres along the left camera's x axis: a point at depth z has disparity d = x_left - x_right = fm * baseline / z.
+ * Rectifying rotations are the caller's, as the registration of a depth image is.
+ * The left map is the tracker's. The right map is any detected map with the same rows and cols on the same device, of the left
+ * context or of another live one (a second camera wants its own threshold servo: a second, detect-only context is the intended
+ * source). It is only read.
+ * fp64 behind the loads; every + - * / sqrt, floor and ceil one IEEE operation in the order written, no contraction; a / b / c and
+ * a * b / c associate from the left. fb = (double)fm * baseline. Per left keyline i < size:
+ *   1. px = pos[0], py = pos[1] - the detector's position, NOT pos_img (as in the depth prior). The direction is usable when
+ *      gradient_norm > 0, ux = gradient[0] / gradient_norm and uy = gradient[1] / gradient_norm are both finite and
+ *      fabs(ux) >= min_ux (an edge parallel to the epipolar line measures no disparity). Otherwise UNUSABLE, all bits kept.
+ *   2. Inside means px + 0.5 >= 0 && px + 0.5 < cols && py + 0.5 >= 0 && py + 0.5 < rows (a NaN or infinite position is outside):
+ *      otherwise NONE. xi = (int)floor(px + 0.5), yi = (int)floor(py + 0.5). The window's rows are yi, and with row_tol = 1 also
+ *      yi - 1 and yi + 1; its columns xi - (int)ceil(d_max) - 1 ... xi - (int)floor(d_min) + 1; both clipped to the image. The
+ *      integer window is part of the definition.
+ *   3. Per cell of the window with j = mask_right[cell], 0 <= j < the right map's size, (qx, qy) = pos, (hx, hy) = gradient and
+ *      hn = gradient_norm of right keyline j: the keyline is a candidate when, in this order, hn > 0;
+ *      (gx * hx + gy * hy) / (gn * hn) >= cos_min;  fabs(hn / gn - 1.0) <= norm_tol;  with uxr = hx / hn, uyr = hy / hn:
+ *      fabs(uxr) >= min_ux;  xr = qx - (uyr * (py - qy)) / uxr  (where the right edge's tangent crosses the left keyline's row);
+ *      d = px - xr;  d > 0 && d_min <= d && d <= d_max. All tests are positive: a NaN fails. A keyline with a candidate is SEEN;
+ *      without one: NONE.
+ *   4. rho_m = d / fb;  s_m = (sigma_px / fabs(ux)) / fb;  s = (double)sigma_rho;  v = s * s + q_abs * q_abs;  S = v + s_m * s_m;
+ *      e = rho_m - (double)rho.  A candidate is IN the gate when e * e <= (gate_sigma * gate_sigma) * S. SEEN with none in: GATED.
+ *   5. d_lo, d_hi = the smallest and the largest d of the candidates in the gate. d_hi - d_lo > ambig_px: AMBIGUOUS, the keyline is
+ *      left as it was - its own prior is what disambiguates repeated structure once it is metric; a fresh keyline in front of a
+ *      grating stays untouched.
+ *   6. The winner is the candidate in the gate with the smallest (gx - hx) * (gx - hx) + (gy - hy) * (gy - hy), ties to the smaller
+ *      j. With its d:  K = v / S;  rho_n = rho + K * e;  v_n = (1.0 - K) * v;  sig_n = sqrt(v_n);  GATED unless rho_n, v_n and
+ *      sig_n are finite and v_n >= 0; then the RHO_MIN / RHO_MAX clamp of the depth prior's step 5, counted as clamped. FUSED: the
+ *      map gets (float)rho_n and (float)sig_n. matches and every other field are untouched.
+ * outcome[i] = 0 none, 1 fused, 2 gated, 3 unusable, 4 ambiguous;  + 32 for clamped (with 1). winner[i] = the winner's j where
+ * fused, else -1. Counts: candidates = the left map's size, usable = those not UNUSABLE, seen, fused, gated, ambiguous, clamped -
+ * integer sums. Only minima, maxima, an OR and integer sums cross threads: every output word is the same on every run and in any
+ * order of the window's cells.
+ * Where in a stream: as the depth image - the right map of frame k goes into left map k AFTER the pair in which k was the new map,
+ * or right after detection for a stream's first map, and BEFORE map k serves as an old map. With a depth image for the same frame
+ * the depth image goes first.
+ * Map acceptance: the left map as for the depth image (-7 when promised to R_prior_next or when it has served as an old map; -10
+ * when its context is destroyed). The right map: -3 when it is null, of another rows x cols or of another device; -10 when its
+ * context is destroyed. -3 also for null counts, a left map of another context than ctx (queued entry) and an invalid option
+ * (rebvio_hip_last_error names it); every -3 is checked before the device is touched.
+ * One kernel per call (k_stereo_prior: 16 lanes per left keyline take consecutive cells of the window's rows, ceil(keylines_max /
+ * 16) workgroups of 256, both sizes read on the device) behind one clear of the count block, on the LEFT context's track stream
+ * under the track-side thread rule of rebvio_hip_map_point_cloud. Before queuing, the entry waits on the host for the right map's
+ * own detection (as rebvio_hip_map_download of a fresh map does); what the right map's context has queued for it beyond that is
+ * the caller's to order. The first call gives the left context one more owned device allocation (8 count words and 2 *
+ * keylines_max words; kept until the context goes).
+ *   rebvio_hip_map_fuse_stereo            synchronous. outcome_host, winner_host: NULL, or room for the left map's size each.
+ *   rebvio_hip_map_fuse_stereo_async      queued in call order, returns at once - for use between _finish_async(k) and _begin(k+1).
+ *                                         The caller keeps the right map unreleased until the counts have been fetched
+ *                                         (rebvio_hip_stereo_prior_last_counts) or a later synchronising call on the left context
+ *                                         has returned.
+ *   rebvio_hip_stereo_prior_last_counts   the counts of ctx's most recent stereo fusion (either entry); waits for them; all zero
+ *                                         before the first.
+ *   rebvio_hip_test_stereo_prior_host     test hook, touches no device: the same statements over n left keylines (rho / sigma_rho
+ *                                         updated in place) in index order, the window's cells row by row. right_mask: rows * cols
+ *                                         ints; words outside [0, nr) are no keyline. -3 as above, and for a negative size. */
+typedef struct rebvio_hip_stereo_prior_opts { /* defaults from rebvio_hip_default_stereo_prior_opts */
+  double baseline;   /* > 0, no default (0 after the defaults call): metres between the cameras */
+  double d_min;      /* default 0;  0 <= d_min <= d_max <= cols: accepted disparities, pixels */
+  double d_max;      /* default 64 */
+  double min_ux;     /* in (0, 1], default 0.5: least |x component| of a unit gradient, left and right */
+  int row_tol;       /* 0 or 1, default 1: rows searched above and below the keyline's */
+  double sigma_px;  /* > 0, default 0.5: standard deviation of a disparity along the gradient, pixels */
+  double gate_sigma; /* > 0, default 3.0: innovation gate in standard deviations */
+  double ambig_px;   /* >= 0, default 2.0: largest spread of the disparities in the gate */
+  double cos_min;    /* in [-1, 1], default cos(match_threshold_angle): least cosine between the two gradients */
+  double norm_tol;   /* >= 0, default match_threshold_norm: largest |gn' / gn - 1| */
+  double q_abs;      /* >= 0, default 0: added in quadrature to sigma_rho before the update */
+  int reserved;      /* 0 */
+} rebvio_hip_stereo_prior_opts;
+typedef struct rebvio_hip_stereo_prior_counts {
+  int candidates; /* the left map's size */
+  int usable;     /* keylines with a usable direction */
+  int seen;       /* ...with at least one candidate in the window */
+  int fused;      /* ...updated */
+  int gated;      /* seen, but no candidate inside the gate, or a non-finite update (left as they were) */
+  int ambiguous;  /* the gate's candidates spread over more than ambig_px (left as they were) */
+  int clamped;    /* among fused: rho ran into RHO_MIN or RHO_MAX */
+  int reserved;   /* 0 */
+} rebvio_hip_stereo_prior_counts;
+/* ctx NULL: cos_min = cos(45 degrees), norm_tol = 1, the default context's. */
+void rebvio_hip_default_stereo_prior_opts(rebvio_hip_ctx* ctx /*NULL ok*/, rebvio_hip_stereo_prior_opts* opts);
+int rebvio_hip_map_fuse_stereo(rebvio_hip_map* left, rebvio_hip_map* right, const rebvio_hip_stereo_prior_opts* opts,
+                               rebvio_hip_stereo_prior_counts* counts, int* outcome_host /*NULL ok*/, int* winner_host /*NULL ok*/);
+int rebvio_hip_map_fuse_stereo_async(rebvio_hip_ctx* ctx, rebvio_hip_map* left, rebvio_hip_map* right,
+                                     const rebvio_hip_stereo_prior_opts* opts);
+int rebvio_hip_stereo_prior_last_counts(rebvio_hip_ctx* ctx, rebvio_hip_stereo_prior_counts* counts);
+int rebvio_hip_test_stereo_prior_host(int rows, int cols, float fm, rebvio_hip_keyline* left /*in/out*/, int n,
+                                      const rebvio_hip_keyline* right, int nr, const int* right_mask,
+                                      const rebvio_hip_stereo_prior_opts* opts, rebvio_hip_stereo_prior_counts* counts,
+                                      int* outcome /*NULL or n ints*/, int* winner /*NULL or n ints*/);
+
 /* Depth hand-over between keyframe snapshots: what the fusion above has made of a retiring keyframe's rho / sigma_rho is lost when
  * the next keyframe is marked - the successor's snapshot is cut from the tracker's map and starts with the tracker's raw depths.
  * rebvio_hip_kf_snapshot_handover_depth carries the refined depths over, as forwardMatch + updateInverseDepth carry depth from map
@@ -833,6 +932,10 @@ int rebvio_hip_test_kf_cloud_host(float fm, const float* snap_prs4, const unsign
 
 /* Test hook: overwrite the device keylines (count must equal the map size). */
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n);
+/* Test hook: overwrite the device's dense mask (rows * cols ints, each -1 or a keyline index below the map's size; -3 otherwise) - with
+ * rebvio_hip_map_upload a right map for rebvio_hip_map_fuse_stereo planted by hand. The map's distance field is not rebuilt: such a
+ * map is not for tracking. */
+int rebvio_hip_test_map_set_mask(rebvio_hip_map* m, const int* mask);
 /* Map handles may outlive their context: after rebvio_hip_destroy the entries that take a map alone (size, threshold, download,
  * render, upload, map_distance_field) fail with -10 (NaN for the threshold) and rebvio_hip_map_release frees what is left of the
  * handle - nothing of the destroyed context is touched. (A handle must still be released exactly once.) */

@@ -131,6 +131,22 @@ class DepthPriorCounts(C.Structure):
         return (self.candidates, self.sampled, self.fused, self.gated, self.jumps, self.clamped)
 
 
+class StereoPriorOpts(C.Structure):
+    """rebvio_hip_stereo_prior_opts (Map.fuse_stereo); defaults from default_stereo_prior_opts, baseline has none"""
+    _fields_ = [("baseline", C.c_double), ("d_min", C.c_double), ("d_max", C.c_double), ("min_ux", C.c_double), ("row_tol", C.c_int),
+                ("sigma_px", C.c_double), ("gate_sigma", C.c_double), ("ambig_px", C.c_double), ("cos_min", C.c_double),
+                ("norm_tol", C.c_double), ("q_abs", C.c_double), ("reserved", C.c_int)]
+
+
+class StereoPriorCounts(C.Structure):
+    """rebvio_hip_stereo_prior_counts: the counts of one stereo fusion"""
+    _fields_ = [("candidates", C.c_int), ("usable", C.c_int), ("seen", C.c_int), ("fused", C.c_int), ("gated", C.c_int),
+                ("ambiguous", C.c_int), ("clamped", C.c_int), ("reserved", C.c_int)]
+
+    def as_tuple(self):
+        return (self.candidates, self.usable, self.seen, self.fused, self.gated, self.ambiguous, self.clamped, self.reserved)
+
+
 class KfHandoverOpts(C.Structure):
     """rebvio_hip_kf_handover_opts (KfSnapshot.handover_depth); defaults from default_kf_handover_opts"""
     _fields_ = [("kf_filter", CloudFilter), ("min_cos", C.c_double), ("gate_sigma", C.c_double), ("q_abs", C.c_double),
@@ -303,6 +319,13 @@ SIGNATURES = {
     "rebvio_hip_depth_prior_last_counts": (C.c_int, [_vp, C.POINTER(DepthPriorCounts)]),
     "rebvio_hip_test_depth_prior_host": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, C.c_int,
                                                    C.POINTER(DepthPriorOpts), C.POINTER(DepthPriorCounts), _ip]),
+    "rebvio_hip_default_stereo_prior_opts": (None, [_vp, C.POINTER(StereoPriorOpts)]),
+    "rebvio_hip_map_fuse_stereo": (C.c_int, [_vp, _vp, C.POINTER(StereoPriorOpts), C.POINTER(StereoPriorCounts), _ip, _ip]),
+    "rebvio_hip_map_fuse_stereo_async": (C.c_int, [_vp, _vp, _vp, C.POINTER(StereoPriorOpts)]),
+    "rebvio_hip_stereo_prior_last_counts": (C.c_int, [_vp, C.POINTER(StereoPriorCounts)]),
+    "rebvio_hip_test_stereo_prior_host": (C.c_int, [C.c_int, C.c_int, C.c_float, _vp, C.c_int, _vp, C.c_int, _vp,
+                                                    C.POINTER(StereoPriorOpts), C.POINTER(StereoPriorCounts), _ip, _ip]),
+    "rebvio_hip_test_map_set_mask": (C.c_int, [_vp, _vp]),
     "rebvio_hip_test_live_resources": (C.c_long, []),
     "rebvio_hip_test_handover_counters": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "rebvio_hip_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -733,6 +756,33 @@ def depth_prior_host(rows, cols, keylines, depth, fmt=None, opts=None):
     return out, kl, outcome
 
 
+def default_stereo_prior_opts(ctx=None, **over) -> StereoPriorOpts:
+    """The library's defaults (rebvio_hip_default_stereo_prior_opts): cos_min and norm_tol are ctx's match_threshold_angle and
+    match_threshold_norm (45 degrees and 1, the default ones, without a context). baseline has no default: give it."""
+    o = StereoPriorOpts()
+    lib().rebvio_hip_default_stereo_prior_opts(ctx.h if ctx is not None else None, C.byref(o))
+    for k, v in over.items():
+        setattr(o, k, v)
+    return o
+
+
+def stereo_prior_host(rows, cols, fm, left, right, right_mask, opts):
+    """Map.fuse_stereo on the host, from arrays (rebvio_hip_test_stereo_prior_host). Touches no device and leaves its inputs alone.
+    Returns (StereoPriorCounts, the updated KEYLINE_DTYPE copy of left, outcome int32 [n], winner int32 [n])."""
+    kl = np.array(left, KEYLINE_DTYPE).reshape(-1)  # (a copy: the hook updates it in place)
+    kr = np.ascontiguousarray(right, KEYLINE_DTYPE).reshape(-1)
+    mask = np.ascontiguousarray(right_mask, np.int32).reshape(-1)
+    assert mask.size == int(rows) * int(cols), (mask.size, rows, cols)
+    out = StereoPriorCounts()
+    outcome = np.zeros(len(kl), np.int32)
+    winner = np.zeros(len(kl), np.int32)
+    _chk(lib().rebvio_hip_test_stereo_prior_host(int(rows), int(cols), float(fm), kl.ctypes.data if len(kl) else None, len(kl),
+                                                 kr.ctypes.data if len(kr) else None, len(kr), mask.ctypes.data if mask.size else None,
+                                                 opts, C.byref(out), outcome.ctypes.data_as(_ip) if len(kl) else None,
+                                                 winner.ctypes.data_as(_ip) if len(kl) else None))
+    return out, kl, outcome, winner
+
+
 def default_kf_handover_opts(ctx=None, **over) -> KfHandoverOpts:
     """The library's defaults (rebvio_hip_default_kf_handover_opts): max_dist is ctx's search_range (40, the default one, without a
     context); kf_filter takes a CloudFilter or a dict of its fields to change."""
@@ -1111,6 +1161,30 @@ class Map:
         del keep
         return (out, outcome[:out.candidates]) if want_outcome else out
 
+    def set_mask(self, mask: np.ndarray):
+        """Test hook: overwrite the dense mask (rebvio_hip_test_map_set_mask), for a right map planted by hand."""
+        mask = np.ascontiguousarray(mask, np.int32)
+        assert mask.size == self.ctx.rows * self.ctx.cols, mask.shape
+        _chk(lib().rebvio_hip_test_map_set_mask(self.h, mask.ctypes.data))
+
+    def fuse_stereo(self, right, opts, queued=False, want_outcome=False):
+        """Folds the disparities found in `right`, the edge map of the rectified right image of the same instant (a Map of this
+        context or of another one on the same device), into this map's (rho, sigma_rho) (rebvio_hip_map_fuse_stereo*;
+        include/rebvio_hip.h is the definition and says where in a stream it belongs). Returns the StereoPriorCounts, with
+        want_outcome also the int32 outcome and winner words per keyline; queued=True returns None at once:
+        Context.stereo_prior_last_counts fetches the counts, and `right` stays unreleased until then."""
+        rh = right.h if right is not None else None
+        if queued:
+            _chk(lib().rebvio_hip_map_fuse_stereo_async(self.ctx.h, self.h, rh, opts))
+            return None
+        out = StereoPriorCounts()
+        kmax = self.ctx.p.keylines_max
+        outcome = np.zeros(kmax, np.int32) if want_outcome else None
+        winner = np.zeros(kmax, np.int32) if want_outcome else None
+        _chk(lib().rebvio_hip_map_fuse_stereo(self.h, rh, opts, C.byref(out), outcome.ctypes.data_as(_ip) if want_outcome else None,
+                                              winner.ctypes.data_as(_ip) if want_outcome else None))
+        return (out, outcome[:out.candidates], winner[:out.candidates]) if want_outcome else out
+
     def upload(self, kl: np.ndarray):
         kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)
         _chk(lib().rebvio_hip_map_upload(self.h, kl.ctypes.data if kl.size else None, len(kl)))
@@ -1257,6 +1331,13 @@ class Context:
         (rebvio_hip_depth_prior_last_counts). All zero before the first."""
         out = DepthPriorCounts()
         _chk(lib().rebvio_hip_depth_prior_last_counts(self.h, C.byref(out)))
+        return out
+
+    def stereo_prior_last_counts(self) -> StereoPriorCounts:
+        """The counts of the context's most recent stereo fusion, queued ones included; waits for them
+        (rebvio_hip_stereo_prior_last_counts). All zero before the first."""
+        out = StereoPriorCounts()
+        _chk(lib().rebvio_hip_stereo_prior_last_counts(self.h, C.byref(out)))
         return out
 
     def detect_u8_device(self, dev_addr: int, ts_us=0) -> Map:

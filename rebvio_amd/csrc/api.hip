@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <shared_mutex>
 #include <thread>
 #include <string>
@@ -30,6 +31,7 @@
 #include "kf_pose.hpp"
 #include "owned.hpp"
 #include "pixel_format.hpp"
+#include "stereo_prior.hpp"
 
 using namespace rh;
 
@@ -579,6 +581,13 @@ struct rebvio_hip_ctx {
   int* dpr_outcome = nullptr;  // (a view into dpr_cnt's allocation)
   char* dpr_pin = nullptr;
   bool dpr_queued = false;
+  // scratch of the stereo entries (ONE device allocation on first use, kept; track-side entries): 8 count words
+  // (rebvio_hip_stereo_prior_counts), then keylines_max outcome words, then keylines_max winner words. spr_queued: a fusion has
+  // been queued.
+  int* spr_cnt = nullptr;
+  int* spr_outcome = nullptr;  // (views into spr_cnt's allocation)
+  int* spr_winner = nullptr;
+  bool spr_queued = false;
 };
 
 namespace {
@@ -2917,6 +2926,205 @@ int rebvio_hip_test_depth_prior_host(int rows, int cols, rebvio_hip_keyline* key
   return 0;
 }
 
+// ---- depth prior from a rectified stereo partner's edge map (include/rebvio_hip.h is the definition; stereo_prior.hpp the statements)
+void rebvio_hip_default_stereo_prior_opts(rebvio_hip_ctx* c, rebvio_hip_stereo_prior_opts* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->d_min = 0.0;
+  o->d_max = 64.0;
+  o->min_ux = 0.5;
+  o->row_tol = 1;
+  o->sigma_px = 0.5;
+  o->gate_sigma = 3.0;
+  o->ambig_px = 2.0;
+  o->cos_min = c ? (double)c->K.cang_min_edge : (double)(float)std::cos(45.0 * M_PI / 180.0);  // (as create leaves it in KParams)
+  o->norm_tol = c ? (double)c->K.match_threshold_norm : 1.0;
+  o->q_abs = 0.0;
+}
+
+namespace {
+static_assert(sizeof(rebvio_hip_stereo_prior_opts) == 96, "four doubles, an int, six doubles, an int, padding");
+static_assert(sizeof(rebvio_hip_stereo_prior_counts) == 32, "eight ints");
+
+// The options, refused before the device is touched.
+int check_stereo_prior_opts(const char* who, int cols, const rebvio_hip_stereo_prior_opts& o) {
+  const std::string w(who);
+  if (!(o.baseline > 0.0 && o.baseline < HUGE_VAL)) return fail_msg((w + ": baseline must be > 0 and finite").c_str(), -3);
+  if (!(o.d_min >= 0.0 && o.d_min <= o.d_max && o.d_max <= (double)cols))
+    return fail_msg((w + ": 0 <= d_min <= d_max <= cols does not hold").c_str(), -3);
+  if (!(o.min_ux > 0.0 && o.min_ux <= 1.0)) return fail_msg((w + ": min_ux must be in (0, 1]").c_str(), -3);
+  if (o.row_tol != 0 && o.row_tol != 1) return fail_msg((w + ": row_tol must be 0 or 1").c_str(), -3);
+  if (!(o.sigma_px > 0.0 && o.sigma_px < HUGE_VAL)) return fail_msg((w + ": sigma_px must be > 0 and finite").c_str(), -3);
+  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
+  if (!(o.ambig_px >= 0.0)) return fail_msg((w + ": ambig_px must be >= 0").c_str(), -3);
+  if (!(o.cos_min >= -1.0 && o.cos_min <= 1.0)) return fail_msg((w + ": cos_min must be in [-1, 1]").c_str(), -3);
+  if (!(o.norm_tol >= 0.0)) return fail_msg((w + ": norm_tol must be >= 0").c_str(), -3);
+  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
+  if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
+  return 0;
+}
+
+// Holds the life blocks of a left and a right map for an entry's duration: one block once when both maps are of one context (a
+// shared_mutex is not taken twice by one thread), else both, in the order of their addresses.
+class PairAlive {
+ public:
+  PairAlive(const rebvio_hip_map* l, const rebvio_hip_map* r) {
+    const bool same = l->life.get() == r->life.get();
+    const bool l_first = same || std::less<const LifeBlock*>()(l->life.get(), r->life.get());
+    if (l_first) a_.emplace(l); else a_.emplace(r);
+    if (!same) {
+      if (l_first) b_.emplace(r); else b_.emplace(l);
+    }
+    dead_ = a_->dead() || (b_ && b_->dead());
+  }
+  bool dead() const { return dead_; }
+
+ private:
+  std::optional<MapAlive> a_, b_;
+  bool dead_;
+};
+
+// Everything between the null checks and the launch that both entries share. The caller holds the life blocks. -3 for a right map
+// that does not fit and for the options, before the device is touched; then the left map's state rule, the scratch, the host wait
+// for the right map's detection, the clear and the kernel on the left context's track stream.
+int enqueue_stereo_prior(const char* who, rebvio_hip_map* m, rebvio_hip_map* r, const rebvio_hip_stereo_prior_opts* opts) {
+  const std::string w(who);
+  rebvio_hip_ctx* c = m->ctx;
+  const rebvio_hip_ctx* rc = r->ctx;
+  if (rc->P.rows != c->P.rows || rc->P.cols != c->P.cols) return fail_msg((w + ": the right map has another rows x cols").c_str(), -3);
+  if (rc->device != c->device) return fail_msg((w + ": the right map lives on another device").c_str(), -3);
+  rebvio_hip_stereo_prior_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_stereo_prior_opts(c, &o);
+  int rv = check_stereo_prior_opts(who, c->P.cols, o);
+  if (rv) return rv;
+  rv = depth_prior_state_rule(who, m);
+  if (rv) return rv;
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->spr_cnt) {
+    char* b = nullptr;
+    HIPCHK(c->own.device_bytes(&b, (8 + 2 * (size_t)c->P.keylines_max) * sizeof(int)));
+    c->spr_cnt = reinterpret_cast<int*>(b);
+    c->spr_outcome = c->spr_cnt + 8;
+    c->spr_winner = c->spr_outcome + c->P.keylines_max;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  if (r != m) {
+    // the right map's own detection (+ distance field), on the host: no event of another context enters this stream
+    wait_enqueued(r);
+    HIPCHK(hipEventSynchronize(r->ready));
+  }
+  HIPCHK(hipMemsetAsync(c->spr_cnt, 0, 8 * sizeof(int), c->s_trk));
+  launch_stereo_prior(c->s_trk, c->K, m->d, r->d, rc->P.keylines_max, spr::make_args(c->P.rows, c->P.cols, c->P.fm, o), c->spr_cnt,
+                      c->spr_outcome, c->spr_winner);
+  HIPCHK(hipGetLastError());
+  c->spr_queued = true;
+  return 0;
+}
+
+// Behind enqueue_stereo_prior: the counts, then exactly the outcome / winner words that exist.
+int fetch_stereo_prior(rebvio_hip_ctx* c, rebvio_hip_stereo_prior_counts* counts, int* outcome_host, int* winner_host) {
+  rebvio_hip_stereo_prior_counts res;
+  HIPCHK(hipMemcpyAsync(&res, c->spr_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  int rc = trk_sync(c);
+  if (rc) return rc;
+  if ((outcome_host || winner_host) && res.candidates > 0) {
+    const size_t bytes = (size_t)res.candidates * sizeof(int);
+    if (outcome_host) HIPCHK(hipMemcpyAsync(outcome_host, c->spr_outcome, bytes, hipMemcpyDeviceToHost, c->s_trk));
+    if (winner_host) HIPCHK(hipMemcpyAsync(winner_host, c->spr_winner, bytes, hipMemcpyDeviceToHost, c->s_trk));
+    rc = trk_sync(c);
+    if (rc) return rc;
+  }
+  *counts = res;
+  return 0;
+}
+}  // namespace
+
+int rebvio_hip_map_fuse_stereo(rebvio_hip_map* m, rebvio_hip_map* r, const rebvio_hip_stereo_prior_opts* opts,
+                               rebvio_hip_stereo_prior_counts* counts, int* outcome_host, int* winner_host) {
+  if (!m) return fail_msg("map_fuse_stereo: null left map", -3);
+  if (!r) return fail_msg("map_fuse_stereo: null right map", -3);
+  if (!counts) return fail_msg("map_fuse_stereo: null counts", -3);
+  const PairAlive alive(m, r);
+  if (alive.dead()) return -10;
+  std::memset(counts, 0, sizeof(*counts));
+  const int rc = enqueue_stereo_prior("map_fuse_stereo", m, r, opts);
+  if (rc) return rc;
+  return fetch_stereo_prior(m->ctx, counts, outcome_host, winner_host);
+}
+
+int rebvio_hip_map_fuse_stereo_async(rebvio_hip_ctx* c, rebvio_hip_map* m, rebvio_hip_map* r, const rebvio_hip_stereo_prior_opts* opts) {
+  if (!c || !m) return fail_msg("map_fuse_stereo_async: null context or left map", -3);
+  if (!r) return fail_msg("map_fuse_stereo_async: null right map", -3);
+  const PairAlive alive(m, r);
+  if (alive.dead()) return -10;
+  if (m->ctx != c) return fail_msg("map_fuse_stereo_async: left map of another context", -3);
+  return enqueue_stereo_prior("map_fuse_stereo_async", m, r, opts);
+}
+
+int rebvio_hip_stereo_prior_last_counts(rebvio_hip_ctx* c, rebvio_hip_stereo_prior_counts* counts) {
+  if (!c || !counts) return fail_msg("stereo_prior_last_counts: null context or counts", -3);
+  std::memset(counts, 0, sizeof(*counts));
+  if (!c->spr_queued) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  return fetch_stereo_prior(c, counts, nullptr, nullptr);
+}
+
+int rebvio_hip_test_stereo_prior_host(int rows, int cols, float fm, rebvio_hip_keyline* left, int n, const rebvio_hip_keyline* right, int nr,
+                                      const int* right_mask, const rebvio_hip_stereo_prior_opts* opts, rebvio_hip_stereo_prior_counts* counts,
+                                      int* outcome, int* winner) {
+  if (!counts || n < 0 || nr < 0 || rows < 0 || cols < 0 || (n > 0 && !left) || (nr > 0 && !right) || ((size_t)rows * cols > 0 && !right_mask))
+    return fail_msg("test_stereo_prior_host: null array or negative size", -3);
+  rebvio_hip_stereo_prior_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_stereo_prior_opts(nullptr, &o);
+  const int rc = check_stereo_prior_opts("test_stereo_prior_host", cols, o);
+  if (rc) return rc;
+  const spr::Args a = spr::make_args(rows, cols, fm, o);
+  rebvio_hip_stereo_prior_counts res;
+  std::memset(&res, 0, sizeof(res));
+  res.candidates = n;
+  for (int i = 0; i < n; ++i) {
+    rebvio_hip_keyline& k = left[i];
+    spr::Left L;
+    int oc = spr::left_setup(a, k.pos[0], k.pos[1], k.gradient[0], k.gradient[1], k.gradient_norm, k.rho, k.sigma_rho, &L);
+    int win = -1;
+    if (oc != spr::kUnusable) ++res.usable;
+    if (oc < 0) {
+      spr::Fold f;
+      spr::fold_clear(&f);
+      for (int t = 0; t < (a.row_tol ? 3 : 1); ++t) {
+        const int y = L.yi + (t == 0 ? 0 : (t == 1 ? -1 : 1));
+        if (y < 0 || y >= rows) continue;
+        const int* row = right_mask + (size_t)y * cols;
+        for (int x = L.x0; x <= L.x1; ++x) {
+          const int j = row[x];
+          if (j < 0 || j >= nr) continue;
+          const rebvio_hip_keyline& q = right[j];
+          spr::fold_candidate(a, L, j, q.pos[0], q.pos[1], q.gradient[0], q.gradient[1], q.gradient_norm, &f);
+        }
+      }
+      if (f.seen & 1) ++res.seen;
+      oc = spr::decide(a, f);
+      if (oc < 0) {
+        float rho_n = 0.f, sig_n = 0.f;
+        oc = spr::update(a, L, f.d_win, &rho_n, &sig_n);
+        if ((oc & 7) == spr::kFused) {
+          win = f.j;
+          k.rho = rho_n;
+          k.sigma_rho = sig_n;
+        }
+      }
+    }
+    if ((oc & 7) == spr::kFused) ++res.fused;
+    if ((oc & 7) == spr::kGated) ++res.gated;
+    if ((oc & 7) == spr::kAmbiguous) ++res.ambiguous;
+    if (oc & spr::kClampedBit) ++res.clamped;
+    if (outcome) outcome[i] = oc;
+    if (winner) winner[i] = win;
+  }
+  *counts = res;
+  return 0;
+}
+
 void rebvio_hip_default_kf_handover_opts(rebvio_hip_ctx* c, rebvio_hip_kf_handover_opts* o) {
   std::memset(o, 0, sizeof(*o));
   rebvio_hip_default_cloud_filter(&o->kf_filter);
@@ -3249,6 +3457,28 @@ int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines,
   HIPCHK(hipStreamSynchronize(c->s_key));
   m->df_built = false;
   m->raster_order = false;  // arbitrary keylines: the rebuild goes through the scatter kernel
+  return 0;
+}
+
+int rebvio_hip_test_map_set_mask(rebvio_hip_map* m, const int* mask) {
+  if (!m || !mask) return fail_msg("test_map_set_mask: null map or mask", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = m->ctx;
+  const size_t Pn = (size_t)c->P.rows * c->P.cols;
+  HIPCHK(hipSetDevice(c->device));
+  int rc = ensure_size(m);
+  if (rc) return rc;
+  for (size_t k = 0; k < Pn; ++k)
+    if (mask[k] < -1 || mask[k] >= m->n_host) return fail_msg("test_map_set_mask: a word outside [-1, size)", -3);
+  std::lock_guard<std::mutex> dl(c->dl_mu);
+  HIPCHK(hipStreamSynchronize(c->s_key));
+  HIPCHK(hipStreamSynchronize(c->s_det));
+  HIPCHK(hipStreamSynchronize(c->s_key));
+  { const int rc_ts = trk_sync(c); if (rc_ts) return rc_ts; }
+  HIPCHK(hipMemcpyAsync(m->d.mask, mask, Pn * sizeof(int), hipMemcpyHostToDevice, c->s_key));
+  HIPCHK(hipStreamSynchronize(c->s_key));
+  m->df_built = false;
   return 0;
 }
 

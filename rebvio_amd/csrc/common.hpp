@@ -425,6 +425,16 @@ struct Args;
 }
 void launch_depth_prior(hipStream_t s, const KParams& p, const MapDev& m, const dpr::Args& a, int* cnt, int* outcome);
 
+// k_stereo_prior on stream s (rebvio_hip_map_fuse_stereo*): one Kalman update of (rho, sigma_rho) per keyline of m from the epipolar
+// search in the mask of the right map r (stereo_prior.hpp; r is only read, r_kmax = the capacity of its arrays). cnt = 8 ints,
+// cleared by the caller in front of the launch (the kernel leaves rebvio_hip_stereo_prior_counts there); outcome, winner = kmax ints
+// each. ceil(kmax / 16) workgroups whatever the maps hold.
+namespace spr {
+struct Args;
+}
+void launch_stereo_prior(hipStream_t s, const KParams& p, const MapDev& m, const MapDev& r, int r_kmax, const spr::Args& a, int* cnt,
+                         int* outcome, int* winner);
+
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
 // ---- several camera streams ("lanes") of one GPU advanced in lock-step by batched launches (rebvio_hip_batch_*) --------

@@ -13,6 +13,7 @@
 #include "edge_chains.hpp"
 #include "glue_dev.hpp"
 #include "kf_cloud.hpp"
+#include "stereo_prior.hpp"
 #include "kf_handover.hpp"
 #include "kf_pose.hpp"
 
@@ -4148,6 +4149,97 @@ __global__ __launch_bounds__(256) void k_depth_prior(KParams p, MapDev m, dpr::A
 
 void launch_depth_prior(hipStream_t s, const KParams& p, const MapDev& m, const dpr::Args& a, int* cnt, int* outcome) {
   RH_LAUNCH(k_depth_prior, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, p, m, a, cnt, outcome);
+}
+
+// ---- depth prior from a rectified stereo partner's edge map (rebvio_hip_map_fuse_stereo*) ---------------------------------------------
+// stereo_prior.hpp holds the definition's statements. A sub-group of kSprLanes lanes serves one left keyline (256 / kSprLanes
+// keylines per workgroup, the sizes of both maps read on the device): every lane loads the keyline and runs spr::left_setup, the
+// lanes then take consecutive columns of the window's rows in the right map's mask - one coalesced read per row and step - and a
+// lane that meets a keyline gathers its pos, gradient and gradient_norm and folds it (spr::fold_candidate). The folds meet in a
+// butterfly of __shfl_xor inside the sub-group: an OR, a minimum, a maximum and the smallest (score, j), none of which depends on
+// the order - every lane ends with the same fold, and lane 0 decides, updates and stores. A mask word outside [0, right size) is
+// no keyline. The six counts (usable, seen, fused, gated, ambiguous, clamped) are ballots per wave over the sub-groups' lanes 0,
+// which kf_add_counts adds to cnt[1..6]. Slots behind the size get outcome 0, winner -1.
+#ifndef RH_SPR_LANES
+#define RH_SPR_LANES 16
+#endif
+constexpr int kSprLanes = RH_SPR_LANES;
+static_assert(kSprLanes == 4 || kSprLanes == 8 || kSprLanes == 16 || kSprLanes == 32 || kSprLanes == 64, "a power of two inside a wave");
+__global__ __launch_bounds__(256) void k_stereo_prior(KParams p, MapDev m, MapDev r, int r_kmax, spr::Args a, int* __restrict__ cnt,
+                                                      int* __restrict__ outcome, int* __restrict__ winner) {
+  __shared__ int sh_cnt[4][6];
+  const int tid = threadIdx.x;
+  const int sub = tid & (kSprLanes - 1);
+  const int n = min(max(m.st->n, 0), p.kmax);
+  const int nr = min(max(r.st->n, 0), r_kmax);
+  const int i = blockIdx.x * (256 / kSprLanes) + tid / kSprLanes;
+  int pre = spr::kNone;
+  spr::Left L;
+  L.x0 = 0;
+  L.x1 = -1;
+  L.yi = 0;
+  if (i < n) {
+    const float2 pos = m.pos[i], g = m.grad[i], rs = m.rs[i];
+    pre = spr::left_setup(a, pos.x, pos.y, g.x, g.y, m.gnorm[i], rs.x, rs.y, &L);
+  }
+  spr::Fold f;
+  spr::fold_clear(&f);
+  if (pre < 0) {
+    const int nrow = a.row_tol ? 3 : 1;
+    for (int k = 0; k < nrow; ++k) {
+      const int y = L.yi + (k == 0 ? 0 : (k == 1 ? -1 : 1));
+      if (y < 0 || y >= a.rows) continue;
+      const int* __restrict__ row = r.mask + (size_t)y * a.cols;
+      for (int x = L.x0 + sub; x <= L.x1; x += kSprLanes) {
+        const int j = row[x];
+        if (j < 0 || j >= nr) continue;
+        const float2 q = r.pos[j], h = r.grad[j];
+        spr::fold_candidate(a, L, j, q.x, q.y, h.x, h.y, r.gnorm[j], &f);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = kSprLanes / 2; o > 0; o >>= 1) {
+    spr::Fold t;
+    t.seen = __shfl_xor(f.seen, o, kSprLanes);
+    t.d_lo = __shfl_xor(f.d_lo, o, kSprLanes);
+    t.d_hi = __shfl_xor(f.d_hi, o, kSprLanes);
+    t.score = __shfl_xor(f.score, o, kSprLanes);
+    t.d_win = __shfl_xor(f.d_win, o, kSprLanes);
+    t.j = __shfl_xor(f.j, o, kSprLanes);
+    spr::fold_join(&f, t);
+  }
+  int oc = pre, win = -1;
+  const bool lead = sub == 0 && i < n;
+  if (pre < 0) {
+    oc = spr::decide(a, f);
+    if (oc < 0) {
+      float rho_n = 0.f, sig_n = 0.f;
+      oc = spr::update(a, L, f.d_win, &rho_n, &sig_n);
+      if ((oc & 7) == spr::kFused) {
+        win = f.j;
+        if (lead) m.rs[i] = make_float2(rho_n, sig_n);
+      }
+    }
+  }
+  if (sub == 0 && i < p.kmax) {
+    outcome[i] = oc;
+    winner[i] = win;
+  }
+  int nc[6];
+  nc[0] = __popcll(__ballot(lead && oc != spr::kUnusable));
+  nc[1] = __popcll(__ballot(lead && (f.seen & 1) != 0));
+  nc[2] = __popcll(__ballot(lead && (oc & 7) == spr::kFused));
+  nc[3] = __popcll(__ballot(lead && (oc & 7) == spr::kGated));
+  nc[4] = __popcll(__ballot(lead && (oc & 7) == spr::kAmbiguous));
+  nc[5] = __popcll(__ballot(lead && (oc & spr::kClampedBit) != 0));
+  kf_add_counts(nc, sh_cnt, cnt + 1);
+  if (blockIdx.x == 0 && tid == 0) cnt[0] = n;
+}
+
+void launch_stereo_prior(hipStream_t s, const KParams& p, const MapDev& m, const MapDev& r, int r_kmax, const spr::Args& a, int* cnt,
+                         int* outcome, int* winner) {
+  RH_LAUNCH(k_stereo_prior, dim3(div_up(p.kmax, 256 / kSprLanes)), dim3(256), 0, s, p, m, r, r_kmax, a, cnt, outcome, winner);
 }
 
 }  // namespace rh

@@ -167,6 +167,27 @@ rebvio::types::DepthPriorCounts EdgeMap::fuseDepthImage(const rebvio::types::Dep
   return counts;
 }
 
+rebvio::types::StereoPriorCounts EdgeMap::fuseStereo(const EdgeMap& right, const rebvio::types::StereoPriorOpts& opts, std::vector<int>* outcome,
+                                                     std::vector<int>* winner) {
+  static_assert(sizeof(types::StereoPriorOpts) == sizeof(rebvio_hip_stereo_prior_opts) &&
+                    offsetof(types::StereoPriorOpts, row_tol) == offsetof(rebvio_hip_stereo_prior_opts, row_tol) &&
+                    offsetof(types::StereoPriorOpts, sigma_px) == offsetof(rebvio_hip_stereo_prior_opts, sigma_px) &&
+                    offsetof(types::StereoPriorOpts, q_abs) == offsetof(rebvio_hip_stereo_prior_opts, q_abs) &&
+                    offsetof(types::StereoPriorOpts, reserved) == offsetof(rebvio_hip_stereo_prior_opts, reserved) &&
+                    sizeof(types::StereoPriorCounts) == sizeof(rebvio_hip_stereo_prior_counts) &&
+                    offsetof(types::StereoPriorCounts, clamped) == offsetof(rebvio_hip_stereo_prior_counts, clamped),
+                "stereo-prior types mirror the C-ABI's");
+  if (outcome) outcome->assign((size_t)size(), 0);
+  if (winner) winner->assign((size_t)size(), -1);
+  types::StereoPriorCounts counts;
+  check("rebvio_hip_map_fuse_stereo",
+        rebvio_hip_map_fuse_stereo(handle_, right.handle_, reinterpret_cast<const rebvio_hip_stereo_prior_opts*>(&opts),
+                                   reinterpret_cast<rebvio_hip_stereo_prior_counts*>(&counts), outcome && !outcome->empty() ? outcome->data() : nullptr,
+                                   winner && !winner->empty() ? winner->data() : nullptr));
+  invalidateMirror();
+  return counts;
+}
+
 EdgeMap::EdgeChains EdgeMap::edgeChains() {
   static_assert(sizeof(types::ChainRef) == sizeof(rebvio_hip_chain_ref) && offsetof(types::ChainRef, flags) == offsetof(rebvio_hip_chain_ref, flags),
                 "chain records mirror the C-ABI's");

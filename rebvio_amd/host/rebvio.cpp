@@ -101,6 +101,43 @@ void Rebvio::registerDepthPriorCallback(std::function<void(uint64_t ts_us, const
   depth_prior_callbacks_.push_back(cb);
 }
 
+void Rebvio::setStereo(const rebvio::types::StereoPriorOpts& opts) {
+  std::lock_guard<std::mutex> guard(stereo_mutex_);
+  stereo_opts_ = opts;
+  if (!right_detector_) {
+    backend::Session::newScope(config_.device_id);  // a context of its own: the right camera's threshold servo is not the left one's
+    right_detector_ = std::make_unique<rebvio::EdgeDetector>(std::make_shared<rebvio::Camera>(camera_),
+                                                             std::make_shared<rebvio::EdgeDetectorConfig>(config_.edge_detector));
+  }
+}
+
+void Rebvio::rightImageCallback(rebvio::types::Image&& image) {
+  if (image.data.rows != (int)camera_.rows_ || image.data.cols != (int)camera_.cols_)
+    backend::fail("Rebvio::rightImageCallback: the image must have the camera's size", -3);
+  rebvio::types::Image q;
+  q.ts_us = image.ts_us;
+  const int t = image.data.type();
+  if (t != CV_8UC1 && t != CV_8UC3 && t != CV_8UC4) {
+    cv::Mat img;
+    image.data.convertTo(img, CV_FLOAT_PRECISION, 3.0);
+    q.data = camera_.undistort(img);
+  } else {
+    q.data = image.data.clone();  // (the caller's buffer may be reused before the frame's pair comes up)
+  }
+  std::lock_guard<std::mutex> guard(stereo_mutex_);
+  if (!right_detector_) backend::fail("Rebvio::rightImageCallback: call setStereo first", -3);
+  if (right_queue_.size() >= 8) {
+    right_queue_.pop_front();
+    ++right_dropped_;
+  }
+  right_queue_.push_back(std::move(q));
+  ++right_seen_;
+}
+
+void Rebvio::registerStereoPriorCallback(std::function<void(uint64_t ts_us, const rebvio::types::StereoPriorCounts&)> cb) {
+  stereo_prior_callbacks_.push_back(cb);
+}
+
 void Rebvio::imageCallback(rebvio::types::Image&& image) {
   std::lock_guard<std::mutex> guard(image_buffer_mutex_);
   const int t = image.data.type();
@@ -404,7 +441,36 @@ void Rebvio::stateEstimationProcess() {
     // depth images: a fusion into the new map was queued behind the second half; its counts (fetched where the pair's counters are)
     bool have_depth = false;
     types::DepthPriorCounts depth_counts;
+    // the stereo partner: the same for the fusion of the right frame's edge map
+    bool have_stereo = false;
+    types::StereoPriorCounts stereo_counts;
   } pending;
+  // the stereo partner. take_right: the queued right image with exactly this stamp (older ones are dropped and counted); nothing is
+  // touched while no right image has ever been handed in. queue_stereo: the image through the right detector, then the fusion on
+  // the track stream in call order. The right map used two fusions ago is free, as the depth images' staging frames are.
+  auto take_right = [&](uint64_t ts_us, types::Image* out, types::StereoPriorOpts* opts) -> bool {
+    if (right_seen_.load() == 0) return false;
+    std::lock_guard<std::mutex> guard(stereo_mutex_);
+    while (!right_queue_.empty() && right_queue_.front().ts_us < ts_us) {
+      right_queue_.pop_front();
+      ++right_dropped_;
+    }
+    if (right_queue_.empty() || right_queue_.front().ts_us != ts_us) return false;
+    *out = std::move(right_queue_.front());
+    right_queue_.pop_front();
+    *opts = stereo_opts_;
+    return true;
+  };
+  auto queue_stereo = [&](rebvio::EdgeMap& map, types::Image& right, const types::StereoPriorOpts& opts) {
+    rebvio::EdgeMap::SharedPtr& hold = right_hold_[right_hold_turn_++ & 1u];
+    hold = right_detector_->detect(right);
+    backend::check("rebvio_hip_map_fuse_stereo_async",
+                   rebvio_hip_map_fuse_stereo_async(ctx, map.handle(), hold->handle(), reinterpret_cast<const rebvio_hip_stereo_prior_opts*>(&opts)));
+    map.invalidateMirror();
+  };
+  bool have_first_stereo = false;
+  uint64_t first_stereo_ts = 0;
+  types::StereoPriorCounts first_stereo_counts;
   // depth images. take_depth: the queued image with exactly this stamp (older ones are dropped and counted); nothing is touched
   // while no image has ever been handed in. queue_depth: the image into one of the two device staging frames, then the fusion on
   // the track stream in call order. The frame used two fusions ago is free: a pair's first half, which the thread has waited for
@@ -464,6 +530,12 @@ void Rebvio::stateEstimationProcess() {
     }
     if (pending.have_depth)
       for (auto& cb : depth_prior_callbacks_) cb(pending.odometry.ts_us, pending.depth_counts);
+    if (have_first_stereo) {
+      have_first_stereo = false;
+      for (auto& cb : stereo_prior_callbacks_) cb(first_stereo_ts, first_stereo_counts);
+    }
+    if (pending.have_stereo)
+      for (auto& cb : stereo_prior_callbacks_) cb(pending.odometry.ts_us, pending.stereo_counts);
     if (!keyframe_callbacks_.empty()) {
       const int keylines = pending.new_map->size();
       for (auto& cb : keyframe_callbacks_) cb(pending.odometry.ts_us, pending.kf_matches, keylines);
@@ -518,6 +590,9 @@ void Rebvio::stateEstimationProcess() {
     if (pending.have_depth)  // queued right behind that second half, and nothing of the kind since
       backend::check("rebvio_hip_depth_prior_last_counts",
                      rebvio_hip_depth_prior_last_counts(ctx, reinterpret_cast<rebvio_hip_depth_prior_counts*>(&pending.depth_counts)));
+    if (pending.have_stereo)
+      backend::check("rebvio_hip_stereo_prior_last_counts",
+                     rebvio_hip_stereo_prior_last_counts(ctx, reinterpret_cast<rebvio_hip_stereo_prior_counts*>(&pending.stereo_counts)));
     for (rebvio_hip_cloud* cl : pending.clouds) {  // queued right behind that second half
       int n = 0;
       backend::check("rebvio_hip_cloud_wait", rebvio_hip_cloud_wait(cl, nullptr, &n, nullptr));
@@ -598,6 +673,8 @@ void Rebvio::stateEstimationProcess() {
     // depth images: the stream's first map has been no pair's new map - its image goes in right behind its detection
     QueuedDepth depth_image;
     types::DepthPriorOpts depth_opts;
+    types::Image right_image;
+    types::StereoPriorOpts stereo_opts;
     if (first_pair) {
       first_pair = false;
       if (take_depth(old_edge_map->ts_us(), &depth_image, &depth_opts)) {
@@ -606,6 +683,13 @@ void Rebvio::stateEstimationProcess() {
                        rebvio_hip_depth_prior_last_counts(ctx, reinterpret_cast<rebvio_hip_depth_prior_counts*>(&first_depth_counts)));
         first_depth_ts = old_edge_map->ts_us();
         have_first_depth = true;
+      }
+      if (take_right(old_edge_map->ts_us(), &right_image, &stereo_opts)) {  // (behind the depth image, where there is one)
+        queue_stereo(*old_edge_map, right_image, stereo_opts);
+        backend::check("rebvio_hip_stereo_prior_last_counts",
+                       rebvio_hip_stereo_prior_last_counts(ctx, reinterpret_cast<rebvio_hip_stereo_prior_counts*>(&first_stereo_counts)));
+        first_stereo_ts = old_edge_map->ts_us();
+        have_first_stereo = true;
       }
     }
 
@@ -729,6 +813,7 @@ void Rebvio::stateEstimationProcess() {
     // Nor with a keyframe-pose or keyframe-cloud callback: snapshot and pose take the new map in this pair's frame as well.
     // Nor while a depth image waits for the new map: it is folded into the map's depths in THIS pair's frame.
     const bool have_depth = take_depth(new_edge_map->ts_us(), &depth_image, &depth_opts);
+    const bool have_stereo = take_right(new_edge_map->ts_us(), &right_image, &stereo_opts);  // (the same holds for a right image)
     float Rnext[9];
     bool have_next = false;
     rebvio::EdgeMap::SharedPtr next_map;
@@ -736,7 +821,7 @@ void Rebvio::stateEstimationProcess() {
       std::lock_guard<std::mutex> guard(edge_map_buffer_mutex_);
       if (edge_map_buffer_.size() >= 2) {
         next_map = edge_map_buffer_[1];
-        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud && !want_polylines && !have_depth) {
+        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud && !want_polylines && !have_depth && !have_stereo) {
           store3(next_map->imu().R(), Rnext);
           have_next = true;
         }
@@ -750,6 +835,7 @@ void Rebvio::stateEstimationProcess() {
     // the depth image of the new map's frame, right behind the second half (which has written the map's depths for the last time
     // as a new map) and in front of everything that reads them: clouds, keyframe snapshots, polylines, the next pair
     if (have_depth) queue_depth(*new_edge_map, depth_image, depth_opts);
+    if (have_stereo) queue_stereo(*new_edge_map, right_image, stereo_opts);  // the depth image first
     if (want_cloud) {
       store3(R_global, cloud_pose.R);
       for (int i = 0; i < 3; ++i) cloud_pose.t[i] = Pos[i];
@@ -905,6 +991,7 @@ void Rebvio::stateEstimationProcess() {
     pending.polylines = std::move(polylines);
     pending.polyline_pose = polyline_pose;
     pending.have_depth = have_depth;
+    pending.have_stereo = have_stereo;
     timers.lap(3);
     timers.end_pair();
     timers.n++;

@@ -35,6 +35,12 @@
 // stream, whatever --first is), raw little-endian uint16 counts of U metres (default 0.001; 0 = no depth), W x H each, dense. Every
 // frame's image is handed to Rebvio::depthImageCallback in front of the frame itself; the reader then stays at most seven frames
 // ahead of the tracker, so that none of the eight queued images is pushed out. The summary on stderr counts the images, the fused frames and keylines.
+// --right FILE|DIR --baseline B: the right camera of a rectified stereo pair through the same readers as the left stream - with --raw a
+// raw file of W x H frames, with --asl a mav0 folder whose cam1 is read - frame i belonging to left frame i and taking its stamp; B
+// metres from the left camera to the right one along the left camera's x axis. The right frames are assumed rectified to the left
+// ones. Every right frame is handed to Rebvio::rightImageCallback in front of its left frame (Rebvio::setStereo with the default
+// options and B), the reader staying at most seven frames ahead of the tracker. The summary on stderr counts the images, the fused
+// frames and keylines.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -50,8 +56,8 @@
 
 int main(int argc, char** argv) {
   std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix, kf_window_path, kf_handover_path;
-  std::string polylines_prefix, depth_path;
-  double depth_unit = 0.001;
+  std::string polylines_prefix, depth_path, right_path;
+  double depth_unit = 0.001, baseline = 0.0;
   int min_chain = 8;
   int kf_window = 0;
   bool kf_align = false;
@@ -64,7 +70,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--depth FILE [--depth-unit U]] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
+                 "[--mask mask.png] [--depth FILE [--depth-unit U]] [--right FILE|DIR --baseline B] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -92,6 +98,8 @@ int main(int argc, char** argv) {
     }
     else if (a == "--depth") depth_path = next();
     else if (a == "--depth-unit") depth_unit = std::atof(next());
+    else if (a == "--right") right_path = next();
+    else if (a == "--baseline") baseline = std::atof(next());
     else if (a == "--cloud") cloud_prefix = next();
     else if (a == "--cloud-dry") cloud_dry = true;
     else if (a == "--polylines") {
@@ -131,6 +139,7 @@ int main(int argc, char** argv) {
     }
   }
   if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1 || min_chain < 1 || !(depth_unit > 0.0)) return usage();
+  if (right_path.empty() != !(baseline > 0.0)) return usage();  // --right and --baseline come together
   if (!kf_window_path.empty() && (!kf_align || kf_pose_path.empty() || kf_window < 1 || kf_window > 15)) return usage();  // needs --kf-align FILE
   if (!kf_handover_path.empty() && (!kf_align || kf_pose_path.empty())) return usage();  // needs --kf-align FILE
   if (!kf_fuse_path.empty()) {  // the fusion runs behind the alignment only
@@ -285,9 +294,36 @@ int main(int argc, char** argv) {
         n_depth_fused += (size_t)c.fused;
       });
     }
+    std::unique_ptr<rebvio::io::StreamSource> right_src;
+    size_t n_right = 0, n_right_fused = 0, n_right_handed = 0;
+    if (!right_path.empty()) {
+      if (!asl.empty()) right_src.reset(new rebvio::io::EurocReader(right_path, "cam1", "imu0", colour));
+      else right_src.reset(new rebvio::io::RawReader(right_path, H, W, 0, dt, ""));
+      if (right_src->numFrames() == 0) {
+        std::fprintf(stderr, "error: cannot read %s\n", right_path.c_str());
+        return 1;
+      }
+      rebvio::types::StereoPriorOpts so;
+      so.baseline = baseline;
+      rebvio.setStereo(so);
+      rebvio.registerStereoPriorCallback([&](uint64_t, const rebvio::types::StereoPriorCounts& c) {
+        ++n_right;
+        n_right_fused += (size_t)c.fused;
+      });
+    }
+    size_t frame_index = first;
     const size_t n = rebvio::io::replay(
         *src,
         [&](rebvio::types::Image&& im) {
+          if (right_src && frame_index < right_src->numFrames()) {
+            while (n_right_handed >= (size_t)rebvio.framesProcessed() + 7 && rebvio.running()) std::this_thread::sleep_for(std::chrono::microseconds(100));
+            rebvio::types::Image r;
+            r.ts_us = im.ts_us;
+            r.data = right_src->frame(frame_index);
+            rebvio.rightImageCallback(std::move(r));
+            ++n_right_handed;
+          }
+          ++frame_index;
           if (depth_file && std::fread(depth_frame.data(), 2, depth_frame.size(), depth_file) == depth_frame.size()) {
             while (n_depth_handed >= (size_t)rebvio.framesProcessed() + 7 && rebvio.running()) std::this_thread::sleep_for(std::chrono::microseconds(100));
             rebvio::types::DepthImage d;
@@ -310,6 +346,9 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "depth_images=%zu depth_fused_frames=%zu depth_fused_keylines=%zu depth_dropped=%u\n", n_depth_handed, n_depth, n_depth_fused,
                    rebvio.depthImagesDropped());
     }
+    if (right_src)
+      std::fprintf(stderr, "right_images=%zu stereo_fused_frames=%zu stereo_fused_keylines=%zu right_dropped=%u\n", n_right_handed, n_right, n_right_fused,
+                   rebvio.rightImagesDropped());
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
     if (!kf_cloud_prefix.empty()) std::fprintf(stderr, "kf_clouds=%zu kf_points=%zu\n", n_kf_clouds, n_kf_points);
     if (!polylines_prefix.empty()) std::fprintf(stderr, "polyline_files=%zu lines=%zu line_points=%zu\n", n_polyline_files, n_lines, n_line_points);

@@ -149,9 +149,13 @@ def pose(scene: Scene, t: float):
     return R, p
 
 
-def render_frame(scene: Scene, cam: Camera, t: float, noise_seed: int | None = None, noise_sigma: float = 2.0) -> np.ndarray:
-    """Render frame t as u8 [height, width]."""
+def render_frame(scene: Scene, cam: Camera, t: float, noise_seed: int | None = None, noise_sigma: float = 2.0,
+                 cam_offset=None) -> np.ndarray:
+    """Render frame t as u8 [height, width]. cam_offset: the camera sits at R(t) @ cam_offset from the pose's position, with the
+    pose's rotation (a stereo partner); None: at the pose."""
     R, p = pose(scene, t)
+    if cam_offset is not None:
+        p = p + R @ np.asarray(cam_offset, np.float64)
     X, Y = cam.undistorted_rays()
     dx = R[0, 0] * X + R[0, 1] * Y + R[0, 2]
     dy = R[1, 0] * X + R[1, 1] * Y + R[1, 2]
@@ -193,6 +197,24 @@ def render_stream(width: int, height: int, n_frames: int, stream_id: int = 0, de
     for t in range(n_frames):
         frames[t] = render_frame(scene, cam, float(t), noise_seed=(stream_id * 100003 + t) if noise else None)
     return frames, cam
+
+
+RIGHT_NOISE_SEED = 7000003  # added to a left frame's noise seed for its right partner
+
+
+def render_stereo_stream(width: int, height: int, n_frames: int, baseline: float, stream_id: int = 0, density: float = 1.0,
+                         noise: bool = True):
+    """A rectified stereo pair of streams -> (left u8 [n, H, W], right u8 [n, H, W], Camera). The left frames are render_stream's
+    for the same arguments, byte for byte; the right camera has the left one's rotation and intrinsics and sits at
+    R(t) @ (baseline, 0, 0) from it, so a point at depth z has disparity x_left - x_right = fm * baseline / z. The right frames
+    carry noise of their own seed."""
+    left, cam = render_stream(width, height, n_frames, stream_id, density, noise)
+    scene = make_scene(stream_id, density)
+    right = np.empty_like(left)
+    for t in range(n_frames):
+        right[t] = render_frame(scene, cam, float(t), noise_seed=(stream_id * 100003 + t + RIGHT_NOISE_SEED) if noise else None,
+                                cam_offset=(float(baseline), 0.0, 0.0))
+    return left, right, cam
 
 
 def render_depth(scene: Scene, cam: Camera, t: float) -> np.ndarray:
