@@ -13,11 +13,13 @@
 #include "rebvio/types/keyline.hpp"
 #include "rebvio/types/depth_image.hpp"
 #include "rebvio/types/point_cloud.hpp"
+#include "rebvio/types/place.hpp"
 #include "rebvio/types/stereo_prior.hpp"
 
 struct rebvio_hip_map;
 struct rebvio_hip_ctx;
 struct rebvio_hip_kf_snapshot;
+struct rebvio_hip_place_db;
 
 namespace rebvio {
 
@@ -72,6 +74,51 @@ class KeyframeSnapshot {
  private:
   std::shared_ptr<void> keepalive_;  // the backend context the handle belongs to (as EdgeMap's)
   rebvio_hip_kf_snapshot* handle_ = nullptr;
+};
+
+// A device-resident database of place signatures (EdgeMap::placeDb; rebvio_hip.h "Place recognition"): add() the maps keyframes are
+// marked on, query() with a later map - the entries whose edges look like it, nearest first, are the keyframes to hand to
+// EdgeMap::keyframeAlignMany. Owns the backend's handle and releases it; the device memory goes with its context at the latest.
+// Move-only. Every call runs on the context's track stream, from the tracking thread; the maps are of the database's context.
+class PlaceDb {
+ public:
+  PlaceDb() = default;
+  PlaceDb(rebvio_hip_place_db* handle, int capacity, std::shared_ptr<void> keepalive)
+      : keepalive_(std::move(keepalive)), handle_(handle), capacity_(capacity) {}
+  ~PlaceDb() { reset(); }
+  PlaceDb(PlaceDb&& o) noexcept : keepalive_(std::move(o.keepalive_)), handle_(o.handle_), capacity_(o.capacity_) { o.handle_ = nullptr; }
+  PlaceDb& operator=(PlaceDb&& o) noexcept {
+    if (this != &o) {
+      reset();
+      keepalive_ = std::move(o.keepalive_);
+      handle_ = o.handle_;
+      capacity_ = o.capacity_;
+      o.handle_ = nullptr;
+    }
+    return *this;
+  }
+  PlaceDb(const PlaceDb&) = delete;
+  PlaceDb& operator=(const PlaceDb&) = delete;
+  void reset();
+  int size() const;
+  int capacity() const { return capacity_; }
+  void clear();
+  // the signature of `map` as the next entry (queued, no host wait) -> its index, or -1 when the database is full
+  int add(const rebvio::EdgeMap& map, uint64_t tag);
+  // a saved entry back in (synchronous) -> its index, or -1 when the database is full
+  int addSignature(const rebvio::types::PlaceSignature& signature, int counted, uint64_t tag);
+  // one entry (synchronous; after a queued add it waits for it). counted, tag: null, or where they go
+  rebvio::types::PlaceSignature entry(int index, int* counted = nullptr, uint64_t* tag = nullptr) const;
+  // the k <= 16 entries nearest to the map's signature among all but the last exclude_last, ascending (distance, index); synchronous
+  std::vector<rebvio::types::PlaceMatch> query(const rebvio::EdgeMap& map, int k, int exclude_last = 0) const;
+  std::vector<rebvio::types::PlaceMatch> querySignature(const rebvio::types::PlaceSignature& signature, int k, int exclude_last = 0) const;
+  explicit operator bool() const { return handle_ != nullptr; }
+  rebvio_hip_place_db* handle() const { return handle_; }
+
+ private:
+  std::shared_ptr<void> keepalive_;  // the backend context the handle belongs to (as EdgeMap's)
+  rebvio_hip_place_db* handle_ = nullptr;
+  int capacity_ = 0;
 };
 
 // the best of keyframeAlignMany's results (rebvio_hip_kf_align_best): status 0 and inliers >= min_inliers; the most inliers, then the
@@ -179,6 +226,13 @@ class EdgeMap {
   // keyframeAlign on the winner (keyframeAlignBest) for them.
   std::vector<rebvio::types::KfHypResult> keyframeAlignMany(const std::vector<rebvio::types::KfHypothesis>& hypotheses,
                                                             const rebvio::types::KfAlignOpts& opts = rebvio::types::KfAlignOpts());
+
+  // addition: place recognition (rebvio_hip.h "Place recognition"). placeSignature: 384 words, 8 x 6 image cells x 8 orientation
+  // bins over the keylines this map holds now, normalised to 65535 (synchronous, from the tracking thread; take it where the map is
+  // marked, as the snapshot: a map promised to the next pair's rotation is refused). counted: the keylines that entered it.
+  // placeDb(capacity): a database of 1..65536 such signatures on this map's context.
+  rebvio::types::PlaceSignature placeSignature(int* counted = nullptr) const;
+  rebvio::PlaceDb placeDb(int capacity) const;
 
   // --- backend plumbing (not part of the reference surface) ---
   // `keepalive` owns the backend context the handle belongs to (backend::Session): a map kept by an edge-image consumer

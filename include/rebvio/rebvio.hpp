@@ -21,6 +21,7 @@
 #include "rebvio/types/image.hpp"
 #include "rebvio/types/imu.hpp"
 #include "rebvio/types/odometry.hpp"
+#include "rebvio/types/place.hpp"
 #include "rebvio/types/stereo_prior.hpp"
 #include "rebvio/types/point_cloud.hpp"
 
@@ -118,6 +119,22 @@ class Rebvio {
   // does not change by a digit either way. setKeyframeWindow is callable from any thread; register before the first frame is handed in.
   void setKeyframeWindow(int n) { keyframe_window_ = n < 0 ? 0 : (n > 15 ? 15 : n); }
   void registerKeyframeWindowCallback(std::function<void(uint64_t ts_us, const std::vector<rebvio::types::KfWindowPose>&)> cb);
+  // addition: place recognition (rebvio/types/place.hpp, rebvio_hip.h "Place recognition"): notice that the camera has been here
+  // before. Off at capacity 0, the default. On, the state-estimation thread keeps a PlaceDb of `capacity` (1..65536) signatures: at
+  // every requestKeyframe mark, right behind the snapshot, it queries the database with the marked map (EdgeMap::placeSignature's
+  // 384 words against every entry but the last exclude_last, the top_k <= 16 nearest) and then adds the map with tag = the
+  // keyframe's stamp. A full database stops adding and counts the misses (placeMisses). The place callback gets the record's stamp
+  // and the matches with distance <= max_distance, nearest first - possibly none - once per mark, on the state-estimation thread,
+  // after the other keyframe callbacks of the record. The matches are candidates, not poses: their tags say which keyframes to
+  // hand to EdgeMap::keyframeAlignMany. max_distance = 32768 is a choice, a quarter of the largest distance two normalised
+  // signatures can have, not a measurement on real footage (INTEGRATION.md "Places"). A marked map is not handed to the next
+  // pair's rotation early (as with a keyframe-pose callback); on or off the odometry does not change by a digit, and off the
+  // thread runs exactly the calls it runs without this. Call both before the first frame is handed in.
+  void setPlaceRecognition(int capacity, int top_k = 4, int exclude_last = 10, uint32_t max_distance = 32768);
+  void registerPlaceCallback(std::function<void(uint64_t ts_us, const std::vector<rebvio::types::PlaceMatch>&)> cb);
+  unsigned int placeQueries() const { return place_queries_; }
+  unsigned int placeMatches() const { return place_matches_; }
+  unsigned int placeMisses() const { return place_misses_; }
   // addition: every keyframe's depth-bearing keylines as one point cloud, handed out as the keyframe is retired
   // (KeyframeSnapshot::pointCloud; rebvio_hip.h defines it). While such a callback is registered requestKeyframe snapshots the
   // keyframe behind its mark as a keyframe-pose callback makes it do, and remembers R_global, Pos, K of the odometry record of the map
@@ -208,6 +225,10 @@ class Rebvio {
   std::vector<EdgePolylineCallback> edge_polyline_callbacks_;
   std::vector<std::function<void(uint64_t, int, int)>> keyframe_callbacks_;
   std::vector<std::function<void(uint64_t, const rebvio::types::KfPose&)>> keyframe_pose_callbacks_;
+  std::vector<std::function<void(uint64_t, const std::vector<rebvio::types::PlaceMatch>&)>> place_callbacks_;
+  std::atomic<int> place_capacity_{0}, place_top_k_{4}, place_exclude_last_{10};
+  std::atomic<uint32_t> place_max_distance_{32768};
+  std::atomic<unsigned int> place_queries_{0}, place_matches_{0}, place_misses_{0};
   std::atomic<bool> keyframe_requested_{false};
   std::atomic<bool> keyframe_align_{false};
   std::vector<std::function<void(uint64_t, const rebvio::types::KfFuse&)>> keyframe_fuse_callbacks_;

@@ -45,7 +45,9 @@ extern "C" {
  *    _async), rebvio_hip_depth_prior_last_counts, their structs rebvio_hip_depth_prior_opts / rebvio_hip_depth_prior_counts and the
  *    test hook rebvio_hip_test_depth_prior_host; the stereo prior rebvio_hip_default_stereo_prior_opts, rebvio_hip_map_fuse_stereo(_async),
  *    rebvio_hip_stereo_prior_last_counts, their structs rebvio_hip_stereo_prior_opts / rebvio_hip_stereo_prior_counts and the test
- *    hooks rebvio_hip_test_stereo_prior_host / rebvio_hip_test_map_set_mask. */
+ *    hooks rebvio_hip_test_stereo_prior_host / rebvio_hip_test_map_set_mask; place recognition rebvio_hip_map_place_signature,
+ *    rebvio_hip_place_db_create / _release / _clear / _size / _add / _add_signature / _entry / _query / _query_signature, their
+ *    struct rebvio_hip_place_match and the test hooks rebvio_hip_test_place_signature_host / rebvio_hip_test_place_query_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -821,6 +823,83 @@ int rebvio_hip_test_stereo_prior_host(int rows, int cols, float fm, rebvio_hip_k
                                       const rebvio_hip_keyline* right, int nr, const int* right_mask,
                                       const rebvio_hip_stereo_prior_opts* opts, rebvio_hip_stereo_prior_counts* counts,
                                       int* outcome /*NULL or n ints*/, int* winner /*NULL or n ints*/);
+
+/* Place recognition: a fixed-size signature of a map's edges, and a device-resident database of such signatures that is searched in
+ * one pass - the retrieval step in front of rebvio_hip_map_keyframe_align_many, which has to be told which old keyframes to try.
+ * (The reference has nothing of the kind: it tracks frame to frame and never looks back.)
+ *
+ * Signature: REBVIO_HIP_PLACE_WORDS = 384 unsigned 16-bit words, 8 x 6 image cells x 8 orientation bins, from the keylines i < size
+ * of a map as the map holds them in stream order - pos, gradient, gradient_norm, the fields rebvio_hip_map_upload replaces and
+ * rebvio_hip_map_download returns. A keyline is COUNTED when all of these hold (positive tests: a NaN fails)
+ *   pos.x >= 0, pos.x < cols, pos.y >= 0, pos.y < rows;  gradient_norm > 0;  |gx| < inf, |gy| < inf;  |gx| > 0 or |gy| > 0
+ * and then, with xi = (int)pos.x, yi = (int)pos.y,
+ *   cell = ((yi * 6) / rows) * 8 + (xi * 8) / cols                      (integer division)
+ *   bin  = 4 * (gy < 0) + 2 * (gx < 0) + (|gy| > |gx|)                  (-0.0 < 0 is false; a tie |gy| == |gx| gives 0)
+ *   h[cell * 8 + bin] += 1
+ * With n the number of counted keylines sig[k] = (uint16)(((uint64)h[k] * 65535) / n); every word is 0 when n == 0. counted = n
+ * goes out next to the signature. There is no transcendental and no floating-point sum: only integer sums cross threads, so
+ * every word is the same on every run and equals a host restatement exactly.
+ * The gradients of a map that has served as a pair's OLD map are rotated in place; the signature is of what the map holds at that
+ * point. The intended place is where the keyframe mark and the snapshot are taken. A map promised to R_prior_next
+ * (rebvio_hip_track_pair_finish_async) is refused with -7, as its cloud and its snapshot are.
+ *
+ * Distance: d(a, b) = sum over the 384 words of |a[k] - b[k]|, a uint32; any u16 words are legal, so d <= 384 * 65535.
+ *
+ * Database: a rebvio_hip_place_db belongs to a context and holds `cap` signature rows of 768 bytes in device memory, cap in
+ * 1..65536 (one owned allocation, plus one for the distances, the counted words and the results; both count in
+ * rebvio_hip_test_live_resources and are freed with the handle or with the context, whichever goes first), and on the host its
+ * size and a uint64 tag per entry. The handle may outlive its context as a husk: every entry then answers -10 and
+ * rebvio_hip_place_db_release still deletes it.
+ *
+ * Query: among the eligible entries e < size - exclude_last the k with the smallest (distance, index), ascending, k in
+ * 1..REBVIO_HIP_PLACE_TOPK_MAX = 16; a tie goes to the lower index; *count = min(k, eligible). An empty eligible set gives
+ * *count = 0 and launches nothing.
+ *
+ * Launches, whatever the sizes: a signature is one clear, k_place_hist (one thread per keyline, workgroups of 256, the map's size
+ * read on the device, a 384-word LDS histogram per workgroup) and k_place_norm (one workgroup; writes the u16 words straight into
+ * the context's query row or into row `index` of the database); a query adds k_place_dist (one wave per row, the query row in
+ * registers), k_place_topk (one workgroup) and one copy of the count and k records. All on the context's track stream under the
+ * thread rule of rebvio_hip_map_keyframe_snapshot and rebvio_hip_map_keyframe_align. The first signature gives the context one more
+ * owned device allocation (the histogram, the query row and its counted word; kept until the context goes).
+ *   rebvio_hip_map_place_signature         synchronous.
+ *   rebvio_hip_place_db_create / _release  release once; safe after rebvio_hip_destroy.
+ *   rebvio_hip_place_db_clear / _size      size 0 again (the rows stay allocated) / the entries held (-3 as a negative: null handle).
+ *   rebvio_hip_place_db_add                queued, no host wait: the signature of `map` becomes row *index = the old size, with `tag`.
+ *                                          -7 when the database is full.
+ *   rebvio_hip_place_db_add_signature      synchronous upload of a row and its counted word: restores a saved database.
+ *   rebvio_hip_place_db_entry              synchronous: row `index`, its counted word and its tag (each output NULL ok). After a
+ *                                          queued _add this is the first place that learns that entry's counted; it waits for the stream.
+ *   rebvio_hip_place_db_query              the signature of `map` (as rebvio_hip_map_place_signature forms it) against the database.
+ *   rebvio_hip_place_db_query_signature    the same from 384 words of the caller's.
+ *   rebvio_hip_test_place_signature_host   test hook, touches no device: the signature of n keylines of a rows x cols image.
+ *   rebvio_hip_test_place_query_host       test hook, touches no device: the query over `size` rows of 384 words; tag 0 in every record.
+ * -3, checked before the device is touched: null arguments; a map of another context than the database's; k outside 1..16, cap
+ * outside 1..65536, index outside [0, size); a negative exclude_last or counted; the hooks: a negative size, rows or cols < 1.
+ * -10: the context is gone. */
+#define REBVIO_HIP_PLACE_WORDS 384
+#define REBVIO_HIP_PLACE_TOPK_MAX 16
+typedef struct rebvio_hip_place_match {
+  uint32_t distance;
+  int32_t index; /* the entry's row in the database */
+  uint64_t tag;  /* as given when the entry was added */
+} rebvio_hip_place_match;
+typedef struct rebvio_hip_place_db rebvio_hip_place_db;
+int rebvio_hip_map_place_signature(rebvio_hip_map* map, uint16_t* sig /*384*/, int* counted);
+int rebvio_hip_place_db_create(rebvio_hip_ctx* ctx, int cap, rebvio_hip_place_db** out);
+void rebvio_hip_place_db_release(rebvio_hip_place_db* db);
+int rebvio_hip_place_db_clear(rebvio_hip_place_db* db);
+int rebvio_hip_place_db_size(rebvio_hip_place_db* db);
+int rebvio_hip_place_db_add(rebvio_hip_place_db* db, rebvio_hip_map* map, uint64_t tag, int* index /*NULL ok*/);
+int rebvio_hip_place_db_add_signature(rebvio_hip_place_db* db, const uint16_t* sig /*384*/, int counted, uint64_t tag, int* index /*NULL ok*/);
+int rebvio_hip_place_db_entry(rebvio_hip_place_db* db, int index, uint16_t* sig /*384, NULL ok*/, int* counted /*NULL ok*/,
+                              uint64_t* tag /*NULL ok*/);
+int rebvio_hip_place_db_query(rebvio_hip_place_db* db, rebvio_hip_map* map, int k, int exclude_last, rebvio_hip_place_match* out /*k*/,
+                              int* count);
+int rebvio_hip_place_db_query_signature(rebvio_hip_place_db* db, const uint16_t* sig /*384*/, int k, int exclude_last,
+                                        rebvio_hip_place_match* out /*k*/, int* count);
+int rebvio_hip_test_place_signature_host(int rows, int cols, const rebvio_hip_keyline* keylines, int n, uint16_t* sig /*384*/, int* counted);
+int rebvio_hip_test_place_query_host(const uint16_t* rows384, int size, const uint16_t* sig /*384*/, int k, int exclude_last,
+                                     rebvio_hip_place_match* out /*k*/, int* count);
 
 /* Depth hand-over between keyframe snapshots: what the fusion above has made of a retiring keyframe's rho / sigma_rho is lost when
  * the next keyframe is marked - the successor's snapshot is cut from the tracker's map and starts with the tracker's raw depths.

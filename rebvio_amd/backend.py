@@ -147,6 +147,18 @@ class StereoPriorCounts(C.Structure):
         return (self.candidates, self.usable, self.seen, self.fused, self.gated, self.ambiguous, self.clamped, self.reserved)
 
 
+class PlaceMatch(C.Structure):
+    """rebvio_hip_place_match: one result record of a place query"""
+    _fields_ = [("distance", C.c_uint32), ("index", C.c_int32), ("tag", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.distance, self.index, self.tag)
+
+
+PLACE_WORDS = 384
+PLACE_TOPK_MAX = 16
+
+
 class KfHandoverOpts(C.Structure):
     """rebvio_hip_kf_handover_opts (KfSnapshot.handover_depth); defaults from default_kf_handover_opts"""
     _fields_ = [("kf_filter", CloudFilter), ("min_cos", C.c_double), ("gate_sigma", C.c_double), ("q_abs", C.c_double),
@@ -326,6 +338,18 @@ SIGNATURES = {
     "rebvio_hip_test_stereo_prior_host": (C.c_int, [C.c_int, C.c_int, C.c_float, _vp, C.c_int, _vp, C.c_int, _vp,
                                                     C.POINTER(StereoPriorOpts), C.POINTER(StereoPriorCounts), _ip, _ip]),
     "rebvio_hip_test_map_set_mask": (C.c_int, [_vp, _vp]),
+    "rebvio_hip_map_place_signature": (C.c_int, [_vp, _vp, _ip]),
+    "rebvio_hip_place_db_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    "rebvio_hip_place_db_release": (None, [_vp]),
+    "rebvio_hip_place_db_clear": (C.c_int, [_vp]),
+    "rebvio_hip_place_db_size": (C.c_int, [_vp]),
+    "rebvio_hip_place_db_add": (C.c_int, [_vp, _vp, C.c_uint64, _ip]),
+    "rebvio_hip_place_db_add_signature": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, _ip]),
+    "rebvio_hip_place_db_entry": (C.c_int, [_vp, C.c_int, _vp, _ip, C.POINTER(C.c_uint64)]),
+    "rebvio_hip_place_db_query": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(PlaceMatch), _ip]),
+    "rebvio_hip_place_db_query_signature": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(PlaceMatch), _ip]),
+    "rebvio_hip_test_place_signature_host": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, _vp, _ip]),
+    "rebvio_hip_test_place_query_host": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.POINTER(PlaceMatch), _ip]),
     "rebvio_hip_test_live_resources": (C.c_long, []),
     "rebvio_hip_test_handover_counters": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "rebvio_hip_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -783,6 +807,103 @@ def stereo_prior_host(rows, cols, fm, left, right, right_mask, opts):
     return out, kl, outcome, winner
 
 
+def _place_sig(sig):
+    sig = np.ascontiguousarray(sig, np.uint16).reshape(-1)
+    assert sig.size == PLACE_WORDS, sig.shape
+    return sig
+
+
+def _place_matches(out, count):
+    return [PlaceMatch(out[i].distance, out[i].index, out[i].tag) for i in range(count)]
+
+
+def place_signature_host(rows, cols, keylines):
+    """Map.place_signature on the host, from a KEYLINE_DTYPE array (rebvio_hip_test_place_signature_host). Touches no device.
+    Returns (sig uint16 [384], counted)."""
+    kl = np.ascontiguousarray(keylines, KEYLINE_DTYPE).reshape(-1)
+    sig = np.zeros(PLACE_WORDS, np.uint16)
+    n = C.c_int()
+    _chk(lib().rebvio_hip_test_place_signature_host(int(rows), int(cols), kl.ctypes.data if len(kl) else None, len(kl), sig.ctypes.data,
+                                                    C.byref(n)))
+    return sig, n.value
+
+
+def place_query_host(rows384, sig, k, exclude_last=0):
+    """PlaceDb.query_signature on the host (rebvio_hip_test_place_query_host): rows384 uint16 [size, 384]. Touches no device. Returns
+    the list of PlaceMatch (tag 0), nearest first."""
+    rows384 = np.ascontiguousarray(rows384, np.uint16).reshape(-1, PLACE_WORDS)
+    sig = _place_sig(sig)
+    out = (PlaceMatch * PLACE_TOPK_MAX)()
+    n = C.c_int()
+    _chk(lib().rebvio_hip_test_place_query_host(rows384.ctypes.data if len(rows384) else None, len(rows384), sig.ctypes.data, int(k),
+                                                int(exclude_last), out, C.byref(n)))
+    return _place_matches(out, n.value)
+
+
+class PlaceDb:
+    """A device-resident database of place signatures (rebvio_hip_place_db_create; include/rebvio_hip.h is the definition):
+    add() maps as keyframes are marked, query() with a later map, release() when done."""
+
+    def __init__(self, h, cap):
+        self.h, self.cap = h, cap
+
+    def add(self, map, tag=0) -> int:
+        """Queues the signature of `map` as the next row (rebvio_hip_place_db_add; no host wait). Returns its index."""
+        i = C.c_int()
+        _chk(lib().rebvio_hip_place_db_add(self.h, map.h if map is not None else None, int(tag), C.byref(i)))
+        return i.value
+
+    def add_signature(self, sig, counted=0, tag=0) -> int:
+        """Uploads 384 words of the caller's as the next row (rebvio_hip_place_db_add_signature; synchronous). Returns its index."""
+        sig = _place_sig(sig)
+        i = C.c_int()
+        _chk(lib().rebvio_hip_place_db_add_signature(self.h, sig.ctypes.data, int(counted), int(tag), C.byref(i)))
+        return i.value
+
+    def entry(self, index):
+        """(sig uint16 [384], counted, tag) of one row (rebvio_hip_place_db_entry; waits for the stream)"""
+        sig = np.zeros(PLACE_WORDS, np.uint16)
+        n, tag = C.c_int(), C.c_uint64()
+        _chk(lib().rebvio_hip_place_db_entry(self.h, int(index), sig.ctypes.data, C.byref(n), C.byref(tag)))
+        return sig, n.value, tag.value
+
+    def query(self, map, k=1, exclude_last=0):
+        """The k entries nearest to the signature of `map` among all but the last exclude_last, nearest first, as a list of
+        PlaceMatch (rebvio_hip_place_db_query)."""
+        out = (PlaceMatch * PLACE_TOPK_MAX)()
+        n = C.c_int()
+        _chk(lib().rebvio_hip_place_db_query(self.h, map.h if map is not None else None, int(k), int(exclude_last), out, C.byref(n)))
+        return _place_matches(out, n.value)
+
+    def query_signature(self, sig, k=1, exclude_last=0):
+        """The same from 384 words of the caller's (rebvio_hip_place_db_query_signature)"""
+        sig = _place_sig(sig)
+        out = (PlaceMatch * PLACE_TOPK_MAX)()
+        n = C.c_int()
+        _chk(lib().rebvio_hip_place_db_query_signature(self.h, sig.ctypes.data, int(k), int(exclude_last), out, C.byref(n)))
+        return _place_matches(out, n.value)
+
+    def clear(self):
+        _chk(lib().rebvio_hip_place_db_clear(self.h))
+
+    def size(self) -> int:
+        n = lib().rebvio_hip_place_db_size(self.h)
+        if n < 0:
+            raise HipError(lib().rebvio_hip_last_error().decode())
+        return n
+
+    def release(self):
+        if self.h:
+            lib().rebvio_hip_place_db_release(self.h)  # safe after the context is closed too
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 def default_kf_handover_opts(ctx=None, **over) -> KfHandoverOpts:
     """The library's defaults (rebvio_hip_default_kf_handover_opts): max_dist is ctx's search_range (40, the default one, without a
     context); kf_filter takes a CloudFilter or a dict of its fields to change."""
@@ -1185,6 +1306,14 @@ class Map:
                                               winner.ctypes.data_as(_ip) if want_outcome else None))
         return (out, outcome[:out.candidates], winner[:out.candidates]) if want_outcome else out
 
+    def place_signature(self):
+        """(sig uint16 [384], counted): this map's edge signature, 8 x 6 image cells x 8 orientation bins over the keylines it holds
+        now (rebvio_hip_map_place_signature; synchronous). Take it where the map is marked, as the snapshot."""
+        sig = np.zeros(PLACE_WORDS, np.uint16)
+        n = C.c_int()
+        _chk(lib().rebvio_hip_map_place_signature(self.h, sig.ctypes.data, C.byref(n)))
+        return sig, n.value
+
     def upload(self, kl: np.ndarray):
         kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)
         _chk(lib().rebvio_hip_map_upload(self.h, kl.ctypes.data if kl.size else None, len(kl)))
@@ -1339,6 +1468,12 @@ class Context:
         out = StereoPriorCounts()
         _chk(lib().rebvio_hip_stereo_prior_last_counts(self.h, C.byref(out)))
         return out
+
+    def place_db(self, cap: int) -> PlaceDb:
+        """A place database of `cap` rows (1..65536) on this context's device (rebvio_hip_place_db_create)"""
+        h = _vp()
+        _chk(lib().rebvio_hip_place_db_create(self.h, int(cap), C.byref(h)))
+        return PlaceDb(h, int(cap))
 
     def detect_u8_device(self, dev_addr: int, ts_us=0) -> Map:
         h = _vp()

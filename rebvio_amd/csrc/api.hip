@@ -31,6 +31,7 @@
 #include "kf_pose.hpp"
 #include "owned.hpp"
 #include "pixel_format.hpp"
+#include "place.hpp"
 #include "stereo_prior.hpp"
 
 using namespace rh;
@@ -303,6 +304,23 @@ struct rebvio_hip_kf_snapshot {
   std::mutex nor_mu;
   void* normals_buf = nullptr;
   void* normals = nullptr;
+};
+
+// A place database (rebvio_hip_place_db_create): `cap` signature rows of 768 bytes in one device buffer, and a second one with the
+// cap distance words of a query, the cap counted words of the entries and the result block (a 16-byte head with the count, 16
+// records). Size and tags live on the host. Listed in its context, which frees the buffers when it is destroyed; like a snapshot
+// it may outlive the context as a husk.
+struct rebvio_hip_place_db {
+  rebvio_hip_ctx* ctx = nullptr;
+  std::shared_ptr<LifeBlock> life;
+  Owned own;                   // the two buffers
+  uint16_t* rows = nullptr;
+  unsigned* dist = nullptr;    // views into the second buffer
+  int* counted = nullptr;
+  char* res = nullptr;
+  int cap = 0;
+  int size = 0;
+  std::vector<uint64_t> tags;
 };
 
 // A finished pair's record as the caller gets it.
@@ -588,6 +606,14 @@ struct rebvio_hip_ctx {
   int* spr_outcome = nullptr;  // (views into spr_cnt's allocation)
   int* spr_winner = nullptr;
   bool spr_queued = false;
+  // scratch of the place entries (ONE device allocation on first use, kept; track-side entries): 385 histogram words (padded to
+  // 388), then the query row of 384 u16 words, then its counted word. place_dbs: the databases that are out (place_mu:
+  // rebvio_hip_place_db_release may come from any thread).
+  unsigned* plc_hist = nullptr;
+  uint16_t* plc_query = nullptr;  // (views into plc_hist's allocation)
+  int* plc_counted = nullptr;
+  std::mutex place_mu;
+  std::vector<rebvio_hip_place_db*> place_dbs;
 };
 
 namespace {
@@ -1521,6 +1547,12 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
     sn->ctx = nullptr;
   }
   c->snaps.clear();
+  for (auto* db : c->place_dbs) {  // every listed database is out: its release deletes the husk
+    db->own.release();
+    db->rows = nullptr;
+    db->ctx = nullptr;
+  }
+  c->place_dbs.clear();
   c->own.release();
   delete c;
 }
@@ -3122,6 +3154,293 @@ int rebvio_hip_test_stereo_prior_host(int rows, int cols, float fm, rebvio_hip_k
     if (winner) winner[i] = win;
   }
   *counts = res;
+  return 0;
+}
+
+// ---- place recognition (include/rebvio_hip.h is the definition; place.hpp the statements) -------------------------------------------
+namespace {
+static_assert(sizeof(rebvio_hip_place_match) == 16, "copied from the device as it is");
+constexpr size_t kPlcRowBytes = plc::kWords * sizeof(uint16_t);
+constexpr size_t kPlcResHead = 16;  // the count, in front of the records
+
+const char* const kPlcPromised = ": the map was handed to track_pair_finish_async with R_prior_next and its gradients are rotated for the "
+                                 "next pair; take the signature where the snapshot is taken, or once the next track_pair_begin has run";
+
+// the context's scratch, made at the first signature
+int place_scratch(rebvio_hip_ctx* c) {
+  if (c->plc_hist) return 0;
+  char* b = nullptr;
+  const size_t hist = 388 * sizeof(unsigned);
+  HIPCHK(c->own.device_bytes(&b, hist + kPlcRowBytes + 16));
+  c->plc_hist = reinterpret_cast<unsigned*>(b);
+  c->plc_query = reinterpret_cast<uint16_t*>(b + hist);
+  c->plc_counted = reinterpret_cast<int*>(b + hist + kPlcRowBytes);
+  return 0;
+}
+
+// One clear and the two signature kernels on the track stream (the caller holds the life block and has done its checks).
+int enqueue_place_signature(rebvio_hip_ctx* c, rebvio_hip_map* m, uint16_t* sig_dev, int* counted_dev) {
+  const int rc = place_scratch(c);
+  if (rc) return rc;
+  if (!sig_dev) {  // the context's own query row
+    sig_dev = c->plc_query;
+    counted_dev = c->plc_counted;
+  }
+  wait_enqueued(m);
+  HIPCHK(trk_wait_ready_once(c, m));
+  HIPCHK(hipMemsetAsync(c->plc_hist, 0, (plc::kWords + 1) * sizeof(unsigned), c->s_trk));
+  launch_place_signature(c->s_trk, c->K, m->d, c->plc_hist, sig_dev, counted_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The two query kernels over the first `eligible` (> 0) rows, the copy of the count and k records, the tags.
+int run_place_query(rebvio_hip_place_db* db, const uint16_t* query_dev, int eligible, int k, rebvio_hip_place_match* out, int* count) {
+  rebvio_hip_ctx* c = db->ctx;
+  launch_place_query(c->s_trk, db->rows, eligible, query_dev, k, db->dist, db->res);
+  HIPCHK(hipGetLastError());
+  alignas(16) char host[kPlcResHead + REBVIO_HIP_PLACE_TOPK_MAX * sizeof(rebvio_hip_place_match)];
+  HIPCHK(hipMemcpyAsync(host, db->res, kPlcResHead + (size_t)k * sizeof(rebvio_hip_place_match), hipMemcpyDeviceToHost, c->s_trk));
+  const int rc = trk_sync(c);
+  if (rc) return rc;
+  int n = 0;
+  std::memcpy(&n, host, sizeof(int));
+  if (n < 0 || n > k || n > eligible) return fail_msg("place_db_query: the device returned an impossible count", -2);
+  for (int r = 0; r < n; ++r) {
+    rebvio_hip_place_match rec;
+    std::memcpy(&rec, host + kPlcResHead + (size_t)r * sizeof(rec), sizeof(rec));
+    if (rec.index < 0 || rec.index >= eligible) return fail_msg("place_db_query: the device returned an index outside the eligible rows", -2);
+    rec.tag = db->tags[(size_t)rec.index];
+    out[r] = rec;
+  }
+  *count = n;
+  return 0;
+}
+
+int check_place_query_args(const char* who, int k, int exclude_last) {
+  if (k < 1 || k > REBVIO_HIP_PLACE_TOPK_MAX) return fail_msg((std::string(who) + ": k outside 1..16").c_str(), -3);
+  if (exclude_last < 0) return fail_msg((std::string(who) + ": negative exclude_last").c_str(), -3);
+  return 0;
+}
+
+// Holds a database's life block (shared) for an entry's duration, as MapAlive does for a map.
+class DbAlive {
+ public:
+  explicit DbAlive(const rebvio_hip_place_db* db) : hold_(db->life), lock_(hold_->mu) {
+    dead_ = hold_->dead.load(std::memory_order_acquire);
+    if (dead_) g_err = "the place database's context has been destroyed (rebvio_hip_destroy)";
+  }
+  bool dead() const { return dead_; }
+
+ private:
+  std::shared_ptr<LifeBlock> hold_;
+  std::shared_lock<std::shared_mutex> lock_;
+  bool dead_;
+};
+}  // namespace
+
+int rebvio_hip_map_place_signature(rebvio_hip_map* m, uint16_t* sig, int* counted) {
+  if (!m || !sig || !counted) return fail_msg("map_place_signature: null map, signature or counted", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = m->ctx;
+  if (m->promised.load(std::memory_order_acquire)) return fail_msg((std::string("map_place_signature") + kPlcPromised).c_str(), -7);
+  HIPCHK(hipSetDevice(c->device));
+  int rc = enqueue_place_signature(c, m, nullptr, nullptr);
+  if (rc) return rc;
+  // (the row and its counted word lie next to each other: one copy)
+  alignas(4) char host[kPlcRowBytes + sizeof(int)];
+  HIPCHK(hipMemcpyAsync(host, c->plc_query, sizeof(host), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  std::memcpy(sig, host, kPlcRowBytes);
+  std::memcpy(counted, host + kPlcRowBytes, sizeof(int));
+  return 0;
+}
+
+int rebvio_hip_place_db_create(rebvio_hip_ctx* c, int cap, rebvio_hip_place_db** out) {
+  if (out) *out = nullptr;
+  if (!c || !out) return fail_msg("place_db_create: null context or output", -3);
+  if (cap < 1 || cap > 65536) return fail_msg("place_db_create: cap outside 1..65536", -3);
+  HIPCHK(hipSetDevice(c->device));
+  auto* db = new rebvio_hip_place_db;
+  db->ctx = c;
+  db->life = c->life;
+  db->cap = cap;
+  char* rows = nullptr;
+  char* aux = nullptr;
+  hipError_t e = db->own.device_bytes(&rows, (size_t)cap * kPlcRowBytes);
+  const size_t words = ((size_t)cap + 3) / 4 * 4;  // (keeps the result block 16-byte aligned)
+  if (e == hipSuccess) e = db->own.device_bytes(&aux, words * (sizeof(unsigned) + sizeof(int)) + kPlcResHead +
+                                                          REBVIO_HIP_PLACE_TOPK_MAX * sizeof(rebvio_hip_place_match));
+  if (e != hipSuccess) {
+    delete db;
+    return fail("place_db_create: device buffers", e);
+  }
+  db->rows = reinterpret_cast<uint16_t*>(rows);
+  db->dist = reinterpret_cast<unsigned*>(aux);
+  db->counted = reinterpret_cast<int*>(aux + words * sizeof(unsigned));
+  db->res = aux + words * (sizeof(unsigned) + sizeof(int));
+  try {
+    db->tags.reserve((size_t)cap);
+    std::lock_guard<std::mutex> lk(c->place_mu);
+    c->place_dbs.push_back(db);
+  } catch (...) {
+    delete db;
+    return fail_msg("place_db_create: out of host memory", -2);
+  }
+  *out = db;
+  return 0;
+}
+
+void rebvio_hip_place_db_release(rebvio_hip_place_db* db) {
+  if (!db) return;
+  {
+    const std::shared_ptr<LifeBlock> life = db->life;
+    std::shared_lock<std::shared_mutex> lk(life->mu);
+    if (!life->dead.load(std::memory_order_acquire)) {  // (else: the context is gone, its destroy freed the buffers)
+      rebvio_hip_ctx* c = db->ctx;
+      (void)hipSetDevice(c->device);
+      {
+        std::lock_guard<std::mutex> sl(c->place_mu);
+        for (size_t i = 0; i < c->place_dbs.size(); ++i)
+          if (c->place_dbs[i] == db) {
+            c->place_dbs.erase(c->place_dbs.begin() + (std::ptrdiff_t)i);
+            break;
+          }
+      }
+      db->own.release();  // (hipFree waits for the kernels that still use the buffers)
+    }
+  }
+  delete db;
+}
+
+int rebvio_hip_place_db_clear(rebvio_hip_place_db* db) {
+  if (!db) return fail_msg("place_db_clear: null database", -3);
+  const DbAlive alive(db);
+  if (alive.dead()) return -10;
+  db->size = 0;
+  db->tags.clear();
+  return 0;
+}
+
+int rebvio_hip_place_db_size(rebvio_hip_place_db* db) {
+  if (!db) return fail_msg("place_db_size: null database", -3);
+  const DbAlive alive(db);
+  if (alive.dead()) return -10;
+  return db->size;
+}
+
+int rebvio_hip_place_db_add(rebvio_hip_place_db* db, rebvio_hip_map* m, uint64_t tag, int* index) {
+  if (!db || !m) return fail_msg("place_db_add: null database or map", -3);
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (db->life != m->life) {
+    if (db->life->dead.load(std::memory_order_acquire)) return fail_msg("the place database's context has been destroyed (rebvio_hip_destroy)", -10);
+    return fail_msg("place_db_add: map of another context than the database's", -3);
+  }
+  rebvio_hip_ctx* c = db->ctx;
+  if (m->promised.load(std::memory_order_acquire)) return fail_msg((std::string("place_db_add") + kPlcPromised).c_str(), -7);
+  if (db->size >= db->cap) return fail_msg("place_db_add: the database is full", -7);
+  HIPCHK(hipSetDevice(c->device));
+  const int i = db->size;
+  const int rc = enqueue_place_signature(c, m, db->rows + (size_t)i * plc::kWords, db->counted + i);
+  if (rc) return rc;
+  db->tags.push_back(tag);  // (room reserved at create)
+  db->size = i + 1;
+  if (index) *index = i;
+  return 0;
+}
+
+int rebvio_hip_place_db_add_signature(rebvio_hip_place_db* db, const uint16_t* sig, int counted, uint64_t tag, int* index) {
+  if (!db || !sig) return fail_msg("place_db_add_signature: null database or signature", -3);
+  if (counted < 0) return fail_msg("place_db_add_signature: negative counted", -3);
+  const DbAlive alive(db);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = db->ctx;
+  if (db->size >= db->cap) return fail_msg("place_db_add_signature: the database is full", -7);
+  HIPCHK(hipSetDevice(c->device));
+  const int i = db->size;
+  HIPCHK(hipMemcpyAsync(db->rows + (size_t)i * plc::kWords, sig, kPlcRowBytes, hipMemcpyHostToDevice, c->s_trk));
+  HIPCHK(hipMemcpyAsync(db->counted + i, &counted, sizeof(int), hipMemcpyHostToDevice, c->s_trk));
+  const int rc = trk_sync(c);
+  if (rc) return rc;
+  db->tags.push_back(tag);
+  db->size = i + 1;
+  if (index) *index = i;
+  return 0;
+}
+
+int rebvio_hip_place_db_entry(rebvio_hip_place_db* db, int index, uint16_t* sig, int* counted, uint64_t* tag) {
+  if (!db) return fail_msg("place_db_entry: null database", -3);
+  const DbAlive alive(db);
+  if (alive.dead()) return -10;
+  if (index < 0 || index >= db->size) return fail_msg("place_db_entry: index outside [0, size)", -3);
+  rebvio_hip_ctx* c = db->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  int n = 0;
+  if (sig) HIPCHK(hipMemcpyAsync(sig, db->rows + (size_t)index * plc::kWords, kPlcRowBytes, hipMemcpyDeviceToHost, c->s_trk));
+  if (counted) HIPCHK(hipMemcpyAsync(&n, db->counted + index, sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  const int rc = trk_sync(c);
+  if (rc) return rc;
+  if (counted) *counted = n;
+  if (tag) *tag = db->tags[(size_t)index];
+  return 0;
+}
+
+int rebvio_hip_place_db_query(rebvio_hip_place_db* db, rebvio_hip_map* m, int k, int exclude_last, rebvio_hip_place_match* out, int* count) {
+  if (count) *count = 0;
+  if (!db || !m || !out || !count) return fail_msg("place_db_query: null database, map, output or count", -3);
+  int rc = check_place_query_args("place_db_query", k, exclude_last);
+  if (rc) return rc;
+  const MapAlive alive(m);
+  if (alive.dead()) return -10;
+  if (db->life != m->life) {
+    if (db->life->dead.load(std::memory_order_acquire)) return fail_msg("the place database's context has been destroyed (rebvio_hip_destroy)", -10);
+    return fail_msg("place_db_query: map of another context than the database's", -3);
+  }
+  rebvio_hip_ctx* c = db->ctx;
+  if (m->promised.load(std::memory_order_acquire)) return fail_msg((std::string("place_db_query") + kPlcPromised).c_str(), -7);
+  const int eligible = db->size - exclude_last;
+  if (eligible <= 0) return 0;  // nothing is launched
+  HIPCHK(hipSetDevice(c->device));
+  rc = enqueue_place_signature(c, m, nullptr, nullptr);
+  if (rc) return rc;
+  return run_place_query(db, c->plc_query, eligible, k, out, count);
+}
+
+int rebvio_hip_place_db_query_signature(rebvio_hip_place_db* db, const uint16_t* sig, int k, int exclude_last, rebvio_hip_place_match* out,
+                                        int* count) {
+  if (count) *count = 0;
+  if (!db || !sig || !out || !count) return fail_msg("place_db_query_signature: null database, signature, output or count", -3);
+  int rc = check_place_query_args("place_db_query_signature", k, exclude_last);
+  if (rc) return rc;
+  const DbAlive alive(db);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = db->ctx;
+  const int eligible = db->size - exclude_last;
+  if (eligible <= 0) return 0;  // nothing is launched
+  HIPCHK(hipSetDevice(c->device));
+  rc = place_scratch(c);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(c->plc_query, sig, kPlcRowBytes, hipMemcpyHostToDevice, c->s_trk));
+  return run_place_query(db, c->plc_query, eligible, k, out, count);
+}
+
+int rebvio_hip_test_place_signature_host(int rows, int cols, const rebvio_hip_keyline* keylines, int n, uint16_t* sig, int* counted) {
+  if (!sig || !counted || n < 0 || (n > 0 && !keylines)) return fail_msg("test_place_signature_host: null array or negative size", -3);
+  if (rows < 1 || cols < 1) return fail_msg("test_place_signature_host: rows or cols < 1", -3);
+  plc::signature_host(rows, cols, keylines, n, sig, counted);
+  return 0;
+}
+
+int rebvio_hip_test_place_query_host(const uint16_t* rows384, int size, const uint16_t* sig, int k, int exclude_last,
+                                     rebvio_hip_place_match* out, int* count) {
+  if (count) *count = 0;
+  if (!sig || !out || !count || size < 0 || (size > 0 && !rows384)) return fail_msg("test_place_query_host: null array or negative size", -3);
+  const int rc = check_place_query_args("test_place_query_host", k, exclude_last);
+  if (rc) return rc;
+  plc::query_host(rows384, size, sig, k, exclude_last, out, count);
   return 0;
 }
 

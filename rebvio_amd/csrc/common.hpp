@@ -435,6 +435,13 @@ struct Args;
 void launch_stereo_prior(hipStream_t s, const KParams& p, const MapDev& m, const MapDev& r, int r_kmax, const spr::Args& a, int* cnt,
                          int* outcome, int* winner);
 
+// Place recognition on stream s (rebvio_hip_map_place_signature, rebvio_hip_place_db_*; place.hpp). launch_place_signature:
+// k_place_hist + k_place_norm; hist = 385 words the caller cleared in front of the launch, sig = 384 u16 words and counted = one
+// int, both written whatever the map holds. launch_place_query: k_place_dist + k_place_topk over rows e < eligible (> 0) of
+// 384 u16 words each; dist = eligible words, res = a 16-byte head (the count) and k records of rebvio_hip_place_match, k <= 16.
+void launch_place_signature(hipStream_t s, const KParams& p, const MapDev& m, unsigned* hist, uint16_t* sig, int* counted);
+void launch_place_query(hipStream_t s, const uint16_t* rows, int eligible, const uint16_t* query, int k, unsigned* dist, char* res);
+
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
 // ---- several camera streams ("lanes") of one GPU advanced in lock-step by batched launches (rebvio_hip_batch_*) --------

@@ -16,6 +16,7 @@
 #include "stereo_prior.hpp"
 #include "kf_handover.hpp"
 #include "kf_pose.hpp"
+#include "place.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -4240,6 +4241,161 @@ __global__ __launch_bounds__(256) void k_stereo_prior(KParams p, MapDev m, MapDe
 void launch_stereo_prior(hipStream_t s, const KParams& p, const MapDev& m, const MapDev& r, int r_kmax, const spr::Args& a, int* cnt,
                          int* outcome, int* winner) {
   RH_LAUNCH(k_stereo_prior, dim3(div_up(p.kmax, 256 / kSprLanes)), dim3(256), 0, s, p, m, r, r_kmax, a, cnt, outcome, winner);
+}
+
+// ---- place recognition (rebvio_hip_map_place_signature, rebvio_hip_place_db_*) ---------------------------------------------------------
+// place.hpp holds the definition's statements. Everything that crosses threads is an integer sum or a minimum of distinct keys,
+// so no output word depends on an order.
+//
+// k_place_hist: one thread per keyline, the map's size read on the device. A workgroup fills a 384-word LDS histogram (+ the
+// counted total as word 384) with LDS integer atomics and, behind a barrier, adds its non-zero words to hist[385] in global memory,
+// which the caller cleared in front of the launch.
+__global__ __launch_bounds__(256) void k_place_hist(KParams p, MapDev m, unsigned* __restrict__ hist) {
+  __shared__ unsigned sh[plc::kWords + 1];
+  const int tid = threadIdx.x;
+  for (int k = tid; k <= plc::kWords; k += 256) sh[k] = 0u;
+  __syncthreads();
+  const int n = min(max(m.st->n, 0), p.kmax);
+  const int i = blockIdx.x * 256 + tid;
+  bool in = false;
+  if (i < n) {
+    const float2 pos = m.pos[i], g = m.grad[i];
+    if (plc::counted(p.rows, p.cols, pos.x, pos.y, g.x, g.y, m.gnorm[i])) {
+      in = true;
+      atomicAdd(&sh[plc::word_of(p.rows, p.cols, pos.x, pos.y, g.x, g.y)], 1u);
+    }
+  }
+  const int c = __popcll(__ballot(in));
+  if ((tid & 63) == 0 && c) atomicAdd(&sh[plc::kWords], (unsigned)c);
+  __syncthreads();
+  for (int k = tid; k <= plc::kWords; k += 256) {
+    const unsigned v = sh[k];
+    if (v) atomicAdd(&hist[k], v);
+  }
+}
+
+// k_place_norm: one workgroup. The 384 u16 words go straight to their destination (the context's query row, or a row of a
+// database), the counted total next to its own.
+__global__ __launch_bounds__(256) void k_place_norm(const unsigned* __restrict__ hist, uint16_t* __restrict__ sig, int* __restrict__ counted) {
+  const unsigned n = hist[plc::kWords];
+  for (int k = threadIdx.x; k < plc::kWords; k += 256) sig[k] = plc::normalise(hist[k], n);
+  if (threadIdx.x == 0) *counted = (int)n;
+}
+
+// k_place_dist: one wave per database row. A row is 64 lanes x 12 bytes: lane l holds words 6l .. 6l + 5 as three dwords, the
+// query's in registers for the wave's whole loop. Three sums of absolute differences of packed u16 pairs per lane and row
+// (v_sad_u16), a butterfly over the wave, lane 0 stores dist[e]. A wave strides over the rows by the number of waves in the
+// grid, kPlcUnroll rows at a time: their loads do not depend on each other and are in flight together.
+struct PlcLane {
+  unsigned a, b, c;
+};
+static_assert(sizeof(PlcLane) == 12 && alignof(PlcLane) == 4, "three dwords: one 12-byte load per lane");
+__device__ __forceinline__ unsigned plc_lane_sad(const PlcLane& r, const PlcLane& q) {
+  unsigned d = __builtin_amdgcn_sad_u16(r.a, q.a, 0u);
+  d = __builtin_amdgcn_sad_u16(r.b, q.b, d);
+  return __builtin_amdgcn_sad_u16(r.c, q.c, d);
+}
+__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+constexpr int kPlcUnroll = 4;
+constexpr int kPlcDistBlocks = 2048;  // 8 workgroups of 4 waves per CU of an MI355X: every wave slot holds one
+__global__ __launch_bounds__(256) void k_place_dist(const uint16_t* __restrict__ rows, int eligible, const uint16_t* __restrict__ query,
+                                                    unsigned* __restrict__ dist) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int waves = gridDim.x * 4;
+  const PlcLane q = reinterpret_cast<const PlcLane*>(query)[lane];
+  const PlcLane* __restrict__ tab = reinterpret_cast<const PlcLane*>(rows);
+  int e = wave;
+  for (; e + (kPlcUnroll - 1) * waves < eligible; e += kPlcUnroll * waves) {
+    PlcLane r[kPlcUnroll];
+#pragma unroll
+    for (int u = 0; u < kPlcUnroll; ++u) r[u] = tab[(size_t)(e + u * waves) * 64 + lane];
+#pragma unroll
+    for (int u = 0; u < kPlcUnroll; ++u) {
+      const unsigned d = wave_sum_u(plc_lane_sad(r[u], q));
+      if (lane == 0) dist[e + u * waves] = d;
+    }
+  }
+  for (; e < eligible; e += waves) {
+    const unsigned d = wave_sum_u(plc_lane_sad(tab[(size_t)e * 64 + lane], q));
+    if (lane == 0) dist[e] = d;
+  }
+}
+
+// k_place_topk: one workgroup of 1024. Keys are (dist << 32 | index) over the eligible rows, all distinct; min(k, eligible) rounds
+// of "the smallest key above the previous winner". A thread keeps the smallest key of its own strided rows that has not won yet:
+// one full scan in front of the rounds, and after a round only the winner's owner scans its rows again - every other thread's key
+// is larger than the winner and stays what it was. Per round a butterfly on 64-bit minima inside each wave and LDS across the 16
+// waves. res: the count (an int in a 16-byte head), then the records with tag 0 (the host owns the tags).
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), o), hi = __shfl_xor((unsigned)(v >> 32), o);
+    const unsigned long long t = ((unsigned long long)hi << 32) | lo;
+    v = t < v ? t : v;
+  }
+  return v;
+}
+// the smallest key >= lo among the rows tid, tid + 1024, ...: eight loads in flight at a time (the scan is a chain of L2 latencies)
+__device__ __forceinline__ unsigned long long plc_scan(const unsigned* __restrict__ dist, int eligible, int tid, unsigned long long lo) {
+  unsigned long long best = ~0ull;
+  for (int e = tid; e < eligible; e += 8 * 1024) {
+    unsigned d[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = e + u * 1024;
+      d[u] = i < eligible ? dist[i] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = e + u * 1024;
+      const unsigned long long key = i < eligible ? ((unsigned long long)d[u] << 32) | (unsigned)i : ~0ull;
+      if (key >= lo && key < best) best = key;
+    }
+  }
+  return best;
+}
+__global__ __launch_bounds__(1024) void k_place_topk(const unsigned* __restrict__ dist, int eligible, int k, char* __restrict__ res) {
+  __shared__ unsigned long long sh[16];
+  __shared__ unsigned long long sh_win;
+  const int tid = threadIdx.x;
+  const int rounds = min(k, eligible);
+  rebvio_hip_place_match* out = reinterpret_cast<rebvio_hip_place_match*>(res + 16);
+  if (tid == 0) *reinterpret_cast<int*>(res) = rounds;
+  unsigned long long mine = plc_scan(dist, eligible, tid, 0ull);
+  for (int r = 0; r < rounds; ++r) {
+    const unsigned long long best = wave_min_u64(mine);
+    if ((tid & 63) == 0) sh[tid >> 6] = best;
+    __syncthreads();
+    if (tid < 64) {
+      unsigned long long v = tid < 16 ? sh[tid] : ~0ull;
+      v = wave_min_u64(v);
+      if (tid == 0) {
+        out[r].distance = (unsigned)(v >> 32);
+        out[r].index = (int)(unsigned)(v & 0xffffffffull);
+        out[r].tag = 0ull;
+        sh_win = v;
+      }
+    }
+    __syncthreads();
+    const unsigned long long win = sh_win;
+    if (((unsigned)(win & 0xffffffffull) & 1023u) == (unsigned)tid) mine = plc_scan(dist, eligible, tid, win + 1ull);
+  }
+}
+
+void launch_place_signature(hipStream_t s, const KParams& p, const MapDev& m, unsigned* hist, uint16_t* sig, int* counted) {
+  RH_LAUNCH(k_place_hist, dim3(div_up(p.kmax, 256)), dim3(256), 0, s, p, m, hist);
+  RH_LAUNCH(k_place_norm, dim3(1), dim3(256), 0, s, hist, sig, counted);
+}
+
+void launch_place_query(hipStream_t s, const uint16_t* rows, int eligible, const uint16_t* query, int k, unsigned* dist, char* res) {
+  const int blocks = div_up(eligible, 4) < kPlcDistBlocks ? div_up(eligible, 4) : kPlcDistBlocks;
+  RH_LAUNCH(k_place_dist, dim3(blocks), dim3(256), 0, s, rows, eligible, query, dist);
+  RH_LAUNCH(k_place_topk, dim3(1), dim3(1024), 0, s, dist, eligible, k, res);
 }
 
 }  // namespace rh

@@ -248,6 +248,79 @@ void KeyframeSnapshot::reset() {
   keepalive_.reset();
 }
 
+// ---- place recognition ----------------------------------------------------------------------------------------------------------
+static_assert(sizeof(types::PlaceMatch) == sizeof(rebvio_hip_place_match) && offsetof(types::PlaceMatch, distance) == offsetof(rebvio_hip_place_match, distance) &&
+                  offsetof(types::PlaceMatch, index) == offsetof(rebvio_hip_place_match, index) &&
+                  offsetof(types::PlaceMatch, tag) == offsetof(rebvio_hip_place_match, tag) && types::kPlaceWords == REBVIO_HIP_PLACE_WORDS &&
+                  types::kPlaceTopKMax == REBVIO_HIP_PLACE_TOPK_MAX,
+              "place records mirror the C-ABI's");
+
+rebvio::types::PlaceSignature EdgeMap::placeSignature(int* counted) const {
+  types::PlaceSignature sig{};
+  int n = 0;
+  check("rebvio_hip_map_place_signature", rebvio_hip_map_place_signature(handle_, sig.data(), &n));
+  if (counted) *counted = n;
+  return sig;
+}
+
+rebvio::PlaceDb EdgeMap::placeDb(int capacity) const {
+  rebvio_hip_place_db* h = nullptr;
+  check("rebvio_hip_place_db_create", rebvio_hip_place_db_create(ctx_, capacity, &h));
+  return rebvio::PlaceDb(h, capacity, keepalive_);
+}
+
+void PlaceDb::reset() {
+  if (handle_) rebvio_hip_place_db_release(handle_);
+  handle_ = nullptr;
+  keepalive_.reset();
+}
+
+int PlaceDb::size() const {
+  const int n = rebvio_hip_place_db_size(handle_);
+  if (n < 0) check("rebvio_hip_place_db_size", n);
+  return n;
+}
+
+void PlaceDb::clear() { check("rebvio_hip_place_db_clear", rebvio_hip_place_db_clear(handle_)); }
+
+int PlaceDb::add(const rebvio::EdgeMap& map, uint64_t tag) {
+  if (handle_ && size() >= capacity_) return -1;
+  int index = -1;
+  check("rebvio_hip_place_db_add", rebvio_hip_place_db_add(handle_, map.handle(), tag, &index));
+  return index;
+}
+
+int PlaceDb::addSignature(const rebvio::types::PlaceSignature& signature, int counted, uint64_t tag) {
+  if (handle_ && size() >= capacity_) return -1;
+  int index = -1;
+  check("rebvio_hip_place_db_add_signature", rebvio_hip_place_db_add_signature(handle_, signature.data(), counted, tag, &index));
+  return index;
+}
+
+rebvio::types::PlaceSignature PlaceDb::entry(int index, int* counted, uint64_t* tag) const {
+  types::PlaceSignature sig{};
+  check("rebvio_hip_place_db_entry", rebvio_hip_place_db_entry(handle_, index, sig.data(), counted, tag));
+  return sig;
+}
+
+std::vector<rebvio::types::PlaceMatch> PlaceDb::query(const rebvio::EdgeMap& map, int k, int exclude_last) const {
+  std::vector<types::PlaceMatch> out((size_t)(k > 0 && k <= types::kPlaceTopKMax ? k : 0));
+  int n = 0;
+  check("rebvio_hip_place_db_query",
+        rebvio_hip_place_db_query(handle_, map.handle(), k, exclude_last, reinterpret_cast<rebvio_hip_place_match*>(out.data()), &n));
+  out.resize((size_t)n);
+  return out;
+}
+
+std::vector<rebvio::types::PlaceMatch> PlaceDb::querySignature(const rebvio::types::PlaceSignature& signature, int k, int exclude_last) const {
+  std::vector<types::PlaceMatch> out((size_t)(k > 0 && k <= types::kPlaceTopKMax ? k : 0));
+  int n = 0;
+  check("rebvio_hip_place_db_query_signature",
+        rebvio_hip_place_db_query_signature(handle_, signature.data(), k, exclude_last, reinterpret_cast<rebvio_hip_place_match*>(out.data()), &n));
+  out.resize((size_t)n);
+  return out;
+}
+
 rebvio::KeyframeSnapshot EdgeMap::keyframeSnapshot() {
   rebvio_hip_kf_snapshot* h = nullptr;
   const int rc = rebvio_hip_map_keyframe_snapshot(ctx_, handle_, &h);

@@ -138,6 +138,20 @@ void Rebvio::registerStereoPriorCallback(std::function<void(uint64_t ts_us, cons
   stereo_prior_callbacks_.push_back(cb);
 }
 
+void Rebvio::setPlaceRecognition(int capacity, int top_k, int exclude_last, uint32_t max_distance) {
+  if (capacity < 0 || capacity > 65536) backend::fail("Rebvio::setPlaceRecognition: capacity outside 0..65536", -3);
+  if (top_k < 1 || top_k > types::kPlaceTopKMax) backend::fail("Rebvio::setPlaceRecognition: top_k outside 1..16", -3);
+  if (exclude_last < 0) backend::fail("Rebvio::setPlaceRecognition: negative exclude_last", -3);
+  place_top_k_ = top_k;
+  place_exclude_last_ = exclude_last;
+  place_max_distance_ = max_distance;
+  place_capacity_ = capacity;
+}
+
+void Rebvio::registerPlaceCallback(std::function<void(uint64_t ts_us, const std::vector<rebvio::types::PlaceMatch>&)> cb) {
+  place_callbacks_.push_back(cb);
+}
+
 void Rebvio::imageCallback(rebvio::types::Image&& image) {
   std::lock_guard<std::mutex> guard(image_buffer_mutex_);
   const int t = image.data.type();
@@ -444,6 +458,9 @@ void Rebvio::stateEstimationProcess() {
     // the stereo partner: the same for the fusion of the right frame's edge map
     bool have_stereo = false;
     types::StereoPriorCounts stereo_counts;
+    // setPlaceRecognition: the new map was marked and the database queried with it; the matches under max_distance
+    bool have_place = false;
+    std::vector<types::PlaceMatch> place_matches;
   } pending;
   // the stereo partner. take_right: the queued right image with exactly this stamp (older ones are dropped and counted); nothing is
   // touched while no right image has ever been handed in. queue_stereo: the image through the right detector, then the fusion on
@@ -514,6 +531,8 @@ void Rebvio::stateEstimationProcess() {
     bool warm;
   };
   std::deque<KfWindowMember> kf_window;
+  // setPlaceRecognition: the signatures of the maps keyframes were marked on, made at the first mark
+  rebvio::PlaceDb place_db;
   bool kf_marked_here = false;  // this pair's new map is the one the snapshot was taken from: it is not fused into itself
   // keyframe-cloud callbacks: stamp and odometry pose (R_global, Pos, K) of the record on whose map the snapshot was taken
   uint64_t kf_ts = 0;
@@ -563,6 +582,8 @@ void Rebvio::stateEstimationProcess() {
       const types::PointCloud pc{pending.kf_cloud_ts, pending.kf_cloud_pose, reinterpret_cast<const types::CloudPoint*>(pts), (size_t)n};
       keyframe_cloud_callbacks_[i].cb(pc);
     }
+    if (pending.have_place)  // after the other keyframe callbacks of the record
+      for (auto& cb : place_callbacks_) cb(pending.odometry.ts_us, pending.place_matches);
     for (size_t i = 0; i < pending.clouds.size(); ++i) {
       const rebvio_hip_cloud_point* pts = nullptr;
       int n = 0;
@@ -814,6 +835,11 @@ void Rebvio::stateEstimationProcess() {
     // Nor while a depth image waits for the new map: it is folded into the map's depths in THIS pair's frame.
     const bool have_depth = take_depth(new_edge_map->ts_us(), &depth_image, &depth_opts);
     const bool have_stereo = take_right(new_edge_map->ts_us(), &right_image, &stereo_opts);  // (the same holds for a right image)
+    // setPlaceRecognition: a keyframe request is taken here, not at the mark below - the marked map's signature is of its gradients
+    // in THIS pair's frame, so the next pair's rotation must not ride in this pair's last kernel. Off, the request is read where
+    // it always was.
+    const int place_capacity = place_capacity_.load();
+    const bool kf_taken_early = place_capacity > 0 && keyframe_requested_.exchange(false);
     float Rnext[9];
     bool have_next = false;
     rebvio::EdgeMap::SharedPtr next_map;
@@ -821,7 +847,7 @@ void Rebvio::stateEstimationProcess() {
       std::lock_guard<std::mutex> guard(edge_map_buffer_mutex_);
       if (edge_map_buffer_.size() >= 2) {
         next_map = edge_map_buffer_[1];
-        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud && !want_polylines && !have_depth && !have_stereo) {
+        if (imu_state_.initialized && !want_cloud && !want_kf_pose && !want_kf_cloud && !want_polylines && !have_depth && !have_stereo && !kf_taken_early) {
           store3(next_map->imu().R(), Rnext);
           have_next = true;
         }
@@ -857,7 +883,8 @@ void Rebvio::stateEstimationProcess() {
     rebvio::KeyframeSnapshot handover_outgoing;
     types::KfPose handover_guess;
     uint64_t handover_ts = 0;
-    if (keyframe_requested_.exchange(false)) {
+    const bool kf_mark = place_capacity > 0 ? kf_taken_early : keyframe_requested_.exchange(false);
+    if (kf_mark) {
       new_edge_map->markKeyframe();
       if (want_kf_pose || want_kf_cloud) {  // the keyframe as it is now, right behind its mark; the previous one goes
         if (want_kf_cloud && kf_snapshot) {  // ... as a cloud, queued before its snapshot is released (which is safe right behind)
@@ -893,6 +920,20 @@ void Rebvio::stateEstimationProcess() {
       }
     }
     publish_pending();  // the previous pair's record: its callbacks run while the device works on this pair's second half
+    // setPlaceRecognition: the marked map against the database, right behind its snapshot in stream order (the query waits for this
+    // pair's second half), then the map itself goes in. The last exclude_last entries are the keyframes the tracker has just left.
+    bool have_place = false;
+    std::vector<types::PlaceMatch> place_matches;
+    if (kf_mark && place_capacity > 0) {
+      if (!place_db) place_db = new_edge_map->placeDb(place_capacity);
+      const uint32_t max_distance = place_max_distance_.load();
+      for (const types::PlaceMatch& m : place_db.query(*new_edge_map, place_top_k_.load(), place_exclude_last_.load()))
+        if (m.distance <= max_distance) place_matches.push_back(m);
+      if (place_db.add(*new_edge_map, new_edge_map->ts_us()) < 0) ++place_misses_;
+      ++place_queries_;
+      place_matches_ += (unsigned int)place_matches.size();
+      have_place = true;
+    }
     // edge-polyline callbacks: the new map's polylines in this pair's frame, behind this pair's second half (the call waits for it)
     std::vector<rebvio::EdgeMap::EdgePolylines> polylines;
     types::CloudPose polyline_pose;
@@ -992,6 +1033,8 @@ void Rebvio::stateEstimationProcess() {
     pending.polyline_pose = polyline_pose;
     pending.have_depth = have_depth;
     pending.have_stereo = have_stereo;
+    pending.have_place = have_place;
+    pending.place_matches = std::move(place_matches);
     timers.lap(3);
     timers.end_pair();
     timers.n++;

@@ -31,6 +31,11 @@
 // --kf-cloud PREFIX [--kf-every N]: every retired keyframe's point cloud (Rebvio::registerKeyframeCloudCallback, default filter) as
 // PREFIX<ts_us>.ply, ts_us the keyframe's own stamp, through the same PLY writer; keyframes are requested as for --kf-pose. Alone it
 // writes the keyframes as marked; with --kf-fuse (and --kf-align) the refined ones. The keyframe current at the end is not written.
+// --places FILE [--place-exclude N] [--kf-every N]: place recognition (Rebvio::setPlaceRecognition with room for 4096 keyframes, the
+// default top_k and max_distance, exclude_last = N, default 10; Rebvio::registerPlaceCallback), one line per match: ts_us tag distance
+// index - ts_us the record whose map was marked, tag the stamp of the keyframe it looks like, index that keyframe's row in the
+// database. Keyframes are requested as for --kf-pose. The summary on stderr counts the queries and the matches. The odometry file is
+// what it is without it.
 // --depth FILE [--depth-unit U]: registered depth images, one per frame in frame order (frame 0 of the file belongs to frame 0 of the
 // stream, whatever --first is), raw little-endian uint16 counts of U metres (default 0.001; 0 = no depth), W x H each, dense. Every
 // frame's image is handed to Rebvio::depthImageCallback in front of the frame itself; the reader then stays at most seven frames
@@ -56,7 +61,8 @@
 
 int main(int argc, char** argv) {
   std::string asl, raw, imu, out, mask_png, cloud_prefix, kf_pose_path, kf_fuse_path, kf_cloud_prefix, kf_window_path, kf_handover_path;
-  std::string polylines_prefix, depth_path, right_path;
+  std::string polylines_prefix, depth_path, right_path, places_path;
+  int place_exclude = 10;
   double depth_unit = 0.001, baseline = 0.0;
   int min_chain = 8;
   int kf_window = 0;
@@ -70,7 +76,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--depth FILE [--depth-unit U]] [--right FILE|DIR --baseline B] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] --out file\n", argv[0]);
+                 "[--mask mask.png] [--depth FILE [--depth-unit U]] [--right FILE|DIR --baseline B] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] [--places FILE [--place-exclude N]] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -127,6 +133,11 @@ int main(int argc, char** argv) {
     }
     else if (a == "--kf-cloud") kf_cloud_prefix = next();
     else if (a == "--kf-every") kf_every = std::atoi(next());
+    else if (a == "--places") {
+      if (!places_path.empty()) return usage();
+      places_path = next();
+    }
+    else if (a == "--place-exclude") place_exclude = std::atoi(next());
     else if (a == "--keylines") { kref = std::atoi(next()); kmax = std::atoi(next()); }
     else if (a == "--min-matches") min_matches = std::atoi(next());
     else if (a == "--camera") {
@@ -140,6 +151,7 @@ int main(int argc, char** argv) {
   }
   if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1 || min_chain < 1 || !(depth_unit > 0.0)) return usage();
   if (right_path.empty() != !(baseline > 0.0)) return usage();  // --right and --baseline come together
+  if (place_exclude < 0) return usage();
   if (!kf_window_path.empty() && (!kf_align || kf_pose_path.empty() || kf_window < 1 || kf_window > 15)) return usage();  // needs --kf-align FILE
   if (!kf_handover_path.empty() && (!kf_align || kf_pose_path.empty())) return usage();  // needs --kf-align FILE
   if (!kf_fuse_path.empty()) {  // the fusion runs behind the alignment only
@@ -198,7 +210,7 @@ int main(int argc, char** argv) {
       t_last = std::chrono::steady_clock::now();
       if (n_odo == 0) t_first = t_last;
       ++n_odo;
-      if ((want_kf || !kf_cloud_prefix.empty()) && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
+      if ((want_kf || !kf_cloud_prefix.empty() || !places_path.empty()) && n_odo % (size_t)kf_every == 0) rebvio.requestKeyframe();
     });
     std::FILE *kf_pose_file = nullptr, *kf_fuse_file = nullptr, *kf_window_file = nullptr, *kf_handover_file = nullptr;
     size_t n_poses = 0, n_fusions = 0, n_window = 0, n_handovers = 0;
@@ -260,6 +272,20 @@ int main(int argc, char** argv) {
         n_kf_points += pc.size;
       });
       if (!want_kf) rebvio.requestKeyframe();
+    }
+    std::FILE* places_file = nullptr;
+    if (!places_path.empty()) {
+      places_file = std::fopen(places_path.c_str(), "w");
+      if (!places_file) {
+        std::fprintf(stderr, "error: cannot write %s\n", places_path.c_str());
+        return 1;
+      }
+      rebvio.setPlaceRecognition(4096, 4, place_exclude);
+      rebvio.registerPlaceCallback([&](uint64_t ts_us, const std::vector<rebvio::types::PlaceMatch>& matches) {
+        for (const rebvio::types::PlaceMatch& m : matches)
+          std::fprintf(places_file, "%llu %llu %u %d\n", (unsigned long long)ts_us, (unsigned long long)m.tag, m.distance, m.index);
+      });
+      if (!want_kf && kf_cloud_prefix.empty()) rebvio.requestKeyframe();
     }
     size_t n_clouds = 0, n_points = 0;
     if (!cloud_prefix.empty() || cloud_dry)
@@ -349,6 +375,10 @@ int main(int argc, char** argv) {
     if (right_src)
       std::fprintf(stderr, "right_images=%zu stereo_fused_frames=%zu stereo_fused_keylines=%zu right_dropped=%u\n", n_right_handed, n_right, n_right_fused,
                    rebvio.rightImagesDropped());
+    if (places_file) {
+      std::fclose(places_file);
+      std::fprintf(stderr, "place_queries=%u place_matches=%u place_misses=%u\n", rebvio.placeQueries(), rebvio.placeMatches(), rebvio.placeMisses());
+    }
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
     if (!kf_cloud_prefix.empty()) std::fprintf(stderr, "kf_clouds=%zu kf_points=%zu\n", n_kf_clouds, n_kf_points);
     if (!polylines_prefix.empty()) std::fprintf(stderr, "polyline_files=%zu lines=%zu line_points=%zu\n", n_polyline_files, n_lines, n_line_points);
