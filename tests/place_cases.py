@@ -1,6 +1,8 @@
 """Crafted inputs of place recognition, shared by tests/test_place.py (hooks against the numpy restatement) and
 tests/test_place_gpu.py (kernels against the hooks): keyline tables with keylines planted on every edge of the definition, random
-tables with hostile values mixed in, and database rows with extreme, tied and lane-boundary entries."""
+tables with hostile values mixed in, database rows with extreme, tied and lane-boundary entries, a 65 536-row table whose top 16 is
+known in closed form for 4096 queries that together name every row, the launch arithmetic of a query restated, and 17 000 rows
+with ties and cuts planted in single threads' shares of k_place_topk's scan."""
 import numpy as np
 
 from rebvio_amd import backend as B
@@ -132,6 +134,145 @@ def db_rows(rng, n):
         rows[n // 2] = np.where(q < 32768, 65535, 0).astype(np.uint16)
         rows[40] = rows[41] = rows[n - 1]   # ties among random rows
     return rows, q
+
+
+# ---- a table in which every row is some query's answer ---------------------------------------------------------------------------
+# Row i: every even word is 16 * (i // 16), every odd word (i % 16) + off[w]; query j: even words 16 * j, odd words off[w]. The 192
+# even words differ by 16 * |i // 16 - j| each and the 192 odd words by i % 16 each: d(i) = 3072 * |i // 16 - j| + 192 * (i % 16).
+# Block j holds 0, 192, ..., 2880, its neighbours start at 3072 (row r of block j - 1 ties with row r of block j + 1: the lower
+# index first); at 65 536 eligible rows query j returns rows 16 j .. 16 j + 15, so the 4096 queries name every row once.
+BLOCK_ROWS = 65536
+BLOCK = 16
+
+
+_BLOCK_OFF = np.random.default_rng(20250).integers(0, 60000, WORDS // 2).astype(np.uint16)
+_BLOCK_OFF.setflags(write=False)
+
+
+def block_offsets():
+    """one offset per odd word, 0 .. 59 999: the lanes of k_place_dist hold different words, so a lane mix-up shows"""
+    return _BLOCK_OFF
+
+
+def block_table(n=BLOCK_ROWS):
+    """-> rows uint16 [n, 384]; the largest word is 16 * 4095 = 65 520"""
+    i = np.arange(n, dtype=np.int64)
+    rows = np.empty((n, WORDS), np.uint16)
+    rows[:, 0::2] = (BLOCK * (i // BLOCK))[:, None]
+    rows[:, 1::2] = (i % BLOCK)[:, None] + block_offsets().astype(np.int64)[None, :]
+    return rows
+
+
+def block_query(j):
+    q = np.empty(WORDS, np.uint16)
+    q[0::2] = BLOCK * j
+    q[1::2] = block_offsets()
+    return q
+
+
+def block_tag(i):
+    return (1 << 40) + 3 * i
+
+
+def block_top(eligible, j, k=16):
+    """the closed form: [(distance, index)] of query j over the rows i < eligible, for a j whose block holds an eligible row. Blocks
+    j - 2 .. j + 2 cut at `eligible` are enough: with j >= 1 block j - 1 is whole and no farther than 3072 + 2880, so with the row
+    of block j there are 17 rows under the 3 * 3072 of every block outside; with j = 0 block 0 is either whole or all there is."""
+    assert 0 <= BLOCK * j < eligible
+    near = range(max(0, BLOCK * (j - 2)), min(eligible, BLOCK * (j + 3)))
+    return sorted((3072 * abs(i // BLOCK - j) + 192 * (i % BLOCK), i) for i in near)[:k]
+
+
+# ---- the launch arithmetic of a query, restated ---------------------------------------------------------------------------------
+# track.hip: k_place_dist runs min(ceil(E / 4), kPlcDistBlocks) workgroups of four waves; wave w takes rows w, w + waves, ...,
+# kPlcUnroll at a time while the last of the four is eligible, then one at a time. k_place_topk's plc_scan gives thread t of 1024
+# the rows t, t + 1024, ..., eight per outer iteration.
+PLC_DIST_BLOCKS = 2048   # kPlcDistBlocks
+PLC_UNROLL = 4           # kPlcUnroll
+PLC_TOPK_THREADS = 1024
+PLC_SCAN_STEP = 8 * 1024
+
+# the eligible counts the block-table tests run at; tests/test_place.py::test_launch_arithmetic_of_the_sizes asserts what each reaches
+BLOCK_ELIGIBLE = (8188, 8189, 8192, 8193, 24576, 24577, 32768, 32769, 40000, 57344, 57345, 65535, 65536)
+
+
+def dist_waves(eligible):
+    return 4 * min(-(-eligible // 4), PLC_DIST_BLOCKS)
+
+
+def dist_wave_shape(eligible, wave):
+    """-> (unrolled passes, tail rounds, rows) of one wave of k_place_dist"""
+    waves = dist_waves(eligible)
+    e, passes, tail, rows = wave, 0, 0, []
+    while e + (PLC_UNROLL - 1) * waves < eligible:
+        rows += [e + u * waves for u in range(PLC_UNROLL)]
+        passes, e = passes + 1, e + PLC_UNROLL * waves
+    while e < eligible:
+        rows.append(e)
+        tail, e = tail + 1, e + waves
+    return passes, tail, rows
+
+
+def scan_shape(eligible, tid):
+    """-> (outer iterations, rows) of thread tid in plc_scan"""
+    return len(range(tid, eligible, PLC_SCAN_STEP)), len(range(tid, eligible, PLC_TOPK_THREADS))
+
+
+# ---- rows for k_place_topk: one thread's rows over more than one outer iteration of its scan --------------------------------------
+TOPK_ROWS = 17000   # thread t of 1024 owns rows t, t + 1024, ...: 17 of them for t < 616, 16 above; a scan takes 8 per iteration
+TOPK_CASES = ("16-way tie of thread 5", "16-way tie of thread 1023", "distances falling with the index", "two owners alternating",
+              "exclude_last through a group of eight", "the last row alone", "the last eligible row alone")
+
+
+def topk_rows():
+    """-> (rows uint16 [17000, 384], cases). Random rows with the rows of six cases planted among them, each case around a random
+    query of its own, so that the rows of the other cases are as far from it as random rows are (about 384 * 21 845; the planted
+    ones are within 16). cases: name -> (query, k, exclude_last, head), head = the first records by hand as [(distance, index)];
+    what follows the head, if anything, are random rows and comes from the references."""
+    rng = np.random.default_rng(1717)
+    n = TOPK_ROWS
+    rows = rng.integers(0, 65536, (n, WORDS), dtype=np.uint16)
+    cases = {}
+
+    def query():
+        return rng.integers(1000, 60000, WORDS, dtype=np.uint16)
+
+    def near(q, d):
+        r = q.copy()
+        r[int(rng.integers(0, WORDS))] += d    # one word, d above: distance d
+        return r
+
+    # sixteen copies of the query, all one thread's: a 16-way tie, won in index order by rescanning above the last winner
+    for t in (5, 1023):
+        q = query()
+        own = [t + 1024 * u for u in range(16)]
+        rows[own] = q
+        cases[f"16-way tie of thread {t}"] = (q, 16, 0, [(0, i) for i in own])
+    # the same thread's rows at distances that fall with u: the winners walk backwards through the owner's rows
+    q = query()
+    for u in range(16):
+        rows[7 + 1024 * u] = near(q, 16 - u)
+    cases["distances falling with the index"] = (q, 16, 0, [(16 - u, 7 + 1024 * u) for u in range(15, -1, -1)])
+    # two owners taking turns in a tie
+    q = query()
+    own = [9 + (u & 1) + 1024 * u for u in range(16)]
+    rows[own] = q
+    cases["two owners alternating"] = (q, 16, 0, [(0, i) for i in own])
+    # exclude_last cuts through one group of eight of thread 100's second scan iteration: rows 100 + 1024 u, u = 8 .. 15, are
+    # copies; eligible = 100 + 1024 * 13, so u = 8 .. 12 count and u = 13 (the row AT eligible), 14 and 15 do not
+    q = query()
+    rows[[100 + 1024 * u for u in range(8, 16)]] = q
+    eligible = 100 + 1024 * 13
+    cases["exclude_last through a group of eight"] = (q, 16, n - eligible, [(0, 100 + 1024 * u) for u in range(8, 13)])
+    # the last eligible row as the only match: the last row of all, and the last one in front of a cut that hides a copy behind it
+    q = query()
+    rows[n - 1] = q
+    cases["the last row alone"] = (q, 16, 0, [(0, n - 1)])
+    q = query()
+    rows[[12345, 12346]] = q
+    cases["the last eligible row alone"] = (q, 16, n - 12346, [(0, 12345)])
+    assert tuple(cases) == TOPK_CASES
+    return rows, cases
 
 
 def extreme_rows():

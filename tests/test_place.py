@@ -228,6 +228,124 @@ def test_query_rows_differing_in_one_word(backend):
     assert got == [(0, 8)] + [(r + 1, r) for r in range(8)], got
 
 
+# ---- the block table: every row is some query's answer --------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def block_rows():
+    rows = PC.block_table()
+    rows.setflags(write=False)
+    return rows
+
+
+def _blocks_to_try(eligible):
+    last = (eligible - 1) // PC.BLOCK
+    return sorted({j for j in (0, 1, last // 2, last - 1, last) if 0 <= j <= last})
+
+
+def test_block_table_closed_form_against_the_restatement(block_rows):
+    """the closed form of tests/place_cases.py equals place_ref.query at every eligible count the GPU tests use (and at 17, inside
+    the second block), for the first two blocks, a middle one and the last two - the last is cut wherever the count is no multiple
+    of 16 - and every row is in the top 16 of its own block's query: the queries together name every eligible row"""
+    assert block_rows.shape == (65536, 384) and int(block_rows.max()) == 65520
+    assert len(np.unique(block_rows[:, :2].astype(np.int64) @ np.array([65536, 1]))) == 65536   # the first two words name the row
+    for eligible in (17,) + PC.BLOCK_ELIGIBLE:
+        ex = PC.BLOCK_ROWS - eligible
+        for j in _blocks_to_try(eligible):
+            want = R.query(block_rows, PC.block_query(j), 16, ex)
+            assert PC.block_top(eligible, j) == want, (eligible, j, PC.block_top(eligible, j), want)
+            for k in (1, 4):
+                assert PC.block_top(eligible, j, k) == want[:k]
+        named = set()
+        for j in range(-(-eligible // PC.BLOCK)):
+            named.update(i for _, i in PC.block_top(eligible, j))
+        assert named == set(range(eligible)), eligible
+    full = PC.block_top(65536, 4095)
+    assert full == [(192 * r, 65520 + r) for r in range(16)]
+    assert PC.block_top(8189, 511) == [(192 * r, 8176 + r) for r in range(13)] + [(3072 + 192 * r, 8160 + r) for r in range(3)]
+    assert PC.block_top(17, 1)[:3] == [(0, 16), (3072, 0), (3264, 1)]
+
+
+@pytest.mark.parametrize("eligible,j", [(65536, 4095), (65535, 4095), (24577, 1536), (8193, 512), (40000, 1234)])
+def test_block_table_closed_form_against_the_hook(backend, block_rows, eligible, j):
+    """a handful only: the hook recomputes every distance in every round"""
+    got = backend.place_query_host(block_rows, PC.block_query(j), 16, PC.BLOCK_ROWS - eligible)
+    assert [(m.distance, m.index) for m in got] == PC.block_top(eligible, j)
+
+
+def test_launch_arithmetic_of_the_sizes():
+    """what each eligible count of the block-table tests reaches in k_place_dist (waves; unrolled passes and tail rounds of wave 0
+    and of the last wave) and in plc_scan (outer iterations), from the restatement of the launch arithmetic in
+    tests/place_cases.py: kPlcDistBlocks = 2048, kPlcUnroll = 4, plc_scan's 8 * 1024"""
+    assert (PC.PLC_DIST_BLOCKS, PC.PLC_UNROLL, PC.PLC_SCAN_STEP) == (2048, 4, 8 * 1024)
+    text = open(os.path.join(ROOT, "rebvio_amd", "csrc", "track.hip")).read()
+    assert "constexpr int kPlcUnroll = 4;" in text and "constexpr int kPlcDistBlocks = 2048;" in text
+    assert "for (int e = tid; e < eligible; e += 8 * 1024)" in text and "__launch_bounds__(1024) void k_place_topk" in text
+
+    def shape(eligible):
+        waves = PC.dist_waves(eligible)
+        first, last = PC.dist_wave_shape(eligible, 0)[:2], PC.dist_wave_shape(eligible, waves - 1)[:2]
+        return waves, first, last
+
+    # every row is some wave's, once
+    for eligible in PC.BLOCK_ELIGIBLE + (4200, PC.TOPK_ROWS):
+        waves = PC.dist_waves(eligible)
+        seen = np.zeros(eligible, np.int64)
+        for w in range(waves):
+            np.add.at(seen, PC.dist_wave_shape(eligible, w)[2], 1)
+        assert (seen == 1).all(), eligible
+    # what the suite had: 4200 rows are as many rows as waves - one row per wave through the tail loop, no stride, no unrolled pass -
+    # and at most five rows per thread of k_place_topk in one outer iteration
+    assert shape(4200) == (4200, (0, 1), (0, 1)) and PC.scan_shape(4200, 0) == (1, 5) and PC.scan_shape(4200, 1023) == (1, 4)
+    # the cap of 2048 workgroups: 2047 of them, then 2048 with the last three waves idle
+    assert shape(8188) == (8188, (0, 1), (0, 1))
+    assert shape(8189) == (8192, (0, 1), (0, 0))
+    # the last size with one row per wave; then the tail loop's first stride and plc_scan's first second iteration, thread 0 alone
+    assert shape(8192) == (8192, (0, 1), (0, 1)) and PC.scan_shape(8192, 0) == (1, 8)
+    assert shape(8193) == (8192, (0, 2), (0, 1))
+    assert PC.scan_shape(8193, 0) == (2, 9) and PC.scan_shape(8193, 1) == (1, 8)
+    # three tail rounds and no unrolled pass; then wave 0 alone takes one, over rows 0, 8192, 16 384, 24 576
+    assert shape(24576) == (8192, (0, 3), (0, 3))
+    assert shape(24577) == (8192, (1, 0), (0, 3)) and PC.dist_wave_shape(24577, 0)[2] == [0, 8192, 16384, 24576]
+    assert PC.dist_wave_shape(24577, 1)[:2] == (0, 3)
+    # exactly one unrolled pass each and no tail; plus one tail row
+    assert shape(32768) == (8192, (1, 0), (1, 0))
+    assert shape(32769) == (8192, (1, 1), (1, 0))
+    # one unrolled pass, a tail for the waves below 7232 only
+    assert shape(40000) == (8192, (1, 1), (1, 0))
+    assert PC.dist_wave_shape(40000, 7231)[:2] == (1, 1) and PC.dist_wave_shape(40000, 7232)[:2] == (1, 0)
+    # the second unrolled pass begins
+    assert shape(57344) == (8192, (1, 3), (1, 3))
+    assert shape(57345) == (8192, (2, 0), (1, 3))
+    # the envelope: at 65 535 the last wave falls out of its second pass into three tail rounds
+    assert shape(65535) == (8192, (2, 0), (1, 3))
+    assert shape(65536) == (8192, (2, 0), (2, 0))
+    assert PC.scan_shape(65536, 0) == PC.scan_shape(65536, 1023) == (8, 64)
+    assert PC.scan_shape(65535, 1023) == (8, 63)
+    # the top-k table: thread 5 scans 17 rows in three outer iterations, thread 1023 16 rows in two
+    assert PC.scan_shape(PC.TOPK_ROWS, 5) == (3, 17) and PC.scan_shape(PC.TOPK_ROWS, 1023) == (2, 16)
+    assert PC.scan_shape(PC.TOPK_ROWS, 615) == (3, 17) and PC.scan_shape(PC.TOPK_ROWS, 616) == (2, 16)
+    assert shape(PC.TOPK_ROWS) == (8192, (0, 3), (0, 2))
+
+
+def test_topk_cases_by_hand_and_against_both_references(backend):
+    """the rows planted for k_place_topk (tests/place_cases.py::topk_rows): the hook and the restatement agree on every record and
+    begin with the records stated by hand; what follows a head is a random row, far away"""
+    rows, cases = PC.topk_rows()
+    assert rows.shape == (PC.TOPK_ROWS, 384) and len(cases) == 7
+    for name, (q, k, ex, head) in cases.items():
+        got = both_query(backend, rows, q, k, ex)
+        assert got[:len(head)] == head, (name, got, head)
+        assert len(got) == 16 and all(i < PC.TOPK_ROWS - ex for _, i in got), name
+        assert all(d > 1000000 for d, _ in got[len(head):]), (name, got)
+        for kk in (1, 4):
+            assert both_query(backend, rows, q, kk, ex) == got[:kk], name
+    # the row at the cut and the copies behind it exist and are not eligible
+    q, k, ex, head = cases["exclude_last through a group of eight"]
+    eligible = PC.TOPK_ROWS - ex
+    assert eligible == 100 + 1024 * 13 and all(np.array_equal(rows[100 + 1024 * u], q) for u in range(8, 16))
+    q, k, ex, head = cases["the last eligible row alone"]
+    assert np.array_equal(rows[PC.TOPK_ROWS - ex], q) and head == [(0, PC.TOPK_ROWS - ex - 1)]
+
+
 # ---- what it buys --------------------------------------------------------------------------------------------------------------------
 def _oracle_sigs(orc_mod, backend, cam, scene, ts, seed_add):
     """signatures of the maps a fresh oracle, warmed by three detections of its first frame, detects at the times ts"""

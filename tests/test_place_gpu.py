@@ -3,8 +3,11 @@
 Maps are crafted through rebvio_hip_map_upload (a context of keylines_max = n detects exactly n keylines on a checkerboard frame; the
 upload then replaces them), database rows are planted through rebvio_hip_place_db_add_signature. Every word the device leaves - the
 384 signature words, counted, each result record - is compared with the hooks (rebvio_hip_test_place_signature_host / _query_host,
-the same statements), which tests/test_place.py holds against the numpy restatement of the header."""
+the same statements), which tests/test_place.py holds against the numpy restatement of the header. The tests at the end run where
+the kernels' loops iterate - databases of 8188 .. 65 536 eligible rows against a closed form that names every row, 17 000 rows with
+ties planted inside one thread's share of k_place_topk, a map of 65 536 keylines."""
 import ctypes as C
+import time
 
 import numpy as np
 import pytest
@@ -13,7 +16,7 @@ import place_cases as PC
 import place_ref as R
 from conftest import params_for
 from support import B  # noqa: F401
-from support import F32, KW_TRACK, vision_only_fusion
+from support import F32, KW_TRACK, noise_frames, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
 
@@ -200,8 +203,10 @@ def test_database_geometry(B, cap):
 
 
 def test_rows_differing_in_one_word_and_many_rows(B):
-    """word 0, 5, 6 and 383 - the ends of lane 0, the start of lane 1, the end of lane 63; then 4200 rows: more rows than the waves
-    of one pass of k_place_dist's unrolled loop at this size, and more than the 1024 threads of k_place_topk"""
+    """word 0, 5, 6 and 383 - the ends of lane 0, the start of lane 1, the end of lane 63; then 4200 rows: 1050 workgroups of
+    k_place_dist, so as many waves as rows - one row per wave, through the tail loop, which never takes its stride, and no pass of
+    the unrolled loop - and up to five rows per thread of k_place_topk, in one outer iteration of its scan. The sizes at which
+    those loops iterate are the block-table and top-k tests at the end of this file."""
     rng = np.random.default_rng(6)
     ctx = sized_ctx(B, 1)
     db = ctx.place_db(4200)
@@ -330,3 +335,158 @@ def test_launches_and_lifetime(B):
     for x in (m, m0):
         x.release()
     assert B.test_live_resources() == live
+
+
+# ---- where the query's loops iterate: up to 65 536 rows -------------------------------------------------------------------------------
+def as_records(matches):
+    return [(m.distance, m.index, m.tag) for m in matches]
+
+
+@pytest.fixture(scope="module")
+def block_db(B):
+    """one database of capacity 65 536 holding tests/place_cases.py's block table; a test chooses the eligible count through
+    exclude_last, so one fill serves every size"""
+    ctx = sized_ctx(B, 1)
+    db = ctx.place_db(PC.BLOCK_ROWS)
+    rows = PC.block_table()
+    t0 = time.perf_counter()
+    for i in range(PC.BLOCK_ROWS):
+        db.add_signature(rows[i], counted=i, tag=PC.block_tag(i))
+    print(f"block_db: {PC.BLOCK_ROWS} add_signature calls in {time.perf_counter() - t0:.2f} s")
+    assert db.size() == PC.BLOCK_ROWS
+    for i in (0, 8191, 8192, 40000, 65535):
+        sig, counted, tag = db.entry(i)
+        assert np.array_equal(sig, rows[i]) and counted == i and tag == PC.block_tag(i), i
+    yield db
+    db.release()
+    ctx.close()
+
+
+def sweep_blocks(db, eligible, blocks, k=16):
+    ex = PC.BLOCK_ROWS - eligible
+    for j in blocks:
+        got = as_records(db.query_signature(PC.block_query(j), k, ex))
+        want = [(d, i, PC.block_tag(i)) for d, i in PC.block_top(eligible, j, k)]
+        assert got == want, (eligible, j, k, got, want)
+
+
+def test_every_row_of_a_full_database(B, block_db):
+    """65 536 eligible rows: every wave of k_place_dist takes two unrolled passes and no tail, every thread of k_place_topk scans 64
+    rows in eight outer iterations. The 4096 queries of the block table return every row once - distance, index and tag of every
+    record against the closed form - so a wrong dist[e] of any row shows."""
+    waves = PC.dist_waves(65536)
+    assert waves == 8192 and PC.dist_wave_shape(65536, 0)[:2] == PC.dist_wave_shape(65536, waves - 1)[:2] == (2, 0)
+    named = []
+    for j in range(4096):
+        got = as_records(block_db.query_signature(PC.block_query(j), 16))
+        assert got == [(192 * r, 16 * j + r, PC.block_tag(16 * j + r)) for r in range(16)], (j, got)
+        assert [(d, i) for d, i, _ in got] == PC.block_top(65536, j)
+        named += [i for _, i, _ in got]
+    assert named == list(range(65536))
+
+
+@pytest.mark.parametrize("eligible", [e for e in PC.BLOCK_ELIGIBLE if e != 65536])
+def test_every_eligible_row_at_the_sizes_where_the_loops_change(B, block_db, eligible):
+    """the eligible counts of tests/place_cases.py::BLOCK_ELIGIBLE (what each reaches in k_place_dist and plc_scan is asserted by
+    tests/test_place.py::test_launch_arithmetic_of_the_sizes): every query whose block holds an eligible row, every record against
+    the closed form; at the first, a middle and the last two blocks k = 1 and k = 4 return the prefix of k = 16"""
+    last = (eligible - 1) // PC.BLOCK
+    sweep_blocks(block_db, eligible, range(last + 1))
+    for k in (1, 4):
+        sweep_blocks(block_db, eligible, sorted({0, last // 2, last - 1, last}), k)
+    # no row at or past the cut comes back, whatever is asked
+    for j in (last, min(last + 1, 4095), 4095):
+        got = block_db.query_signature(PC.block_query(j), 16, PC.BLOCK_ROWS - eligible)
+        assert len(got) == 16 and all(m.index < eligible for m in got), (eligible, j)
+
+
+@pytest.fixture(scope="module")
+def topk_db(B):
+    ctx = sized_ctx(B, 1)
+    db = ctx.place_db(PC.TOPK_ROWS)
+    rows, cases = PC.topk_rows()
+    for i in range(PC.TOPK_ROWS):
+        db.add_signature(rows[i], tag=PC.block_tag(i))
+    want = {name: B.place_query_host(rows, q, k, ex) for name, (q, k, ex, _) in cases.items()}   # once, for every test below
+    yield db, cases, want
+    db.release()
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", PC.TOPK_CASES)
+def test_one_thread_wins_round_after_round(B, topk_db, name):
+    """17 000 rows: thread t of k_place_topk owns 16 or 17 rows over two or three outer iterations of plc_scan. The planted rows of
+    tests/place_cases.py::topk_rows - a 16-way tie owned by thread 5 and by thread 1023, which must win 16 rounds in a row by
+    scanning above its own last winner; distances falling with the index, so that the winners walk backwards through the owner's
+    rows; two owners alternating in a tie; exclude_last cutting through one group of eight, the copy at the cut and the two behind
+    it not returned; the last (eligible) row as the only match - every record against the hook and against the list by hand"""
+    db, cases, hook = topk_db
+    q, k, ex, head = cases[name]
+    got = db.query_signature(q, k, ex)
+    want = hook[name]
+    assert as_pairs(got) == as_pairs(want), (name, as_pairs(got), as_pairs(want))
+    assert [m.tag for m in got] == [PC.block_tag(m.index) for m in want]
+    assert as_pairs(got)[:len(head)] == head, (name, as_pairs(got), head)
+    assert len(got) == 16 and all(m.index < PC.TOPK_ROWS - ex for m in got)
+    for kk in (1, 4):
+        assert as_pairs(db.query_signature(q, kk, ex)) == as_pairs(got)[:kk], (name, kk)
+
+
+def test_signature_at_the_envelope_of_65536_keylines(B):
+    """keylines_max = 65 536 on a 640 x 896 noise frame: 256 workgroups of k_place_hist add into one global histogram. The detected
+    keylines as they come, a random table with hostile values, all 65 536 in one word (every workgroup's full LDS count into one
+    global word), 65 535 in one word and one in another ((65535 * 65535) // 65536 = 65534 and 65535 // 65536 = 0), one keyline
+    of 65 536 uncounted; then maps of the same context that hold few and no keylines, where the workgroups past the size add nothing.
+    Every word against the hook and against the numpy restatement."""
+    rows, cols = 640, 896
+    ctx = B.Context(B.default_params(rows, cols, fm=500.0, cx=447.5, cy=319.5, keylines_ref=60000, keylines_max=65536))
+    m = ctx.detect_u8(noise_frames(cols, rows, 1, 3)[0], 0)
+    assert m.size() == 65536
+
+    def against_numpy(m, kl, what):
+        want, want_n = R.signature(rows, cols, kl)
+        got, got_n = m.place_signature()
+        assert got_n == want_n, (what, got_n, want_n)
+        assert np.array_equal(got, want), (what, np.flatnonzero(got != want)[:8])
+        return got, got_n
+
+    kl = m.keylines()
+    sig, n = check_signature(B, m, kl, "detected")
+    against_numpy(m, kl, "detected")
+    assert n == 65536 and np.count_nonzero(sig) > 256
+    rng = np.random.default_rng(65536)
+    kl = PC.random_table(rng, rows, cols, 65536)
+    sig, n = check_signature(B, m, kl, "random table")
+    against_numpy(m, kl, "random table")
+    assert 40000 < n < 65536 and np.count_nonzero(sig) == 384
+    # by hand
+    kl, w = PC.one_word(65536, rows, cols)
+    sig, n = check_signature(B, m, kl, "one word")
+    assert n == 65536 and sig[w] == 65535 and np.count_nonzero(sig) == 1
+    two = kl.copy()
+    two["pos"][40000] = (0.0, 0.0)
+    two["gradient"][40000] = (1.0, 0.0)
+    sig, n = check_signature(B, m, two, "65535 and 1")
+    against_numpy(m, two, "65535 and 1")
+    assert n == 65536 and sig[w] == 65534 and sig[0] == 0 and np.count_nonzero(sig) == 1
+    for dead in (0, 255, 256, 65535):
+        one = kl.copy()
+        one["gradient_norm"][dead] = 0.0
+        sig, n = check_signature(B, m, one, f"keyline {dead} uncounted")
+        assert n == 65535 and sig[w] == 65535 and np.count_nonzero(sig) == 1
+    # the same context, maps well under its keylines_max
+    step = np.full((rows, cols), 20, np.uint8)
+    step[:, cols // 2:] = 220
+    sizes = []
+    for ts, frame in ((50000, step), (100000, np.full((rows, cols), 128, np.uint8))):
+        few = ctx.detect_u8(frame, ts)
+        kl = few.keylines()
+        sizes.append(len(kl))
+        assert len(kl) == few.size() < 65536 - 256
+        want, want_n = B.place_signature_host(rows, cols, kl)
+        got, got_n = against_numpy(few, kl, f"{len(kl)} keylines")
+        assert got_n == want_n and np.array_equal(got, want)
+        few.release()
+    assert sizes[0] > 256 and sizes[1] == 0 and got_n == 0 and not got.any(), sizes   # (one edge down the middle: about 1300)
+    m.release()
+    ctx.close()
