@@ -127,6 +127,9 @@ void rebvio_hip_default_params(rebvio_hip_params* p, int rows, int cols);
  * Also -3: search_range > 255 or search_range + 2 * pixel_uncertainty_match >= 258 (per-wave probe sequence buffer),
  * quantile_num_bins outside 1..128, keylines_max * 2 * search_range >= 2^23 (distance-field key encoding),
  * keylines_max outside 1..65536 (the LM reduction stages at most 256 record groups of 256 keylines in LDS).
+ * Also -3, here and in rebvio_hip_batch_create, before a device is queried: a search_range that is not a whole number of pixels.
+ * The field kernels walk r over [-(int)search_range, (int)search_range); the reference's loop runs up to the float itself
+ * (core.hpp:49) and takes one step more for a fractional range, so only whole numbers give the reference's field.
  * Also -3 (rebvio_hip_last_error names the fields), checked with the rest before a device is queried, here and in
  * rebvio_hip_batch_create: detection parameters whose gradient gate cannot reject a zero gradient. The gate keeps a candidate
  * unless g2 < (thr * 765 * dog_threshold)^2 (edge_detector.cpp:70,107), and the lowest thr the servo hands it is

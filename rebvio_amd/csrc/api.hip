@@ -1317,8 +1317,21 @@ static int check_detection_params(const rebvio_hip_params* p) {
   return 0;
 }
 
+// The field kernels walk r in [-(df_nr >> 1), df_nr >> 1) with df_nr = 2 * (int)search_range: the half is the truncated range on
+// both sides. The reference walks `for (int r = -search_range_; r < search_range_; ++r)` with the float itself as the upper bound
+// (core.hpp:49), one step more for a fractional range (7.5: r = -7 .. 7 against -7 .. 6). The two agree for a whole number only, so
+// anything else is refused here, before any device is touched. (A float of 2^23 or more has no fraction; the size checks take it.)
+static int check_search_range(const rebvio_hip_params* p) {
+  const float s = p->search_range;
+  if (!std::isfinite(s) || (std::fabs(s) < 8388608.0f && s != (float)(int)s))
+    return fail_msg("search_range must be a whole number of pixels (the distance field of a fractional range would miss the "
+                    "reference's last step)", -3);
+  return 0;
+}
+
 int rebvio_hip_create(const rebvio_hip_params* p, rebvio_hip_ctx** out) {
   *out = nullptr;
+  if (int rc = check_search_range(p)) return rc;
   if (p->rows < 32 || p->cols < 32) return fail_msg("rows/cols must be >= 32", -3);
   if (p->cols > 4096) return fail_msg("cols > 4096 unsupported", -3);
   if ((size_t)(p->rows + 12) * 16 * sizeof(float) > 160 * 1024 || (size_t)(p->cols + 3 + 8) * 4 * sizeof(float) > 160 * 1024)
@@ -5396,6 +5409,7 @@ void rebvio_hip_batch_destroy(rebvio_hip_batch* b) {
 int rebvio_hip_batch_create(const rebvio_hip_params* p, int lanes, rebvio_hip_batch** out) {
   *out = nullptr;
   if (lanes < 1 || lanes > kMaxLanes) return fail_msg("batch: lanes must be in 1..16", -3);
+  if (int rc = check_search_range(p)) return rc;
   if (int rc = check_detection_params(p)) return rc;
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));

@@ -3,7 +3,7 @@ in numpy, the ranking restated in Python, and small builders for hypothesis and 
 kf_align_ref.py: no test lives here and importing it needs no GPU."""
 import numpy as np
 
-from kf_align_ref import _residual, np_kf_align_sums
+from kf_align_ref import _residual, cam_of, current_data, np_kf_align_sums  # noqa: F401  (cam_of / current_data: handed on to the device tests)
 from kf_pose_ref import DEFAULT_FILTER
 from support import F32
 
@@ -94,18 +94,6 @@ def stream():
         from rebvio_amd import synth
         _STREAM["s"] = synth.render_stream(W, H, NF)
     return _STREAM["s"]
-
-
-def cam_of(ctx):
-    return (ctx.p.fm, ctx.p.cx, ctx.p.cy, ctx.rows, ctx.cols)
-
-
-def current_data(mc):
-    """what the restatement is given of the current map: pos, unit, the field - downloaded"""
-    from kf_align_ref import unit_of
-    kl = mc.keylines()
-    ids, dists = mc.distance_field()
-    return kl, (np.ascontiguousarray(kl["pos"]), unit_of(kl), ids.reshape(-1), dists.reshape(-1))
 
 
 class Scene800:

@@ -87,6 +87,37 @@ def test_envelope_corners_pass_the_parameter_check(backend):
             assert "error -3:" not in str(e.value), str(e.value)
 
 
+def test_a_fractional_search_range_is_refused(backend):
+    """rebvio_hip_create and rebvio_hip_batch_create return -3, before any device is queried, for a search_range that is no whole
+    number of pixels: the field kernels walk r over [-(int)search_range, (int)search_range), the reference up to the float itself
+    (core.hpp:49) - one step more (tests/test_context_geometry.py pins the difference on the oracle). Whole numbers get past
+    validation: without a device create fails at the device query that follows it, not with -3."""
+    import ctypes as C
+    import torch
+    L = backend.lib()
+    kw = dict(keylines_max=2000, keylines_ref=1500)
+    for sr in (7.5, 40.5, 0.5):
+        p = backend.default_params(144, 192, search_range=sr, **kw)
+        h = C.c_void_p()
+        for rc in (L.rebvio_hip_create(C.byref(p), C.byref(h)), L.rebvio_hip_batch_create(C.byref(p), 2, C.byref(h))):
+            msg = L.rebvio_hip_last_error().decode()
+            assert rc == -3 and not h.value, (sr, rc, msg)
+            assert "search_range" in msg and "whole number of pixels" in msg, (sr, msg)
+        with pytest.raises(backend.HipError) as e:
+            backend.Context(p)
+        assert "error -3:" in str(e.value), (sr, str(e.value))
+    for sr, more in ((7.0, {}), (255.0, dict(pixel_uncertainty_match=1.0))):
+        p = backend.default_params(144, 192, search_range=sr, **kw, **more)
+        if torch.cuda.is_available():
+            backend.Context(p).close()
+            backend.Batch(p, 2).close()
+        else:
+            for make in (lambda: backend.Context(p), lambda: backend.Batch(p, 2)):
+                with pytest.raises(backend.HipError) as e:
+                    make()
+                assert "error -3:" not in str(e.value), (sr, str(e.value))
+
+
 # detection parameters whose gradient gate, !(g2 < (thr * 765 * dog_threshold)^2), cannot reject a zero gradient at the lowest
 # threshold the servo can reach; and non-finite or negative ones. (fields to set, words the error has to name)
 _NAN = float("nan")

@@ -20,7 +20,8 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from kf_align_ref import GUARD, OFFSETS, craft_against, craft_kf_keylines, np_kf_align, np_kf_align_sums, offset_guess, unit_of
+from kf_align_ref import (DEV_VS_NP, GUARD, OFFSETS, assert_evaluation, cam_of, craft_against, craft_kf_keylines, current_data, data_of, np_kf_align,
+                          np_kf_align_sums, offset_guess, same_bytes, unit_of)
 from kf_pose_ref import pose_err, pose_sums, true_motion
 from support import B  # noqa: F401
 from support import F32, TS, assert_keylines_equal, enlarged_stream, rec, rodrigues, same_records, vision_only_fusion
@@ -30,21 +31,12 @@ pytestmark = pytest.mark.gpu
 W, H, NF = 160, 120, 10
 KW_FULL = dict(keylines_ref=1200, keylines_max=1601, global_min_matches_threshold=1)
 KW_STREAM = dict(keylines_ref=600, keylines_max=800, global_min_matches_threshold=50)      # the stream of the pose tests: every pair tracks
-# |device - numpy| over R and t of the solves of test_solve_from_the_offsets - measured maximum on an MI355X: 2.22e-16 (device sin /
-# cos and the Cholesky order differ from numpy's by a few ulp, amplified by cond(H) of 17); the bound is 100 x that. It has to stay
-# <= 0.1 x the restatement's own error from the crafted motion (1.09e-9 at the least), which the test asserts as a condition. (The
-# displaced-keyline solves and the re-acquisition, held to the same bound, measured 2.22e-16 and 1.8e-16 at most.)
-DEV_VS_NP = 2.22e-14
 
 
 @functools.lru_cache(maxsize=None)
 def stream():
     from rebvio_amd import synth
     return synth.render_stream(W, H, NF)
-
-
-def cam_of(ctx):
-    return (ctx.p.fm, ctx.p.cx, ctx.p.cy, ctx.rows, ctx.cols)
 
 
 def sized_maps(B, n, count=2):
@@ -58,13 +50,6 @@ def sized_maps(B, n, count=2):
         maps = [ctx.detect_u8(frames[1 + k], k * TS) for k in range(count)]
     assert all(m.size() == n for m in maps), (n, [m.size() for m in maps])
     return ctx, maps
-
-
-def current_data(mc):
-    """what the restatement is given of the current map: pos, unit, the field - downloaded"""
-    kl = mc.keylines()
-    ids, dists = mc.distance_field()
-    return kl, (np.ascontiguousarray(kl["pos"]), unit_of(kl), ids.reshape(-1), dists.reshape(-1))
 
 
 def snapshot_of(mk, kf_keylines):
@@ -89,38 +74,6 @@ def crafted_scene(B, n=None, seed=1, displaced=0.0):
     base["matches"] = 0
     snap = snapshot_of(mk, craft_kf_keylines(base, A, min(len(A["prs4"]), len(base))))
     return ctx, mk, mc, snap, data_of(ctx, snap, cur), A
-
-
-def data_of(ctx, snap, cur, normals=True):
-    prs4, mt = snap.download()
-    return (cam_of(ctx), prs4, mt, snap.normals() if normals else None, *cur)
-
-
-def same_bytes(a, b):
-    return bytes(a) == bytes(b)
-
-
-def np_kw(opts):
-    return {("huber" if k == "huber_px" else k): v for k, v in opts.items()}
-
-
-def assert_evaluation(B, ctx, mc, snap, D, R, t, what, **opts):
-    """one evaluation (max_iter 0) at (R, t): the restatement's guards, assoc element for element, the 28 sums within the bound, the
-    pose untouched, a second call equal in every byte"""
-    S, absS, used, assoc, g = np_kf_align_sums(*D, R, t, **np_kw(opts))
-    assert min(g.values()) > GUARD, (what, g)
-    o = B.default_kf_align_opts(ctx, max_iter=0, **opts)
-    got, a = mc.keyframe_align(snap, o, R, t, want_assoc=True)
-    assert np.array_equal(a, assoc), (what, np.flatnonzero(a != assoc)[:8], a[a != assoc][:8], assoc[a != assoc][:8])
-    assert got.used == used and got.candidates == len(D[1]) and got.iterations == 0, (what, got.used, used, got.candidates)
-    assert got.status == (3 if used < 12 else 0)
-    assert np.array_equal(np.array(got.R), np.asarray(R, np.float64).reshape(9)) and np.array_equal(np.array(got.t), np.asarray(t, np.float64))
-    d = np.abs(pose_sums(got) - S)
-    bound = (used + 64) * 2.0 ** -52 * absS
-    assert (d <= bound).all(), (what, np.flatnonzero(d > bound), d[d > bound], bound[d > bound])
-    again, a2 = mc.keyframe_align(snap, o, R, t, want_assoc=True)
-    assert same_bytes(got, again) and np.array_equal(a, a2), what
-    return used
 
 
 def random_guess(seed):
