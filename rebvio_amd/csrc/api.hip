@@ -32,6 +32,7 @@
 #include "owned.hpp"
 #include "pixel_format.hpp"
 #include "place.hpp"
+#include "scratch_layout.hpp"
 #include "stereo_prior.hpp"
 
 using namespace rh;
@@ -108,6 +109,12 @@ int fail_msg(const char* what, int code) {
   do {                                        \
     hipError_t _e = (expr);                   \
     if (_e != hipSuccess) return fail(#expr, _e); \
+  } while (0)
+// the same for a callee that has already set g_err and returns the entry's code
+#define RCCHK(expr)            \
+  do {                         \
+    const int _rc = (expr);    \
+    if (_rc) return _rc;       \
   } while (0)
 
 // ---- profiler ------------------------------------------------------------------------------------
@@ -548,70 +555,26 @@ struct rebvio_hip_ctx {
   int* cloud_scratch = nullptr;  // [kMaxRecBlocks] counts, then the ticket word
   hipStream_t s_cloud{};         // the copies to the host: PCIe writes next to the track stream's kernels, not between them
   unsigned cloud_seq = 0;
-  // keyframes: rebvio_hip_keyframe_next is pending for the next frame pushed; scratch of rebvio_hip_map_keyframe_matches (allocated
-  // on first use, kept; only that entry, a track-side one, uses it): the slot table - ceil(keylines_max / 256) * 256 winner keys,
-  // as many claimant counts, then kMaxRecBlocks block counts and the record count - and keylines_max records.
+  // keyframes: rebvio_hip_keyframe_next is pending for the next frame pushed
   bool kf_pending = false;
-  unsigned long long* kf_key = nullptr;
-  int* kf_claimants = nullptr;  // (views into kf_key's allocation)
-  int* kf_blk = nullptr;
-  rebvio_hip_kf_match* kf_rec = nullptr;
-  // keyframe snapshots that are out (snap_mu: rebvio_hip_kf_snapshot_release may come from any thread), and the scratch of
-  // rebvio_hip_map_keyframe_pose (allocated on first use, kept; a track-side entry): the result block the kernels iterate on,
-  // then kMaxRecBlocks partials of 28 doubles and as many used counts
+  // keyframe snapshots and place databases that are out (their mutexes: a release may come from any thread)
   std::mutex snap_mu;
   std::vector<rebvio_hip_kf_snapshot*> snaps;
-  rebvio_hip_kf_pose* kfp_state = nullptr;
-  double* kfp_part = nullptr;  // (views into kfp_state's allocation)
-  int* kfp_used = nullptr;
-  // scratch of rebvio_hip_map_keyframe_align (ONE allocation on first use, kept; a track-side entry): the result block, kMaxRecBlocks
-  // partials of 28 doubles, as many used counts, keylines_max association words
-  rebvio_hip_kf_pose* kfa_state = nullptr;
-  double* kfa_part = nullptr;  // (views into kfa_state's allocation)
-  int* kfa_used = nullptr;
-  int* kfa_assoc = nullptr;
-  // scratch of rebvio_hip_map_keyframe_align_many (ONE allocation on first use, kept; a track-side entry): REBVIO_HIP_KF_HYP_MAX
-  // descriptors, then as many result blocks (uploaded together), then per hypothesis kMaxRecBlocks partials of 28 doubles, used
-  // counts and inlier counts
-  KfHypDesc* kfm_desc = nullptr;
-  rebvio_hip_kf_hyp_result* kfm_res = nullptr;  // (views into kfm_desc's allocation)
-  double* kfm_part = nullptr;
-  int* kfm_used = nullptr;
-  int* kfm_inl = nullptr;
-  // scratch of rebvio_hip_kf_snapshot_fuse_depth (ONE allocation on first use, kept; a track-side entry): 8 count words (the six of
-  // rebvio_hip_kf_fuse in front), then keylines_max association words
-  int* kff_cnt = nullptr;
-  int* kff_assoc = nullptr;  // (a view into kff_cnt's allocation)
-  // scratch of rebvio_hip_kf_snapshot_handover_depth (ONE allocation on first use, kept; a track-side entry): keylines_max claim
-  // words, keylines_max 8-byte staging records, 8 count words (the seven of rebvio_hip_kf_handover in front), keylines_max
-  // association words
-  unsigned long long* kfh_key = nullptr;
-  void* kfh_stage = nullptr;  // (views into kfh_key's allocation)
-  int* kfh_cnt = nullptr;
-  int* kfh_assoc = nullptr;
-  // scratch of rebvio_hip_map_edge_chains / _edge_polylines (ONE allocation on first use, kept; track-side entries): views into it
-  char* ech_buf = nullptr;
-  ChainDev ech{};
-  // scratch of the depth-image entries (ONE device allocation on first use, kept; track-side entries): 8 count words (the six of
-  // rebvio_hip_depth_prior_counts in front), then keylines_max outcome words. dpr_pin: the host-image entry's pinned staging frame
-  // (rows * cols * 4 bytes, on ITS first use), which the kernel reads in place. dpr_queued: a fusion has been queued.
-  int* dpr_cnt = nullptr;
-  int* dpr_outcome = nullptr;  // (a view into dpr_cnt's allocation)
+  // Scratch of the on-demand entries, track-side ones all: each ONE device allocation made at the entry's first call and kept
+  // (scratch_layout.hpp states what lies where; ensure_scratch makes it). kf: the correspondences, with the records as a second
+  // allocation; kfp / kfa / kfm: the solves of keyframe_pose, _align and _align_many; kff / kfh: fuse_depth and handover_depth; ech:
+  // the edge chains and polylines; dpr / spr: the depth-image and stereo entries; plc: the place entries.
+  scratch::KfMatches kf;
+  scratch::KfSolve kfp, kfa;
+  scratch::KfMany<KfHypDesc> kfm;
+  scratch::Counted kff, dpr, spr;
+  scratch::KfHandover kfh;
+  scratch::Chains<ChainDev> ech;
+  scratch::Place plc;
+  // dpr_pin: the host-image entry's pinned staging frame (rows * cols * 4 bytes, on ITS first use), which the kernel reads in
+  // place. dpr_queued / spr_queued: a fusion has been queued.
   char* dpr_pin = nullptr;
-  bool dpr_queued = false;
-  // scratch of the stereo entries (ONE device allocation on first use, kept; track-side entries): 8 count words
-  // (rebvio_hip_stereo_prior_counts), then keylines_max outcome words, then keylines_max winner words. spr_queued: a fusion has
-  // been queued.
-  int* spr_cnt = nullptr;
-  int* spr_outcome = nullptr;  // (views into spr_cnt's allocation)
-  int* spr_winner = nullptr;
-  bool spr_queued = false;
-  // scratch of the place entries (ONE device allocation on first use, kept; track-side entries): 385 histogram words (padded to
-  // 388), then the query row of 384 u16 words, then its counted word. place_dbs: the databases that are out (place_mu:
-  // rebvio_hip_place_db_release may come from any thread).
-  unsigned* plc_hist = nullptr;
-  uint16_t* plc_query = nullptr;  // (views into plc_hist's allocation)
-  int* plc_counted = nullptr;
+  bool dpr_queued = false, spr_queued = false;
   std::mutex place_mu;
   std::vector<rebvio_hip_place_db*> place_dbs;
 };
@@ -627,17 +590,22 @@ inline void drop_carry(rebvio_hip_ctx* c) {
   c->carry = nullptr;
 }
 
-// A map handle whose context has been destroyed: every entry point that takes a map alone answers with this.
-inline bool map_dead(const rebvio_hip_map* m) { return !m || !m->life || m->life->dead.load(std::memory_order_acquire); }
-// Holds the life block (shared) for as long as it lives - declared at the top of an entry, for the rest of it: a rebvio_hip_destroy
-// on another thread waits until the entry has returned instead of freeing the context under it (the check alone would leave a
-// window between test and use). dead(): the context is gone already (g_err says so); the entry returns at once.
-class MapAlive {
+// what an entry answers (-10) with for a handle whose context is gone
+inline const char* gone_text(const rebvio_hip_map*) { return "the map's context has been destroyed (rebvio_hip_destroy)"; }
+inline const char* gone_text(const rebvio_hip_kf_snapshot*) { return "the snapshot's context has been destroyed (rebvio_hip_destroy)"; }
+inline const char* gone_text(const rebvio_hip_place_db*) { return "the place database's context has been destroyed (rebvio_hip_destroy)"; }
+// Holds the life block of a map, a snapshot or a place database (shared) for as long as it lives - declared at the top of an
+// entry, for the rest of it: a rebvio_hip_destroy on another thread waits until the entry has returned instead of freeing the
+// context under it (the check alone would leave a window between test and use). dead(): the context is gone already (g_err says
+// so); the entry returns -10 at once. A null handle, or one without a life block, counts as dead. say = false: a release, which
+// returns nothing and leaves the thread's message alone.
+class Alive {
  public:
-  explicit MapAlive(const rebvio_hip_map* m) : hold_(m ? m->life : nullptr) {
+  template <class Handle>
+  explicit Alive(const Handle* h, bool say = true) : hold_(h ? h->life : nullptr) {
     if (hold_) lock_ = std::shared_lock<std::shared_mutex>(hold_->mu);
-    dead_ = map_dead(m);
-    if (dead_) g_err = "the map's context has been destroyed (rebvio_hip_destroy)";
+    dead_ = !hold_ || hold_->dead.load(std::memory_order_acquire);
+    if (dead_ && say) g_err = gone_text(h);
   }
   bool dead() const { return dead_; }
 
@@ -646,6 +614,53 @@ class MapAlive {
   std::shared_lock<std::shared_mutex> lock_;
   bool dead_;
 };
+
+// Makes a feature's scratch at its first call: one allocation of exactly the bytes its layout measures (scratch_layout.hpp).
+template <class Layout, class... Args>
+int ensure_scratch(rebvio_hip_ctx* c, Layout& s, Args... args) {
+  if (s.base) return 0;
+  char* b = nullptr;
+  HIPCHK(c->own.device_bytes(&b, Layout().lay(nullptr, args...)));
+  s.lay(b, args...);
+  return 0;
+}
+
+// Snapshots and place databases are listed in their context. At rebvio_hip_destroy every listed handle is still out: its device
+// memory goes with the context, the host struct stays as a husk for its release to delete.
+template <class Handle, class Buffer>
+void leave_husks(std::vector<Handle*>& list, Buffer Handle::*first) {
+  for (Handle* h : list) {
+    h->own.release();
+    h->*first = nullptr;
+    h->ctx = nullptr;
+  }
+  list.clear();
+}
+
+// A listed handle's release. While the context lives: off the list (under the list's mutex: a release may come from any thread)
+// and its device memory freed (hipFree waits for the kernels that still use it); after rebvio_hip_destroy, which freed it: the husk.
+template <class Handle>
+void unlist_and_release(std::vector<Handle*> rebvio_hip_ctx::*list, std::mutex rebvio_hip_ctx::*mu, Handle* h) {
+  if (!h) return;
+  {
+    const Alive alive(h, false);
+    if (!alive.dead()) {
+      rebvio_hip_ctx* c = h->ctx;
+      (void)hipSetDevice(c->device);
+      {
+        std::lock_guard<std::mutex> sl(c->*mu);
+        auto& v = c->*list;
+        for (size_t i = 0; i < v.size(); ++i)
+          if (v[i] == h) {
+            v.erase(v.begin() + (std::ptrdiff_t)i);
+            break;
+          }
+      }
+      h->own.release();
+    }
+  }
+  delete h;
+}
 
 // events of a map may only be waited on once the batch's detect worker has recorded them
 inline void wait_enqueued(rebvio_hip_map* m) {
@@ -1554,18 +1569,8 @@ void rebvio_hip_destroy(rebvio_hip_ctx* c) {
     free_cloud_device(cl);
     if (!cl->in_use) delete cl;  // (else: the handle is still out; its release deletes the husk)
   }
-  for (auto* sn : c->snaps) {  // every listed snapshot is out: its release deletes the husk
-    sn->own.release();
-    sn->buf = nullptr;
-    sn->ctx = nullptr;
-  }
-  c->snaps.clear();
-  for (auto* db : c->place_dbs) {  // every listed database is out: its release deletes the husk
-    db->own.release();
-    db->rows = nullptr;
-    db->ctx = nullptr;
-  }
-  c->place_dbs.clear();
+  leave_husks(c->snaps, &rebvio_hip_kf_snapshot::buf);  // (every listed snapshot or database is out: its release deletes the husk)
+  leave_husks(c->place_dbs, &rebvio_hip_place_db::rows);
   c->own.release();
   delete c;
 }
@@ -1707,13 +1712,13 @@ int rebvio_hip_detector_state(rebvio_hip_ctx* c, float* threshold, float* auto_t
 }
 
 int rebvio_hip_map_size(rebvio_hip_map* m) {
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   if (ensure_size(m)) return -1;
   return m->n_host;
 }
 float rebvio_hip_map_threshold(rebvio_hip_map* m) {
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return std::numeric_limits<float>::quiet_NaN();
   if (ensure_size(m)) return std::numeric_limits<float>::quiet_NaN();
   return m->thr_host;
@@ -1721,7 +1726,7 @@ float rebvio_hip_map_threshold(rebvio_hip_map* m) {
 uint64_t rebvio_hip_map_ts(rebvio_hip_map* m) { return m->ts; }
 
 int rebvio_hip_map_download(rebvio_hip_map* m, rebvio_hip_keyline* keylines, int* mask) {
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));
@@ -1754,7 +1759,7 @@ int rebvio_hip_map_download(rebvio_hip_map* m, rebvio_hip_keyline* keylines, int
 }
 
 int rebvio_hip_render_edge_image(rebvio_hip_map* m, const uint8_t* gray, uint8_t* rgb_out) {
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));
@@ -1793,14 +1798,98 @@ int check_cloud_args(const char* who, const rebvio_hip_cloud_filter* f, const re
   return 0;
 }
 
-// Scratch of the keyframe correspondences (rebvio_hip_map_keyframe_matches, rebvio_hip_map_keyframe_pose), allocated on first use
+// ---- statements the on-demand entries share. `who` is the entry's name as its messages begin; every entry calls
+// them in the order it has always tested things in: that order decides which refusal wins when several apply. ----
+// -3: a handle (`what`: "map", "left map", "snapshot") that belongs to another live context than the one it is used with
+int other_context(const char* who, const char* what, const char* than = "") {
+  return fail_msg((std::string(who) + ": " + what + " of another context" + than).c_str(), -3);
+}
+// A snapshot or database handed in next to a live map m is of m's context: else -10 with the handle's own sentence when its
+// context is gone, -3 (other_context) when that is another live one.
+template <class Handle>
+int of_map_context(const char* who, const Handle* h, const rebvio_hip_map* m, const char* what, const char* than = "") {
+  if (h->life == m->life) return 0;
+  if (h->life->dead.load(std::memory_order_acquire)) return fail_msg(gone_text(h), -10);
+  return other_context(who, what, than);
+}
+int snapshot_of(const char* who, const rebvio_hip_kf_snapshot* sn, const rebvio_hip_map* m) { return of_map_context(who, sn, m, "snapshot"); }
+// -7: the entries that look keylines up in m's distance field need the one detection built, over keylines in detection's order
+int needs_detection_field(const char* who, const rebvio_hip_map* m) {
+  if (m->df_built && m->raster_order) return 0;
+  return fail_msg((std::string(who) + ": the map's distance field is not detection's (none was built, or its keylines were uploaded)").c_str(), -7);
+}
+// -3: a pose's nine and three doubles are finite. may_be_null: a guess (R0, t0), where null stands for identity / zero.
+int check_rt(const char* who, const double* R, const double* t, bool may_be_null) {
+  bool fin = true;
+  for (int i = 0; R && i < 9; ++i) fin = fin && std::isfinite(R[i]);
+  for (int i = 0; t && i < 3; ++i) fin = fin && std::isfinite(t[i]);
+  if (!fin) return fail_msg((std::string(who) + (may_be_null ? ": non-finite R0 or t0" : ": non-finite R or t")).c_str(), -3);
+  return 0;
+}
+// -3: the association options of the entries that look keylines up in a distance field
+int check_assoc_opts(const char* who, double min_cos, int max_dist, int search_range) {
+  if (!(min_cos >= -1.0 && min_cos <= 1.0)) return fail_msg((std::string(who) + ": min_cos outside [-1, 1]").c_str(), -3);
+  if (max_dist < 0 || max_dist > search_range) return fail_msg((std::string(who) + ": max_dist outside 0..search_range").c_str(), -3);
+  return 0;
+}
+// -3: the options of a scalar Kalman update of (rho, sigma_rho)
+int check_gate_sigma(const char* who, double gate_sigma) {
+  return gate_sigma > 0.0 ? 0 : fail_msg((std::string(who) + ": gate_sigma must be > 0").c_str(), -3);
+}
+int check_q_abs(const char* who, double q_abs) { return q_abs >= 0.0 ? 0 : fail_msg((std::string(who) + ": q_abs must be >= 0").c_str(), -3); }
+
+// What rebvio_hip_kf_snapshot_fuse_depth and _handover_depth ask of their pose and options, in the order both test it in.
+// pixel_sigma: null where the options have none (the hand-over).
+int check_kf_depth_args(const char* who, const rebvio_hip_cloud_filter& flt, const double* pixel_sigma, double gate_sigma, double q_abs,
+                        double min_cos, int max_dist, int reserved, int search_range, const double* R, const double* t) {
+  if (!R || !t) return fail_msg((std::string(who) + ": null R or t").c_str(), -3);
+  RCCHK(check_cloud_args(who, &flt, nullptr));
+  RCCHK(check_rt(who, R, t, false));
+  if (pixel_sigma && !(*pixel_sigma > 0.0)) return fail_msg((std::string(who) + ": pixel_sigma must be > 0").c_str(), -3);
+  RCCHK(check_gate_sigma(who, gate_sigma));
+  RCCHK(check_q_abs(who, q_abs));
+  RCCHK(check_assoc_opts(who, min_cos, max_dist, search_range));
+  if (reserved != 0) return fail_msg((std::string(who) + ": reserved must be 0").c_str(), -3);
+  return 0;
+}
+
+// Behind the kernel of fuse_depth / handover_depth on the track stream: the result struct the kernel left in the count words, the
+// association words when the caller wants them, ONE wait.
+template <class Result>
+int fetch_counted(rebvio_hip_ctx* c, const int* cnt, const int* assoc, int kf_size, Result* out, int* assoc_host) {
+  Result res;
+  HIPCHK(hipMemcpyAsync(&res, cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  const int rc = trk_sync(c);
+  if (rc) return rc;
+  *out = res;
+  return 0;
+}
+
+// Behind enqueue_depth_prior / enqueue_stereo_prior, in two steps: the counts, then exactly the words per keyline that exist
+// (the outcome; the stereo entries' winner too).
+template <class Counts>
+int fetch_prior(rebvio_hip_ctx* c, const scratch::Counted& s, Counts* counts, int* out_host, int* out2_host) {
+  Counts res;
+  HIPCHK(hipMemcpyAsync(&res, s.cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  int rc = trk_sync(c);
+  if (rc) return rc;
+  if ((out_host || out2_host) && res.candidates > 0) {
+    const size_t bytes = (size_t)res.candidates * sizeof(int);
+    if (out_host) HIPCHK(hipMemcpyAsync(out_host, s.out, bytes, hipMemcpyDeviceToHost, c->s_trk));
+    if (out2_host) HIPCHK(hipMemcpyAsync(out2_host, s.out2, bytes, hipMemcpyDeviceToHost, c->s_trk));
+    rc = trk_sync(c);
+    if (rc) return rc;
+  }
+  *counts = res;
+  return 0;
+}
+
+// Scratch of the keyframe correspondences (rebvio_hip_map_keyframe_matches, rebvio_hip_map_keyframe_pose), made at the first call
 int kf_scratch(rebvio_hip_ctx* c) {
-  if (c->kf_rec) return 0;
-  const size_t slots = (size_t)div_up(c->P.keylines_max, 256) * 256;
-  if (!c->kf_key) HIPCHK(c->own.device_bytes(&c->kf_key, slots * (sizeof(unsigned long long) + sizeof(int)) + (kMaxRecBlocks + 1) * sizeof(int)));
-  c->kf_claimants = reinterpret_cast<int*>(c->kf_key + slots);
-  c->kf_blk = c->kf_claimants + slots;
-  HIPCHK(c->own.device(&c->kf_rec, (size_t)c->P.keylines_max));
+  if (c->kf.rec) return 0;
+  RCCHK(ensure_scratch(c, c->kf, (size_t)c->P.keylines_max, (size_t)kMaxRecBlocks));
+  HIPCHK(c->own.device(&c->kf.rec, (size_t)c->P.keylines_max));
   return 0;
 }
 
@@ -1968,7 +2057,7 @@ int rebvio_hip_map_point_cloud(rebvio_hip_map* m, const rebvio_hip_cloud_filter*
   if (cap < 0 || (cap > 0 && !points)) return fail_msg("map_point_cloud: cap records need a points buffer (cap >= 0)", -3);
   int rc = check_cloud_args("map_point_cloud", filter, pose);
   if (rc) return rc;
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   *count = 0;
   rebvio_hip_cloud* cl = nullptr;
@@ -1989,9 +2078,9 @@ int rebvio_hip_map_point_cloud_async(rebvio_hip_ctx* c, rebvio_hip_map* m, const
   if (!c || !m || !out) return fail_msg("map_point_cloud_async: null context, map or output", -3);
   const int rc = check_cloud_args("map_point_cloud_async", filter, pose);
   if (rc) return rc;
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (m->ctx != c) return fail_msg("map_point_cloud_async: map of another context", -3);
+  if (m->ctx != c) return other_context("map_point_cloud_async", "map");
   return enqueue_cloud("map_point_cloud_async", m, filter, pose, -1, out);
 }
 
@@ -2024,9 +2113,9 @@ void rebvio_hip_cloud_release(rebvio_hip_cloud* cl) {
 
 int rebvio_hip_map_mark_keyframe(rebvio_hip_ctx* c, rebvio_hip_map* m) {
   if (!c || !m) return fail_msg("map_mark_keyframe: null context or map", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (m->ctx != c) return fail_msg("map_mark_keyframe: map of another context", -3);
+  if (m->ctx != c) return other_context("map_mark_keyframe", "map");
   HIPCHK(hipSetDevice(c->device));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
@@ -2042,7 +2131,7 @@ int rebvio_hip_map_keyframe_matches(rebvio_hip_map* m, int kf_size, rebvio_hip_k
   if (!count) return fail_msg("map_keyframe_matches: null count", -3);
   if (cap < 0 || (cap > 0 && !out_host)) return fail_msg("map_keyframe_matches: cap records need an output buffer (cap >= 0)", -3);
   if (kf_size < 0) return fail_msg("map_keyframe_matches: negative kf_size", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   if (kf_size > c->P.keylines_max) return fail_msg("map_keyframe_matches: kf_size above keylines_max", -3);
@@ -2056,8 +2145,8 @@ int rebvio_hip_map_keyframe_matches(rebvio_hip_map* m, int kf_size, rebvio_hip_k
   if (cap > c->P.keylines_max) cap = c->P.keylines_max;  // (no more slots than that can hold a claimant)
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
-  int* count_dev = c->kf_blk + kMaxRecBlocks;
-  HIPCHK((hipError_t)launch_kf_matches(c->s_trk, c->K, m->d, kf_size, cap, c->kf_key, c->kf_claimants, c->kf_blk, count_dev, c->kf_rec));
+  int* count_dev = c->kf.blk + kMaxRecBlocks;
+  HIPCHK((hipError_t)launch_kf_matches(c->s_trk, c->K, m->d, kf_size, cap, c->kf.key, c->kf.claimants, c->kf.blk, count_dev, c->kf.rec));
   HIPCHK(hipGetLastError());
   // the count first; then one copy of exactly the records that exist
   int n = 0;
@@ -2065,7 +2154,7 @@ int rebvio_hip_map_keyframe_matches(rebvio_hip_map* m, int kf_size, rebvio_hip_k
   { const int rc_ts = trk_sync(c); if (rc_ts) return rc_ts; }
   const int k = n < cap ? n : cap;
   if (k > 0) {
-    HIPCHK(hipMemcpyAsync(out_host, c->kf_rec, (size_t)k * sizeof(rebvio_hip_kf_match), hipMemcpyDeviceToHost, c->s_trk));
+    HIPCHK(hipMemcpyAsync(out_host, c->kf.rec, (size_t)k * sizeof(rebvio_hip_kf_match), hipMemcpyDeviceToHost, c->s_trk));
     const int rc_ts = trk_sync(c);
     if (rc_ts) return rc_ts;
   }
@@ -2076,9 +2165,9 @@ int rebvio_hip_map_keyframe_matches(rebvio_hip_map* m, int kf_size, rebvio_hip_k
 int rebvio_hip_map_keyframe_snapshot(rebvio_hip_ctx* c, rebvio_hip_map* m, rebvio_hip_kf_snapshot** out) {
   if (out) *out = nullptr;
   if (!c || !m || !out) return fail_msg("map_keyframe_snapshot: null context, map or output", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (m->ctx != c) return fail_msg("map_keyframe_snapshot: map of another context", -3);
+  if (m->ctx != c) return other_context("map_keyframe_snapshot", "map");
   if (m->promised.load(std::memory_order_acquire))
     return fail_msg("map_keyframe_snapshot: the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
                     "take the snapshot before that call, or once the next track_pair_begin has run", -7);
@@ -2107,27 +2196,7 @@ int rebvio_hip_map_keyframe_snapshot(rebvio_hip_ctx* c, rebvio_hip_map* m, rebvi
   return 0;
 }
 
-void rebvio_hip_kf_snapshot_release(rebvio_hip_kf_snapshot* sn) {
-  if (!sn) return;
-  {
-    const std::shared_ptr<LifeBlock> life = sn->life;
-    std::shared_lock<std::shared_mutex> lk(life->mu);
-    if (!life->dead.load(std::memory_order_acquire)) {  // (else: the context is gone, its destroy freed the buffer)
-      rebvio_hip_ctx* c = sn->ctx;
-      (void)hipSetDevice(c->device);
-      {
-        std::lock_guard<std::mutex> sl(c->snap_mu);
-        for (size_t i = 0; i < c->snaps.size(); ++i)
-          if (c->snaps[i] == sn) {
-            c->snaps.erase(c->snaps.begin() + (std::ptrdiff_t)i);
-            break;
-          }
-      }
-      sn->own.release();  // (hipFree waits for the kernels that still use the buffer)
-    }
-  }
-  delete sn;
-}
+void rebvio_hip_kf_snapshot_release(rebvio_hip_kf_snapshot* sn) { unlist_and_release(&rebvio_hip_ctx::snaps, &rebvio_hip_ctx::snap_mu, sn); }
 
 namespace {
 // the keyframe's size on the host: fetched once, behind the snapshot kernel in stream order
@@ -2147,11 +2216,7 @@ int check_kf_pose_args(const char* who, const rebvio_hip_kf_pose_opts& o, const 
   if (!(o.huber_px > 0.0)) return fail_msg((std::string(who) + ": huber_px must be > 0").c_str(), -3);
   if (o.max_iter < 0 || o.max_iter > 32) return fail_msg((std::string(who) + ": max_iter outside 0..32").c_str(), -3);
   if (o.min_used < 0 || o.min_used > 65536) return fail_msg((std::string(who) + ": min_used outside 0..65536").c_str(), -3);
-  bool fin = true;
-  for (int i = 0; R0 && i < 9; ++i) fin = fin && std::isfinite(R0[i]);
-  for (int i = 0; t0 && i < 3; ++i) fin = fin && std::isfinite(t0[i]);
-  if (!fin) return fail_msg((std::string(who) + ": non-finite R0 or t0").c_str(), -3);
-  return 0;
+  return check_rt(who, R0, t0, true);
 }
 
 // the result block before the first evaluation: the guess, everything else zero
@@ -2166,9 +2231,8 @@ int rebvio_hip_kf_snapshot_download(rebvio_hip_kf_snapshot* sn, float* prs4, uns
   if (!sn || !n) return fail_msg("kf_snapshot_download: null snapshot or n", -3);
   if (cap < 0 || (cap > 0 && (!prs4 || !matches))) return fail_msg("kf_snapshot_download: cap records need both output buffers (cap >= 0)", -3);
   *n = 0;
-  const std::shared_ptr<LifeBlock> life = sn->life;
-  std::shared_lock<std::shared_mutex> lk(life->mu);
-  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  const Alive alive(sn);
+  if (alive.dead()) return -10;
   rebvio_hip_ctx* c = sn->ctx;
   HIPCHK(hipSetDevice(c->device));
   int rc = snapshot_size(c, sn);
@@ -2192,9 +2256,8 @@ int rebvio_hip_kf_snapshot_point_cloud(rebvio_hip_kf_snapshot* sn, const rebvio_
   int rc = check_cloud_args("kf_snapshot_point_cloud", filter, pose);
   if (rc) return rc;
   *count = 0;
-  const std::shared_ptr<LifeBlock> life = sn->life;
-  std::shared_lock<std::shared_mutex> lk(life->mu);
-  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  const Alive alive(sn);
+  if (alive.dead()) return -10;
   rebvio_hip_cloud* cl = nullptr;
   rc = enqueue_kf_cloud("kf_snapshot_point_cloud", sn, filter, pose, cap, &cl);
   if (rc) return rc;
@@ -2213,9 +2276,8 @@ int rebvio_hip_kf_snapshot_point_cloud_async(rebvio_hip_kf_snapshot* sn, const r
   if (!sn || !out) return fail_msg("kf_snapshot_point_cloud_async: null snapshot or output", -3);
   const int rc = check_cloud_args("kf_snapshot_point_cloud_async", filter, pose);
   if (rc) return rc;
-  const std::shared_ptr<LifeBlock> life = sn->life;
-  std::shared_lock<std::shared_mutex> lk(life->mu);
-  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  const Alive alive(sn);
+  if (alive.dead()) return -10;
   return enqueue_kf_cloud("kf_snapshot_point_cloud_async", sn, filter, pose, -1, out);
 }
 
@@ -2249,21 +2311,16 @@ int rebvio_hip_map_keyframe_pose(rebvio_hip_map* m, rebvio_hip_kf_snapshot* sn, 
   if (!m || !sn || !out) return fail_msg("map_keyframe_pose: null map, snapshot or output", -3);
   rebvio_hip_kf_pose_opts o;
   if (opts) o = *opts; else rebvio_hip_default_kf_pose_opts(&o);
-  int rc = check_kf_pose_args("map_keyframe_pose", o, R0, t0);
-  if (rc) return rc;
-  const MapAlive alive(m);
+  RCCHK(check_kf_pose_args("map_keyframe_pose", o, R0, t0));
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (sn->life != m->life) {
-    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
-    return fail_msg("map_keyframe_pose: snapshot of another context", -3);
-  }
+  RCCHK(snapshot_of("map_keyframe_pose", sn, m));
   rebvio_hip_ctx* c = m->ctx;
   if (m->promised.load(std::memory_order_acquire))
     return fail_msg("map_keyframe_pose: the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
                     "its pose is available again once the next track_pair_begin has run", -7);
   HIPCHK(hipSetDevice(c->device));
-  rc = snapshot_size(c, sn);
-  if (rc) return rc;
+  RCCHK(snapshot_size(c, sn));
   const int kf_size = sn->n_host;
   rebvio_hip_kf_pose start;
   kf_pose_start(&start, R0, t0);
@@ -2273,30 +2330,21 @@ int rebvio_hip_map_keyframe_pose(rebvio_hip_map* m, rebvio_hip_kf_snapshot* sn, 
     return 0;
   }
   // scratch of the correspondences and of the solve
-  rc = kf_scratch(c);
-  if (rc) return rc;
-  if (!c->kfp_state) {
-    const size_t head = (sizeof(rebvio_hip_kf_pose) + 63) / 64 * 64, part = (size_t)kMaxRecBlocks * kfp::kSums * sizeof(double);
-    char* b = nullptr;
-    HIPCHK(c->own.device_bytes(&b, head + part + kMaxRecBlocks * sizeof(int)));
-    c->kfp_state = reinterpret_cast<rebvio_hip_kf_pose*>(b);
-    c->kfp_part = reinterpret_cast<double*>(b + head);
-    c->kfp_used = reinterpret_cast<int*>(b + head + part);
-  }
+  RCCHK(kf_scratch(c));
+  RCCHK(ensure_scratch(c, c->kfp, (size_t)kMaxRecBlocks, (size_t)0));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
-  int* count_dev = c->kf_blk + kMaxRecBlocks;
-  HIPCHK((hipError_t)launch_kf_matches(c->s_trk, c->K, m->d, kf_size, c->P.keylines_max, c->kf_key, c->kf_claimants, c->kf_blk, count_dev, c->kf_rec));
+  int* count_dev = c->kf.blk + kMaxRecBlocks;
+  HIPCHK((hipError_t)launch_kf_matches(c->s_trk, c->K, m->d, kf_size, c->P.keylines_max, c->kf.key, c->kf.claimants, c->kf.blk, count_dev, c->kf.rec));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->kfp_state, &start, sizeof(start), hipMemcpyHostToDevice, c->s_trk));
+  HIPCHK(hipMemcpyAsync(c->kfp.state, &start, sizeof(start), hipMemcpyHostToDevice, c->s_trk));
   for (int it = 0; it <= o.max_iter; ++it)
-    launch_kf_pose_eval(c->s_trk, c->K, m->d, kf_size, c->kf_rec, count_dev, sn->prs, sn->matches, o.kf_filter, o.huber_px, it == 0,
-                        it == o.max_iter, o.min_used, c->kfp_state, c->kfp_part, c->kfp_used);
+    launch_kf_pose_eval(c->s_trk, c->K, m->d, kf_size, c->kf.rec, count_dev, sn->prs, sn->matches, o.kf_filter, o.huber_px, it == 0,
+                        it == o.max_iter, o.min_used, c->kfp.state, c->kfp.part, c->kfp.used);
   HIPCHK(hipGetLastError());
   rebvio_hip_kf_pose res;
-  HIPCHK(hipMemcpyAsync(&res, c->kfp_state, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
-  rc = trk_sync(c);
-  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(&res, c->kfp.state, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  RCCHK(trk_sync(c));
   *out = res;
   return 0;
 }
@@ -2340,12 +2388,9 @@ int rebvio_hip_test_kf_pose_host(float fm, const float* snap_prs4, const unsigne
 
 int rebvio_hip_kf_snapshot_add_normals(rebvio_hip_kf_snapshot* sn, rebvio_hip_map* m) {
   if (!sn || !m) return fail_msg("kf_snapshot_add_normals: null snapshot or map", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (sn->life != m->life) {
-    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
-    return fail_msg("kf_snapshot_add_normals: map of another context", -3);
-  }
+  RCCHK(of_map_context("kf_snapshot_add_normals", sn, m, "map"));
   rebvio_hip_ctx* c = m->ctx;
   if (m->promised.load(std::memory_order_acquire))
     return fail_msg("kf_snapshot_add_normals: the map was handed to track_pair_finish_async with R_prior_next and its gradients are rotated "
@@ -2370,9 +2415,8 @@ int rebvio_hip_kf_snapshot_download_normals(rebvio_hip_kf_snapshot* sn, float* n
   if (!sn || !n) return fail_msg("kf_snapshot_download_normals: null snapshot or n", -3);
   if (cap < 0 || (cap > 0 && !n2)) return fail_msg("kf_snapshot_download_normals: cap pairs need an output buffer (cap >= 0)", -3);
   *n = 0;
-  const std::shared_ptr<LifeBlock> life = sn->life;
-  std::shared_lock<std::shared_mutex> lk(life->mu);
-  if (life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
+  const Alive alive(sn);
+  if (alive.dead()) return -10;
   rebvio_hip_ctx* c = sn->ctx;
   const void* normals;
   {
@@ -2411,10 +2455,7 @@ int check_kf_align_args(const char* who, const rebvio_hip_kf_align_opts& o, int 
   po.max_iter = o.max_iter;
   po.min_used = o.min_used;
   const int rc = check_kf_pose_args(who, po, R0, t0);
-  if (rc) return rc;
-  if (!(o.min_cos >= -1.0 && o.min_cos <= 1.0)) return fail_msg((std::string(who) + ": min_cos outside [-1, 1]").c_str(), -3);
-  if (o.max_dist < 0 || o.max_dist > search_range) return fail_msg((std::string(who) + ": max_dist outside 0..search_range").c_str(), -3);
-  return 0;
+  return rc ? rc : check_assoc_opts(who, o.min_cos, o.max_dist, search_range);
 }
 }  // namespace
 
@@ -2423,22 +2464,16 @@ static_assert(sizeof(rebvio_hip_kf_align_opts) == 48, "filter, two doubles, thre
 int rebvio_hip_map_keyframe_align(rebvio_hip_map* m, rebvio_hip_kf_snapshot* sn, const rebvio_hip_kf_align_opts* opts, const double* R0,
                                   const double* t0, rebvio_hip_kf_pose* out, int* assoc_host) {
   if (!m || !sn || !out) return fail_msg("map_keyframe_align: null map, snapshot or output", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (sn->life != m->life) {
-    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
-    return fail_msg("map_keyframe_align: snapshot of another context", -3);
-  }
+  RCCHK(snapshot_of("map_keyframe_align", sn, m));
   rebvio_hip_ctx* c = m->ctx;
   rebvio_hip_kf_align_opts o;
   if (opts) o = *opts; else rebvio_hip_default_kf_align_opts(c, &o);
-  int rc = check_kf_align_args("map_keyframe_align", o, (int)c->P.search_range, R0, t0);
-  if (rc) return rc;
-  if (!m->df_built || !m->raster_order)
-    return fail_msg("map_keyframe_align: the map's distance field is not detection's (none was built, or its keylines were uploaded)", -7);
+  RCCHK(check_kf_align_args("map_keyframe_align", o, (int)c->P.search_range, R0, t0));
+  RCCHK(needs_detection_field("map_keyframe_align", m));
   HIPCHK(hipSetDevice(c->device));
-  rc = snapshot_size(c, sn);
-  if (rc) return rc;
+  RCCHK(snapshot_size(c, sn));
   const int kf_size = sn->n_host;
   rebvio_hip_kf_pose start;
   kf_pose_start(&start, R0, t0);
@@ -2447,18 +2482,10 @@ int rebvio_hip_map_keyframe_align(rebvio_hip_map* m, rebvio_hip_kf_snapshot* sn,
     *out = start;
     return 0;
   }
-  if (!c->kfa_state) {
-    const size_t head = (sizeof(rebvio_hip_kf_pose) + 63) / 64 * 64, part = (size_t)kMaxRecBlocks * kfp::kSums * sizeof(double);
-    char* b = nullptr;
-    HIPCHK(c->own.device_bytes(&b, head + part + kMaxRecBlocks * sizeof(int) + (size_t)c->P.keylines_max * sizeof(int)));
-    c->kfa_state = reinterpret_cast<rebvio_hip_kf_pose*>(b);
-    c->kfa_part = reinterpret_cast<double*>(b + head);
-    c->kfa_used = reinterpret_cast<int*>(b + head + part);
-    c->kfa_assoc = c->kfa_used + kMaxRecBlocks;
-  }
+  RCCHK(ensure_scratch(c, c->kfa, (size_t)kMaxRecBlocks, (size_t)c->P.keylines_max));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready(c->s_trk, m));
-  HIPCHK(hipMemcpyAsync(c->kfa_state, &start, sizeof(start), hipMemcpyHostToDevice, c->s_trk));
+  HIPCHK(hipMemcpyAsync(c->kfa.state, &start, sizeof(start), hipMemcpyHostToDevice, c->s_trk));
   const void* normals;
   {
     std::lock_guard<std::mutex> lk(sn->nor_mu);
@@ -2466,13 +2493,12 @@ int rebvio_hip_map_keyframe_align(rebvio_hip_map* m, rebvio_hip_kf_snapshot* sn,
   }
   for (int it = 0; it <= o.max_iter; ++it)
     launch_kf_align_eval(c->s_trk, c->K, m->d, kf_size, sn->n_dev, sn->prs, sn->matches, normals, o.kf_filter, o.huber_px, o.min_cos,
-                         o.max_dist, it == 0, it == o.max_iter, o.min_used, c->kfa_state, c->kfa_part, c->kfa_used, c->kfa_assoc);
+                         o.max_dist, it == 0, it == o.max_iter, o.min_used, c->kfa.state, c->kfa.part, c->kfa.used, c->kfa.assoc);
   HIPCHK(hipGetLastError());
   rebvio_hip_kf_pose res;
-  HIPCHK(hipMemcpyAsync(&res, c->kfa_state, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
-  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, c->kfa_assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
-  rc = trk_sync(c);
-  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(&res, c->kfa.state, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
+  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, c->kfa.assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
+  RCCHK(trk_sync(c));
   *out = res;
   return 0;
 }
@@ -2515,24 +2541,14 @@ int rebvio_hip_map_keyframe_align_many(rebvio_hip_map* m, const rebvio_hip_kf_hy
   if (n < 1 || n > REBVIO_HIP_KF_HYP_MAX) return fail_msg("map_keyframe_align_many: n outside 1..REBVIO_HIP_KF_HYP_MAX", -3);
   for (int h = 0; h < n; ++h)
     if (!hyp[h].snap) return fail_msg("map_keyframe_align_many: null snapshot in the list", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  for (int h = 0; h < n; ++h) {
-    const rebvio_hip_kf_snapshot* sn = hyp[h].snap;
-    if (sn->life == m->life) continue;
-    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
-    return fail_msg("map_keyframe_align_many: snapshot of another context", -3);
-  }
+  for (int h = 0; h < n; ++h) RCCHK(snapshot_of("map_keyframe_align_many", hyp[h].snap, m));
   rebvio_hip_ctx* c = m->ctx;
   rebvio_hip_kf_align_opts o;
   if (opts) o = *opts; else rebvio_hip_default_kf_align_opts(c, &o);
-  int rc = 0;
-  for (int h = 0; h < n && !rc; ++h)
-    rc = check_kf_align_args("map_keyframe_align_many", o, (int)c->P.search_range, hyp[h].R0, hyp[h].t0);
-  if (rc) return rc;
-  if (!m->df_built || !m->raster_order)
-    return fail_msg("map_keyframe_align_many: the map's distance field is not detection's (none was built, or its keylines were uploaded)",
-                    -7);
+  for (int h = 0; h < n; ++h) RCCHK(check_kf_align_args("map_keyframe_align_many", o, (int)c->P.search_range, hyp[h].R0, hyp[h].t0));
+  RCCHK(needs_detection_field("map_keyframe_align_many", m));
   HIPCHK(hipSetDevice(c->device));
   // sizes and normals: each distinct snapshot is asked once (its mutex taken once, never inside another's)
   const void* normals[REBVIO_HIP_KF_HYP_MAX];
@@ -2546,8 +2562,7 @@ int rebvio_hip_map_keyframe_align_many(rebvio_hip_map* m, const rebvio_hip_kf_hy
       normals[h] = normals[seen];
       continue;
     }
-    rc = snapshot_size(c, sn);
-    if (rc) return rc;
+    RCCHK(snapshot_size(c, sn));
     if (sn->n_host > (int)c->P.keylines_max) return fail_msg("map_keyframe_align_many: a snapshot larger than keylines_max", -2);
     {
       std::lock_guard<std::mutex> lk(sn->nor_mu);
@@ -2571,41 +2586,32 @@ int rebvio_hip_map_keyframe_align_many(rebvio_hip_map* m, const rebvio_hip_kf_hy
     for (int h = 0; h < n; ++h) out[h] = stage->res[h];
     return 0;
   }
-  if (!c->kfm_desc) {
-    const size_t head = sizeof(Stage), part = (size_t)kMaxRecBlocks * kfp::kSums * sizeof(double), cnt = (size_t)kMaxRecBlocks * sizeof(int);
-    static_assert(sizeof(Stage) % 64 == 0, "the partials start on a 64-byte line");
-    char* b = nullptr;
-    HIPCHK(c->own.device_bytes(&b, head + REBVIO_HIP_KF_HYP_MAX * (part + 2 * cnt)));
-    c->kfm_desc = reinterpret_cast<KfHypDesc*>(b);
-    c->kfm_res = reinterpret_cast<rebvio_hip_kf_hyp_result*>(b + offsetof(Stage, res));
-    c->kfm_part = reinterpret_cast<double*>(b + head);
-    c->kfm_used = reinterpret_cast<int*>(b + head + REBVIO_HIP_KF_HYP_MAX * part);
-    c->kfm_inl = c->kfm_used + (size_t)REBVIO_HIP_KF_HYP_MAX * kMaxRecBlocks;
-  }
+  static_assert(sizeof(Stage) % 64 == 0, "the partials start on a 64-byte line");
+  static_assert(sizeof(KfHypDesc) == 64 && sizeof(ChainDev) == 13 * sizeof(void*), "as their stand-ins in tests/cpp/scratch_layout_check.cpp");
+  RCCHK(ensure_scratch(c, c->kfm, (size_t)kMaxRecBlocks));
   for (int h = 0; h < n; ++h) {
     const rebvio_hip_kf_snapshot* sn = hyp[h].snap;
     KfHypDesc& d = stage->desc[h];
     d.prs = sn->prs;
     d.matches = sn->matches;
     d.normals = normals[h];
-    d.res = c->kfm_res + h;
-    d.part = c->kfm_part + (size_t)h * kMaxRecBlocks * kfp::kSums;
-    d.part_used = c->kfm_used + (size_t)h * kMaxRecBlocks;
-    d.part_inl = c->kfm_inl + (size_t)h * kMaxRecBlocks;
+    d.res = c->kfm.res + h;
+    d.part = c->kfm.part + (size_t)h * kMaxRecBlocks * kfp::kSums;
+    d.part_used = c->kfm.used + (size_t)h * kMaxRecBlocks;
+    d.part_inl = c->kfm.inl + (size_t)h * kMaxRecBlocks;
     d.size = sn->n_host;
   }
   wait_enqueued(m);
   HIPCHK(trk_wait_ready(c->s_trk, m));
   // ONE upload: the whole table and the first n result blocks lie next to each other
-  HIPCHK(hipMemcpyAsync(c->kfm_desc, stage.get(), offsetof(Stage, res) + (size_t)n * sizeof(rebvio_hip_kf_hyp_result), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(c->kfm.desc, stage.get(), offsetof(Stage, res) + (size_t)n * sizeof(rebvio_hip_kf_hyp_result), hipMemcpyHostToDevice,
                         c->s_trk));
   for (int it = 0; it <= o.max_iter; ++it)
-    launch_kf_align_many_eval(c->s_trk, c->K, m->d, c->kfm_desc, n, nb_max, o.kf_filter, o.huber_px, o.min_cos, o.max_dist, it == 0,
+    launch_kf_align_many_eval(c->s_trk, c->K, m->d, c->kfm.desc, n, nb_max, o.kf_filter, o.huber_px, o.min_cos, o.max_dist, it == 0,
                               it == o.max_iter, o.min_used);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(stage->res, c->kfm_res, (size_t)n * sizeof(rebvio_hip_kf_hyp_result), hipMemcpyDeviceToHost, c->s_trk));
-  rc = trk_sync(c);
-  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(stage->res, c->kfm.res, (size_t)n * sizeof(rebvio_hip_kf_hyp_result), hipMemcpyDeviceToHost, c->s_trk));
+  RCCHK(trk_sync(c));
   for (int h = 0; h < n; ++h) out[h] = stage->res[h];
   return 0;
 }
@@ -2671,21 +2677,7 @@ void rebvio_hip_default_kf_fuse_opts(rebvio_hip_ctx* c, rebvio_hip_kf_fuse_opts*
 
 namespace {
 int check_kf_fuse_args(const char* who, const rebvio_hip_kf_fuse_opts& o, int search_range, const double* R, const double* t) {
-  const std::string w(who);
-  if (!R || !t) return fail_msg((w + ": null R or t").c_str(), -3);
-  const int rc = check_cloud_args(who, &o.kf_filter, nullptr);
-  if (rc) return rc;
-  bool fin = true;
-  for (int i = 0; i < 9; ++i) fin = fin && std::isfinite(R[i]);
-  for (int i = 0; i < 3; ++i) fin = fin && std::isfinite(t[i]);
-  if (!fin) return fail_msg((w + ": non-finite R or t").c_str(), -3);
-  if (!(o.pixel_sigma > 0.0)) return fail_msg((w + ": pixel_sigma must be > 0").c_str(), -3);
-  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
-  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
-  if (!(o.min_cos >= -1.0 && o.min_cos <= 1.0)) return fail_msg((w + ": min_cos outside [-1, 1]").c_str(), -3);
-  if (o.max_dist < 0 || o.max_dist > search_range) return fail_msg((w + ": max_dist outside 0..search_range").c_str(), -3);
-  if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
-  return 0;
+  return check_kf_depth_args(who, o.kf_filter, &o.pixel_sigma, o.gate_sigma, o.q_abs, o.min_cos, o.max_dist, o.reserved, search_range, R, t);
 }
 }  // namespace
 
@@ -2695,46 +2687,29 @@ static_assert(sizeof(rebvio_hip_kf_fuse) == 24, "six ints");
 int rebvio_hip_kf_snapshot_fuse_depth(rebvio_hip_kf_snapshot* sn, rebvio_hip_map* m, const rebvio_hip_kf_fuse_opts* opts, const double* R,
                                       const double* t, rebvio_hip_kf_fuse* out, int* assoc_host) {
   if (!sn || !m || !out) return fail_msg("kf_snapshot_fuse_depth: null snapshot, map or output", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (sn->life != m->life) {
-    if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
-    return fail_msg("kf_snapshot_fuse_depth: snapshot of another context", -3);
-  }
+  RCCHK(snapshot_of("kf_snapshot_fuse_depth", sn, m));
   rebvio_hip_ctx* c = m->ctx;
   rebvio_hip_kf_fuse_opts o;
   if (opts) o = *opts; else rebvio_hip_default_kf_fuse_opts(c, &o);
-  int rc = check_kf_fuse_args("kf_snapshot_fuse_depth", o, (int)c->P.search_range, R, t);
-  if (rc) return rc;
-  if (!m->df_built || !m->raster_order)
-    return fail_msg("kf_snapshot_fuse_depth: the map's distance field is not detection's (none was built, or its keylines were uploaded)", -7);
+  RCCHK(check_kf_fuse_args("kf_snapshot_fuse_depth", o, (int)c->P.search_range, R, t));
+  RCCHK(needs_detection_field("kf_snapshot_fuse_depth", m));
   HIPCHK(hipSetDevice(c->device));
-  rc = snapshot_size(c, sn);
-  if (rc) return rc;
+  RCCHK(snapshot_size(c, sn));
   const int kf_size = sn->n_host;
   std::memset(out, 0, sizeof(*out));
   if (kf_size == 0) return 0;  // nothing to fuse: nothing is launched
-  if (!c->kff_cnt) {
-    char* b = nullptr;
-    HIPCHK(c->own.device_bytes(&b, (8 + (size_t)c->P.keylines_max) * sizeof(int)));
-    c->kff_cnt = reinterpret_cast<int*>(b);
-    c->kff_assoc = c->kff_cnt + 8;
-  }
+  RCCHK(ensure_scratch(c, c->kff, (size_t)c->P.keylines_max, 1));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready(c->s_trk, m));
-  rebvio_hip_kf_fuse res;
   {
     std::lock_guard<std::mutex> lk(sn->nor_mu);  // (the snapshot is this call's from the clear to the kernel, as in add_normals)
-    HIPCHK(hipMemsetAsync(c->kff_cnt, 0, 8 * sizeof(int), c->s_trk));
-    launch_kf_fuse_depth(c->s_trk, c->K, m->d, kf_size, sn->n_dev, sn->prs, sn->matches, sn->normals, o, R, t, c->kff_cnt, c->kff_assoc);
+    HIPCHK(hipMemsetAsync(c->kff.cnt, 0, 8 * sizeof(int), c->s_trk));
+    launch_kf_fuse_depth(c->s_trk, c->K, m->d, kf_size, sn->n_dev, sn->prs, sn->matches, sn->normals, o, R, t, c->kff.cnt, c->kff.out);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemcpyAsync(&res, c->kff_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
-  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, c->kff_assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
-  rc = trk_sync(c);
-  if (rc) return rc;
-  *out = res;
-  return 0;
+  return fetch_counted(c, c->kff.cnt, c->kff.out, kf_size, out, assoc_host);
 }
 
 int rebvio_hip_test_kf_fuse_host(float fm, float cx, float cy, int rows, int cols, int search_range, float* snap_prs4, unsigned* snap_matches,
@@ -2823,8 +2798,8 @@ int check_depth_prior_args(const char* who, const void* depth, size_t* pitch, in
   if (!(o.sigma_z0 >= 0.0)) return fail_msg((w + ": sigma_z0 must be >= 0").c_str(), -3);
   if (!(o.sigma_z2 >= 0.0)) return fail_msg((w + ": sigma_z2 must be >= 0").c_str(), -3);
   if (!(o.sigma_z0 + o.sigma_z2 > 0.0)) return fail_msg((w + ": sigma_z0 + sigma_z2 must be > 0").c_str(), -3);
-  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
-  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
+  RCCHK(check_gate_sigma(who, o.gate_sigma));
+  RCCHK(check_q_abs(who, o.q_abs));
   if (!(o.unit > 0.0)) return fail_msg((w + ": unit must be > 0").c_str(), -3);
   if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
   return 0;
@@ -2844,34 +2819,18 @@ int enqueue_depth_prior(const char* who, rebvio_hip_map* m, const void* img, siz
   rebvio_hip_ctx* c = m->ctx;
   const int rc_state = depth_prior_state_rule(who, m);
   if (rc_state) return rc_state;
-  if (!c->dpr_cnt) {
-    char* b = nullptr;
-    HIPCHK(c->own.device_bytes(&b, (8 + (size_t)c->P.keylines_max) * sizeof(int)));
-    c->dpr_cnt = reinterpret_cast<int*>(b);
-    c->dpr_outcome = c->dpr_cnt + 8;
-  }
+  RCCHK(ensure_scratch(c, c->dpr, (size_t)c->P.keylines_max, 1));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
-  HIPCHK(hipMemsetAsync(c->dpr_cnt, 0, 8 * sizeof(int), c->s_trk));
-  launch_depth_prior(c->s_trk, c->K, m->d, dpr::make_args(img, pitch, c->P.rows, c->P.cols, fmt, o), c->dpr_cnt, c->dpr_outcome);
+  HIPCHK(hipMemsetAsync(c->dpr.cnt, 0, 8 * sizeof(int), c->s_trk));
+  launch_depth_prior(c->s_trk, c->K, m->d, dpr::make_args(img, pitch, c->P.rows, c->P.cols, fmt, o), c->dpr.cnt, c->dpr.out);
   HIPCHK(hipGetLastError());
   c->dpr_queued = true;
   return 0;
 }
 
-// Behind enqueue_depth_prior: the counts, then exactly the outcome words that exist.
 int fetch_depth_prior(rebvio_hip_ctx* c, rebvio_hip_depth_prior_counts* counts, int* outcome_host) {
-  rebvio_hip_depth_prior_counts res;
-  HIPCHK(hipMemcpyAsync(&res, c->dpr_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
-  int rc = trk_sync(c);
-  if (rc) return rc;
-  if (outcome_host && res.candidates > 0) {
-    HIPCHK(hipMemcpyAsync(outcome_host, c->dpr_outcome, (size_t)res.candidates * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
-    rc = trk_sync(c);
-    if (rc) return rc;
-  }
-  *counts = res;
-  return 0;
+  return fetch_prior(c, c->dpr, counts, outcome_host, nullptr);
 }
 
 int fuse_depth_image_sync(const char* who, rebvio_hip_map* m, const void* depth, size_t pitch, int fmt, const rebvio_hip_depth_prior_opts* opts,
@@ -2879,7 +2838,7 @@ int fuse_depth_image_sync(const char* who, rebvio_hip_map* m, const void* depth,
   const std::string w(who);
   if (!m) return fail_msg((w + ": null map").c_str(), -3);
   if (!counts) return fail_msg((w + ": null counts").c_str(), -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   rebvio_hip_depth_prior_opts o;
@@ -2921,9 +2880,9 @@ int rebvio_hip_map_fuse_depth_image_device(rebvio_hip_map* m, const void* depth_
 int rebvio_hip_map_fuse_depth_image_async(rebvio_hip_ctx* c, rebvio_hip_map* m, const void* depth_dev, size_t pitch_bytes, int fmt,
                                           const rebvio_hip_depth_prior_opts* opts) {
   if (!c || !m) return fail_msg("map_fuse_depth_image_async: null context or map", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (m->ctx != c) return fail_msg("map_fuse_depth_image_async: map of another context", -3);
+  if (m->ctx != c) return other_context("map_fuse_depth_image_async", "map");
   rebvio_hip_depth_prior_opts o;
   if (opts) o = *opts; else rebvio_hip_default_depth_prior_opts(&o);
   const int rc = check_depth_prior_args("map_fuse_depth_image_async", depth_dev, &pitch_bytes, fmt, c->P.cols, o);
@@ -2999,11 +2958,11 @@ int check_stereo_prior_opts(const char* who, int cols, const rebvio_hip_stereo_p
   if (!(o.min_ux > 0.0 && o.min_ux <= 1.0)) return fail_msg((w + ": min_ux must be in (0, 1]").c_str(), -3);
   if (o.row_tol != 0 && o.row_tol != 1) return fail_msg((w + ": row_tol must be 0 or 1").c_str(), -3);
   if (!(o.sigma_px > 0.0 && o.sigma_px < HUGE_VAL)) return fail_msg((w + ": sigma_px must be > 0 and finite").c_str(), -3);
-  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
+  RCCHK(check_gate_sigma(who, o.gate_sigma));
   if (!(o.ambig_px >= 0.0)) return fail_msg((w + ": ambig_px must be >= 0").c_str(), -3);
   if (!(o.cos_min >= -1.0 && o.cos_min <= 1.0)) return fail_msg((w + ": cos_min must be in [-1, 1]").c_str(), -3);
   if (!(o.norm_tol >= 0.0)) return fail_msg((w + ": norm_tol must be >= 0").c_str(), -3);
-  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
+  RCCHK(check_q_abs(who, o.q_abs));
   if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
   return 0;
 }
@@ -3024,7 +2983,7 @@ class PairAlive {
   bool dead() const { return dead_; }
 
  private:
-  std::optional<MapAlive> a_, b_;
+  std::optional<Alive> a_, b_;
   bool dead_;
 };
 
@@ -3044,13 +3003,7 @@ int enqueue_stereo_prior(const char* who, rebvio_hip_map* m, rebvio_hip_map* r, 
   rv = depth_prior_state_rule(who, m);
   if (rv) return rv;
   HIPCHK(hipSetDevice(c->device));
-  if (!c->spr_cnt) {
-    char* b = nullptr;
-    HIPCHK(c->own.device_bytes(&b, (8 + 2 * (size_t)c->P.keylines_max) * sizeof(int)));
-    c->spr_cnt = reinterpret_cast<int*>(b);
-    c->spr_outcome = c->spr_cnt + 8;
-    c->spr_winner = c->spr_outcome + c->P.keylines_max;
-  }
+  RCCHK(ensure_scratch(c, c->spr, (size_t)c->P.keylines_max, 2));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
   if (r != m) {
@@ -3058,29 +3011,16 @@ int enqueue_stereo_prior(const char* who, rebvio_hip_map* m, rebvio_hip_map* r, 
     wait_enqueued(r);
     HIPCHK(hipEventSynchronize(r->ready));
   }
-  HIPCHK(hipMemsetAsync(c->spr_cnt, 0, 8 * sizeof(int), c->s_trk));
-  launch_stereo_prior(c->s_trk, c->K, m->d, r->d, rc->P.keylines_max, spr::make_args(c->P.rows, c->P.cols, c->P.fm, o), c->spr_cnt,
-                      c->spr_outcome, c->spr_winner);
+  HIPCHK(hipMemsetAsync(c->spr.cnt, 0, 8 * sizeof(int), c->s_trk));
+  launch_stereo_prior(c->s_trk, c->K, m->d, r->d, rc->P.keylines_max, spr::make_args(c->P.rows, c->P.cols, c->P.fm, o), c->spr.cnt,
+                      c->spr.out, c->spr.out2);
   HIPCHK(hipGetLastError());
   c->spr_queued = true;
   return 0;
 }
 
-// Behind enqueue_stereo_prior: the counts, then exactly the outcome / winner words that exist.
 int fetch_stereo_prior(rebvio_hip_ctx* c, rebvio_hip_stereo_prior_counts* counts, int* outcome_host, int* winner_host) {
-  rebvio_hip_stereo_prior_counts res;
-  HIPCHK(hipMemcpyAsync(&res, c->spr_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
-  int rc = trk_sync(c);
-  if (rc) return rc;
-  if ((outcome_host || winner_host) && res.candidates > 0) {
-    const size_t bytes = (size_t)res.candidates * sizeof(int);
-    if (outcome_host) HIPCHK(hipMemcpyAsync(outcome_host, c->spr_outcome, bytes, hipMemcpyDeviceToHost, c->s_trk));
-    if (winner_host) HIPCHK(hipMemcpyAsync(winner_host, c->spr_winner, bytes, hipMemcpyDeviceToHost, c->s_trk));
-    rc = trk_sync(c);
-    if (rc) return rc;
-  }
-  *counts = res;
-  return 0;
+  return fetch_prior(c, c->spr, counts, outcome_host, winner_host);
 }
 }  // namespace
 
@@ -3102,7 +3042,7 @@ int rebvio_hip_map_fuse_stereo_async(rebvio_hip_ctx* c, rebvio_hip_map* m, rebvi
   if (!r) return fail_msg("map_fuse_stereo_async: null right map", -3);
   const PairAlive alive(m, r);
   if (alive.dead()) return -10;
-  if (m->ctx != c) return fail_msg("map_fuse_stereo_async: left map of another context", -3);
+  if (m->ctx != c) return other_context("map_fuse_stereo_async", "left map");
   return enqueue_stereo_prior("map_fuse_stereo_async", m, r, opts);
 }
 
@@ -3180,29 +3120,19 @@ const char* const kPlcPromised = ": the map was handed to track_pair_finish_asyn
                                  "next pair; take the signature where the snapshot is taken, or once the next track_pair_begin has run";
 
 // the context's scratch, made at the first signature
-int place_scratch(rebvio_hip_ctx* c) {
-  if (c->plc_hist) return 0;
-  char* b = nullptr;
-  const size_t hist = 388 * sizeof(unsigned);
-  HIPCHK(c->own.device_bytes(&b, hist + kPlcRowBytes + 16));
-  c->plc_hist = reinterpret_cast<unsigned*>(b);
-  c->plc_query = reinterpret_cast<uint16_t*>(b + hist);
-  c->plc_counted = reinterpret_cast<int*>(b + hist + kPlcRowBytes);
-  return 0;
-}
+int place_scratch(rebvio_hip_ctx* c) { return ensure_scratch(c, c->plc); }
 
 // One clear and the two signature kernels on the track stream (the caller holds the life block and has done its checks).
 int enqueue_place_signature(rebvio_hip_ctx* c, rebvio_hip_map* m, uint16_t* sig_dev, int* counted_dev) {
-  const int rc = place_scratch(c);
-  if (rc) return rc;
+  RCCHK(place_scratch(c));
   if (!sig_dev) {  // the context's own query row
-    sig_dev = c->plc_query;
-    counted_dev = c->plc_counted;
+    sig_dev = c->plc.query;
+    counted_dev = c->plc.counted;
   }
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
-  HIPCHK(hipMemsetAsync(c->plc_hist, 0, (plc::kWords + 1) * sizeof(unsigned), c->s_trk));
-  launch_place_signature(c->s_trk, c->K, m->d, c->plc_hist, sig_dev, counted_dev);
+  HIPCHK(hipMemsetAsync(c->plc.hist, 0, (plc::kWords + 1) * sizeof(unsigned), c->s_trk));
+  launch_place_signature(c->s_trk, c->K, m->d, c->plc.hist, sig_dev, counted_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3235,26 +3165,11 @@ int check_place_query_args(const char* who, int k, int exclude_last) {
   if (exclude_last < 0) return fail_msg((std::string(who) + ": negative exclude_last").c_str(), -3);
   return 0;
 }
-
-// Holds a database's life block (shared) for an entry's duration, as MapAlive does for a map.
-class DbAlive {
- public:
-  explicit DbAlive(const rebvio_hip_place_db* db) : hold_(db->life), lock_(hold_->mu) {
-    dead_ = hold_->dead.load(std::memory_order_acquire);
-    if (dead_) g_err = "the place database's context has been destroyed (rebvio_hip_destroy)";
-  }
-  bool dead() const { return dead_; }
-
- private:
-  std::shared_ptr<LifeBlock> hold_;
-  std::shared_lock<std::shared_mutex> lock_;
-  bool dead_;
-};
 }  // namespace
 
 int rebvio_hip_map_place_signature(rebvio_hip_map* m, uint16_t* sig, int* counted) {
   if (!m || !sig || !counted) return fail_msg("map_place_signature: null map, signature or counted", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   if (m->promised.load(std::memory_order_acquire)) return fail_msg((std::string("map_place_signature") + kPlcPromised).c_str(), -7);
@@ -3263,7 +3178,7 @@ int rebvio_hip_map_place_signature(rebvio_hip_map* m, uint16_t* sig, int* counte
   if (rc) return rc;
   // (the row and its counted word lie next to each other: one copy)
   alignas(4) char host[kPlcRowBytes + sizeof(int)];
-  HIPCHK(hipMemcpyAsync(host, c->plc_query, sizeof(host), hipMemcpyDeviceToHost, c->s_trk));
+  HIPCHK(hipMemcpyAsync(host, c->plc.query, sizeof(host), hipMemcpyDeviceToHost, c->s_trk));
   rc = trk_sync(c);
   if (rc) return rc;
   std::memcpy(sig, host, kPlcRowBytes);
@@ -3307,30 +3222,12 @@ int rebvio_hip_place_db_create(rebvio_hip_ctx* c, int cap, rebvio_hip_place_db**
 }
 
 void rebvio_hip_place_db_release(rebvio_hip_place_db* db) {
-  if (!db) return;
-  {
-    const std::shared_ptr<LifeBlock> life = db->life;
-    std::shared_lock<std::shared_mutex> lk(life->mu);
-    if (!life->dead.load(std::memory_order_acquire)) {  // (else: the context is gone, its destroy freed the buffers)
-      rebvio_hip_ctx* c = db->ctx;
-      (void)hipSetDevice(c->device);
-      {
-        std::lock_guard<std::mutex> sl(c->place_mu);
-        for (size_t i = 0; i < c->place_dbs.size(); ++i)
-          if (c->place_dbs[i] == db) {
-            c->place_dbs.erase(c->place_dbs.begin() + (std::ptrdiff_t)i);
-            break;
-          }
-      }
-      db->own.release();  // (hipFree waits for the kernels that still use the buffers)
-    }
-  }
-  delete db;
+  unlist_and_release(&rebvio_hip_ctx::place_dbs, &rebvio_hip_ctx::place_mu, db);
 }
 
 int rebvio_hip_place_db_clear(rebvio_hip_place_db* db) {
   if (!db) return fail_msg("place_db_clear: null database", -3);
-  const DbAlive alive(db);
+  const Alive alive(db);
   if (alive.dead()) return -10;
   db->size = 0;
   db->tags.clear();
@@ -3339,19 +3236,16 @@ int rebvio_hip_place_db_clear(rebvio_hip_place_db* db) {
 
 int rebvio_hip_place_db_size(rebvio_hip_place_db* db) {
   if (!db) return fail_msg("place_db_size: null database", -3);
-  const DbAlive alive(db);
+  const Alive alive(db);
   if (alive.dead()) return -10;
   return db->size;
 }
 
 int rebvio_hip_place_db_add(rebvio_hip_place_db* db, rebvio_hip_map* m, uint64_t tag, int* index) {
   if (!db || !m) return fail_msg("place_db_add: null database or map", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (db->life != m->life) {
-    if (db->life->dead.load(std::memory_order_acquire)) return fail_msg("the place database's context has been destroyed (rebvio_hip_destroy)", -10);
-    return fail_msg("place_db_add: map of another context than the database's", -3);
-  }
+  RCCHK(of_map_context("place_db_add", db, m, "map", " than the database's"));
   rebvio_hip_ctx* c = db->ctx;
   if (m->promised.load(std::memory_order_acquire)) return fail_msg((std::string("place_db_add") + kPlcPromised).c_str(), -7);
   if (db->size >= db->cap) return fail_msg("place_db_add: the database is full", -7);
@@ -3368,7 +3262,7 @@ int rebvio_hip_place_db_add(rebvio_hip_place_db* db, rebvio_hip_map* m, uint64_t
 int rebvio_hip_place_db_add_signature(rebvio_hip_place_db* db, const uint16_t* sig, int counted, uint64_t tag, int* index) {
   if (!db || !sig) return fail_msg("place_db_add_signature: null database or signature", -3);
   if (counted < 0) return fail_msg("place_db_add_signature: negative counted", -3);
-  const DbAlive alive(db);
+  const Alive alive(db);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = db->ctx;
   if (db->size >= db->cap) return fail_msg("place_db_add_signature: the database is full", -7);
@@ -3386,7 +3280,7 @@ int rebvio_hip_place_db_add_signature(rebvio_hip_place_db* db, const uint16_t* s
 
 int rebvio_hip_place_db_entry(rebvio_hip_place_db* db, int index, uint16_t* sig, int* counted, uint64_t* tag) {
   if (!db) return fail_msg("place_db_entry: null database", -3);
-  const DbAlive alive(db);
+  const Alive alive(db);
   if (alive.dead()) return -10;
   if (index < 0 || index >= db->size) return fail_msg("place_db_entry: index outside [0, size)", -3);
   rebvio_hip_ctx* c = db->ctx;
@@ -3406,12 +3300,9 @@ int rebvio_hip_place_db_query(rebvio_hip_place_db* db, rebvio_hip_map* m, int k,
   if (!db || !m || !out || !count) return fail_msg("place_db_query: null database, map, output or count", -3);
   int rc = check_place_query_args("place_db_query", k, exclude_last);
   if (rc) return rc;
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  if (db->life != m->life) {
-    if (db->life->dead.load(std::memory_order_acquire)) return fail_msg("the place database's context has been destroyed (rebvio_hip_destroy)", -10);
-    return fail_msg("place_db_query: map of another context than the database's", -3);
-  }
+  RCCHK(of_map_context("place_db_query", db, m, "map", " than the database's"));
   rebvio_hip_ctx* c = db->ctx;
   if (m->promised.load(std::memory_order_acquire)) return fail_msg((std::string("place_db_query") + kPlcPromised).c_str(), -7);
   const int eligible = db->size - exclude_last;
@@ -3419,7 +3310,7 @@ int rebvio_hip_place_db_query(rebvio_hip_place_db* db, rebvio_hip_map* m, int k,
   HIPCHK(hipSetDevice(c->device));
   rc = enqueue_place_signature(c, m, nullptr, nullptr);
   if (rc) return rc;
-  return run_place_query(db, c->plc_query, eligible, k, out, count);
+  return run_place_query(db, c->plc.query, eligible, k, out, count);
 }
 
 int rebvio_hip_place_db_query_signature(rebvio_hip_place_db* db, const uint16_t* sig, int k, int exclude_last, rebvio_hip_place_match* out,
@@ -3428,16 +3319,15 @@ int rebvio_hip_place_db_query_signature(rebvio_hip_place_db* db, const uint16_t*
   if (!db || !sig || !out || !count) return fail_msg("place_db_query_signature: null database, signature, output or count", -3);
   int rc = check_place_query_args("place_db_query_signature", k, exclude_last);
   if (rc) return rc;
-  const DbAlive alive(db);
+  const Alive alive(db);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = db->ctx;
   const int eligible = db->size - exclude_last;
   if (eligible <= 0) return 0;  // nothing is launched
   HIPCHK(hipSetDevice(c->device));
-  rc = place_scratch(c);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(c->plc_query, sig, kPlcRowBytes, hipMemcpyHostToDevice, c->s_trk));
-  return run_place_query(db, c->plc_query, eligible, k, out, count);
+  RCCHK(place_scratch(c));
+  HIPCHK(hipMemcpyAsync(c->plc.query, sig, kPlcRowBytes, hipMemcpyHostToDevice, c->s_trk));
+  return run_place_query(db, c->plc.query, eligible, k, out, count);
 }
 
 int rebvio_hip_test_place_signature_host(int rows, int cols, const rebvio_hip_keyline* keylines, int n, uint16_t* sig, int* counted) {
@@ -3468,20 +3358,7 @@ void rebvio_hip_default_kf_handover_opts(rebvio_hip_ctx* c, rebvio_hip_kf_handov
 
 namespace {
 int check_kf_handover_args(const char* who, const rebvio_hip_kf_handover_opts& o, int search_range, const double* R, const double* t) {
-  const std::string w(who);
-  if (!R || !t) return fail_msg((w + ": null R or t").c_str(), -3);
-  const int rc = check_cloud_args(who, &o.kf_filter, nullptr);
-  if (rc) return rc;
-  bool fin = true;
-  for (int i = 0; i < 9; ++i) fin = fin && std::isfinite(R[i]);
-  for (int i = 0; i < 3; ++i) fin = fin && std::isfinite(t[i]);
-  if (!fin) return fail_msg((w + ": non-finite R or t").c_str(), -3);
-  if (!(o.gate_sigma > 0.0)) return fail_msg((w + ": gate_sigma must be > 0").c_str(), -3);
-  if (!(o.q_abs >= 0.0)) return fail_msg((w + ": q_abs must be >= 0").c_str(), -3);
-  if (!(o.min_cos >= -1.0 && o.min_cos <= 1.0)) return fail_msg((w + ": min_cos outside [-1, 1]").c_str(), -3);
-  if (o.max_dist < 0 || o.max_dist > search_range) return fail_msg((w + ": max_dist outside 0..search_range").c_str(), -3);
-  if (o.reserved != 0) return fail_msg((w + ": reserved must be 0").c_str(), -3);
-  return 0;
+  return check_kf_depth_args(who, o.kf_filter, nullptr, o.gate_sigma, o.q_abs, o.min_cos, o.max_dist, o.reserved, search_range, R, t);
 }
 }  // namespace
 
@@ -3494,41 +3371,25 @@ int rebvio_hip_kf_snapshot_handover_depth(rebvio_hip_kf_snapshot* dst, rebvio_hi
                                           rebvio_hip_kf_handover* out, int* assoc_host) {
   if (!dst || !src || !m || !out) return fail_msg("kf_snapshot_handover_depth: null snapshot, map or output", -3);
   if (dst == src) return fail_msg("kf_snapshot_handover_depth: dst and src are the same snapshot", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
-  for (rebvio_hip_kf_snapshot* sn : {dst, src})
-    if (sn->life != m->life) {
-      if (sn->life->dead.load(std::memory_order_acquire)) return fail_msg("the snapshot's context has been destroyed (rebvio_hip_destroy)", -10);
-      return fail_msg("kf_snapshot_handover_depth: snapshot of another context", -3);
-    }
+  RCCHK(snapshot_of("kf_snapshot_handover_depth", dst, m));
+  RCCHK(snapshot_of("kf_snapshot_handover_depth", src, m));
   rebvio_hip_ctx* c = m->ctx;
   rebvio_hip_kf_handover_opts o;
   if (opts) o = *opts; else rebvio_hip_default_kf_handover_opts(c, &o);
-  int rc = check_kf_handover_args("kf_snapshot_handover_depth", o, (int)c->P.search_range, R, t);
-  if (rc) return rc;
-  if (!m->df_built || !m->raster_order)
-    return fail_msg("kf_snapshot_handover_depth: the map's distance field is not detection's (none was built, or its keylines were uploaded)", -7);
+  RCCHK(check_kf_handover_args("kf_snapshot_handover_depth", o, (int)c->P.search_range, R, t));
+  RCCHK(needs_detection_field("kf_snapshot_handover_depth", m));
   HIPCHK(hipSetDevice(c->device));
-  rc = snapshot_size(c, src);
-  if (rc) return rc;
+  RCCHK(snapshot_size(c, src));
   const int kf_size = src->n_host;
   std::memset(out, 0, sizeof(*out));
   if (kf_size == 0) return 0;  // nothing to hand over: nothing is launched
-  rc = snapshot_size(c, dst);
-  if (rc) return rc;
+  RCCHK(snapshot_size(c, dst));
   const int dst_size = dst->n_host;
-  const size_t kmax = (size_t)c->P.keylines_max;
-  if (!c->kfh_key) {
-    char* b = nullptr;
-    HIPCHK(c->own.device_bytes(&b, kmax * (sizeof(unsigned long long) + sizeof(kfp::HandoverStage) + sizeof(int)) + 8 * sizeof(int)));
-    c->kfh_key = reinterpret_cast<unsigned long long*>(b);
-    c->kfh_stage = b + kmax * sizeof(unsigned long long);
-    c->kfh_cnt = reinterpret_cast<int*>(b + kmax * (sizeof(unsigned long long) + sizeof(kfp::HandoverStage)));
-    c->kfh_assoc = c->kfh_cnt + 8;
-  }
+  RCCHK(ensure_scratch(c, c->kfh, (size_t)c->P.keylines_max));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready(c->s_trk, m));
-  rebvio_hip_kf_handover res;
   {
     // both snapshots are this call's from the clears to the kernels; in address order: std::mutex is not recursive (dst != src) and
     // two threads may name the pair in opposite roles
@@ -3537,18 +3398,13 @@ int rebvio_hip_kf_snapshot_handover_depth(rebvio_hip_kf_snapshot* dst, rebvio_hi
     if (std::less<std::mutex*>()(second, first)) std::swap(first, second);
     std::lock_guard<std::mutex> l1(*first);
     std::lock_guard<std::mutex> l2(*second);
-    if (dst_size > 0) HIPCHK(hipMemsetAsync(c->kfh_key, 0xFF, (size_t)dst_size * sizeof(unsigned long long), c->s_trk));
-    HIPCHK(hipMemsetAsync(c->kfh_cnt, 0, 8 * sizeof(int), c->s_trk));
+    if (dst_size > 0) HIPCHK(hipMemsetAsync(c->kfh.key, 0xFF, (size_t)dst_size * sizeof(unsigned long long), c->s_trk));
+    HIPCHK(hipMemsetAsync(c->kfh.cnt, 0, 8 * sizeof(int), c->s_trk));
     launch_kf_handover(c->s_trk, c->K, m->d, kf_size, src->n_dev, dst_size, dst->n_dev, src->prs, src->matches, src->normals, dst->prs,
-                       dst->matches, o, R, t, c->kfh_key, c->kfh_stage, c->kfh_cnt, c->kfh_assoc);
+                       dst->matches, o, R, t, c->kfh.key, c->kfh.stage, c->kfh.cnt, c->kfh.assoc);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemcpyAsync(&res, c->kfh_cnt, sizeof(res), hipMemcpyDeviceToHost, c->s_trk));
-  if (assoc_host) HIPCHK(hipMemcpyAsync(assoc_host, c->kfh_assoc, (size_t)kf_size * sizeof(int), hipMemcpyDeviceToHost, c->s_trk));
-  rc = trk_sync(c);
-  if (rc) return rc;
-  *out = res;
-  return 0;
+  return fetch_counted(c, c->kfh.cnt, c->kfh.assoc, kf_size, out, assoc_host);
 }
 
 int rebvio_hip_test_kf_handover_host(float fm, float cx, float cy, int rows, int cols, int search_range, const float* src_prs4,
@@ -3592,33 +3448,6 @@ static_assert(sizeof(rebvio_hip_chain_ref) == 16 && sizeof(rebvio_hip_polyline) 
               "16-byte records: one load, one store");
 static_assert(sizeof(rebvio_hip_polyline_opts) == 24, "filter, two ints");
 
-// Scratch of the edge chains and polylines, allocated at the first call that reaches the device
-int ech_scratch(rebvio_hip_ctx* c) {
-  if (c->ech_buf) return 0;
-  const size_t kp = (size_t)div_up(c->P.keylines_max, 256) * 256;
-  // 16-byte records first, then the 8-byte ones, then the ints
-  const size_t bytes = kp * (2 * sizeof(ech::ChainNode) + sizeof(rebvio_hip_chain_ref) + sizeof(rebvio_hip_cloud_point) +
-                             sizeof(rebvio_hip_polyline) + sizeof(int2) + 4 * sizeof(int)) +
-                       (kp + 4 + 4 * (size_t)kMaxRecBlocks + kChainWords) * sizeof(int);
-  HIPCHK(c->own.device_bytes(&c->ech_buf, bytes));
-  char* b = c->ech_buf;
-  ChainDev& d = c->ech;
-  d.node[0] = b; b += kp * sizeof(ech::ChainNode);
-  d.node[1] = b; b += kp * sizeof(ech::ChainNode);
-  d.refs = reinterpret_cast<rebvio_hip_chain_ref*>(b); b += kp * sizeof(rebvio_hip_chain_ref);
-  d.points = b; b += kp * sizeof(rebvio_hip_cloud_point);
-  d.lines = reinterpret_cast<rebvio_hip_polyline*>(b); b += kp * sizeof(rebvio_hip_polyline);
-  d.refs2 = reinterpret_cast<int2*>(b); b += kp * sizeof(int2);
-  d.succ = reinterpret_cast<int*>(b); b += kp * sizeof(int);
-  d.len = reinterpret_cast<int*>(b); b += kp * sizeof(int);
-  d.start_of = reinterpret_cast<int*>(b); b += kp * sizeof(int);
-  d.order = reinterpret_cast<int*>(b); b += kp * sizeof(int);
-  d.starts = reinterpret_cast<int*>(b); b += (kp + 4) * sizeof(int);
-  d.blk = reinterpret_cast<int*>(b); b += 4 * (size_t)kMaxRecBlocks * sizeof(int);
-  d.words = reinterpret_cast<int*>(b);
-  return 0;
-}
-
 // What both entries do up to their launches: the state rule, the scratch, the waits. The caller holds the map's life block.
 int ech_begin(const char* who, rebvio_hip_map* m) {
   rebvio_hip_ctx* c = m->ctx;
@@ -3626,8 +3455,7 @@ int ech_begin(const char* who, rebvio_hip_map* m) {
     return fail_msg((std::string(who) + ": the map was handed to track_pair_finish_async with R_prior_next and is rotated for the next pair; "
                      "it is available again once the next track_pair_begin has run").c_str(), -7);
   HIPCHK(hipSetDevice(c->device));
-  const int rc = ech_scratch(c);
-  if (rc) return rc;
+  RCCHK(ensure_scratch(c, c->ech, (size_t)c->P.keylines_max, (size_t)kMaxRecBlocks, (size_t)kChainWords));
   wait_enqueued(m);
   HIPCHK(trk_wait_ready_once(c, m));
   return 0;
@@ -3651,7 +3479,7 @@ int rebvio_hip_map_edge_chains(rebvio_hip_map* m, rebvio_hip_chain_ref* refs_hos
                                int cap_chains, int* n_keylines, int* n_chains) {
   if (!m) return fail_msg("map_edge_chains: null map", -3);
   if (cap_keylines < 0 || cap_chains < 0) return fail_msg("map_edge_chains: negative cap", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   if (n_keylines) *n_keylines = 0;
@@ -3689,7 +3517,7 @@ int rebvio_hip_map_edge_polylines(rebvio_hip_map* m, const rebvio_hip_polyline_o
   if (!m) return fail_msg("map_edge_polylines: null map", -3);
   int rc = check_polyline_args("map_edge_polylines", opts, pose, points_host, cap_points, lines_host, cap_lines, n_points, n_lines);
   if (rc) return rc;
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   *n_points = *n_lines = 0;
@@ -3770,7 +3598,7 @@ int rebvio_hip_test_edge_polylines_host(float fm, const rebvio_hip_keyline* keyl
 }
 
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n) {
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));
@@ -3794,7 +3622,7 @@ int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines,
 
 int rebvio_hip_test_map_set_mask(rebvio_hip_map* m, const int* mask) {
   if (!m || !mask) return fail_msg("test_map_set_mask: null map or mask", -3);
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   const size_t Pn = (size_t)c->P.rows * c->P.cols;
@@ -3893,7 +3721,7 @@ int rebvio_hip_distance_field(rebvio_hip_ctx* c, int* id_out, int* dist_out) {
 }
 
 int rebvio_hip_map_distance_field(rebvio_hip_map* m, int* id_out, int* dist_out) {
-  const MapAlive alive(m);
+  const Alive alive(m);
   if (alive.dead()) return -10;
   rebvio_hip_ctx* c = m->ctx;
   HIPCHK(hipSetDevice(c->device));

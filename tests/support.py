@@ -1,5 +1,6 @@
 """What more than one test file uses: constants, bit-level comparison, the numpy reference models the GPU tests compare against
-(and the CPU tests check by hand), the crafted forwardMatch maps, stream and pair drivers, and the backend / B / host_lib fixtures.
+(and the CPU tests check by hand), the crafted forwardMatch maps, stream and pair drivers, the handles and sentences of the
+refusal tables, and the backend / B / host_lib / refusal_scene fixtures.
 
 A plain module, importable as `support` because tests/ is on the path; importing it needs no GPU (torch and rebvio_amd.backend
 are imported inside the functions and fixtures that use them). A test file takes a fixture with
@@ -1091,7 +1092,97 @@ def oracle_fusion(orc_mod, po):
     return np.array(po.V, F32), np.array(po.P_V, F32), np.array(po.R, F32), R0
 
 
+# ---- refusals of the on-demand entries: the sentences, the handles, the assertion ---------------------------
+DEAD_MAP = "the map's context has been destroyed (rebvio_hip_destroy)"
+DEAD_SNAPSHOT = "the snapshot's context has been destroyed (rebvio_hip_destroy)"
+DEAD_PLACE_DB = "the place database's context has been destroyed (rebvio_hip_destroy)"
+
+
+def foreign_snapshot(who):
+    return f"{who}: snapshot of another context"
+
+
+def no_field(who):
+    return f"{who}: the map's distance field is not detection's (none was built, or its keylines were uploaded)"
+
+
+class RefusalScene:
+    """The handles a refusal table names. A live context `ctx` with two detected maps (m, m2) and their snapshots (snap, snap2), a
+    third map whose keylines were uploaded (up: its field is not detection's) and a place database (db); a second live context
+    `other` with a map, its snapshot and a database (fm, fsnap, fdb); the map, snapshot and database of a context that has been
+    destroyed (dm, dsnap, ddb). R, t: a pose; nan_R, inf_t: the same with one entry that is not finite."""
+
+    def __init__(self, B, frames, cam, **kw):
+        self.B = B
+        make = lambda: B.Context(params_for(B, cam, **kw))
+        self.ctx, self.other, gone = make(), make(), make()
+        self.m, self.m2, self.up = [self.ctx.detect_u8(frames[k], k * TS) for k in range(3)]
+        self.up.upload(self.up.keylines())
+        self.snap, self.snap2, self.db = self.m.keyframe_snapshot(), self.m2.keyframe_snapshot(), self.ctx.place_db(4)
+        self.fm = self.other.detect_u8(frames[0], 0)
+        self.fsnap, self.fdb = self.fm.keyframe_snapshot(), self.other.place_db(4)
+        self.dm = gone.detect_u8(frames[0], 0)
+        self.dsnap, self.ddb = self.dm.keyframe_snapshot(), gone.place_db(4)
+        gone.close()
+        self.R, self.t = np.eye(3), np.array([0.01, 0.0, 0.0])
+        self.nan_R, self.inf_t = np.eye(3), np.array([0.0, 0.0, -np.inf])
+        self.nan_R[2, 0] = np.nan
+        self.sr = int(self.ctx.p.search_range)
+
+    def close(self):
+        for h in (self.snap, self.snap2, self.db, self.fsnap, self.fdb, self.dsnap, self.ddb, self.m, self.m2, self.up, self.fm, self.dm):
+            h.release()
+        self.ctx.close()
+        self.other.close()
+
+
+def assert_refused(scene, call, rc, text):
+    """call(scene) - a binding's method, which raises, or an entry of the library itself, which returns its code - is refused with
+    exactly this code and this rebvio_hip_last_error text, and allocates nothing"""
+    B = scene.B
+    live = B.test_live_resources()
+    try:
+        got = call(scene)
+    except B.HipError as e:
+        assert str(e) == f"rebvio_hip error {rc}: {text}", str(e)
+    else:
+        assert got == rc, got
+    assert B.lib().rebvio_hip_last_error().decode() == text
+    assert B.test_live_resources() == live
+
+
+def assert_release_keeps_the_message(B, make):
+    """make(context) -> a KfSnapshot or a PlaceDb: released after its context was destroyed (a husk) and while it lives, the handle's
+    release leaves rebvio_hip_last_error as an earlier refused call left it - a cleanup path does not replace the reason for it"""
+    from rebvio_amd import synth
+    _, cam = synth.render_stream(160, 120, 1)
+    L = B.lib()
+    for destroy_first in (True, False):
+        ctx = B.Context(params_for(B, cam, keylines_ref=600, keylines_max=800))
+        handle = make(ctx)
+        if destroy_first:
+            ctx.close()
+        assert L.rebvio_hip_map_point_cloud(None, None, None, None, 0, None) == -3     # any refused call: its text is the thread's message now
+        text = L.rebvio_hip_last_error().decode()
+        assert text and "destroyed" not in text, text
+        handle.release()
+        assert L.rebvio_hip_last_error().decode() == text
+        ctx.close()
+
+
 # ---- fixtures -----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def refusal_scene(B):
+    """one RefusalScene per test module, on three frames of the 160x120 stream of the keyframe tests"""
+    from rebvio_amd import synth
+    frames, cam = synth.render_stream(160, 120, 3)
+    live = B.test_live_resources()
+    scene = RefusalScene(B, frames, cam, keylines_ref=600, keylines_max=800)
+    yield scene
+    scene.close()
+    assert B.test_live_resources() == live
+
+
 @pytest.fixture(scope="module")
 def backend():
     """the binding without a device: the library built if it is missing, nothing run"""

@@ -12,7 +12,8 @@ import pytest
 
 import depth_prior_ref as R
 from conftest import params_for
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, assert_refused
 from support import (F32, KW_TRACK, assert_keylines_equal, noise_frames, oracle_fusion, rec, same_records, vision_only_fusion,
                      words)
 
@@ -416,3 +417,29 @@ def test_a_stream_without_a_depth_call_is_unchanged(B, small_stream, oracle_runs
     same_records([rec(r, n) for r, n in zip(want["records"], want["sizes"])], got, "no depth")
     assert_keylines_equal(want["keylines"], maps[9].keylines(), what="newest map without depth")
     ctx.close()
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+IMG = "map_fuse_depth_image"
+_depth = lambda s: np.full((s.ctx.rows, s.ctx.cols), 2.0, np.float32)
+_do = lambda s, **kw: s.B.default_depth_prior_opts(**kw)
+_queued = lambda s, m: s.B.lib().rebvio_hip_map_fuse_depth_image_async(s.other.h, m.h, C.c_void_p(256), 0, 1, None)
+REFUSED = {
+    "queued: map of another context": (lambda s: _queued(s, s.m), -3, "map_fuse_depth_image_async: map of another context"),
+    "queued: wins: a destroyed map over another context": (lambda s: _queued(s, s.dm), -10, DEAD_MAP),
+    "destroyed map": (lambda s: s.dm.fuse_depth_image(_depth(s)), -10, DEAD_MAP),
+    "gate_sigma": (lambda s: s.m.fuse_depth_image(_depth(s), opts=_do(s, gate_sigma=0.0)), -3, f"{IMG}: gate_sigma must be > 0"),
+    "q_abs": (lambda s: s.m.fuse_depth_image(_depth(s), opts=_do(s, q_abs=-1.0)), -3, f"{IMG}: q_abs must be >= 0"),
+    "wins: a destroyed map over an option": (lambda s: s.dm.fuse_depth_image(_depth(s), opts=_do(s, q_abs=-1.0)), -10, DEAD_MAP),
+    "wins: the sigmas over gate_sigma": (lambda s: s.m.fuse_depth_image(_depth(s), opts=_do(s, sigma_z0=0.0, sigma_z2=0.0, gate_sigma=0.0)), -3,
+                                         f"{IMG}: sigma_z0 + sigma_z2 must be > 0"),
+    "wins: gate_sigma over q_abs": (lambda s: s.m.fuse_depth_image(_depth(s), opts=_do(s, gate_sigma=0.0, q_abs=-1.0)), -3,
+                                    f"{IMG}: gate_sigma must be > 0"),
+    "wins: q_abs over unit": (lambda s: s.m.fuse_depth_image(_depth(s), opts=_do(s, q_abs=-1.0, unit=0.0)), -3, f"{IMG}: q_abs must be >= 0"),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

@@ -23,7 +23,8 @@ from conftest import params_for
 from kf_align_ref import (DEV_VS_NP, GUARD, OFFSETS, assert_evaluation, cam_of, craft_against, craft_kf_keylines, current_data, data_of, np_kf_align,
                           np_kf_align_sums, offset_guess, same_bytes, unit_of)
 from kf_pose_ref import pose_err, pose_sums, true_motion
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, DEAD_SNAPSHOT, assert_refused, foreign_snapshot, no_field
 from support import F32, TS, assert_keylines_equal, enlarged_stream, rec, rodrigues, same_records, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
@@ -572,3 +573,39 @@ def test_alignment_calls_between_pairs_disturb_nothing(B):
     aligned, kl_aligned = run(True)
     same_records(plain, aligned, "with and without normals and alignment calls")
     assert_keylines_equal(kl_plain, kl_aligned, "final keylines")
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+ALIGN, NORMALS = "map_keyframe_align", "kf_snapshot_add_normals"
+_ao = lambda s, **kw: s.B.default_kf_align_opts(s.ctx, **kw)
+REFUSED = {
+    "destroyed map": (lambda s: s.dm.keyframe_align(s.dsnap), -10, DEAD_MAP),
+    "destroyed snapshot": (lambda s: s.m.keyframe_align(s.dsnap), -10, DEAD_SNAPSHOT),
+    "foreign snapshot": (lambda s: s.m.keyframe_align(s.fsnap), -3, foreign_snapshot(ALIGN)),
+    "no field": (lambda s: s.up.keyframe_align(s.snap), -7, no_field(ALIGN)),
+    "R0 not finite": (lambda s: s.m.keyframe_align(s.snap, None, s.nan_R), -3, f"{ALIGN}: non-finite R0 or t0"),
+    "t0 not finite": (lambda s: s.m.keyframe_align(s.snap, None, None, s.inf_t), -3, f"{ALIGN}: non-finite R0 or t0"),
+    "min_cos above": (lambda s: s.m.keyframe_align(s.snap, _ao(s, min_cos=1.5)), -3, f"{ALIGN}: min_cos outside [-1, 1]"),
+    "min_cos NaN": (lambda s: s.m.keyframe_align(s.snap, _ao(s, min_cos=float("nan"))), -3, f"{ALIGN}: min_cos outside [-1, 1]"),
+    "max_dist below": (lambda s: s.m.keyframe_align(s.snap, _ao(s, max_dist=-1)), -3, f"{ALIGN}: max_dist outside 0..search_range"),
+    "max_dist above": (lambda s: s.m.keyframe_align(s.snap, _ao(s, max_dist=s.sr + 1)), -3, f"{ALIGN}: max_dist outside 0..search_range"),
+    "wins: a foreign snapshot over an option and no field": (lambda s: s.up.keyframe_align(s.fsnap, _ao(s, min_cos=2.0), s.nan_R), -3,
+                                                             foreign_snapshot(ALIGN)),
+    "wins: a destroyed snapshot over an option": (lambda s: s.m.keyframe_align(s.dsnap, _ao(s, max_dist=-1)), -10, DEAD_SNAPSHOT),
+    "wins: a destroyed map over a foreign snapshot": (lambda s: s.dm.keyframe_align(s.snap), -10, DEAD_MAP),
+    "wins: a guess over min_cos": (lambda s: s.m.keyframe_align(s.snap, _ao(s, min_cos=2.0), s.nan_R), -3, f"{ALIGN}: non-finite R0 or t0"),
+    "wins: min_cos over max_dist": (lambda s: s.m.keyframe_align(s.snap, _ao(s, min_cos=2.0, max_dist=-1)), -3,
+                                    f"{ALIGN}: min_cos outside [-1, 1]"),
+    "wins: an option over no field": (lambda s: s.up.keyframe_align(s.snap, _ao(s, max_dist=-1)), -3, f"{ALIGN}: max_dist outside 0..search_range"),
+    "normals: destroyed map": (lambda s: s.dsnap.add_normals(s.dm), -10, DEAD_MAP),
+    "normals: destroyed snapshot": (lambda s: s.dsnap.add_normals(s.m), -10, DEAD_SNAPSHOT),
+    "normals: foreign snapshot": (lambda s: s.fsnap.add_normals(s.m), -3, f"{NORMALS}: map of another context"),
+    "normals: wins: a destroyed map over a foreign snapshot": (lambda s: s.snap.add_normals(s.dm), -10, DEAD_MAP),
+    "normals: download from a destroyed snapshot": (lambda s: s.dsnap.normals(), -10, DEAD_SNAPSHOT),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

@@ -15,7 +15,8 @@ from conftest import params_for
 from kf_align_many_ref import Scene800, cam_of, current_data, np_inliers, seeded_guesses, stream
 from kf_align_ref import GUARD, OFFSETS, craft_against, craft_kf_keylines, offset_guess
 from kf_pose_ref import true_motion
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, DEAD_SNAPSHOT, assert_refused, foreign_snapshot, no_field
 from support import F32, TS, assert_keylines_equal, enlarged_stream, rec, same_records, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
@@ -297,3 +298,33 @@ def test_align_many_calls_between_pairs_disturb_nothing(B):
     aligned, kl_aligned = run(True)
     same_records(plain, aligned, "with and without align_many calls")
     assert_keylines_equal(kl_plain, kl_aligned, "final keylines")
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+MANY = "map_keyframe_align_many"
+_ao = lambda s, **kw: s.B.default_kf_align_opts(s.ctx, **kw)
+_hy = lambda s, *snaps, R0=None: [s.B.kf_hypothesis(sn, R0 if k == len(snaps) - 1 else None, None) for k, sn in enumerate(snaps)]
+REFUSED = {
+    "destroyed map": (lambda s: s.dm.keyframe_align_many(_hy(s, s.dsnap)), -10, DEAD_MAP),
+    "destroyed snapshot, second in the list": (lambda s: s.m.keyframe_align_many(_hy(s, s.snap, s.dsnap)), -10, DEAD_SNAPSHOT),
+    "foreign snapshot, second in the list": (lambda s: s.m.keyframe_align_many(_hy(s, s.snap, s.fsnap)), -3, foreign_snapshot(MANY)),
+    "no field": (lambda s: s.up.keyframe_align_many(_hy(s, s.snap)), -7, no_field(MANY)),
+    "R0 not finite, second in the list": (lambda s: s.m.keyframe_align_many(_hy(s, s.snap, s.snap2, R0=s.nan_R)), -3,
+                                          f"{MANY}: non-finite R0 or t0"),
+    "min_cos below": (lambda s: s.m.keyframe_align_many(_hy(s, s.snap), _ao(s, min_cos=-1.5)), -3, f"{MANY}: min_cos outside [-1, 1]"),
+    "max_dist above": (lambda s: s.m.keyframe_align_many(_hy(s, s.snap), _ao(s, max_dist=s.sr + 1)), -3,
+                       f"{MANY}: max_dist outside 0..search_range"),
+    "wins: a foreign snapshot over an option and no field": (lambda s: s.up.keyframe_align_many(_hy(s, s.snap, s.fsnap, R0=s.nan_R),
+                                                                                               _ao(s, min_cos=2.0)), -3, foreign_snapshot(MANY)),
+    "wins: the first of the list, foreign": (lambda s: s.m.keyframe_align_many(_hy(s, s.fsnap, s.dsnap)), -3, foreign_snapshot(MANY)),
+    "wins: the first of the list, destroyed": (lambda s: s.m.keyframe_align_many(_hy(s, s.dsnap, s.fsnap)), -10, DEAD_SNAPSHOT),
+    "wins: a destroyed map over a foreign snapshot": (lambda s: s.dm.keyframe_align_many(_hy(s, s.snap)), -10, DEAD_MAP),
+    "wins: an option over no field": (lambda s: s.up.keyframe_align_many(_hy(s, s.snap), _ao(s, min_cos=2.0)), -3,
+                                      f"{MANY}: min_cos outside [-1, 1]"),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

@@ -16,7 +16,8 @@ from kf_align_ref import GUARD, craft_against, craft_kf_keylines, unit_of
 from kf_cloud_ref import DEFAULT, ODD, SIZES, assert_cloud_equal, edge_rows, flt_dict, np_kf_cloud, random_pose, random_snapshot
 from kf_fuse_ref import np_kf_fuse, perturbed
 from kf_pose_ref import true_motion
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_SNAPSHOT, assert_refused, assert_release_keeps_the_message
 from support import F32, TS, enlarged_stream, np_passes, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
@@ -414,3 +415,26 @@ def test_a_snapshot_released_right_after_the_queued_call(B):
     q.release()
     other.release()
     ctx.close()
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+REFUSED = {
+    "download": (lambda s: s.dsnap.download(), -10, DEAD_SNAPSHOT),
+    "point_cloud": (lambda s: s.dsnap.point_cloud(cap=4), -10, DEAD_SNAPSHOT),
+    "point_cloud_async": (lambda s: s.dsnap.point_cloud_async(), -10, DEAD_SNAPSHOT),
+    "wins: the filter over a destroyed snapshot": (lambda s: s.dsnap.point_cloud(s.B.default_cloud_filter(rho_min=-1.0), cap=4), -3,
+                                                   "kf_snapshot_point_cloud: filter rho_min must be > 0"),
+    "wins: the filter over a destroyed snapshot, queued": (lambda s: s.dsnap.point_cloud_async(s.B.default_cloud_filter(rho_min=-1.0)), -3,
+                                                           "kf_snapshot_point_cloud_async: filter rho_min must be > 0"),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])
+
+
+def test_releasing_a_snapshot_leaves_the_last_error_alone(B):
+    """rebvio_hip_kf_snapshot_release, of a husk and of a live snapshot, writes no message"""
+    assert_release_keeps_the_message(B, lambda ctx: ctx.detect_u8(np.full((120, 160), 128, np.uint8), 0).keyframe_snapshot())

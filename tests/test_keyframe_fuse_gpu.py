@@ -20,7 +20,8 @@ from conftest import params_for
 from kf_align_ref import GUARD, OFFSETS, craft_against, craft_kf_keylines, np_kf_align, offset_guess, unit_of
 from kf_fuse_ref import INT_MIN, counts_of, np_kf_fuse, perturbed
 from kf_pose_ref import pose_err, true_motion
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, DEAD_SNAPSHOT, assert_refused, foreign_snapshot, no_field
 from support import F32, TS, enlarged_stream, rec, same_records
 
 pytestmark = pytest.mark.gpu
@@ -432,3 +433,45 @@ def test_fusion_calls_between_pairs_disturb_nothing(B):
     fused, kl_fused = run(True)
     same_records(plain, fused, "with and without alignment and fusion calls")
     assert kl_plain.tobytes() == kl_fused.tobytes()
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+FUSE = "kf_snapshot_fuse_depth"
+_fo = lambda s, **kw: s.B.default_kf_fuse_opts(s.ctx, **kw)
+_fu = lambda snap, m, s, R="R", t="t", **kw: snap.fuse_depth(m, getattr(s, R) if R else None, getattr(s, t) if t else None, _fo(s, **kw) if kw else None)
+REFUSED = {
+    "destroyed map": (lambda s: _fu(s.dsnap, s.dm, s), -10, DEAD_MAP),
+    "destroyed snapshot": (lambda s: _fu(s.dsnap, s.m, s), -10, DEAD_SNAPSHOT),
+    "foreign snapshot": (lambda s: _fu(s.fsnap, s.m, s), -3, foreign_snapshot(FUSE)),
+    "no field": (lambda s: _fu(s.snap, s.up, s), -7, no_field(FUSE)),
+    "null R": (lambda s: _fu(s.snap, s.m, s, R=None), -3, f"{FUSE}: null R or t"),
+    "null t": (lambda s: _fu(s.snap, s.m, s, t=None), -3, f"{FUSE}: null R or t"),
+    "R not finite": (lambda s: _fu(s.snap, s.m, s, R="nan_R"), -3, f"{FUSE}: non-finite R or t"),
+    "t not finite": (lambda s: _fu(s.snap, s.m, s, t="inf_t"), -3, f"{FUSE}: non-finite R or t"),
+    "pixel_sigma": (lambda s: _fu(s.snap, s.m, s, pixel_sigma=0.0), -3, f"{FUSE}: pixel_sigma must be > 0"),
+    "gate_sigma": (lambda s: _fu(s.snap, s.m, s, gate_sigma=0.0), -3, f"{FUSE}: gate_sigma must be > 0"),
+    "q_abs": (lambda s: _fu(s.snap, s.m, s, q_abs=-1.0), -3, f"{FUSE}: q_abs must be >= 0"),
+    "min_cos": (lambda s: _fu(s.snap, s.m, s, min_cos=1.5), -3, f"{FUSE}: min_cos outside [-1, 1]"),
+    "max_dist below": (lambda s: _fu(s.snap, s.m, s, max_dist=-1), -3, f"{FUSE}: max_dist outside 0..search_range"),
+    "max_dist above": (lambda s: _fu(s.snap, s.m, s, max_dist=s.sr + 1), -3, f"{FUSE}: max_dist outside 0..search_range"),
+    "wins: a foreign snapshot over a pose, an option and no field": (lambda s: _fu(s.fsnap, s.up, s, R="nan_R", gate_sigma=0.0), -3,
+                                                                     foreign_snapshot(FUSE)),
+    "wins: a destroyed snapshot over a null pose": (lambda s: _fu(s.dsnap, s.up, s, R=None), -10, DEAD_SNAPSHOT),
+    "wins: a destroyed map over a foreign snapshot": (lambda s: _fu(s.snap, s.dm, s), -10, DEAD_MAP),
+    "wins: a null pose over the filter": (lambda s: _fu(s.snap, s.m, s, R=None, kf_filter=dict(rho_min=-1.0)), -3, f"{FUSE}: null R or t"),
+    "wins: the filter over the pose": (lambda s: _fu(s.snap, s.m, s, R="nan_R", kf_filter=dict(rho_min=-1.0)), -3,
+                                       f"{FUSE}: filter rho_min must be > 0"),
+    "wins: the pose over pixel_sigma": (lambda s: _fu(s.snap, s.m, s, R="nan_R", pixel_sigma=0.0), -3, f"{FUSE}: non-finite R or t"),
+    "wins: pixel_sigma over gate_sigma": (lambda s: _fu(s.snap, s.m, s, pixel_sigma=0.0, gate_sigma=0.0), -3, f"{FUSE}: pixel_sigma must be > 0"),
+    "wins: gate_sigma over q_abs": (lambda s: _fu(s.snap, s.m, s, gate_sigma=0.0, q_abs=-1.0), -3, f"{FUSE}: gate_sigma must be > 0"),
+    "wins: q_abs over min_cos": (lambda s: _fu(s.snap, s.m, s, q_abs=-1.0, min_cos=2.0), -3, f"{FUSE}: q_abs must be >= 0"),
+    "wins: min_cos over max_dist": (lambda s: _fu(s.snap, s.m, s, min_cos=2.0, max_dist=-1), -3, f"{FUSE}: min_cos outside [-1, 1]"),
+    "wins: max_dist over reserved": (lambda s: _fu(s.snap, s.m, s, max_dist=-1, reserved=2), -3, f"{FUSE}: max_dist outside 0..search_range"),
+    "wins: an option over no field": (lambda s: _fu(s.snap, s.up, s, reserved=2), -3, f"{FUSE}: reserved must be 0"),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, assert_refused
 from support import (F32, KF_MATCH_DTYPE, TS, assert_keylines_equal, gyro_rotations, np_kf_matches, rec, same_records, set_forms,
                      state_words, vision_only_fusion)
 
@@ -475,3 +476,18 @@ def test_every_new_entry_gives_its_resources_back(B):
     ctx.keyframe_next()
     ctx.close()
     assert B.test_live_resources() == live
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+_mark = lambda s, m: s.B.lib().rebvio_hip_map_mark_keyframe(s.other.h, m.h)
+_snapshot = lambda s, m: s.B.lib().rebvio_hip_map_keyframe_snapshot(s.other.h, m.h, C.byref(C.c_void_p()))
+REFUSED = {
+    "mark: map of another context": (lambda s: _mark(s, s.m), -3, "map_mark_keyframe: map of another context"),
+    "mark: wins: a destroyed map over another context": (lambda s: _mark(s, s.dm), -10, DEAD_MAP),
+    "snapshot: map of another context": (lambda s: _snapshot(s, s.m), -3, "map_keyframe_snapshot: map of another context"),
+    "snapshot: wins: a destroyed map over another context": (lambda s: _snapshot(s, s.dm), -10, DEAD_MAP),
+}
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

@@ -23,7 +23,8 @@ from kf_align_ref import GUARD, craft_against, craft_kf_keylines
 from kf_fuse_ref import INT_MIN
 from kf_handover_ref import assert_identities, counts_of, guard_min, np_kf_handover
 from kf_pose_ref import true_motion
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, DEAD_SNAPSHOT, assert_refused, foreign_snapshot, no_field
 from support import F32, TS, enlarged_stream, rec, same_records
 
 pytestmark = pytest.mark.gpu
@@ -448,3 +449,45 @@ def test_handover_calls_between_pairs_disturb_nothing(B):
     handed, kl_handed = run(True)
     same_records(plain, handed, "with and without alignment, fusion and hand-over calls")
     assert kl_plain.tobytes() == kl_handed.tobytes()
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+HAND = "kf_snapshot_handover_depth"
+_ho = lambda dst, src, m, s, R="R", t="t", **kw: dst.handover_depth(src, m, getattr(s, R) if R else None, getattr(s, t) if t else None,
+                                                                  s.B.default_kf_handover_opts(s.ctx, **kw) if kw else None)
+REFUSED = {
+    "destroyed map": (lambda s: _ho(s.dsnap, s.snap, s.dm, s), -10, DEAD_MAP),
+    "destroyed successor": (lambda s: _ho(s.dsnap, s.snap, s.m2, s), -10, DEAD_SNAPSHOT),
+    "destroyed source": (lambda s: _ho(s.snap2, s.dsnap, s.m2, s), -10, DEAD_SNAPSHOT),
+    "foreign successor": (lambda s: _ho(s.fsnap, s.snap, s.m2, s), -3, foreign_snapshot(HAND)),
+    "foreign source": (lambda s: _ho(s.snap2, s.fsnap, s.m2, s), -3, foreign_snapshot(HAND)),
+    "no field": (lambda s: _ho(s.snap2, s.snap, s.up, s), -7, no_field(HAND)),
+    "null R": (lambda s: _ho(s.snap2, s.snap, s.m2, s, R=None), -3, f"{HAND}: null R or t"),
+    "R not finite": (lambda s: _ho(s.snap2, s.snap, s.m2, s, R="nan_R"), -3, f"{HAND}: non-finite R or t"),
+    "t not finite": (lambda s: _ho(s.snap2, s.snap, s.m2, s, t="inf_t"), -3, f"{HAND}: non-finite R or t"),
+    "gate_sigma": (lambda s: _ho(s.snap2, s.snap, s.m2, s, gate_sigma=0.0), -3, f"{HAND}: gate_sigma must be > 0"),
+    "q_abs": (lambda s: _ho(s.snap2, s.snap, s.m2, s, q_abs=float("nan")), -3, f"{HAND}: q_abs must be >= 0"),
+    "min_cos": (lambda s: _ho(s.snap2, s.snap, s.m2, s, min_cos=-1.5), -3, f"{HAND}: min_cos outside [-1, 1]"),
+    "max_dist below": (lambda s: _ho(s.snap2, s.snap, s.m2, s, max_dist=-1), -3, f"{HAND}: max_dist outside 0..search_range"),
+    "max_dist above": (lambda s: _ho(s.snap2, s.snap, s.m2, s, max_dist=s.sr + 1), -3, f"{HAND}: max_dist outside 0..search_range"),
+    "wins: the successor, foreign, over the source, destroyed": (lambda s: _ho(s.fsnap, s.dsnap, s.m2, s), -3, foreign_snapshot(HAND)),
+    "wins: the successor, destroyed, over the source, foreign": (lambda s: _ho(s.dsnap, s.fsnap, s.m2, s), -10, DEAD_SNAPSHOT),
+    "wins: a foreign snapshot over a pose, an option and no field": (lambda s: _ho(s.snap2, s.fsnap, s.up, s, R="nan_R", gate_sigma=0.0), -3,
+                                                                     foreign_snapshot(HAND)),
+    "wins: a destroyed map over a foreign snapshot": (lambda s: _ho(s.snap2, s.snap, s.dm, s), -10, DEAD_MAP),
+    "wins: the filter over the pose": (lambda s: _ho(s.snap2, s.snap, s.m2, s, R="nan_R", kf_filter=dict(rho_min=-1.0)), -3,
+                                       f"{HAND}: filter rho_min must be > 0"),
+    "wins: the pose over gate_sigma": (lambda s: _ho(s.snap2, s.snap, s.m2, s, t="inf_t", gate_sigma=0.0), -3, f"{HAND}: non-finite R or t"),
+    "wins: gate_sigma over q_abs": (lambda s: _ho(s.snap2, s.snap, s.m2, s, gate_sigma=0.0, q_abs=-1.0), -3, f"{HAND}: gate_sigma must be > 0"),
+    "wins: q_abs over min_cos": (lambda s: _ho(s.snap2, s.snap, s.m2, s, q_abs=-1.0, min_cos=2.0), -3, f"{HAND}: q_abs must be >= 0"),
+    "wins: min_cos over max_dist": (lambda s: _ho(s.snap2, s.snap, s.m2, s, min_cos=2.0, max_dist=-1), -3, f"{HAND}: min_cos outside [-1, 1]"),
+    "wins: max_dist over reserved": (lambda s: _ho(s.snap2, s.snap, s.m2, s, max_dist=-1, reserved=2), -3,
+                                     f"{HAND}: max_dist outside 0..search_range"),
+    "wins: an option over no field": (lambda s: _ho(s.snap2, s.snap, s.up, s, reserved=2), -3, f"{HAND}: reserved must be 0"),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

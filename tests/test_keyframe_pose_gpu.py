@@ -17,7 +17,8 @@ import pytest
 
 from conftest import params_for
 from kf_pose_ref import craft_arrays, craft_keylines, np_kf_pose, np_kf_pose_sums, off_guess, pose_err, pose_sums
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, DEAD_SNAPSHOT, assert_refused, foreign_snapshot
 from support import F32, TS, assert_keylines_equal, enlarged_stream, np_kf_matches, rec, same_records, ulp_down, ulp_up, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
@@ -479,3 +480,24 @@ def test_pose_along_the_synthetic_stream_and_nothing_disturbed(B):
     posed, kl_posed = run(True)
     same_records(plain, posed, "with and without snapshot and pose calls")
     assert_keylines_equal(kl_plain, kl_posed, "final keylines")
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+POSE = "map_keyframe_pose"
+REFUSED = {
+    "destroyed map": (lambda s: s.dm.keyframe_pose(s.dsnap), -10, DEAD_MAP),
+    "destroyed snapshot": (lambda s: s.m.keyframe_pose(s.dsnap), -10, DEAD_SNAPSHOT),
+    "foreign snapshot": (lambda s: s.m.keyframe_pose(s.fsnap), -3, foreign_snapshot(POSE)),
+    "R0 not finite": (lambda s: s.m.keyframe_pose(s.snap, None, s.nan_R, s.t), -3, f"{POSE}: non-finite R0 or t0"),
+    "t0 not finite": (lambda s: s.m.keyframe_pose(s.snap, None, None, s.inf_t), -3, f"{POSE}: non-finite R0 or t0"),
+    "wins: an option over a guess": (lambda s: s.m.keyframe_pose(s.snap, s.B.default_kf_pose_opts(huber_px=0.0), s.nan_R), -3,
+                                     f"{POSE}: huber_px must be > 0"),
+    "wins: a guess over a destroyed map": (lambda s: s.dm.keyframe_pose(s.fsnap, None, s.nan_R), -3, f"{POSE}: non-finite R0 or t0"),
+    "wins: a destroyed map over a foreign snapshot": (lambda s: s.dm.keyframe_pose(s.snap), -10, DEAD_MAP),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

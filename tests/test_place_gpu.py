@@ -15,7 +15,8 @@ import pytest
 import place_cases as PC
 import place_ref as R
 from conftest import params_for
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, DEAD_PLACE_DB, assert_refused, assert_release_keeps_the_message
 from support import F32, KW_TRACK, noise_frames, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
@@ -490,3 +491,38 @@ def test_signature_at_the_envelope_of_65536_keylines(B):
     assert sizes[0] > 256 and sizes[1] == 0 and got_n == 0 and not got.any(), sizes   # (one edge down the middle: about 1300)
     m.release()
     ctx.close()
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+_sig = lambda: np.zeros(384, np.uint16)
+_other = lambda who: f"{who}: map of another context than the database's"
+REFUSED = {
+    "clear": (lambda s: s.ddb.clear(), -10, DEAD_PLACE_DB),
+    "size": (lambda s: s.B.lib().rebvio_hip_place_db_size(s.ddb.h), -10, DEAD_PLACE_DB),
+    "add_signature": (lambda s: s.ddb.add_signature(_sig()), -10, DEAD_PLACE_DB),
+    "entry": (lambda s: s.ddb.entry(0), -10, DEAD_PLACE_DB),
+    "query_signature": (lambda s: s.ddb.query_signature(_sig()), -10, DEAD_PLACE_DB),
+    "add: destroyed map": (lambda s: s.ddb.add(s.dm), -10, DEAD_MAP),
+    "add: destroyed database": (lambda s: s.ddb.add(s.m), -10, DEAD_PLACE_DB),
+    "add: foreign database": (lambda s: s.fdb.add(s.m), -3, _other("place_db_add")),
+    "query: destroyed map": (lambda s: s.ddb.query(s.dm), -10, DEAD_MAP),
+    "query: destroyed database": (lambda s: s.ddb.query(s.m), -10, DEAD_PLACE_DB),
+    "query: foreign database": (lambda s: s.fdb.query(s.m), -3, _other("place_db_query")),
+    "signature: destroyed map": (lambda s: s.dm.place_signature(), -10, DEAD_MAP),
+    "wins: k over a destroyed database": (lambda s: s.ddb.query(s.m, k=0), -3, "place_db_query: k outside 1..16"),
+    "wins: k over a destroyed database, by signature": (lambda s: s.ddb.query_signature(_sig(), k=17), -3,
+                                                        "place_db_query_signature: k outside 1..16"),
+    "wins: a destroyed database over the index": (lambda s: s.ddb.entry(-1), -10, DEAD_PLACE_DB),
+    "wins: a destroyed map over a foreign database": (lambda s: s.db.add(s.dm), -10, DEAD_MAP),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])
+
+
+def test_releasing_a_database_leaves_the_last_error_alone(B):
+    """rebvio_hip_place_db_release, of a husk and of a live database, writes no message"""
+    assert_release_keeps_the_message(B, lambda ctx: ctx.place_db(4))

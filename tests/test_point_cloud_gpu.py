@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import params_for
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, assert_refused
 from support import CLOUD_DTYPE, F32, KW_C2, enlarged_stream, np_cloud, np_passes, vision_only_fusion
 
 pytestmark = pytest.mark.gpu
@@ -305,3 +306,16 @@ def test_refusals(B, small_stream):
     assert "error -10:" in str(e.value) and "destroyed" in str(e.value)
     q.release()
     m.release()
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+REFUSED = {
+    "queued: map of another context": (lambda s: s.other.point_cloud_async(s.m), -3, "map_point_cloud_async: map of another context"),
+    "queued: wins: a destroyed map over another context": (lambda s: s.other.point_cloud_async(s.dm), -10, DEAD_MAP),
+    "queued: wins: the filter over another context": (lambda s: s.other.point_cloud_async(s.m, s.B.default_cloud_filter(rho_min=-1.0)), -3,
+                                                      "map_point_cloud_async: filter rho_min must be > 0"),
+}
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])

@@ -18,7 +18,8 @@ import pytest
 import stereo_prior_cases as SC
 import stereo_prior_ref as R
 from conftest import params_for
-from support import B  # noqa: F401
+from support import B, refusal_scene  # noqa: F401
+from support import DEAD_MAP, assert_refused
 from support import F32, KW_TRACK, assert_keylines_equal, noise_frames, oracle_fusion, rec, same_records, vision_only_fusion, words
 
 pytestmark = pytest.mark.gpu
@@ -385,3 +386,30 @@ def test_a_stream_without_a_stereo_call_is_unchanged(B, stereo_runs):
     same_records([rec(r, n) for r, n in zip(want["records"], want["sizes"])], got, "no stereo")
     assert_keylines_equal(want["keylines"][9], maps[9].keylines(), what="newest map without stereo")
     ctx.close()
+
+
+# ---- the refusal table: every shared refusal with its code and whole text; which one wins when several apply ------
+
+STEREO = "map_fuse_stereo"
+_so = lambda s, **kw: s.B.default_stereo_prior_opts(s.ctx, baseline=0.1, **kw)
+_queued = lambda s, m, r: s.B.lib().rebvio_hip_map_fuse_stereo_async(s.other.h, m.h, r.h, _so(s))
+REFUSED = {
+    "queued: left map of another context": (lambda s: _queued(s, s.m, s.m2), -3, "map_fuse_stereo_async: left map of another context"),
+    "queued: wins: a destroyed right map over another context": (lambda s: _queued(s, s.m, s.dm), -10, DEAD_MAP),
+    "destroyed left map": (lambda s: s.dm.fuse_stereo(s.m, _so(s)), -10, DEAD_MAP),
+    "destroyed right map": (lambda s: s.m.fuse_stereo(s.dm, _so(s)), -10, DEAD_MAP),
+    "gate_sigma": (lambda s: s.m.fuse_stereo(s.m2, _so(s, gate_sigma=0.0)), -3, f"{STEREO}: gate_sigma must be > 0"),
+    "q_abs": (lambda s: s.m.fuse_stereo(s.m2, _so(s, q_abs=-1.0)), -3, f"{STEREO}: q_abs must be >= 0"),
+    "wins: a destroyed map over an option": (lambda s: s.m.fuse_stereo(s.dm, _so(s, q_abs=-1.0)), -10, DEAD_MAP),
+    "wins: sigma_px over gate_sigma": (lambda s: s.m.fuse_stereo(s.m2, _so(s, sigma_px=0.0, gate_sigma=0.0)), -3,
+                                       f"{STEREO}: sigma_px must be > 0 and finite"),
+    "wins: gate_sigma over ambig_px": (lambda s: s.m.fuse_stereo(s.m2, _so(s, gate_sigma=0.0, ambig_px=-1.0)), -3,
+                                       f"{STEREO}: gate_sigma must be > 0"),
+    "wins: norm_tol over q_abs": (lambda s: s.m.fuse_stereo(s.m2, _so(s, norm_tol=-1.0, q_abs=-1.0)), -3, f"{STEREO}: norm_tol must be >= 0"),
+    "wins: q_abs over reserved": (lambda s: s.m.fuse_stereo(s.m2, _so(s, q_abs=-1.0, reserved=2)), -3, f"{STEREO}: q_abs must be >= 0"),
+}
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusal_table(refusal_scene, case):
+    """every refusal of the table with its return code and its whole rebvio_hip_last_error text; nothing is allocated"""
+    assert_refused(refusal_scene, *REFUSED[case])
