@@ -163,7 +163,10 @@ int rebvio_hip_detect_u8(rebvio_hip_ctx* ctx, const uint8_t* img_host, size_t pi
                          rebvio_hip_map** out);
 /* Lens model of the front end (camera.hpp:39-40,54-58: cv::undistort(in, out, K(fm,0,cx;0,fm,cy), D(k1,k2,p1,p2,k3))).
  * K4 = fx, fy, cx, cy; D5 = k1, k2, p1, p2, k3. Once set, every *_u8 detect entry runs convertTo(CV_32F,3.0) +
- * undistort on the device before the scale space (rebvio.cpp:43-47); all-zero D5 switches it off. Synchronises. */
+ * undistort on the device before the scale space (rebvio.cpp:43-47); all-zero D5 switches it off. Synchronises.
+ * A K4 or D5 word that is not finite, or a focal length that is not positive, is refused with -3 before the context is
+ * touched, an all-zero D5 included: the model in force stays. Source coordinates saturate as OpenCV's maps do (a pixel whose
+ * source lies beyond +-2^31 / 32 px, or is a NaN, reads the constant border 0). */
 int rebvio_hip_set_undistort(rebvio_hip_ctx* ctx, const float K4[4], const float D5[5]);
 /* The front end alone: u8 host frame -> undistorted fp32 host frame (rows*cols floats). Needs a lens model. */
 int rebvio_hip_front_end_u8(rebvio_hip_ctx* ctx, const uint8_t* img_host, float* out_host);

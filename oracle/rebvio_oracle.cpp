@@ -2239,8 +2239,19 @@ float estimate_bias(orc_ctx* c, const float sacc[3], const float facc[3], float 
 // with initUndistortRectifyMap (double arithmetic, normalised x advanced by repeated addition of 1/fx, principal point
 // moved by the stripe offset, coordinates quantised to 1/32 px with cvRound = round-half-even) and calls
 // remap(INTER_LINEAR, BORDER_CONSTANT 0), whose float path weighs the four taps with the table tab_y[k1]*tab_x[k2].
+// Both conversions saturate as initUndistortRectifyMap's do: saturate_cast<int>(u * INTER_TAB_SIZE), a NaN to INT_MIN as
+// cvRound leaves it on x86, then saturate_cast<short>(iu >> INTER_BITS). A coordinate past +-32 768 px therefore reads the
+// border and never wraps back into the image.
 // Parity unpinned (no OpenCV here); exactness of the interpolation itself: every tap*weight product and their sum are
 // exactly representable for 8-bit*3 sources, so only the double-precision map can differ from a real OpenCV.
+namespace {
+int sat_int(double v) {
+  if (!(v > -2147483648.5)) return std::numeric_limits<int>::min();
+  if (v >= 2147483647.5) return std::numeric_limits<int>::max();
+  return (int)std::lrint(v);
+}
+short sat_short(int v) { return (short)std::min(std::max(v, -32768), 32767); }
+}  // namespace
 extern "C" void orc_front_end_u8(orc_ctx* c, const uint8_t* img, const float K4[4], const float D5[5], float* out) {
   const int R = c->p.rows, C = c->p.cols;
   std::vector<float> src((size_t)R * C);
@@ -2270,9 +2281,9 @@ extern "C" void orc_front_end_u8(orc_ctx* c, const uint8_t* img, const float K4[
         const double xd = x * kr + p1 * _2xy + p2 * (r2 + 2 * x2);
         const double yd = yy * kr + p1 * (r2 + 2 * y2) + p2 * _2xy;
         const double u = fx * xd + u0, v = fy * yd + v0;
-        const int iu = (int)std::lrint(u * 32), iv = (int)std::lrint(v * 32);
-        m1[((size_t)i * C + j) * 2] = (short)(iu >> 5);
-        m1[((size_t)i * C + j) * 2 + 1] = (short)(iv >> 5);
+        const int iu = sat_int(u * 32), iv = sat_int(v * 32);
+        m1[((size_t)i * C + j) * 2] = sat_short(iu >> 5);
+        m1[((size_t)i * C + j) * 2 + 1] = sat_short(iv >> 5);
         m2[(size_t)i * C + j] = (unsigned short)((iv & 31) * 32 + (iu & 31));
       }
     }

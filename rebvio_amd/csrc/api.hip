@@ -1640,6 +1640,10 @@ int rebvio_hip_detect_px_masked_device(rebvio_hip_ctx* c, const void* frame_dev,
 }
 
 int rebvio_hip_set_undistort(rebvio_hip_ctx* c, const float K4[4], const float D5[5]) {
+  // refused before the context is touched (the model in force stays), an all-zero D5 included; a word that is not finite first
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(i < 4 ? K4[i] : D5[i - 4])) return fail_msg("set_undistort: K4 and D5 must be finite", -3);
+  if (!(K4[0] > 0.0f) || !(K4[1] > 0.0f)) return fail_msg("set_undistort: focal lengths must be positive", -3);
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipDeviceSynchronize());  // no frame in flight may still read the old map
   bool any = false;
@@ -1648,7 +1652,6 @@ int rebvio_hip_set_undistort(rebvio_hip_ctx* c, const float K4[4], const float D
     c->own.drop(&c->undist_map);
     return 0;
   }
-  if (!(K4[0] > 0.0f) || !(K4[1] > 0.0f)) return fail_msg("set_undistort: focal lengths must be positive", -3);
   const size_t Pn = (size_t)c->P.rows * c->P.cols;
   std::vector<int> map(2 * Pn);
   hm::undistort_fixed_map(c->P.rows, c->P.cols, K4[0], K4[1], K4[2], K4[3], D5[0], D5[1], D5[2], D5[3], D5[4], map.data());

@@ -443,6 +443,13 @@ RH_HD inline void gyro_bias_correction(float X[6], float Wx[36], M3& Wb, const M
 // the reference calls it (camera.hpp:39-40,54-58): OpenCV builds CV_16SC2 maps in double, stripe by stripe
 // (stripe = max(1, 4096/cols) rows, principal point shifted by the stripe's first row), u and v quantised to 1/32 pixel
 // with round-half-even; remap then interpolates bilinearly with constant-zero border. out[2*i] = iu, out[2*i+1] = iv.
+// The words saturate to int (saturate_cast<int>(u * INTER_TAB_SIZE); a NaN gives INT_MIN, as cvRound leaves it on x86):
+// every image this library accepts is narrower than 2^26, so a saturated word's taps are all outside and read the border.
+inline int saturate_fixed(double v) {
+  if (!(v > -2147483648.5)) return std::numeric_limits<int>::min();  // (a NaN fails the test too)
+  if (v >= 2147483647.5) return std::numeric_limits<int>::max();
+  return (int)std::nearbyint(v);
+}
 inline void undistort_fixed_map(int rows, int cols, double fx, double fy, double cx, double cy, double k1, double k2, double p1,
                                 double p2, double k3, int* out) {
   const int stripe = std::min(std::max(1, (1 << 12) / std::max(cols, 1)), rows);
@@ -462,8 +469,8 @@ inline void undistort_fixed_map(int rows, int cols, double fx, double fy, double
         const double xd = x * kr + p1 * xy2 + p2 * (r2 + 2 * x2);
         const double yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2;
         const double u = fx * xd + cx, v = fy * yd + cy;
-        o[2 * j] = (int)std::nearbyint(u * 32.0);
-        o[2 * j + 1] = (int)std::nearbyint(v * 32.0);
+        o[2 * j] = saturate_fixed(u * 32.0);
+        o[2 * j + 1] = saturate_fixed(v * 32.0);
       }
     }
   }

@@ -88,7 +88,8 @@ rebvio_hip_ctx* Session::ctx() {
   std::lock_guard<std::mutex> g(mu_);
   if (!ctx_) {
     check("rebvio_hip_create", rebvio_hip_create(&p_, &ctx_));
-    check("rebvio_hip_set_undistort", rebvio_hip_set_undistort(ctx_, K4_, D5_));
+    if (hasDistortion())  // (a fresh context has no model; the entry also checks the intrinsics of an all-zero D5)
+      check("rebvio_hip_set_undistort", rebvio_hip_set_undistort(ctx_, K4_, D5_));
   }
   return ctx_;
 }

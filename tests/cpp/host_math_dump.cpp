@@ -9,6 +9,7 @@
 //   bias  : n x (sacc3 facc3 kP Rot9 Qg9 Qrot9 Qbias9 QKp Rg g_norm Rs9 Rf9 Wvw36 | X7 P49 g_est3 b_est3 Xvw6)
 //                                                          -> n x (K | X7 P49 g_est3 b_est3 Xvw6)   (Core::estimateBias; the
 //           record layout of REBVIO_DUMP_FUSION, rebvio_amd/host/rebvio.cpp)
+//   undistort : rows cols fm cx cy k1 k2 p1 p2 k3 img[rows*cols]  -> Camera::undistort(img)[rows*cols]
 //   so3   : w3 a3 b3                                       -> exp(w)9 ln(exp(w))3 R(a->b)9 hostmath exp(w)9
 #include <cstdio>
 #include <cstring>
@@ -149,6 +150,16 @@ int main(int argc, char** argv) {
     const hm::M3 H = hm::so3_exp(p);
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) out.push_back(H.a[i][j]);
+  } else if (mode == "undistort") {
+    if (in.size() < 10) return 3;
+    const int rows = (int)p[0], cols = (int)p[1];
+    if (in.size() != 10 + (size_t)rows * cols) return 3;
+    Camera cam(rows, cols, p[2], p[2], p[3], p[4]);
+    cam.k1_ = p[5]; cam.k2_ = p[6]; cam.p1_ = p[7]; cam.p2_ = p[8]; cam.k3_ = p[9];
+    cv::Mat img(rows, cols, CV_32FC1);
+    for (int i = 0; i < rows; ++i) std::memcpy(img.ptr<float>(i), p + 10 + (size_t)i * cols, cols * sizeof(float));
+    cv::Mat und = cam.undistort(img);
+    for (int i = 0; i < rows; ++i) out.insert(out.end(), und.ptr<float>(i), und.ptr<float>(i) + cols);
   } else {
     return 2;
   }
