@@ -186,6 +186,15 @@ class EdgeMap {
   EdgeChains edgeChains();
   EdgePolylines edgePolylines(const rebvio::types::PolylineOpts& opts = rebvio::types::PolylineOpts(),
                               const rebvio::types::CloudPose& pose = rebvio::types::CloudPose());
+  // addition: the polylines split where they bend, each straight piece with two 3D end points whose depths are fitted to all of
+  // its keylines (rebvio_hip_map_edge_segments defines it; synchronous, from the tracking thread, like edgePolylines). The kept
+  // segments in point order and the counts of everything.
+  struct EdgeSegments {
+    std::vector<rebvio::types::LineSegment> segments;
+    rebvio::types::SegmentCounts counts{};
+  };
+  EdgeSegments edgeSegments(const rebvio::types::SegmentOpts& opts = rebvio::types::SegmentOpts(),
+                            const rebvio::types::CloudPose& pose = rebvio::types::CloudPose());
   // addition: a registered depth image folded into this map's rho / sigma_rho, one Kalman update per keyline
   // (rebvio_hip_map_fuse_depth_image defines it and says where in a stream it belongs: after the map has been a pair's new map -
   // or right after detection for a stream's first map - and before it serves as an old map; synchronous, from the tracking

@@ -116,6 +116,11 @@ struct PlyEdge {
   int vertex1, vertex2;
 };
 std::vector<PlyVertex> readPolylinesPly(const std::string& path, std::vector<PlyEdge>* edges, uint64_t* ts_us = nullptr);
+// Straight segments (EdgeMap::edgeSegments) as a PLY file with the polyline file's elements: two vertices (xyz0, xyz1; intensity =
+// the end's sigma_rho) and one edge per depth-valid segment, in order; segments without a valid depth have no 3D end points and are
+// left out. The comment line says "rebvio segments". readSegmentsPly accepts what writeSegmentsPly writes, nothing else.
+void writeSegmentsPly(const std::string& path, const rebvio::types::LineSegment* segments, size_t n, uint64_t ts_us = 0);
+std::vector<PlyVertex> readSegmentsPly(const std::string& path, std::vector<PlyEdge>* edges, uint64_t* ts_us = nullptr);
 
 // Plays frames [first, first+count) in time order: every IMU sample with ts <= the frame's stamp is delivered before the
 // frame (a time-ordered bag delivers them that way, ros_rebvio.cpp:108-121). Returns the number of frames delivered.

@@ -61,6 +61,13 @@ class Rebvio {
   // before the first frame is handed in.
   void registerEdgePolylineCallback(std::function<void(const rebvio::types::EdgePolylines&)> cb,
                                     rebvio::types::PolylineOpts opts = rebvio::types::PolylineOpts());
+  // addition: the straight segments of every published pair's new map (EdgeMap::edgeSegments; rebvio_hip_map_edge_segments defines
+  // a segment and its fitted end depths), with the pose, the thread, the order (behind the polyline callbacks of the record) and
+  // the rules of an edge-polyline callback: synchronous, the next pair's first rotation not fused into this pair's last kernel,
+  // the odometry unchanged by a digit. Without one the thread runs exactly the calls it ran. Register before the first frame is
+  // handed in.
+  void registerEdgeSegmentCallback(std::function<void(const rebvio::types::EdgeSegments&)> cb,
+                                   rebvio::types::SegmentOpts opts = rebvio::types::SegmentOpts());
   // addition: keyframes (rebvio_hip.h "Keyframes"). requestKeyframe: the newest tracked map becomes the keyframe - it is marked
   // (EdgeMap::markKeyframe) behind the second half of the pair being tracked when the request is seen, in front of the next pair's
   // first half; callable from any thread. The keyframe callback is called once per published odometry record, right after the
@@ -223,6 +230,11 @@ class Rebvio {
     rebvio::types::PolylineOpts opts;
   };
   std::vector<EdgePolylineCallback> edge_polyline_callbacks_;
+  struct EdgeSegmentCallback {
+    std::function<void(const rebvio::types::EdgeSegments&)> cb;
+    rebvio::types::SegmentOpts opts;
+  };
+  std::vector<EdgeSegmentCallback> edge_segment_callbacks_;
   std::vector<std::function<void(uint64_t, int, int)>> keyframe_callbacks_;
   std::vector<std::function<void(uint64_t, const rebvio::types::KfPose&)>> keyframe_pose_callbacks_;
   std::vector<std::function<void(uint64_t, const std::vector<rebvio::types::PlaceMatch>&)>> place_callbacks_;

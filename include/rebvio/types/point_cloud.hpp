@@ -174,6 +174,33 @@ struct Polyline {
 };
 static_assert(sizeof(Polyline) == 16, "Polyline must stay layout-compatible with rebvio_hip_polyline");
 
+// Straight segments of the polylines (EdgeMap::edgeSegments), layout-compatible with the C-ABI's rebvio_hip_segment_opts,
+// rebvio_hip_line_segment and rebvio_hip_segment_counts; rebvio_hip.h defines the split rounds, a kept segment and the depth fit.
+struct SegmentOpts {
+  PolylineOpts poly;      // the polylines that are split
+  float tol{1.0f};        // px: the largest deviation from its chord a segment keeps
+  float min_length{4.0f}; // px between the end points of a kept segment
+  int min_points{8};      // >= 2: points of a kept segment, both ends counted
+  int max_rounds{16};     // 1..32 split rounds
+};
+static_assert(sizeof(SegmentOpts) == 40, "SegmentOpts must stay layout-compatible with rebvio_hip_segment_opts");
+struct LineSegment {
+  float xyz0[3], xyz1[3];  // the end points, posed as a cloud's points (zeros without a valid depth)
+  float uv0[2], uv1[2];    // their pos_img
+  float rho0, rho1, sigma_rho0, sigma_rho1;  // the fitted inverse depths at the ends and their standard deviations
+  float max_dev2;          // px^2: the largest squared deviation of a member from the chord
+  float chi2;              // the fit's weighted residual sum
+  int first_point;         // index of the first end in EdgePolylines::points under the same options
+  int points;              // members, both ends counted
+  int line;                // index of its line
+  int flags;               // bit 0: depth valid; bit 1: unresolved (max_rounds did not suffice)
+};
+static_assert(sizeof(LineSegment) == 80, "LineSegment must stay layout-compatible with rebvio_hip_line_segment");
+struct SegmentCounts {
+  int segments_all, kept, depth_valid, unresolved, rounds_used, points, lines, reserved;
+};
+static_assert(sizeof(SegmentCounts) == 32, "SegmentCounts must stay layout-compatible with rebvio_hip_segment_counts");
+
 // What a point-cloud or keyframe-cloud callback of rebvio::Rebvio receives; `points` is valid during the callback only.
 struct PointCloud {
   uint64_t ts_us;            // the odometry record's stamp (= the map's); keyframe cloud: the stamp of the record the keyframe was marked on
@@ -191,6 +218,15 @@ struct EdgePolylines {
   size_t size;
   const Polyline* lines;
   size_t num_lines;
+};
+
+// What an edge-segment callback of rebvio::Rebvio receives; the array is valid during the callback only.
+struct EdgeSegments {
+  uint64_t ts_us;               // the odometry record's stamp (= the map's)
+  CloudPose pose;               // R_global, Pos, K of that record: the end points are metric, in the odometry's frame
+  const LineSegment* segments;  // the kept segments in point order
+  size_t size;
+  SegmentCounts counts;
 };
 
 }  // namespace types

@@ -47,7 +47,9 @@ extern "C" {
  *    rebvio_hip_stereo_prior_last_counts, their structs rebvio_hip_stereo_prior_opts / rebvio_hip_stereo_prior_counts and the test
  *    hooks rebvio_hip_test_stereo_prior_host / rebvio_hip_test_map_set_mask; place recognition rebvio_hip_map_place_signature,
  *    rebvio_hip_place_db_create / _release / _clear / _size / _add / _add_signature / _entry / _query / _query_signature, their
- *    struct rebvio_hip_place_match and the test hooks rebvio_hip_test_place_signature_host / rebvio_hip_test_place_query_host. */
+ *    struct rebvio_hip_place_match and the test hooks rebvio_hip_test_place_signature_host / rebvio_hip_test_place_query_host; the
+ *    straight segments rebvio_hip_default_segment_opts, rebvio_hip_map_edge_segments, their structs rebvio_hip_segment_opts /
+ *    rebvio_hip_line_segment / rebvio_hip_segment_counts and the test hook rebvio_hip_test_edge_segments_host. */
 #define REBVIO_HIP_ABI_VERSION 3
 
 /* Host mirror of one keyline: field-for-field rebvio::types::KeyLine
@@ -358,6 +360,72 @@ int rebvio_hip_test_edge_chains_host(const int* id_prev, const int* id_next, int
 int rebvio_hip_test_edge_polylines_host(float fm, const rebvio_hip_keyline* keylines, int n, const rebvio_hip_polyline_opts* opts,
                                         const rebvio_hip_cloud_pose* pose, rebvio_hip_cloud_point* points, int* refs2, int cap_points,
                                         rebvio_hip_polyline* lines, int cap_lines, int* n_points, int* n_lines);
+
+/* Straight segments: the polylines split where they bend, each straight piece with two 3D end points whose depths come from all of
+ * the piece's keylines at once (along the image of a 3D straight line inverse depth is an affine function of image position).
+ * Input: the polylines of the map under opts.poly. Points are 0..np-1 in slot order, lines are the maximal runs, q[p] is the pos_img
+ * of point p's keyline. A line of one point has no segment; a closed line is treated as the open run from its first to its last point.
+ * State: every point is a vertex, or interior to a segment [a, b] with a < p < b. Initially a line's first and last points are vertices
+ * and every other point is interior to [first, last].
+ * One split round, for every interior point p - every * / + - is one fp32 operation in this order, nothing contracted:
+ *   ex = q[b].x - q[a].x; ey = q[b].y - q[a].y; px = q[p].x - q[a].x; py = q[p].y - q[a].y;
+ *   l2 = ex*ex + ey*ey; cr = ex*py - ey*px;
+ *   d2 = (l2 == 0) ? px*px + py*py : (cr*cr) / l2; if (!(d2 >= 0)) d2 = 0;          (a NaN position never splits)
+ * The segment's winner is the point with the largest d2, a tie goes to the lowest p: the 64-bit maximum of the keys
+ * (bits(d2) << 32) | (0xFFFFFFFF - p), which are distinct - the result does not depend on the order the maximum is taken in. If the
+ * winner's d2 > tol * tol (one fp32 multiply) the winner m becomes a vertex: points of (a, m) get b = m, points of (m, b) get a = m.
+ * Rounds are level-synchronous: every segment that exists at the start of a round is tested once in it. max_rounds rounds are
+ * launched; rounds_used is the number of rounds in which something split. After the last round one more measuring pass leaves every
+ * segment's max_dev2 (its winner's d2, or 0 with no interior point); the segment is unresolved if max_dev2 is still > tol * tol.
+ * Segments are numbered in point order: every vertex that is not its line's last point begins one; adjacent segments share their
+ * vertex. A segment is kept when points = b - a + 1 >= min_points and l2 >= min_length * min_length (one fp32 multiply); only kept
+ * segments are emitted, in order.
+ * Depth fit of a kept segment over its members i = 0..points-1 (p = a + i, both ends included). In fp32: t = (px*ex + py*ey) / l2.
+ * Then in fp64: sg = fabsf(sigma_rho); if (!(sg >= 1e-6f)) sg = 1e-6f; w = 1.0 / ((double)sg * sg); r = (double)rho;
+ *   wt = w*t; wr = w*r; the six terms are w, wt, wt*t, wr, wt*r, wr*r and their sums Sw, Swt, Swtt, Swr, Swtr, Swrr.
+ * Each sum is 16 partial sums: partial j adds the members i = j, j+16, ... in ascending order, starting from +0.0; the 16 partials are
+ * combined as the pairwise tree ((p0+p1)+(p2+p3)) + ... - this order is part of the definition.
+ *   det = Sw*Swtt - Swt*Swt; r0 = (Swtt*Swr - Swt*Swtr) / det; sl = (Sw*Swtr - Swt*Swr) / det; r1 = r0 + sl;
+ *   v0 = Swtt / det; v1 = ((Swtt - 2*Swt) + Sw) / det; chi2 = Swrr - (r0*Swr + sl*Swtr); if (!(chi2 > 0)) chi2 = 0;
+ * Depth valid (positive tests, a NaN fails): det > 0, v0 >= 0, v1 >= 0 and (float)r0, (float)r1 both in the filter's
+ * [rho_min, rho_max]. When valid rho0 / rho1 = (float)r0 / r1, sigma_rho0 / 1 = (float)sqrt(v0 / v1) and xyz0 / xyz1 = the point of
+ * a map's cloud at q[a] / q[b] with rho0 / rho1 (same formula, operation order and pose); otherwise those ten floats are 0.
+ * counts: segments_all and unresolved count every segment, kept and depth_valid the kept ones (whatever cap_segments is); points and
+ * lines are the polylines' counts. min(kept, cap_segments) records are written; a cap below the count is no error. opts NULL = the
+ * defaults (the polyline defaults, tol 1, min_length 4, min_points 8, max_rounds 16); pose NULL = identity. -3, before the device is
+ * touched: everything rebvio_hip_map_edge_polylines refuses in opts.poly and the pose, a negative or NaN tol or min_length,
+ * min_points < 2, max_rounds outside 1..32, null counts, a negative cap_segments, null segs_host with cap_segments > 0. Otherwise
+ * the rules of rebvio_hip_map_edge_polylines: synchronous, track-side, -7, -10.
+ * Launches, fixed per context and max_rounds whatever the map holds: the polylines' R + 8, then 2 * max_rounds + 5 (k_seg_init,
+ * max_rounds x (k_seg_far + k_seg_split), the measuring k_seg_far, k_seg_count, k_seg_emit, k_seg_fit). A round behind a round
+ * in which nothing split returns at once. Scratch is one more allocation per context, made at this entry's first call that
+ * reaches the device (about 132 bytes per keylines_max). */
+typedef struct rebvio_hip_segment_opts {
+  rebvio_hip_polyline_opts poly;
+  float tol;        /* px: the largest deviation a segment keeps */
+  float min_length; /* px: between the two end points */
+  int min_points;   /* >= 2 */
+  int max_rounds;   /* 1..32 */
+} rebvio_hip_segment_opts;
+typedef struct rebvio_hip_line_segment { /* 80 bytes */
+  float xyz0[3], xyz1[3];
+  float uv0[2], uv1[2]; /* q[a], q[b] */
+  float rho0, rho1, sigma_rho0, sigma_rho1, max_dev2, chi2;
+  int first_point; /* a: index into the polylines' points */
+  int points;
+  int line;
+  int flags; /* bit 0: depth valid; bit 1: unresolved */
+} rebvio_hip_line_segment;
+typedef struct rebvio_hip_segment_counts {
+  int segments_all, kept, depth_valid, unresolved, rounds_used, points, lines, reserved;
+} rebvio_hip_segment_counts;
+void rebvio_hip_default_segment_opts(rebvio_hip_segment_opts* o);
+int rebvio_hip_map_edge_segments(rebvio_hip_map* map, const rebvio_hip_segment_opts* opts, const rebvio_hip_cloud_pose* pose,
+                                 rebvio_hip_line_segment* segs_host, int cap_segments, rebvio_hip_segment_counts* counts);
+/* Test hook: the same statements on the host (rebvio_amd/csrc/edge_segments.hpp) over the host polylines of n keylines. */
+int rebvio_hip_test_edge_segments_host(float fm, const rebvio_hip_keyline* keylines, int n, const rebvio_hip_segment_opts* opts,
+                                       const rebvio_hip_cloud_pose* pose, rebvio_hip_line_segment* segs, int cap_segments,
+                                       rebvio_hip_segment_counts* counts);
 
 /* Keyframes. Every keyline carries match_id_keyframe, "ID of the matching keyline in the last keyframe" (types/keyline.hpp:39):
  * forwardMatch and directedMatch copy it from the matched keyline of the old map (edge_map.cpp:93,210) and directedMatch counts the

@@ -40,6 +40,12 @@ assert CHAIN_REF_DTYPE.itemsize == 16
 POLYLINE_DTYPE = np.dtype([("first_point", "<i4"), ("points", "<i4"), ("head", "<i4"), ("flags", "<i4")])
 assert POLYLINE_DTYPE.itemsize == 16
 
+# rebvio_hip_line_segment: one straight segment of Map.edge_segments; flags bit 0 = depth valid, bit 1 = unresolved
+LINE_SEGMENT_DTYPE = np.dtype([("xyz0", "<f4", (3,)), ("xyz1", "<f4", (3,)), ("uv0", "<f4", (2,)), ("uv1", "<f4", (2,)), ("rho0", "<f4"),
+                               ("rho1", "<f4"), ("sigma_rho0", "<f4"), ("sigma_rho1", "<f4"), ("max_dev2", "<f4"), ("chi2", "<f4"),
+                               ("first_point", "<i4"), ("points", "<i4"), ("line", "<i4"), ("flags", "<i4")])
+assert LINE_SEGMENT_DTYPE.itemsize == 80
+
 
 class Params(C.Structure):
     _fields_ = [
@@ -82,6 +88,20 @@ class CloudPose(C.Structure):
 class PolylineOpts(C.Structure):
     """rebvio_hip_polyline_opts (Map.edge_polylines); defaults from default_polyline_opts"""
     _fields_ = [("filter", CloudFilter), ("min_chain_length", C.c_int), ("reserved", C.c_int)]
+
+
+class SegmentOpts(C.Structure):
+    """rebvio_hip_segment_opts (Map.edge_segments); defaults from default_segment_opts"""
+    _fields_ = [("poly", PolylineOpts), ("tol", C.c_float), ("min_length", C.c_float), ("min_points", C.c_int), ("max_rounds", C.c_int)]
+
+
+class SegmentCounts(C.Structure):
+    """rebvio_hip_segment_counts: what Map.edge_segments found, whatever the cap let through"""
+    _fields_ = [("segments_all", C.c_int), ("kept", C.c_int), ("depth_valid", C.c_int), ("unresolved", C.c_int),
+                ("rounds_used", C.c_int), ("points", C.c_int), ("lines", C.c_int), ("reserved", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class KfMatch(C.Structure):
@@ -230,6 +250,10 @@ SIGNATURES = {
     "rebvio_hip_test_edge_chains_host": (C.c_int, [_ip, _ip, C.c_int, _vp, C.c_int, _ip, _ip, C.c_int, _ip, _ip]),
     "rebvio_hip_test_edge_polylines_host": (C.c_int, [C.c_float, _vp, C.c_int, C.POINTER(PolylineOpts), C.POINTER(CloudPose), _vp, _ip,
                                                       C.c_int, _vp, C.c_int, _ip, _ip]),
+    "rebvio_hip_default_segment_opts": (None, [C.POINTER(SegmentOpts)]),
+    "rebvio_hip_map_edge_segments": (C.c_int, [_vp, C.POINTER(SegmentOpts), C.POINTER(CloudPose), _vp, C.c_int, C.POINTER(SegmentCounts)]),
+    "rebvio_hip_test_edge_segments_host": (C.c_int, [C.c_float, _vp, C.c_int, C.POINTER(SegmentOpts), C.POINTER(CloudPose), _vp, C.c_int,
+                                                     C.POINTER(SegmentCounts)]),
     "rebvio_hip_map_mark_keyframe": (C.c_int, [_vp, _vp]),
     "rebvio_hip_map_keyframe_matches": (C.c_int, [_vp, C.c_int, C.POINTER(KfMatch), C.c_int, _ip]),
     "rebvio_hip_map_keyframe_snapshot": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -550,6 +574,32 @@ def edge_polylines_host(fm, keylines, opts=None, pose=None, cap_points=None, cap
     kl = np.ascontiguousarray(keylines, KEYLINE_DTYPE)
     return _polylines_call(lib().rebvio_hip_test_edge_polylines_host, (float(fm), kl.ctypes.data if len(kl) else None, len(kl)), len(kl),
                            opts, pose, cap_points, cap_lines)
+
+
+def default_segment_opts(**over) -> SegmentOpts:
+    """The library's defaults (rebvio_hip_default_segment_opts): the polyline defaults, tol 1 px, min_length 4 px, min_points 8,
+    max_rounds 16; poly takes a PolylineOpts or a dict for default_polyline_opts."""
+    o = SegmentOpts()
+    lib().rebvio_hip_default_segment_opts(C.byref(o))
+    for k, v in over.items():
+        setattr(o, k, default_polyline_opts(**v) if k == "poly" and not isinstance(v, PolylineOpts) else v)
+    return o
+
+
+def _segments_call(fn, head_args, n_hint, opts, pose, cap):
+    cs = n_hint if cap is None else cap
+    segs = np.zeros(max(cs, 0), LINE_SEGMENT_DTYPE)
+    counts = SegmentCounts()
+    _chk(fn(*head_args, opts, _cloud_pose(pose), segs.ctypes.data if len(segs) else None, cs, C.byref(counts)))
+    return segs[:min(counts.kept, cs)], counts
+
+
+def edge_segments_host(fm, keylines, opts=None, pose=None, cap=None):
+    """Map.edge_segments on the host, from a KEYLINE_DTYPE array (rebvio_hip_test_edge_segments_host). Touches no device. Returns
+    (segments LINE_SEGMENT_DTYPE, SegmentCounts)."""
+    kl = np.ascontiguousarray(keylines, KEYLINE_DTYPE)
+    return _segments_call(lib().rebvio_hip_test_edge_segments_host, (float(fm), kl.ctypes.data if len(kl) else None, len(kl)), len(kl), opts,
+                          pose, cap)
 
 
 def default_kf_pose_opts(**over) -> KfPoseOpts:
@@ -1196,6 +1246,12 @@ class Map:
         lines POLYLINE_DTYPE, n_points, n_lines); the caps (default: everything) cut the arrays, never the counts."""
         return _polylines_call(lib().rebvio_hip_map_edge_polylines, (self.h,), self.ctx.p.keylines_max, opts, pose, cap_points, cap_lines)
 
+    def edge_segments(self, opts=None, pose=None, cap=None):
+        """The map's polylines split into straight 3D segments with fitted end depths (rebvio_hip_map_edge_segments). opts: a
+        SegmentOpts or None for the defaults; pose: None (identity), a CloudPose, or (R, t, scale). Returns (segments
+        LINE_SEGMENT_DTYPE, SegmentCounts); the cap (default: everything) cuts the array, never the counts."""
+        return _segments_call(lib().rebvio_hip_map_edge_segments, (self.h,), self.ctx.p.keylines_max, opts, pose, cap)
+
     def mark_keyframe(self):
         """Makes this map the keyframe: match_id_keyframe[i] = i for every keyline (rebvio_hip_map_mark_keyframe; queued on the track
         stream, returns at once). Mark a map after it has been a pair's new map and before it serves as an old map."""
@@ -1737,11 +1793,11 @@ class Context:
         lib().rebvio_hip_profile_reset(self.h)
 
     def profile_read(self):
-        cap = 64
-        names = C.create_string_buffer(8192)
+        cap = 128
+        names = C.create_string_buffer(16384)
         avg = (C.c_double * cap)()
         calls = (C.c_int * cap)()
-        k = lib().rebvio_hip_profile_read(self.h, names, 8192, avg, calls, cap)
+        k = lib().rebvio_hip_profile_read(self.h, names, 16384, avg, calls, cap)
         ns = names.value.decode().split("\n")
         return {ns[i]: (avg[i], calls[i]) for i in range(k)}
 

@@ -570,6 +570,7 @@ struct rebvio_hip_ctx {
   scratch::Counted kff, dpr, spr;
   scratch::KfHandover kfh;
   scratch::Chains<ChainDev> ech;
+  scratch::Segments<SegDev> esg;  // the straight segments (behind ech)
   scratch::Place plc;
   // dpr_pin: the host-image entry's pinned staging frame (rows * cols * 4 bytes, on ITS first use), which the kernel reads in
   // place. dpr_queued / spr_queued: a fusion has been queued.
@@ -3599,6 +3600,106 @@ int rebvio_hip_test_edge_polylines_host(float fm, const rebvio_hip_keyline* keyl
                       refs2, cap_points, lines, cap_lines, n_points, n_lines);
   return 0;
 }
+
+}  // extern "C"
+
+namespace {
+static_assert(sizeof(rebvio_hip_line_segment) == 80 && sizeof(esg::SegPoint) == 16 && sizeof(esg::SegSpan) == 8,
+              "an 80-byte record: five 16-byte stores; a point: one load");
+static_assert(sizeof(rebvio_hip_segment_opts) == 40 && sizeof(rebvio_hip_segment_counts) == 32, "the polyline options and four words; eight ints");
+
+int check_segment_args(const char* who, const rebvio_hip_segment_opts* o, const rebvio_hip_cloud_pose* pose, const void* segs, int cap,
+                       const rebvio_hip_segment_counts* counts) {
+  if (!counts) return fail_msg((std::string(who) + ": null counts").c_str(), -3);
+  if (cap < 0 || (cap > 0 && !segs)) return fail_msg((std::string(who) + ": cap_segments records need a segs buffer (cap_segments >= 0)").c_str(), -3);
+  if (o) {
+    if (!(o->tol >= 0.0f) || !(o->min_length >= 0.0f)) return fail_msg((std::string(who) + ": tol and min_length must be >= 0").c_str(), -3);
+    if (o->min_points < 2) return fail_msg((std::string(who) + ": min_points must be >= 2").c_str(), -3);
+    if (o->max_rounds < 1 || o->max_rounds > esg::kMaxRounds) return fail_msg((std::string(who) + ": max_rounds must be in 1..32").c_str(), -3);
+    if (o->poly.min_chain_length < 1) return fail_msg((std::string(who) + ": min_chain_length must be >= 1").c_str(), -3);
+  }
+  return check_cloud_args(who, o ? &o->poly.filter : nullptr, pose);
+}
+}  // namespace
+
+extern "C" {
+
+void rebvio_hip_default_segment_opts(rebvio_hip_segment_opts* o) {
+  rebvio_hip_default_polyline_opts(&o->poly);
+  o->tol = 1.0f;
+  o->min_length = 4.0f;
+  o->min_points = 8;
+  o->max_rounds = 16;
+}
+
+int rebvio_hip_map_edge_segments(rebvio_hip_map* m, const rebvio_hip_segment_opts* opts, const rebvio_hip_cloud_pose* pose,
+                                 rebvio_hip_line_segment* segs_host, int cap_segments, rebvio_hip_segment_counts* counts) {
+  if (!m) return fail_msg("map_edge_segments: null map", -3);
+  int rc = check_segment_args("map_edge_segments", opts, pose, segs_host, cap_segments, counts);
+  if (rc) return rc;
+  const Alive alive(m);
+  if (alive.dead()) return -10;
+  rebvio_hip_ctx* c = m->ctx;
+  std::memset(counts, 0, sizeof(*counts));
+  rc = ech_begin("map_edge_segments", m);
+  if (rc) return rc;
+  RCCHK(ensure_scratch(c, c->esg, (size_t)c->P.keylines_max, (size_t)kMaxRecBlocks, (size_t)esg::kSegWords));
+  rebvio_hip_segment_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_segment_opts(&o);
+  // every point and line stays on the device: the polylines run with both caps at keylines_max
+  const CloudArgs a = cloud_args(c, &o.poly.filter, pose, -1);
+  const SegArgs sa{o.tol * o.tol, o.min_length * o.min_length, o.min_points, o.max_rounds};
+  launch_edge_chains(c->s_trk, c->K, m->d, c->ech, ech::chain_rounds(c->P.keylines_max));
+  launch_edge_polylines(c->s_trk, c->K, m->d, c->ech, a, o.poly.min_chain_length, c->P.keylines_max);
+  launch_edge_segments(c->s_trk, c->K, m->d, c->ech, c->esg, a, sa);
+  HIPCHK(hipGetLastError());
+  int w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(w, c->esg.words, sizeof(w), hipMemcpyDeviceToHost, c->s_trk));
+  rc = trk_sync(c);
+  if (rc) return rc;
+  const size_t ks = (size_t)(w[3] < cap_segments ? w[3] : cap_segments);
+  if (ks) {
+    HIPCHK(hipMemcpyAsync(segs_host, c->esg.recs, ks * sizeof(rebvio_hip_line_segment), hipMemcpyDeviceToHost, c->s_trk));
+    rc = trk_sync(c);
+    if (rc) return rc;
+  }
+  *counts = rebvio_hip_segment_counts{w[2], w[3], w[4], w[5], w[6], w[0], w[1], 0};
+  return 0;
+}
+
+int rebvio_hip_test_edge_segments_host(float fm, const rebvio_hip_keyline* keylines, int n, const rebvio_hip_segment_opts* opts,
+                                       const rebvio_hip_cloud_pose* pose, rebvio_hip_line_segment* segs, int cap_segments,
+                                       rebvio_hip_segment_counts* counts) {
+  if (n < 0 || (n > 0 && !keylines)) return fail_msg("test_edge_segments_host: negative n or null keylines", -3);
+  int rc = check_segment_args("test_edge_segments_host", opts, pose, segs, cap_segments, counts);
+  if (rc) return rc;
+  rebvio_hip_segment_opts o;
+  if (opts) o = *opts; else rebvio_hip_default_segment_opts(&o);
+  const size_t N = (size_t)n;
+  std::vector<rebvio_hip_cloud_point> pts(N);
+  std::vector<rebvio_hip_polyline> lines(N);
+  int np = 0, nl = 0;
+  rc = rebvio_hip_test_edge_polylines_host(fm, keylines, n, &o.poly, pose, pts.data(), nullptr, n, lines.data(), n, &np, &nl);
+  if (rc) return rc;
+  std::vector<esg::SegPoint> q((size_t)np);
+  for (int p = 0; p < np; ++p) {
+    const rebvio_hip_keyline& k = keylines[pts[(size_t)p].keyline];
+    q[(size_t)p] = esg::SegPoint{k.pos_img[0], k.pos_img[1], k.rho, k.sigma_rho};
+  }
+  std::vector<esg::SegSpan> span((size_t)np);
+  std::vector<int> nxt((size_t)np), line_of((size_t)np);
+  std::vector<unsigned long long> far((size_t)np);
+  float R[9], t[3];
+  for (int i = 0; i < 9; ++i) R[i] = pose ? pose->R[i] : (i % 4 == 0 ? 1.0f : 0.0f);
+  for (int i = 0; i < 3; ++i) t[i] = pose ? pose->t[i] : 0.0f;
+  esg::segments_host(fm, q.data(), np, lines.data(), nl, o, R, t, pose ? pose->scale : 1.0f, span.data(), nxt.data(), line_of.data(), far.data(),
+                     segs, cap_segments, counts);
+  return 0;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int rebvio_hip_map_upload(rebvio_hip_map* m, const rebvio_hip_keyline* keylines, int n) {
   const Alive alive(m);

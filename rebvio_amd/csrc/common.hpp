@@ -417,6 +417,28 @@ void launch_edge_chains(hipStream_t s, const KParams& p, const MapDev& m, const 
 void launch_edge_polylines(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, const CloudArgs& a, int min_chain_length,
                            int cap_lines);
 
+// Scratch of the straight segments (rebvio_hip_map_edge_segments): views into one allocation of the context. Arrays per point
+// hold ceil(kmax / 256) * 256 entries (a map has at most kmax points).
+struct SegDev {
+  void* q;                      // esg::SegPoint per point
+  void* recs;                   // rebvio_hip_line_segment per kept segment
+  void* span;                   // esg::SegSpan per point
+  unsigned long long* far[2];   // by segment start: the winner's key, one buffer per round parity
+  int* nxt;                     // by vertex: the end of the segment it begins (itself: it begins none)
+  int* line_of;                 // by point: its line
+  int* seg;                     // by kept segment: its start
+  int* blk;                     // [4][kMaxRecBlocks] workgroup counts: segments, kept, unresolved, spare
+  int* words;                   // [esg::kSegWords]
+};
+struct SegArgs {
+  float tol2, min_len2;
+  int min_points, max_rounds;
+};
+// k_seg_init, max_rounds x (k_seg_far + k_seg_split), k_seg_far, k_seg_count, k_seg_emit, k_seg_fit on stream s behind
+// launch_edge_chains + launch_edge_polylines (which ran with both caps at kmax): 2 * max_rounds + 5 launches whatever the map holds.
+void launch_edge_segments(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, const SegDev& g, const CloudArgs& a,
+                          const SegArgs& sa);
+
 // k_depth_prior on stream s (rebvio_hip_map_fuse_depth_image*): one Kalman update of (rho, sigma_rho) per keyline of m from the depth
 // image of a (depth_prior.hpp). cnt = 8 ints, cleared by the caller in front of the launch (the kernel leaves the six words of
 // rebvio_hip_depth_prior_counts there); outcome = kmax ints. ceil(kmax / 256) workgroups whatever the map holds.

@@ -9,9 +9,10 @@
 
 #include <type_traits>
 
-#include "edge_chains.hpp"  // ech::ChainNode
-#include "kf_handover.hpp"  // kfp::HandoverStage; kfp::kSums (kf_pose.hpp)
-#include "place.hpp"        // plc::kWords
+#include "edge_chains.hpp"    // ech::ChainNode
+#include "edge_segments.hpp"  // esg::SegPoint, esg::SegSpan
+#include "kf_handover.hpp"    // kfp::HandoverStage; kfp::kSums (kf_pose.hpp)
+#include "place.hpp"          // plc::kWords
 #include "rebvio_hip.h"
 
 namespace rh {
@@ -144,6 +145,27 @@ struct Chains : Layout, Dev {
     this->start_of = c.take<int>(kp);
     this->order = c.take<int>(kp);
     this->starts = c.take<int>(kp + 4);
+    this->blk = c.take<int>(4 * blocks);
+    this->words = c.take<int>(words_n);
+    return c.size();
+  }
+};
+
+// rebvio_hip_map_edge_segments: Dev = SegDev with its views (common.hpp says what each holds) laid over kp = ceil(kmax / 256) * 256
+// entries per point - the 16-byte records first (80 = 5 x 16), then the 8-byte ones, then the ints
+template <class Dev>
+struct Segments : Layout, Dev {
+  size_t lay(char* b, size_t kmax, size_t blocks, size_t words_n) {
+    const size_t kp = slots256(kmax);
+    Carve c(base = b);
+    this->q = c.take<esg::SegPoint>(kp);
+    this->recs = c.take<rebvio_hip_line_segment>(kp);
+    this->span = c.take<esg::SegSpan>(kp);
+    this->far[0] = c.take<unsigned long long>(kp);
+    this->far[1] = c.take<unsigned long long>(kp);
+    this->nxt = c.take<int>(kp);
+    this->line_of = c.take<int>(kp);
+    this->seg = c.take<int>(kp);
     this->blk = c.take<int>(4 * blocks);
     this->words = c.take<int>(words_n);
     return c.size();

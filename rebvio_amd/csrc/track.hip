@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "depth_prior.hpp"
 #include "edge_chains.hpp"
+#include "edge_segments.hpp"
 #include "glue_dev.hpp"
 #include "kf_cloud.hpp"
 #include "stereo_prior.hpp"
@@ -4116,6 +4117,193 @@ void launch_edge_polylines(hipStream_t s, const KParams& p, const MapDev& m, con
   RH_LAUNCH(k_poly_count, grid, dim3(256), 0, s, m, c, f, min_chain_length);
   RH_LAUNCH(k_poly_emit, grid, dim3(256), 0, s, p, m, c, a, min_chain_length, cap_lines);
   RH_LAUNCH(k_poly_lines, grid, dim3(256), 0, s, c, cap_lines);
+}
+
+// ---- straight segments of the polylines (rebvio_hip_map_edge_segments) ---------------------------------------------------------------
+// Breadth-first Douglas-Peucker over the polylines' points and a weighted line fit of inverse depth per kept segment; esg::*
+// (edge_segments.hpp) are the definition's per-point statements. One thread per point, ceil(kmax / 256) workgroups per launch (the
+// fit: 16 lanes per segment), the counts read on the device. No workgroup waits for another: every dependency is a kernel boundary.
+//   k_seg_init   the point (pos_img, rho, sigma_rho) next to its state: its line by bisection over the line records, the first
+//                span, nxt of a vertex = the end of the segment it begins; both far buffers' own slot cleared; workgroup 0 leaves the
+//                counts and the "split" words
+//   k_seg_far    x (max_rounds + 1): every interior point forms its key; a wave's lanes are in point order, so lanes of one segment
+//                are a run of equal `a`: a segmented maximum over the run (shuffles), then ONE 64-bit atomicMax per (wave, segment) on
+//                far[k & 1][a]. The keys are distinct: the maximum does not depend on the order it is taken in.
+//   k_seg_split  x max_rounds: the point reads its segment's winner and takes its new span; the winner stores nxt[a] = m,
+//                nxt[m] = b and words[8 + k + 1] = 1; every point clears its own slot of the OTHER far buffer for the round behind.
+//                A far / split behind a round in which nothing split returns at once: far[rounds_used & 1] holds every segment's
+//                final measure whichever pass was the last to run.
+//   k_seg_count / k_seg_emit  segment, kept and unresolved flags per segment start, their fixed-order scans, the list of kept starts
+//   k_seg_fit    one 16-lane row per kept segment (four per wave): lane j forms partial j of the six sums, the xor-1, 2, 4, 8
+//                butterfly inside the row is the definition's pairwise tree (a + b == b + a bit for bit), lane 0 stores the record
+// The only floating-point values that cross threads are the keys (a maximum) and the partials (a fixed tree).
+__device__ __forceinline__ int seg_rounds_used(const int* __restrict__ words, int max_rounds) {
+  int ru = 0;
+  for (int k = 1; k <= max_rounds; ++k) ru += words[8 + k];
+  return ru;
+}
+
+__global__ __launch_bounds__(256) void k_seg_init(MapDev m, ChainDev c, SegDev g) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int np = c.words[2], nl = c.words[3];
+  if (blockIdx.x == 0 && (int)threadIdx.x < esg::kSegWords)
+    g.words[threadIdx.x] = threadIdx.x == 0 ? np : (threadIdx.x == 1 ? nl : (threadIdx.x == 8 ? 1 : 0));
+  if (p >= np || nl <= 0) return;
+  int lo = 0, hi = nl - 1;  // the last line that begins at or in front of p
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (c.lines[mid].first_point <= p) lo = mid; else hi = mid - 1;
+  }
+  const rebvio_hip_polyline ln = c.lines[lo];
+  const int first = ln.first_point, last = first + ln.points - 1;
+  const float4* rec = reinterpret_cast<const float4*>(c.points) + 2 * (size_t)p;
+  const float4 r0 = rec[0], r1 = rec[1];
+  const float2 pi = m.pos_img[__float_as_int(r1.z)];
+  reinterpret_cast<esg::SegPoint*>(g.q)[p] = esg::SegPoint{pi.x, pi.y, r0.w, r1.x};
+  const bool vertex = p <= first || p >= last;
+  reinterpret_cast<esg::SegSpan*>(g.span)[p] = vertex ? esg::SegSpan{p, p} : esg::SegSpan{first, last};
+  g.nxt[p] = (p == first && last > first) ? last : p;
+  g.line_of[p] = lo;
+  g.far[0][p] = 0ull;
+  g.far[1][p] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_seg_far(SegDev g, int k) {
+  if (g.words[8 + k] == 0) return;  // nothing split in the round in front: the measures stand
+  const int p = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  const int np = g.words[0];
+  const esg::SegPoint* q = reinterpret_cast<const esg::SegPoint*>(g.q);
+  int id = 0x7FFFFFFF;  // a vertex joins the run of the segment it begins with key 0
+  unsigned long long key = 0ull;
+  if (p < np) {
+    const esg::SegSpan s = reinterpret_cast<const esg::SegSpan*>(g.span)[p];
+    id = s.a;
+    if (s.a != p) key = esg::seg_key(esg::seg_dev2(q[s.a], q[s.b], q[p]), p);
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {  // the maximum of the run up to and with this lane (ids ascend along the wave)
+    const int id_o = __shfl_up(id, o);
+    const unsigned long long key_o = __shfl_up(key, o);
+    if (lane >= o && id_o == id && key_o > key) key = key_o;
+  }
+  const int id_n = __shfl_down(id, 1);
+  if ((lane == 63 || id_n != id) && key != 0ull) atomicMax(&g.far[k & 1][id], key);
+}
+
+__global__ __launch_bounds__(256) void k_seg_split(SegDev g, int k, float tol2) {
+  if (g.words[8 + k] == 0) return;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int np = g.words[0];
+  bool won = false;
+  if (p < np) {
+    g.far[(k + 1) & 1][p] = 0ull;
+    esg::SegSpan* span = reinterpret_cast<esg::SegSpan*>(g.span);
+    const esg::SegSpan s = span[p];
+    if (s.a != p) {
+      const esg::SegSpan t = esg::seg_split(s, p, g.far[k & 1][s.a], tol2, &won);
+      if (t.a != s.a || t.b != s.b) span[p] = t;
+      if (won) {
+        g.nxt[s.a] = p;
+        g.nxt[p] = s.b;
+      }
+    }
+  }
+  if (__ballot(won) != 0ull && (threadIdx.x & 63) == 0) g.words[8 + k + 1] = 1;
+}
+
+// segment / kept / unresolved of point p < np
+__device__ __forceinline__ void seg_flags(const SegDev& g, const SegArgs& sa, const unsigned long long* __restrict__ far, int p, int* is_seg,
+                                          int* kept, int* unres) {
+  const esg::SegPoint* q = reinterpret_cast<const esg::SegPoint*>(g.q);
+  const int b = g.nxt[p];
+  *is_seg = reinterpret_cast<const esg::SegSpan*>(g.span)[p].a == p && b != p;
+  *kept = *unres = 0;
+  if (!*is_seg) return;
+  *unres = esg::key_splits(far[p], sa.tol2);
+  *kept = esg::seg_kept(b - p + 1, esg::seg_l2(q[p], q[b]), sa.min_points, sa.min_len2);
+}
+
+__global__ __launch_bounds__(256) void k_seg_count(SegDev g, SegArgs sa) {
+  __shared__ int sh[12];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int np = g.words[0];
+  int is_seg = 0, kept = 0, unres = 0;
+  if (p < np) seg_flags(g, sa, g.far[seg_rounds_used(g.words, sa.max_rounds) & 1], p, &is_seg, &kept, &unres);
+  chain_block_sum(is_seg, sh, g.blk);
+  chain_block_sum(kept, sh + 4, g.blk + kMaxRecBlocks);
+  chain_block_sum(unres, sh + 8, g.blk + 2 * kMaxRecBlocks);
+}
+
+__global__ __launch_bounds__(256) void k_seg_emit(SegDev g, SegArgs sa) {
+  __shared__ int sh[28];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int np = g.words[0];
+  const int ru = seg_rounds_used(g.words, sa.max_rounds);
+  int is_seg = 0, kept = 0, unres = 0;
+  if (p < np) seg_flags(g, sa, g.far[ru & 1], p, &is_seg, &kept, &unres);
+  const int2 alls = chain_blk_sums(g.blk, sh);
+  const int2 kepts = chain_blk_sums(g.blk + kMaxRecBlocks, sh + 8);
+  const int2 unress = chain_blk_sums(g.blk + 2 * kMaxRecBlocks, sh + 16);
+  const int idx = kepts.x + chain_block_scan(kept, sh + 24);
+  if (kept) g.seg[idx] = p;  // (idx < kept segments < np)
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    g.words[2] = alls.y;
+    g.words[3] = kepts.y;
+    g.words[4] = 0;  // depth valid: k_seg_fit counts
+    g.words[5] = unress.y;
+    g.words[6] = ru;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_seg_fit(KParams p, SegDev g, CloudArgs a, SegArgs sa) {
+  const int row = threadIdx.x >> 4, j = threadIdx.x & (esg::kLanes - 1);
+  const int n_kept = g.words[3];
+  const esg::SegPoint* q = reinterpret_cast<const esg::SegPoint*>(g.q);
+  const unsigned long long* far = g.far[g.words[6] & 1];
+  for (int i = blockIdx.x * 16 + row; i < n_kept; i += gridDim.x * 16) {
+    const int a0 = g.seg[i], b = g.nxt[a0], points = b - a0 + 1;
+    const esg::SegPoint qa = q[a0], qb = q[b];
+    const float l2 = esg::seg_l2(qa, qb);
+    esg::FitSums f = esg::fit_zero();
+    for (int mbr = j; mbr < points; mbr += esg::kLanes) esg::fit_add(&f, qa, qb, l2, q[a0 + mbr]);
+#pragma unroll
+    for (int w = 1; w < esg::kLanes; w <<= 1) {
+      esg::FitSums o;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) o.s[k] = __shfl_xor(f.s[k], w);
+      f = esg::fit_pair(f, o);
+    }
+    if (j != 0) continue;
+    const unsigned long long key = far[a0];
+    const rebvio_hip_line_segment rec = esg::fit_finish(f, qa, qb, esg::key_dev2(key), a0, points, g.line_of[a0], esg::key_splits(key, sa.tol2),
+                                                        p.fm, a.R, a.t, a.scale, a.rho_min, a.rho_max);
+    // five 16-byte stores per record
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) volatile v4f* GRec;
+    GRec out = (GRec)(reinterpret_cast<float4*>(g.recs) + 5 * (size_t)i);
+    out[0] = v4f{rec.xyz0[0], rec.xyz0[1], rec.xyz0[2], rec.xyz1[0]};
+    out[1] = v4f{rec.xyz1[1], rec.xyz1[2], rec.uv0[0], rec.uv0[1]};
+    out[2] = v4f{rec.uv1[0], rec.uv1[1], rec.rho0, rec.rho1};
+    out[3] = v4f{rec.sigma_rho0, rec.sigma_rho1, rec.max_dev2, rec.chi2};
+    out[4] = v4f{__int_as_float(rec.first_point), __int_as_float(rec.points), __int_as_float(rec.line), __int_as_float(rec.flags)};
+    if (rec.flags & 1) atomicAdd(&g.words[4], 1);
+  }
+}
+
+void launch_edge_segments(hipStream_t s, const KParams& p, const MapDev& m, const ChainDev& c, const SegDev& g, const CloudArgs& a,
+                          const SegArgs& sa) {
+  const dim3 grid(div_up(p.kmax, 256));
+  RH_LAUNCH(k_seg_init, grid, dim3(256), 0, s, m, c, g);
+  for (int k = 0; k < sa.max_rounds; ++k) {
+    RH_LAUNCH(k_seg_far, grid, dim3(256), 0, s, g, k);
+    RH_LAUNCH(k_seg_split, grid, dim3(256), 0, s, g, k, sa.tol2);
+  }
+  RH_LAUNCH(k_seg_far, grid, dim3(256), 0, s, g, sa.max_rounds);
+  RH_LAUNCH(k_seg_count, grid, dim3(256), 0, s, g, sa);
+  RH_LAUNCH(k_seg_emit, grid, dim3(256), 0, s, g, sa);
+  // the fit: 16 rows per workgroup, i.e. one row per 16 points at once (kept segments of min_points >= 2 number fewer than the
+  // points; the default min_points 8 leaves at most one per 7); the stride loop covers what is left
+  RH_LAUNCH(k_seg_fit, grid, dim3(256), 0, s, p, g, a, sa);
 }
 
 // ---- depth prior from a registered depth image (rebvio_hip_map_fuse_depth_image*) --------------------------------------------------

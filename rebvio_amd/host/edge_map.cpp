@@ -227,6 +227,25 @@ EdgeMap::EdgePolylines EdgeMap::edgePolylines(const rebvio::types::PolylineOpts&
   return out;
 }
 
+EdgeMap::EdgeSegments EdgeMap::edgeSegments(const rebvio::types::SegmentOpts& opts, const rebvio::types::CloudPose& pose) {
+  static_assert(sizeof(types::SegmentOpts) == sizeof(rebvio_hip_segment_opts) && sizeof(types::LineSegment) == sizeof(rebvio_hip_line_segment) &&
+                    sizeof(types::SegmentCounts) == sizeof(rebvio_hip_segment_counts) &&
+                    offsetof(types::SegmentOpts, max_rounds) == offsetof(rebvio_hip_segment_opts, max_rounds) &&
+                    offsetof(types::LineSegment, rho0) == offsetof(rebvio_hip_line_segment, rho0) &&
+                    offsetof(types::LineSegment, flags) == offsetof(rebvio_hip_line_segment, flags) &&
+                    offsetof(types::SegmentCounts, lines) == offsetof(rebvio_hip_segment_counts, lines), "segment types mirror the C-ABI's");
+  EdgeSegments out;
+  const size_t n = (size_t)size();
+  out.segments.resize(n);  // (a map of n keylines has fewer than n segments: nothing is cut)
+  check("rebvio_hip_map_edge_segments",
+        rebvio_hip_map_edge_segments(handle_, reinterpret_cast<const rebvio_hip_segment_opts*>(&opts),
+                                     reinterpret_cast<const rebvio_hip_cloud_pose*>(&pose),
+                                     reinterpret_cast<rebvio_hip_line_segment*>(out.segments.data()), (int)n,
+                                     reinterpret_cast<rebvio_hip_segment_counts*>(&out.counts)));
+  out.segments.resize((size_t)out.counts.kept);
+  return out;
+}
+
 void EdgeMap::markKeyframe() {
   check("rebvio_hip_map_mark_keyframe", rebvio_hip_map_mark_keyframe(ctx_, handle_));
   invalidateMirror();

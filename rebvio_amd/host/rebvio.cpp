@@ -210,6 +210,10 @@ void Rebvio::registerEdgePolylineCallback(std::function<void(const rebvio::types
   edge_polyline_callbacks_.push_back({cb, opts});
 }
 
+void Rebvio::registerEdgeSegmentCallback(std::function<void(const rebvio::types::EdgeSegments&)> cb, rebvio::types::SegmentOpts opts) {
+  edge_segment_callbacks_.push_back({cb, opts});
+}
+
 void Rebvio::registerPointCloudCallback(std::function<void(const rebvio::types::PointCloud&)> cb, rebvio::types::CloudFilter filter) {
   point_cloud_callbacks_.push_back({cb, filter});
 }
@@ -452,6 +456,8 @@ void Rebvio::stateEstimationProcess() {
     // edge-polyline callbacks: the new map's polylines, one extraction per callback, with the pose they were extracted at
     std::vector<rebvio::EdgeMap::EdgePolylines> polylines;
     types::CloudPose polyline_pose;
+    // edge-segment callbacks: the same for the new map's straight segments (at polyline_pose)
+    std::vector<rebvio::EdgeMap::EdgeSegments> segments;
     // depth images: a fusion into the new map was queued behind the second half; its counts (fetched where the pair's counters are)
     bool have_depth = false;
     types::DepthPriorCounts depth_counts;
@@ -598,6 +604,12 @@ void Rebvio::stateEstimationProcess() {
       edge_polyline_callbacks_[i].cb(ep);
     }
     pending.polylines.clear();
+    for (size_t i = 0; i < pending.segments.size(); ++i) {
+      const rebvio::EdgeMap::EdgeSegments& g = pending.segments[i];
+      const types::EdgeSegments es{pending.odometry.ts_us, pending.polyline_pose, g.segments.data(), g.segments.size(), g.counts};
+      edge_segment_callbacks_[i].cb(es);
+    }
+    pending.segments.clear();
     pending.old_map.reset();
     pending.new_map.reset();
     ++num_published_;
@@ -822,7 +834,7 @@ void Rebvio::stateEstimationProcess() {
     const bool want_cloud = !point_cloud_callbacks_.empty();
     const bool want_kf_pose = !keyframe_pose_callbacks_.empty();
     const bool want_kf_cloud = !keyframe_cloud_callbacks_.empty();
-    const bool want_polylines = !edge_polyline_callbacks_.empty();
+    const bool want_polylines = !edge_polyline_callbacks_.empty() || !edge_segment_callbacks_.empty();  // (segments: lines of the same frame)
     std::vector<rebvio_hip_cloud*> clouds, kf_clouds;
     types::CloudPose cloud_pose, kf_cloud_pose;
     uint64_t kf_cloud_ts = 0;
@@ -936,12 +948,14 @@ void Rebvio::stateEstimationProcess() {
     }
     // edge-polyline callbacks: the new map's polylines in this pair's frame, behind this pair's second half (the call waits for it)
     std::vector<rebvio::EdgeMap::EdgePolylines> polylines;
+    std::vector<rebvio::EdgeMap::EdgeSegments> segments;
     types::CloudPose polyline_pose;
     if (want_polylines) {
       store3(R_global, polyline_pose.R);
       for (int i = 0; i < 3; ++i) polyline_pose.t[i] = Pos[i];
       polyline_pose.scale = K;
       for (const EdgePolylineCallback& epc : edge_polyline_callbacks_) polylines.push_back(new_edge_map->edgePolylines(epc.opts, polyline_pose));
+      for (const EdgeSegmentCallback& esc : edge_segment_callbacks_) segments.push_back(new_edge_map->edgeSegments(esc.opts, polyline_pose));
     }
     // keyframe-pose callbacks: the new map against the keyframe, behind this pair's second half (the call waits for it)
     bool have_kf_pose = false;
@@ -1031,6 +1045,7 @@ void Rebvio::stateEstimationProcess() {
     pending.kf_window = std::move(kf_window_poses);
     pending.polylines = std::move(polylines);
     pending.polyline_pose = polyline_pose;
+    pending.segments = std::move(segments);
     pending.have_depth = have_depth;
     pending.have_stereo = have_stereo;
     pending.have_place = have_place;

@@ -13,6 +13,9 @@
 // tools/cloud_rate.py).
 // --polylines PREFIX [--min-chain N]: every published record's edge polylines (Rebvio::registerEdgePolylineCallback, default filter,
 // chains of at least N members, default 8) as PREFIX<ts_us>.ply: the cloud's vertex element plus `element edge` (io::writePolylinesPly).
+// --segments PREFIX [--seg-tol T]: every published record's straight segments (Rebvio::registerEdgeSegmentCallback, the default
+// options with --min-chain's N and a split tolerance of T px, 0..1000, default 1) as PREFIX<ts_us>.ply: two vertices and one edge per
+// depth-valid segment (io::writeSegmentsPly). The odometry file is what it is without it.
 // --kf-pose FILE [--kf-every N]: the pose of every tracked map relative to the keyframe (Rebvio::registerKeyframePoseCallback), one
 // line per record that has one: ts_us status used R (9 values, row-major) t (3 values). A keyframe is requested before the first
 // frame and again after every N-th record (default 10).
@@ -65,6 +68,9 @@ int main(int argc, char** argv) {
   int place_exclude = 10;
   double depth_unit = 0.001, baseline = 0.0;
   int min_chain = 8;
+  std::string segments_prefix;
+  double seg_tol = 1.0;
+  bool have_seg_tol = false;
   int kf_window = 0;
   bool kf_align = false;
   int kf_every = 10;
@@ -76,7 +82,7 @@ int main(int argc, char** argv) {
   int ncam = 0, kref = 0, kmax = 0, min_matches = -1;
   auto usage = [&]() {
     std::fprintf(stderr, "usage: %s (--asl mav0 [--colour] | --raw frames.u8 --size W H [--imu imu.bin]) [--euroc | --camera fm cx cy [k1 k2 p1 p2 k3]] "
-                 "[--mask mask.png] [--depth FILE [--depth-unit U]] [--right FILE|DIR --baseline B] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] [--places FILE [--place-exclude N]] --out file\n", argv[0]);
+                 "[--mask mask.png] [--depth FILE [--depth-unit U]] [--right FILE|DIR --baseline B] [--cloud PREFIX | --cloud-dry] [--polylines PREFIX [--min-chain N]] [--segments PREFIX [--seg-tol T]] [(--kf-pose | --kf-align) FILE [--kf-every N]] [--kf-fuse FILE] [--kf-handover FILE] [--kf-cloud PREFIX] [--places FILE [--place-exclude N]] --out file\n", argv[0]);
     return 2;
   };
   for (int i = 1; i < argc; ++i) {
@@ -113,6 +119,18 @@ int main(int argc, char** argv) {
       polylines_prefix = next();
     }
     else if (a == "--min-chain") min_chain = std::atoi(next());
+    else if (a == "--segments") {
+      if (!segments_prefix.empty()) return usage();
+      segments_prefix = next();
+    }
+    else if (a == "--seg-tol") {
+      if (have_seg_tol) return usage();
+      have_seg_tol = true;
+      const char* text = next();
+      char* end = nullptr;
+      seg_tol = std::strtod(text, &end);
+      if (end == text || *end != 0) return usage();  // not a number
+    }
     else if (a == "--kf-pose" || a == "--kf-align") {
       if (!kf_pose_path.empty()) return usage();  // one of the two, once
       kf_align = a == "--kf-align";
@@ -151,6 +169,7 @@ int main(int argc, char** argv) {
   }
   if ((asl.empty() == raw.empty()) || out.empty() || kf_every < 1 || min_chain < 1 || !(depth_unit > 0.0)) return usage();
   if (right_path.empty() != !(baseline > 0.0)) return usage();  // --right and --baseline come together
+  if (!(seg_tol >= 0.0 && seg_tol <= 1000.0) || (have_seg_tol && segments_prefix.empty())) return usage();  // --seg-tol: 0..1000 px, with --segments
   if (place_exclude < 0) return usage();
   if (!kf_window_path.empty() && (!kf_align || kf_pose_path.empty() || kf_window < 1 || kf_window > 15)) return usage();  // needs --kf-align FILE
   if (!kf_handover_path.empty() && (!kf_align || kf_pose_path.empty())) return usage();  // needs --kf-align FILE
@@ -305,6 +324,18 @@ int main(int argc, char** argv) {
         n_line_points += ep.size;
       }, po);
     }
+    size_t n_segment_files = 0, n_segments = 0, n_segments_valid = 0;
+    if (!segments_prefix.empty()) {
+      rebvio::types::SegmentOpts so;
+      so.poly.min_chain_length = min_chain;
+      so.tol = (float)seg_tol;
+      rebvio.registerEdgeSegmentCallback([&](const rebvio::types::EdgeSegments& es) {
+        rebvio::io::writeSegmentsPly(segments_prefix + std::to_string(es.ts_us) + ".ply", es.segments, es.size, es.ts_us);
+        ++n_segment_files;
+        n_segments += es.size;
+        n_segments_valid += (size_t)es.counts.depth_valid;
+      }, so);
+    }
     std::FILE* depth_file = nullptr;
     size_t n_depth = 0, n_depth_fused = 0, n_depth_handed = 0;
     std::vector<uint16_t> depth_frame;
@@ -382,6 +413,7 @@ int main(int argc, char** argv) {
     if (!cloud_prefix.empty() || cloud_dry) std::fprintf(stderr, "clouds=%zu points=%zu\n", n_clouds, n_points);
     if (!kf_cloud_prefix.empty()) std::fprintf(stderr, "kf_clouds=%zu kf_points=%zu\n", n_kf_clouds, n_kf_points);
     if (!polylines_prefix.empty()) std::fprintf(stderr, "polyline_files=%zu lines=%zu line_points=%zu\n", n_polyline_files, n_lines, n_line_points);
+    if (!segments_prefix.empty()) std::fprintf(stderr, "segment_files=%zu segments=%zu segments_valid=%zu\n", n_segment_files, n_segments, n_segments_valid);
     if (kf_pose_file) std::fclose(kf_pose_file);
     if (want_kf) std::fprintf(stderr, "kf_poses=%zu\n", n_poses);
     if (kf_window_file) {

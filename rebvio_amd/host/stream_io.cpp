@@ -316,25 +316,21 @@ uint32_t get_le32(const std::vector<unsigned char>& body, size_t at) {
 }
 }  // namespace
 
-void writePolylinesPly(const std::string& path, const rebvio::types::CloudPoint* points, size_t n, const rebvio::types::Polyline* lines,
-                       size_t n_lines, uint64_t ts_us) {
-  std::vector<PlyEdge> edges;
-  for (size_t l = 0; l < n_lines; ++l) {
-    const rebvio::types::Polyline& ln = lines[l];
-    if (ln.first_point < 0 || ln.points < 1 || (size_t)ln.first_point >= n) continue;
-    const size_t first = (size_t)ln.first_point, whole = first + (size_t)ln.points, end = std::min(whole, n);
-    for (size_t k = first; k + 1 < end; ++k) edges.push_back(PlyEdge{(int)k, (int)k + 1});
-    if ((ln.flags & 1) && end == whole && ln.points >= 2) edges.push_back(PlyEdge{(int)end - 1, (int)first});
-  }
+namespace {
+// n vertices and the edges as a PLY file; kind = the word of the comment line ("polylines", "segments"); vertex(i) = the i-th
+// vertex, read where it lies: nothing is copied in front of the file's body
+template <class VertexOf>
+void write_edges_ply(const std::string& path, const char* kind, size_t n, VertexOf vertex, const std::vector<PlyEdge>& edges, uint64_t ts_us) {
   std::FILE* f = std::fopen(path.c_str(), "wb");
   if (!f) bad("cannot create " + path);
-  std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment rebvio polylines ts_us %llu\nelement vertex %zu\n"
+  std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment rebvio %s ts_us %llu\nelement vertex %zu\n"
                "property float x\nproperty float y\nproperty float z\nproperty float intensity\nelement edge %zu\n"
                "property int vertex1\nproperty int vertex2\nend_header\n",
-               (unsigned long long)ts_us, n, edges.size());
+               kind, (unsigned long long)ts_us, n, edges.size());
   std::vector<unsigned char> body(n * 16 + edges.size() * 8);
   for (size_t i = 0; i < n; ++i) {
-    const float v[4] = {points[i].xyz[0], points[i].xyz[1], points[i].xyz[2], points[i].gradient_norm};
+    const PlyVertex pv = vertex(i);
+    const float v[4] = {pv.x, pv.y, pv.z, pv.intensity};
     for (int k = 0; k < 4; ++k) {
       uint32_t w;
       std::memcpy(&w, &v[k], 4);
@@ -348,8 +344,47 @@ void writePolylinesPly(const std::string& path, const rebvio::types::CloudPoint*
   const bool ok = body.empty() || std::fwrite(body.data(), 1, body.size(), f) == body.size();
   if (std::fclose(f) != 0 || !ok) bad("cannot write " + path);
 }
+std::vector<PlyVertex> read_edges_ply(const std::string& path, const char* kind, std::vector<PlyEdge>* edges, uint64_t* ts_us);
+}  // namespace
+
+void writePolylinesPly(const std::string& path, const rebvio::types::CloudPoint* points, size_t n, const rebvio::types::Polyline* lines,
+                       size_t n_lines, uint64_t ts_us) {
+  std::vector<PlyEdge> edges;
+  for (size_t l = 0; l < n_lines; ++l) {
+    const rebvio::types::Polyline& ln = lines[l];
+    if (ln.first_point < 0 || ln.points < 1 || (size_t)ln.first_point >= n) continue;
+    const size_t first = (size_t)ln.first_point, whole = first + (size_t)ln.points, end = std::min(whole, n);
+    for (size_t k = first; k + 1 < end; ++k) edges.push_back(PlyEdge{(int)k, (int)k + 1});
+    if ((ln.flags & 1) && end == whole && ln.points >= 2) edges.push_back(PlyEdge{(int)end - 1, (int)first});
+  }
+  write_edges_ply(path, "polylines", n,
+                  [points](size_t i) { return PlyVertex{points[i].xyz[0], points[i].xyz[1], points[i].xyz[2], points[i].gradient_norm}; }, edges, ts_us);
+}
 
 std::vector<PlyVertex> readPolylinesPly(const std::string& path, std::vector<PlyEdge>* edges, uint64_t* ts_us) {
+  return read_edges_ply(path, "polylines", edges, ts_us);
+}
+
+void writeSegmentsPly(const std::string& path, const rebvio::types::LineSegment* segments, size_t n, uint64_t ts_us) {
+  std::vector<PlyVertex> vertices;
+  std::vector<PlyEdge> edges;
+  for (size_t i = 0; i < n; ++i) {
+    const rebvio::types::LineSegment& s = segments[i];
+    if (!(s.flags & 1)) continue;
+    const int at = (int)vertices.size();
+    vertices.push_back(PlyVertex{s.xyz0[0], s.xyz0[1], s.xyz0[2], s.sigma_rho0});
+    vertices.push_back(PlyVertex{s.xyz1[0], s.xyz1[1], s.xyz1[2], s.sigma_rho1});
+    edges.push_back(PlyEdge{at, at + 1});
+  }
+  write_edges_ply(path, "segments", vertices.size(), [&vertices](size_t i) { return vertices[i]; }, edges, ts_us);
+}
+
+std::vector<PlyVertex> readSegmentsPly(const std::string& path, std::vector<PlyEdge>* edges, uint64_t* ts_us) {
+  return read_edges_ply(path, "segments", edges, ts_us);
+}
+
+namespace {
+std::vector<PlyVertex> read_edges_ply(const std::string& path, const char* kind, std::vector<PlyEdge>* edges, uint64_t* ts_us) {
   std::FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) bad("cannot open " + path);
   std::vector<std::string> lines;
@@ -366,14 +401,14 @@ std::vector<PlyVertex> readPolylinesPly(const std::string& path, std::vector<Ply
   }
   unsigned long long ts = 0, n = 0, m = 0;
   const bool header_ok = lines.size() == 12 && lines[0] == "ply" && lines[1] == "format binary_little_endian 1.0" &&
-                         std::sscanf(lines[2].c_str(), "comment rebvio polylines ts_us %llu", &ts) == 1 &&
+                         std::sscanf(lines[2].c_str(), (std::string("comment rebvio ") + kind + " ts_us %llu").c_str(), &ts) == 1 &&
                          std::sscanf(lines[3].c_str(), "element vertex %llu", &n) == 1 && lines[4] == "property float x" &&
                          lines[5] == "property float y" && lines[6] == "property float z" && lines[7] == "property float intensity" &&
                          std::sscanf(lines[8].c_str(), "element edge %llu", &m) == 1 && lines[9] == "property int vertex1" &&
                          lines[10] == "property int vertex2" && lines[11] == "end_header" && n <= (1ull << 31) && m <= (1ull << 31);
   if (!header_ok) {
     std::fclose(f);
-    bad(path + ": not a polyline PLY file of writePolylinesPly");
+    bad(path + (std::string(kind) == "polylines" ? ": not a polyline PLY file of writePolylinesPly" : ": not a segment PLY file of writeSegmentsPly"));
   }
   std::vector<unsigned char> body((size_t)n * 16 + (size_t)m * 8);
   const bool ok = (body.empty() || std::fread(body.data(), 1, body.size(), f) == body.size()) && std::fgetc(f) == EOF;
@@ -398,6 +433,7 @@ std::vector<PlyVertex> readPolylinesPly(const std::string& path, std::vector<Ply
   if (ts_us) *ts_us = ts;
   return out;
 }
+}  // namespace
 
 size_t replay(StreamSource& src, const std::function<void(rebvio::types::Image&&)>& image_cb,
               const std::function<void(rebvio::types::Imu&&)>& imu_cb, size_t first, size_t count) {
